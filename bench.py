@@ -29,6 +29,13 @@ Prints ONE JSON line on rank 0 (contract in the round prompt) carrying, next to 
                (sgp_logpdf / sgp_elbo: uploads X, y; workspace from the context's cache)
   cpu_baseline the NumPy/SciPy/OpenBLAS oracle restatement -- NOT Julia -- timed on this host's
                cores on a bounded sample.
+
+--dump-outputs DIR writes, after the timed steps, what the timed entry point returned in the last of them as
+DIR/<name>.npy (fp64, under 64 MB in all; the inputs are seeded, so two builds can be compared file by file):
+  logpdf / elbo     the value(s) the call returns (rank 0)
+  factor_diag       sgp_dev_logpdf only (the default 1-GPU line): the diagonal of the Cholesky factor L left in d_A
+  factor_sample     ... 2^21 entries L[i, j], N > i >= j, at positions drawn from default_rng(DUMP_SEED), sorted by (j, i)
+  solved_row        ... the bordered row of d_A: (L^-1 (y - m))'
 """
 from __future__ import annotations
 
@@ -50,6 +57,9 @@ import bench_configs as bc  # noqa: E402
 PEAK_FP64_MFMA_TFLOPS = 78.6   # MI355X datasheet FP64 matrix rate; measured
                                # instruction ceilings are in DESIGN.md section 5
 PEAK_HBM_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_FACTOR_SAMPLE = 1 << 21
+DUMP_SEED = 20240611
 
 
 def cpu_baseline(name, n_sample):
@@ -127,6 +137,38 @@ def lookup_traffic(config, schedule):
     return None
 
 
+def factor_sample_positions(N, k=DUMP_FACTOR_SAMPLE, seed=DUMP_SEED):
+    """(rows i, columns j) of the factor entries --dump-outputs keeps: k draws of N > i >= j >= 0 (with replacement),
+    sorted by column, then row -- the same positions for the same N whatever the build."""
+    rng = np.random.default_rng(seed)
+    a, b = rng.integers(0, N, k), rng.integers(0, N, k)
+    i, j = np.maximum(a, b), np.minimum(a, b)
+    order = np.lexsort((i, j))
+    return i[order], j[order]
+
+
+def factor_outputs(A, N, n_pad, m_tot):
+    """The parts of sgp_dev_logpdf's d_A (m_tot x n_pad, column-major, ld = m_tot) that --dump-outputs writes: the
+    diagonal of L, a seeded sample of its lower triangle and the solved bordered row n_pad."""
+    import torch
+    i, j = factor_sample_positions(N)
+    cols = np.arange(N, dtype=np.int64)
+    pick = {"factor_diag": cols * m_tot + cols, "factor_sample": j * m_tot + i, "solved_row": cols * m_tot + n_pad}
+    assert A.numel() == n_pad * m_tot and max(int(p.max()) for p in pick.values()) < A.numel()
+    return {name: A[torch.from_numpy(lin).to(A.device)].cpu().numpy() for name, lin in pick.items()}
+
+
+def write_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise SystemExit(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def resolve_devices(gpus, devices_arg, device_count, world):
     """Which GPUs an in-process (WORLD_SIZE unset) run uses: `--devices a,b,..` verbatim (a device may repeat: several
     ranks on one GPU, the 1-GPU test hook), else 0 .. gpus-1.  Raises SystemExit -- never falls back to fewer GPUs."""
@@ -173,7 +215,11 @@ def main():
                          "16384 size sweep) that ride in the same JSON line")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"],
                     help="f32: the fp32 instantiation (sgp_logpdf_f32, host-buffer entry point; 1 GPU, dense configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed entry point returned in the last one as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # The contract is ONE JSON line on stdout.  Native libraries may write there too (RCCL prints a
     # version banner on rank 0): route file descriptor 1 to stderr for the whole run and keep the real
@@ -270,6 +316,7 @@ def main():
 
     timings = np.zeros(8)
     host_step = None
+    dev_factor = None       # (d_A, n_pad, m_tot) of the device-resident entry point: the factor it leaves is an output
     if is_elbo:
         # the ELBO has no device-resident entry point: the timed step is the host-buffer C-ABI call
         # itself (X, Z, y uploaded every step; everything N x M stays on the device)
@@ -308,6 +355,7 @@ def main():
         npad, mtot = C.c_int64(), C.c_int64()
         lib.sgp_geometry(N, 1, C.byref(npad), C.byref(mtot))
         A = torch.empty(npad.value * mtot.value, dtype=torch.float64, device="cuda")
+        dev_factor = (A, npad.value, mtot.value)
         dY = torch.from_numpy(y).cuda()
         out = np.zeros(1)
         nz = np.array([sigma2])
@@ -349,6 +397,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # before the extras below: they run d_A through further factorisations
+        outputs = {"elbo" if is_elbo else "logpdf": np.array([val], dtype=np.float64)}
+        if dev_factor is not None:
+            outputs.update(factor_outputs(dev_factor[0], N, dev_factor[1], dev_factor[2]))
+        write_outputs(args.dump_outputs, outputs)
 
     # ---- untimed extras on 1 GPU: instrumented step (stage split + per-launch GEMM timing), host API
     roofline = stages = host_api = None
