@@ -14,6 +14,8 @@ using Stheno: GPPP, SthenoAbstractGP, AtomicGP, DerivedGP, BlockData, GPPPInput,
 import AbstractGPs: logpdf, rand, posterior, elbo, FiniteGP, VFE
 
 const LIB = get(ENV, "STHENOMI_LIB", "libsthenomi.so")
+# include/sthenomi_batch.h (sgp_logpdf_grad_batch): a library of its own next to the product library, linked against it
+const LIB_BATCH = get(ENV, "STHENOMI_BATCH_LIB", joinpath(dirname(LIB), "libsthenomi_batch.so"))
 const SthenoFGP = FiniteGP{<:Union{GPPP,SthenoAbstractGP}}
 
 # ---- C structs (include/sthenomi.h) --------------------------------------------------------
@@ -332,6 +334,55 @@ function logpdf_and_gradient(fx::SthenoFGP, y::AbstractVector{<:Real})
          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
         ctx(), sp.c, m, kind, nz, yd, lp, gy, gm, gn, gc, gs))
     return (logpdf = lp[1], y = gy, mean = gm, noise = gn, coef = gc, inscale = gs)
+end
+
+# logpdf and its gradient for several INDEPENDENT models in one call (sgp_logpdf_grad_batch): one step of B hyper-parameter
+# chains at once (restarts, folds, candidates).  Every member's result is bit-equal to its own `logpdf_and_gradient`; members
+# of one padded size with scalar / diagonal Σy are factored as one task pool of the dataflow kernel and their C⁻¹ computed
+# by one launch.  A member that is not positive definite gives logpdf = NaN, empty gradients and its LAPACK info in the
+# second result instead of throwing.
+function logpdf_and_gradient_batch(fxs::AbstractVector{<:SthenoFGP}, ys::AbstractVector{<:AbstractVector{<:Real}})
+    length(fxs) == length(ys) || throw(DimensionMismatch("logpdf_and_gradient_batch: one y per model"))
+    B = length(fxs)
+    ms = [collect(Float64, mean(fx.f, fx.x)) for fx in fxs]
+    for (fx, y, m) in zip(fxs, ys, ms)        # checked here: the library reads length(fx) values behind every pointer
+        length(y) == length(fx) || throw(DimensionMismatch("length(y) != length(fx)"))
+        length(m) == length(fx) || throw(DimensionMismatch("length(mean(fx)) != length(fx)"))
+    end
+    failed(info) = (logpdf = NaN, y = Float64[], mean = Float64[], noise = Float64[], coef = Float64[], inscale = Float64[])
+    kinds = [noise_args(fx.Σy)[1] for fx in fxs]
+    if B == 0 || !allequal(kinds) || first(kinds) == 2        # mixed or dense noise kinds: member by member
+        res = []; infos = Cint[]
+        for (fx, y) in zip(fxs, ys)
+            try
+                push!(res, logpdf_and_gradient(fx, y)); push!(infos, 0)
+            catch e
+                e isa PosDefException || rethrow()
+                push!(res, failed(e.info)); push!(infos, e.info)
+            end
+        end
+        return res, infos
+    end
+    kind = first(kinds)
+    sps = [build_spec(fx.f, fx.x) for fx in fxs]
+    nzs = [noise_args(fx.Σy)[2] for fx in fxs]
+    yv = [collect(Float64, y) for y in ys]
+    gy = [zeros(length(y)) for y in yv]; gm = [zeros(length(y)) for y in yv]
+    gn = [zeros(kind == 1 ? length(y) : 1) for y in yv]
+    gc = [zeros(max(1, length(sp.keep[5]))) for sp in sps]; gs = [zeros(max(1, length(sp.keep[5]))) for sp in sps]
+    specs = [Ptr{CSpec}(pointer_from_objref(sp)) for sp in sps]     # (`c` is the first field of the mutable Spec: its address)
+    lp = zeros(B); infos = zeros(Cint, B)
+    # (include/sthenomi_batch.h: the entry point lives in libsthenomi_batch.so, which links against LIB)
+    pms = pointer.(ms); pnz = pointer.(nzs); pys = pointer.(yv)
+    pgy = pointer.(gy); pgm = pointer.(gm); pgn = pointer.(gn); pgc = pointer.(gc); pgs = pointer.(gs)
+    GC.@preserve sps ms nzs yv gy gm gn gc gs specs lp infos pms pnz pys pgy pgm pgn pgc pgs check(
+        @ccall LIB_BATCH.sgp_logpdf_grad_batch(ctx()::Ptr{Cvoid}, B::Cint, specs::Ptr{Ptr{CSpec}}, pms::Ptr{Ptr{Float64}},
+            kind::Cint, pnz::Ptr{Ptr{Float64}}, pys::Ptr{Ptr{Float64}}, lp::Ptr{Float64}, pgy::Ptr{Ptr{Float64}},
+            pgm::Ptr{Ptr{Float64}}, pgn::Ptr{Ptr{Float64}}, pgc::Ptr{Ptr{Float64}}, pgs::Ptr{Ptr{Float64}},
+            infos::Ptr{Cint})::Cint)
+    res = [infos[b] != 0 ? failed(infos[b]) :
+           (logpdf = lp[b], y = gy[b], mean = gm[b], noise = gn[b], coef = gc[b], inscale = gs[b]) for b in 1:B]
+    return res, infos
 end
 
 function elbo_and_gradient(v::VFE, fx::SthenoFGP, y::AbstractVector{<:Real})

@@ -1916,6 +1916,223 @@ extern "C" int sgp_logpdf_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const d
   });
 }
 
+// logpdf + gradient of nspec INDEPENDENT models in one call (sthenomi_batch.h: sgp_logpdf_grad_batch) -- the optimiser loops of
+// hyper-parameter learning run value AND gradient, and at the sizes where one gradient call is bound by its diagonal chain
+// (N = 4096: 0.2 of the fp64 MFMA peak) the members of an equally sized batch share the chip as logpdf_batch_impl's do:
+//   assembly of every member's [K + Sigma_y ; (y - m)' ; I] as logpdf_grad_core does it;
+//   ONE dataflow launch factors all of them (task pool), with ONE tile pattern: the gradient border of a DENSE K -- the
+//   identity rows are upper triangular by tile in any model, so their zero tiles are skipped as tasks and as k blocks;
+//   ONE launch computes every member's C^-1 = inv(L)' inv(L) (launch_gemm_nt_uut_batch: the single call's dense tile program);
+//   then per member the mirror, alpha, the noise gradient and the term contractions -- the single call's launches in its
+//   order, so every reduction sums in the same order; one download of all small results at the end of a chunk.
+// A structured member's own call skips K's zero tiles; the batch computes them as the exact zeros they are: same bits.
+// Everything else (different padded sizes, dense noise, sizes the single call factors with the hybrid schedule or beyond
+// SGP_BATCH_MAX_N, a multi-GPU context) goes member by member through sgp_logpdf_grad.
+static int logpdf_grad_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                                  int noise_kind, const double* const* noises, const double* const* ys, double* logpdf_out,
+                                  double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
+                                  double* const* grad_coef, double* const* grad_inscale, int* infos) {
+  CHECK_ARG(ctx && specs && noises && ys && logpdf_out && nspec >= 1, "sgp_logpdf_grad_batch: NULL argument");
+  CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad_batch: bad noise kind");
+  for (int b = 0; b < nspec; ++b) {
+    CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_grad_batch: NULL member");
+    CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_grad_batch: specs must be symmetric");
+    if (infos) infos[b] = 0;
+  }
+  auto out_of = [](double* const* v, int b) { return v ? v[b] : nullptr; };
+  int first_bad = 0;
+  auto note_bad = [&](int b, int info) {
+    logpdf_out[b] = std::numeric_limits<double>::quiet_NaN();
+    if (infos) infos[b] = info;
+    if (!first_bad) {
+      first_bad = info;
+      set_error("matrix is not positive definite; Cholesky factorization failed at leading minor " + std::to_string(info) +
+                " (batch member " + std::to_string(b) + ")");
+    }
+  };
+  // members [b0, nspec) one by one through their own call
+  auto singles = [&](int b0) -> int {
+    for (int b = b0; b < nspec; ++b) {
+      const int rc = sgp_logpdf_grad(ctx, specs[b], means ? means[b] : nullptr, noise_kind, noises[b], ys[b], logpdf_out + b,
+                                     out_of(grad_y, b), out_of(grad_mean, b), out_of(grad_noise, b), out_of(grad_coef, b),
+                                     out_of(grad_inscale, b));
+      if (rc < 0) return rc;
+      if (rc > 0) note_bad(b, rc);
+    }
+    return infos ? 0 : first_bad;
+  };
+  const long N0 = spec_rows_host(specs[0]);
+  const long n_pad = rup(std::max<long>(N0, 1), TILE), m_tot = 2 * n_pad + TILE;   // logpdf_grad_core's geometry
+  bool same = N0 >= 1;
+  for (int b = 1; b < nspec && same; ++b) {
+    const long Nb = spec_rows_host(specs[b]);
+    same = Nb >= 1 && rup(Nb, TILE) == n_pad;
+  }
+  const bool pooled = same && nspec >= 2 && !ctx->multi && ctx->dataflow != 0 && ctx->batch_max_n > 0 &&
+                      n_pad <= ctx->batch_max_n && n_pad < ctx->hybrid_grow_min_n &&
+                      (noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG);
+  if (!pooled) return singles(0);
+  CtxScope scope(ctx);
+  hipStream_t s = ctx->stream;
+  const long T_c = n_pad / TILE, T_r = m_tot / TILE;
+  // the shared pattern: the gradient border of a dense K (sz_pattern.h), the same for every member and every chunk
+  SzPattern pat;
+  sz_symbolic(std::vector<char>(1, 1), 1, std::vector<long>(1, 0), std::vector<long>(1, n_pad), n_pad, TILE, T_c, T_r, pat, true);
+  // chunk size from the device memory left (the unused blocks of the context's cache count as free)
+  const double member_bytes =
+      8.0 * ((double)m_tot * n_pad + (double)n_pad * n_pad + (double)T_c * INVD_STRIDE + 16.0 * T_c * T_c + 8.0 * n_pad);
+  int chunk = DF_MAX_BATCH;
+  {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      double avail = (double)free_b;
+      for (const auto& pb : ctx->pool)
+        if (!pb.used) avail += (double)pb.bytes;
+      chunk = (int)std::max(1.0, std::min((double)DF_MAX_BATCH, 0.9 * avail / member_bytes));
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  struct Member {
+    SpecGuard g;
+    DevBuf A, Kinv, mean, y, part;
+    NoiseDev nd;
+    long N = 0, nt = 0, off = 0;   // off: the member's results in the chunk's result buffer
+  };
+  for (int b0 = 0; b0 < nspec; b0 += chunk) {
+    const int nb = std::min(chunk, nspec - b0);
+    std::vector<Member> mem((size_t)nb);
+    DevBuf inv, res, infobuf;
+    // per member in `res`: [T_c] logdet slots | logdet | |z|^2 | logpdf | (pad to T_c + 8) | alpha [n_pad] | noise gradient
+    // [n_pad] | d coef [nt] | d inscale [nt]
+    long res_len = 0;
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      CHECK_RC(dspec_create(ctx, specs[b0 + b], &M.g.ds));
+      M.N = M.g.ds->N;
+      M.nt = std::max<long>(1, (long)M.g.ds->h_terms.size());
+      M.off = res_len;
+      res_len += T_c + 8 + 2 * n_pad + 2 * M.nt;
+    }
+    // device memory: an allocation that fails hands the remaining members to their own calls instead of failing the call
+    int arc = 0;
+    arc = arc ? arc : inv.alloc((size_t)nb * T_c * INVD_STRIDE);
+    arc = arc ? arc : res.alloc((size_t)res_len);
+    arc = arc ? arc : infobuf.alloc((size_t)nb);   // (ints inside doubles' storage)
+    for (int b = 0; b < nb && !arc; ++b) {
+      Member& M = mem[(size_t)b];
+      const int gb = b0 + b;
+      arc = M.A.alloc((size_t)m_tot * n_pad);
+      arc = arc ? arc : M.Kinv.alloc((size_t)n_pad * n_pad);
+      arc = arc ? arc : M.y.upload(ys[gb], M.N);
+      if (!arc && means && means[gb]) arc = M.mean.upload(means[gb], M.N);
+      arc = arc ? arc : upload_noise(M.nd, noise_kind, noises[gb], M.N);
+    }
+    if (arc == -2) {
+      mem.clear();
+      inv.release();
+      res.release();
+      infobuf.release();
+      return singles(b0);
+    }
+    CHECK_RC(arc);
+    int* d_infos = reinterpret_cast<int*>(infobuf.p);
+    SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
+    SGP_HIP(hipMemsetAsync(res.p, 0, sizeof(double) * res_len, s));
+    CHECK_RC(df_scratch(ctx, m_tot, nb, 0, s));
+    SzMask sz;
+    CHECK_RC(sz_upload(ctx, pat.nz, pat.words, s, &sz));
+    // 1. assembly (logpdf_grad_core's)
+    DfProb probs[DF_MAX_BATCH];
+    const double* rinv[DF_MAX_BATCH];
+    double* kinv[DF_MAX_BATCH];
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      CHECK_RC(assemble(M.g.ds, M.A.p, m_tot, 0, T_c, 0, T_c, 1, M.nd.kind, M.nd.sigma2, M.nd.diag.p, s));
+      CHECK_RC(launch_fill_pad(M.A.p, m_tot, M.N, n_pad, 0, n_pad, m_tot, 0, s));
+      CHECK_RC(launch_grad_border(M.A.p, m_tot, n_pad, M.N, M.y.p, M.mean.p, TILE + n_pad, s));
+      probs[b] = DfProb{M.A.p, inv.p + (size_t)b * T_c * INVD_STRIDE, res.p + M.off, d_infos + b};
+      rinv[b] = M.A.p + n_pad + TILE;
+      kinv[b] = M.Kinv.p;
+    }
+    // 2. one pooled factorisation: the factors and inv(L)' of every member
+    CHECK_RC(launch_chol_dataflow_batch(probs, nb, m_tot, n_pad, m_tot, ctx->d_df_state,
+                                        ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s,
+                                        sz.d_nz, sz.words));
+    // 3. one launch: C^-1 = inv(L)' inv(L), lower tiles, every member
+    CHECK_RC(launch_gemm_nt_uut_batch(rinv, m_tot, kinv, n_pad, n_pad, nb, s));
+    // 4. + 5. per member, in the single call's order
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      double* sm = res.p + M.off;
+      double* alpha = sm + T_c + 8;
+      double* gn = alpha + n_pad;
+      double* gc = gn + n_pad;
+      double* gs = gc + M.nt;
+      const double* zrow = M.A.p + n_pad;
+      CHECK_RC(launch_rowsumsq(zrow, m_tot, M.N, 1, sm + T_c + 1, 0, s));
+      CHECK_RC(launch_sum_array(sm, T_c, sm + T_c, s));
+      CHECK_RC(launch_logpdf_final(sm + T_c, sm + T_c + 1, M.N, 1, sm + T_c + 2, s));
+      CHECK_RC(launch_gemv_rows(rinv[b], m_tot, M.N, n_pad, zrow, m_tot, nullptr, alpha, s, 1));
+      CHECK_RC(launch_mirror_lower(M.Kinv.p, n_pad, n_pad, s));
+      if (out_of(grad_noise, b0 + b))
+        CHECK_RC(launch_grad_noise(M.Kinv.p, n_pad, alpha, M.N, M.nd.kind == SGP_NOISE_DIAG, gn, s));
+      if (out_of(grad_coef, b0 + b) || out_of(grad_inscale, b0 + b))
+        CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, n_pad, alpha, T_c, T_c, M.part, gc, gs, s));
+    }
+    std::vector<double> h_res((size_t)res_len);
+    std::vector<int> h_info((size_t)nb);
+    int h_abort = 0;
+    SGP_HIP(hipMemcpyAsync(h_res.data(), res.p, sizeof(double) * h_res.size(), hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipMemcpyAsync(&h_abort, ctx->d_df_state + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipStreamSynchronize(s));
+    // the abort word is shared by every member of the launch: once raised, no member's result is complete, whatever its
+    // own info says -- the call reports the time-out and with_df_fallback reruns it on the launch-based schedule
+    bool timed_out = h_abort != 0;
+    for (int b = 0; b < nb; ++b) timed_out = timed_out || h_info[(size_t)b] == SGP_DF_TIMEOUT;
+    if (timed_out) {
+      ctx->df_timed_out = true;
+      set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
+      return -3;
+    }
+    for (int b = 0; b < nb; ++b) {
+      const Member& M = mem[(size_t)b];
+      const int gb = b0 + b;
+      const int info = h_info[(size_t)b];
+      if (info > 0) {
+        note_bad(gb, info);
+        continue;
+      }
+      const double* sm = h_res.data() + M.off;
+      const double* ha = sm + T_c + 8;
+      const double* hn = ha + n_pad;
+      const double* hc = hn + n_pad;
+      const double* hs = hc + M.nt;
+      const long nterms = (long)M.g.ds->h_terms.size();
+      logpdf_out[gb] = sm[T_c + 2];
+      if (double* o = out_of(grad_y, gb))
+        for (long i = 0; i < M.N; ++i) o[i] = -ha[i];
+      if (double* o = out_of(grad_mean, gb))
+        for (long i = 0; i < M.N; ++i) o[i] = ha[i];
+      if (double* o = out_of(grad_noise, gb)) std::copy(hn, hn + (M.nd.kind == SGP_NOISE_DIAG ? M.N : 1), o);
+      if (double* o = out_of(grad_coef, gb)) std::copy(hc, hc + nterms, o);
+      if (double* o = out_of(grad_inscale, gb)) std::copy(hs, hs + nterms, o);
+    }
+  }
+  return infos ? 0 : first_bad;
+}
+// (the C entry point, sgp_logpdf_grad_batch, is in batch_entry.hip: libsthenomi_batch.so, include/sthenomi_batch.h)
+int sgp::drv_logpdf_grad_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                               int noise_kind, const double* const* noises, const double* const* ys, double* logpdf_out,
+                               double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
+                               double* const* grad_coef, double* const* grad_inscale, int* infos) {
+  return with_df_fallback(ctx, [&]() {
+    return logpdf_grad_batch_impl(ctx, nspec, specs, means, noise_kind, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise,
+                                  grad_coef, grad_inscale, infos);
+  });
+}
+
 // ---------------------------------------------------------------------------------------
 // posterior
 // ---------------------------------------------------------------------------------------

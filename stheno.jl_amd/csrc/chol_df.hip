@@ -629,9 +629,11 @@ int launch_chol_dataflow(double* A, long ld, long n_pad, long m_tot, int* d_stat
   return df_launch(a, n_pad, m_tot, ld, n_wg, timeout_s, fat, s);
 }
 
-// nb equally shaped independent matrices as one task pool (dense patterns: a batch shares no structure)
+// nb equally shaped independent matrices as one task pool.  d_nz (optional): ONE tile pattern every member shares -- the
+// gradient batch passes the border pattern of a dense K (the identity rows of [K ; (y - m)' ; I] are upper triangular by
+// tile whatever the model), so the zero tiles are skipped as tasks and their k blocks in the contractions, as in panel mode
 int launch_chol_dataflow_batch(const DfProb* probs, int nb, long ld, long n_pad, long m_tot, int* d_state, int n_wg,
-                               double timeout_s, int fat, hipStream_t s) {
+                               double timeout_s, int fat, hipStream_t s, const sz_word* d_nz, int nz_words) {
   if (nb < 1 || nb > DF_MAX_BATCH) {
     set_error("chol_dataflow: batch size out of range");
     return -1;
@@ -642,8 +644,8 @@ int launch_chol_dataflow_batch(const DfProb* probs, int nb, long ld, long n_pad,
   a.state = d_state;
   a.stats = nullptr;
   a.cols = nullptr;
-  a.nz = nullptr;
-  a.nzw = 0;
+  a.nz = d_nz;
+  a.nzw = d_nz ? nz_words : 0;
   a.gcol_base = 0;
   a.nz_t0 = 0;
   a.T_f = (int)(n_pad / TILE);

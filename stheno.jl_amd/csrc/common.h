@@ -211,7 +211,7 @@ int launch_chol_dataflow(double* A, long ld, long n_pad, long m_tot, int* d_stat
                          long long* d_cols = nullptr, int fat = 0, const sz_word* d_nz = nullptr, int nz_words = 0,
                          long gcol_base = 0, const DfPanel* px = nullptr);
 int launch_chol_dataflow_batch(const DfProb* probs, int nb, long ld, long n_pad, long m_tot, int* d_state, int n_wg,
-                               double timeout_s, int fat, hipStream_t s);
+                               double timeout_s, int fat, hipStream_t s, const sz_word* d_nz = nullptr, int nz_words = 0);
 long df_state_words(long m_tot, int nb);   // ints of d_state a launch needs
 constexpr long SGP_DF_STATE_WORDS = 16;   // state words ahead of the per-tile-row progress counters
 int launch_gemm_nt_stamps(const double* P, long ldp, double* C, long ldc, long M, long Nc, long K, long long* dbg,
@@ -254,6 +254,9 @@ int launch_gemm_nt_lz(const double* L, long ldl, const double* Zt, long ldz, dou
 int launch_gemm_nt_lz_k(const double* L, long ldl, const double* Zt, long ldz, double* C, long ldc, long n,
                         long ns, long K, double beta, hipStream_t s);
 int launch_gemm_nt_uut(const double* X, long ldx, double* C, long ldc, long n, hipStream_t s, const TileSkip* sk = nullptr);
+// the same product for nb <= DF_MAX_BATCH equally sized members in ONE launch (the member is blockIdx.z): member b computes
+// C[b] = X[b] X[b]' with exactly the dense tile program of launch_gemm_nt_uut (no TileSkip), so its bits are that call's
+int launch_gemm_nt_uut_batch(const double* const* X, long ldx, double* const* C, long ldc, long n, int nb, hipStream_t s);
 int launch_gemm_nt_splitk(const double* A, long lda, const double* B, long ldb, double* Cpart, long ldc,
                           long M, long Nc, long K, int nsplit, long part_stride, int lower_only,
                           hipStream_t s);

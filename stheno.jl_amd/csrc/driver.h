@@ -46,6 +46,12 @@ int drv_copy_strided(const double* src, long stride, long n, double* dst, hipStr
 int drv_axpy_block(double* C, long ldc, const double* S, long lds, long nr, long nc, double a, hipStream_t s);
 // dst[i + c * ld] = mean[i] (i < N) else 0
 int drv_fill_mean_cols(double* dst, long ld, long nrows, long ncols, long N, const double* mean, hipStream_t s);
+// logpdf + gradient of nspec independent models (include/sthenomi_batch.h: sgp_logpdf_grad_batch, whose C entry point in
+// libsthenomi_batch.so forwards here); takes the context itself, with the dataflow time-out fallback
+int drv_logpdf_grad_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means, int noise_kind,
+                          const double* const* noises, const double* const* ys, double* logpdf_out, double* const* grad_y,
+                          double* const* grad_mean, double* const* grad_noise, double* const* grad_coef,
+                          double* const* grad_inscale, int* infos);
 // sparse-ELBO partial sums of a slice of the data / the final factorisation (see sgp_dev_elbo_partial / _finish);
 // keep != 0: the M x M factors stay in the caller's buffers (sparse posterior)
 long drv_vfe_part_len(long m_pad);

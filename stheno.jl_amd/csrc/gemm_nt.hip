@@ -996,6 +996,40 @@ int launch_gemm_nt_uut(const double* X, long ldx, double* C, long ldc, long n, h
   return 0;
 }
 
+// launch_gemm_nt_uut for a batch of members (sgp_logpdf_grad_batch): blockIdx.z picks the member, every workgroup then runs
+// the single launch's dense tile program on that member's operands -- same tiles, same k range (k >= tr), same order
+struct UutBatch {
+  const double* X[DF_MAX_BATCH];
+  double* C[DF_MAX_BATCH];
+};
+__global__ __launch_bounds__(512, 4) void gemm_nt_uut_batch_kernel(UutBatch b, long ldx, long ldc, long n, long n_t) {
+  __shared__ __attribute__((aligned(16))) double smem[2 * 2 * KB * LDS_LD];
+  const double* X = b.X[blockIdx.z];
+  double* C = b.C[blockIdx.z];
+  const TileSkip none;
+  long tr, tc;
+  gemm_nt_dma_tile<false>(X, ldx, X, ldx, C, ldc, n, 1.0, 0.0, 0L, n_t, n_t, 0L, (const double*)C, ldc, 1, smem, tr, tc,
+                          nullptr, &none);
+}
+int launch_gemm_nt_uut_batch(const double* const* X, long ldx, double* const* C, long ldc, long n, int nb, hipStream_t s) {
+  if (n <= 0 || nb <= 0) return 0;
+  if (n % TILE || nb > DF_MAX_BATCH) {
+    set_error("gemm_nt_uut_batch: n must be a multiple of 128 and the batch at most DF_MAX_BATCH");
+    return -1;
+  }
+  UutBatch b;
+  for (int i = 0; i < DF_MAX_BATCH; ++i) {
+    b.X[i] = i < nb ? X[i] : nullptr;
+    b.C[i] = i < nb ? C[i] : nullptr;
+  }
+  const long n_t = n / TILE;
+  const long per_xcd = tri_ids_per_xcd(tri_shape(n_t, n_t, -1));
+  hipLaunchKernelGGL(gemm_nt_uut_batch_kernel, dim3((unsigned)(per_xcd * 8), 1, (unsigned)nb), dim3(512), 0, s, b, ldx, ldc,
+                     n, n_t);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
 // C (n x ns) = beta C + L Zt' for the lower-triangular-by-tile factor L (n x n, ld ldl) and Zt (ns x n,
 // ld ldz): rand's m + L Z, with every tile row contracting only the columns left of its diagonal
 // tile's right edge.  Tile rows are spread over all XCDs (n / 128 of them) -- the transposed

@@ -404,6 +404,76 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
                 _raw=(gc, gs), _rowscale=grs, _spec=spec)
 
 
+def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
+    """[logpdf_and_gradient(fx, y) for fx, y in zip(fxs, ys)] in ONE library call (sgp_logpdf_grad_batch): the step of several
+    independent hyper-parameter chains at once -- restarts, cross-validation folds, a population of candidates.  Members of one
+    padded size with scalar / diagonal noise are factored as one task pool of the dataflow kernel and their C^-1 computed by
+    one launch; every dict holds what the member's own `logpdf_and_gradient(fx, y)` returns (inputs=False, scales=False), bit
+    for bit.  A member that is not positive definite gives a dict with logpdf = NaN, `info` = its LAPACK info and no
+    gradients, instead of raising; return_infos=True also returns the infos as an array."""
+    fxs, ys = list(fxs), list(ys)
+    if len(fxs) != len(ys):
+        raise ValueError("logpdf_and_gradient_batch: one y per model")
+    if not fxs:
+        return ([], np.zeros(0, dtype=np.int32)) if return_infos else []
+    keep = []          # (spec, mean, noise kind, noise buffer, y) stay alive until the call returns
+    for fx, y in zip(fxs, ys):
+        if isinstance(fx, SparseFiniteGP):
+            raise NotImplementedError("logpdf_and_gradient_batch takes FiniteGPs (use elbo_and_gradient for a SparseFiniteGP)")
+        if not _is_prior(fx.f):
+            raise NotImplementedError("gradients are implemented for prior Stheno processes")
+        n = len(fx)
+        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+        if yv.shape[0] != n:
+            raise ValueError("length(y) != length(fx)")
+        kind, nbuf = _lib._noise_args(fx.noise, n)
+        keep.append((_prior_spec(fx.f, fx.x), _f64(mean_vector(fx.f, fx.x)), kind, nbuf, yv))
+
+    def failed(spec, info):
+        return dict(logpdf=float("nan"), info=int(info), y=None, mean=None, noise=None, terms=None, inputs=None, x=None,
+                    scales=None, _raw=None, _rowscale=None, _spec=spec)
+
+    kinds = {k[2] for k in keep}
+    if len(kinds) != 1 or _lib.NOISE_DENSE in kinds:
+        # mixed or dense noise kinds: member by member (same values; sgp_logpdf_grad_batch takes one noise kind)
+        res, infos = [], []
+        for fx, y, k in zip(fxs, ys, keep):
+            try:
+                res.append(logpdf_and_gradient(fx, y))
+                infos.append(0)
+            except _lib.PosDefException as e:
+                res.append(failed(k[0], e.info))
+                infos.append(e.info)
+        return (res, np.array(infos, dtype=np.int32)) if return_infos else res
+    kind = kinds.pop()
+    nb = len(keep)
+    outs = []          # per member: gy, gm, gn, gc, gs (the buffers logpdf_and_gradient passes)
+    for spec, _, _, _, yv in keep:
+        n, nt = len(yv), max(1, spec.n_terms)
+        outs.append((np.zeros(n), np.zeros(n), np.zeros(n if kind == _lib.NOISE_DIAG else 1), np.zeros(nt), np.zeros(nt)))
+
+    def ptrs(arrs):
+        return (C.POINTER(C.c_double) * nb)(*[_lib.dptr(a) for a in arrs])
+
+    specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
+    lp = np.zeros(nb)
+    infos = np.zeros(nb, dtype=np.int32)
+    rc = _ctx().batch.sgp_logpdf_grad_batch(_ctx().handle, nb, specs, ptrs([k[1] for k in keep]), kind,
+                                            ptrs([k[3] for k in keep]), ptrs([k[4] for k in keep]), _lib.dptr(lp),
+                                            *[ptrs([o[q] for o in outs]) for q in range(5)],
+                                            infos.ctypes.data_as(C.POINTER(C.c_int)))
+    _lib.check(rc, "sgp_logpdf_grad_batch")
+    res = []
+    for b, ((spec, _, _, _, _), (gy, gm, gn, gc, gs)) in enumerate(zip(keep, outs)):
+        if infos[b]:
+            res.append(failed(spec, infos[b]))
+            continue
+        res.append(dict(logpdf=float(lp[b]), y=gy, mean=gm, noise=(gn if kind != _lib.NOISE_SCALAR else float(gn[0])),
+                        terms=_term_records(spec, gc, gs, True), inputs=None, x=None, scales=None, _raw=(gc, gs),
+                        _rowscale=None, _spec=spec))
+    return (res, infos) if return_infos else res
+
+
 def _draw(rng, n, s):
     """Z = randn(rng, n, s) in Julia's column-major fill order, from the caller's RNG."""
     if hasattr(rng, "standard_normal"):

@@ -15,6 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi.so")
 BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_bench.so")
+BATCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_batch.so")
 
 # kernel kinds / noise kinds (sthenomi.h enums)
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
@@ -169,6 +170,19 @@ _SIGS_BENCH = {
     "sgp_bench_gemm": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _D, _D]),
 }
 
+# include/sthenomi_batch.h: the batched gradient, exported by libsthenomi_batch.so (it links against the product library and
+# works on its contexts) -- the host mirror reaches it through batch_lib() / Context.batch
+_SIGS_BATCH = {
+    "sgp_logpdf_grad_batch": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(sgp_cov_spec)), C.POINTER(_D), C.c_int,
+                                        C.POINTER(_D), C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D),
+                                        C.POINTER(_D), C.POINTER(_D), C.POINTER(C.c_int)]),
+}
+
+
+def batch_symbols():
+    """Names include/sthenomi_batch.h declares: the entry points of libsthenomi_batch.so."""
+    return sorted(_SIGS_BATCH)
+
 
 def exported_symbols():
     """Names include/sthenomi.h declares (used by the CPU-side symbol test)."""
@@ -199,6 +213,27 @@ def bench_lib():
             fn.restype = res
             fn.argtypes = args
         _bench = lib
+        return lib
+
+
+_batch = None
+
+
+def batch_lib():
+    """dlopen libsthenomi_batch.so (include/sthenomi_batch.h) after the product library it links against."""
+    global _batch
+    load()
+    with _lib_lock:
+        if _batch is not None:
+            return _batch
+        if not os.path.exists(BATCH_LIB_PATH):
+            raise SthenoMIError(f"{BATCH_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(BATCH_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_BATCH.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _batch = lib
         return lib
 
 
@@ -270,6 +305,11 @@ class Context:
     def bench(self):
         """libsthenomi_bench.so (sthenomi_bench.h): `ctx.bench.sgp_bench_*(ctx.handle, ...)`"""
         return bench_lib()
+
+    @property
+    def batch(self):
+        """libsthenomi_batch.so (sthenomi_batch.h): `ctx.batch.sgp_logpdf_grad_batch(ctx.handle, ...)`"""
+        return batch_lib()
 
     @property
     def ndev(self):
