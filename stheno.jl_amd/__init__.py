@@ -7,14 +7,14 @@ through the C-ABI of include/sthenomi.h.  Import name: `stheno_jl_amd` (see __gr
 """
 from . import lib  # noqa: F401
 from .lib import PosDefException, SthenoMIError  # noqa: F401
-from .inputs import BlockData, ColVecs, GPPPInput, blocks, split, vcat  # noqa: F401
+from .inputs import BlockData, ColVecs, GPPPInput, ImageVector, blocks, split, vcat  # noqa: F401
 from .kernels import (ConstantKernel, ExponentialKernel, KernelSum, Matern12Kernel,  # noqa: F401
                       Matern32Kernel, Matern52Kernel, PeriodicTransform, ScaledKernel, ScaleTransform,
                       ScaleTransformedKernel, TransformedKernel,
                       SEKernel, SqExponentialKernel, WhiteKernel, with_lengthscale)
 from .gp import (GP, GPC, AtomicGP, DerivedGP, Periodic, Select, Shift, Stretch,  # noqa: F401
-                 additive_gp, atomic, compose, cross, mean_vector, periodic, select, shift,
-                 stretch)
+                 additive_gp, atomic, compose, conv_geometry, cross, extract_patches, mean_vector, patch_convolve,
+                 periodic, select, shift, stretch)
 from .gppp import GPPP, extract_components, gppp, gppp_sum_model  # noqa: F401
 from .finite_gp import (VFE, ApproxPosteriorGP, FiniteGP, PosteriorGP, SparseFiniteGP,  # noqa: F401
                         cov, elbo, elbo_and_gradient, logpdf, logpdf_and_gradient, logpdf_and_gradient_batch, logpdf_batch, logpdf_f32, marginals, mean, mean_and_cov, mean_and_var,

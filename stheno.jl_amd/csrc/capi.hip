@@ -372,7 +372,27 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           return fail("spec: term input index out of range");
         const sgp_input& ri = sp->inputs[T.row_input];
         const sgp_input& ci = sp->inputs[T.col_input];
-        if (ri.dim != ci.dim) return fail("spec: row / col input dimension mismatch");
+        if (T.reserved) {
+          // a patch term (include/sthenomi_conv.h): reserved = row geometry id | column geometry id << 16, 0 = plain side
+          const int gid[2] = {(int)((uint32_t)T.reserved & 0xffffu), (int)((uint32_t)T.reserved >> 16)};
+          const PatchGeom* g[2] = {nullptr, nullptr};
+          for (int k = 0; k < 2; ++k) {
+            if (gid[k] > (int)ctx->conv_geoms.size())
+              return fail("spec: unknown patch geometry id (register it on this context with sgp_conv_geom; a multi-GPU "
+                          "context takes none)");
+            if (gid[k]) g[k] = &ctx->conv_geoms[gid[k] - 1];
+          }
+          if (g[0] && ri.dim != (int64_t)g[0]->h * g[0]->w) return fail("spec: a patched row input must have dim = height * width");
+          if (g[1] && ci.dim != (int64_t)g[1]->h * g[1]->w) return fail("spec: a patched column input must have dim = height * width");
+          if (g[0] && g[1] && (g[0]->ph != g[1]->ph || g[0]->pw != g[1]->pw))
+            return fail("spec: both sides patched with different patch sizes");
+          const PatchGeom* gp = g[0] ? g[0] : g[1];
+          if (!g[0] && ri.dim != (int64_t)gp->ph * gp->pw) return fail("spec: a plain row side must have dim = patch_h * patch_w");
+          if (!g[1] && ci.dim != (int64_t)gp->ph * gp->pw) return fail("spec: a plain column side must have dim = patch_h * patch_w");
+          ++ds->n_patch;
+        } else if (ri.dim != ci.dim) {
+          return fail("spec: row / col input dimension mismatch");
+        }
         if (ri.n != ds->row_len[I] || ci.n != ds->col_len[J])
           return fail("spec: input length does not match block length");
         if (T.row_scale && ds->row_len[I] > 0) {
@@ -383,7 +403,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           cs_len[t] = ds->col_len[J];
           cs_off[t] = place(sizeof(double) * (size_t)cs_len[t]);
         }
-        ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
+        if (!T.reserved) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
       }
     }
   const size_t terms_off = place(sizeof(DevTerm) * (size_t)std::max(1, nterms));
@@ -420,13 +440,32 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
-      for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t) {
+      // patch terms after the plain ones of their pair (the caller's order when the spec has none)
+      std::vector<int> order;
+      for (int pass = 0; pass < 2; ++pass)
+        for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t)
+          if ((sp->terms[t].reserved != 0) == (pass == 1)) order.push_back(t);
+      ds->pair_nplain.push_back((int)(order.size() - std::count_if(order.begin(), order.end(), [&](int t) {
+                                  return sp->terms[t].reserved != 0;
+                                })));
+      for (size_t k = 0; k < order.size(); ++k) {
+        const int t = order[k], pos = sp->term_ptr[p] + (int)k;
         const sgp_term& T = sp->terms[t];
         const sgp_input& ri = sp->inputs[T.row_input];
         const sgp_input& ci = sp->inputs[T.col_input];
         DevTerm D;
         D.kind = T.kind;
         D.dim = (int)ri.dim;
+        D.ph = D.pw = D.hr = D.wr = D.hc = D.wc = 0;
+        if (T.reserved) {
+          const int gr = (int)((uint32_t)T.reserved & 0xffffu), gc = (int)((uint32_t)T.reserved >> 16);
+          const PatchGeom& g = ctx->conv_geoms[(gr ? gr : gc) - 1];
+          D.ph = g.ph;
+          D.pw = g.pw;
+          D.dim = g.ph * g.pw;
+          if (gr) D.hr = ctx->conv_geoms[gr - 1].h, D.wr = ctx->conv_geoms[gr - 1].w;
+          if (gc) D.hc = ctx->conv_geoms[gc - 1].h, D.wc = ctx->conv_geoms[gc - 1].w;
+        }
         D.coef = T.coef;
         D.param = T.param;
         D.xr = (const double*)(d_base + in_off[T.row_input]);
@@ -443,7 +482,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           memcpy(h_base + cs_off[t], T.col_scale, sizeof(double) * (size_t)cs_len[t]);
           D.cs = (const double*)(d_base + cs_off[t]);
         }
-        h_terms[t] = D;
+        h_terms[pos] = D;
         ds->h_terms.push_back(D);
         ds->term_row_input.push_back(T.row_input);
         ds->term_col_input.push_back(T.col_input);
@@ -511,12 +550,16 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
                                        sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
         continue;
       }
-      for (int t = t0; t < t1; t += per) {
-        int cnt = std::min(per, t1 - t);
+      const int tp = ds->n_patch ? t0 + ds->pair_nplain[p] : t1;   // patch terms: [tp, t1), conv.hip
+      for (int t = t0; t < tp; t += per) {
+        int cnt = std::min(per, tp - t);
         CHECK_RC(launch_assemble_block(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax,
                                        lower_only, t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2,
                                        d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
       }
+      for (int t = tp; t < t1; ++t)
+        CHECK_RC(launch_assemble_conv(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only, t > t0 ? 1 : 0,
+                                      t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
     }
   }
   return 0;
@@ -1455,6 +1498,19 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag: block lengths differ");
     int p = I * ds->ncb + I;
     int t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
+    const int np = ds->n_patch ? ds->pair_nplain[p] : t1 - t0;
+    if (np < t1 - t0) {   // patch terms (conv.hip)
+      int max_d = 1, d_all = -1, max_px = 1;
+      for (int t = t0 + np; t < t1; ++t) {
+        const DevTerm& T = ds->h_terms[t];
+        max_d = std::max(max_d, T.dim);
+        d_all = (d_all < 0 || d_all == T.dim) ? T.dim : 0;
+        max_px = std::max(max_px, T.hr * T.wr + T.hc * T.wc);
+      }
+      CHECK_RC(launch_diag_conv(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, np, t1 - t0, max_d, d_all, max_px,
+                                s));
+      continue;
+    }
     CHECK_RC(launch_diag_terms(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, t1 - t0, s));
   }
   return 0;
@@ -1697,6 +1753,7 @@ extern "C" int sgp_rand(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* me
 // G = (alpha alpha' - Kinv) / 2 when alpha != nullptr, else G = the matrix at `Gm` itself.
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr,
                          long n_tc, DevBuf& dpart, double* dgc, double* dgs, hipStream_t s) {
+  CHECK_ARG(!ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
   CHECK_RC(dpart.alloc((size_t)std::max<long>(1, n_tr * n_tc) * 16));
   for (int I = 0; I < ds->nrb; ++I) {
     if (ds->row_len[I] == 0) continue;
@@ -1730,6 +1787,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   CHECK_ARG(ctx && spec && noise && y && logpdf_out, "sgp_logpdf_grad: NULL argument");
   CHECK_ARG(spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
   CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
+  CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
   CtxScope scope(ctx);
   // a multi-GPU context shards the gradient -- kernel terms, noise, y, the mean and (round 6) the input points and function
   // scales, a dense Sigma_y (multi.hip)
@@ -1937,6 +1995,7 @@ static int logpdf_grad_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* c
   for (int b = 0; b < nspec; ++b) {
     CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_grad_batch: NULL member");
     CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_grad_batch: specs must be symmetric");
+    CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_batch: gradients through patch (convolutional) terms are not supported");
     if (infos) infos[b] = 0;
   }
   auto out_of = [](double* const* v, int b) { return v ? v[b] : nullptr; };
@@ -3360,6 +3419,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
 // the three entry points: one record of arguments; a multi-GPU context shards the data points over its ranks (round 6)
 static int elbo_grad_entry(sgp_ctx* ctx, const sgp::ElboGradArgs& a) {
   CHECK_ARG(ctx, "sgp_elbo_grad: NULL context");
+  CHECK_ARG(!spec_has_patch(a.zz) && !spec_has_patch(a.xz),
+            "sgp_elbo_grad: gradients through patch (convolutional) terms are not supported");
   if (ctx->multi && ctx->multi_nranks > 1) return sgp_multi_elbo_grad(ctx, a);
   return sgp::drv_elbo_grad(ctx, a, nullptr);
 }
@@ -3414,6 +3475,7 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
                           double* grad_inscale, double* const* grad_inputs, double* const* grad_rowscale = nullptr,
                           double* const* grad_colscale = nullptr) {
   CHECK_ARG(ctx && spec && w && grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad: NULL argument");
+  CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_diag_grad: gradients through patch (convolutional) terms are not supported");
   CtxScope scope(ctx);
   SpecGuard g;
   CHECK_RC(dspec_create(ctx, spec, &g.ds));
@@ -3807,6 +3869,25 @@ int drv_diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStream
   return diag_of_spec(ctx, ds, d_out, s);
 }
 int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) { return dspec_create(ctx, sp, out); }
+int drv_conv_geom(sgp_ctx* ctx, int h, int w, int ph, int pw, int32_t* id_out) {
+  CHECK_ARG(ctx && id_out, "sgp_conv_geom: NULL argument");
+  CtxScope scope(ctx);
+  CHECK_ARG(!ctx->multi, "sgp_conv_geom: patch (convolutional) terms are not supported on a multi-GPU context");
+  CHECK_ARG(h >= 1 && w >= 1 && ph >= 1 && pw >= 1 && ph <= h && pw <= w, "sgp_conv_geom: need 1 <= patch_h <= height, 1 <= patch_w <= width");
+  CHECK_ARG((long)h * w <= CONV_MAX_PIXELS, "sgp_conv_geom: images of more than 3072 pixels are not supported");
+  CHECK_ARG(ph * pw <= CONV_MAX_PATCH, "sgp_conv_geom: patches of more than 64 pixels are not supported");
+  for (size_t k = 0; k < ctx->conv_geoms.size(); ++k) {
+    const PatchGeom& g = ctx->conv_geoms[k];
+    if (g.h == h && g.w == w && g.ph == ph && g.pw == pw) {
+      *id_out = (int32_t)(k + 1);
+      return 0;
+    }
+  }
+  CHECK_ARG(ctx->conv_geoms.size() < 0xffff, "sgp_conv_geom: too many geometries on this context");
+  ctx->conv_geoms.push_back(PatchGeom{h, w, ph, pw});
+  *id_out = (int32_t)ctx->conv_geoms.size();
+  return 0;
+}
 void drv_dspec_free(sgp_dspec* ds) { dspec_free(ds); }
 long drv_invd_stride() { return INVD_STRIDE; }
 int drv_copy_strided(const double* src, long stride, long n, double* dst, hipStream_t s) {

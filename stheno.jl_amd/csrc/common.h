@@ -81,7 +81,28 @@ struct DevTerm {
   long ldc;
   const double* rs;  // row scale or nullptr
   const double* cs;  // col scale or nullptr
+  // patch term (conv.hip): ph x pw patches, stride 1, of the images of a side with hr / hc > 0 -- that side's points are
+  // column-major hr x wr (hc x wc) images, dim = ph * pw counts the patch; ph == 0: a plain term
+  int ph, pw, hr, wr, hc, wc;
 };
+
+// a patch geometry registered on a context (sgp_conv_geom)
+struct PatchGeom {
+  int h, w, ph, pw;
+};
+constexpr int CONV_MAX_PIXELS = 3072;   // images of at most this many pixels: five of them are staged in LDS at once
+constexpr int CONV_MAX_PATCH = 64;      // ph * pw
+
+// conv.hip: patch terms of one block pair, one launch per term, onto what the plain terms wrote (accumulate != 0) or
+// written afresh with the pair's noise; `dterm` is the device copy of `T`
+int launch_assemble_conv(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm& T, const DevTerm* dterm,
+                         int lower_only, int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,
+                         long tile_r_first, long tile_c_first, long tile_r_cnt, long tile_c_cnt, hipStream_t s);
+// out[i] (i < n) = the plain terms' diagonal (nplain of them, diag_terms_kernel's sum) followed by the patch terms
+// terms[nplain, nterms), each summed as launch_assemble_conv sums entry (i, i).  max_d: the widest patch of those terms,
+// d_all: their common patch dimension (0: they differ), max_pixels: the most image pixels (row + column side) of one term
+int launch_diag_conv(double* out, long n, const DevTerm* d_terms, int nplain, int nterms, int max_d, int d_all,
+                     int max_pixels, hipStream_t s);
 
 void set_error(const std::string& s);
 

@@ -87,6 +87,8 @@ struct sgp_ctx {
   long serial = 0;                // unique per created context (capi.hip: ctx_is_live)
   sgp_multi* multi = nullptr;     // non-null: the operators shard over several GPUs (sgp_ctx_create_multi)
   int multi_nranks = 0;
+  // patch geometries registered on this context (include/sthenomi_conv.h: sgp_conv_geom): id k >= 1 is conv_geoms[k - 1]
+  std::vector<sgp::PatchGeom> conv_geoms;
   hipStream_t stream = nullptr;   // panel / critical-path stream (high priority)
   hipStream_t stream2 = nullptr;  // trailing-update stream (look-ahead overlap)
   hipEvent_t ev_panel = nullptr, ev_rest = nullptr;
@@ -291,6 +293,16 @@ struct DevBuf {
 
 }  // namespace sgp
 
+// whether a host spec carries patch terms (sgp_term.reserved != 0, include/sthenomi_conv.h): the paths without a patch
+// kernel (gradients, fp32) refuse such a spec up front rather than read its terms as plain ones
+inline bool spec_has_patch(const sgp_cov_spec* sp) {
+  if (!sp || !sp->term_ptr || !sp->terms) return false;
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t)
+    if (sp->terms[t].reserved) return true;
+  return false;
+}
+
 struct sgp_dspec {
   sgp_ctx* ctx = nullptr;
   int nrb = 0, ncb = 0, symmetric = 0;
@@ -305,4 +317,8 @@ struct sgp_dspec {
   std::vector<int> term_col_input;
   std::vector<int> in_dim;             // per spec input
   std::vector<long> in_n;
+  // patch terms (DevTerm::ph > 0): within every pair the plain terms come first (pair_nplain of them), the patch terms
+  // after them; n_patch == 0: the spec has none and the terms keep the caller's order
+  std::vector<int> pair_nplain;
+  int n_patch = 0;
 };

@@ -30,6 +30,9 @@ int drv_back_substitute(const double* Lv, long ld, const double* wall_v, long k_
                         double* d_z, double* d_alpha, hipStream_t s);
 int drv_diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStream_t s);
 int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out);   // caller holds the context
+// register a patch geometry on ctx (include/sthenomi_conv.h: sgp_conv_geom, whose C entry point in libsthenomi_conv.so
+// forwards here); takes the context itself; an equal geometry registered before keeps its id
+int drv_conv_geom(sgp_ctx* ctx, int h, int w, int ph, int pw, int32_t* id_out);
 void drv_dspec_free(sgp_dspec* ds);
 long drv_invd_stride();
 // structural zeros (common.h; capi.hip: sz_pattern / sz_upload): rank 0's context computes the tile pattern of the factor

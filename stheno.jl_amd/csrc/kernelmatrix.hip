@@ -16,38 +16,10 @@
 // registers.  Distances are the direct sum_d (a_d - b_d)^2 (exactly 0 on coincident points, so
 // SE diagonals are exactly 1: test/gp/atomic_gp.jl:34), not the GEMM trick.
 #include "common.h"
+#include "kern_eval.h"
 #include <algorithm>
 
 namespace sgp {
-
-enum { K_SE = 0, K_M12 = 1, K_M32 = 2, K_M52 = 3, K_WHITE = 4, K_CONST = 5 };
-
-template <int KIND>
-__device__ __forceinline__ double kern_eval_t(double d2, double param) {
-  if (KIND == K_SE) return exp_nonpos(-0.5 * d2);
-  if (KIND == K_M12) return exp_nonpos(-sqrt_nonneg(d2));
-  if (KIND == K_M32) {
-    double l = 1.7320508075688772 * sqrt_nonneg(d2);
-    return (1.0 + l) * exp_nonpos(-l);
-  }
-  if (KIND == K_M52) {
-    double l = 2.23606797749979 * sqrt_nonneg(d2);
-    return fma(l, fma(l, 0.3333333333333333, 1.0), 1.0) * exp_nonpos(-l);   // 1 + l + l^2 / 3
-  }
-  if (KIND == K_WHITE) return d2 == 0.0 ? 1.0 : 0.0;
-  return param;
-}
-
-__device__ __forceinline__ double kern_eval(int kind, double d2, double param) {
-  switch (kind) {
-    case K_SE: return kern_eval_t<K_SE>(d2, param);
-    case K_M12: return kern_eval_t<K_M12>(d2, param);
-    case K_M32: return kern_eval_t<K_M32>(d2, param);
-    case K_M52: return kern_eval_t<K_M52>(d2, param);
-    case K_WHITE: return kern_eval_t<K_WHITE>(d2, param);
-    default: return param;
-  }
-}
 
 constexpr int CCHUNK = 8;  // columns processed per accumulator chunk
 
@@ -528,20 +500,7 @@ int launch_border_rows(double* A, long ld, long n_pad, long N, long c0, long nc,
 __global__ void diag_terms_kernel(double* out, long n, const DevTerm* terms, int nterms) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  double acc = 0.0;
-  for (int tm = 0; tm < nterms; ++tm) {
-    const DevTerm T = terms[tm];
-    double d2 = 0.0;
-    for (int d = 0; d < T.dim; ++d) {
-      double df = T.xr[i * T.ldr + d] - T.xc[i * T.ldc + d];
-      d2 = fma(df, df, d2);
-    }
-    // same operation order as assemble_block_kernel, so var(f, x) == diag(cov(f, x)) bit for bit
-    double cw = T.coef * (T.rs ? T.rs[i] : 1.0);
-    if (T.cs) cw = cw * T.cs[i];
-    acc = fma(kern_eval(T.kind, d2, T.param), cw, acc);
-  }
-  out[i] = acc;
+  out[i] = diag_plain_sum(terms, nterms, i);
 }
 
 int launch_diag_terms(double* out, long n, const DevTerm* d_terms, int nterms, hipStream_t s) {

@@ -37,6 +37,13 @@ class FiniteGP:
 
 
 # ---- a prior-like object is anything below; dispatch by type ---------------------------------
+def _refuse_patch_gradient(*specs):
+    """gradients through patch_convolve terms are not implemented (the library refuses them too): never a silently wrong
+    gradient"""
+    if any(sp.has_patch for sp in specs):
+        raise NotImplementedError("gradients through patch_convolve (convolutional) covariance terms are not supported")
+
+
 def _is_prior(f):
     return isinstance(f, (GPPP, SthenoAbstractGP))
 
@@ -269,6 +276,8 @@ def logpdf_batch(fxs, ys, return_infos=False):
                 infos.append(e.info)
         return (np.array(vals), np.array(infos, dtype=np.int32)) if return_infos else np.array(vals)
     nb = len(keep)
+    for k in keep:
+        k[0].ref()           # (patch terms: their geometry ids on the context)
     specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
     means = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[1]) for k in keep])
     noises = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[2]) for k in keep])
@@ -354,6 +363,7 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     n = len(fx)
     yv = _f64(np.asarray(y, dtype=np.float64).ravel())
     spec = _prior_spec(fx.f, fx.x)
+    _refuse_patch_gradient(spec)
     m = _f64(mean_vector(fx.f, fx.x))
     kind, nbuf = _lib._noise_args(fx.noise, n)
     lp = np.zeros(1)
@@ -427,7 +437,9 @@ def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
         if yv.shape[0] != n:
             raise ValueError("length(y) != length(fx)")
         kind, nbuf = _lib._noise_args(fx.noise, n)
-        keep.append((_prior_spec(fx.f, fx.x), _f64(mean_vector(fx.f, fx.x)), kind, nbuf, yv))
+        spec = _prior_spec(fx.f, fx.x)
+        _refuse_patch_gradient(spec)
+        keep.append((spec, _f64(mean_vector(fx.f, fx.x)), kind, nbuf, yv))
 
     def failed(spec, info):
         return dict(logpdf=float("nan"), info=int(info), y=None, mean=None, noise=None, terms=None, inputs=None, x=None,
@@ -787,6 +799,7 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
     n, m = len(fx), len(vfe.fz)
     yv = _f64(np.asarray(y, dtype=np.float64).ravel())
     xx = _prior_spec(fx.f, fx.x)
+    _refuse_patch_gradient(zz, xz, xx)
     var_x = _f64(_kernelmatrix_diag(xx))
     out = np.zeros(1)
     gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)

@@ -31,11 +31,12 @@ from .inputs import BlockData, ColVecs, GPPPInput, as_matrix, blocks, is_pair_ve
 
 
 class _Path:
-    __slots__ = ("key", "atom", "c", "r", "X", "chain")
+    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom")
 
-    def __init__(self, key, atom, c, r, X, chain=()):
+    def __init__(self, key, atom, c, r, X, chain=(), geom=None):
         # chain: the input warps applied on the way down, outermost first, as (warp, inputs before it)
-        self.key, self.atom, self.c, self.r, self.X, self.chain = key, atom, c, r, X, chain
+        # geom: (H, W, ph, pw) when the path passed a patch_convolve node -- X then holds the flattened images
+        self.key, self.atom, self.c, self.r, self.X, self.chain, self.geom = key, atom, c, r, X, chain, geom
 
 
 class _ScaleVector(np.ndarray):
@@ -116,7 +117,13 @@ def block_list(f, x):
     return [(f, x)]
 
 
-def _paths(f, x, c, r, key, mat, chain=()):
+def _warp_name(g):
+    return getattr(g, "__name__", type(g).__name__)
+
+
+def _paths(f, x, c, r, key, mat, chain=(), geom=None):
+    if geom is not None:
+        return _conv_paths(f, x, c, r, key, mat, chain, geom)
     if isinstance(f, GPPP):  # a GPPP wrapped in atomic(...) (nested programmes, test gppp.jl:107-120)
         node, v = extract_components(f, x)
         if isinstance(node, _gp.DerivedGP) and node.args[0] == "cross":
@@ -140,19 +147,55 @@ def _paths(f, x, c, r, key, mat, chain=()):
         return _paths(f.args[2], x, c, mat.scale(f, s, x, r), key, mat, chain)
     if op == "o":
         return _paths(f.args[1], mat.warp(f, f.args[2], x), c, r, key, mat, chain + ((f.args[2], x),))
+    if op == "conv":
+        # patch_convolve: the paths of g read the patches of these images (flattened, one per column); the library sums
+        # over the patches (include/sthenomi_conv.h)
+        return _paths(f.args[1], x, c, r, key, mat, chain, _gp.conv_geometry(f, x))
     if op == "cross":
         raise ValueError("cross(...) can only appear at block level")
     raise ValueError(op)
 
 
+def _conv_paths(f, x, c, r, key, mat, chain, geom):
+    """the paths below a patch_convolve node: what commutes with patch extraction -- sums, scalar scales, `+ known`,
+    scalar Stretch warps -- and nothing else"""
+    if isinstance(f, _gp.AtomicGP):
+        if isinstance(f.gp, _gp.GP):
+            return [_Path(key + (id(f),), f, c, r, mat(x), chain, geom)]
+        raise NotImplementedError("patch_convolve of a nested GPPP is not supported")
+    if isinstance(f, GPPP) or not isinstance(f, _gp.DerivedGP):
+        raise NotImplementedError(f"patch_convolve over {type(f).__name__} is not supported")
+    op = f.args[0]
+    if op == "+":
+        return (_conv_paths(f.args[1], x, c, r, key, mat, chain, geom) +
+                _conv_paths(f.args[2], x, c, r, key, mat, chain, geom))
+    if op == "+known":
+        return _conv_paths(f.args[2], x, c, r, key, mat, chain, geom)
+    if op == "*":
+        s = f.args[1]
+        if not _gp._is_real(s):
+            raise NotImplementedError("patch_convolve: a function scale below patch_convolve does not commute with patch "
+                                      "extraction (only scalar scales do)")
+        return _conv_paths(f.args[2], x, c * float(s), r, key, mat, chain, geom)
+    if op == "o":
+        g = f.args[2]
+        if isinstance(g, _gp.Stretch) and np.ndim(g.l) == 0:
+            return _conv_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), geom)
+        raise NotImplementedError(f"patch_convolve: the warp {_warp_name(g)} below patch_convolve does not commute with "
+                                  "patch extraction (only a scalar Stretch does)")
+    if op == "conv":
+        raise NotImplementedError("patch_convolve of a patch_convolve is not supported")
+    raise NotImplementedError(f"patch_convolve over `{op}` is not supported")
+
+
 def _merge_paths(ps):
     out, index = [], {}
     for p in ps:
-        k = (p.key, id(p.X), id(p.r) if p.r is not None else None)
+        k = (p.key, id(p.X), id(p.r) if p.r is not None else None, p.geom)
         if k in index:
             index[k].c += p.c
         else:
-            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain)
+            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom)
             index[k] = q
             out.append(q)
     # paths that cancel exactly (f - f, 2 f - f - f, ...) leave no term: the block is an exact zero, as in the
@@ -191,7 +234,7 @@ def build_spec(f, x, f2=None, x2=None):
     rpaths = [_merge_paths(_paths(n, v, 1.0, None, (), mat)) for n, v in rows]
     cpaths = rpaths if symmetric else [_merge_paths(_paths(n, v, 1.0, None, (), mat)) for n, v in cols]
     table = _InputTable()
-    pairs = {}
+    pairs, geoms = {}, {}
     for I, pi in enumerate(rpaths):
         for J, pj in enumerate(cpaths):
             merged, order = {}, []
@@ -199,25 +242,39 @@ def build_spec(f, x, f2=None, x2=None):
                 for q in pj:
                     if p.key != q.key:
                         continue
-                    if p.X.shape[0] != q.X.shape[0]:
+                    if _point_dim(p) != _point_dim(q):
                         raise ValueError("input dimension mismatch between two views of one process")
+                    if p.geom is not None and q.geom is not None and p.geom[2:] != q.geom[2:]:
+                        raise ValueError("patch_convolve: two views of one process with different patch sizes")
                     for (kind, kc, param, s) in p.atom.gp.kernel.leaf_terms():
+                        if (p.geom is not None or q.geom is not None) and _kernels.chain_scale(s) is None:
+                            raise NotImplementedError("patch_convolve: the kernel's input transform does not commute with "
+                                                      "patch extraction (only a scalar ScaleTransform / with_lengthscale "
+                                                      "does)")
                         ri = table.get(p.X, s, ("row", I, p.chain))
                         ci = table.get(q.X, s, ("row" if symmetric else "col", J, q.chain))
                         k = (kind, param, ri, ci, id(p.r) if p.r is not None else None,
-                             id(q.r) if q.r is not None else None)
+                             id(q.r) if q.r is not None else None, p.geom, q.geom)
                         if k in merged:
-                            merged[k][3] += p.c * q.c * kc
+                            merged[k][0][3] += p.c * q.c * kc
                         else:
-                            merged[k] = [kind, ri, ci, p.c * q.c * kc, param, p.r, q.r]
+                            merged[k] = ([kind, ri, ci, p.c * q.c * kc, param, p.r, q.r], (p.geom, q.geom))
                             order.append(k)
             if order:
-                pairs[(I, J)] = [tuple(merged[k]) for k in order]
-    spec = _lib.Spec([len(v) for _, v in rows], [len(v) for _, v in cols], table.arrays, pairs, symmetric)
+                pairs[(I, J)] = [tuple(merged[k][0]) for k in order]
+                if any(merged[k][1] != (None, None) for k in order):
+                    geoms[(I, J)] = [merged[k][1] for k in order]
+    spec = _lib.Spec([len(v) for _, v in rows], [len(v) for _, v in cols], table.arrays, pairs, symmetric,
+                     geoms=geoms or None)
     spec._mat_keep = mat  # keep the source arrays alive (ids are identity keys)
     spec.input_origin = table.origin   # per spec input: (side, block, warp chain, kernel input chain, raw points)
     spec.block_shapes = ([_leaf_shape(v) for _, v in rows], [_leaf_shape(v) for _, v in cols])
     return spec, rows, cols
+
+
+def _point_dim(p):
+    """the dimension of the points the kernel of path p compares: the patch for a patch_convolve path"""
+    return p.geom[2] * p.geom[3] if p.geom is not None else p.X.shape[0]
 
 
 def _leaf_shape(v):

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .inputs import BlockData, ColVecs, GPPPInput, as_matrix, blocks, is_pair_vector, regroup_pairs
+from .inputs import BlockData, ColVecs, GPPPInput, ImageVector, as_matrix, blocks, is_pair_vector, regroup_pairs
 from .kernels import Kernel
 
 
@@ -211,6 +211,55 @@ def cross(fs):
     return DerivedGP(("cross", fs), fs[0].gpc)
 
 
+# ---- convolutional GPs (the reference's examples/convolutional_gp/script.jl) ----------------------------------------
+def patch_convolve(g, image_shape=None, patch_shape=(3, 3)):
+    """f = patch_convolve(g): the process f(x) = sum_p g(patch_p(x)) over every patch_shape patch, stride 1, of an image x
+    (the convolutional GP, van der Wilk et al. 2017).  Its inputs are images: an ImageVector, or a ColVecs of column-major
+    flattened images (then image_shape = (H, W) is required).  Below f, g may carry sums, scalar scales, `+ known` and
+    scalar Stretch warps; the kernel's ScaleTransform / with_lengthscale commutes with patch extraction too.  Any other
+    warp under f raises NotImplementedError."""
+    ph, pw = (int(patch_shape[0]), int(patch_shape[1]))
+    if ph < 1 or pw < 1:
+        raise ValueError("patch_convolve: patch_shape must be positive")
+    shape = None if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+    return DerivedGP(("conv", g, shape, (ph, pw)), g.gpc)
+
+
+def conv_geometry(f, x):
+    """(H, W, ph, pw) of the patch_convolve node f evaluated at the images x"""
+    _, _, shape, (ph, pw) = f.args
+    if isinstance(x, ImageVector):
+        if shape is not None and shape != x.image_shape:
+            raise ValueError(f"patch_convolve: images of {x.image_shape} given to a process of {shape} images")
+        shape = x.image_shape
+    elif not isinstance(x, ColVecs):
+        raise TypeError("patch_convolve: the inputs must be an ImageVector or a ColVecs of flattened images")
+    if shape is None:
+        raise ValueError("patch_convolve: pass image_shape=(H, W) to read flattened images from a ColVecs")
+    H, W = shape
+    if as_matrix(x).shape[0] != H * W:
+        raise ValueError(f"patch_convolve: inputs of dimension {as_matrix(x).shape[0]} are not {H} x {W} images")
+    if ph > H or pw > W:
+        raise ValueError("patch_convolve: the patch is larger than the image")
+    return (H, W, ph, pw)
+
+
+def extract_patches(x, patch_shape=(3, 3), image_shape=None):
+    """[ColVecs of patch (p, q) of every image]: patch (p, q) of image n is X[p:p+ph, q:q+pw, n] flattened column-major,
+    listed p-major as the reference example's comprehension `for p in ... for q in ...` lists them."""
+    ph, pw = patch_shape
+    if isinstance(x, ImageVector):
+        H, W = x.image_shape
+    elif image_shape is not None:
+        H, W = image_shape
+    else:
+        raise ValueError("extract_patches: pass image_shape=(H, W) for a ColVecs of flattened images")
+    X = as_matrix(x).reshape(H, W, -1, order="F")
+    n = X.shape[2]
+    return [ColVecs(X[p:p + ph, q:q + pw, :].reshape(ph * pw, n, order="F"))
+            for p in range(H - ph + 1) for q in range(W - pw + 1)]
+
+
 # ---- prior mean (host, O(N) per node) ----------------------------------------------------------
 def mean_vector(f, x):
     """mean(f, x) by the reference's recursion (addition.jl:26,73-74; product.jl:25,54;
@@ -239,6 +288,12 @@ def mean_vector(f, x):
         return (float(s) if _is_real(s) else _map_points(s, x)) * mean_vector(f.args[2], x)
     if op == "o":
         return mean_vector(f.args[1], warp(f.args[2], x))
+    if op == "conv":
+        H, W, ph, pw = conv_geometry(f, x)
+        out = np.zeros(len(x))
+        for xp in extract_patches(x, (ph, pw), (H, W)):
+            out = out + mean_vector(f.args[1], xp)
+        return out
     if op == "cross":
         return np.concatenate([mean_vector(g, b) for g, b in zip(f.args[1], blocks(x))])
     raise ValueError(op)

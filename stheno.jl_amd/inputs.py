@@ -33,6 +33,26 @@ class ColVecs:
         return isinstance(other, ColVecs) and np.array_equal(self.X, other.X)
 
 
+class ImageVector(ColVecs):
+    """ImageVector(X): n images of H x W pixels, X an H x W x n array (the reference example's GreyScaleImageVector,
+    examples/convolutional_gp/script.jl).  Stored as the ColVecs of the column-major flattened images (dim H * W, the row
+    index fastest: Julia's `reshape(X, :, n)`), which is what the library reads; `image_shape` = (H, W)."""
+
+    def __init__(self, X):
+        is32 = getattr(X, "dtype", None) == np.float32
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 3:
+            raise ValueError("ImageVector needs an H x W x n array")
+        self.image_shape = (int(X.shape[0]), int(X.shape[1]))
+        super().__init__(X.reshape(X.shape[0] * X.shape[1], X.shape[2], order="F"))
+        if is32:
+            self.eltype = np.float32
+
+    def image(self, n):
+        """image n as an H x W array"""
+        return self.X[:, n].reshape(self.image_shape, order="F")
+
+
 def is_pair_vector(x):
     """a generic vector of (process key, input) pairs -- the form gppp.jl:32-43 regroups by key"""
     return isinstance(x, (list, tuple)) and len(x) > 0 and all(

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi.so")
 BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_bench.so")
 BATCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_batch.so")
+CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 
 # kernel kinds / noise kinds (sthenomi.h enums)
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
@@ -179,6 +180,22 @@ _SIGS_BATCH = {
 }
 
 
+# include/sthenomi_conv.h: patch-geometry registration, exported by libsthenomi_conv.so (it links against the product library
+# and works on its contexts) -- Spec.bind reaches it through conv_lib()
+class sgp_patch_geom(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("patch_h", C.c_int32), ("patch_w", C.c_int32)]
+
+
+_SIGS_CONV = {
+    "sgp_conv_geom": (C.c_int, [_P, C.POINTER(sgp_patch_geom), C.POINTER(C.c_int32)]),
+}
+
+
+def conv_symbols():
+    """Names include/sthenomi_conv.h declares: the entry points of libsthenomi_conv.so."""
+    return sorted(_SIGS_CONV)
+
+
 def batch_symbols():
     """Names include/sthenomi_batch.h declares: the entry points of libsthenomi_batch.so."""
     return sorted(_SIGS_BATCH)
@@ -234,6 +251,27 @@ def batch_lib():
             fn.restype = res
             fn.argtypes = args
         _batch = lib
+        return lib
+
+
+_conv = None
+
+
+def conv_lib():
+    """dlopen libsthenomi_conv.so (include/sthenomi_conv.h) after the product library it links against."""
+    global _conv
+    load()
+    with _lib_lock:
+        if _conv is not None:
+            return _conv
+        if not os.path.exists(CONV_LIB_PATH):
+            raise SthenoMIError(f"{CONV_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(CONV_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_CONV.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _conv = lib
         return lib
 
 
@@ -380,7 +418,10 @@ class Spec:
                         (kind, row_input, col_input, coef, param, row_scale|None, col_scale|None)
     """
 
-    def __init__(self, row_len, col_len, inputs, pairs, symmetric):
+    def __init__(self, row_len, col_len, inputs, pairs, symmetric, geoms=None):
+        """geoms: dict (I, J) -> [(row_geom, col_geom)] aligned with pairs[(I, J)], a geometry being None (plain side) or
+        (H, W, ph, pw) -- patch terms (include/sthenomi_conv.h); their geometry ids are registered on the context the
+        spec is used with (bind)."""
         self.row_len = np.asarray(row_len, dtype=np.int64)
         self.col_len = np.asarray(col_len, dtype=np.int64)
         self.N = int(self.row_len.sum())
@@ -403,10 +444,15 @@ class Spec:
             self._in_arr[k].x = dptr(x)
         term_ptr = [0]
         terms = []
+        self.term_geoms = []
         for I in range(nrb):
             for J in range(ncb):
-                terms.extend(pairs.get((I, J), []))
+                pt = pairs.get((I, J), [])
+                terms.extend(pt)
+                self.term_geoms.extend((geoms or {}).get((I, J), [(None, None)] * len(pt)))
                 term_ptr.append(len(terms))
+        self.has_patch = any(g != (None, None) for g in self.term_geoms)
+        self._bound = None
         self.n_terms = len(terms)
         self._term_ptr = np.asarray(term_ptr, dtype=np.int32)
         self._terms = (sgp_term * max(1, len(terms)))()
@@ -441,12 +487,38 @@ class Spec:
         s.reserved = 0
         self.c = s
 
-    def ref(self):
+    def bind(self, ctx):
+        """Write the patch terms' geometry ids of `ctx` (sgp_conv_geom) into their sgp_term.reserved; a spec without patch
+        terms needs none.  Returns self."""
+        if self.has_patch and self._bound != ctx.handle.value:
+            lib = conv_lib()
+            ids = {}
+            for k, (rg, cg) in enumerate(self.term_geoms):
+                code = 0
+                for side, g in enumerate((rg, cg)):
+                    if g is None:
+                        continue
+                    if g not in ids:
+                        geom = sgp_patch_geom(*[int(v) for v in g])
+                        gid = C.c_int32()
+                        check(lib.sgp_conv_geom(ctx.handle, C.byref(geom), C.byref(gid)), "sgp_conv_geom")
+                        ids[g] = gid.value
+                    code |= ids[g] << (16 * side)
+                self._terms[k].reserved = code
+            self._bound = ctx.handle.value
+        return self
+
+    def ref(self, ctx=None):
+        """sgp_cov_spec* for a call on `ctx` (default: the default context, which every host-mirror operator uses)."""
+        if self.has_patch:
+            self.bind(ctx if ctx is not None else default_context())
         return C.byref(self.c)
 
     def f32_supported(self):
         """The fp32 device kernels (csrc/f32.hip: assemble_f32) take input dimension <= 16 and, per block pair,
         (number of terms) x (dimension rounded up to a power of two) <= 64; anything else runs on the fp64 path."""
+        if self.has_patch:
+            return False                 # patch terms: fp64 only (a Float32 model runs there and is rounded back)
         tp = self._term_ptr
         for p in range(len(tp) - 1):
             t0, t1 = int(tp[p]), int(tp[p + 1])
