@@ -68,7 +68,9 @@ typedef struct {
   int32_t row_input;  /* index into sgp_cov_spec.inputs; must have n == row block length */
   int32_t col_input;  /* index into sgp_cov_spec.inputs; must have n == col block length */
   int32_t reserved;   /* 0: a plain term.  Patch (convolutional) terms: row_geom_id | col_geom_id << 16, ids
-                         registered by sgp_conv_geom (include/sthenomi_conv.h, libsthenomi_conv.so)     */
+                         registered by sgp_conv_geom (include/sthenomi_conv.h, libsthenomi_conv.so).
+                         Stencil terms: the same encoding, ids of the same table registered by
+                         sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
   double param;       /* SGP_CONST: c                                                    */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */

@@ -14,7 +14,7 @@ from .kernels import (ConstantKernel, ExponentialKernel, KernelSum, Matern12Kern
                       SEKernel, SqExponentialKernel, WhiteKernel, with_lengthscale)
 from .gp import (GP, GPC, AtomicGP, DerivedGP, Periodic, Select, Shift, Stretch,  # noqa: F401
                  additive_gp, atomic, compose, conv_geometry, cross, extract_patches, mean_vector, patch_convolve,
-                 periodic, select, shift, stretch)
+                 periodic, quadrature_convolve, select, shift, stencil, stretch)
 from .gppp import GPPP, extract_components, gppp, gppp_sum_model  # noqa: F401
 from .finite_gp import (VFE, ApproxPosteriorGP, FiniteGP, PosteriorGP, SparseFiniteGP,  # noqa: F401
                         cov, elbo, elbo_and_gradient, logpdf, logpdf_and_gradient, logpdf_and_gradient_batch, logpdf_batch, logpdf_f32, marginals, mean, mean_and_cov, mean_and_var,

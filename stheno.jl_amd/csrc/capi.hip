@@ -282,6 +282,7 @@ extern "C" int sgp_ctx_destroy(sgp_ctx* c) {
   if (c->d_slots) hipFree(c->d_slots);
   if (c->d_scal) hipFree(c->d_scal);
   if (c->d_info) hipFree(c->d_info);
+  for (auto& st : c->stencils) hipFree(st.dev);
   if (c->d_df_state) hipFree(c->d_df_state);
   if (c->d_sz) hipFree(c->d_sz);
   if (c->d_szmap) hipFree(c->d_szmap);
@@ -373,23 +374,36 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
         const sgp_input& ri = sp->inputs[T.row_input];
         const sgp_input& ci = sp->inputs[T.col_input];
         if (T.reserved) {
-          // a patch term (include/sthenomi_conv.h): reserved = row geometry id | column geometry id << 16, 0 = plain side
+          // a patch or stencil term (include/sthenomi_conv.h, include/sthenomi_stencil.h): reserved = row id | column id
+          // << 16 into the context's table, 0 = plain side
           const int gid[2] = {(int)((uint32_t)T.reserved & 0xffffu), (int)((uint32_t)T.reserved >> 16)};
           const PatchGeom* g[2] = {nullptr, nullptr};
+          const StencilDesc* st[2] = {nullptr, nullptr};
           for (int k = 0; k < 2; ++k) {
             if (gid[k] > (int)ctx->conv_geoms.size())
-              return fail("spec: unknown patch geometry id (register it on this context with sgp_conv_geom; a multi-GPU "
-                          "context takes none)");
-            if (gid[k]) g[k] = &ctx->conv_geoms[gid[k] - 1];
+              return fail("spec: unknown patch geometry or stencil id (register it on this context with sgp_conv_geom / "
+                          "sgp_stencil_register; a multi-GPU context takes none)");
+            if (!gid[k]) continue;
+            const PatchGeom& e = ctx->conv_geoms[gid[k] - 1];
+            if (e.st > 0) st[k] = &ctx->stencils[e.st - 1];
+            else g[k] = &e;
           }
-          if (g[0] && ri.dim != (int64_t)g[0]->h * g[0]->w) return fail("spec: a patched row input must have dim = height * width");
-          if (g[1] && ci.dim != (int64_t)g[1]->h * g[1]->w) return fail("spec: a patched column input must have dim = height * width");
-          if (g[0] && g[1] && (g[0]->ph != g[1]->ph || g[0]->pw != g[1]->pw))
-            return fail("spec: both sides patched with different patch sizes");
-          const PatchGeom* gp = g[0] ? g[0] : g[1];
-          if (!g[0] && ri.dim != (int64_t)gp->ph * gp->pw) return fail("spec: a plain row side must have dim = patch_h * patch_w");
-          if (!g[1] && ci.dim != (int64_t)gp->ph * gp->pw) return fail("spec: a plain column side must have dim = patch_h * patch_w");
-          ++ds->n_patch;
+          if ((g[0] || g[1]) && (st[0] || st[1])) return fail("spec: a term cannot pair a patch side with a stencil side");
+          if (st[0] || st[1]) {
+            if (ri.dim != ci.dim) return fail("spec: stencil term: row / col input dimension mismatch");
+            if ((st[0] && st[0]->dim != ri.dim) || (st[1] && st[1]->dim != ci.dim))
+              return fail("spec: a stencil's dim must equal the input dimension of its side");
+            ++ds->n_stencil;
+          } else {
+            if (g[0] && ri.dim != (int64_t)g[0]->h * g[0]->w) return fail("spec: a patched row input must have dim = height * width");
+            if (g[1] && ci.dim != (int64_t)g[1]->h * g[1]->w) return fail("spec: a patched column input must have dim = height * width");
+            if (g[0] && g[1] && (g[0]->ph != g[1]->ph || g[0]->pw != g[1]->pw))
+              return fail("spec: both sides patched with different patch sizes");
+            const PatchGeom* gp = g[0] ? g[0] : g[1];
+            if (!g[0] && ri.dim != (int64_t)gp->ph * gp->pw) return fail("spec: a plain row side must have dim = patch_h * patch_w");
+            if (!g[1] && ci.dim != (int64_t)gp->ph * gp->pw) return fail("spec: a plain column side must have dim = patch_h * patch_w");
+            ++ds->n_patch;
+          }
         } else if (ri.dim != ci.dim) {
           return fail("spec: row / col input dimension mismatch");
         }
@@ -440,14 +454,20 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
-      // patch terms after the plain ones of their pair (the caller's order when the spec has none)
+      // plain | patch | stencil within every pair (the caller's order when the spec has neither)
+      auto cls = [&](int t) {
+        const uint32_t code = (uint32_t)sp->terms[t].reserved;
+        if (!code) return 0;
+        const uint32_t id = (code & 0xffffu) ? (code & 0xffffu) : (code >> 16);
+        return ctx->conv_geoms[id - 1].st > 0 ? 2 : 1;
+      };
       std::vector<int> order;
-      for (int pass = 0; pass < 2; ++pass)
+      int ncls[3] = {0, 0, 0};
+      for (int pass = 0; pass < 3; ++pass)
         for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t)
-          if ((sp->terms[t].reserved != 0) == (pass == 1)) order.push_back(t);
-      ds->pair_nplain.push_back((int)(order.size() - std::count_if(order.begin(), order.end(), [&](int t) {
-                                  return sp->terms[t].reserved != 0;
-                                })));
+          if (cls(t) == pass) order.push_back(t), ++ncls[pass];
+      ds->pair_nplain.push_back(ncls[0]);
+      ds->pair_npatch.push_back(ncls[1]);
       for (size_t k = 0; k < order.size(); ++k) {
         const int t = order[k], pos = sp->term_ptr[p] + (int)k;
         const sgp_term& T = sp->terms[t];
@@ -457,7 +477,19 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
         D.kind = T.kind;
         D.dim = (int)ri.dim;
         D.ph = D.pw = D.hr = D.wr = D.hc = D.wc = 0;
-        if (T.reserved) {
+        D.qr = D.qc = 0;
+        D.str = D.stc = nullptr;
+        if (cls(t) == 2) {
+          const int gr = (int)((uint32_t)T.reserved & 0xffffu), gc = (int)((uint32_t)T.reserved >> 16);
+          if (gr) {
+            const StencilDesc& sd = ctx->stencils[ctx->conv_geoms[gr - 1].st - 1];
+            D.qr = sd.npoints, D.str = sd.dev;
+          }
+          if (gc) {
+            const StencilDesc& sd = ctx->stencils[ctx->conv_geoms[gc - 1].st - 1];
+            D.qc = sd.npoints, D.stc = sd.dev;
+          }
+        } else if (T.reserved) {
           const int gr = (int)((uint32_t)T.reserved & 0xffffu), gc = (int)((uint32_t)T.reserved >> 16);
           const PatchGeom& g = ctx->conv_geoms[(gr ? gr : gc) - 1];
           D.ph = g.ph;
@@ -550,16 +582,22 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
                                        sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
         continue;
       }
-      const int tp = ds->n_patch ? t0 + ds->pair_nplain[p] : t1;   // patch terms: [tp, t1), conv.hip
+      const bool structured = ds->n_patch || ds->n_stencil;
+      const int tp = structured ? t0 + ds->pair_nplain[p] : t1;        // patch terms: [tp, ts), conv.hip
+      const int ts = ds->n_stencil ? tp + ds->pair_npatch[p] : t1;    // stencil terms: [ts, t1), stencil.hip
       for (int t = t0; t < tp; t += per) {
         int cnt = std::min(per, tp - t);
         CHECK_RC(launch_assemble_block(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax,
                                        lower_only, t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2,
                                        d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
       }
-      for (int t = tp; t < t1; ++t)
+      for (int t = tp; t < ts; ++t)
         CHECK_RC(launch_assemble_conv(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only, t > t0 ? 1 : 0,
                                       t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+      for (int t = ts; t < t1; ++t)
+        CHECK_RC(launch_assemble_stencil(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only,
+                                         t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf,
+                                         tcl - tcf, s));
     }
   }
   return 0;
@@ -1498,20 +1536,26 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag: block lengths differ");
     int p = I * ds->ncb + I;
     int t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
-    const int np = ds->n_patch ? ds->pair_nplain[p] : t1 - t0;
-    if (np < t1 - t0) {   // patch terms (conv.hip)
+    const int np = (ds->n_patch || ds->n_stencil) ? ds->pair_nplain[p] : t1 - t0;
+    const int te = ds->n_stencil ? t0 + np + ds->pair_npatch[p] : t1;   // plain + patch terms: [t0, te)
+    if (np < te - t0) {   // patch terms (conv.hip)
       int max_d = 1, d_all = -1, max_px = 1;
-      for (int t = t0 + np; t < t1; ++t) {
+      for (int t = t0 + np; t < te; ++t) {
         const DevTerm& T = ds->h_terms[t];
         max_d = std::max(max_d, T.dim);
         d_all = (d_all < 0 || d_all == T.dim) ? T.dim : 0;
         max_px = std::max(max_px, T.hr * T.wr + T.hc * T.wc);
       }
-      CHECK_RC(launch_diag_conv(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, np, t1 - t0, max_d, d_all, max_px,
+      CHECK_RC(launch_diag_conv(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, np, te - t0, max_d, d_all, max_px,
                                 s));
-      continue;
+    } else {
+      CHECK_RC(launch_diag_terms(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, te - t0, s));
     }
-    CHECK_RC(launch_diag_terms(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, t1 - t0, s));
+    if (te < t1) {        // stencil terms (stencil.hip), added onto the plain and patch diagonal
+      int max_dim = 1;
+      for (int t = te; t < t1; ++t) max_dim = std::max(max_dim, ds->h_terms[t].dim);
+      CHECK_RC(launch_diag_stencil(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + te, t1 - te, max_dim, s));
+    }
   }
   return 0;
 }
@@ -1753,6 +1797,7 @@ extern "C" int sgp_rand(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* me
 // G = (alpha alpha' - Kinv) / 2 when alpha != nullptr, else G = the matrix at `Gm` itself.
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr,
                          long n_tc, DevBuf& dpart, double* dgc, double* dgs, hipStream_t s) {
+  CHECK_ARG(!ds->n_stencil, "gradient contraction: stencil terms are not supported");
   CHECK_ARG(!ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
   CHECK_RC(dpart.alloc((size_t)std::max<long>(1, n_tr * n_tc) * 16));
   for (int I = 0; I < ds->nrb; ++I) {
@@ -1787,6 +1832,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   CHECK_ARG(ctx && spec && noise && y && logpdf_out, "sgp_logpdf_grad: NULL argument");
   CHECK_ARG(spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
   CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
+  CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
   CtxScope scope(ctx);
   // a multi-GPU context shards the gradient -- kernel terms, noise, y, the mean and (round 6) the input points and function
@@ -1995,6 +2041,7 @@ static int logpdf_grad_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* c
   for (int b = 0; b < nspec; ++b) {
     CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_grad_batch: NULL member");
     CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_grad_batch: specs must be symmetric");
+    CHECK_ARG(!spec_has_stencil(ctx, specs[b]), "sgp_logpdf_grad_batch: gradients through stencil terms are not supported");
     CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_batch: gradients through patch (convolutional) terms are not supported");
     if (infos) infos[b] = 0;
   }
@@ -3419,6 +3466,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
 // the three entry points: one record of arguments; a multi-GPU context shards the data points over its ranks (round 6)
 static int elbo_grad_entry(sgp_ctx* ctx, const sgp::ElboGradArgs& a) {
   CHECK_ARG(ctx, "sgp_elbo_grad: NULL context");
+  CHECK_ARG(!spec_has_stencil(ctx, a.zz) && !spec_has_stencil(ctx, a.xz),
+            "sgp_elbo_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(a.zz) && !spec_has_patch(a.xz),
             "sgp_elbo_grad: gradients through patch (convolutional) terms are not supported");
   if (ctx->multi && ctx->multi_nranks > 1) return sgp_multi_elbo_grad(ctx, a);
@@ -3475,6 +3524,7 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
                           double* grad_inscale, double* const* grad_inputs, double* const* grad_rowscale = nullptr,
                           double* const* grad_colscale = nullptr) {
   CHECK_ARG(ctx && spec && w && grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad: NULL argument");
+  CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_diag_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_diag_grad: gradients through patch (convolutional) terms are not supported");
   CtxScope scope(ctx);
   SpecGuard g;
@@ -3885,6 +3935,45 @@ int drv_conv_geom(sgp_ctx* ctx, int h, int w, int ph, int pw, int32_t* id_out) {
   }
   CHECK_ARG(ctx->conv_geoms.size() < 0xffff, "sgp_conv_geom: too many geometries on this context");
   ctx->conv_geoms.push_back(PatchGeom{h, w, ph, pw});
+  *id_out = (int32_t)ctx->conv_geoms.size();
+  return 0;
+}
+int drv_stencil_register(sgp_ctx* ctx, int dim, int npoints, const double* offsets, const double* weights, int32_t* id_out) {
+  CHECK_ARG(ctx && id_out, "sgp_stencil_register: NULL argument");
+  CtxScope scope(ctx);
+  CHECK_ARG(!ctx->multi, "sgp_stencil_register: stencil terms are not supported on a multi-GPU context");
+  CHECK_ARG(dim >= 1 && dim <= STENCIL_MAX_DIM, "sgp_stencil_register: stencil dim must be in 1 .. 16");
+  CHECK_ARG(npoints >= 1 && npoints <= STENCIL_MAX_POINTS, "sgp_stencil_register: stencil npoints must be in 1 .. 64");
+  CHECK_ARG(offsets && weights, "sgp_stencil_register: NULL offsets / weights");
+  std::vector<double> host((size_t)dim * npoints + npoints);
+  memcpy(host.data(), offsets, sizeof(double) * (size_t)dim * npoints);
+  memcpy(host.data() + (size_t)dim * npoints, weights, sizeof(double) * (size_t)npoints);
+  for (double v : host) CHECK_ARG(std::isfinite(v), "sgp_stencil_register: stencil offsets and weights must be finite");
+  for (size_t k = 0; k < ctx->conv_geoms.size(); ++k) {
+    const int st = ctx->conv_geoms[k].st;
+    if (st <= 0) continue;
+    const StencilDesc& e = ctx->stencils[st - 1];
+    if (e.dim == dim && e.npoints == npoints && !memcmp(e.host.data(), host.data(), sizeof(double) * host.size())) {
+      *id_out = (int32_t)(k + 1);   // bitwise-equal: the same id
+      return 0;
+    }
+  }
+  CHECK_ARG(ctx->conv_geoms.size() < 0xffff, "sgp_stencil_register: too many geometries and stencils on this context");
+  StencilDesc d;
+  d.dim = dim;
+  d.npoints = npoints;
+  d.host = std::move(host);
+  SGP_HIP(hipMalloc((void**)&d.dev, sizeof(double) * d.host.size()));
+  if (hipMemcpy(d.dev, d.host.data(), sizeof(double) * d.host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    hipFree(d.dev);
+    set_error("sgp_stencil_register: upload failed");
+    return -2;
+  }
+  ctx->stencils.push_back(std::move(d));
+  PatchGeom e{0, 0, 0, 0};
+  e.st = (int)ctx->stencils.size();
+  ctx->conv_geoms.push_back(e);
   *id_out = (int32_t)ctx->conv_geoms.size();
   return 0;
 }

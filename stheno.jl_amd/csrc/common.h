@@ -84,12 +84,27 @@ struct DevTerm {
   // patch term (conv.hip): ph x pw patches, stride 1, of the images of a side with hr / hc > 0 -- that side's points are
   // column-major hr x wr (hc x wc) images, dim = ph * pw counts the patch; ph == 0: a plain term
   int ph, pw, hr, wr, hc, wc;
+  // stencil term (stencil.hip): a side with qr / qc > 0 reads its points shifted by a registered stencil -- str (stc)
+  // holds its offsets (dim x qr, column-major) followed by its qr weights on the device; qr == 0: that side is plain
+  int qr, qc;
+  const double* str;
+  const double* stc;
 };
 
-// a patch geometry registered on a context (sgp_conv_geom)
+// a patch geometry registered on a context (sgp_conv_geom).  Stencils (sgp_stencil_register) take their ids from the same
+// table: an entry with st > 0 names the context's stencil st - 1 and no geometry (h == 0)
 struct PatchGeom {
   int h, w, ph, pw;
+  int st = 0;
 };
+// a stencil registered on a context (include/sthenomi_stencil.h): g(x) = sum_q w_q f(x - a_q)
+struct StencilDesc {
+  int dim, npoints;
+  std::vector<double> host;   // offsets (dim x npoints, column-major), then the npoints weights
+  double* dev = nullptr;      // the same on the context's device
+};
+constexpr int STENCIL_MAX_POINTS = 64;
+constexpr int STENCIL_MAX_DIM = 16;
 constexpr int CONV_MAX_PIXELS = 3072;   // images of at most this many pixels: five of them are staged in LDS at once
 constexpr int CONV_MAX_PATCH = 64;      // ph * pw
 
@@ -103,6 +118,14 @@ int launch_assemble_conv(double* K, long ld, long r0, long nr, long c0, long nc,
 // d_all: their common patch dimension (0: they differ), max_pixels: the most image pixels (row + column side) of one term
 int launch_diag_conv(double* out, long n, const DevTerm* d_terms, int nplain, int nterms, int max_d, int d_all,
                      int max_pixels, hipStream_t s);
+
+// stencil.hip: stencil terms of one block pair, one launch per term, arguments as launch_assemble_conv
+int launch_assemble_stencil(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm& T, const DevTerm* dterm,
+                            int lower_only, int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,
+                            long tile_r_first, long tile_c_first, long tile_r_cnt, long tile_c_cnt, hipStream_t s);
+// out[i] (i < n) = fma(s_t(i), w_t(i), out[i]) for the stencil terms t in order, s_t(i) summed as launch_assemble_stencil
+// sums entry (i, i); out holds the pair's plain and patch diagonal.  max_dim: the largest input dimension of those terms
+int launch_diag_stencil(double* out, long n, const DevTerm* d_terms, int nterms, int max_dim, hipStream_t s);
 
 void set_error(const std::string& s);
 

@@ -89,6 +89,8 @@ struct sgp_ctx {
   int multi_nranks = 0;
   // patch geometries registered on this context (include/sthenomi_conv.h: sgp_conv_geom): id k >= 1 is conv_geoms[k - 1]
   std::vector<sgp::PatchGeom> conv_geoms;
+  // stencils registered on this context (include/sthenomi_stencil.h): named by the conv_geoms entries with st > 0
+  std::vector<sgp::StencilDesc> stencils;
   hipStream_t stream = nullptr;   // panel / critical-path stream (high priority)
   hipStream_t stream2 = nullptr;  // trailing-update stream (look-ahead overlap)
   hipEvent_t ev_panel = nullptr, ev_rest = nullptr;
@@ -303,6 +305,20 @@ inline bool spec_has_patch(const sgp_cov_spec* sp) {
   return false;
 }
 
+// whether a host spec carries a stencil side that `ctx` knows (an id of ctx's table that names a stencil): the paths without
+// a stencil kernel refuse such a spec with a message of its own, before the patch refusal
+inline bool spec_has_stencil(const sgp_ctx* ctx, const sgp_cov_spec* sp) {
+  if (!ctx || !spec_has_patch(sp)) return false;
+  std::lock_guard<std::recursive_mutex> lk(const_cast<sgp_ctx*>(ctx)->mu);   // (registration may grow the table)
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t) {
+    const uint32_t code = (uint32_t)sp->terms[t].reserved;
+    for (uint32_t id : {code & 0xffffu, code >> 16})
+      if (id && id <= ctx->conv_geoms.size() && ctx->conv_geoms[id - 1].st > 0) return true;
+  }
+  return false;
+}
+
 struct sgp_dspec {
   sgp_ctx* ctx = nullptr;
   int nrb = 0, ncb = 0, symmetric = 0;
@@ -321,4 +337,7 @@ struct sgp_dspec {
   // after them; n_patch == 0: the spec has none and the terms keep the caller's order
   std::vector<int> pair_nplain;
   int n_patch = 0;
+  // stencil terms (DevTerm::qr or qc > 0): after the patch terms of their pair (pair_npatch of those); n_stencil == 0: none
+  std::vector<int> pair_npatch;
+  int n_stencil = 0;
 };

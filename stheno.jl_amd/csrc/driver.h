@@ -33,6 +33,9 @@ int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out);   /
 // register a patch geometry on ctx (include/sthenomi_conv.h: sgp_conv_geom, whose C entry point in libsthenomi_conv.so
 // forwards here); takes the context itself; an equal geometry registered before keeps its id
 int drv_conv_geom(sgp_ctx* ctx, int h, int w, int ph, int pw, int32_t* id_out);
+// register a stencil on ctx (include/sthenomi_stencil.h: sgp_stencil_register, forwarded from libsthenomi_stencil.so); ids
+// share the table of sgp_conv_geom; a bitwise-equal stencil registered before keeps its id
+int drv_stencil_register(sgp_ctx* ctx, int dim, int npoints, const double* offsets, const double* weights, int32_t* id_out);
 void drv_dspec_free(sgp_dspec* ds);
 long drv_invd_stride();
 // structural zeros (common.h; capi.hip: sz_pattern / sz_upload): rank 0's context computes the tile pattern of the factor

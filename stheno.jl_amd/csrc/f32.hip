@@ -514,6 +514,7 @@ extern "C" int sgp_logpdf_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const doub
   F_CHECK_ARG(spec->symmetric, "sgp_logpdf_f32: spec must be symmetric");
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG,
               "sgp_logpdf_f32: noise kind must be SCALAR or DIAG");
+  F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   sgp_dspec* ds = nullptr;
@@ -588,6 +589,7 @@ extern "C" int sgp_logpdf_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const doub
 
 extern "C" int sgp_kernelmatrix_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, float* K, int64_t ldk) {
   F_CHECK_ARG(ctx && spec && K, "sgp_kernelmatrix_f32: NULL argument");
+  F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   sgp_dspec* ds = nullptr;
@@ -694,6 +696,7 @@ extern "C" int sgp_rand_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   F_CHECK_ARG(ctx && spec && noise && Z && out, "sgp_rand_f32: NULL argument");
   F_CHECK_ARG(spec->symmetric, "sgp_rand_f32: spec must be symmetric");
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG, "sgp_rand_f32: noise kind must be SCALAR or DIAG");
+  F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_rand_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_rand_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   SpecG g;
@@ -748,6 +751,7 @@ extern "C" int sgp_posterior_mean_var_f32(sgp_ctx* ctx, const sgp_cov_spec* spec
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG,
               "sgp_posterior_mean_var_f32: noise kind must be SCALAR or DIAG");
   F_CHECK_ARG(!var_out || prior_ss, "sgp_posterior_mean_var_f32: prior_ss spec required for var");
+  F_CHECK_ARG(!spec_has_stencil(ctx, spec) && !spec_has_stencil(ctx, cross) && !spec_has_stencil(ctx, prior_ss), "sgp_posterior_mean_var_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec) && !spec_has_patch(cross) && !spec_has_patch(prior_ss), "sgp_posterior_mean_var_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   SpecG g, gc, gp;

@@ -38,8 +38,10 @@ class FiniteGP:
 
 # ---- a prior-like object is anything below; dispatch by type ---------------------------------
 def _refuse_patch_gradient(*specs):
-    """gradients through patch_convolve terms are not implemented (the library refuses them too): never a silently wrong
-    gradient"""
+    """gradients through patch_convolve or stencil terms are not implemented (the library refuses them too): never a
+    silently wrong gradient"""
+    if any(sp.has_stencil for sp in specs):
+        raise NotImplementedError("gradients through stencil covariance terms are not supported")
     if any(sp.has_patch for sp in specs):
         raise NotImplementedError("gradients through patch_convolve (convolutional) covariance terms are not supported")
 
@@ -299,6 +301,8 @@ def logpdf_f32(fx, y):
     if yv.shape[0] != n:
         raise ValueError("length(y) != length(fx)")
     spec = _prior_spec(fx.f, fx.x)
+    if spec.has_stencil:
+        raise NotImplementedError("stencil terms have no fp32 path: call logpdf, which runs them in fp64")
     m = _f64(mean_vector(fx.f, fx.x))
     kind, nbuf = _lib._noise_args(fx.noise, n)
     if kind == _lib.NOISE_DENSE:

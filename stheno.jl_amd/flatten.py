@@ -15,6 +15,8 @@ with  +            -> union of paths                 (addition.jl:20-47; known-f
       * function   -> r <- r .* sigma.(x)             (product.jl:25-48; x as seen at that node)
       o g          -> X <- g.(X)                      (compose.jl:16-28, fast warps :36-127)
       cross / GPPP -> one process per block           (cross.jl:54-93, gppp.jl:25-43)
+      stencil      -> the path carries (offsets, weights): ONE term per pair of paths, the library sums the
+                      shifted evaluations (include/sthenomi_stencil.h)
 and the leaf kernel expanded into SimpleKernel terms (ScaledKernel -> coefficient, KernelSum ->
 several terms, ScaleTransform -> input scale).  Block pairs without a common atom get no
 terms, which the library writes as exact zeros (test/gp/atomic_gp.jl:33).
@@ -31,12 +33,13 @@ from .inputs import BlockData, ColVecs, GPPPInput, as_matrix, blocks, is_pair_ve
 
 
 class _Path:
-    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom")
+    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom", "st")
 
-    def __init__(self, key, atom, c, r, X, chain=(), geom=None):
+    def __init__(self, key, atom, c, r, X, chain=(), geom=None, st=None):
         # chain: the input warps applied on the way down, outermost first, as (warp, inputs before it)
         # geom: (H, W, ph, pw) when the path passed a patch_convolve node -- X then holds the flattened images
-        self.key, self.atom, self.c, self.r, self.X, self.chain, self.geom = key, atom, c, r, X, chain, geom
+        # st: (offsets D x Q, weights Q) when the path passed a stencil node -- the offsets in the coordinates of X
+        self.key, self.atom, self.c, self.r, self.X, self.chain, self.geom, self.st = key, atom, c, r, X, chain, geom, st
 
 
 class _ScaleVector(np.ndarray):
@@ -151,6 +154,10 @@ def _paths(f, x, c, r, key, mat, chain=(), geom=None):
         # patch_convolve: the paths of g read the patches of these images (flattened, one per column); the library sums
         # over the patches (include/sthenomi_conv.h)
         return _paths(f.args[1], x, c, r, key, mat, chain, _gp.conv_geometry(f, x))
+    if op == "stencil":
+        # sum_q w_q f(x - a_q): the paths of f read these points, shifted by the stencil in the library
+        # (include/sthenomi_stencil.h)
+        return _stencil_paths(f.args[1], x, c, r, key, mat, chain, (f.args[2], f.args[3]))
     if op == "cross":
         raise ValueError("cross(...) can only appear at block level")
     raise ValueError(op)
@@ -185,17 +192,82 @@ def _conv_paths(f, x, c, r, key, mat, chain, geom):
                                   "patch extraction (only a scalar Stretch does)")
     if op == "conv":
         raise NotImplementedError("patch_convolve of a patch_convolve is not supported")
+    if op == "stencil":
+        raise NotImplementedError("patch_convolve of a stencil is not supported")
     raise NotImplementedError(f"patch_convolve over `{op}` is not supported")
+
+
+def _map_offsets(g, A):
+    """the offsets A (D x Q) seen through the linear warp g (Stretch / Select): g(x - a) = g(x) - g(a)"""
+    if isinstance(g, _gp.Stretch):
+        return float(g.l) * A if np.ndim(g.l) == 0 else np.asarray(g.l, dtype=np.float64) @ A
+    if isinstance(g.idx, (int, np.integer)):
+        return A[[int(g.idx)], :]
+    return A[np.asarray(g.idx), :]
+
+
+def _stencil_paths(f, x, c, r, key, mat, chain, st):
+    """the paths below a stencil node: what commutes with shifting the points -- sums, scalar scales, `+ known`, Shift
+    (moves the points), Stretch and Select (map the points and the offsets alike), and stencils (which fold into one) --
+    and nothing else"""
+    A, w = st
+    if isinstance(f, _gp.AtomicGP):
+        if isinstance(f.gp, _gp.GP):
+            X = mat(x)
+            if X.shape[0] != A.shape[0]:
+                raise ValueError(f"stencil: offsets of dimension {A.shape[0]} for inputs of dimension {X.shape[0]}")
+            if A.shape[0] > _lib.STENCIL_MAX_DIM or len(w) > _lib.STENCIL_MAX_POINTS:
+                raise NotImplementedError(f"stencil: {len(w)} points of dimension {A.shape[0]} are beyond the library's "
+                                          f"limits ({_lib.STENCIL_MAX_POINTS} points, dimension "
+                                          f"{_lib.STENCIL_MAX_DIM})")
+            return [_Path(key + (id(f),), f, c, r, X, chain, None, st)]
+        raise NotImplementedError("stencil of a nested GPPP is not supported")
+    if isinstance(f, GPPP) or not isinstance(f, _gp.DerivedGP):
+        raise NotImplementedError(f"stencil over {type(f).__name__} is not supported")
+    op = f.args[0]
+    if op == "+":
+        return (_stencil_paths(f.args[1], x, c, r, key, mat, chain, st) +
+                _stencil_paths(f.args[2], x, c, r, key, mat, chain, st))
+    if op == "+known":
+        return _stencil_paths(f.args[2], x, c, r, key, mat, chain, st)
+    if op == "*":
+        s = f.args[1]
+        if not _gp._is_real(s):
+            raise NotImplementedError("stencil: a function scale below a stencil does not commute with its shifts (only "
+                                      "scalar scales do)")
+        return _stencil_paths(f.args[2], x, c * float(s), r, key, mat, chain, st)
+    if op == "o":
+        g = f.args[2]
+        if isinstance(g, _gp.Shift):
+            return _stencil_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), st)
+        if isinstance(g, (_gp.Stretch, _gp.Select)):
+            return _stencil_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), (_map_offsets(g, A), w))
+        raise NotImplementedError(f"stencil: the warp {_warp_name(g)} below a stencil does not commute with its shifts "
+                                  "(only Shift, Stretch and Select do)")
+    if op == "stencil":
+        # a stencil of a stencil: sum_p w_p sum_q v_q f(x - a_p - b_q), point (p, q) at p * Q_b + q
+        B, v = f.args[2], f.args[3]
+        if B.shape[0] != A.shape[0]:
+            raise ValueError(f"stencil: offsets of dimension {B.shape[0]} below offsets of dimension {A.shape[0]}")
+        A2 = (A[:, :, None] + B[:, None, :]).reshape(A.shape[0], -1)
+        return _stencil_paths(f.args[1], x, c, r, key, mat, chain, (A2, np.outer(w, v).reshape(-1)))
+    if op == "conv":
+        raise NotImplementedError("stencil of a patch_convolve is not supported")
+    raise NotImplementedError(f"stencil over `{op}` is not supported")
+
+
+def _st_key(st):
+    return None if st is None else (st[0].shape, st[0].tobytes(), st[1].tobytes())
 
 
 def _merge_paths(ps):
     out, index = [], {}
     for p in ps:
-        k = (p.key, id(p.X), id(p.r) if p.r is not None else None, p.geom)
+        k = (p.key, id(p.X), id(p.r) if p.r is not None else None, p.geom, _st_key(p.st))
         if k in index:
             index[k].c += p.c
         else:
-            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom)
+            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom, p.st)
             index[k] = q
             out.append(q)
     # paths that cancel exactly (f - f, 2 f - f - f, ...) leave no term: the block is an exact zero, as in the
@@ -234,7 +306,7 @@ def build_spec(f, x, f2=None, x2=None):
     rpaths = [_merge_paths(_paths(n, v, 1.0, None, (), mat)) for n, v in rows]
     cpaths = rpaths if symmetric else [_merge_paths(_paths(n, v, 1.0, None, (), mat)) for n, v in cols]
     table = _InputTable()
-    pairs, geoms = {}, {}
+    pairs, geoms, stencils = {}, {}, {}
     for I, pi in enumerate(rpaths):
         for J, pj in enumerate(cpaths):
             merged, order = {}, []
@@ -246,26 +318,41 @@ def build_spec(f, x, f2=None, x2=None):
                         raise ValueError("input dimension mismatch between two views of one process")
                     if p.geom is not None and q.geom is not None and p.geom[2:] != q.geom[2:]:
                         raise ValueError("patch_convolve: two views of one process with different patch sizes")
+                    has_st = p.st is not None or q.st is not None
+                    if has_st and (p.geom is not None or q.geom is not None):
+                        raise NotImplementedError("a covariance between a patch_convolve view and a stencil view of one "
+                                                  "process is not supported")
                     for (kind, kc, param, s) in p.atom.gp.kernel.leaf_terms():
                         if (p.geom is not None or q.geom is not None) and _kernels.chain_scale(s) is None:
                             raise NotImplementedError("patch_convolve: the kernel's input transform does not commute with "
                                                       "patch extraction (only a scalar ScaleTransform / with_lengthscale "
                                                       "does)")
+                        sts = (None, None)
+                        if has_st:
+                            sc = _kernels.chain_scale(s)
+                            if sc is None:
+                                raise NotImplementedError("stencil: the kernel's input transform (PeriodicTransform) does "
+                                                          "not commute with its shifts (only a scalar ScaleTransform / "
+                                                          "with_lengthscale does)")
+                            sts = tuple(None if st is None else (st[0] if sc == 1.0 else sc * st[0], st[1])
+                                        for st in (p.st, q.st))
                         ri = table.get(p.X, s, ("row", I, p.chain))
                         ci = table.get(q.X, s, ("row" if symmetric else "col", J, q.chain))
                         k = (kind, param, ri, ci, id(p.r) if p.r is not None else None,
-                             id(q.r) if q.r is not None else None, p.geom, q.geom)
+                             id(q.r) if q.r is not None else None, p.geom, q.geom, _st_key(sts[0]), _st_key(sts[1]))
                         if k in merged:
                             merged[k][0][3] += p.c * q.c * kc
                         else:
-                            merged[k] = ([kind, ri, ci, p.c * q.c * kc, param, p.r, q.r], (p.geom, q.geom))
+                            merged[k] = ([kind, ri, ci, p.c * q.c * kc, param, p.r, q.r], (p.geom, q.geom), sts)
                             order.append(k)
             if order:
                 pairs[(I, J)] = [tuple(merged[k][0]) for k in order]
                 if any(merged[k][1] != (None, None) for k in order):
                     geoms[(I, J)] = [merged[k][1] for k in order]
+                if any(merged[k][2] != (None, None) for k in order):
+                    stencils[(I, J)] = [merged[k][2] for k in order]
     spec = _lib.Spec([len(v) for _, v in rows], [len(v) for _, v in cols], table.arrays, pairs, symmetric,
-                     geoms=geoms or None)
+                     geoms=geoms or None, stencils=stencils or None)
     spec._mat_keep = mat  # keep the source arrays alive (ids are identity keys)
     spec.input_origin = table.origin   # per spec input: (side, block, warp chain, kernel input chain, raw points)
     spec.block_shapes = ([_leaf_shape(v) for _, v in rows], [_leaf_shape(v) for _, v in cols])

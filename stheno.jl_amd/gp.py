@@ -8,6 +8,8 @@ Same names and semantics as the reference's Julia surface:
   compose (the Julia `∘`), stretch, select, periodic, shift   compose.jl:8-127
   additive_gp                      additive_gp.jl:10-29
   cross                            cross.jl:37-45
+  stencil, quadrature_convolve     weighted sums of shifted views (the reference's examples/quadrature-convolution,
+                                   custom_affine_transformations, differentiation)
 
 Nothing here touches a covariance matrix: the tree is only *described* on the host.  Means are
 evaluated on the host (O(N), as SURVEY.md Appendix B prescribes); covariances are flattened
@@ -260,6 +262,33 @@ def extract_patches(x, patch_shape=(3, 3), image_shape=None):
             for p in range(H - ph + 1) for q in range(W - pw + 1)]
 
 
+# ---- stencils: weighted sums of shifted views ----------------------------------------------------------------------
+def stencil(f, offsets, weights):
+    """g = stencil(f, A, w): the process g(x) = sum_q w[q] f(x - A[:, q]) (the sign of `shift`).  `offsets` is a length-Q
+    vector for scalar inputs or a D x Q matrix for ColVecs; `weights` a finite length-Q vector, Q >= 1.  The reference's
+    examples/quadrature-convolution (`quadrature_convolve`), custom_affine_transformations (f(x) + f(x + 3):
+    stencil(f, [0, -3], [1, 1])) and differentiation (central differences) are such sums.  The library assembles one
+    term per pair of paths (include/sthenomi_stencil.h) instead of Q^2 terms of shifted copies."""
+    w = np.array(weights, dtype=np.float64)
+    if w.ndim != 1 or w.shape[0] < 1:
+        raise ValueError("stencil: weights must be a vector of length Q >= 1")
+    A = np.array(offsets, dtype=np.float64)
+    if A.ndim == 1:
+        A = A.reshape(1, -1)
+    if A.ndim != 2 or A.shape[1] != w.shape[0]:
+        raise ValueError("stencil: offsets must be a length-Q vector or a D x Q matrix, Q = length(weights)")
+    if not (np.all(np.isfinite(w)) and np.all(np.isfinite(A))):
+        raise ValueError("stencil: offsets and weights must be finite")
+    return DerivedGP(("stencil", f, A, w), f.gpc)
+
+
+def quadrature_convolve(f, num_points=15):
+    """the reference example's `convolve(f)` (examples/quadrature-convolution/script.jl): Gauss-Hermite quadrature of
+    int exp(-t^2) f(x - t) dt with num_points nodes, on 1-D inputs -- stencil(f, t, w) with t, w = hermgauss(num_points)"""
+    t, w = np.polynomial.hermite.hermgauss(int(num_points))
+    return stencil(f, t, w)
+
+
 # ---- prior mean (host, O(N) per node) ----------------------------------------------------------
 def mean_vector(f, x):
     """mean(f, x) by the reference's recursion (addition.jl:26,73-74; product.jl:25,54;
@@ -293,6 +322,12 @@ def mean_vector(f, x):
         out = np.zeros(len(x))
         for xp in extract_patches(x, (ph, pw), (H, W)):
             out = out + mean_vector(f.args[1], xp)
+        return out
+    if op == "stencil":
+        _, g, A, w = f.args
+        out = np.zeros(len(x))
+        for q in range(len(w)):
+            out = out + w[q] * mean_vector(g, warp(Shift(A[:, q] if isinstance(x, ColVecs) else A[0, q]), x))
         return out
     if op == "cross":
         return np.concatenate([mean_vector(g, b) for g, b in zip(f.args[1], blocks(x))])

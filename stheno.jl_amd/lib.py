@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi.so")
 BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_bench.so")
 BATCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_batch.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
+STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
 
 # kernel kinds / noise kinds (sthenomi.h enums)
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
@@ -191,6 +192,26 @@ _SIGS_CONV = {
 }
 
 
+STENCIL_MAX_POINTS, STENCIL_MAX_DIM = 64, 16      # include/sthenomi_stencil.h: the limits of a stencil
+
+
+# include/sthenomi_stencil.h: stencil registration, exported by libsthenomi_stencil.so (links against the product library and
+# works on its contexts) -- Spec.bind reaches it through stencil_lib()
+class sgp_stencil(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("npoints", C.c_int32), ("offsets", C.POINTER(C.c_double)),
+                ("weights", C.POINTER(C.c_double))]
+
+
+_SIGS_STENCIL = {
+    "sgp_stencil_register": (C.c_int, [_P, C.POINTER(sgp_stencil), C.POINTER(C.c_int32)]),
+}
+
+
+def stencil_symbols():
+    """Names include/sthenomi_stencil.h declares: the entry points of libsthenomi_stencil.so."""
+    return sorted(_SIGS_STENCIL)
+
+
 def conv_symbols():
     """Names include/sthenomi_conv.h declares: the entry points of libsthenomi_conv.so."""
     return sorted(_SIGS_CONV)
@@ -275,6 +296,27 @@ def conv_lib():
         return lib
 
 
+_stencil = None
+
+
+def stencil_lib():
+    """dlopen libsthenomi_stencil.so (include/sthenomi_stencil.h) after the product library it links against."""
+    global _stencil
+    load()
+    with _lib_lock:
+        if _stencil is not None:
+            return _stencil
+        if not os.path.exists(STENCIL_LIB_PATH):
+            raise SthenoMIError(f"{STENCIL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(STENCIL_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_STENCIL.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _stencil = lib
+        return lib
+
+
 def load():
     """dlopen libsthenomi.so (after torch, so both share one HIP runtime) and type its symbols."""
     global _lib
@@ -337,6 +379,7 @@ class Context:
             check(lib.sgp_ctx_create(int(device), C.byref(h)), "sgp_ctx_create")
         self.handle = h
         self.device = device
+        self.is_multi = devices is not None
         self.lib = lib
 
     @property
@@ -418,10 +461,12 @@ class Spec:
                         (kind, row_input, col_input, coef, param, row_scale|None, col_scale|None)
     """
 
-    def __init__(self, row_len, col_len, inputs, pairs, symmetric, geoms=None):
+    def __init__(self, row_len, col_len, inputs, pairs, symmetric, geoms=None, stencils=None):
         """geoms: dict (I, J) -> [(row_geom, col_geom)] aligned with pairs[(I, J)], a geometry being None (plain side) or
         (H, W, ph, pw) -- patch terms (include/sthenomi_conv.h); their geometry ids are registered on the context the
-        spec is used with (bind)."""
+        spec is used with (bind).
+        stencils: dict (I, J) -> [(row_stencil, col_stencil)] aligned the same way, a stencil being None (plain side) or
+        (offsets D x Q, weights Q) -- stencil terms (include/sthenomi_stencil.h), registered by bind likewise."""
         self.row_len = np.asarray(row_len, dtype=np.int64)
         self.col_len = np.asarray(col_len, dtype=np.int64)
         self.N = int(self.row_len.sum())
@@ -445,13 +490,16 @@ class Spec:
         term_ptr = [0]
         terms = []
         self.term_geoms = []
+        self.term_stencils = []
         for I in range(nrb):
             for J in range(ncb):
                 pt = pairs.get((I, J), [])
                 terms.extend(pt)
                 self.term_geoms.extend((geoms or {}).get((I, J), [(None, None)] * len(pt)))
+                self.term_stencils.extend((stencils or {}).get((I, J), [(None, None)] * len(pt)))
                 term_ptr.append(len(terms))
         self.has_patch = any(g != (None, None) for g in self.term_geoms)
+        self.has_stencil = any(st != (None, None) for st in self.term_stencils)
         self._bound = None
         self.n_terms = len(terms)
         self._term_ptr = np.asarray(term_ptr, dtype=np.int32)
@@ -488,37 +536,48 @@ class Spec:
         self.c = s
 
     def bind(self, ctx):
-        """Write the patch terms' geometry ids of `ctx` (sgp_conv_geom) into their sgp_term.reserved; a spec without patch
-        terms needs none.  Returns self."""
-        if self.has_patch and self._bound != ctx.handle.value:
-            lib = conv_lib()
+        """Write the ids of `ctx` of the patch terms' geometries (sgp_conv_geom) and of the stencil terms' stencils
+        (sgp_stencil_register) into their sgp_term.reserved; a spec with neither needs none.  Returns self."""
+        if (self.has_patch or self.has_stencil) and self._bound != ctx.handle.value:
+            if self.has_stencil and getattr(ctx, "is_multi", False):
+                raise NotImplementedError("stencil terms are not supported on a multi-GPU context")
             ids = {}
-            for k, (rg, cg) in enumerate(self.term_geoms):
+            for k, sides in enumerate(zip(self.term_geoms, self.term_stencils)):
                 code = 0
-                for side, g in enumerate((rg, cg)):
-                    if g is None:
-                        continue
-                    if g not in ids:
-                        geom = sgp_patch_geom(*[int(v) for v in g])
-                        gid = C.c_int32()
-                        check(lib.sgp_conv_geom(ctx.handle, C.byref(geom), C.byref(gid)), "sgp_conv_geom")
-                        ids[g] = gid.value
-                    code |= ids[g] << (16 * side)
+                for side, (g, st) in enumerate(zip(*sides)):
+                    if g is not None:
+                        if ("g", g) not in ids:
+                            geom = sgp_patch_geom(*[int(v) for v in g])
+                            gid = C.c_int32()
+                            check(conv_lib().sgp_conv_geom(ctx.handle, C.byref(geom), C.byref(gid)), "sgp_conv_geom")
+                            ids[("g", g)] = gid.value
+                        code |= ids[("g", g)] << (16 * side)
+                    elif st is not None:
+                        key = ("s", st[0].shape, st[0].tobytes(), st[1].tobytes())
+                        if key not in ids:
+                            o = np.ascontiguousarray(st[0].T, dtype=np.float64)     # column-major D x Q
+                            w = np.ascontiguousarray(st[1], dtype=np.float64)
+                            desc = sgp_stencil(int(st[0].shape[0]), int(st[0].shape[1]), dptr(o), dptr(w))
+                            sid = C.c_int32()
+                            check(stencil_lib().sgp_stencil_register(ctx.handle, C.byref(desc), C.byref(sid)),
+                                  "sgp_stencil_register")
+                            ids[key] = sid.value
+                        code |= ids[key] << (16 * side)
                 self._terms[k].reserved = code
             self._bound = ctx.handle.value
         return self
 
     def ref(self, ctx=None):
         """sgp_cov_spec* for a call on `ctx` (default: the default context, which every host-mirror operator uses)."""
-        if self.has_patch:
+        if self.has_patch or self.has_stencil:
             self.bind(ctx if ctx is not None else default_context())
         return C.byref(self.c)
 
     def f32_supported(self):
         """The fp32 device kernels (csrc/f32.hip: assemble_f32) take input dimension <= 16 and, per block pair,
         (number of terms) x (dimension rounded up to a power of two) <= 64; anything else runs on the fp64 path."""
-        if self.has_patch:
-            return False                 # patch terms: fp64 only (a Float32 model runs there and is rounded back)
+        if self.has_patch or self.has_stencil:
+            return False                 # patch / stencil terms: fp64 only (a Float32 model runs there and is rounded back)
         tp = self._term_ptr
         for p in range(len(tp) - 1):
             t0, t1 = int(tp[p]), int(tp[p + 1])
