@@ -20,15 +20,24 @@ N = 65536, D = 8).
 --gpus N never runs on fewer than N GPUs: without WORLD_SIZE it builds the N-device context and exits non-zero when
 fewer devices are visible; under torch.distributed.run WORLD_SIZE must equal N.
 
-Prints ONE JSON line on rank 0 (contract in the round prompt) carrying, next to the contract's keys:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step, the workload that ran, the
+value the last step returned and the rates that follow from ms_per_step.  A plain run does nothing else: it sets up,
+warms up, times the steps, writes --dump-outputs and prints the line.
+
+--full also measures and checks everything beyond the headline, after the timed steps (the keys stay null without it):
   parity_rel   |value - CPU golden| / |golden| for the configuration that ran (tests/golden/)
-  roofline     the dominant kernel against its bound (fp64-MFMA trailing-update GEMM timed with HIP
-               events on its own streams inside libsthenomi; for the ELBO also the HBM-bound
-               K(x,z) assembly stage)
+  stages, roofline
+               the dominant kernel against its bound (fp64-MFMA trailing-update GEMM timed with HIP
+               events on its own streams inside libsthenomi, one instrumented step; for the ELBO also the
+               HBM-bound K(x,z) assembly stage); under the hybrid schedule also the same launches on one
+               stream and the older schedule on the same box
   host_api     the same step through the host-buffer entry point the Julia `ccall` binds
                (sgp_logpdf / sgp_elbo: uploads X, y; workspace from the context's cache)
   cpu_baseline the NumPy/SciPy/OpenBLAS oracle restatement -- NOT Julia -- timed on this host's
-               cores on a bounded sample.
+               cores on a bounded sample
+  north_star_target, sizes, grad
+               (default c5 line) the north-star model, the N = 4096 / 16384 sizes and batches, the gradient.
+--no-host-api, --no-extras and --cpu-sample N trim a --full run.
 
 --dump-outputs DIR writes, after the timed steps, what the timed entry point returned in the last of them as
 DIR/<name>.npy (fp64, under 64 MB in all; the inputs are seeded, so two builds can be compared file by file):
@@ -200,8 +209,12 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default=os.environ.get("SGP_BENCH_CONFIG", "c5"), choices=sorted(bc.CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: parity against the "
+                         "CPU golden, stage split and roofline, host-buffer entry point, CPU baseline, the default line's other "
+                         "models, sizes and gradient")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="N of the bounded CPU-baseline sample (0 = skip; -1 = automatic: min(N, 32768) -- at the headline size the "
+                    help="--full: N of the bounded CPU-baseline sample (0 = skip; -1 = automatic: min(N, 32768) -- at the headline size the "
                          "Cholesky of the sample is 1/8 of the workload's, 8 s of LAPACK dpotrf; round 5 sampled 16384 = 1/64; "
                          "ELBO: 2x this many data points, automatic 16384)")
     ap.add_argument("--panel", type=int, default=1024, help="column-panel width of the multi-GPU path")
@@ -209,10 +222,10 @@ def main():
     ap.add_argument("--devices", default=os.environ.get("SGP_BENCH_DEVICES", ""),
                     help="in-process multi-GPU context over exactly these devices, e.g. 0,1,2,3 (a repeated device = "
                          "several ranks on one GPU: loopback test configuration)")
-    ap.add_argument("--no-host-api", action="store_true", help="skip the host-buffer C-ABI leg")
+    ap.add_argument("--no-host-api", action="store_true", help="--full: skip the host-buffer C-ABI leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default c5 line only: skip the untimed-by-the-headline extras (north-star `target` model, N = 4096 / "
-                         "16384 size sweep) that ride in the same JSON line")
+                    help="--full: skip the extra schedules of the roofline and, on the default c5 line, the extras untimed by the "
+                         "headline (north-star `target` model, N = 4096 / 16384 size sweep, gradient)")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"],
                     help="f32: the fp32 instantiation (sgp_logpdf_f32, host-buffer entry point; 1 GPU, dense configs)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -404,11 +417,13 @@ def main():
             outputs.update(factor_outputs(dev_factor[0], N, dev_factor[1], dev_factor[2]))
         write_outputs(args.dump_outputs, outputs)
 
-    # ---- untimed extras on 1 GPU: instrumented step (stage split + per-launch GEMM timing), host API
+    # ---- untimed extras on 1 GPU (--full): instrumented step (stage split + per-launch GEMM timing), host API
     roofline = stages = host_api = None
     M = bc.ELBO_M
     if is_elbo:
         flops = 2.0 * M * M * N + 2.0 * M ** 3 / 3.0 + 2.0 * D * M * N   # 8.86 TFLOP
+        whole_tflops = flops / (ms_per_step * 1e-3) / 1e12
+    if is_elbo and args.full:
         L.check(lib.sgp_ctx_stage_timing(ctx.handle, 1))
         step()
         st = np.zeros(16)
@@ -438,8 +453,7 @@ def main():
             "binding": ("mfma: the two M^2 N products take %.0f%% of the device time, the K(x,z) assembly %.0f%%"
                         % (100 * mfma_ms / max(st[:6].sum(), 1e-9), 100 * st[1] / max(st[:6].sum(), 1e-9))),
         }
-        whole_tflops = flops / (ms_per_step * 1e-3) / 1e12
-    else:
+    if not is_elbo:
         # Models with independent components have exact zero blocks in their covariance and in its Cholesky factor; the
         # factorisation skips the tile products with a structurally zero operand (sthenomi.h: sgp_ctx_factor_work).  Rates
         # and roofline fractions are quoted on the flops that RAN (work_frac x N^3 / 3); the dense-equivalent rate -- what a
@@ -450,7 +464,7 @@ def main():
             if de > 0:
                 work_frac = ex / de
         whole_tflops = work_frac * (N ** 3 / 3.0) / (ms_per_step * 1e-3) / 1e12
-    if args.dtype == "f32" and not is_elbo:
+    if args.full and args.dtype == "f32" and not is_elbo:
         PEAK_F32 = 157.3   # v_mfma_f32_32x32x2_f32 / fp32 vector peak (guide section 3)
         roofline = {"kernel": "gemm_nt_f32_dma_kernel (v_mfma_f32_32x32x2_f32 trailing updates; second instantiation, LDS-DMA operand "
                               "path, 4 workgroups per CU)",
@@ -477,7 +491,7 @@ def main():
                                      2: "explicit list (SGP_MULTI_OWNERS)"}.get(int(st[9 + 4 * P_]), "?"),
                  "late_bound_event_waits": int(st[10 + 4 * P_]),
                  "transport_probe_ms": transport_probe}
-        if not is_elbo:
+        if args.full and not is_elbo:
             tf = [r["update_tflops"] for r in per_rank if r["update_tflops"]]
             per_gpu = whole_tflops / len(set(devs))
             roofline = {"kernel": "sgp::gemm_nt_seg_kernel (batched trailing updates of the in-library column-panel driver: one launch "
@@ -488,7 +502,7 @@ def main():
                         "note": "achieved = whole-step N^3/3 rate per physical GPU of the sharded run (panel factorisations "
                                 "and transport included); per_rank_update_tflops = each rank's trailing-update flops / the "
                                 "span from its first to its last update (HIP events)" + ("" if tf else " (no updates ran)")}
-    if not use_dist and not inproc and not is_elbo and args.dtype == "f64":
+    if args.full and not use_dist and not inproc and not is_elbo and args.dtype == "f64":
         step(timings)
         upd_ms, n_launch, upd_flops = timings[3], int(timings[4]), timings[5]
         achieved = upd_flops / (upd_ms * 1e-3) / 1e12 if upd_ms > 0 else 0.0
@@ -640,14 +654,14 @@ def main():
         stages = {"assemble_ms": timings[0], "cholesky_ms": timings[1], "finalize_ms": timings[2],
                   "kernelmatrix_GBps": asm_bytes / (timings[0] * 1e-3) / 1e9,
                   "kernelmatrix_frac_of_hbm_peak": asm_bytes / (timings[0] * 1e-3) / 1e9 / PEAK_HBM_GBS}
-    if use_dist and not inproc and not is_elbo:
+    if args.full and use_dist and not inproc and not is_elbo:
         # the per-launch HIP-event instrument lives in the 1-GPU driver; the sharded run reports its whole-step rate
         per_gpu = whole_tflops / world
         roofline = {"kernel": "sgp::gemm_nt_dma_kernel<1> (per-panel trailing updates of the column-panel driver)",
                     "bound": "mfma", "achieved": per_gpu, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
                     "frac": per_gpu / PEAK_FP64_MFMA_TFLOPS, "traffic": None,
                     "note": "whole-step N^3/3 rate per GPU of the sharded run (panel broadcasts and factorisations included)"}
-    if host_step is not None and not args.no_host_api:
+    if args.full and host_step is not None and not args.no_host_api:
         # the real boundary: host buffers in, workspace from the context's grow-only cache
         hv = host_step()          # first call sizes the cache
         torch.cuda.synchronize()
@@ -661,9 +675,11 @@ def main():
 
     # ---- extras of the DEFAULT line (round-3 verdict: the driver only ever timed c5): the north-star model (`target`: the
     # 3-process @gppp over BlockData, N = 65536, D = 8) and the N = 4096 / 16384 points of the size sweep, each through the
-    # host-buffer entry point the Julia `ccall` binds, on the same context, AFTER the timed region of the headline.
+    # host-buffer entry point the Julia `ccall` binds, on the same context, AFTER the timed region of the headline (--full).
     north_star = sizes = None
-    if (args.config == "c5" and not args.no_extras and not use_dist and not inproc and args.dtype == "f64" and rank == 0):
+    c5_extras = (args.full and args.config == "c5" and not args.no_extras and not use_dist and not inproc and args.dtype == "f64"
+                 and rank == 0)
+    if c5_extras:
         def time_config(name, steps, warmup, ctx=ctx):
             kd, Nn, Dd = bc.CONFIGS[name]
             ww = bc.build(pkg, name)
@@ -760,7 +776,7 @@ def main():
     # MFMA peak on its N^3 flops (factorisation N^3/3 + inverse 2N^3/3: LAPACK dpotri economics), and parity of d/d sigma^2
     # and d/d inscale against the standalone CPU goldens (tests/golden/grad_configs.json; n32k: logpdf only).
     grad = None
-    if (args.config == "c5" and not args.no_extras and not use_dist and not inproc and args.dtype == "f64" and rank == 0):
+    if c5_extras:
         gg_all = {}
         gpath = os.path.join(ROOT, "tests", "golden", "grad_configs.json")
         if os.path.exists(gpath):
@@ -803,12 +819,12 @@ def main():
             grad[name] = rec
 
     if rank == 0:
-        g = bc.golden(args.config)
+        g = bc.golden(args.config) if args.full else None
         gval = None if g is None else g.get("elbo" if is_elbo else "logpdf")
         parity = None if gval is None else abs(val - gval) / abs(gval)   # (fp32 lines: fp32 accuracy, ~1e-6)
         cpu = None
         cpu_n = args.cpu_sample if args.cpu_sample >= 0 else (16384 if is_elbo else min(N, 32768))
-        if cpu_n > 0 and world == 1 and not inproc:
+        if args.full and cpu_n > 0 and world == 1 and not inproc:
             # (a reported baseline must never cost the line: a failing CPU leg is retried on half the sample, then recorded)
             for attempt, n_try in enumerate((cpu_n, max(cpu_n // 2, 1024))):
                 try:
@@ -834,7 +850,8 @@ def main():
                                        "sgp_logpdf_f32 (host buffers)" if args.dtype == "f32" else
                                        "sgp_logpdf on the multi-GPU context (host buffers)" if inproc else
                                        "dist_logpdf (process per GPU, device-resident panels)" if use_dist else
-                                       "sgp_dev_logpdf (X, y device-resident; the host-buffer sgp_logpdf is timed in host_api)"),
+                                       "sgp_dev_logpdf (X, y device-resident; the host-buffer sgp_logpdf is timed in host_api "
+                                       "under --full)"),
                        "N": N, "D": D, "kernel": kind,
                        "parallelism": (f"in-process multi-GPU context x{len(devs)} ({'data points' if is_elbo else 'column panels'} "
                                        f"sharded inside libsthenomi, transport {ctx.transport})" if inproc
@@ -846,7 +863,9 @@ def main():
             "cholesky_frac_of_fp64_matrix_peak": (whole_tflops / (PEAK_FP64_MFMA_TFLOPS * (len(set(devs)) if inproc else world))
                                                   if args.dtype == "f64" else None),
             "multi_gpu": multi,
-            "logpdf": val, "golden": gval, "parity_rel": parity,
+            "logpdf": val,
+            "full": args.full,      # false: the keys below are null (neither measured nor checked)
+            "golden": gval, "parity_rel": parity,
             "stages": stages, "roofline": roofline, "host_api": host_api, "cpu_baseline": cpu,
             "north_star_target": north_star, "sizes": sizes, "grad": grad,
         }

@@ -77,7 +77,8 @@ def test_gpus_2_exits_nonzero_without_two_gpus(gpus):
 
 @pytest.mark.gpu
 def test_inprocess_multi_gpu_line_on_loopback_ranks():
-    r = _bench("--gpus", "2", "--devices", "0,0", "--config", "c1", "--steps", "2", "--warmup", "1", "--cpu-sample", "0")
+    r = _bench("--gpus", "2", "--devices", "0,0", "--config", "c1", "--steps", "2", "--warmup", "1", "--cpu-sample", "0",
+               "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     # two loopback ranks on ONE physical GPU: n_gpus counts GPUs, `ranks` the ranks, and the line says it is a loopback run
@@ -95,7 +96,7 @@ def test_transport_probe_code_path_on_loopback_ranks():
     """On a node with > 2 GPUs bench.py times one untimed logpdf per panel transport and keeps the faster one; the
     probe's code path runs here with loopback ranks (both candidates resolve to same-device copies)."""
     r = _bench("--gpus", "3", "--devices", "0,0,0", "--config", "c1", "--steps", "1", "--warmup", "1", "--cpu-sample", "0",
-               env={"SGP_BENCH_FORCE_PROBE": "1", "SGP_MULTI_PANEL": "512"})
+               "--full", env={"SGP_BENCH_FORCE_PROBE": "1", "SGP_MULTI_PANEL": "512"})
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     probe = line["multi_gpu"]["transport_probe_ms"]
@@ -112,3 +113,36 @@ def test_gpus_2_refuses_on_the_one_gpu_box(gpus):
         pytest.skip("this box has that many GPUs")
     r = _bench("--gpus", gpus, "--config", "c1", "--steps", "1", "--warmup", "0", "--cpu-sample", "0")
     assert r.returncode != 0 and r.stdout.strip() == "" and "refusing" in r.stderr
+
+
+FULL_ONLY = ("golden", "parity_rel", "stages", "roofline", "host_api", "cpu_baseline", "north_star_target", "sizes", "grad")
+
+
+def test_full_is_an_option_and_off_by_default():
+    r = _bench("--help")
+    assert r.returncode == 0 and "--full" in r.stdout                     # (off by default: the GPU test below reads `full`)
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_full_adds_the_rest():
+    """A plain run prints the headline of the timed steps and nothing it would have to measure or check besides; --full times
+    the same steps of the same seeded problem and then adds the parity check, the stage split, the roofline and the
+    host-buffer leg."""
+    lines = {}
+    for mode, extra in (("plain", ()), ("full", ("--full", "--cpu-sample", "0"))):
+        r = _bench("--gpus", "1", "--config", "c1", "--steps", "2", "--warmup", "1", *extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = r.stdout.strip().splitlines()
+        assert len(out) == 1, out
+        lines[mode] = json.loads(out[0])
+    for mode, line in lines.items():
+        assert line["metric"] == "logpdf_per_sec" and line["unit"] == "logpdf/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f64" and line["steps"] == 2 and line["warmup"] == 1
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-12 * line["value"]
+        assert line["full"] is (mode == "full")
+    plain, full = lines["plain"], lines["full"]
+    assert all(plain[k] is None for k in FULL_ONLY), {k: plain[k] for k in FULL_ONLY if plain[k] is not None}
+    assert plain["logpdf"] == full["logpdf"]                               # the same step, bit for bit
+    assert full["parity_rel"] is not None and full["parity_rel"] < 1e-10
+    assert full["stages"]["cholesky_ms"] > 0 and full["roofline"]["bound"] == "mfma"
+    assert full["host_api"]["calls"] >= 1 and abs(full["host_api"]["logpdf"] - full["logpdf"]) < 1e-10 * abs(full["logpdf"])

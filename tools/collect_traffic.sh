@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM-side traffic of the dominant kernel over a whole bench step (separate --pmc passes, MI355X_MICROARCH.md):
-# rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE on `bench.py --config <c> --steps 1`, averaged over the launches of
+# rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE on `bench.py --full --config <c> --steps 1`, averaged over the launches of
 # sgp::gemm_nt_dma_kernel<1> / gemm_nt_dma_potrf_kernel<1, true> (the trailing updates).  -> gpurun_out/r02traffic/<c>_{FETCH_SIZE,WRITE_SIZE}.json
 # usage: collect_traffic.sh [configs...]   (default: c5 target)
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -11,7 +11,7 @@ CONFIGS=${@:-c5 target}
 for c in $CONFIGS; do
   for cnt in FETCH_SIZE WRITE_SIZE; do
     timeout 400 rocprofv3 --pmc $cnt --output-format csv -d $OUT/pmc_${c}_$cnt -o p -- \
-        python $R/bench.py --config $c --steps 1 --warmup 0 --cpu-sample 0 --no-host-api > $OUT/${c}_$cnt.bench.json 2> $OUT/${c}_$cnt.err
+        python $R/bench.py --full --config $c --steps 1 --warmup 0 --cpu-sample 0 --no-host-api > $OUT/${c}_$cnt.bench.json 2> $OUT/${c}_$cnt.err
     f=$(find $OUT/pmc_${c}_$cnt -name "*counter_collection.csv" | head -1)
     [ -n "$f" ] && python - "$f" $cnt > $OUT/${c}_$cnt.json <<'PY'
 import csv, json, sys

@@ -6,7 +6,7 @@ O=gpurun_out/r06_call13
 mkdir -p $O
 run() {  # name, env...
   local name=$1; shift
-  env "$@" timeout 600 python bench.py --config c4 --steps 4 --warmup 1 > $O/c4_$name.json 2> $O/c4_$name.err
+  env "$@" timeout 600 python bench.py --full --config c4 --steps 4 --warmup 1 > $O/c4_$name.json 2> $O/c4_$name.err
   python - "$name" "$O/c4_$name.json" <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ mkdir -p $O
 L=stheno.jl_amd/csrc
 cp $L/libsthenomi.so /tmp/lib_default.so
 line() {  # tag config
-  timeout 600 python bench.py --config $2 --steps 4 --warmup 1 --cpu-sample 0 --no-host-api --no-extras > $O/$2_$1.json 2> $O/$2_$1.err
+  timeout 600 python bench.py --full --config $2 --steps 4 --warmup 1 --cpu-sample 0 --no-host-api --no-extras > $O/$2_$1.json 2> $O/$2_$1.err
   python - "$1" "$2" "$O/$2_$1.json" <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ timeout 1500 python -m pytest tests -m gpu -q -x -p no:cacheprovider > $OUT/pyte
 grep -E "passed|failed|rc=" $OUT/pytest_gpu.log | tail -3
 timeout 900 python tools/gpu_midn_sweep.py 12288 16384 20480 > $OUT/midn_sweep.json 2> $OUT/midn_sweep.err; tail -3 $OUT/midn_sweep.err; grep -v "^{" $OUT/midn_sweep.json
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; tail -2 $OUT/bench_default.err
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; tail -2 $OUT/bench_default.err
 python - <<'PY'
 import json,os
 d=json.load(open(os.environ.get("GRAFT_REPO_ROOT","/root/repo")+"/gpurun_out/r06_call4/bench_default.json"))

@@ -8,7 +8,7 @@ timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest_
 grep -E "passed|failed|rc=|^FAILED|^ERROR" $OUT/pytest_gpu.log | tail -15
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; tail -2 $OUT/bench_default.err
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; tail -2 $OUT/bench_default.err
 python - <<'PY'
 import json,os
 d=json.load(open(os.environ.get("GRAFT_REPO_ROOT","/root/repo")+"/gpurun_out/r06_call5/bench_default.json"))

@@ -15,9 +15,9 @@ for v in st2 st3e st4e st3m st4m; do
   fi
   for c in c2 n4k n32k c3; do
     st=10; [ $c = n32k ] && st=4; [ $c = c3 ] && st=4
-    ( cd /tmp && timeout 300 python $R/bench.py --config $c --steps $st --warmup 2 --cpu-sample 0 --no-host-api --no-extras > $OUT/bench_${c}_$v.json 2> $OUT/bench_${c}_$v.err )
+    ( cd /tmp && timeout 300 python $R/bench.py --full --config $c --steps $st --warmup 2 --cpu-sample 0 --no-host-api --no-extras > $OUT/bench_${c}_$v.json 2> $OUT/bench_${c}_$v.err )
   done
-  ( cd /tmp && timeout 300 python $R/bench.py --config c5 --steps 3 --warmup 1 --cpu-sample 0 --no-host-api --no-extras > $OUT/bench_c5_$v.json 2> $OUT/bench_c5_$v.err )
+  ( cd /tmp && timeout 300 python $R/bench.py --full --config c5 --steps 3 --warmup 1 --cpu-sample 0 --no-host-api --no-extras > $OUT/bench_c5_$v.json 2> $OUT/bench_c5_$v.err )
   timeout 300 python tools/gpu_batch_time.py 4096 8192 > $OUT/batch_$v.json 2> $OUT/batch_$v.err
   python - $OUT $v <<'PY'
 import json, sys
