@@ -16,6 +16,8 @@ import AbstractGPs: logpdf, rand, posterior, elbo, FiniteGP, VFE
 const LIB = get(ENV, "STHENOMI_LIB", "libsthenomi.so")
 # include/sthenomi_batch.h (sgp_logpdf_grad_batch): a library of its own next to the product library, linked against it
 const LIB_BATCH = get(ENV, "STHENOMI_BATCH_LIB", joinpath(dirname(LIB), "libsthenomi_batch.so"))
+# include/sthenomi_extend.h (sgp_posterior_extend): likewise
+const LIB_EXTEND = get(ENV, "STHENOMI_EXTEND_LIB", joinpath(dirname(LIB), "libsthenomi_extend.so"))
 const SthenoFGP = FiniteGP{<:Union{GPPP,SthenoAbstractGP}}
 
 # ---- C structs (include/sthenomi.h) --------------------------------------------------------
@@ -303,6 +305,31 @@ function predict(p::MI355XPosterior, xs; want_cov = false)
         (Ptr{Cvoid}, Ref{CSpec}, Ref{CSpec}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
         p.handle, cr.c, ss.c, ms, μ, v, want_cov ? pointer(C) : C_NULL, max(n, 1)))
     return μ, v, C
+end
+# update_posterior(f_post, fx2, y2): the kept factor is extended by the rows of the new data (sgp_posterior_extend) instead of
+# factoring the stacked covariance again.  The posterior object does not keep its observation noise: the caller passes the
+# old one (Σy_old, in the form fx.Σy has: a ScalMat or a Diagonal); two equal ScalMats stay a scalar noise, anything else becomes a diagonal.  Dense noise
+# has no extension (condition on the stacked data with `posterior`).  reserve: points to size a reallocated factor for.
+stack_inputs(a, b) = BlockData(vcat(a isa BlockData ? a.X : [a], b isa BlockData ? b.X : [b]))
+function AbstractGPs.update_posterior(p::MI355XPosterior, fx::SthenoFGP, y::AbstractVector{<:Real}; Σy_old, reserve::Integer = 0)
+    k_old, nz_old = noise_args(Σy_old); k_new, nz_new = noise_args(fx.Σy)
+    @assert k_old != 2 && k_new != 2 "dense observation noise has no extension: use posterior on the stacked data"
+    n1 = length(p.δ); n2 = length(fx); xx = stack_inputs(p.x, fx.x)
+    sp = build_spec(p.prior, xx); m = collect(Float64, mean(p.prior, xx))
+    yd = vcat(p.δ .+ m[1:n1], collect(Float64, y))
+    scalar = k_old == 0 && k_new == 0 && nz_old[1] == nz_new[1]
+    kind = scalar ? 0 : 1
+    nz = scalar ? collect(Float64, nz_old) : vcat(k_old == 0 ? fill(nz_old[1], n1) : collect(Float64, nz_old),
+                                                  k_new == 0 ? fill(nz_new[1], n2) : collect(Float64, nz_new))
+    α = zeros(n1 + n2); lp = zeros(1)
+    GC.@preserve sp m nz yd α lp check(
+        @ccall LIB_EXTEND.sgp_posterior_extend(p.handle::Ptr{Cvoid}, sp.c::Ref{CSpec}, m::Ptr{Float64}, kind::Cint,
+                                               nz::Ptr{Float64}, yd::Ptr{Float64}, n2::Int64, Int64(reserve)::Int64,
+                                               α::Ptr{Float64}, lp::Ptr{Float64})::Cint)
+    post = MI355XPosterior(p.prior, xx, α, yd .- m, p.handle)     # the new object takes the factor over
+    p.handle = C_NULL                                              # (sgp_posterior_destroy(NULL) is a no-op)
+    finalizer(q -> ccall((:sgp_posterior_destroy, LIB), Cint, (Ptr{Cvoid},), q.handle), post)
+    return post
 end
 AbstractGPs.mean(p::MI355XPosterior, xs::AbstractVector) = predict(p, xs)[1]
 AbstractGPs.var(p::MI355XPosterior, xs::AbstractVector) = predict(p, xs)[2]

@@ -2242,14 +2242,7 @@ int sgp::drv_logpdf_grad_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* cons
 // ---------------------------------------------------------------------------------------
 // posterior
 // ---------------------------------------------------------------------------------------
-struct sgp_post {
-  sgp_ctx* ctx = nullptr;
-  long ctx_serial = 0;
-  long N = 0, n_pad = 0, m_tot = 0;
-  double* dA = nullptr;     // L (lower tiles) + row n_pad = (L^-1 (y - m))'
-  double* d_wall = nullptr; // inverse 16x16 diagonal blocks (INVD_STRIDE per 128-block)
-  sgp_mpost* mp = nullptr;  // non-null: the factor is sharded over the ranks of a multi-GPU context (multi.hip)
-};
+// (struct sgp_post: ctx.h -- extend.hip grows the kept factor)
 
 // rows <- rows * L^-T for `nrows` (multiple of 128) rows stored at R (ld = ldr), against the factor L
 // (ld = ldl) with its stored inverse 16x16 diagonal blocks.  Blocked left-looking: a 512-column
@@ -2356,7 +2349,7 @@ static int back_substitute_range(const double* Lv, long ld, const double* wall_v
 }
 static int back_substitute(const sgp_post* post, double* d_z /*n_pad, overwritten*/,
                            double* d_alpha, hipStream_t s) {
-  return back_substitute_range(post->dA, post->m_tot, post->d_wall, post->n_pad - TILE, 0, post->n_pad, d_z, d_alpha,
+  return back_substitute_range(post->dA, post->ld, post->d_wall, post->n_pad - TILE, 0, post->n_pad, d_z, d_alpha,
                                s);
 }
 
@@ -2408,6 +2401,10 @@ static int sgp_posterior_create_impl(sgp_ctx* ctx, const sgp_cov_spec* spec, con
   post->N = N;
   post->n_pad = n_pad;
   post->m_tot = m_tot;
+  post->ld = m_tot;
+  post->n_cap = n_pad;
+  post->noise_kind = noise_kind;
+  post->sigma2 = (noise_kind == SGP_NOISE_SCALAR && noise) ? noise[0] : 0.0;
   struct PostGuard {  // every error exit (incl. the SGP_HIP early returns) frees the 8 N^2-byte factor
     sgp_post* p;
     ~PostGuard() {
@@ -2431,7 +2428,7 @@ static int sgp_posterior_create_impl(sgp_ctx* ctx, const sgp_cov_spec* spec, con
     DevBuf dz, dal;
     if (dz.alloc(n_pad) || dal.alloc(n_pad)) return fail(-2);
     hipLaunchKernelGGL(copy_strided_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s,
-                       post->dA + n_pad, m_tot, n_pad, dz.p);
+                       post->dA + n_pad, post->ld, n_pad, dz.p);
     rc = back_substitute(post, dz.p, dal.p, s);
     if (rc) return fail(rc);
     SGP_HIP(hipStreamSynchronize(s));
@@ -2518,9 +2515,9 @@ extern "C" int sgp_posterior_predict(sgp_post* post, const sgp_cov_spec* cross,
   if (mean_s) CHECK_RC(dms.upload(mean_s, Ns));
   SGP_HIP(hipMemsetAsync(dV.p, 0, sizeof(double) * ns_pad * n_pad, s));
   CHECK_RC(assemble(gc.ds, dV.p, ns_pad, 0, ns_pad / TILE, 0, n_pad / TILE, 0, -1, 0.0, nullptr, s));
-  CHECK_RC(row_trsm(ctx, dV.p, ns_pad, ns_pad, post->dA, post->m_tot, post->d_wall, n_pad, s));
+  CHECK_RC(row_trsm(ctx, dV.p, ns_pad, ns_pad, post->dA, post->ld, post->d_wall, n_pad, s));
   return predict_common(ctx, gc.ds, gp.ds, mean_s ? dms.p : nullptr, Ns, ns_pad, dV.p, n_pad,
-                        post->dA + n_pad, post->m_tot, post->N, mean_out, var_out, cov_out, ldcov,
+                        post->dA + n_pad, post->ld, post->N, mean_out, var_out, cov_out, ldcov,
                         0.0, nullptr, s);
 }
 
@@ -2553,10 +2550,10 @@ extern "C" int sgp_posterior_predict_explicit(sgp_post* post, const double* cros
   SGP_HIP(hipMemsetAsync(dV.p, 0, sizeof(double) * ns_pad * n_pad, s));
   SGP_HIP(hipMemcpy2DAsync(dV.p, sizeof(double) * ns_pad, cross, sizeof(double) * ldc, sizeof(double) * Ns, (size_t)N,
                            hipMemcpyHostToDevice, s));
-  CHECK_RC(row_trsm(ctx, dV.p, ns_pad, ns_pad, post->dA, post->m_tot, post->d_wall, n_pad, s));
+  CHECK_RC(row_trsm(ctx, dV.p, ns_pad, ns_pad, post->dA, post->ld, post->d_wall, n_pad, s));
   if (mean_out) {
     CHECK_RC(dmu.alloc(Ns));
-    CHECK_RC(launch_gemv_rows(dV.p, ns_pad, Ns, N, post->dA + n_pad, post->m_tot, mean_s ? dms.p : nullptr, dmu.p, s));
+    CHECK_RC(launch_gemv_rows(dV.p, ns_pad, Ns, N, post->dA + n_pad, post->ld, mean_s ? dms.p : nullptr, dmu.p, s));
   }
   if (var_out) {
     CHECK_RC(dprior.upload(prior_var, Ns));
@@ -3919,6 +3916,16 @@ int drv_diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStream
   return diag_of_spec(ctx, ds, d_out, s);
 }
 int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) { return dspec_create(ctx, sp, out); }
+int drv_row_trsm_block(double* R, long ldr, long nrows, const double* L, long ldl, const double* d_invall, long c, long w,
+                       hipStream_t s) {
+  return row_trsm_block(R, ldr, nrows, L, ldl, d_invall, c, w, 512, s);
+}
+int drv_chol_sub(sgp_ctx* ctx, double* A, long ld, long n_cols, long m_rows, double* d_wall, hipStream_t s) {
+  return chol_bordered(ctx, A, ld, n_cols, m_rows, d_wall, s);
+}
+int drv_fetch_info(sgp_ctx* ctx, hipStream_t s) { return fetch_info(ctx, s); }
+bool drv_ctx_is_live(const sgp_ctx* ctx, long serial) { return ctx_is_live(ctx, serial); }
+int drv_with_df_fallback(sgp_ctx* ctx, const std::function<int()>& run) { return with_df_fallback(ctx, run); }
 int drv_conv_geom(sgp_ctx* ctx, int h, int w, int ph, int pw, int32_t* id_out) {
   CHECK_ARG(ctx && id_out, "sgp_conv_geom: NULL argument");
   CtxScope scope(ctx);

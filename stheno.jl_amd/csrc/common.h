@@ -305,7 +305,7 @@ int launch_gemm_nt_splitk(const double* A, long lda, const double* B, long ldb, 
                           long M, long Nc, long K, int nsplit, long part_stride, int lower_only,
                           hipStream_t s);
 int launch_splitk_reduce(const double* part, long part_stride, int nsplit, double* C, long ldc, long M,
-                         long Nc, double alpha, double beta, int lower_only, hipStream_t s, long K = 0);
+                         long Nc, double alpha, double beta, int lower_only, hipStream_t s, long K = 0, long ld_part = 0);
 long splitk_sub(long M, long K);                 // further k split of the Gram product's leftover tiles (gemm_nt.hip)
 long splitk_slabs(long M, long K, int nsplit);   // slabs launch_gemm_nt_splitk writes for this shape
 

@@ -195,6 +195,21 @@ struct sgp_ctx {
   size_t stage_cap = 0;
 };
 
+// a kept Cholesky factor (sgp_posterior_create; capi.hip) -- extend.hip grows it (include/sthenomi_extend.h)
+struct sgp_post {
+  sgp_ctx* ctx = nullptr;
+  long ctx_serial = 0;
+  long N = 0, n_pad = 0, m_tot = 0;
+  // the buffer: element (r, c) at dA[r + c * ld], n_cap columns allocated.  ld == m_tot and n_cap == n_pad for a posterior
+  // that was never extended; an extended one may sit in a buffer sized for more points (reserve_n)
+  long ld = 0, n_cap = 0;
+  int noise_kind = 0;       // what the posterior was created / last extended with; sigma2: the value of a scalar noise
+  double sigma2 = 0.0;
+  double* dA = nullptr;     // L (lower tiles) + row n_pad = (L^-1 (y - m))'
+  double* d_wall = nullptr; // inverse 16x16 diagonal blocks (INVD_STRIDE per 128-block), n_cap / 128 blocks
+  sgp_mpost* mp = nullptr;  // non-null: the factor is sharded over the ranks of a multi-GPU context (multi.hip)
+};
+
 namespace sgp {
 
 extern thread_local sgp_ctx* tl_ctx;  // the context whose entry point this thread is inside

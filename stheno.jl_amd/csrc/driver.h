@@ -28,6 +28,23 @@ int drv_row_trsm(sgp_ctx* ctx, double* R, long ldr, long nrows, const double* L,
 // wall_v + b * INVD_STRIDE; d_z / d_alpha are indexed globally, rows up to n_end are read.
 int drv_back_substitute(const double* Lv, long ld, const double* wall_v, long k_first, long k_last, long n_end,
                         double* d_z, double* d_alpha, hipStream_t s);
+// the columns [c, c + w) of a row block whose columns left of c are solved and applied (row_trsm's in-block part)
+int drv_row_trsm_block(double* R, long ldr, long nrows, const double* L, long ldl, const double* d_invall, long c, long w,
+                       hipStream_t s);
+// the bordered factorisation (capi.hip: chol_bordered, dense) of the sub-matrix whose element (0, 0) is A[0]: n_cols columns
+// over m_rows rows; d_wall (offset by the caller) receives the inverse diagonal blocks, ctx->d_slots[0 .. n_cols / 128) the
+// logdet contributions, *ctx->d_info the failing minor counted from the sub-matrix's first column
+int drv_chol_sub(sgp_ctx* ctx, double* A, long ld, long n_cols, long m_rows, double* d_wall, hipStream_t s);
+int drv_fetch_info(sgp_ctx* ctx, hipStream_t s);   // *ctx->d_info after draining s (notes a dataflow time-out on ctx)
+bool drv_ctx_is_live(const sgp_ctx* ctx, long serial);
+// run() once more on the launch-based schedule when it came back with a dataflow time-out (capi.hip: with_df_fallback)
+int drv_with_df_fallback(sgp_ctx* ctx, const std::function<int()>& run);
+// update_posterior (include/sthenomi_extend.h: sgp_posterior_extend, forwarded from libsthenomi_extend.so) -- extend.hip
+int drv_posterior_extend(sgp_post* post, const sgp_cov_spec* spec_all, const double* mean_all, int noise_kind,
+                         const double* noise, const double* y_all, int64_t n_new, int64_t reserve_n, double* alpha_out,
+                         double* logpdf_out);
+// times the row solve of `tile_rows` 128-row tiles against the kept factor by one schedule (sthenomi_extend_bench.h: sgp_bench_extend_row_solve)
+int drv_extend_row_solve_ms(sgp_post* post, int64_t tile_rows, int schedule, int reps, double* ms_out);
 int drv_diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStream_t s);
 int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out);   // caller holds the context
 // register a patch geometry on ctx (include/sthenomi_conv.h: sgp_conv_geom, whose C entry point in libsthenomi_conv.so

@@ -1101,7 +1101,7 @@ int launch_gemm_nt_splitk(const double* A, long lda, const double* B, long ldb, 
 // tiles split further): whole tiles sum slabs 0, sub, 2 sub, ..., leftover tiles all 8 * sub slabs -- ascending k either way.
 __global__ void splitk_reduce_kernel(const double* part, long part_stride, int nsplit, double* C,
                                      long ldc, long M, long Nc, double alpha, double beta,
-                                     int lower_only, int sub, long full) {
+                                     int lower_only, int sub, long full, long ldp) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= M * Nc) return;
   long r = idx % M, c = idx / M;
@@ -1111,9 +1111,9 @@ __global__ void splitk_reduce_kernel(const double* part, long part_stride, int n
   if (sub > 1) {
     const bool whole = tr * (tr + 1) / 2 + tc < full;
     const int step = whole ? sub : 1;
-    for (int k = 0; k < nsplit * sub; k += step) s += part[k * part_stride + r + c * ldc];
+    for (int k = 0; k < nsplit * sub; k += step) s += part[k * part_stride + r + c * ldp];
   } else {
-    for (int k = 0; k < nsplit; ++k) s += part[k * part_stride + r + c * ldc];
+    for (int k = 0; k < nsplit; ++k) s += part[k * part_stride + r + c * ldp];
   }
   double* p = C + r + c * ldc;
   double old = (beta == 0.0) ? 0.0 : beta * (*p);
@@ -1121,13 +1121,15 @@ __global__ void splitk_reduce_kernel(const double* part, long part_stride, int n
 }
 
 // K: the contraction length the slabs came from (launch_gemm_nt_splitk's K; 0 = plain nsplit slabs)
+// ld_part: the leading dimension of the slabs (0: they share C's)
 int launch_splitk_reduce(const double* part, long part_stride, int nsplit, double* C, long ldc, long M,
-                         long Nc, double alpha, double beta, int lower_only, hipStream_t s, long K) {
+                         long Nc, double alpha, double beta, int lower_only, hipStream_t s, long K, long ld_part) {
   long tot = M * Nc;
   const long sub = (K > 0 && lower_only && nsplit == 8 && M == Nc) ? splitk_sub(M, K) : 1;
   const long n_t = M / TILE, tiles = n_t * (n_t + 1) / 2;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
-                     part_stride, nsplit, C, ldc, M, Nc, alpha, beta, lower_only, (int)sub, tiles / 64 * 64);
+                     part_stride, nsplit, C, ldc, M, Nc, alpha, beta, lower_only, (int)sub, tiles / 64 * 64,
+                     ld_part > 0 ? ld_part : ldc);
   SGP_HIP(hipGetLastError());
   return 0;
 }

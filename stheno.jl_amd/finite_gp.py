@@ -613,6 +613,29 @@ def _concat(xs, zs):
     return BlockData(list(xs.X) + list(zb))
 
 
+def _stack_observations(p1, fx2, y2):
+    """(x, Sigma_y, y) of the data a posterior was conditioned on followed by the observations fx2 / y2: the old points in
+    their old block order, the new ones in further blocks.  Two equal scalar noises stay a scalar, a dense Sigma_y on either
+    side makes the stacked noise dense (block diagonal), anything else a diagonal."""
+    if p1.noise is None:
+        raise NotImplementedError("this posterior does not carry its observation model")
+    n1, n2 = len(p1.x), len(fx2)
+    a1, a2 = np.asarray(p1.noise, dtype=np.float64), np.asarray(fx2.noise, dtype=np.float64)
+    if a1.ndim > 1 or a2.ndim > 1:
+        # a dense Sigma_y on either side: the stacked observation noise is block diagonal (dense noise kind)
+        noise = np.zeros((n1 + n2, n1 + n2))
+        noise[:n1, :n1] = _noise_dense(a1, n1)
+        noise[n1:, n1:] = _noise_dense(a2, n2)
+    elif a1.ndim == 0 and a2.ndim == 0 and float(a1) == float(a2):
+        noise = float(a1)
+    else:
+        noise = np.concatenate([_noise_diag(a1, n1), _noise_diag(a2, n2)])
+    x1 = p1.x if isinstance(p1.x, BlockData) else BlockData([p1.x])
+    xx = _concat(x1, fx2.x)
+    yy = np.concatenate([p1.y, np.asarray(y2, dtype=np.float64).ravel()])
+    return xx, noise, yy
+
+
 def posterior(fx, y, y_vfe=None):
     """posterior(fx, y)  |  posterior(VFE(fz), fx, y)  |  posterior(SparseFiniteGP, y)"""
     if isinstance(fx, VFE):                  # posterior(VFE(fz), fx, y)  (sparse_finite_gp.jl:60-62)
@@ -623,24 +646,8 @@ def posterior(fx, y, y_vfe=None):
         # Sequential conditioning (AbstractGPs: posterior(f_post(x2, s2), y2) is again a PosteriorGP): the
         # posterior given (x1, y1) and then (x2, y2) IS the prior conditioned on the stacked data, which is
         # one factorisation of the joint covariance on the device instead of a Schur-complement update.
-        p1 = fx.f
-        if p1.noise is None:
-            raise NotImplementedError("this posterior does not carry its observation model")
-        n1, n2 = len(p1.x), len(fx)
-        a1, a2 = np.asarray(p1.noise, dtype=np.float64), np.asarray(fx.noise, dtype=np.float64)
-        if a1.ndim > 1 or a2.ndim > 1:
-            # a dense Sigma_y on either side: the stacked observation noise is block diagonal (dense noise kind)
-            noise = np.zeros((n1 + n2, n1 + n2))
-            noise[:n1, :n1] = _noise_dense(a1, n1)
-            noise[n1:, n1:] = _noise_dense(a2, n2)
-        elif a1.ndim == 0 and a2.ndim == 0 and float(a1) == float(a2):
-            noise = float(a1)
-        else:
-            noise = np.concatenate([_noise_diag(a1, n1), _noise_diag(a2, n2)])
-        x1 = p1.x if isinstance(p1.x, BlockData) else BlockData([p1.x])
-        xx = _concat(x1, fx.x)
-        yy = np.concatenate([p1.y, np.asarray(y, dtype=np.float64).ravel()])
-        return posterior(FiniteGP(p1.prior, xx, noise), yy)
+        xx, noise, yy = _stack_observations(fx.f, fx, y)
+        return posterior(FiniteGP(fx.f.prior, xx, noise), yy)
     if not _is_prior(fx.f):
         # a process that is not a prior Stheno process but answers mean / var / cov -- the approximate (VFE) posterior, which the
         # reference returns as an ordinary AbstractGP (sparse_finite_gp.jl:60-62): conditioned through explicit covariances
@@ -659,6 +666,42 @@ def posterior(fx, y, y_vfe=None):
     # path (one fp32 factorisation with x* riding along as bordered rows) is the explicit posterior_mean_and_var_f32.
     post._ensure()                 # PosDefException here, as `cholesky` throws in the reference's posterior
     return post
+
+
+def update_posterior(post, fx2, y2, reserve=None):
+    """update_posterior(f_post, fx2, y2) [AbstractGPs]: the posterior given the data of `post` AND the observations y2 of
+    fx2 = f(x2, s2), by extending the kept Cholesky factor with the rows of the new data (sgp_posterior_extend:
+    O(N^2 k + N k^2 + k^3) for k new points) instead of factoring the stacked covariance from scratch.
+
+    Returns a PosteriorGP on the stacked data that TAKES OVER the factor in HBM; `post` stays usable -- it rebuilds a factor
+    of its own the next time it is asked something.  reserve: the number of points the factor buffer is sized for when it
+    has to grow (a loop that keeps adding points passes the size it will reach and pays one reallocation).
+    A dense Sigma_y on either side or a multi-GPU context go through the stacked one-shot `posterior` -- the same posterior, to rounding.  A stacked covariance that is not positive definite raises
+    PosDefException with the failing leading minor; `post` is then exactly what it was."""
+    if not isinstance(post, PosteriorGP):
+        raise TypeError("update_posterior extends an exact PosteriorGP (posterior(fx, y))")
+    if not isinstance(fx2, FiniteGP) or not (fx2.f is post.prior or fx2.f is post):
+        raise ValueError("update_posterior: fx2 must be the posterior's prior process (or the posterior itself) at the new points")
+    xx, noise, yy = _stack_observations(post, fx2, y2)
+    n = len(yy)
+    if len(fx2) != n - len(post.y):
+        raise ValueError("length(y2) != length(fx2)")
+    if np.ndim(noise) > 1 or getattr(_ctx(), "is_multi", False):
+        return posterior(FiniteGP(post.prior, xx, noise), yy)
+    spec = _prior_spec(post.prior, xx)
+    m = _f64(mean_vector(post.prior, xx))
+    yy = _f64(yy)
+    kind, nbuf = _lib._noise_args(noise, n)
+    alpha, lp = np.zeros(n), np.zeros(1)
+    reserve_n = 0 if reserve is None else max(int(reserve), n)
+    h = post._ensure()
+    rc = _ctx().extend.sgp_posterior_extend(h, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf), _lib.dptr(yy), n - len(post.y),
+                                            reserve_n, _lib.dptr(alpha), _lib.dptr(lp))
+    _lib.check(rc, "sgp_posterior_extend")      # rc > 0: PosDefException(info); the old posterior is untouched
+    post._h = None                              # the new object owns the factor; the old one rebuilds its own on demand
+    new = PosteriorGP(post.prior, xx, h, alpha, yy - m, noise, yy.copy(), mean_x=m)
+    new.logpdf_y = float(lp[0])                 # logpdf(f(x_all, Sigma_y), y_all): the call computes it on the way
+    return new
 
 
 def posterior_mean_and_var_f32(fx, y, xs):

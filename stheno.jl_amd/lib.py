@@ -16,6 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi.so")
 BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_bench.so")
 BATCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_batch.so")
+EXTEND_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend.so")
+EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
 
@@ -180,6 +182,17 @@ _SIGS_BATCH = {
                                         C.POINTER(_D), C.POINTER(_D), C.POINTER(C.c_int)]),
 }
 
+# include/sthenomi_extend.h: extending a kept factor with new data, exported by libsthenomi_extend.so (it links against the
+# product library and works on its posteriors) -- update_posterior reaches it through extend_lib() / Context.extend
+_SIGS_EXTEND = {
+    "sgp_posterior_extend": (C.c_int, [_P, C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, C.c_int64, C.c_int64, _D, _D]),
+}
+
+# include/sthenomi_extend_bench.h: the measurement hook of the extension (libsthenomi_extend_bench.so; tools and tests only)
+_SIGS_EXTEND_BENCH = {
+    "sgp_bench_extend_row_solve": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D]),
+}
+
 
 # include/sthenomi_conv.h: patch-geometry registration, exported by libsthenomi_conv.so (it links against the product library
 # and works on its contexts) -- Spec.bind reaches it through conv_lib()
@@ -215,6 +228,11 @@ def stencil_symbols():
 def conv_symbols():
     """Names include/sthenomi_conv.h declares: the entry points of libsthenomi_conv.so."""
     return sorted(_SIGS_CONV)
+
+
+def extend_symbols():
+    """Names include/sthenomi_extend.h declares: the entry points of libsthenomi_extend.so."""
+    return sorted(_SIGS_EXTEND)
 
 
 def batch_symbols():
@@ -272,6 +290,48 @@ def batch_lib():
             fn.restype = res
             fn.argtypes = args
         _batch = lib
+        return lib
+
+
+_extend = None
+
+
+def extend_lib():
+    """dlopen libsthenomi_extend.so (include/sthenomi_extend.h) after the product library it links against."""
+    global _extend
+    load()
+    with _lib_lock:
+        if _extend is not None:
+            return _extend
+        if not os.path.exists(EXTEND_LIB_PATH):
+            raise SthenoMIError(f"{EXTEND_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(EXTEND_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_EXTEND.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _extend = lib
+        return lib
+
+
+_extend_bench = None
+
+
+def extend_bench_lib():
+    """dlopen libsthenomi_extend_bench.so (include/sthenomi_extend_bench.h); nothing on a product path loads it."""
+    global _extend_bench
+    load()
+    with _lib_lock:
+        if _extend_bench is not None:
+            return _extend_bench
+        if not os.path.exists(EXTEND_BENCH_LIB_PATH):
+            raise SthenoMIError(f"{EXTEND_BENCH_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(EXTEND_BENCH_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_EXTEND_BENCH.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _extend_bench = lib
         return lib
 
 
@@ -391,6 +451,11 @@ class Context:
     def batch(self):
         """libsthenomi_batch.so (sthenomi_batch.h): `ctx.batch.sgp_logpdf_grad_batch(ctx.handle, ...)`"""
         return batch_lib()
+
+    @property
+    def extend(self):
+        """libsthenomi_extend.so (sthenomi_extend.h): `ctx.extend.sgp_posterior_extend(post_handle, ...)`"""
+        return extend_lib()
 
     @property
     def ndev(self):
