@@ -33,8 +33,9 @@ __device__ __forceinline__ double mfma44_f64(double a, double b, double c) {
 // ---- fp64 elementary functions of the covariance kernels -----------------------------------------
 // The assembly kernel is fp64-VALU bound: libm's exp / sqrt / a true division
 // cost it ~100 issue slots per Matern-5/2 entry.  These straight-line versions (no special-case
-// branches; arguments are known to be <= 0 resp. >= 0) are accurate to ~1 ulp, which is far inside
-// the 1e-12 entry-wise parity the tests hold against the CPU oracle.
+// branches; arguments are known to be <= 0 resp. >= 0) are accurate to ~1 ulp: tests/test_gpu_kernel_formulas.py holds
+// the kernels built from them to a 60-digit table (SE within 2 ulp of the truth, subnormal results included; the
+// measured maxima are in docs/04_oracle_and_parity.md).
 // exp(x) for x <= 0: n = rint(x log2 e), r = x - n ln2 (two-part), degree-13 Taylor on |r| <= 0.347
 // (remainder 4e-18), scaled by 2^n with v_ldexp_f64 (correct down to denormals / 0).
 __device__ __forceinline__ double exp_nonpos(double x) {
@@ -60,9 +61,12 @@ __device__ __forceinline__ double exp_nonpos(double x) {
 }
 // sqrt(a) for a >= 0: v_rsq_f64 seed (~2^-26), one Newton step on 1/sqrt, then one Newton step on the
 // root itself (quadratic: rounding-level result).  a is clamped to 1e-300 so that a == 0 needs no
-// branch: the result is then 1e-150, which every kernel maps to exactly kappa(0) (1 + 1e-150 == 1).
+// branch: the result is then 1e-150, which every kernel maps to exactly kappa(0) (1 + 1e-150 == 1).  It is clamped
+// to 1e300 at the top as well: a squared distance that overflowed (a sentinel coordinate) gives rsq(inf) = 0 and with
+// it inf * 0 = NaN in the Newton step, and the Matern-5/2 polynomial overflows from l = 1.3e154; at 1e150 every kernel
+// is an exact 0 through exp_nonpos.  No finite argument below 1e300 changes a bit.
 __device__ __forceinline__ double sqrt_nonneg(double a) {
-  a = fmax(a, 1e-300);
+  a = fmin(fmax(a, 1e-300), 1e300);
   double r = __builtin_amdgcn_rsq(a);
   r = r * fma(-0.5 * a, r * r, 1.5);
   double d = a * r;

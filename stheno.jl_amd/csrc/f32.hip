@@ -32,16 +32,18 @@ constexpr int LDF = 128 + 4;     // LDS leading dimension (floats) of a 128-row 
 
 enum { K_SE = 0, K_M12 = 1, K_M32 = 2, K_M52 = 3, K_WHITE = 4, K_CONST = 5 };
 
+// d2 is clamped to 1e30 under the roots: a squared distance that overflowed float32 makes l = inf and the Matern
+// polynomials inf * __expf(-inf) = NaN; at a distance of 1e15 every kernel is an exact 0, and no smaller d2 changes a bit
 __device__ __forceinline__ float kern_f32(int kind, float d2, float param) {
   switch (kind) {
     case K_SE: return __expf(-0.5f * d2);
-    case K_M12: return __expf(-sqrtf(d2));
+    case K_M12: return __expf(-sqrtf(fminf(d2, 1e30f)));
     case K_M32: {
-      float l = 1.7320508f * sqrtf(d2);
+      float l = 1.7320508f * sqrtf(fminf(d2, 1e30f));
       return (1.0f + l) * __expf(-l);
     }
     case K_M52: {
-      float l = 2.236068f * sqrtf(d2);
+      float l = 2.236068f * sqrtf(fminf(d2, 1e30f));
       return fmaf(l, fmaf(l, 0.33333334f, 1.0f), 1.0f) * __expf(-l);
     }
     case K_WHITE: return d2 == 0.0f ? 1.0f : 0.0f;

@@ -18,8 +18,10 @@ namespace sgp {
 enum { G_SE = 0, G_M12 = 1, G_M32 = 2, G_M52 = 3, G_WHITE = 4, G_CONST = 5 };
 constexpr int GRAD_MAXT = 8;  // terms per launch
 
-// k and d k / d g (input scale, at g = 1) from the squared distance
+// k and d k / d g (input scale, at g = 1) from the squared distance.  d2 is clamped to 1e150: every kernel and
+// derivative is an exact 0 long before, and a squared distance that overflowed would make them inf * 0 = NaN
 __device__ __forceinline__ void kern_and_dscale(int kind, double d2, double param, double& k, double& dk) {
+  d2 = fmin(d2, 1e150);
   switch (kind) {
     case G_SE:
       k = exp(-0.5 * d2);
@@ -567,6 +569,7 @@ int launch_vfe_gxz(double* E, long ld, const double* delta, const double* ut, co
 // same input array are ordered on one stream.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ double kern_dd2(int kind, double d2, double param) {
+  d2 = fmin(d2, 1e150);   // (as kern_and_dscale)
   switch (kind) {
     case G_SE:
       return -0.5 * exp(-0.5 * d2);

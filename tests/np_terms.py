@@ -9,7 +9,7 @@ from stheno_jl_amd import lib as L
 
 
 def _kern(kind, d2, param):
-    d = np.sqrt(d2)
+    d = np.sqrt(np.minimum(d2, 1e300))      # (sqrt_nonneg's upper clamp: a squared distance that overflowed stays finite)
     if kind == L.SE:
         return np.exp(-0.5 * d2)
     if kind == L.MATERN12:
