@@ -481,7 +481,7 @@ def test_input_dimension_limit_is_reported():
         al = Ci @ yd
         Gm = 0.5 * (np.outer(al, al) - Ci)
         (ec, es), = _oracle_term_grads(g["_spec"], Gm)
-        assert abs(gc[0] - ec) <= 1e-8 * max(1.0, abs(ec)) and abs(gs[0] - es) <= 2e-6 * max(1.0, abs(es))
+        assert abs(gc[0] - ec) <= 1e-8 * max(1.0, abs(ec)) and abs(gs[0] - es) <= 1e-8 * max(1.0, abs(es))
     y60 = rng.standard_normal(60)
     for D in (17, 40):
         X = np.asfortranarray(rng.standard_normal((D, 60)) / np.sqrt(D))
@@ -516,7 +516,9 @@ def test_input_dimension_limit_is_reported():
 
 # ---- reverse-mode gradient of logpdf -------------------------------------------
 def _oracle_term_grads(spec, G):
-    """sum_ij G_ij d C_ij / d theta for every raw spec term, with NumPy (tests/np_terms.py kernels)."""
+    """sum_ij G_ij d C_ij / d theta for every raw spec term, with NumPy (tests/np_terms.py kernels, the analytic
+    derivative w.r.t. the input scale of tests/grad_truth.py)."""
+    import grad_truth
     import np_terms
     roff = np.concatenate([[0], np.cumsum(spec.row_len)])
     coff = np.concatenate([[0], np.cumsum(spec.col_len)])
@@ -525,8 +527,7 @@ def _oracle_term_grads(spec, G):
         X, Y = spec.inputs[ri], spec.inputs[ci]
         d2 = ((X[:, :, None] - Y[:, None, :]) ** 2).sum(0)
         k = np_terms._kern(kind, d2, param)
-        h = 1e-6
-        dk = (np_terms._kern(kind, d2 * (1 + h) ** 2, param) - np_terms._kern(kind, d2 * (1 - h) ** 2, param)) / (2 * h)
+        dk = grad_truth.kappa(kind, d2, param, np.float64)[2]        # analytic d kappa(g x, g x') / dg at g = 1
         w = G[roff[I]:roff[I + 1], coff[J]:coff[J + 1]]
         if rs is not None:
             w = w * rs[:, None]
@@ -565,7 +566,7 @@ def test_logpdf_gradient_terms_noise_y_mean(recipe):
         assert len(exp) == g["_spec"].n_terms
         for t, (ec, es) in enumerate(exp):
             assert abs(gc[t] - ec) <= 1e-8 * max(1.0, abs(ec)), (t, gc[t], ec)
-            assert abs(gs[t] - es) <= 2e-6 * max(1.0, abs(es)), (t, gs[t], es)   # FD reference for dk/dg
+            assert abs(gs[t] - es) <= 1e-8 * max(1.0, abs(es)), (t, gs[t], es)
 
 
 def test_logpdf_gradient_matches_finite_differences_of_hyperparameters():

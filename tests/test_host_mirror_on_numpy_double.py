@@ -78,6 +78,15 @@ for _name in [n for n in dir(TD) if n.startswith("test_")]:
 del _name
 
 
+# the gradient bodies against the extended-precision truth (tests/test_gpu_grad_truth.py): the double is a second,
+# independent float64 implementation (LAPACK, GEMM-free kernels of its own), so this checks the bodies and their bounds
+import test_gpu_grad_truth as GT  # noqa: E402
+
+for _name in [n for n in dir(GT) if n.startswith("test_")]:
+    globals()[_name] = getattr(GT, _name)
+del _name
+
+
 def test_logpdf_batch_host_mirror_marshalling():
     """Round 6: `logpdf_batch(fxs, ys)` -> sgp_logpdf_batch: the arrays of spec / mean / noise / y pointers the host builds, the
     NaN + info convention for a member that is not positive definite, and the member-by-member route for mixed noise kinds --
