@@ -16,6 +16,8 @@ import AbstractGPs: logpdf, rand, posterior, elbo, FiniteGP, VFE
 const LIB = get(ENV, "STHENOMI_LIB", "libsthenomi.so")
 # include/sthenomi_batch.h (sgp_logpdf_grad_batch): a library of its own next to the product library, linked against it
 const LIB_BATCH = get(ENV, "STHENOMI_BATCH_LIB", joinpath(dirname(LIB), "libsthenomi_batch.so"))
+# (include/sthenomi_pool.h: sgp_logpdf_pool / sgp_logpdf_grad_pool live in libsthenomi_pool.so, which links against LIB)
+const LIB_POOL = get(ENV, "STHENOMI_POOL_LIB", joinpath(dirname(LIB), "libsthenomi_pool.so"))
 # include/sthenomi_extend.h (sgp_posterior_extend): likewise
 const LIB_EXTEND = get(ENV, "STHENOMI_EXTEND_LIB", joinpath(dirname(LIB), "libsthenomi_extend.so"))
 const SthenoFGP = FiniteGP{<:Union{GPPP,SthenoAbstractGP}}
@@ -410,6 +412,74 @@ function logpdf_and_gradient_batch(fxs::AbstractVector{<:SthenoFGP}, ys::Abstrac
     res = [infos[b] != 0 ? failed(infos[b]) :
            (logpdf = lp[b], y = gy[b], mean = gm[b], noise = gn[b], coef = gc[b], inscale = gs[b]) for b in 1:B]
     return res, infos
+end
+
+# Members of DIFFERENT sizes and noise kinds in one call (include/sthenomi_pool.h): folds that straddle a tile boundary, a
+# learning curve, one GP per series.  The scalar / diagonal-Σy members are factored by ONE ragged launch of the dataflow kernel,
+# each in the geometry of its own call; a dense-Σy member runs through its own call inside the library.  Every value is
+# bit-equal to the member's own `logpdf`; NaN + info for a member that is not positive definite.  Third result: what the call
+# did (launches, pooled members, single members, distinct padded sizes).
+struct PoolReport
+    pool_launches::Int32
+    pooled_members::Int32
+    single_members::Int32
+    distinct_sizes::Int32
+end
+
+function logpdf_pool(fxs::AbstractVector{<:SthenoFGP}, ys::AbstractVector{<:AbstractVector{<:Real}})
+    length(fxs) == length(ys) || throw(DimensionMismatch("logpdf_pool: one y per model"))
+    B = length(fxs)
+    ms = [collect(Float64, mean(fx.f, fx.x)) for fx in fxs]
+    for (fx, y, m) in zip(fxs, ys, ms)        # checked here: the library reads length(fx) values behind every pointer
+        length(y) == length(fx) || throw(DimensionMismatch("length(y) != length(fx)"))
+        length(m) == length(fx) || throw(DimensionMismatch("length(mean(fx)) != length(fx)"))
+    end
+    B == 0 && return Float64[], Cint[], PoolReport(0, 0, 0, 0)
+    sps = [build_spec(fx.f, fx.x) for fx in fxs]
+    kinds = Cint[noise_args(fx.Σy)[1] for fx in fxs]
+    nzs = [noise_args(fx.Σy)[2] for fx in fxs]
+    yv = [collect(Float64, y) for y in ys]
+    specs = [Ptr{CSpec}(pointer_from_objref(sp)) for sp in sps]     # (`c` is the first field of the mutable Spec: its address)
+    out = zeros(B); infos = zeros(Cint, B); rep = Ref(PoolReport(0, 0, 0, 0))
+    pms = pointer.(ms); pnz = pointer.(nzs); pys = pointer.(yv)
+    GC.@preserve sps ms nzs yv specs kinds out infos pms pnz pys rep check(
+        @ccall LIB_POOL.sgp_logpdf_pool(ctx()::Ptr{Cvoid}, B::Cint, specs::Ptr{Ptr{CSpec}}, pms::Ptr{Ptr{Float64}},
+            kinds::Ptr{Cint}, pnz::Ptr{Ptr{Float64}}, pys::Ptr{Ptr{Float64}}, out::Ptr{Float64}, infos::Ptr{Cint},
+            rep::Ref{PoolReport})::Cint)
+    return out, infos, rep[]
+end
+
+# ... and value plus gradient (sgp_logpdf_grad_pool): every member's result is bit-equal to its own `logpdf_and_gradient`.
+function logpdf_and_gradient_pool(fxs::AbstractVector{<:SthenoFGP}, ys::AbstractVector{<:AbstractVector{<:Real}})
+    length(fxs) == length(ys) || throw(DimensionMismatch("logpdf_and_gradient_pool: one y per model"))
+    B = length(fxs)
+    ms = [collect(Float64, mean(fx.f, fx.x)) for fx in fxs]
+    for (fx, y, m) in zip(fxs, ys, ms)        # checked here: the library reads length(fx) values behind every pointer
+        length(y) == length(fx) || throw(DimensionMismatch("length(y) != length(fx)"))
+        length(m) == length(fx) || throw(DimensionMismatch("length(mean(fx)) != length(fx)"))
+    end
+    B == 0 && return [], Cint[], PoolReport(0, 0, 0, 0)
+    failed(info) = (logpdf = NaN, y = Float64[], mean = Float64[], noise = Float64[], coef = Float64[], inscale = Float64[])
+    kinds = Cint[noise_args(fx.Σy)[1] for fx in fxs]
+    @assert all(k != 2 for k in kinds) "dense observation noise has no device gradient"
+    sps = [build_spec(fx.f, fx.x) for fx in fxs]
+    nzs = [noise_args(fx.Σy)[2] for fx in fxs]
+    yv = [collect(Float64, y) for y in ys]
+    gy = [zeros(length(y)) for y in yv]; gm = [zeros(length(y)) for y in yv]
+    gn = [zeros(k == 1 ? length(y) : 1) for (k, y) in zip(kinds, yv)]
+    gc = [zeros(max(1, length(sp.keep[5]))) for sp in sps]; gs = [zeros(max(1, length(sp.keep[5]))) for sp in sps]
+    specs = [Ptr{CSpec}(pointer_from_objref(sp)) for sp in sps]
+    lp = zeros(B); infos = zeros(Cint, B); rep = Ref(PoolReport(0, 0, 0, 0))
+    pms = pointer.(ms); pnz = pointer.(nzs); pys = pointer.(yv)
+    pgy = pointer.(gy); pgm = pointer.(gm); pgn = pointer.(gn); pgc = pointer.(gc); pgs = pointer.(gs)
+    GC.@preserve sps ms nzs yv gy gm gn gc gs specs kinds lp infos pms pnz pys pgy pgm pgn pgc pgs rep check(
+        @ccall LIB_POOL.sgp_logpdf_grad_pool(ctx()::Ptr{Cvoid}, B::Cint, specs::Ptr{Ptr{CSpec}}, pms::Ptr{Ptr{Float64}},
+            kinds::Ptr{Cint}, pnz::Ptr{Ptr{Float64}}, pys::Ptr{Ptr{Float64}}, lp::Ptr{Float64}, pgy::Ptr{Ptr{Float64}},
+            pgm::Ptr{Ptr{Float64}}, pgn::Ptr{Ptr{Float64}}, pgc::Ptr{Ptr{Float64}}, pgs::Ptr{Ptr{Float64}},
+            infos::Ptr{Cint}, rep::Ref{PoolReport})::Cint)
+    res = [infos[b] != 0 ? failed(infos[b]) :
+           (logpdf = lp[b], y = gy[b], mean = gm[b], noise = gn[b], coef = gc[b], inscale = gs[b]) for b in 1:B]
+    return res, infos, rep[]
 end
 
 function elbo_and_gradient(v::VFE, fx::SthenoFGP, y::AbstractVector{<:Real})

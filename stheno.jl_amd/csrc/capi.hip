@@ -5,6 +5,7 @@
 #include "tilemap.h"
 #include "sz_pattern.h"
 #include "df_tasks.h"
+#include "df_pool.h"
 #include <limits>
 
 #include <algorithm>
@@ -894,8 +895,8 @@ struct SzScope {   // the launch-based updates read the pattern through gemm_nt.
 
 // scratch of a dataflow launch on this context (grow-only): progress words for nb matrices of m_tot rows and -- when the caller
 // keeps no inverse diagonal blocks itself -- room for those of inv_cols columns (0: not needed)
-static int df_scratch(sgp_ctx* ctx, long m_tot, int nb, long inv_cols, hipStream_t s) {
-  const long need_state = df_state_words(m_tot, nb), need_inv = (inv_cols / TILE) * INVD_STRIDE;
+// (the state words alone: a ragged pool counts them itself -- df_pool_state_words)
+static int df_scratch_state(sgp_ctx* ctx, long need_state, hipStream_t s) {
   if (need_state > ctx->n_df_state) {
     SGP_HIP(hipStreamSynchronize(s));
     if (ctx->d_df_state) hipFree(ctx->d_df_state);
@@ -904,6 +905,11 @@ static int df_scratch(sgp_ctx* ctx, long m_tot, int nb, long inv_cols, hipStream
     SGP_HIP(hipMalloc(&ctx->d_df_state, sizeof(int) * need_state));
     ctx->n_df_state = need_state;
   }
+  return 0;
+}
+static int df_scratch(sgp_ctx* ctx, long m_tot, int nb, long inv_cols, hipStream_t s) {
+  const long need_inv = (inv_cols / TILE) * INVD_STRIDE;
+  CHECK_RC(df_scratch_state(ctx, df_state_words(m_tot, nb), s));
   if (need_inv > ctx->n_df_inv) {
     SGP_HIP(hipStreamSynchronize(s));
     if (ctx->d_df_inv) hipFree(ctx->d_df_inv);
@@ -2236,6 +2242,458 @@ int sgp::drv_logpdf_grad_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* cons
   return with_df_fallback(ctx, [&]() {
     return logpdf_grad_batch_impl(ctx, nspec, specs, means, noise_kind, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise,
                                   grad_coef, grad_inscale, infos);
+  });
+}
+
+// ---------------------------------------------------------------------------------------
+// ragged pools (include/sthenomi_pool.h): independent models of DIFFERENT sizes and noise kinds in one call
+// ---------------------------------------------------------------------------------------
+// The loops that evaluate one model on data sets of different sizes -- folds that straddle a tile boundary, learning curves,
+// one GP per series (the reference's examples/getting_started/script.jl:154-213 runs them member by member) -- fall off the
+// equal-size batch's pool entirely.  Here every poolable member is assembled exactly as its own call assembles it (its own
+// n_pad, m_tot, leading dimension) and ONE launch of the ragged dataflow kernel (chol_df.hip: chol_pool_kernel, task order
+// df_pool.h) factors up to DF_MAX_BATCH of them; the reductions behind it are each member's own, in its own call's order: every
+// output is bit-equal to the member's own call.
+namespace {
+struct PoolPlan {
+  std::vector<int> single;                  // members that run through their own call, input order
+  std::vector<std::vector<int>> chunks;     // poolable members, by task count (descending), at most DF_MAX_BATCH per launch
+};
+// geo(b, &n_pad, &m_tot) -> is member b poolable (and its geometry)
+template <class Geo>
+PoolPlan pool_plan(int nspec, Geo&& geo) {
+  PoolPlan plan;
+  std::vector<std::pair<long, int>> pooled;   // (tasks, member)
+  for (int b = 0; b < nspec; ++b) {
+    long n_pad = 0, m_tot = 0;
+    if (geo(b, &n_pad, &m_tot)) pooled.emplace_back(df_ntasks((int)(m_tot / TILE), (int)(n_pad / TILE)), b);
+    else plan.single.push_back(b);
+  }
+  std::stable_sort(pooled.begin(), pooled.end(), [](const std::pair<long, int>& x, const std::pair<long, int>& y) { return x.first > y.first; });
+  for (size_t k = 0; k < pooled.size(); k += DF_MAX_BATCH) {
+    const size_t e = std::min(pooled.size(), k + (size_t)DF_MAX_BATCH);
+    if (e - k < 2) {   // a launch of one member is that member's own call
+      plan.single.push_back(pooled[k].second);
+      continue;
+    }
+    plan.chunks.emplace_back();
+    for (size_t q = k; q < e; ++q) plan.chunks.back().push_back(pooled[q].second);
+  }
+  std::sort(plan.single.begin(), plan.single.end());
+  return plan;
+}
+// the ragged launch of one chunk: task table (host-built, uploaded on s), progress words, launch.  `order` and `d_order` stay
+// alive until the caller has drained s.
+int pool_launch(sgp_ctx* ctx, const DfPoolMember* pm, int nb, std::vector<uint32_t>& order, DevBuf& d_order, hipStream_t s) {
+  int T_r[DF_MAX_BATCH], T_c[DF_MAX_BATCH];
+  bool equal = true;
+  for (int b = 0; b < nb; ++b) {
+    T_r[b] = pm[b].T_r;
+    T_c[b] = pm[b].T_c;
+    equal = equal && T_r[b] == T_r[0] && T_c[b] == T_c[0] && pm[b].ld == pm[0].ld && pm[b].nz == pm[0].nz && pm[b].nzw == pm[0].nzw;
+  }
+  if (equal) {
+    // one shape: the ragged order IS the equal-size batch's round robin (df_pool.h), and that kernel needs no table: this
+    // shape class takes it (8 members at N = 4096 through the ragged kernel: 5.19 ms against 5.15 -- profiles/r09_pool.json)
+    DfProb probs[DF_MAX_BATCH];
+    for (int b = 0; b < nb; ++b) probs[b] = pm[b].p;
+    const long m_tot = (long)T_r[0] * TILE;
+    CHECK_RC(df_scratch_state(ctx, df_state_words(m_tot, nb), s));
+    return launch_chol_dataflow_batch(probs, nb, pm[0].ld, (long)T_c[0] * TILE, m_tot, ctx->d_df_state,
+                                      ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s,
+                                      pm[0].nz, pm[0].nzw);
+  }
+  CHECK_ARG(df_pool_order(T_r, T_c, nb, order), "pool: a member's tile grid does not fit the task table");
+  CHECK_RC(d_order.alloc((order.size() + 1) / 2));   // (32-bit entries inside doubles' storage)
+  SGP_HIP(hipMemcpyAsync(d_order.p, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
+  CHECK_RC(df_scratch_state(ctx, df_pool_state_words(pm, nb), s));
+  return launch_chol_pool(pm, nb, ctx->d_df_state, reinterpret_cast<const uint32_t*>(d_order.p), (long)order.size(),
+                          ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s);
+}
+int pool_distinct(const std::vector<long>& sizes) {
+  std::vector<long> u(sizes);
+  std::sort(u.begin(), u.end());
+  return (int)(std::unique(u.begin(), u.end()) - u.begin());
+}
+}  // namespace
+
+static int logpdf_pool_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                            const int* kinds, const double* const* noises, const double* const* ys, double* out, int* infos,
+                            sgp_pool_report* report) {
+  CHECK_ARG(ctx && specs && kinds && noises && ys && out && nspec >= 1, "sgp_logpdf_pool: NULL argument");
+  for (int b = 0; b < nspec; ++b) {
+    CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_pool: NULL member");
+    CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_pool: specs must be symmetric");
+    CHECK_ARG(kinds[b] >= SGP_NOISE_SCALAR && kinds[b] <= SGP_NOISE_DENSE, "sgp_logpdf_pool: bad noise kind");
+    if (infos) infos[b] = 0;
+  }
+  sgp_pool_report rep = {0, 0, 0, 0};
+  if (report) *report = rep;
+  const bool pool_on = !ctx->multi && ctx->dataflow != 0 && ctx->batch_max_n > 0;
+  const PoolPlan plan = pool_plan(nspec, [&](int b, long* n_pad, long* m_tot) {
+    const long N = spec_rows_host(specs[b]);
+    if (!pool_on || N < 1 || (kinds[b] != SGP_NOISE_SCALAR && kinds[b] != SGP_NOISE_DIAG)) return false;
+    int64_t np = 0, mt = 0;
+    sgp_geometry(N, 1, &np, &mt);
+    *n_pad = np;
+    *m_tot = mt;
+    return np <= ctx->batch_max_n;
+  });
+  int first_bad = 0;
+  auto note_bad = [&](int b, int info) {
+    out[b] = std::numeric_limits<double>::quiet_NaN();
+    if (infos) infos[b] = info;
+    if (!first_bad) {
+      first_bad = info;
+      set_error("matrix is not positive definite; Cholesky factorization failed at leading minor " + std::to_string(info) +
+                " (pool member " + std::to_string(b) + ")");
+    }
+  };
+  auto run_single = [&](int b) -> int {
+    const int rc = sgp_logpdf(ctx, specs[b], means ? means[b] : nullptr, kinds[b], noises[b], ys[b], spec_rows_host(specs[b]), 1,
+                              out + b);
+    if (rc < 0) return rc;
+    if (rc > 0) note_bad(b, rc);
+    rep.single_members += 1;
+    return 0;
+  };
+  for (int b : plan.single) CHECK_RC(run_single(b));
+  std::vector<long> sizes;
+  CtxScope scope(ctx);
+  hipStream_t s = ctx->stream;
+  struct Member {
+    SpecGuard g;
+    DevBuf A, mean, y;
+    NoiseDev nd;
+    long N = 0, n_pad = 0, m_tot = 0, T_c = 0, off = 0, inv_off = 0;
+  };
+  for (size_t c = 0; c < plan.chunks.size(); ++c) {
+    const std::vector<int>& ids = plan.chunks[c];
+    const int nb = (int)ids.size();
+    std::vector<Member> mem((size_t)nb);
+    DevBuf inv, small, infobuf, d_order;
+    std::vector<uint32_t> order;
+    // per member in `small`: logdet slots [T_c] | logdet | |L^-1 (y - m)|^2 | logpdf | (pad to T_c + 8)
+    long small_len = 0, inv_len = 0;
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      CHECK_RC(dspec_create(ctx, specs[ids[b]], &M.g.ds));
+      M.N = M.g.ds->N;
+      int64_t np = 0, mt = 0;
+      sgp_geometry(M.N, 1, &np, &mt);
+      M.n_pad = np;
+      M.m_tot = mt;
+      M.T_c = np / TILE;
+      M.off = small_len;
+      M.inv_off = inv_len;
+      small_len += M.T_c + 8;
+      inv_len += M.T_c * INVD_STRIDE;
+    }
+    // device memory: an allocation that fails hands this chunk's and the later chunks' members to their own calls
+    int arc = inv.alloc((size_t)inv_len);
+    arc = arc ? arc : small.alloc((size_t)small_len);
+    arc = arc ? arc : infobuf.alloc((size_t)nb);   // (ints inside doubles' storage)
+    int* d_infos = reinterpret_cast<int*>(infobuf.p);
+    if (!arc) SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
+    DfPoolMember pm[DF_MAX_BATCH];
+    // (member by member: the next member's uploads run under the assembly of the one before, as in the equal-size batch)
+    for (int b = 0; b < nb && !arc; ++b) {
+      Member& M = mem[(size_t)b];
+      const int gb = ids[b];
+      arc = M.A.alloc((size_t)M.m_tot * M.n_pad);
+      arc = arc ? arc : M.y.upload(ys[gb], M.N);
+      if (!arc && means && means[gb]) arc = M.mean.upload(means[gb], M.N);
+      arc = arc ? arc : upload_noise(M.nd, kinds[gb], noises[gb], M.N);
+      if (arc) break;
+      // (no structural zeros of the members' own models inside a pool, as in the equal-size batch)
+      CHECK_RC(build_bordered(ctx, M.g.ds, M.A.p, M.n_pad, M.m_tot, M.mean.p, M.nd.kind, M.nd.sigma2, M.nd.diag.p, nullptr, 0,
+                              M.y.p, M.N, 1, s, nullptr));
+      pm[b] = DfPoolMember{DfProb{M.A.p, inv.p + M.inv_off, small.p + M.off, d_infos + b}, M.m_tot, (int)(M.m_tot / TILE),
+                           (int)M.T_c, nullptr, 0};
+    }
+    if (arc == -2) {
+      SGP_HIP(hipStreamSynchronize(s));   // (assemblies of the members that did fit may still be running on their buffers)
+      mem.clear();
+      inv.release();
+      small.release();
+      infobuf.release();
+      std::vector<int> rest;
+      for (size_t c2 = c; c2 < plan.chunks.size(); ++c2) rest.insert(rest.end(), plan.chunks[c2].begin(), plan.chunks[c2].end());
+      std::sort(rest.begin(), rest.end());
+      for (int b : rest) CHECK_RC(run_single(b));
+      break;
+    }
+    CHECK_RC(arc);
+    CHECK_RC(pool_launch(ctx, pm, nb, order, d_order, s));
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      double* sm = small.p + M.off;
+      CHECK_RC(launch_rowsumsq(M.A.p + M.n_pad, M.m_tot, M.N, 1, sm + M.T_c + 1, 0, s));
+      CHECK_RC(launch_sum_array(sm, M.T_c, sm + M.T_c, s));
+      CHECK_RC(launch_logpdf_final(sm + M.T_c, sm + M.T_c + 1, M.N, 1, sm + M.T_c + 2, s));
+    }
+    std::vector<double> h_small((size_t)small_len);
+    std::vector<int> h_info((size_t)nb);
+    int h_abort = 0;
+    SGP_HIP(hipMemcpyAsync(h_small.data(), small.p, sizeof(double) * h_small.size(), hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipMemcpyAsync(&h_abort, ctx->d_df_state + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipStreamSynchronize(s));
+    // the abort word is shared by the whole launch: once raised no member's result is complete, whatever its own info says
+    bool timed_out = h_abort != 0;
+    for (int b = 0; b < nb; ++b) timed_out = timed_out || h_info[(size_t)b] == SGP_DF_TIMEOUT;
+    if (timed_out) {
+      ctx->df_timed_out = true;   // (with_df_fallback reruns the call on the launch-based schedule: every member on its own)
+      set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
+      return -3;
+    }
+    for (int b = 0; b < nb; ++b) {
+      const Member& M = mem[(size_t)b];
+      out[ids[b]] = h_small[(size_t)(M.off + M.T_c + 2)];
+      if (h_info[(size_t)b] > 0) note_bad(ids[b], h_info[(size_t)b]);
+      sizes.push_back(M.n_pad);
+    }
+    rep.pool_launches += 1;
+    rep.pooled_members += nb;
+  }
+  rep.distinct_sizes = pool_distinct(sizes);
+  if (report) *report = rep;
+  return infos ? 0 : first_bad;
+}
+int sgp::drv_logpdf_pool(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                         const int* noise_kinds, const double* const* noises, const double* const* ys, double* out, int* infos,
+                         sgp_pool_report* report) {
+  return with_df_fallback(ctx, [&]() { return logpdf_pool_impl(ctx, nspec, specs, means, noise_kinds, noises, ys, out, infos, report); });
+}
+
+// value + gradient: logpdf_grad_batch_impl's steps with every member in its own geometry -- one ragged launch factors every
+// member's [K + Sigma_y ; (y - m)' ; I] with the border pattern of its own padded size (one sz_symbolic per distinct size, one
+// upload of them all), C^-1 = inv(L)' inv(L) is one launch per distinct padded size, then per member the single call's launches
+// in its order.
+static int logpdf_grad_pool_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                                 const int* kinds, const double* const* noises, const double* const* ys, double* logpdf_out,
+                                 double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
+                                 double* const* grad_coef, double* const* grad_inscale, int* infos, sgp_pool_report* report) {
+  CHECK_ARG(ctx && specs && kinds && noises && ys && logpdf_out && nspec >= 1, "sgp_logpdf_grad_pool: NULL argument");
+  for (int b = 0; b < nspec; ++b) {
+    CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_grad_pool: NULL member");
+    CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_grad_pool: specs must be symmetric");
+    CHECK_ARG(kinds[b] >= SGP_NOISE_SCALAR && kinds[b] <= SGP_NOISE_DENSE, "sgp_logpdf_grad_pool: bad noise kind");
+    CHECK_ARG(!spec_has_stencil(ctx, specs[b]), "sgp_logpdf_grad_pool: gradients through stencil terms are not supported");
+    CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_pool: gradients through patch (convolutional) terms are not supported");
+    if (infos) infos[b] = 0;
+  }
+  sgp_pool_report rep = {0, 0, 0, 0};
+  if (report) *report = rep;
+  auto out_of = [](double* const* v, int b) { return v ? v[b] : nullptr; };
+  const bool pool_on = !ctx->multi && ctx->dataflow != 0 && ctx->batch_max_n > 0;
+  const PoolPlan plan = pool_plan(nspec, [&](int b, long* n_pad, long* m_tot) {
+    const long N = spec_rows_host(specs[b]);
+    if (!pool_on || N < 1 || (kinds[b] != SGP_NOISE_SCALAR && kinds[b] != SGP_NOISE_DIAG)) return false;
+    *n_pad = rup(N, TILE);
+    *m_tot = 2 * *n_pad + TILE;   // logpdf_grad_core's geometry
+    return *n_pad <= ctx->batch_max_n && *n_pad < ctx->hybrid_grow_min_n;
+  });
+  int first_bad = 0;
+  auto note_bad = [&](int b, int info) {
+    logpdf_out[b] = std::numeric_limits<double>::quiet_NaN();
+    if (infos) infos[b] = info;
+    if (!first_bad) {
+      first_bad = info;
+      set_error("matrix is not positive definite; Cholesky factorization failed at leading minor " + std::to_string(info) +
+                " (pool member " + std::to_string(b) + ")");
+    }
+  };
+  auto run_single = [&](int b) -> int {
+    const int rc = sgp_logpdf_grad(ctx, specs[b], means ? means[b] : nullptr, kinds[b], noises[b], ys[b], logpdf_out + b,
+                                   out_of(grad_y, b), out_of(grad_mean, b), out_of(grad_noise, b), out_of(grad_coef, b),
+                                   out_of(grad_inscale, b));
+    if (rc < 0) return rc;
+    if (rc > 0) note_bad(b, rc);
+    rep.single_members += 1;
+    return 0;
+  };
+  for (int b : plan.single) CHECK_RC(run_single(b));
+  std::vector<long> sizes;
+  CtxScope scope(ctx);
+  hipStream_t s = ctx->stream;
+  struct Member {
+    SpecGuard g;
+    DevBuf A, Kinv, mean, y, part;
+    NoiseDev nd;
+    long N = 0, n_pad = 0, m_tot = 0, T_c = 0, nt = 0, off = 0, inv_off = 0, pat_off = 0;
+    int pat_words = 0;
+  };
+  for (size_t c = 0; c < plan.chunks.size(); ++c) {
+    const std::vector<int>& ids = plan.chunks[c];
+    const int nb = (int)ids.size();
+    std::vector<Member> mem((size_t)nb);
+    DevBuf inv, res, infobuf, d_order, d_pat;
+    std::vector<uint32_t> order;
+    // per member in `res`: [T_c] logdet slots | logdet | |z|^2 | logpdf | (pad to T_c + 8) | alpha [n_pad] | noise gradient
+    // [n_pad] | d coef [nt] | d inscale [nt]
+    long res_len = 0, inv_len = 0;
+    // the border pattern of a dense K (sz_pattern.h), one per distinct padded size of the chunk, all in one upload
+    std::vector<sz_word> h_pat;
+    std::vector<long> pat_size, pat_off;
+    std::vector<int> pat_words;
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      CHECK_RC(dspec_create(ctx, specs[ids[b]], &M.g.ds));
+      M.N = M.g.ds->N;
+      M.n_pad = rup(M.N, TILE);
+      M.m_tot = 2 * M.n_pad + TILE;
+      M.T_c = M.n_pad / TILE;
+      M.nt = std::max<long>(1, (long)M.g.ds->h_terms.size());
+      M.off = res_len;
+      M.inv_off = inv_len;
+      res_len += M.T_c + 8 + 2 * M.n_pad + 2 * M.nt;
+      inv_len += M.T_c * INVD_STRIDE;
+      size_t k = 0;
+      while (k < pat_size.size() && pat_size[k] != M.n_pad) ++k;
+      if (k == pat_size.size()) {
+        SzPattern pat;
+        sz_symbolic(std::vector<char>(1, 1), 1, std::vector<long>(1, 0), std::vector<long>(1, M.n_pad), M.n_pad, TILE, M.T_c,
+                    M.m_tot / TILE, pat, true);
+        pat_size.push_back(M.n_pad);
+        pat_off.push_back((long)h_pat.size());
+        pat_words.push_back(pat.words);
+        h_pat.insert(h_pat.end(), pat.nz.begin(), pat.nz.end());
+      }
+      M.pat_off = pat_off[k];
+      M.pat_words = pat_words[k];
+    }
+    int arc = inv.alloc((size_t)inv_len);
+    arc = arc ? arc : res.alloc((size_t)res_len);
+    arc = arc ? arc : infobuf.alloc((size_t)nb);   // (ints inside doubles' storage)
+    arc = arc ? arc : d_pat.alloc(h_pat.size());   // (sz_word and double are both 8 bytes)
+    for (int b = 0; b < nb && !arc; ++b) {
+      Member& M = mem[(size_t)b];
+      const int gb = ids[b];
+      arc = M.A.alloc((size_t)M.m_tot * M.n_pad);
+      arc = arc ? arc : M.Kinv.alloc((size_t)M.n_pad * M.n_pad);
+      arc = arc ? arc : M.y.upload(ys[gb], M.N);
+      if (!arc && means && means[gb]) arc = M.mean.upload(means[gb], M.N);
+      arc = arc ? arc : upload_noise(M.nd, kinds[gb], noises[gb], M.N);
+    }
+    if (arc == -2) {
+      mem.clear();
+      inv.release();
+      res.release();
+      infobuf.release();
+      d_pat.release();
+      std::vector<int> rest;
+      for (size_t c2 = c; c2 < plan.chunks.size(); ++c2) rest.insert(rest.end(), plan.chunks[c2].begin(), plan.chunks[c2].end());
+      std::sort(rest.begin(), rest.end());
+      for (int b : rest) CHECK_RC(run_single(b));
+      break;
+    }
+    CHECK_RC(arc);
+    static_assert(sizeof(sz_word) == sizeof(double), "pattern words are stored in a DevBuf");
+    SGP_HIP(hipMemcpy(d_pat.p, h_pat.data(), sizeof(sz_word) * h_pat.size(), hipMemcpyHostToDevice));
+    const sz_word* d_nz = reinterpret_cast<const sz_word*>(d_pat.p);
+    int* d_infos = reinterpret_cast<int*>(infobuf.p);
+    SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
+    SGP_HIP(hipMemsetAsync(res.p, 0, sizeof(double) * res_len, s));
+    // 1. assembly (logpdf_grad_core's), every member in its own geometry
+    DfPoolMember pm[DF_MAX_BATCH];
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      CHECK_RC(assemble(M.g.ds, M.A.p, M.m_tot, 0, M.T_c, 0, M.T_c, 1, M.nd.kind, M.nd.sigma2, M.nd.diag.p, s));
+      CHECK_RC(launch_fill_pad(M.A.p, M.m_tot, M.N, M.n_pad, 0, M.n_pad, M.m_tot, 0, s));
+      CHECK_RC(launch_grad_border(M.A.p, M.m_tot, M.n_pad, M.N, M.y.p, M.mean.p, TILE + M.n_pad, s));
+      pm[b] = DfPoolMember{DfProb{M.A.p, inv.p + M.inv_off, res.p + M.off, d_infos + b}, M.m_tot, (int)(M.m_tot / TILE),
+                           (int)M.T_c, d_nz + M.pat_off, M.pat_words};
+    }
+    // 2. one ragged launch: the factors and inv(L)' of every member
+    CHECK_RC(pool_launch(ctx, pm, nb, order, d_order, s));
+    // 3. C^-1 = inv(L)' inv(L), lower tiles: one launch per distinct padded size
+    for (size_t k = 0; k < pat_size.size(); ++k) {
+      const double* rinv[DF_MAX_BATCH];
+      double* kinv[DF_MAX_BATCH];
+      int ng = 0;
+      long mt = 0;
+      for (int b = 0; b < nb; ++b) {
+        Member& M = mem[(size_t)b];
+        if (M.n_pad != pat_size[k]) continue;
+        rinv[ng] = M.A.p + M.n_pad + TILE;
+        kinv[ng] = M.Kinv.p;
+        mt = M.m_tot;
+        ++ng;
+      }
+      CHECK_RC(launch_gemm_nt_uut_batch(rinv, mt, kinv, pat_size[k], pat_size[k], ng, s));
+    }
+    // 4. + 5. per member, in the single call's order
+    for (int b = 0; b < nb; ++b) {
+      Member& M = mem[(size_t)b];
+      const int gb = ids[b];
+      double* sm = res.p + M.off;
+      double* alpha = sm + M.T_c + 8;
+      double* gn = alpha + M.n_pad;
+      double* gc = gn + M.n_pad;
+      double* gs = gc + M.nt;
+      const double* zrow = M.A.p + M.n_pad;
+      CHECK_RC(launch_rowsumsq(zrow, M.m_tot, M.N, 1, sm + M.T_c + 1, 0, s));
+      CHECK_RC(launch_sum_array(sm, M.T_c, sm + M.T_c, s));
+      CHECK_RC(launch_logpdf_final(sm + M.T_c, sm + M.T_c + 1, M.N, 1, sm + M.T_c + 2, s));
+      CHECK_RC(launch_gemv_rows(M.A.p + M.n_pad + TILE, M.m_tot, M.N, M.n_pad, zrow, M.m_tot, nullptr, alpha, s, 1));
+      CHECK_RC(launch_mirror_lower(M.Kinv.p, M.n_pad, M.n_pad, s));
+      if (out_of(grad_noise, gb))
+        CHECK_RC(launch_grad_noise(M.Kinv.p, M.n_pad, alpha, M.N, M.nd.kind == SGP_NOISE_DIAG, gn, s));
+      if (out_of(grad_coef, gb) || out_of(grad_inscale, gb))
+        CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, M.n_pad, alpha, M.T_c, M.T_c, M.part, gc, gs, s));
+    }
+    std::vector<double> h_res((size_t)res_len);
+    std::vector<int> h_info((size_t)nb);
+    int h_abort = 0;
+    SGP_HIP(hipMemcpyAsync(h_res.data(), res.p, sizeof(double) * h_res.size(), hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipMemcpyAsync(&h_abort, ctx->d_df_state + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    SGP_HIP(hipStreamSynchronize(s));
+    bool timed_out = h_abort != 0;   // shared by the whole launch (see logpdf_pool_impl)
+    for (int b = 0; b < nb; ++b) timed_out = timed_out || h_info[(size_t)b] == SGP_DF_TIMEOUT;
+    if (timed_out) {
+      ctx->df_timed_out = true;
+      set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
+      return -3;
+    }
+    for (int b = 0; b < nb; ++b) {
+      const Member& M = mem[(size_t)b];
+      const int gb = ids[b];
+      sizes.push_back(M.n_pad);
+      if (h_info[(size_t)b] > 0) {
+        note_bad(gb, h_info[(size_t)b]);
+        continue;
+      }
+      const double* sm = h_res.data() + M.off;
+      const double* ha = sm + M.T_c + 8;
+      const double* hn = ha + M.n_pad;
+      const double* hc = hn + M.n_pad;
+      const double* hs = hc + M.nt;
+      const long nterms = (long)M.g.ds->h_terms.size();
+      logpdf_out[gb] = sm[M.T_c + 2];
+      if (double* o = out_of(grad_y, gb))
+        for (long i = 0; i < M.N; ++i) o[i] = -ha[i];
+      if (double* o = out_of(grad_mean, gb))
+        for (long i = 0; i < M.N; ++i) o[i] = ha[i];
+      if (double* o = out_of(grad_noise, gb)) std::copy(hn, hn + (M.nd.kind == SGP_NOISE_DIAG ? M.N : 1), o);
+      if (double* o = out_of(grad_coef, gb)) std::copy(hc, hc + nterms, o);
+      if (double* o = out_of(grad_inscale, gb)) std::copy(hs, hs + nterms, o);
+    }
+    rep.pool_launches += 1;
+    rep.pooled_members += nb;
+  }
+  rep.distinct_sizes = pool_distinct(sizes);
+  if (report) *report = rep;
+  return infos ? 0 : first_bad;
+}
+int sgp::drv_logpdf_grad_pool(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                              const int* noise_kinds, const double* const* noises, const double* const* ys, double* logpdf_out,
+                              double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
+                              double* const* grad_coef, double* const* grad_inscale, int* infos, sgp_pool_report* report) {
+  return with_df_fallback(ctx, [&]() {
+    return logpdf_grad_pool_impl(ctx, nspec, specs, means, noise_kinds, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise,
+                                 grad_coef, grad_inscale, infos, report);
   });
 }
 

@@ -37,10 +37,16 @@
 //  * a BATCH of nb equally shaped, independent matrices as one task pool (sgp_logpdf_batch): ids are dealt round robin, every
 //    matrix has its own progress counters; at sizes where one factorisation is bound by its diagonal chain (N <= 8192: 0.13
 //    of the MFMA peak at N = 4096) the nb chains sit on different workgroups and hide each other.
+//
+// A RAGGED pool (sgp_logpdf_pool / sgp_logpdf_grad_pool, include/sthenomi_pool.h): members of DIFFERENT shapes in one launch
+// -- chol_pool_kernel below, with an argument struct and entry points of its own; the three phases are shared through a small
+// geometry view (DfArgs or DfView), the two kernels above compile to what they were.  It serves the loops over data sets of
+// different sizes that the reference runs member by member (examples/getting_started/script.jl:154-213).
 #include "common.h"
 #include "potrf_diag.h"
 #include "panel_solve.h"
 #include "df_tasks.h"
+#include "df_pool.h"
 #include "kstep.h"
 #include <vector>
 
@@ -160,8 +166,13 @@ __device__ __forceinline__ void df_contract_diag(const double* Ag, long ld, long
   }
 }
 
+// The three phases and their waits read a launch through a small geometry view G: DfArgs itself (one matrix, a panel, an
+// equally shaped batch) or DfView (one member of a ragged pool, below) -- the same members, so the code of the DfArgs
+// instantiations is what it was.
+
 // thread 0: wait until min(prog[i], prog[j]) > have (returns min(.., cap)), or -1 on abort / timeout
-__device__ __forceinline__ int df_wait(const DfArgs& a, int* prog, int* info, int i, int j, int have, int cap) {
+template <class G>
+__device__ __forceinline__ int df_wait(const G& a, int* prog, int* info, int i, int j, int have, int cap) {
   const long long t0 = wall_clock64();
   int avail;
   for (unsigned spins = 0;; ++spins) {
@@ -182,7 +193,8 @@ __device__ __forceinline__ int df_wait(const DfArgs& a, int* prog, int* info, in
 }
 
 // thread 0: wait until *word >= target; 0, or -1 on abort / timeout
-__device__ __forceinline__ int df_wait_word(const DfArgs& a, int* info, int* word, int target) {
+template <class G>
+__device__ __forceinline__ int df_wait_word(const G& a, int* info, int* word, int target) {
   const long long t0 = wall_clock64();
   for (unsigned spins = 0;; ++spins) {
     if (DF_RLX_LOAD(word) >= target) break;
@@ -201,7 +213,8 @@ __device__ __forceinline__ int df_wait_word(const DfArgs& a, int* info, int* wor
 // structural zeros: is tile (i, j) of the factor structurally non-zero?
 // (nz_t0: the pattern is the whole matrix's; a panel factored by this kernel -- the hybrid schedule, the sharded sweep --
 // sits nz_t0 tiles down and to the right in it, and its k blocks are the panel's own columns)
-__device__ __forceinline__ bool df_nz(const DfArgs& a, int i, int j) {
+template <class G>
+__device__ __forceinline__ bool df_nz(const G& a, int i, int j) {
   const int jj = j + a.nz_t0;
   return !a.nz || ((a.nz[(long)(i + a.nz_t0) * a.nzw + (jj >> 6)] >> (jj & 63)) & 1) != 0;
 }
@@ -231,7 +244,8 @@ __device__ __forceinline__ void df_run(const sz_word* ri, const sz_word* rj, int
 }
 // thread 0: the next run of the matrix's OWN k blocks >= k0 (and < jend) that task (i, j) has to contract -- both L_ik and
 // L_jk structurally non-zero: [ka, kb); ka == jend: none left
-__device__ __forceinline__ void df_next_run(const DfArgs& a, int i, int j, int k0, int jend, int& ka, int& kb) {
+template <class G>
+__device__ __forceinline__ void df_next_run(const G& a, int i, int j, int k0, int jend, int& ka, int& kb) {
   const int t0 = a.nz_t0;
   df_run(a.nz + (long)(i + t0) * a.nzw, a.nz + (long)(j + t0) * a.nzw, k0 + t0, jend + t0, ka, kb);
   ka -= t0;
@@ -266,9 +280,9 @@ __device__ __forceinline__ int df_dequeue(const DfArgs& a, int* b) {
 // Phase 1: acc = -A_ij + sum_k L_ik L_jk' -- the external sources first, then the matrix's own columns as the operand rows
 // become final.  Diagonal tile of a factored column: the result goes into potrf_diag_body's packed LDS layout; every other
 // tile: T = -acc is stored in place.  Returns false on abort.
-template <bool LOWER>   // LOWER: the diagonal tiles' lower-only contraction (the one-workgroup-per-CU instantiation: the sizes
+template <bool LOWER, class G>   // LOWER: the diagonal tiles' lower-only contraction (the one-workgroup-per-CU instantiation: the sizes
                         // where the chain is the step; the lean kernel's register budget stays what it was)
-__device__ __forceinline__ bool df_accumulate_body(const DfArgs& a, double* A, int* prog, int* info, int i, int j, double* smem,
+__device__ __forceinline__ bool df_accumulate_body(const G& a, double* A, int* prog, int* info, int i, int j, double* smem,
                                                    int* s_word) {
   const int t = threadIdx.x;
   const int lane = t & 63;
@@ -373,7 +387,8 @@ __device__ __forceinline__ bool df_accumulate_body(const DfArgs& a, double* A, i
 }
 
 // Phase 2a: Cholesky of the diagonal tile sitting in LDS
-__device__ __forceinline__ void df_diag_body(const DfArgs& a, const DfProb& p, int j) {
+template <class G>
+__device__ __forceinline__ void df_diag_body(const G& a, const DfProb& p, int j) {
   potrf_diag_body<false, double, true>(p.A + (long)j * TILE + (long)j * TILE * a.ld, a.ld, p.invall + (long)j * 2048,
                                        p.slots + j, p.info, a.gcol_base + (long)j * TILE, 0, nullptr);
 }
@@ -558,6 +573,203 @@ __device__ __forceinline__ void chol_dataflow_body(const DfArgs& a) {
 
 __global__ __launch_bounds__(512, 4) void chol_dataflow_kernel(DfArgs a) { chol_dataflow_body<false>(a); }
 __global__ __launch_bounds__(512, 2) void chol_dataflow_fat_kernel(DfArgs a) { chol_dataflow_body<true>(a); }
+
+// ---- A RAGGED pool: up to DF_MAX_BATCH independent matrices, each with its own tile grid, leading dimension, progress
+// counters and (optionally) structural-zero pattern, as ONE task pool.  The task order is a table the host builds
+// (df_pool.h: a merge of the members' own column-major orders, dealt in proportion to their lengths); the three phases are
+// the ones above, reading the task's member through a DfView.  One abort word serves the launch; every wait is bounded.
+struct DfPoolArgs {
+  DfPoolMember m[DF_MAX_BATCH];
+  int prog_off[DF_MAX_BATCH];   // member b's progress counters: state[DF_PROG + prog_off[b] + i]
+  int nb;
+  int* state;                   // [0] next task id, [1] abort, then the progress counters; zeroed before every launch
+  const uint32_t* order;        // order[q] = (member, i, j) of task id q (df_pool_pack)
+  long long spin_ticks;
+  long ntasks;
+};
+// one member's geometry, with the members of DfArgs the phases read; what a pool never has is a constant
+struct DfView {
+  long ld;
+  int T_f;
+  int nzw;
+  const sz_word* nz;
+  int* state;
+  long long spin_ticks;
+  static constexpr int n_ext = 0;
+  static constexpr const DfExt* ext = nullptr;
+  static constexpr int nz_t0 = 0;
+  static constexpr long gcol_base = 0;
+  static constexpr long long* stats = nullptr;
+  static constexpr long long* cols = nullptr;
+};
+// The kernels read their argument struct through the kernarg segment itself (constant address space): a by-value struct that
+// is indexed with a run-time member number would be copied to the stack first -- this way member b's geometry is a scalar
+// load at a scalar offset, and every value of it that steers control flow is scalar.
+typedef const __attribute__((address_space(4))) DfPoolArgs* DfPoolKarg;
+__device__ __forceinline__ DfView df_view(DfPoolKarg a, int b) {
+  return DfView{a->m[b].ld, a->m[b].T_c, a->m[b].nzw, a->m[b].nz, a->state, a->spin_ticks};
+}
+__device__ __forceinline__ DfProb df_prob(DfPoolKarg a, int b) {
+  return DfProb{a->m[b].p.A, a->m[b].p.invall, a->m[b].p.slots, a->m[b].p.info};
+}
+// lane 0: the next task -- tile (i << 16 | j), its member through *b -- or -1: none left / abort raised
+__device__ __forceinline__ int df_pool_dequeue(DfPoolKarg a, int* b) {
+  int* state = a->state;
+  if (DF_RLX_LOAD(state + 1) != 0) return -1;
+  const int q = atomicAdd(state, 1);
+  if ((long)q >= a->ntasks) return -1;
+  int i, j;
+  df_pool_unpack(a->order[q], *b, i, j);
+  return (int)df_pack(i, j);
+}
+// the phases as functions of their own, as above (the view is built inside: nothing but integers crosses the call)
+__device__ __attribute__((noinline)) bool df_accumulate_pool_lean(DfPoolKarg a, int b, int* prog, int i, int j, double* smem,
+                                                                  int* s_word) {
+  const DfView v = df_view(a, b);
+  return df_accumulate_body<false>(v, a->m[b].p.A, prog, a->m[b].p.info, i, j, smem, s_word);
+}
+__device__ __attribute__((noinline)) bool df_accumulate_pool_fat(DfPoolKarg a, int b, int* prog, int i, int j, double* smem,
+                                                                 int* s_word) {
+  const DfView v = df_view(a, b);
+  return df_accumulate_body<true>(v, a->m[b].p.A, prog, a->m[b].p.info, i, j, smem, s_word);
+}
+__device__ __attribute__((noinline)) void df_diag_pool_lean(DfPoolKarg a, int b, int j) {
+  const DfView v = df_view(a, b);
+  const DfProb p = df_prob(a, b);
+  df_diag_body(v, p, j);
+}
+__device__ __attribute__((noinline)) void df_diag_pool_fat(DfPoolKarg a, int b, int j) {
+  const DfView v = df_view(a, b);
+  const DfProb p = df_prob(a, b);
+  df_diag_body(v, p, j);
+}
+
+template <bool FAT>
+__device__ __forceinline__ void chol_pool_body(DfPoolKarg a) {
+  extern __shared__ __attribute__((aligned(16))) double dyn_smem[];
+  __shared__ int s_word[8];   // [0] task, [1] available k blocks / abort, [4] the task's member, [6] first k block of a run
+  const int t = threadIdx.x;
+  if (t == 0) {
+    s_word[0] = df_pool_dequeue(a, s_word + 4);
+    s_word[2] = s_word[3] = 0;
+  }
+  // (the shape of chol_dataflow_body's loop, for its reasons: one lane-0 section per iteration, every value that steers
+  // control flow read through readfirstlane)
+  for (;;) {
+    __syncthreads();
+    const int q = __builtin_amdgcn_readfirstlane(s_word[0]);
+    if (q < 0) break;
+    const int b = __builtin_amdgcn_readfirstlane(s_word[4]);
+    int j, i;
+    df_unpack((uint32_t)q, i, j);
+    const DfView v = df_view(a, b);
+    const DfProb p = df_prob(a, b);
+    int* prog = a->state + DF_PROG + a->prog_off[b];
+    const int has_nz = __builtin_amdgcn_readfirstlane((int)(v.nz != nullptr));
+    if (has_nz && !__builtin_amdgcn_readfirstlane((int)df_nz(v, i, j))) {
+      // a structurally zero tile of this member's pattern: its row's progress counter still moves in column order
+      __syncthreads();
+      if (t == 0) {
+        int r = df_wait_word(v, p.info, prog + i, j);
+        if (r == 0) {
+          df_release_store(prog + i, j + 1);
+          r = df_pool_dequeue(a, s_word + 4);
+        }
+        s_word[0] = r;
+      }
+      continue;
+    }
+    if (i == j || i == j + 1) __builtin_amdgcn_s_setprio(3);
+    else __builtin_amdgcn_s_setprio(0);
+    const bool got = FAT ? df_accumulate_pool_fat(a, b, prog, i, j, dyn_smem, s_word)
+                         : df_accumulate_pool_lean(a, b, prog, i, j, dyn_smem, s_word);
+    if (!__builtin_amdgcn_readfirstlane((int)got)) break;
+    if (i == j) {
+      __syncthreads();
+      if (FAT) df_diag_pool_fat(a, b, j);
+      else df_diag_pool_lean(a, b, j);
+    } else {
+      if (t == 0) s_word[1] = df_wait(v, prog, p.info, j, j, j, j + 1);   // the diagonal tile of column j is final
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (__builtin_amdgcn_readfirstlane(s_word[1]) < 0) break;
+      if (FAT) df_solve_fat(p.A, v.ld, p.invall, i, j, dyn_smem);
+      else df_solve_lean(p.A, v.ld, p.invall, i, j, dyn_smem);
+    }
+    // the tile is final: every wave drains its stores, then lane 0 publishes row i's progress and takes the next task
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) {
+      int r = has_nz ? df_wait_word(v, p.info, prog + i, j) : 0;
+      if (r == 0) {
+        df_release_store(prog + i, j + 1);
+        r = df_pool_dequeue(a, s_word + 4);
+      }
+      s_word[0] = r;
+    }
+  }
+}
+
+// (the explicit arguments start at offset 0 of the kernarg segment)
+__global__ __launch_bounds__(512, 4) void chol_pool_kernel(DfPoolArgs) {
+  chol_pool_body<false>((DfPoolKarg)__builtin_amdgcn_kernarg_segment_ptr());
+}
+__global__ __launch_bounds__(512, 2) void chol_pool_fat_kernel(DfPoolArgs) {
+  chol_pool_body<true>((DfPoolKarg)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
+// state words a ragged pool needs: one progress counter per tile row of every member
+long df_pool_state_words(const DfPoolMember* mem, int nb) {
+  long w = SGP_DF_STATE_WORDS;
+  for (int b = 0; b < nb; ++b) w += mem[b].T_r;
+  return w;
+}
+
+// d_order: df_pool_order's table for exactly these shapes (ntasks entries), final on the stream before the launch
+int launch_chol_pool(const DfPoolMember* mem, int nb, int* d_state, const uint32_t* d_order, long ntasks, int n_wg,
+                     double timeout_s, int fat, hipStream_t s) {
+  if (nb < 1 || nb > DF_MAX_BATCH || !mem || !d_state || !d_order) {
+    set_error("chol_pool: bad arguments");
+    return -1;
+  }
+  DfPoolArgs a;
+  long words = 0, total = 0;
+  for (int b = 0; b < nb; ++b) {
+    const DfPoolMember& m = mem[b];
+    if (m.T_c < 1 || m.T_r < m.T_c || m.T_r > DF_POOL_MAX_T || m.ld < (long)m.T_r * TILE || !m.p.A || !m.p.invall ||
+        !m.p.slots || !m.p.info || (m.nz && m.nzw < (m.T_c + 63) / 64)) {
+      set_error("chol_pool: bad member geometry");
+      return -1;
+    }
+    if ((long)16 * m.ld + (long)m.T_r * TILE >= (1L << 31)) {   // panel_solve_strip's 32-bit lane offset
+      set_error("chol_pool: leading dimension too large");
+      return -1;
+    }
+    a.m[b] = m;
+    a.prog_off[b] = (int)words;
+    words += m.T_r;
+    total += df_ntasks(m.T_r, m.T_c);
+  }
+  if (total != ntasks || ntasks >= (1L << 31)) {
+    set_error("chol_pool: the task table does not belong to these shapes");
+    return -1;
+  }
+  SGP_LDS_ATTR_ONCE(chol_pool_kernel, PD_LDS);
+  SGP_LDS_ATTR_ONCE(chol_pool_fat_kernel, PD_LDS);
+  a.nb = nb;
+  a.state = d_state;
+  a.order = d_order;
+  a.spin_ticks = (long long)(timeout_s * 1e8);
+  a.ntasks = ntasks;
+  SGP_HIP(hipMemsetAsync(d_state, 0, sizeof(int) * (size_t)df_pool_state_words(mem, nb), s));
+  const long grid = std::min<long>(ntasks, n_wg);
+  if (fat)
+    hipLaunchKernelGGL(chol_pool_fat_kernel, dim3((unsigned)grid), dim3(512), PD_LDS, s, a);
+  else
+    hipLaunchKernelGGL(chol_pool_kernel, dim3((unsigned)grid), dim3(512), PD_LDS, s, a);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
 
 // state words a launch of nb matrices with m_tot rows needs (the callers size d_state with it)
 long df_state_words(long m_tot, int nb) { return SGP_DF_STATE_WORDS + (long)nb * (m_tot / TILE); }

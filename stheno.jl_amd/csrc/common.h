@@ -261,6 +261,19 @@ int launch_chol_dataflow(double* A, long ld, long n_pad, long m_tot, int* d_stat
 int launch_chol_dataflow_batch(const DfProb* probs, int nb, long ld, long n_pad, long m_tot, int* d_state, int n_wg,
                                double timeout_s, int fat, hipStream_t s, const sz_word* d_nz = nullptr, int nz_words = 0);
 long df_state_words(long m_tot, int nb);   // ints of d_state a launch needs
+// A RAGGED pool (chol_df.hip: chol_pool_kernel; df_pool.h): up to DF_MAX_BATCH independent matrices of DIFFERENT shapes as one
+// task pool -- every member with its own tile grid, leading dimension and (optional) structural-zero pattern
+struct DfPoolMember {
+  DfProb p;
+  long ld;
+  int T_r, T_c;           // tile rows (m_tot / 128), tile columns (n_pad / 128) of this member
+  const sz_word* nz;      // its own pattern (bit k of row i = tile (i, k) may be non-zero) or nullptr: dense
+  int nzw;                // words per pattern row
+};
+long df_pool_state_words(const DfPoolMember* mem, int nb);   // SGP_DF_STATE_WORDS + the sum of the members' tile rows
+// d_order: the table df_pool_order (df_pool.h) builds for exactly these shapes, ntasks entries, final on s before the launch
+int launch_chol_pool(const DfPoolMember* mem, int nb, int* d_state, const uint32_t* d_order, long ntasks, int n_wg,
+                     double timeout_s, int fat, hipStream_t s);
 constexpr long SGP_DF_STATE_WORDS = 16;   // state words ahead of the per-tile-row progress counters
 int launch_gemm_nt_stamps(const double* P, long ldp, double* C, long ldc, long M, long Nc, long K, long long* dbg,
                           long* n_ids, hipStream_t s);   // bench: per-workgroup phase stamps of one lower update

@@ -3,6 +3,7 @@
 // multi-GPU call) and on an explicit stream.  Not part of the ABI.
 #pragma once
 #include "ctx.h"
+#include "../../include/sthenomi_pool.h"
 
 namespace sgp {
 
@@ -75,6 +76,16 @@ int drv_logpdf_grad_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* sp
                           const double* const* noises, const double* const* ys, double* logpdf_out, double* const* grad_y,
                           double* const* grad_mean, double* const* grad_noise, double* const* grad_coef,
                           double* const* grad_inscale, int* infos);
+// logpdf / logpdf + gradient of nspec independent models of DIFFERENT sizes and noise kinds (include/sthenomi_pool.h, whose C
+// entry points in libsthenomi_pool.so forward here): the poolable members are factored by ragged launches of the dataflow
+// kernel (chol_df.hip: chol_pool_kernel), the others run through their own calls; with the dataflow time-out fallback
+int drv_logpdf_pool(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                    const int* noise_kinds, const double* const* noises, const double* const* ys, double* out, int* infos,
+                    sgp_pool_report* report);
+int drv_logpdf_grad_pool(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                         const int* noise_kinds, const double* const* noises, const double* const* ys, double* logpdf_out,
+                         double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
+                         double* const* grad_coef, double* const* grad_inscale, int* infos, sgp_pool_report* report);
 // sparse-ELBO partial sums of a slice of the data / the final factorisation (see sgp_dev_elbo_partial / _finish);
 // keep != 0: the M x M factors stay in the caller's buffers (sparse posterior)
 long drv_vfe_part_len(long m_pad);

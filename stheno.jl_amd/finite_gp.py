@@ -490,6 +490,159 @@ def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
     return (res, infos) if return_infos else res
 
 
+def _pool_report(rep):
+    return dict(pool_launches=int(rep.pool_launches), pooled_members=int(rep.pooled_members),
+                single_members=int(rep.single_members), distinct_sizes=int(rep.distinct_sizes))
+
+
+def _pool_result(vals, infos, rep, return_infos, return_report):
+    res = (vals,)
+    if return_infos:
+        res += (infos,)
+    if return_report:
+        res += (rep,)
+    return res if len(res) > 1 else vals
+
+
+def logpdf_pool(fxs, ys, return_infos=False, return_report=False):
+    """[logpdf(fx, y) for fx, y in zip(fxs, ys)] in ONE library call (sgp_logpdf_pool) for members of DIFFERENT sizes and
+    noise kinds -- folds that straddle a tile boundary, a learning curve N = 512 ... 8192, one GP per series.  Members with
+    scalar or diagonal noise are factored as ONE ragged task pool of the dataflow kernel, each in the geometry of its own
+    call; a dense-noise or posterior member goes down as dense noise and runs through its own call inside the library.
+    Every value is bit-equal to the member's own `logpdf`.  A Float32 model is evaluated by its own `logpdf` (the fp32
+    kernels) and its value widened, so that contract holds for it too; the report counts it as single.  A member that is
+    not positive definite gives NaN (return_infos=True: its LAPACK info) instead of raising.  return_report=True adds a dict:
+    pool_launches, pooled_members, single_members, distinct_sizes."""
+    fxs, ys = list(fxs), list(ys)
+    if len(fxs) != len(ys):
+        raise ValueError("logpdf_pool: one y per model")
+    n_all = len(fxs)
+    vals = np.zeros(n_all)
+    infos = np.zeros(n_all, dtype=np.int32)
+    rep = dict(pool_launches=0, pooled_members=0, single_members=0, distinct_sizes=0)
+    keep, down = [], []          # (spec, mean, kind, noise buffer, y) stay alive until the call returns; down: their members
+    for b, (fx, y) in enumerate(zip(fxs, ys)):
+        if isinstance(fx, SparseFiniteGP):
+            raise NotImplementedError("logpdf_pool takes FiniteGPs (use elbo for a SparseFiniteGP)")
+        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+        if yv.shape[0] != len(fx):
+            raise ValueError("length(y) != length(fx)")
+        if _is_prior(fx.f) and _is_f32(fx, y):
+            continue
+        spec, m, kind, nbuf = _spec_mean_noise(fx)
+        keep.append((spec, _f64(m), kind, nbuf, yv))
+        down.append(b)
+    for b, (fx, y) in enumerate(zip(fxs, ys)):
+        if b in down:
+            continue
+        try:                         # a Float32 model: its own call, widened
+            vals[b] = float(logpdf(fx, y))
+        except _lib.PosDefException as e:
+            vals[b], infos[b] = float("nan"), e.info
+        rep["single_members"] += 1
+    if keep:
+        nb = len(keep)
+        for k in keep:
+            k[0].ref()           # (patch terms: their geometry ids on the context)
+        specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
+        means = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[1]) for k in keep])
+        kinds = (C.c_int * nb)(*[int(k[2]) for k in keep])
+        noises = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[3]) for k in keep])
+        yp = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[4]) for k in keep])
+        out = np.zeros(nb)
+        inf = np.zeros(nb, dtype=np.int32)
+        crep = _lib.sgp_pool_report()
+        rc = _ctx().pool.sgp_logpdf_pool(_ctx().handle, nb, specs, means, kinds, noises, yp, _lib.dptr(out),
+                                         inf.ctypes.data_as(C.POINTER(C.c_int)), C.byref(crep))
+        _lib.check(rc, "sgp_logpdf_pool")
+        vals[down], infos[down] = out, inf
+        for k, v in _pool_report(crep).items():
+            rep[k] += v
+    return _pool_result(vals, infos, rep, return_infos, return_report)
+
+
+def logpdf_and_gradient_pool(fxs, ys, return_infos=False, return_report=False):
+    """[logpdf_and_gradient(fx, y) for fx, y in zip(fxs, ys)] in ONE library call (sgp_logpdf_grad_pool) for members of
+    DIFFERENT sizes and noise kinds: one ragged launch of the dataflow kernel factors every poolable member's matrix, (y - m)'
+    row and inv(L)', C^-1 is one launch per distinct padded size.  Every dict holds what the member's own
+    `logpdf_and_gradient(fx, y)` returns (inputs=False, scales=False), bit for bit; a member that is not positive definite
+    gives a dict with logpdf = NaN, `info` and no gradients.  A Float32 model is evaluated by its own call (counted as
+    single).  return_infos / return_report as in `logpdf_pool`."""
+    fxs, ys = list(fxs), list(ys)
+    if len(fxs) != len(ys):
+        raise ValueError("logpdf_and_gradient_pool: one y per model")
+    n_all = len(fxs)
+    infos = np.zeros(n_all, dtype=np.int32)
+    rep = dict(pool_launches=0, pooled_members=0, single_members=0, distinct_sizes=0)
+    res = [None] * n_all
+    keep, down = [], []          # (spec, mean, noise kind, noise buffer, y) stay alive until the call returns
+    for b, (fx, y) in enumerate(zip(fxs, ys)):
+        if isinstance(fx, SparseFiniteGP):
+            raise NotImplementedError("logpdf_and_gradient_pool takes FiniteGPs (use elbo_and_gradient for a SparseFiniteGP)")
+        if not _is_prior(fx.f):
+            raise NotImplementedError("gradients are implemented for prior Stheno processes")
+        n = len(fx)
+        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+        if yv.shape[0] != n:
+            raise ValueError("length(y) != length(fx)")
+        kind, nbuf = _lib._noise_args(fx.noise, n)
+        spec = _prior_spec(fx.f, fx.x)
+        _refuse_patch_gradient(spec)
+        if _is_f32(fx, y):
+            continue
+        keep.append((spec, _f64(mean_vector(fx.f, fx.x)), kind, nbuf, yv))
+        down.append(b)
+
+    def failed(spec, info):
+        return dict(logpdf=float("nan"), info=int(info), y=None, mean=None, noise=None, terms=None, inputs=None, x=None,
+                    scales=None, _raw=None, _rowscale=None, _spec=spec)
+
+    for b, (fx, y) in enumerate(zip(fxs, ys)):
+        if b in down:
+            continue
+        try:
+            res[b] = logpdf_and_gradient(fx, y)
+        except _lib.PosDefException as e:
+            res[b], infos[b] = failed(_prior_spec(fx.f, fx.x), e.info), e.info
+        rep["single_members"] += 1
+    if keep:
+        nb = len(keep)
+        outs = []          # per member: gy, gm, gn, gc, gs (the buffers logpdf_and_gradient passes)
+        for spec, _, kind, _, yv in keep:
+            n, nt = len(yv), max(1, spec.n_terms)
+            gn = np.zeros((n, n), order="F") if kind == _lib.NOISE_DENSE else np.zeros(n if kind == _lib.NOISE_DIAG else 1)
+            outs.append((np.zeros(n), np.zeros(n), gn, np.zeros(nt), np.zeros(nt)))
+
+        def ptrs(arrs):
+            return (C.POINTER(C.c_double) * nb)(*[_lib.dptr(a) for a in arrs])
+
+        for k in keep:
+            k[0].ref()
+        specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
+        kinds = (C.c_int * nb)(*[int(k[2]) for k in keep])
+        lp = np.zeros(nb)
+        inf = np.zeros(nb, dtype=np.int32)
+        crep = _lib.sgp_pool_report()
+        rc = _ctx().pool.sgp_logpdf_grad_pool(_ctx().handle, nb, specs, ptrs([k[1] for k in keep]), kinds,
+                                              ptrs([k[3] for k in keep]), ptrs([k[4] for k in keep]), _lib.dptr(lp),
+                                              *[ptrs([o[q] for o in outs]) for q in range(5)],
+                                              inf.ctypes.data_as(C.POINTER(C.c_int)), C.byref(crep))
+        _lib.check(rc, "sgp_logpdf_grad_pool")
+        for q, b in enumerate(down):
+            spec, _, kind, _, _ = keep[q]
+            gy, gm, gn, gc, gs = outs[q]
+            infos[b] = inf[q]
+            if inf[q]:
+                res[b] = failed(spec, inf[q])
+                continue
+            res[b] = dict(logpdf=float(lp[q]), y=gy, mean=gm, noise=(gn if kind != _lib.NOISE_SCALAR else float(gn[0])),
+                          terms=_term_records(spec, gc, gs, True), inputs=None, x=None, scales=None, _raw=(gc, gs),
+                          _rowscale=None, _spec=spec)
+        for k, v in _pool_report(crep).items():
+            rep[k] += v
+    return _pool_result(res, infos, rep, return_infos, return_report)
+
+
 def _draw(rng, n, s):
     """Z = randn(rng, n, s) in Julia's column-major fill order, from the caller's RNG."""
     if hasattr(rng, "standard_normal"):

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi.so")
 BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_bench.so")
 BATCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_batch.so")
+POOL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_pool.so")
 EXTEND_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend.so")
 EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
@@ -182,6 +183,22 @@ _SIGS_BATCH = {
                                         C.POINTER(_D), C.POINTER(_D), C.POINTER(C.c_int)]),
 }
 
+# include/sthenomi_pool.h: independent models of DIFFERENT sizes and noise kinds in one call, exported by libsthenomi_pool.so
+# (it links against the product library and works on its contexts) -- the host mirror reaches it through pool_lib() /
+# Context.pool
+class sgp_pool_report(C.Structure):
+    _fields_ = [("pool_launches", C.c_int32), ("pooled_members", C.c_int32), ("single_members", C.c_int32),
+                ("distinct_sizes", C.c_int32)]
+
+
+_SIGS_POOL = {
+    "sgp_logpdf_pool": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(sgp_cov_spec)), C.POINTER(_D), C.POINTER(C.c_int),
+                                  C.POINTER(_D), C.POINTER(_D), _D, C.POINTER(C.c_int), C.POINTER(sgp_pool_report)]),
+    "sgp_logpdf_grad_pool": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(sgp_cov_spec)), C.POINTER(_D), C.POINTER(C.c_int),
+                                       C.POINTER(_D), C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D),
+                                       C.POINTER(_D), C.POINTER(_D), C.POINTER(C.c_int), C.POINTER(sgp_pool_report)]),
+}
+
 # include/sthenomi_extend.h: extending a kept factor with new data, exported by libsthenomi_extend.so (it links against the
 # product library and works on its posteriors) -- update_posterior reaches it through extend_lib() / Context.extend
 _SIGS_EXTEND = {
@@ -240,6 +257,11 @@ def batch_symbols():
     return sorted(_SIGS_BATCH)
 
 
+def pool_symbols():
+    """Names include/sthenomi_pool.h declares: the entry points of libsthenomi_pool.so."""
+    return sorted(_SIGS_POOL)
+
+
 def exported_symbols():
     """Names include/sthenomi.h declares (used by the CPU-side symbol test)."""
     return sorted(_SIGS)
@@ -290,6 +312,27 @@ def batch_lib():
             fn.restype = res
             fn.argtypes = args
         _batch = lib
+        return lib
+
+
+_pool = None
+
+
+def pool_lib():
+    """dlopen libsthenomi_pool.so (include/sthenomi_pool.h) after the product library it links against."""
+    global _pool
+    load()
+    with _lib_lock:
+        if _pool is not None:
+            return _pool
+        if not os.path.exists(POOL_LIB_PATH):
+            raise SthenoMIError(f"{POOL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(POOL_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_POOL.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _pool = lib
         return lib
 
 
@@ -451,6 +494,11 @@ class Context:
     def batch(self):
         """libsthenomi_batch.so (sthenomi_batch.h): `ctx.batch.sgp_logpdf_grad_batch(ctx.handle, ...)`"""
         return batch_lib()
+
+    @property
+    def pool(self):
+        """libsthenomi_pool.so (sthenomi_pool.h): `ctx.pool.sgp_logpdf_pool(ctx.handle, ...)`"""
+        return pool_lib()
 
     @property
     def extend(self):
