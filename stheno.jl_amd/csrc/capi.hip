@@ -1256,9 +1256,8 @@ int sgp::drv_sz_col_work(const sgp_ctx* ctx, const sgp_cov_spec* sp, int noise_k
 }
 
 // the device copy of a pattern (`h`: rows x words, possibly another context's -- the ranks of a multi-GPU context share one)
-static int sz_upload(sgp_ctx* ctx, const std::vector<sz_word>& h, int words, hipStream_t s, SzMask* out) {
-  *out = SzMask();
-  if (words <= 0 || h.empty()) return 0;
+// (the words alone, into ctx->d_sz: a pooled launch stages the border patterns of its members in one copy)
+static int sz_stage(sgp_ctx* ctx, const std::vector<sz_word>& h, hipStream_t s) {
   if (h.size() > ctx->n_sz) {
     SGP_HIP(hipStreamSynchronize(s));
     if (ctx->d_sz) hipFree(ctx->d_sz);
@@ -1284,6 +1283,12 @@ static int sz_upload(sgp_ctx* ctx, const std::vector<sz_word>& h, int words, hip
   std::memcpy(ctx->h_sz_pin, h.data(), bytes);
   SGP_HIP(hipMemcpyAsync(ctx->d_sz, ctx->h_sz_pin, bytes, hipMemcpyHostToDevice, s));
   SGP_HIP(hipEventRecord(ctx->ev_sz, s));
+  return 0;
+}
+static int sz_upload(sgp_ctx* ctx, const std::vector<sz_word>& h, int words, hipStream_t s, SzMask* out) {
+  *out = SzMask();
+  if (words <= 0 || h.empty()) return 0;
+  CHECK_RC(sz_stage(ctx, h, s));
   {   // room for the id map of the largest lower update this matrix can see
     const long rows = (long)(h.size() / (size_t)words);
     const long half = 16 + 8 * tri_ids_per_xcd(tri_shape(rows, std::min<long>(rows, (long)words * 64), -1));
@@ -1613,130 +1618,6 @@ extern "C" int sgp_logpdf(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
   return with_df_fallback(ctx, [&]() { return sgp_logpdf_impl(ctx, spec, mean, noise_kind, noise, Y, ldy, ncols, out); });
 }
 
-// logpdf of nspec INDEPENDENT models in one call (round 6; sthenomi.h: sgp_logpdf_batch).  At the sizes where one
-// factorisation is bound by its diagonal chain (N = 4096: 0.13 of the fp64 MFMA peak, ~220 CUs idle) the members of an equally
-// sized batch are factored by ONE launch of the dataflow kernel as a single task pool (chol_df.hip: ids dealt round robin,
-// progress counters per matrix): the B chains sit on different workgroups and hide each other.  Every member sees exactly
-// the arithmetic of its own sgp_logpdf call (assembly, k-ascending contractions, the same reductions): the values are
-// bit-equal.  "Equally sized" = the same PADDED size (the same number of 128-column tiles: the folds of a cross-validation,
-// which differ by a point or two, pool).  Members of different padded sizes, dense noise, sizes outside the batched range, a
-// multi-GPU context: one after the other through sgp_logpdf's own path.
-static int logpdf_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
-                             int noise_kind, const double* const* noises, const double* const* ys, double* out, int* infos) {
-  CHECK_ARG(ctx && specs && noises && ys && out && nspec >= 1, "sgp_logpdf_batch: NULL argument");
-  for (int b = 0; b < nspec; ++b) {
-    CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_batch: NULL member");
-    CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_batch: specs must be symmetric");
-    if (infos) infos[b] = 0;
-  }
-  auto rows_of = [](const sgp_cov_spec* sp) {
-    long n = 0;
-    for (int i = 0; i < sp->n_row_blocks; ++i) n += sp->row_len[i];
-    return n;
-  };
-  // members pool when their PADDED geometry agrees (the folds of a cross-validation differ by a point or two: the same 128-column
-  // tiles, each member's own N in its assembly, its row sums and its logpdf)
-  const long N = rows_of(specs[0]);
-  int64_t n_pad = 0, m_tot = 0;
-  if (N >= 1) sgp_geometry(N, 1, &n_pad, &m_tot);
-  bool same = N >= 1;
-  for (int b = 1; b < nspec && same; ++b) {
-    const long nb_ = rows_of(specs[b]);
-    int64_t np_b = 0, mt_b = 0;
-    if (nb_ >= 1) sgp_geometry(nb_, 1, &np_b, &mt_b);
-    same = nb_ >= 1 && np_b == n_pad && mt_b == m_tot;
-  }
-  const bool pooled = same && N >= 1 && nspec >= 2 && !ctx->multi && ctx->dataflow != 0 &&
-                      ctx->batch_max_n > 0 && n_pad <= ctx->batch_max_n &&
-                      (noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG);
-  if (!pooled) {
-    int first_bad = 0;
-    for (int b = 0; b < nspec; ++b) {
-      const int rc = sgp_logpdf(ctx, specs[b], means ? means[b] : nullptr, noise_kind, noises[b], ys[b], rows_of(specs[b]), 1, out + b);
-      if (rc < 0) return rc;
-      if (rc > 0) {
-        out[b] = std::numeric_limits<double>::quiet_NaN();
-        if (infos) infos[b] = rc;
-        if (!first_bad) first_bad = rc;
-      }
-    }
-    return infos ? 0 : first_bad;
-  }
-  CtxScope scope(ctx);
-  hipStream_t s = ctx->stream;
-  const long T_c = n_pad / TILE;
-  const long per_small = T_c + 8;   // per member: logdet slots | [T_c] logdet | [T_c + 1] |L^-1 (y - m)|^2 | [T_c + 2] logpdf
-  int first_bad = 0;
-  for (int b0 = 0; b0 < nspec; b0 += DF_MAX_BATCH) {
-    const int nb = std::min(DF_MAX_BATCH, nspec - b0);
-    struct Member {
-      SpecGuard g;
-      DevBuf A, mean, y;
-      NoiseDev nd;
-    };
-    std::vector<Member> mem((size_t)nb);
-    DevBuf inv, small, infobuf;
-    CHECK_RC(inv.alloc((size_t)nb * T_c * INVD_STRIDE));
-    CHECK_RC(small.alloc((size_t)nb * per_small));
-    CHECK_RC(infobuf.alloc((size_t)nb));   // (ints inside doubles' storage)
-    int* d_infos = reinterpret_cast<int*>(infobuf.p);
-    SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
-    CHECK_RC(df_scratch(ctx, m_tot, nb, 0, s));
-    DfProb probs[DF_MAX_BATCH];
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      const int gb = b0 + b;
-      const long Nb = rows_of(specs[gb]);   // this member's own size (n_pad, m_tot are the batch's)
-      CHECK_RC(dspec_create(ctx, specs[gb], &M.g.ds));
-      CHECK_RC(M.A.alloc((size_t)m_tot * n_pad));
-      if (means && means[gb]) CHECK_RC(M.mean.upload(means[gb], Nb));
-      CHECK_RC(upload_noise(M.nd, noise_kind, noises[gb], Nb));
-      CHECK_RC(M.y.upload(ys[gb], Nb));
-      // (no structural zeros inside a batch: its members need not share a pattern, and these sizes are chain-bound anyway)
-      CHECK_RC(build_bordered(ctx, M.g.ds, M.A.p, n_pad, m_tot, M.mean.p, M.nd.kind, M.nd.sigma2, M.nd.diag.p, nullptr, 0, M.y.p,
-                              Nb, 1, s, nullptr));
-      probs[b] = DfProb{M.A.p, inv.p + (size_t)b * T_c * INVD_STRIDE, small.p + (size_t)b * per_small, d_infos + b};
-    }
-    CHECK_RC(launch_chol_dataflow_batch(probs, nb, m_tot, n_pad, m_tot, ctx->d_df_state, ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs,
-                                        ctx->df_timeout_s, ctx->batch_fat, s));
-    for (int b = 0; b < nb; ++b) {
-      double* sm = small.p + (size_t)b * per_small;
-      const long Nb = rows_of(specs[b0 + b]);
-      CHECK_RC(launch_rowsumsq(mem[(size_t)b].A.p + n_pad, m_tot, Nb, 1, sm + T_c + 1, 0, s));
-      CHECK_RC(launch_sum_array(sm, T_c, sm + T_c, s));
-      CHECK_RC(launch_logpdf_final(sm + T_c, sm + T_c + 1, Nb, 1, sm + T_c + 2, s));
-    }
-    std::vector<double> h_small((size_t)nb * per_small);
-    std::vector<int> h_info((size_t)nb);
-    SGP_HIP(hipMemcpyAsync(h_small.data(), small.p, sizeof(double) * h_small.size(), hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < nb; ++b) {
-      const int info = h_info[(size_t)b];
-      if (info == SGP_DF_TIMEOUT) {
-        ctx->df_timed_out = true;   // (with_df_fallback reruns the call member by member on the launch-based schedule)
-        set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
-        return -3;
-      }
-      out[b0 + b] = h_small[(size_t)b * per_small + T_c + 2];
-      if (info > 0) {
-        out[b0 + b] = std::numeric_limits<double>::quiet_NaN();
-        if (infos) infos[b0 + b] = info;
-        if (!first_bad) {
-          first_bad = info;
-          set_error("matrix is not positive definite; Cholesky factorization failed at leading minor " + std::to_string(info) +
-                    " (batch member " + std::to_string(b0 + b) + ")");
-        }
-      }
-    }
-  }
-  return infos ? 0 : first_bad;
-}
-extern "C" int sgp_logpdf_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
-                                int noise_kind, const double* const* noises, const double* const* ys, double* out, int* infos) {
-  return with_df_fallback(ctx, [&]() { return logpdf_batch_impl(ctx, nspec, specs, means, noise_kind, noises, ys, out, infos); });
-}
-
 // dst[i + c * ld] = mean[i] (i < N) else 0, for an nrows x ncols block
 __global__ void fill_mean_cols_kernel(double* dst, long ld, long nrows, long ncols, long N, const double* mean) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2026,235 +1907,321 @@ extern "C" int sgp_logpdf_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const d
   });
 }
 
-// logpdf + gradient of nspec INDEPENDENT models in one call (sthenomi_batch.h: sgp_logpdf_grad_batch) -- the optimiser loops of
-// hyper-parameter learning run value AND gradient, and at the sizes where one gradient call is bound by its diagonal chain
-// (N = 4096: 0.2 of the fp64 MFMA peak) the members of an equally sized batch share the chip as logpdf_batch_impl's do:
-//   assembly of every member's [K + Sigma_y ; (y - m)' ; I] as logpdf_grad_core does it;
-//   ONE dataflow launch factors all of them (task pool), with ONE tile pattern: the gradient border of a DENSE K -- the
-//   identity rows are upper triangular by tile in any model, so their zero tiles are skipped as tasks and as k blocks;
-//   ONE launch computes every member's C^-1 = inv(L)' inv(L) (launch_gemm_nt_uut_batch: the single call's dense tile program);
-//   then per member the mirror, alpha, the noise gradient and the term contractions -- the single call's launches in its
-//   order, so every reduction sums in the same order; one download of all small results at the end of a chunk.
-// A structured member's own call skips K's zero tiles; the batch computes them as the exact zeros they are: same bits.
-// Everything else (different padded sizes, dense noise, sizes the single call factors with the hybrid schedule or beyond
-// SGP_BATCH_MAX_N, a multi-GPU context) goes member by member through sgp_logpdf_grad.
-static int logpdf_grad_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
-                                  int noise_kind, const double* const* noises, const double* const* ys, double* logpdf_out,
-                                  double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
-                                  double* const* grad_coef, double* const* grad_inscale, int* infos) {
-  CHECK_ARG(ctx && specs && noises && ys && logpdf_out && nspec >= 1, "sgp_logpdf_grad_batch: NULL argument");
-  CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad_batch: bad noise kind");
-  for (int b = 0; b < nspec; ++b) {
-    CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_grad_batch: NULL member");
-    CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_grad_batch: specs must be symmetric");
-    CHECK_ARG(!spec_has_stencil(ctx, specs[b]), "sgp_logpdf_grad_batch: gradients through stencil terms are not supported");
-    CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_batch: gradients through patch (convolutional) terms are not supported");
-    if (infos) infos[b] = 0;
-  }
-  auto out_of = [](double* const* v, int b) { return v ? v[b] : nullptr; };
+// ---------------------------------------------------------------------------------------
+// pooled launches: independent models in one call (include/sthenomi.h: sgp_logpdf_batch, sthenomi_batch.h, sthenomi_pool.h)
+// ---------------------------------------------------------------------------------------
+// At the sizes where one factorisation is bound by its diagonal chain (N = 4096: 0.13 of the fp64 MFMA peak, ~220 CUs idle;
+// value + gradient: 0.2) independent models are factored by ONE launch of the dataflow kernel as a single task pool
+// (chol_df.hip: progress counters per matrix): the chains sit on different workgroups and hide each other.  Every member is
+// assembled exactly as its own call assembles it (its own N, n_pad, m_tot, leading dimension) and the reductions behind the
+// launch are each member's own, in its own call's order: every output is bit-equal to the member's own sgp_logpdf /
+// sgp_logpdf_grad call.  A structured member's own call skips K's zero tiles; a pooled launch computes them as the exact
+// zeros they are: same bits.
+// Four entry points PLAN such launches -- which members pool, how they are cut into launches, what happens to the rest -- and
+// one routine, pooled_chunk, runs a launch:
+//   sgp_logpdf_batch, sgp_logpdf_grad_batch   members of ONE padded size (the folds of a cross-validation, which differ by a
+//                                             point or two, pool) and one noise kind, in input order; anything else: every
+//                                             member through its own call
+//   sgp_logpdf_pool, sgp_logpdf_grad_pool     members of any sizes and noise kinds (folds that straddle a tile boundary,
+//                                             learning curves, one GP per series -- the reference's
+//                                             examples/getting_started/script.jl:154-213 runs them member by member), largest
+//                                             first; the members that do not pool through their own calls
+namespace {
+// what one of the four entry points was called with, and the outcome of its members so far
+struct PoolCall {
+  const char* label;   // "batch" / "pool": names a member in a message
+  bool grad;           // value + gradient (the members carry the gradient border [ (y - m)' ; I ]) or the value alone
+  const sgp_cov_spec* const* specs;
+  const double* const* means;
+  const int* kinds;    // noise kind per member; nullptr: `kind` for every member
+  int kind;
+  const double* const* noises;
+  const double* const* ys;
+  double* out;         // logpdf per member
+  double* const* grad_y;
+  double* const* grad_mean;
+  double* const* grad_noise;
+  double* const* grad_coef;
+  double* const* grad_inscale;
+  int* infos;
   int first_bad = 0;
-  auto note_bad = [&](int b, int info) {
-    logpdf_out[b] = std::numeric_limits<double>::quiet_NaN();
+
+  int kind_of(int b) const { return kinds ? kinds[b] : kind; }
+  static double* at(double* const* v, int b) { return v ? v[b] : nullptr; }
+  // member b through its own call: < 0 an error, > 0 its info
+  int own_call(sgp_ctx* ctx, int b) const {
+    const double* mean = means ? means[b] : nullptr;
+    if (!grad) return sgp_logpdf(ctx, specs[b], mean, kind_of(b), noises[b], ys[b], spec_rows_host(specs[b]), 1, out + b);
+    return sgp_logpdf_grad(ctx, specs[b], mean, kind_of(b), noises[b], ys[b], out + b, at(grad_y, b), at(grad_mean, b),
+                           at(grad_noise, b), at(grad_coef, b), at(grad_inscale, b));
+  }
+  // member b is not positive definite: NaN and its info; true for the first one of the call
+  bool mark_bad(int b, int info) {
+    out[b] = std::numeric_limits<double>::quiet_NaN();
     if (infos) infos[b] = info;
-    if (!first_bad) {
-      first_bad = info;
+    if (first_bad) return false;
+    first_bad = info;
+    return true;
+  }
+  void note_bad(int b, int info) {   // ... and the call's error text names the first one
+    if (mark_bad(b, info))
       set_error("matrix is not positive definite; Cholesky factorization failed at leading minor " + std::to_string(info) +
-                " (batch member " + std::to_string(b) + ")");
-    }
-  };
-  // members [b0, nspec) one by one through their own call
-  auto singles = [&](int b0) -> int {
-    for (int b = b0; b < nspec; ++b) {
-      const int rc = sgp_logpdf_grad(ctx, specs[b], means ? means[b] : nullptr, noise_kind, noises[b], ys[b], logpdf_out + b,
-                                     out_of(grad_y, b), out_of(grad_mean, b), out_of(grad_noise, b), out_of(grad_coef, b),
-                                     out_of(grad_inscale, b));
-      if (rc < 0) return rc;
-      if (rc > 0) note_bad(b, rc);
-    }
-    return infos ? 0 : first_bad;
-  };
-  const long N0 = spec_rows_host(specs[0]);
-  const long n_pad = rup(std::max<long>(N0, 1), TILE), m_tot = 2 * n_pad + TILE;   // logpdf_grad_core's geometry
-  bool same = N0 >= 1;
-  for (int b = 1; b < nspec && same; ++b) {
-    const long Nb = spec_rows_host(specs[b]);
-    same = Nb >= 1 && rup(Nb, TILE) == n_pad;
+                " (" + label + " member " + std::to_string(b) + ")");
   }
-  const bool pooled = same && nspec >= 2 && !ctx->multi && ctx->dataflow != 0 && ctx->batch_max_n > 0 &&
-                      n_pad <= ctx->batch_max_n && n_pad < ctx->hybrid_grow_min_n &&
-                      (noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG);
-  if (!pooled) return singles(0);
-  CtxScope scope(ctx);
-  hipStream_t s = ctx->stream;
-  const long T_c = n_pad / TILE, T_r = m_tot / TILE;
-  // the shared pattern: the gradient border of a dense K (sz_pattern.h), the same for every member and every chunk
-  SzPattern pat;
-  sz_symbolic(std::vector<char>(1, 1), 1, std::vector<long>(1, 0), std::vector<long>(1, n_pad), n_pad, TILE, T_c, T_r, pat, true);
-  // chunk size from the device memory left (the unused blocks of the context's cache count as free)
-  const double member_bytes =
-      8.0 * ((double)m_tot * n_pad + (double)n_pad * n_pad + (double)T_c * INVD_STRIDE + 16.0 * T_c * T_c + 8.0 * n_pad);
-  int chunk = DF_MAX_BATCH;
-  {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      double avail = (double)free_b;
-      for (const auto& pb : ctx->pool)
-        if (!pb.used) avail += (double)pb.bytes;
-      chunk = (int)std::max(1.0, std::min((double)DF_MAX_BATCH, 0.9 * avail / member_bytes));
-    } else {
-      (void)hipGetLastError();
-    }
-  }
-  struct Member {
-    SpecGuard g;
-    DevBuf A, Kinv, mean, y, part;
-    NoiseDev nd;
-    long N = 0, nt = 0, off = 0;   // off: the member's results in the chunk's result buffer
-  };
-  for (int b0 = 0; b0 < nspec; b0 += chunk) {
-    const int nb = std::min(chunk, nspec - b0);
-    std::vector<Member> mem((size_t)nb);
-    DevBuf inv, res, infobuf;
-    // per member in `res`: [T_c] logdet slots | logdet | |z|^2 | logpdf | (pad to T_c + 8) | alpha [n_pad] | noise gradient
-    // [n_pad] | d coef [nt] | d inscale [nt]
-    long res_len = 0;
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      CHECK_RC(dspec_create(ctx, specs[b0 + b], &M.g.ds));
-      M.N = M.g.ds->N;
-      M.nt = std::max<long>(1, (long)M.g.ds->h_terms.size());
-      M.off = res_len;
-      res_len += T_c + 8 + 2 * n_pad + 2 * M.nt;
-    }
-    // device memory: an allocation that fails hands the remaining members to their own calls instead of failing the call
-    int arc = 0;
-    arc = arc ? arc : inv.alloc((size_t)nb * T_c * INVD_STRIDE);
-    arc = arc ? arc : res.alloc((size_t)res_len);
-    arc = arc ? arc : infobuf.alloc((size_t)nb);   // (ints inside doubles' storage)
-    for (int b = 0; b < nb && !arc; ++b) {
-      Member& M = mem[(size_t)b];
-      const int gb = b0 + b;
-      arc = M.A.alloc((size_t)m_tot * n_pad);
-      arc = arc ? arc : M.Kinv.alloc((size_t)n_pad * n_pad);
-      arc = arc ? arc : M.y.upload(ys[gb], M.N);
-      if (!arc && means && means[gb]) arc = M.mean.upload(means[gb], M.N);
-      arc = arc ? arc : upload_noise(M.nd, noise_kind, noises[gb], M.N);
-    }
-    if (arc == -2) {
-      mem.clear();
-      inv.release();
-      res.release();
-      infobuf.release();
-      return singles(b0);
-    }
-    CHECK_RC(arc);
-    int* d_infos = reinterpret_cast<int*>(infobuf.p);
-    SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
-    SGP_HIP(hipMemsetAsync(res.p, 0, sizeof(double) * res_len, s));
-    CHECK_RC(df_scratch(ctx, m_tot, nb, 0, s));
-    SzMask sz;
-    CHECK_RC(sz_upload(ctx, pat.nz, pat.words, s, &sz));
-    // 1. assembly (logpdf_grad_core's)
-    DfProb probs[DF_MAX_BATCH];
-    const double* rinv[DF_MAX_BATCH];
-    double* kinv[DF_MAX_BATCH];
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      CHECK_RC(assemble(M.g.ds, M.A.p, m_tot, 0, T_c, 0, T_c, 1, M.nd.kind, M.nd.sigma2, M.nd.diag.p, s));
-      CHECK_RC(launch_fill_pad(M.A.p, m_tot, M.N, n_pad, 0, n_pad, m_tot, 0, s));
-      CHECK_RC(launch_grad_border(M.A.p, m_tot, n_pad, M.N, M.y.p, M.mean.p, TILE + n_pad, s));
-      probs[b] = DfProb{M.A.p, inv.p + (size_t)b * T_c * INVD_STRIDE, res.p + M.off, d_infos + b};
-      rinv[b] = M.A.p + n_pad + TILE;
-      kinv[b] = M.Kinv.p;
-    }
-    // 2. one pooled factorisation: the factors and inv(L)' of every member
-    CHECK_RC(launch_chol_dataflow_batch(probs, nb, m_tot, n_pad, m_tot, ctx->d_df_state,
-                                        ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s,
-                                        sz.d_nz, sz.words));
-    // 3. one launch: C^-1 = inv(L)' inv(L), lower tiles, every member
-    CHECK_RC(launch_gemm_nt_uut_batch(rinv, m_tot, kinv, n_pad, n_pad, nb, s));
-    // 4. + 5. per member, in the single call's order
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      double* sm = res.p + M.off;
-      double* alpha = sm + T_c + 8;
-      double* gn = alpha + n_pad;
-      double* gc = gn + n_pad;
-      double* gs = gc + M.nt;
-      const double* zrow = M.A.p + n_pad;
-      CHECK_RC(launch_rowsumsq(zrow, m_tot, M.N, 1, sm + T_c + 1, 0, s));
-      CHECK_RC(launch_sum_array(sm, T_c, sm + T_c, s));
-      CHECK_RC(launch_logpdf_final(sm + T_c, sm + T_c + 1, M.N, 1, sm + T_c + 2, s));
-      CHECK_RC(launch_gemv_rows(rinv[b], m_tot, M.N, n_pad, zrow, m_tot, nullptr, alpha, s, 1));
-      CHECK_RC(launch_mirror_lower(M.Kinv.p, n_pad, n_pad, s));
-      if (out_of(grad_noise, b0 + b))
-        CHECK_RC(launch_grad_noise(M.Kinv.p, n_pad, alpha, M.N, M.nd.kind == SGP_NOISE_DIAG, gn, s));
-      if (out_of(grad_coef, b0 + b) || out_of(grad_inscale, b0 + b))
-        CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, n_pad, alpha, T_c, T_c, M.part, gc, gs, s));
-    }
-    std::vector<double> h_res((size_t)res_len);
-    std::vector<int> h_info((size_t)nb);
-    int h_abort = 0;
-    SGP_HIP(hipMemcpyAsync(h_res.data(), res.p, sizeof(double) * h_res.size(), hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipMemcpyAsync(&h_abort, ctx->d_df_state + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipStreamSynchronize(s));
-    // the abort word is shared by every member of the launch: once raised, no member's result is complete, whatever its
-    // own info says -- the call reports the time-out and with_df_fallback reruns it on the launch-based schedule
-    bool timed_out = h_abort != 0;
-    for (int b = 0; b < nb; ++b) timed_out = timed_out || h_info[(size_t)b] == SGP_DF_TIMEOUT;
-    if (timed_out) {
-      ctx->df_timed_out = true;
-      set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
-      return -3;
-    }
-    for (int b = 0; b < nb; ++b) {
-      const Member& M = mem[(size_t)b];
-      const int gb = b0 + b;
-      const int info = h_info[(size_t)b];
-      if (info > 0) {
-        note_bad(gb, info);
-        continue;
-      }
-      const double* sm = h_res.data() + M.off;
-      const double* ha = sm + T_c + 8;
-      const double* hn = ha + n_pad;
-      const double* hc = hn + n_pad;
-      const double* hs = hc + M.nt;
-      const long nterms = (long)M.g.ds->h_terms.size();
-      logpdf_out[gb] = sm[T_c + 2];
-      if (double* o = out_of(grad_y, gb))
-        for (long i = 0; i < M.N; ++i) o[i] = -ha[i];
-      if (double* o = out_of(grad_mean, gb))
-        for (long i = 0; i < M.N; ++i) o[i] = ha[i];
-      if (double* o = out_of(grad_noise, gb)) std::copy(hn, hn + (M.nd.kind == SGP_NOISE_DIAG ? M.N : 1), o);
-      if (double* o = out_of(grad_coef, gb)) std::copy(hc, hc + nterms, o);
-      if (double* o = out_of(grad_inscale, gb)) std::copy(hs, hs + nterms, o);
-    }
-  }
-  return infos ? 0 : first_bad;
+  int rc() const { return infos ? 0 : first_bad; }
+};
+
+// the geometry of a member of N >= 1 rows, as its own call lays it out (value: sgp_geometry(N, 1); gradient: logpdf_grad_core's,
+// the identity rows below the border)
+void pool_geometry(long N, bool grad, long* n_pad, long* m_tot) {
+  int64_t np = 0, mt = 0;
+  sgp_geometry(N, 1, &np, &mt);
+  *n_pad = np;
+  *m_tot = grad ? 2 * np + TILE : mt;
 }
-// (the C entry point, sgp_logpdf_grad_batch, is in batch_entry.hip: libsthenomi_batch.so, include/sthenomi_batch.h)
-int sgp::drv_logpdf_grad_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
-                               int noise_kind, const double* const* noises, const double* const* ys, double* logpdf_out,
-                               double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
-                               double* const* grad_coef, double* const* grad_inscale, int* infos) {
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_batch_impl(ctx, nspec, specs, means, noise_kind, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise,
-                                  grad_coef, grad_inscale, infos);
-  });
+// can member b run in a pooled launch (and its geometry)?  Otherwise -- dense noise, sizes beyond SGP_BATCH_MAX_N or, for the
+// gradient, sizes its own call factors with the hybrid schedule, a multi-GPU context -- it goes through its own call.
+bool poolable(const sgp_ctx* ctx, const PoolCall& call, int b, long* n_pad, long* m_tot) {
+  const long N = spec_rows_host(call.specs[b]);
+  const int kind = call.kind_of(b);
+  if (ctx->multi || ctx->dataflow == 0 || ctx->batch_max_n <= 0 || N < 1 || (kind != SGP_NOISE_SCALAR && kind != SGP_NOISE_DIAG))
+    return false;
+  pool_geometry(N, call.grad, n_pad, m_tot);
+  return *n_pad <= ctx->batch_max_n && (!call.grad || *n_pad < ctx->hybrid_grow_min_n);
 }
 
-// ---------------------------------------------------------------------------------------
-// ragged pools (include/sthenomi_pool.h): independent models of DIFFERENT sizes and noise kinds in one call
-// ---------------------------------------------------------------------------------------
-// The loops that evaluate one model on data sets of different sizes -- folds that straddle a tile boundary, learning curves,
-// one GP per series (the reference's examples/getting_started/script.jl:154-213 runs them member by member) -- fall off the
-// equal-size batch's pool entirely.  Here every poolable member is assembled exactly as its own call assembles it (its own
-// n_pad, m_tot, leading dimension) and ONE launch of the ragged dataflow kernel (chol_df.hip: chol_pool_kernel, task order
-// df_pool.h) factors up to DF_MAX_BATCH of them; the reductions behind it are each member's own, in its own call's order: every
-// output is bit-equal to the member's own call.
-namespace {
+// the launch of one chunk.  Members of one shape: the ragged task order IS the equal-size round robin (df_pool.h), and that
+// kernel needs no table: this shape class takes it (8 members at N = 4096 through the ragged kernel: 5.19 ms against 5.15 --
+// profiles/r09_pool.json).  Otherwise the ragged kernel: task table (host-built, uploaded on s), progress words, launch.
+// `order` and `d_order` stay alive until the caller has drained s.
+int pool_launch(sgp_ctx* ctx, const DfPoolMember* pm, int nb, std::vector<uint32_t>& order, DevBuf& d_order, hipStream_t s) {
+  int T_r[DF_MAX_BATCH], T_c[DF_MAX_BATCH];
+  bool equal = true;
+  for (int b = 0; b < nb; ++b) {
+    T_r[b] = pm[b].T_r;
+    T_c[b] = pm[b].T_c;
+    equal = equal && T_r[b] == T_r[0] && T_c[b] == T_c[0] && pm[b].ld == pm[0].ld && pm[b].nz == pm[0].nz && pm[b].nzw == pm[0].nzw;
+  }
+  if (equal) {
+    DfProb probs[DF_MAX_BATCH];
+    for (int b = 0; b < nb; ++b) probs[b] = pm[b].p;
+    const long m_tot = (long)T_r[0] * TILE;
+    CHECK_RC(df_scratch_state(ctx, df_state_words(m_tot, nb), s));
+    return launch_chol_dataflow_batch(probs, nb, pm[0].ld, (long)T_c[0] * TILE, m_tot, ctx->d_df_state,
+                                      ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s,
+                                      pm[0].nz, pm[0].nzw);
+  }
+  CHECK_ARG(df_pool_order(T_r, T_c, nb, order), "pool: a member's tile grid does not fit the task table");
+  CHECK_RC(d_order.alloc((order.size() + 1) / 2));   // (32-bit entries inside doubles' storage)
+  SGP_HIP(hipMemcpyAsync(d_order.p, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
+  CHECK_RC(df_scratch_state(ctx, df_pool_state_words(pm, nb), s));
+  return launch_chol_pool(pm, nb, ctx->d_df_state, reinterpret_cast<const uint32_t*>(d_order.p), (long)order.size(),
+                          ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s);
+}
+
+struct PoolMember {
+  SpecGuard g;
+  DevBuf A, Kinv, mean, y, part;   // (Kinv, part: gradient only)
+  NoiseDev nd;
+  long N = 0, n_pad = 0, m_tot = 0, T_c = 0, nt = 0;
+  long off = 0, inv_off = 0;   // the member's results / inverse diagonal blocks in the chunk's buffers
+  size_t pat = 0;              // gradient: its border pattern among the chunk's
+};
+struct BorderPattern {   // the gradient border of a dense K (sz_pattern.h) at one padded size
+  long n_pad, off;       // off: its first word in the chunk's one upload
+  int words;
+};
+constexpr int CHUNK_NO_MEMORY = 1;
+
+// ONE pooled launch: the members ids[0 .. nb) of `call` (nb <= DF_MAX_BATCH), each in its own geometry -- assembly as the
+// member's own call does it, one launch that factors them all, then per member the own call's launches in its order (every
+// reduction sums in the same order), one download of all small results.  Returns 0 with the members' outcomes stored in
+// `call` (their padded sizes appended to `sizes`), CHUNK_NO_MEMORY when the device memory did not suffice -- nothing is
+// stored, the stream is drained and the caller runs its own fallback -- or an error (-3: the launch timed out).
+int pooled_chunk(sgp_ctx* ctx, PoolCall& call, const int* ids, int nb, std::vector<long>* sizes) {
+  hipStream_t s = ctx->stream;
+  const bool grad = call.grad;
+  std::vector<PoolMember> mem((size_t)nb);
+  DevBuf inv, res, infobuf, d_order;
+  std::vector<uint32_t> order;
+  // per member in `res`: [T_c] logdet slots | logdet | |L^-1 (y - m)|^2 | logpdf | (pad to T_c + 8), and for the gradient
+  // | alpha [n_pad] | noise gradient [n_pad] | d coef [nt] | d inscale [nt]
+  long res_len = 0, inv_len = 0;
+  // gradient: one border pattern per distinct padded size of the chunk, all in one upload
+  std::vector<sz_word> h_pat;
+  std::vector<BorderPattern> pats;
+  for (int b = 0; b < nb; ++b) {
+    PoolMember& M = mem[(size_t)b];
+    const sgp_cov_spec* sp = call.specs[ids[b]];
+    M.N = spec_rows_host(sp);
+    pool_geometry(M.N, grad, &M.n_pad, &M.m_tot);
+    M.T_c = M.n_pad / TILE;
+    M.nt = std::max<long>(1, sp->term_ptr ? sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks] : 0);
+    M.off = res_len;
+    M.inv_off = inv_len;
+    res_len += M.T_c + 8 + (grad ? 2 * M.n_pad + 2 * M.nt : 0);
+    inv_len += M.T_c * INVD_STRIDE;
+    if (!grad) continue;
+    while (M.pat < pats.size() && pats[M.pat].n_pad != M.n_pad) ++M.pat;
+    if (M.pat == pats.size()) {
+      SzPattern pat;
+      sz_symbolic(std::vector<char>(1, 1), 1, std::vector<long>(1, 0), std::vector<long>(1, M.n_pad), M.n_pad, TILE, M.T_c,
+                  M.m_tot / TILE, pat, true);
+      pats.push_back(BorderPattern{M.n_pad, (long)h_pat.size(), pat.words});
+      h_pat.insert(h_pat.end(), pat.nz.begin(), pat.nz.end());
+    }
+  }
+  // device memory: an allocation that fails before anything of this chunk is needed hands the chunk back to the caller
+  int arc = inv.alloc((size_t)inv_len);
+  arc = arc ? arc : res.alloc((size_t)res_len);
+  arc = arc ? arc : infobuf.alloc((size_t)nb);   // (ints inside doubles' storage)
+  int* d_infos = reinterpret_cast<int*>(infobuf.p);
+  if (!arc) SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
+  if (!arc && grad) {
+    SGP_HIP(hipMemsetAsync(res.p, 0, sizeof(double) * res_len, s));
+    arc = sz_stage(ctx, h_pat, s);   // (ctx->d_sz; pinned staging: the copy is asynchronous)
+  }
+  // 1. assembly, member by member: the next member's uploads (its spec among them) run under the assembly of the one before
+  // (no structural zeros of the members' own models inside a pooled launch: they need not share a pattern, and these sizes are
+  // chain-bound anyway)
+  DfPoolMember pm[DF_MAX_BATCH];
+  for (int b = 0; b < nb && !arc; ++b) {
+    PoolMember& M = mem[(size_t)b];
+    const int gb = ids[b];
+    arc = dspec_create(ctx, call.specs[gb], &M.g.ds);
+    // (the result layout counted the terms from the host spec, before dspec_create had validated it)
+    if (!arc) CHECK_ARG((long)M.g.ds->h_terms.size() <= M.nt && M.g.ds->N == M.N, "pooled member: the device spec disagrees with the host spec's rows / terms");
+    arc = arc ? arc : M.A.alloc((size_t)M.m_tot * M.n_pad);
+    if (!arc && grad) arc = M.Kinv.alloc((size_t)M.n_pad * M.n_pad);
+    arc = arc ? arc : M.y.upload(call.ys[gb], M.N);
+    if (!arc && call.means && call.means[gb]) arc = M.mean.upload(call.means[gb], M.N);
+    arc = arc ? arc : upload_noise(M.nd, call.kind_of(gb), call.noises[gb], M.N);
+    if (arc) break;
+    if (grad) {
+      CHECK_RC(assemble(M.g.ds, M.A.p, M.m_tot, 0, M.T_c, 0, M.T_c, 1, M.nd.kind, M.nd.sigma2, M.nd.diag.p, s));
+      CHECK_RC(launch_fill_pad(M.A.p, M.m_tot, M.N, M.n_pad, 0, M.n_pad, M.m_tot, 0, s));
+      CHECK_RC(launch_grad_border(M.A.p, M.m_tot, M.n_pad, M.N, M.y.p, M.mean.p, TILE + M.n_pad, s));
+    } else {
+      CHECK_RC(build_bordered(ctx, M.g.ds, M.A.p, M.n_pad, M.m_tot, M.mean.p, M.nd.kind, M.nd.sigma2, M.nd.diag.p, nullptr, 0,
+                              M.y.p, M.N, 1, s, nullptr));
+    }
+    pm[b] = DfPoolMember{DfProb{M.A.p, inv.p + M.inv_off, res.p + M.off, d_infos + b}, M.m_tot, (int)(M.m_tot / TILE), (int)M.T_c,
+                         grad ? ctx->d_sz + pats[M.pat].off : nullptr, grad ? pats[M.pat].words : 0};
+  }
+  if (arc == -2) {
+    SGP_HIP(hipStreamSynchronize(s));   // (assemblies of the members that did fit may still be running on their buffers)
+    return CHUNK_NO_MEMORY;
+  }
+  CHECK_RC(arc);
+  // 2. one launch: the factors (and, for the gradient, inv(L)') of every member
+  CHECK_RC(pool_launch(ctx, pm, nb, order, d_order, s));
+  // 3. gradient: C^-1 = inv(L)' inv(L), lower tiles -- one launch per distinct padded size (the single call's dense tile program)
+  for (size_t k = 0; k < pats.size(); ++k) {
+    const double* rinv[DF_MAX_BATCH];
+    double* kinv[DF_MAX_BATCH];
+    int ng = 0;
+    for (const PoolMember& M : mem) {
+      if (M.pat != k) continue;
+      rinv[ng] = M.A.p + M.n_pad + TILE;
+      kinv[ng] = M.Kinv.p;
+      ++ng;
+    }
+    const long n_pad = pats[k].n_pad;
+    CHECK_RC(launch_gemm_nt_uut_batch(rinv, 2 * n_pad + TILE, kinv, n_pad, n_pad, ng, s));
+  }
+  // 4. per member, in the single call's order
+  for (int b = 0; b < nb; ++b) {
+    PoolMember& M = mem[(size_t)b];
+    const int gb = ids[b];
+    double* sm = res.p + M.off;
+    const double* zrow = M.A.p + M.n_pad;
+    CHECK_RC(launch_rowsumsq(zrow, M.m_tot, M.N, 1, sm + M.T_c + 1, 0, s));
+    CHECK_RC(launch_sum_array(sm, M.T_c, sm + M.T_c, s));
+    CHECK_RC(launch_logpdf_final(sm + M.T_c, sm + M.T_c + 1, M.N, 1, sm + M.T_c + 2, s));
+    if (!grad) continue;
+    double* alpha = sm + M.T_c + 8;
+    double* gn = alpha + M.n_pad;
+    double* gc = gn + M.n_pad;
+    double* gs = gc + M.nt;
+    CHECK_RC(launch_gemv_rows(M.A.p + M.n_pad + TILE, M.m_tot, M.N, M.n_pad, zrow, M.m_tot, nullptr, alpha, s, 1));
+    CHECK_RC(launch_mirror_lower(M.Kinv.p, M.n_pad, M.n_pad, s));
+    if (PoolCall::at(call.grad_noise, gb))
+      CHECK_RC(launch_grad_noise(M.Kinv.p, M.n_pad, alpha, M.N, M.nd.kind == SGP_NOISE_DIAG, gn, s));
+    if (PoolCall::at(call.grad_coef, gb) || PoolCall::at(call.grad_inscale, gb))
+      CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, M.n_pad, alpha, M.T_c, M.T_c, M.part, gc, gs, s));
+  }
+  std::vector<double> h_res((size_t)res_len);
+  std::vector<int> h_info((size_t)nb);
+  int h_abort = 0;
+  SGP_HIP(hipMemcpyAsync(h_res.data(), res.p, sizeof(double) * h_res.size(), hipMemcpyDeviceToHost, s));
+  SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+  SGP_HIP(hipMemcpyAsync(&h_abort, ctx->d_df_state + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  SGP_HIP(hipStreamSynchronize(s));
+  // the abort word is shared by every member of the launch: once raised, no member's result is complete, whatever its own
+  // info says (a member that is already not positive definite loses the CAS that records the time-out in its info)
+  bool timed_out = h_abort != 0;
+  for (int b = 0; b < nb; ++b) timed_out = timed_out || h_info[(size_t)b] == SGP_DF_TIMEOUT;
+  if (timed_out) {
+    ctx->df_timed_out = true;   // (with_df_fallback reruns the call on the launch-based schedule: every member on its own)
+    set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
+    return -3;
+  }
+  for (int b = 0; b < nb; ++b) {
+    const PoolMember& M = mem[(size_t)b];
+    const int gb = ids[b];
+    if (sizes) sizes->push_back(M.n_pad);
+    if (h_info[(size_t)b] > 0) {
+      call.note_bad(gb, h_info[(size_t)b]);
+      continue;
+    }
+    const double* sm = h_res.data() + M.off;
+    call.out[gb] = sm[M.T_c + 2];
+    if (!grad) continue;
+    const double* ha = sm + M.T_c + 8;
+    const double* hn = ha + M.n_pad;
+    const double* hc = hn + M.n_pad;
+    const double* hs = hc + M.nt;
+    const long nterms = (long)M.g.ds->h_terms.size();
+    if (double* o = PoolCall::at(call.grad_y, gb))
+      for (long i = 0; i < M.N; ++i) o[i] = -ha[i];
+    if (double* o = PoolCall::at(call.grad_mean, gb))
+      for (long i = 0; i < M.N; ++i) o[i] = ha[i];
+    if (double* o = PoolCall::at(call.grad_noise, gb)) std::copy(hn, hn + (M.nd.kind == SGP_NOISE_DIAG ? M.N : 1), o);
+    if (double* o = PoolCall::at(call.grad_coef, gb)) std::copy(hc, hc + nterms, o);
+    if (double* o = PoolCall::at(call.grad_inscale, gb)) std::copy(hs, hs + nterms, o);
+  }
+  return 0;
+}
+
+// ---- the batch calls: members of ONE padded size, cut into launches in input order
+// do all members pool, in one padded geometry?
+bool batch_pools(const sgp_ctx* ctx, const PoolCall& call, int nspec, long* n_pad = nullptr, long* m_tot = nullptr) {
+  bool pooled = nspec >= 2;
+  long np0 = 0, np = 0, mt = 0;
+  for (int b = 0; b < nspec && pooled; ++b) {
+    pooled = poolable(ctx, call, b, &np, &mt) && (b == 0 || np == np0);
+    np0 = np;
+  }
+  if (n_pad) *n_pad = np;
+  if (m_tot) *m_tot = mt;
+  return pooled;
+}
+// launches of at most `chunk` members; a launch the device memory does not suffice for hands its members and all later ones,
+// [b0, nspec), to singles(b0)
+template <class Singles>
+int batch_chunks(sgp_ctx* ctx, PoolCall& call, int nspec, int chunk, Singles&& singles) {
+  std::vector<int> ids((size_t)std::min(chunk, nspec));
+  for (int b0 = 0; b0 < nspec; b0 += chunk) {
+    const int nb = std::min(chunk, nspec - b0);
+    for (int b = 0; b < nb; ++b) ids[(size_t)b] = b0 + b;
+    const int rc = pooled_chunk(ctx, call, ids.data(), nb, nullptr);
+    if (rc == CHUNK_NO_MEMORY) return singles(b0);
+    CHECK_RC(rc);
+  }
+  return call.rc();
+}
+
+// ---- the pool calls: any sizes and noise kinds
 struct PoolPlan {
   std::vector<int> single;                  // members that run through their own call, input order
   std::vector<std::vector<int>> chunks;     // poolable members, by task count (descending), at most DF_MAX_BATCH per launch
@@ -2282,41 +2249,136 @@ PoolPlan pool_plan(int nspec, Geo&& geo) {
   std::sort(plan.single.begin(), plan.single.end());
   return plan;
 }
-// the ragged launch of one chunk: task table (host-built, uploaded on s), progress words, launch.  `order` and `d_order` stay
-// alive until the caller has drained s.
-int pool_launch(sgp_ctx* ctx, const DfPoolMember* pm, int nb, std::vector<uint32_t>& order, DevBuf& d_order, hipStream_t s) {
-  int T_r[DF_MAX_BATCH], T_c[DF_MAX_BATCH];
-  bool equal = true;
-  for (int b = 0; b < nb; ++b) {
-    T_r[b] = pm[b].T_r;
-    T_c[b] = pm[b].T_c;
-    equal = equal && T_r[b] == T_r[0] && T_c[b] == T_c[0] && pm[b].ld == pm[0].ld && pm[b].nz == pm[0].nz && pm[b].nzw == pm[0].nzw;
-  }
-  if (equal) {
-    // one shape: the ragged order IS the equal-size batch's round robin (df_pool.h), and that kernel needs no table: this
-    // shape class takes it (8 members at N = 4096 through the ragged kernel: 5.19 ms against 5.15 -- profiles/r09_pool.json)
-    DfProb probs[DF_MAX_BATCH];
-    for (int b = 0; b < nb; ++b) probs[b] = pm[b].p;
-    const long m_tot = (long)T_r[0] * TILE;
-    CHECK_RC(df_scratch_state(ctx, df_state_words(m_tot, nb), s));
-    return launch_chol_dataflow_batch(probs, nb, pm[0].ld, (long)T_c[0] * TILE, m_tot, ctx->d_df_state,
-                                      ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s,
-                                      pm[0].nz, pm[0].nzw);
-  }
-  CHECK_ARG(df_pool_order(T_r, T_c, nb, order), "pool: a member's tile grid does not fit the task table");
-  CHECK_RC(d_order.alloc((order.size() + 1) / 2));   // (32-bit entries inside doubles' storage)
-  SGP_HIP(hipMemcpyAsync(d_order.p, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
-  CHECK_RC(df_scratch_state(ctx, df_pool_state_words(pm, nb), s));
-  return launch_chol_pool(pm, nb, ctx->d_df_state, reinterpret_cast<const uint32_t*>(d_order.p), (long)order.size(),
-                          ctx->batch_fat ? ctx->hybrid_wgs : ctx->df_wgs, ctx->df_timeout_s, ctx->batch_fat, s);
-}
 int pool_distinct(const std::vector<long>& sizes) {
   std::vector<long> u(sizes);
   std::sort(u.begin(), u.end());
   return (int)(std::unique(u.begin(), u.end()) - u.begin());
 }
+// the plan of both pool calls (the arguments are checked): the members that do not pool through their own calls, then one
+// launch per chunk; a launch the device memory does not suffice for hands its chunk and the later ones to their own calls
+int pool_run(sgp_ctx* ctx, PoolCall& call, int nspec, sgp_pool_report* report) {
+  sgp_pool_report rep = {0, 0, 0, 0};
+  if (report) *report = rep;
+  const PoolPlan plan = pool_plan(nspec, [&](int b, long* n_pad, long* m_tot) { return poolable(ctx, call, b, n_pad, m_tot); });
+  auto run_single = [&](int b) -> int {
+    const int rc = call.own_call(ctx, b);
+    if (rc < 0) return rc;
+    if (rc > 0) call.note_bad(b, rc);
+    rep.single_members += 1;
+    return 0;
+  };
+  for (int b : plan.single) CHECK_RC(run_single(b));
+  std::vector<long> sizes;
+  CtxScope scope(ctx);
+  for (size_t c = 0; c < plan.chunks.size(); ++c) {
+    const std::vector<int>& ids = plan.chunks[c];
+    const int rc = pooled_chunk(ctx, call, ids.data(), (int)ids.size(), &sizes);
+    if (rc == CHUNK_NO_MEMORY) {
+      std::vector<int> rest;
+      for (size_t c2 = c; c2 < plan.chunks.size(); ++c2) rest.insert(rest.end(), plan.chunks[c2].begin(), plan.chunks[c2].end());
+      std::sort(rest.begin(), rest.end());
+      for (int b : rest) CHECK_RC(run_single(b));
+      break;
+    }
+    CHECK_RC(rc);
+    rep.pool_launches += 1;
+    rep.pooled_members += (int)ids.size();
+  }
+  rep.distinct_sizes = pool_distinct(sizes);
+  if (report) *report = rep;
+  return call.rc();
+}
 }  // namespace
 
+// sgp_logpdf_batch (include/sthenomi.h).  Members of different padded sizes, dense noise, sizes outside the batched range, a
+// multi-GPU context: one after the other through sgp_logpdf's own path.
+static int logpdf_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                             int noise_kind, const double* const* noises, const double* const* ys, double* out, int* infos) {
+  CHECK_ARG(ctx && specs && noises && ys && out && nspec >= 1, "sgp_logpdf_batch: NULL argument");
+  for (int b = 0; b < nspec; ++b) {
+    CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_batch: NULL member");
+    CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_batch: specs must be symmetric");
+    if (infos) infos[b] = 0;
+  }
+  PoolCall call{"batch", false, specs, means, nullptr, noise_kind, noises, ys, out, nullptr, nullptr, nullptr, nullptr, nullptr, infos};
+  // members [b0, nspec) one by one through their own call (whose error text stands)
+  auto singles = [&](int b0) -> int {
+    for (int b = b0; b < nspec; ++b) {
+      const int rc = call.own_call(ctx, b);
+      if (rc < 0) return rc;
+      if (rc > 0) call.mark_bad(b, rc);
+    }
+    return call.rc();
+  };
+  if (!batch_pools(ctx, call, nspec)) return singles(0);
+  CtxScope scope(ctx);
+  return batch_chunks(ctx, call, nspec, DF_MAX_BATCH, singles);
+}
+extern "C" int sgp_logpdf_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                                int noise_kind, const double* const* noises, const double* const* ys, double* out, int* infos) {
+  return with_df_fallback(ctx, [&]() { return logpdf_batch_impl(ctx, nspec, specs, means, noise_kind, noises, ys, out, infos); });
+}
+
+// sgp_logpdf_grad_batch (include/sthenomi_batch.h) -- the optimiser loops of hyper-parameter learning run value AND gradient.
+// Everything that does not pool (different padded sizes, dense noise, sizes the single call factors with the hybrid schedule
+// or beyond SGP_BATCH_MAX_N, a multi-GPU context) goes member by member through sgp_logpdf_grad.
+static int logpdf_grad_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                                  int noise_kind, const double* const* noises, const double* const* ys, double* logpdf_out,
+                                  double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
+                                  double* const* grad_coef, double* const* grad_inscale, int* infos) {
+  CHECK_ARG(ctx && specs && noises && ys && logpdf_out && nspec >= 1, "sgp_logpdf_grad_batch: NULL argument");
+  CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad_batch: bad noise kind");
+  for (int b = 0; b < nspec; ++b) {
+    CHECK_ARG(specs[b] && noises[b] && ys[b], "sgp_logpdf_grad_batch: NULL member");
+    CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_grad_batch: specs must be symmetric");
+    CHECK_ARG(!spec_has_stencil(ctx, specs[b]), "sgp_logpdf_grad_batch: gradients through stencil terms are not supported");
+    CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_batch: gradients through patch (convolutional) terms are not supported");
+    if (infos) infos[b] = 0;
+  }
+  PoolCall call{"batch", true, specs, means, nullptr, noise_kind, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                grad_inscale, infos};
+  // members [b0, nspec) one by one through their own call
+  auto singles = [&](int b0) -> int {
+    for (int b = b0; b < nspec; ++b) {
+      const int rc = call.own_call(ctx, b);
+      if (rc < 0) return rc;
+      if (rc > 0) call.note_bad(b, rc);
+    }
+    return call.rc();
+  };
+  long n_pad = 0, m_tot = 0;
+  if (!batch_pools(ctx, call, nspec, &n_pad, &m_tot)) return singles(0);
+  CtxScope scope(ctx);
+  // chunk size from the device memory left (the unused blocks of the context's cache count as free)
+  const long T_c = n_pad / TILE;
+  const double member_bytes =
+      8.0 * ((double)m_tot * n_pad + (double)n_pad * n_pad + (double)T_c * INVD_STRIDE + 16.0 * T_c * T_c + 8.0 * n_pad);
+  int chunk = DF_MAX_BATCH;
+  {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      double avail = (double)free_b;
+      for (const auto& pb : ctx->pool)
+        if (!pb.used) avail += (double)pb.bytes;
+      chunk = (int)std::max(1.0, std::min((double)DF_MAX_BATCH, 0.9 * avail / member_bytes));
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  return batch_chunks(ctx, call, nspec, chunk, singles);
+}
+// (the C entry point, sgp_logpdf_grad_batch, is in batch_entry.hip: libsthenomi_batch.so, include/sthenomi_batch.h)
+int sgp::drv_logpdf_grad_batch(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
+                               int noise_kind, const double* const* noises, const double* const* ys, double* logpdf_out,
+                               double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
+                               double* const* grad_coef, double* const* grad_inscale, int* infos) {
+  return with_df_fallback(ctx, [&]() {
+    return logpdf_grad_batch_impl(ctx, nspec, specs, means, noise_kind, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise,
+                                  grad_coef, grad_inscale, infos);
+  });
+}
+
+// sgp_logpdf_pool (include/sthenomi_pool.h)
 static int logpdf_pool_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
                             const int* kinds, const double* const* noises, const double* const* ys, double* out, int* infos,
                             sgp_pool_report* report) {
@@ -2327,138 +2389,8 @@ static int logpdf_pool_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* 
     CHECK_ARG(kinds[b] >= SGP_NOISE_SCALAR && kinds[b] <= SGP_NOISE_DENSE, "sgp_logpdf_pool: bad noise kind");
     if (infos) infos[b] = 0;
   }
-  sgp_pool_report rep = {0, 0, 0, 0};
-  if (report) *report = rep;
-  const bool pool_on = !ctx->multi && ctx->dataflow != 0 && ctx->batch_max_n > 0;
-  const PoolPlan plan = pool_plan(nspec, [&](int b, long* n_pad, long* m_tot) {
-    const long N = spec_rows_host(specs[b]);
-    if (!pool_on || N < 1 || (kinds[b] != SGP_NOISE_SCALAR && kinds[b] != SGP_NOISE_DIAG)) return false;
-    int64_t np = 0, mt = 0;
-    sgp_geometry(N, 1, &np, &mt);
-    *n_pad = np;
-    *m_tot = mt;
-    return np <= ctx->batch_max_n;
-  });
-  int first_bad = 0;
-  auto note_bad = [&](int b, int info) {
-    out[b] = std::numeric_limits<double>::quiet_NaN();
-    if (infos) infos[b] = info;
-    if (!first_bad) {
-      first_bad = info;
-      set_error("matrix is not positive definite; Cholesky factorization failed at leading minor " + std::to_string(info) +
-                " (pool member " + std::to_string(b) + ")");
-    }
-  };
-  auto run_single = [&](int b) -> int {
-    const int rc = sgp_logpdf(ctx, specs[b], means ? means[b] : nullptr, kinds[b], noises[b], ys[b], spec_rows_host(specs[b]), 1,
-                              out + b);
-    if (rc < 0) return rc;
-    if (rc > 0) note_bad(b, rc);
-    rep.single_members += 1;
-    return 0;
-  };
-  for (int b : plan.single) CHECK_RC(run_single(b));
-  std::vector<long> sizes;
-  CtxScope scope(ctx);
-  hipStream_t s = ctx->stream;
-  struct Member {
-    SpecGuard g;
-    DevBuf A, mean, y;
-    NoiseDev nd;
-    long N = 0, n_pad = 0, m_tot = 0, T_c = 0, off = 0, inv_off = 0;
-  };
-  for (size_t c = 0; c < plan.chunks.size(); ++c) {
-    const std::vector<int>& ids = plan.chunks[c];
-    const int nb = (int)ids.size();
-    std::vector<Member> mem((size_t)nb);
-    DevBuf inv, small, infobuf, d_order;
-    std::vector<uint32_t> order;
-    // per member in `small`: logdet slots [T_c] | logdet | |L^-1 (y - m)|^2 | logpdf | (pad to T_c + 8)
-    long small_len = 0, inv_len = 0;
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      CHECK_RC(dspec_create(ctx, specs[ids[b]], &M.g.ds));
-      M.N = M.g.ds->N;
-      int64_t np = 0, mt = 0;
-      sgp_geometry(M.N, 1, &np, &mt);
-      M.n_pad = np;
-      M.m_tot = mt;
-      M.T_c = np / TILE;
-      M.off = small_len;
-      M.inv_off = inv_len;
-      small_len += M.T_c + 8;
-      inv_len += M.T_c * INVD_STRIDE;
-    }
-    // device memory: an allocation that fails hands this chunk's and the later chunks' members to their own calls
-    int arc = inv.alloc((size_t)inv_len);
-    arc = arc ? arc : small.alloc((size_t)small_len);
-    arc = arc ? arc : infobuf.alloc((size_t)nb);   // (ints inside doubles' storage)
-    int* d_infos = reinterpret_cast<int*>(infobuf.p);
-    if (!arc) SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
-    DfPoolMember pm[DF_MAX_BATCH];
-    // (member by member: the next member's uploads run under the assembly of the one before, as in the equal-size batch)
-    for (int b = 0; b < nb && !arc; ++b) {
-      Member& M = mem[(size_t)b];
-      const int gb = ids[b];
-      arc = M.A.alloc((size_t)M.m_tot * M.n_pad);
-      arc = arc ? arc : M.y.upload(ys[gb], M.N);
-      if (!arc && means && means[gb]) arc = M.mean.upload(means[gb], M.N);
-      arc = arc ? arc : upload_noise(M.nd, kinds[gb], noises[gb], M.N);
-      if (arc) break;
-      // (no structural zeros of the members' own models inside a pool, as in the equal-size batch)
-      CHECK_RC(build_bordered(ctx, M.g.ds, M.A.p, M.n_pad, M.m_tot, M.mean.p, M.nd.kind, M.nd.sigma2, M.nd.diag.p, nullptr, 0,
-                              M.y.p, M.N, 1, s, nullptr));
-      pm[b] = DfPoolMember{DfProb{M.A.p, inv.p + M.inv_off, small.p + M.off, d_infos + b}, M.m_tot, (int)(M.m_tot / TILE),
-                           (int)M.T_c, nullptr, 0};
-    }
-    if (arc == -2) {
-      SGP_HIP(hipStreamSynchronize(s));   // (assemblies of the members that did fit may still be running on their buffers)
-      mem.clear();
-      inv.release();
-      small.release();
-      infobuf.release();
-      std::vector<int> rest;
-      for (size_t c2 = c; c2 < plan.chunks.size(); ++c2) rest.insert(rest.end(), plan.chunks[c2].begin(), plan.chunks[c2].end());
-      std::sort(rest.begin(), rest.end());
-      for (int b : rest) CHECK_RC(run_single(b));
-      break;
-    }
-    CHECK_RC(arc);
-    CHECK_RC(pool_launch(ctx, pm, nb, order, d_order, s));
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      double* sm = small.p + M.off;
-      CHECK_RC(launch_rowsumsq(M.A.p + M.n_pad, M.m_tot, M.N, 1, sm + M.T_c + 1, 0, s));
-      CHECK_RC(launch_sum_array(sm, M.T_c, sm + M.T_c, s));
-      CHECK_RC(launch_logpdf_final(sm + M.T_c, sm + M.T_c + 1, M.N, 1, sm + M.T_c + 2, s));
-    }
-    std::vector<double> h_small((size_t)small_len);
-    std::vector<int> h_info((size_t)nb);
-    int h_abort = 0;
-    SGP_HIP(hipMemcpyAsync(h_small.data(), small.p, sizeof(double) * h_small.size(), hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipMemcpyAsync(&h_abort, ctx->d_df_state + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipStreamSynchronize(s));
-    // the abort word is shared by the whole launch: once raised no member's result is complete, whatever its own info says
-    bool timed_out = h_abort != 0;
-    for (int b = 0; b < nb; ++b) timed_out = timed_out || h_info[(size_t)b] == SGP_DF_TIMEOUT;
-    if (timed_out) {
-      ctx->df_timed_out = true;   // (with_df_fallback reruns the call on the launch-based schedule: every member on its own)
-      set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
-      return -3;
-    }
-    for (int b = 0; b < nb; ++b) {
-      const Member& M = mem[(size_t)b];
-      out[ids[b]] = h_small[(size_t)(M.off + M.T_c + 2)];
-      if (h_info[(size_t)b] > 0) note_bad(ids[b], h_info[(size_t)b]);
-      sizes.push_back(M.n_pad);
-    }
-    rep.pool_launches += 1;
-    rep.pooled_members += nb;
-  }
-  rep.distinct_sizes = pool_distinct(sizes);
-  if (report) *report = rep;
-  return infos ? 0 : first_bad;
+  PoolCall call{"pool", false, specs, means, kinds, 0, noises, ys, out, nullptr, nullptr, nullptr, nullptr, nullptr, infos};
+  return pool_run(ctx, call, nspec, report);
 }
 int sgp::drv_logpdf_pool(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
                          const int* noise_kinds, const double* const* noises, const double* const* ys, double* out, int* infos,
@@ -2466,10 +2398,7 @@ int sgp::drv_logpdf_pool(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* spe
   return with_df_fallback(ctx, [&]() { return logpdf_pool_impl(ctx, nspec, specs, means, noise_kinds, noises, ys, out, infos, report); });
 }
 
-// value + gradient: logpdf_grad_batch_impl's steps with every member in its own geometry -- one ragged launch factors every
-// member's [K + Sigma_y ; (y - m)' ; I] with the border pattern of its own padded size (one sz_symbolic per distinct size, one
-// upload of them all), C^-1 = inv(L)' inv(L) is one launch per distinct padded size, then per member the single call's launches
-// in its order.
+// sgp_logpdf_grad_pool (include/sthenomi_pool.h)
 static int logpdf_grad_pool_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
                                  const int* kinds, const double* const* noises, const double* const* ys, double* logpdf_out,
                                  double* const* grad_y, double* const* grad_mean, double* const* grad_noise,
@@ -2483,209 +2412,9 @@ static int logpdf_grad_pool_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* co
     CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_pool: gradients through patch (convolutional) terms are not supported");
     if (infos) infos[b] = 0;
   }
-  sgp_pool_report rep = {0, 0, 0, 0};
-  if (report) *report = rep;
-  auto out_of = [](double* const* v, int b) { return v ? v[b] : nullptr; };
-  const bool pool_on = !ctx->multi && ctx->dataflow != 0 && ctx->batch_max_n > 0;
-  const PoolPlan plan = pool_plan(nspec, [&](int b, long* n_pad, long* m_tot) {
-    const long N = spec_rows_host(specs[b]);
-    if (!pool_on || N < 1 || (kinds[b] != SGP_NOISE_SCALAR && kinds[b] != SGP_NOISE_DIAG)) return false;
-    *n_pad = rup(N, TILE);
-    *m_tot = 2 * *n_pad + TILE;   // logpdf_grad_core's geometry
-    return *n_pad <= ctx->batch_max_n && *n_pad < ctx->hybrid_grow_min_n;
-  });
-  int first_bad = 0;
-  auto note_bad = [&](int b, int info) {
-    logpdf_out[b] = std::numeric_limits<double>::quiet_NaN();
-    if (infos) infos[b] = info;
-    if (!first_bad) {
-      first_bad = info;
-      set_error("matrix is not positive definite; Cholesky factorization failed at leading minor " + std::to_string(info) +
-                " (pool member " + std::to_string(b) + ")");
-    }
-  };
-  auto run_single = [&](int b) -> int {
-    const int rc = sgp_logpdf_grad(ctx, specs[b], means ? means[b] : nullptr, kinds[b], noises[b], ys[b], logpdf_out + b,
-                                   out_of(grad_y, b), out_of(grad_mean, b), out_of(grad_noise, b), out_of(grad_coef, b),
-                                   out_of(grad_inscale, b));
-    if (rc < 0) return rc;
-    if (rc > 0) note_bad(b, rc);
-    rep.single_members += 1;
-    return 0;
-  };
-  for (int b : plan.single) CHECK_RC(run_single(b));
-  std::vector<long> sizes;
-  CtxScope scope(ctx);
-  hipStream_t s = ctx->stream;
-  struct Member {
-    SpecGuard g;
-    DevBuf A, Kinv, mean, y, part;
-    NoiseDev nd;
-    long N = 0, n_pad = 0, m_tot = 0, T_c = 0, nt = 0, off = 0, inv_off = 0, pat_off = 0;
-    int pat_words = 0;
-  };
-  for (size_t c = 0; c < plan.chunks.size(); ++c) {
-    const std::vector<int>& ids = plan.chunks[c];
-    const int nb = (int)ids.size();
-    std::vector<Member> mem((size_t)nb);
-    DevBuf inv, res, infobuf, d_order, d_pat;
-    std::vector<uint32_t> order;
-    // per member in `res`: [T_c] logdet slots | logdet | |z|^2 | logpdf | (pad to T_c + 8) | alpha [n_pad] | noise gradient
-    // [n_pad] | d coef [nt] | d inscale [nt]
-    long res_len = 0, inv_len = 0;
-    // the border pattern of a dense K (sz_pattern.h), one per distinct padded size of the chunk, all in one upload
-    std::vector<sz_word> h_pat;
-    std::vector<long> pat_size, pat_off;
-    std::vector<int> pat_words;
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      CHECK_RC(dspec_create(ctx, specs[ids[b]], &M.g.ds));
-      M.N = M.g.ds->N;
-      M.n_pad = rup(M.N, TILE);
-      M.m_tot = 2 * M.n_pad + TILE;
-      M.T_c = M.n_pad / TILE;
-      M.nt = std::max<long>(1, (long)M.g.ds->h_terms.size());
-      M.off = res_len;
-      M.inv_off = inv_len;
-      res_len += M.T_c + 8 + 2 * M.n_pad + 2 * M.nt;
-      inv_len += M.T_c * INVD_STRIDE;
-      size_t k = 0;
-      while (k < pat_size.size() && pat_size[k] != M.n_pad) ++k;
-      if (k == pat_size.size()) {
-        SzPattern pat;
-        sz_symbolic(std::vector<char>(1, 1), 1, std::vector<long>(1, 0), std::vector<long>(1, M.n_pad), M.n_pad, TILE, M.T_c,
-                    M.m_tot / TILE, pat, true);
-        pat_size.push_back(M.n_pad);
-        pat_off.push_back((long)h_pat.size());
-        pat_words.push_back(pat.words);
-        h_pat.insert(h_pat.end(), pat.nz.begin(), pat.nz.end());
-      }
-      M.pat_off = pat_off[k];
-      M.pat_words = pat_words[k];
-    }
-    int arc = inv.alloc((size_t)inv_len);
-    arc = arc ? arc : res.alloc((size_t)res_len);
-    arc = arc ? arc : infobuf.alloc((size_t)nb);   // (ints inside doubles' storage)
-    arc = arc ? arc : d_pat.alloc(h_pat.size());   // (sz_word and double are both 8 bytes)
-    for (int b = 0; b < nb && !arc; ++b) {
-      Member& M = mem[(size_t)b];
-      const int gb = ids[b];
-      arc = M.A.alloc((size_t)M.m_tot * M.n_pad);
-      arc = arc ? arc : M.Kinv.alloc((size_t)M.n_pad * M.n_pad);
-      arc = arc ? arc : M.y.upload(ys[gb], M.N);
-      if (!arc && means && means[gb]) arc = M.mean.upload(means[gb], M.N);
-      arc = arc ? arc : upload_noise(M.nd, kinds[gb], noises[gb], M.N);
-    }
-    if (arc == -2) {
-      mem.clear();
-      inv.release();
-      res.release();
-      infobuf.release();
-      d_pat.release();
-      std::vector<int> rest;
-      for (size_t c2 = c; c2 < plan.chunks.size(); ++c2) rest.insert(rest.end(), plan.chunks[c2].begin(), plan.chunks[c2].end());
-      std::sort(rest.begin(), rest.end());
-      for (int b : rest) CHECK_RC(run_single(b));
-      break;
-    }
-    CHECK_RC(arc);
-    static_assert(sizeof(sz_word) == sizeof(double), "pattern words are stored in a DevBuf");
-    SGP_HIP(hipMemcpy(d_pat.p, h_pat.data(), sizeof(sz_word) * h_pat.size(), hipMemcpyHostToDevice));
-    const sz_word* d_nz = reinterpret_cast<const sz_word*>(d_pat.p);
-    int* d_infos = reinterpret_cast<int*>(infobuf.p);
-    SGP_HIP(hipMemsetAsync(d_infos, 0, sizeof(int) * nb, s));
-    SGP_HIP(hipMemsetAsync(res.p, 0, sizeof(double) * res_len, s));
-    // 1. assembly (logpdf_grad_core's), every member in its own geometry
-    DfPoolMember pm[DF_MAX_BATCH];
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      CHECK_RC(assemble(M.g.ds, M.A.p, M.m_tot, 0, M.T_c, 0, M.T_c, 1, M.nd.kind, M.nd.sigma2, M.nd.diag.p, s));
-      CHECK_RC(launch_fill_pad(M.A.p, M.m_tot, M.N, M.n_pad, 0, M.n_pad, M.m_tot, 0, s));
-      CHECK_RC(launch_grad_border(M.A.p, M.m_tot, M.n_pad, M.N, M.y.p, M.mean.p, TILE + M.n_pad, s));
-      pm[b] = DfPoolMember{DfProb{M.A.p, inv.p + M.inv_off, res.p + M.off, d_infos + b}, M.m_tot, (int)(M.m_tot / TILE),
-                           (int)M.T_c, d_nz + M.pat_off, M.pat_words};
-    }
-    // 2. one ragged launch: the factors and inv(L)' of every member
-    CHECK_RC(pool_launch(ctx, pm, nb, order, d_order, s));
-    // 3. C^-1 = inv(L)' inv(L), lower tiles: one launch per distinct padded size
-    for (size_t k = 0; k < pat_size.size(); ++k) {
-      const double* rinv[DF_MAX_BATCH];
-      double* kinv[DF_MAX_BATCH];
-      int ng = 0;
-      long mt = 0;
-      for (int b = 0; b < nb; ++b) {
-        Member& M = mem[(size_t)b];
-        if (M.n_pad != pat_size[k]) continue;
-        rinv[ng] = M.A.p + M.n_pad + TILE;
-        kinv[ng] = M.Kinv.p;
-        mt = M.m_tot;
-        ++ng;
-      }
-      CHECK_RC(launch_gemm_nt_uut_batch(rinv, mt, kinv, pat_size[k], pat_size[k], ng, s));
-    }
-    // 4. + 5. per member, in the single call's order
-    for (int b = 0; b < nb; ++b) {
-      Member& M = mem[(size_t)b];
-      const int gb = ids[b];
-      double* sm = res.p + M.off;
-      double* alpha = sm + M.T_c + 8;
-      double* gn = alpha + M.n_pad;
-      double* gc = gn + M.n_pad;
-      double* gs = gc + M.nt;
-      const double* zrow = M.A.p + M.n_pad;
-      CHECK_RC(launch_rowsumsq(zrow, M.m_tot, M.N, 1, sm + M.T_c + 1, 0, s));
-      CHECK_RC(launch_sum_array(sm, M.T_c, sm + M.T_c, s));
-      CHECK_RC(launch_logpdf_final(sm + M.T_c, sm + M.T_c + 1, M.N, 1, sm + M.T_c + 2, s));
-      CHECK_RC(launch_gemv_rows(M.A.p + M.n_pad + TILE, M.m_tot, M.N, M.n_pad, zrow, M.m_tot, nullptr, alpha, s, 1));
-      CHECK_RC(launch_mirror_lower(M.Kinv.p, M.n_pad, M.n_pad, s));
-      if (out_of(grad_noise, gb))
-        CHECK_RC(launch_grad_noise(M.Kinv.p, M.n_pad, alpha, M.N, M.nd.kind == SGP_NOISE_DIAG, gn, s));
-      if (out_of(grad_coef, gb) || out_of(grad_inscale, gb))
-        CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, M.n_pad, alpha, M.T_c, M.T_c, M.part, gc, gs, s));
-    }
-    std::vector<double> h_res((size_t)res_len);
-    std::vector<int> h_info((size_t)nb);
-    int h_abort = 0;
-    SGP_HIP(hipMemcpyAsync(h_res.data(), res.p, sizeof(double) * h_res.size(), hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipMemcpyAsync(h_info.data(), d_infos, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipMemcpyAsync(&h_abort, ctx->d_df_state + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SGP_HIP(hipStreamSynchronize(s));
-    bool timed_out = h_abort != 0;   // shared by the whole launch (see logpdf_pool_impl)
-    for (int b = 0; b < nb; ++b) timed_out = timed_out || h_info[(size_t)b] == SGP_DF_TIMEOUT;
-    if (timed_out) {
-      ctx->df_timed_out = true;
-      set_error("dataflow factorisation: a dependency wait inside the kernel ran into its bound (SGP_DF_TIMEOUT_S)");
-      return -3;
-    }
-    for (int b = 0; b < nb; ++b) {
-      const Member& M = mem[(size_t)b];
-      const int gb = ids[b];
-      sizes.push_back(M.n_pad);
-      if (h_info[(size_t)b] > 0) {
-        note_bad(gb, h_info[(size_t)b]);
-        continue;
-      }
-      const double* sm = h_res.data() + M.off;
-      const double* ha = sm + M.T_c + 8;
-      const double* hn = ha + M.n_pad;
-      const double* hc = hn + M.n_pad;
-      const double* hs = hc + M.nt;
-      const long nterms = (long)M.g.ds->h_terms.size();
-      logpdf_out[gb] = sm[M.T_c + 2];
-      if (double* o = out_of(grad_y, gb))
-        for (long i = 0; i < M.N; ++i) o[i] = -ha[i];
-      if (double* o = out_of(grad_mean, gb))
-        for (long i = 0; i < M.N; ++i) o[i] = ha[i];
-      if (double* o = out_of(grad_noise, gb)) std::copy(hn, hn + (M.nd.kind == SGP_NOISE_DIAG ? M.N : 1), o);
-      if (double* o = out_of(grad_coef, gb)) std::copy(hc, hc + nterms, o);
-      if (double* o = out_of(grad_inscale, gb)) std::copy(hs, hs + nterms, o);
-    }
-    rep.pool_launches += 1;
-    rep.pooled_members += nb;
-  }
-  rep.distinct_sizes = pool_distinct(sizes);
-  if (report) *report = rep;
-  return infos ? 0 : first_bad;
+  PoolCall call{"pool", true, specs, means, kinds, 0, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef, grad_inscale,
+                infos};
+  return pool_run(ctx, call, nspec, report);
 }
 int sgp::drv_logpdf_grad_pool(sgp_ctx* ctx, int nspec, const sgp_cov_spec* const* specs, const double* const* means,
                               const int* noise_kinds, const double* const* noises, const double* const* ys, double* logpdf_out,

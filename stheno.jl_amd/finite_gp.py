@@ -242,6 +242,85 @@ def logpdf(fx, y):
     return float(out[0]) if vec else out
 
 
+# ---- the batch / pool calls: what their four host functions share --------------------------------
+def _members(name, fxs, ys, grad, divert_f32):
+    """The member loop of `name` (a batch / pool function): -> (keep, down).  keep[q] = (spec, mean, noise kind, noise
+    buffer, y) of member down[q], alive until the library call returns; with divert_f32 the Float32 models are left out of
+    both (they run through their own call)."""
+    keep, down = [], []
+    for b, (fx, y) in enumerate(zip(fxs, ys)):
+        if isinstance(fx, SparseFiniteGP):
+            raise NotImplementedError(f"{name} takes FiniteGPs (use {'elbo_and_gradient' if grad else 'elbo'} for a SparseFiniteGP)")
+        if grad and not _is_prior(fx.f):
+            raise NotImplementedError("gradients are implemented for prior Stheno processes")
+        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+        if yv.shape[0] != len(fx):
+            raise ValueError("length(y) != length(fx)")
+        f32 = divert_f32 and _is_prior(fx.f) and _is_f32(fx, y)
+        if grad:
+            kind, nbuf = _lib._noise_args(fx.noise, len(fx))
+            spec = _prior_spec(fx.f, fx.x)
+            _refuse_patch_gradient(spec)
+            if f32:
+                continue
+            m = mean_vector(fx.f, fx.x)
+        else:
+            if f32:
+                continue
+            spec, m, kind, nbuf = _spec_mean_noise(fx)
+        keep.append((spec, _f64(m), kind, nbuf, yv))
+        down.append(b)
+    return keep, down
+
+
+def _dptrs(arrs):
+    return (C.POINTER(C.c_double) * len(arrs))(*[_lib.dptr(a) for a in arrs])
+
+
+def _iptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _member_args(keep):
+    """The pointer arrays of a batch / pool call over `keep`: (specs, means, noise kinds, noises, ys)."""
+    nb = len(keep)
+    for k in keep:
+        k[0].ref()           # (patch terms: their geometry ids on the context)
+    return ((C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep]), _dptrs([k[1] for k in keep]),
+            (C.c_int * nb)(*[int(k[2]) for k in keep]), _dptrs([k[3] for k in keep]), _dptrs([k[4] for k in keep]))
+
+
+def _grad_buffers(spec, kind, n):
+    """gy, gm, gn, gc, gs: the output buffers of the gradient entry points for one model."""
+    # dense Sigma_y (round 4): the gradient w.r.t. the matrix is the cotangent G = (alpha alpha' - C^-1) / 2 itself, N x N
+    gn = np.zeros((n, n), order="F") if kind == _lib.NOISE_DENSE else np.zeros(n if kind == _lib.NOISE_DIAG else 1)
+    nt = max(1, spec.n_terms)
+    return np.zeros(n), np.zeros(n), gn, np.zeros(nt), np.zeros(nt)
+
+
+def _grad_record(spec, kind, lp, bufs, inputs=None, x=None, scales=None, rowscale=None):
+    gy, gm, gn, gc, gs = bufs
+    return dict(logpdf=float(lp), y=gy, mean=gm, noise=(gn if kind != _lib.NOISE_SCALAR else float(gn[0])),
+                terms=_term_records(spec, gc, gs, True), inputs=inputs, x=x, scales=scales, _raw=(gc, gs),
+                _rowscale=rowscale, _spec=spec)
+
+
+def _grad_failed(spec, info):
+    return dict(logpdf=float("nan"), info=int(info), y=None, mean=None, noise=None, terms=None, inputs=None, x=None,
+                scales=None, _raw=None, _rowscale=None, _spec=spec)
+
+
+def _grad_members(keep, call):
+    """One gradient batch / pool call over `keep`: call(specs, means, kinds, noises, ys, lp, five output pointer arrays,
+    infos) runs it; -> (one dict per member, infos)."""
+    outs = [_grad_buffers(spec, kind, len(yv)) for spec, _, kind, _, yv in keep]
+    lp = np.zeros(len(keep))
+    infos = np.zeros(len(keep), dtype=np.int32)
+    call(*_member_args(keep), _lib.dptr(lp), [_dptrs([o[q] for o in outs]) for q in range(5)], _iptr(infos))
+    return [_grad_failed(k[0], infos[q]) if infos[q] else _grad_record(k[0], k[2], lp[q], outs[q])
+            for q, k in enumerate(keep)], infos
+
+
 def logpdf_batch(fxs, ys, return_infos=False):
     """[logpdf(fx, y) for fx, y in zip(fxs, ys)] in ONE library call (sgp_logpdf_batch): the members are independent models
     -- restarts of an optimiser, cross-validation folds, a population of hyper-parameter candidates.  Members of one padded
@@ -255,17 +334,8 @@ def logpdf_batch(fxs, ys, return_infos=False):
         raise ValueError("logpdf_batch: one y per model")
     if not fxs:
         return (np.zeros(0), np.zeros(0, dtype=np.int32)) if return_infos else np.zeros(0)
-    keep = []          # (spec, mean, noise buffer, y) stay alive until the call returns
-    kinds = set()
-    for fx, y in zip(fxs, ys):
-        if isinstance(fx, SparseFiniteGP):
-            raise NotImplementedError("logpdf_batch takes FiniteGPs (use elbo for a SparseFiniteGP)")
-        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-        if yv.shape[0] != len(fx):
-            raise ValueError("length(y) != length(fx)")
-        spec, m, kind, nbuf = _spec_mean_noise(fx)
-        kinds.add(kind)
-        keep.append((spec, _f64(m), nbuf, yv))
+    keep, _ = _members("logpdf_batch", fxs, ys, False, False)
+    kinds = {k[2] for k in keep}
     if len(kinds) != 1 or _lib.NOISE_DENSE in kinds:
         # mixed or dense noise kinds: member by member (same values; sgp_logpdf_batch takes one noise kind)
         vals, infos = [], []
@@ -277,17 +347,11 @@ def logpdf_batch(fxs, ys, return_infos=False):
                 vals.append(float("nan"))
                 infos.append(e.info)
         return (np.array(vals), np.array(infos, dtype=np.int32)) if return_infos else np.array(vals)
-    nb = len(keep)
-    for k in keep:
-        k[0].ref()           # (patch terms: their geometry ids on the context)
-    specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
-    means = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[1]) for k in keep])
-    noises = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[2]) for k in keep])
-    yp = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[3]) for k in keep])
-    out = np.zeros(nb)
-    infos = np.zeros(nb, dtype=np.int32)
-    rc = _ctx().lib.sgp_logpdf_batch(_ctx().handle, nb, specs, means, kinds.pop(), noises, yp, _lib.dptr(out),
-                                     infos.ctypes.data_as(C.POINTER(C.c_int)))
+    specs, means, _, noises, yp = _member_args(keep)
+    out = np.zeros(len(keep))
+    infos = np.zeros(len(keep), dtype=np.int32)
+    rc = _ctx().lib.sgp_logpdf_batch(_ctx().handle, len(keep), specs, means, kinds.pop(), noises, yp, _lib.dptr(out),
+                                     _iptr(infos))
     _lib.check(rc, "sgp_logpdf_batch")
     return (out, infos) if return_infos else out
 
@@ -371,11 +435,8 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     m = _f64(mean_vector(fx.f, fx.x))
     kind, nbuf = _lib._noise_args(fx.noise, n)
     lp = np.zeros(1)
-    gy, gm = np.zeros(n), np.zeros(n)
-    # dense Sigma_y (round 4): the gradient w.r.t. the matrix is the cotangent G = (alpha alpha' - C^-1) / 2 itself, N x N
-    gn = np.zeros((n, n), order="F") if kind == _lib.NOISE_DENSE else np.zeros(n if kind == _lib.NOISE_DIAG else 1)
+    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
     nt = max(1, spec.n_terms)
-    gc, gs = np.zeros(nt), np.zeros(nt)
     gx = None
     grs = None
     if scales:
@@ -408,14 +469,11 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
                                         _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
                                         _lib.dptr(gc), _lib.dptr(gs))
         _lib.check(rc, "sgp_logpdf_grad")
-    terms = _term_records(spec, gc, gs, True)
     # x: the same gradient mapped back through the model's input transformations onto the blocks of
     # fx.x (one (D, n) array per block; blocks sharing one input object get their joint gradient in
     # the first of them)
     xb = chain_input_gradients(spec, gx)[0] if inputs else None
-    return dict(logpdf=float(lp[0]), y=gy, mean=gm, noise=(gn if kind != _lib.NOISE_SCALAR else float(gn[0])),
-                terms=terms, inputs=gx, x=xb, scales=(_scale_records(spec, grs) if scales else None),
-                _raw=(gc, gs), _rowscale=grs, _spec=spec)
+    return _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs)
 
 
 def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
@@ -430,25 +488,7 @@ def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
         raise ValueError("logpdf_and_gradient_batch: one y per model")
     if not fxs:
         return ([], np.zeros(0, dtype=np.int32)) if return_infos else []
-    keep = []          # (spec, mean, noise kind, noise buffer, y) stay alive until the call returns
-    for fx, y in zip(fxs, ys):
-        if isinstance(fx, SparseFiniteGP):
-            raise NotImplementedError("logpdf_and_gradient_batch takes FiniteGPs (use elbo_and_gradient for a SparseFiniteGP)")
-        if not _is_prior(fx.f):
-            raise NotImplementedError("gradients are implemented for prior Stheno processes")
-        n = len(fx)
-        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-        if yv.shape[0] != n:
-            raise ValueError("length(y) != length(fx)")
-        kind, nbuf = _lib._noise_args(fx.noise, n)
-        spec = _prior_spec(fx.f, fx.x)
-        _refuse_patch_gradient(spec)
-        keep.append((spec, _f64(mean_vector(fx.f, fx.x)), kind, nbuf, yv))
-
-    def failed(spec, info):
-        return dict(logpdf=float("nan"), info=int(info), y=None, mean=None, noise=None, terms=None, inputs=None, x=None,
-                    scales=None, _raw=None, _rowscale=None, _spec=spec)
-
+    keep, _ = _members("logpdf_and_gradient_batch", fxs, ys, True, False)
     kinds = {k[2] for k in keep}
     if len(kinds) != 1 or _lib.NOISE_DENSE in kinds:
         # mixed or dense noise kinds: member by member (same values; sgp_logpdf_grad_batch takes one noise kind)
@@ -458,35 +498,15 @@ def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
                 res.append(logpdf_and_gradient(fx, y))
                 infos.append(0)
             except _lib.PosDefException as e:
-                res.append(failed(k[0], e.info))
+                res.append(_grad_failed(k[0], e.info))
                 infos.append(e.info)
         return (res, np.array(infos, dtype=np.int32)) if return_infos else res
-    kind = kinds.pop()
-    nb = len(keep)
-    outs = []          # per member: gy, gm, gn, gc, gs (the buffers logpdf_and_gradient passes)
-    for spec, _, _, _, yv in keep:
-        n, nt = len(yv), max(1, spec.n_terms)
-        outs.append((np.zeros(n), np.zeros(n), np.zeros(n if kind == _lib.NOISE_DIAG else 1), np.zeros(nt), np.zeros(nt)))
 
-    def ptrs(arrs):
-        return (C.POINTER(C.c_double) * nb)(*[_lib.dptr(a) for a in arrs])
+    def call(specs, means, _, noises, yp, lp, outs, infos):
+        rc = _ctx().batch.sgp_logpdf_grad_batch(_ctx().handle, len(keep), specs, means, kinds.pop(), noises, yp, lp, *outs, infos)
+        _lib.check(rc, "sgp_logpdf_grad_batch")
 
-    specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
-    lp = np.zeros(nb)
-    infos = np.zeros(nb, dtype=np.int32)
-    rc = _ctx().batch.sgp_logpdf_grad_batch(_ctx().handle, nb, specs, ptrs([k[1] for k in keep]), kind,
-                                            ptrs([k[3] for k in keep]), ptrs([k[4] for k in keep]), _lib.dptr(lp),
-                                            *[ptrs([o[q] for o in outs]) for q in range(5)],
-                                            infos.ctypes.data_as(C.POINTER(C.c_int)))
-    _lib.check(rc, "sgp_logpdf_grad_batch")
-    res = []
-    for b, ((spec, _, _, _, _), (gy, gm, gn, gc, gs)) in enumerate(zip(keep, outs)):
-        if infos[b]:
-            res.append(failed(spec, infos[b]))
-            continue
-        res.append(dict(logpdf=float(lp[b]), y=gy, mean=gm, noise=(gn if kind != _lib.NOISE_SCALAR else float(gn[0])),
-                        terms=_term_records(spec, gc, gs, True), inputs=None, x=None, scales=None, _raw=(gc, gs),
-                        _rowscale=None, _spec=spec))
+    res, infos = _grad_members(keep, call)
     return (res, infos) if return_infos else res
 
 
@@ -520,18 +540,7 @@ def logpdf_pool(fxs, ys, return_infos=False, return_report=False):
     vals = np.zeros(n_all)
     infos = np.zeros(n_all, dtype=np.int32)
     rep = dict(pool_launches=0, pooled_members=0, single_members=0, distinct_sizes=0)
-    keep, down = [], []          # (spec, mean, kind, noise buffer, y) stay alive until the call returns; down: their members
-    for b, (fx, y) in enumerate(zip(fxs, ys)):
-        if isinstance(fx, SparseFiniteGP):
-            raise NotImplementedError("logpdf_pool takes FiniteGPs (use elbo for a SparseFiniteGP)")
-        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-        if yv.shape[0] != len(fx):
-            raise ValueError("length(y) != length(fx)")
-        if _is_prior(fx.f) and _is_f32(fx, y):
-            continue
-        spec, m, kind, nbuf = _spec_mean_noise(fx)
-        keep.append((spec, _f64(m), kind, nbuf, yv))
-        down.append(b)
+    keep, down = _members("logpdf_pool", fxs, ys, False, True)
     for b, (fx, y) in enumerate(zip(fxs, ys)):
         if b in down:
             continue
@@ -541,19 +550,11 @@ def logpdf_pool(fxs, ys, return_infos=False, return_report=False):
             vals[b], infos[b] = float("nan"), e.info
         rep["single_members"] += 1
     if keep:
-        nb = len(keep)
-        for k in keep:
-            k[0].ref()           # (patch terms: their geometry ids on the context)
-        specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
-        means = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[1]) for k in keep])
-        kinds = (C.c_int * nb)(*[int(k[2]) for k in keep])
-        noises = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[3]) for k in keep])
-        yp = (C.POINTER(C.c_double) * nb)(*[_lib.dptr(k[4]) for k in keep])
-        out = np.zeros(nb)
-        inf = np.zeros(nb, dtype=np.int32)
+        out = np.zeros(len(keep))
+        inf = np.zeros(len(keep), dtype=np.int32)
         crep = _lib.sgp_pool_report()
-        rc = _ctx().pool.sgp_logpdf_pool(_ctx().handle, nb, specs, means, kinds, noises, yp, _lib.dptr(out),
-                                         inf.ctypes.data_as(C.POINTER(C.c_int)), C.byref(crep))
+        rc = _ctx().pool.sgp_logpdf_pool(_ctx().handle, len(keep), *_member_args(keep), _lib.dptr(out), _iptr(inf),
+                                         C.byref(crep))
         _lib.check(rc, "sgp_logpdf_pool")
         vals[down], infos[down] = out, inf
         for k, v in _pool_report(crep).items():
@@ -575,69 +576,26 @@ def logpdf_and_gradient_pool(fxs, ys, return_infos=False, return_report=False):
     infos = np.zeros(n_all, dtype=np.int32)
     rep = dict(pool_launches=0, pooled_members=0, single_members=0, distinct_sizes=0)
     res = [None] * n_all
-    keep, down = [], []          # (spec, mean, noise kind, noise buffer, y) stay alive until the call returns
-    for b, (fx, y) in enumerate(zip(fxs, ys)):
-        if isinstance(fx, SparseFiniteGP):
-            raise NotImplementedError("logpdf_and_gradient_pool takes FiniteGPs (use elbo_and_gradient for a SparseFiniteGP)")
-        if not _is_prior(fx.f):
-            raise NotImplementedError("gradients are implemented for prior Stheno processes")
-        n = len(fx)
-        yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-        if yv.shape[0] != n:
-            raise ValueError("length(y) != length(fx)")
-        kind, nbuf = _lib._noise_args(fx.noise, n)
-        spec = _prior_spec(fx.f, fx.x)
-        _refuse_patch_gradient(spec)
-        if _is_f32(fx, y):
-            continue
-        keep.append((spec, _f64(mean_vector(fx.f, fx.x)), kind, nbuf, yv))
-        down.append(b)
-
-    def failed(spec, info):
-        return dict(logpdf=float("nan"), info=int(info), y=None, mean=None, noise=None, terms=None, inputs=None, x=None,
-                    scales=None, _raw=None, _rowscale=None, _spec=spec)
-
+    keep, down = _members("logpdf_and_gradient_pool", fxs, ys, True, True)
     for b, (fx, y) in enumerate(zip(fxs, ys)):
         if b in down:
             continue
         try:
             res[b] = logpdf_and_gradient(fx, y)
         except _lib.PosDefException as e:
-            res[b], infos[b] = failed(_prior_spec(fx.f, fx.x), e.info), e.info
+            res[b], infos[b] = _grad_failed(_prior_spec(fx.f, fx.x), e.info), e.info
         rep["single_members"] += 1
     if keep:
-        nb = len(keep)
-        outs = []          # per member: gy, gm, gn, gc, gs (the buffers logpdf_and_gradient passes)
-        for spec, _, kind, _, yv in keep:
-            n, nt = len(yv), max(1, spec.n_terms)
-            gn = np.zeros((n, n), order="F") if kind == _lib.NOISE_DENSE else np.zeros(n if kind == _lib.NOISE_DIAG else 1)
-            outs.append((np.zeros(n), np.zeros(n), gn, np.zeros(nt), np.zeros(nt)))
-
-        def ptrs(arrs):
-            return (C.POINTER(C.c_double) * nb)(*[_lib.dptr(a) for a in arrs])
-
-        for k in keep:
-            k[0].ref()
-        specs = (C.POINTER(_lib.sgp_cov_spec) * nb)(*[C.pointer(k[0].c) for k in keep])
-        kinds = (C.c_int * nb)(*[int(k[2]) for k in keep])
-        lp = np.zeros(nb)
-        inf = np.zeros(nb, dtype=np.int32)
         crep = _lib.sgp_pool_report()
-        rc = _ctx().pool.sgp_logpdf_grad_pool(_ctx().handle, nb, specs, ptrs([k[1] for k in keep]), kinds,
-                                              ptrs([k[3] for k in keep]), ptrs([k[4] for k in keep]), _lib.dptr(lp),
-                                              *[ptrs([o[q] for o in outs]) for q in range(5)],
-                                              inf.ctypes.data_as(C.POINTER(C.c_int)), C.byref(crep))
-        _lib.check(rc, "sgp_logpdf_grad_pool")
+
+        def call(specs, means, kinds, noises, yp, lp, outs, inf):
+            rc = _ctx().pool.sgp_logpdf_grad_pool(_ctx().handle, len(keep), specs, means, kinds, noises, yp, lp, *outs, inf,
+                                                  C.byref(crep))
+            _lib.check(rc, "sgp_logpdf_grad_pool")
+
+        got, inf = _grad_members(keep, call)
         for q, b in enumerate(down):
-            spec, _, kind, _, _ = keep[q]
-            gy, gm, gn, gc, gs = outs[q]
-            infos[b] = inf[q]
-            if inf[q]:
-                res[b] = failed(spec, inf[q])
-                continue
-            res[b] = dict(logpdf=float(lp[q]), y=gy, mean=gm, noise=(gn if kind != _lib.NOISE_SCALAR else float(gn[0])),
-                          terms=_term_records(spec, gc, gs, True), inputs=None, x=None, scales=None, _raw=(gc, gs),
-                          _rowscale=None, _spec=spec)
+            res[b], infos[b] = got[q], inf[q]
         for k, v in _pool_report(crep).items():
             rep[k] += v
     return _pool_result(res, infos, rep, return_infos, return_report)

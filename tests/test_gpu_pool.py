@@ -199,6 +199,66 @@ def test_gradient_pool_is_bit_equal_and_honours_null_outputs():
         assert np.array_equal(gc[b], r["_raw"][0][:len(gc[b])])
 
 
+def test_a_gradient_pool_of_more_than_sixteen_members_is_cut_into_launches():
+    """18 members of two padded sizes (256, 384, 384): a launch of 16 and one of the two smallest, results in input order"""
+    ms = [_member((130, 260, 300)[b % 3], b) for b in range(18)]
+    fxs, ys = [m[0] for m in ms], [m[1] for m in ms]
+    got, infos, rep = P.logpdf_and_gradient_pool(fxs, ys, return_infos=True, return_report=True)
+    assert rep["pool_launches"] == 2 and rep["pooled_members"] == 18 and rep["single_members"] == 0
+    assert not infos.any()
+    for g, fx, y in zip(got, fxs, ys):
+        _same_gradient(g, P.logpdf_and_gradient(fx, y))
+
+
+def test_the_batch_calls_and_the_pool_calls_agree_on_members_of_one_shape():
+    """both routes plan one launch of the same three members: the same bits from either, and from the members' own calls"""
+    fxs, ys, own = _pool((300, 290, 257))
+    by_batch, by_pool = P.logpdf_batch(fxs, ys), P.logpdf_pool(fxs, ys)
+    assert np.array_equal(by_batch, by_pool) and np.array_equal(by_batch, own) and np.array_equal(by_pool, own)
+    g_batch, g_pool = P.logpdf_and_gradient_batch(fxs, ys), P.logpdf_and_gradient_pool(fxs, ys)
+    for gb, gp, fx, y in zip(g_batch, g_pool, fxs, ys):
+        ref = P.logpdf_and_gradient(fx, y)
+        _same_gradient(gb, gp)
+        _same_gradient(gb, ref)
+        _same_gradient(gp, ref)
+
+
+def test_the_error_text_names_the_bad_member_as_its_entry_point_counts_it():
+    """infos = NULL through the C signatures: the call returns the first bad member's info and names it "(batch member b)" /
+    "(pool member b)", b its index in the caller's arrays; the other members keep their values"""
+    import ctypes as C
+    L = P.lib
+    fxs, ys, own = _pool((130, 130, 130))
+    fxs = list(fxs)
+    fxs[1] = fxs[1].f(fxs[1].x, -3.0)                           # K - 3 I: not positive definite
+    with pytest.raises(P.PosDefException) as e:
+        P.logpdf(fxs[1], ys[1])
+    keep = []
+    for fx, y in zip(fxs, ys):
+        spec, m, kind, nbuf = P.finite_gp._spec_mean_noise(fx)
+        assert kind == L.NOISE_SCALAR
+        keep.append((spec, np.asfortranarray(m, dtype=np.float64), nbuf, np.asarray(y, dtype=np.float64)))
+
+    def ptrs(q):
+        return (C.POINTER(C.c_double) * 3)(*[L.dptr(k[q]) for k in keep])
+
+    for k in keep:
+        k[0].ref()
+    specs = (C.POINTER(L.sgp_cov_spec) * 3)(*[C.pointer(k[0].c) for k in keep])
+    kinds = (C.c_int * 3)(*[L.NOISE_SCALAR] * 3)
+    ctx = L.default_context()
+    out = np.zeros(3)
+    rc = ctx.lib.sgp_logpdf_batch(ctx.handle, 3, specs, ptrs(1), L.NOISE_SCALAR, ptrs(2), ptrs(3), L.dptr(out), None)
+    print("batch:", rc, L.last_error())
+    assert rc == e.value.info and rc >= 1 and "(batch member 1)" in L.last_error()
+    assert out[0] == own[0] and out[2] == own[2]
+    out = np.zeros(3)
+    rc = ctx.pool.sgp_logpdf_pool(ctx.handle, 3, specs, ptrs(1), kinds, ptrs(2), ptrs(3), L.dptr(out), None, None)
+    print("pool:", rc, L.last_error())
+    assert rc == e.value.info and rc >= 1 and "(pool member 1)" in L.last_error()
+    assert out[0] == own[0] and out[2] == own[2]
+
+
 def test_knobs_switch_the_pool_off_bound_it_and_force_the_rerun(monkeypatch):
     """SGP_BATCH_MAX_N=0: no pool.  =512: the member beyond it runs through its own call, the others pool.
     SGP_DF_TIMEOUT_S tiny: the ragged launch runs into its bounded wait, the entry point reruns on the launch-based schedule
