@@ -44,8 +44,14 @@ enum {
   SGP_MATERN32 = 2, /* Matern32Kernel: (1+sqrt3 d) exp(-sqrt3 d)                         */
   SGP_MATERN52 = 3, /* Matern52Kernel: (1+sqrt5 d+5d^2/3) exp(-sqrt5 d)                  */
   SGP_WHITE = 4,    /* WhiteKernel: 1[x == y]                                            */
-  SGP_CONST = 5     /* ConstantKernel(c): param                                          */
+  SGP_CONST = 5,    /* ConstantKernel(c): param                                          */
+  /* the kinds below are evaluated by the product-chain path only (include/sthenomi_kprod.h) */
+  SGP_RQ = 6,       /* RationalQuadraticKernel(alpha): (1 + d^2 / (2 alpha))^-alpha, param = alpha > 0 */
+  SGP_LINEAR = 7    /* LinearKernel(c): x'y + c, param = c >= 0                          */
 };
+/* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
+ * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
+#define SGP_KIND_TIMES_PREV 0x100
 
 /* noise kinds for FiniteGP(f, x, Sigma_y)  (AbstractGPs FiniteGP [EXT], App. A.2) */
 enum {
@@ -64,7 +70,7 @@ typedef struct {
 
 /* one term of one block pair */
 typedef struct {
-  int32_t kind;       /* SGP_SE ...                                                      */
+  int32_t kind;       /* SGP_SE ... [| SGP_KIND_TIMES_PREV]                              */
   int32_t row_input;  /* index into sgp_cov_spec.inputs; must have n == row block length */
   int32_t col_input;  /* index into sgp_cov_spec.inputs; must have n == col block length */
   int32_t reserved;   /* 0: a plain term.  Patch (convolutional) terms: row_geom_id | col_geom_id << 16, ids
@@ -72,7 +78,7 @@ typedef struct {
                          Stencil terms: the same encoding, ids of the same table registered by
                          sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
-  double param;       /* SGP_CONST: c                                                    */
+  double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c                      */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

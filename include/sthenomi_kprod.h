@@ -1,0 +1,64 @@
+/* sthenomi_kprod.h -- product chains of kernels, the RationalQuadratic and Linear kinds, and the gradient of logpdf with
+ * respect to kernel parameters, through libsthenomi_kprod.so.
+ *
+ * An extension of the drop-in boundary (include/sthenomi.h), in a header and a library of its own, as
+ * include/sthenomi_stencil.h is: the product header's entry points are a fixed table.  libsthenomi_kprod.so links against
+ * libsthenomi.so and works on the contexts, specs and error state created there.  Plain C like the product header.
+ *
+ * KernelFunctions' KernelProduct (`k1 * k2`, which Stheno re-exports) multiplies kernels entry by entry.  A term of a
+ * sgp_cov_spec stands for coef rs_i k(x_i, x'_j) cs_j; a CHAIN of terms stands for
+ *     coef_head rs_i cs_j  prod_f k_f(x^f_i, x'^f_j)
+ * Encoding (constants in include/sthenomi.h):
+ *   - SGP_KIND_TIMES_PREV (0x100) or-ed into sgp_term.kind marks a continuation: inside one block pair's CSR range it
+ *     multiplies the chain begun by the nearest preceding term without the flag, the head;
+ *   - every factor names its own row_input / col_input (the factors of one product read differently scaled or transformed
+ *     views of the points); the two inputs of a factor have one dimension;
+ *   - a continuation has coef == 1.0, NULL row_scale / col_scale and reserved == 0, and is never the first term of a pair;
+ *   - the head of a chain, and any term of the kinds SGP_RQ / SGP_LINEAR (a chain of length one), has reserved == 0: there
+ *     are no products with patch or stencil sides.
+ * Kinds that exist on this path only:
+ *   SGP_RQ      param = alpha > 0:  (1 + d^2 / (2 alpha))^-alpha         (RationalQuadraticKernel)
+ *   SGP_LINEAR  param = c >= 0:     x'y + c                              (LinearKernel; PolynomialKernel(n, c) is a chain of
+ *                                                                         n such factors)
+ * Limits, from the assembly and contraction kernels' 64 KiB of column points in LDS and their registers
+ * (stheno.jl_amd/csrc/kprod.hip): at most SGP_KPROD_MAX_FACTORS factors in a chain, factor input dimension at most
+ * SGP_KPROD_MAX_DIM, and factors x (the chain's largest factor dimension rounded up to a power of two) <= 64 -- 8 factors up
+ * to dimension 8, 4 at dimension 9 .. 16.  A spec beyond them, or with a malformed chain, fails wherever it is uploaded
+ * (every entry point; sgp_dspec_create) with rc < 0 and a message naming "product".
+ *
+ * Chains and terms of the new kinds run on every fp64 operator of a single-GPU context: sgp_kernelmatrix / _diag,
+ * sgp_logpdf (_batch, sgp_logpdf_pool), sgp_rand, the posterior and its extension, sgp_elbo and the sparse posterior, and
+ * sgp_logpdf_grad, whose outputs keep one entry per element of spec->terms: for a chain with head h
+ *     grad_coef[h]       = sum_ij G_ij rs_i cs_j prod_f k_f        grad_coef[continuation] = 0
+ *     grad_inscale[f]    = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != f} k_f') d k_f(g x, g x') / dg at g = 1
+ * (LINEAR: 2 x'y;  RQ: -d^2 (1 + d^2 / (2 alpha))^(-alpha - 1)).  These refuse them with rc < 0 and a message naming
+ * "product": sgp_logpdf_grad_x / _xs, every sgp_elbo_grad*, sgp_kernelmatrix_diag_grad*, sgp_logpdf_grad_batch,
+ * sgp_logpdf_grad_pool, the fp32 entry points (sgp_*_f32) and every multi-GPU context. */
+#ifndef STHENOMI_KPROD_H
+#define STHENOMI_KPROD_H
+
+#include "sthenomi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SGP_KPROD_MAX_FACTORS 8
+#define SGP_KPROD_MAX_DIM 16
+
+/* sgp_logpdf_grad plus the gradient with respect to the kernel parameters: grad_param (may be NULL, like every output) has
+ * one entry per element of spec->terms,
+ *     grad_param[t] = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != t} k_f') d k_t / d param
+ * with d k / d param = k (u / (1 + u) - log1p(u)), u = d^2 / (2 alpha), for SGP_RQ; 1 for SGP_LINEAR and SGP_CONST; 0 for the
+ * kinds without a parameter.  Plain terms (outside any chain) get their entries too.  Every other output is bit for bit what
+ * sgp_logpdf_grad returns for the same arguments.  Any spec sgp_logpdf_grad takes, on a single-GPU context: a multi-GPU
+ * context refuses this entry point (rc < 0) whatever the spec holds, product chains or not. */
+int sgp_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
+                          const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
+                          double* grad_coef, double* grad_inscale, double* grad_param);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* STHENOMI_KPROD_H */

@@ -20,6 +20,8 @@ const LIB_BATCH = get(ENV, "STHENOMI_BATCH_LIB", joinpath(dirname(LIB), "libsthe
 const LIB_POOL = get(ENV, "STHENOMI_POOL_LIB", joinpath(dirname(LIB), "libsthenomi_pool.so"))
 # include/sthenomi_extend.h (sgp_posterior_extend): likewise
 const LIB_EXTEND = get(ENV, "STHENOMI_EXTEND_LIB", joinpath(dirname(LIB), "libsthenomi_extend.so"))
+# include/sthenomi_kprod.h (sgp_logpdf_grad_param: + d / d kernel parameters, through product chains and plain terms): likewise
+const LIB_KPROD = get(ENV, "STHENOMI_KPROD_LIB", joinpath(dirname(LIB), "libsthenomi_kprod.so"))
 const SthenoFGP = FiniteGP{<:Union{GPPP,SthenoAbstractGP}}
 
 # ---- C structs (include/sthenomi.h) --------------------------------------------------------
@@ -363,6 +365,25 @@ function logpdf_and_gradient(fx::SthenoFGP, y::AbstractVector{<:Real})
          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
         ctx(), sp.c, m, kind, nz, yd, lp, gy, gm, gn, gc, gs))
     return (logpdf = lp[1], y = gy, mean = gm, noise = gn, coef = gc, inscale = gs)
+end
+
+# The same plus d / d param of every flattened term (include/sthenomi_kprod.h: alpha of a RationalQuadratic factor, c of a
+# Linear or Constant one; 0 for kinds without a parameter).  The entry point a model with a KernelProduct, a
+# RationalQuadraticKernel, a LinearKernel or a PolynomialKernel goes through: a product is a chain of terms (the continuations
+# carry SGP_KIND_TIMES_PREV = 0x100 in `kind`), `coef` has the chain's derivative at its head and 0 on the continuations,
+# `inscale` and `param` one entry per factor.  (build_spec of this shim does not flatten KernelProduct yet: the host mirror
+# stheno.jl_amd/flatten.py shows the encoding.)
+function logpdf_and_gradient_param(fx::SthenoFGP, y::AbstractVector{<:Real})
+    sp = build_spec(fx.f, fx.x); m = collect(Float64, mean(fx.f, fx.x)); kind, nz = noise_args(fx.Σy)
+    @assert kind != 2 "dense observation noise has no device gradient"
+    yd = collect(Float64, y); n = length(yd); nt = max(1, length(sp.keep[5]))
+    lp = zeros(1); gy = zeros(n); gm = zeros(n); gn = zeros(kind == 1 ? n : 1); gc = zeros(nt); gs = zeros(nt); gp = zeros(nt)
+    GC.@preserve sp m nz yd lp gy gm gn gc gs gp check(
+        @ccall LIB_KPROD.sgp_logpdf_grad_param(ctx()::Ptr{Cvoid}, sp.c::Ref{CSpec}, m::Ptr{Float64}, kind::Cint,
+                                               nz::Ptr{Float64}, yd::Ptr{Float64}, lp::Ptr{Float64}, gy::Ptr{Float64},
+                                               gm::Ptr{Float64}, gn::Ptr{Float64}, gc::Ptr{Float64}, gs::Ptr{Float64},
+                                               gp::Ptr{Float64})::Cint)
+    return (logpdf = lp[1], y = gy, mean = gm, noise = gn, coef = gc, inscale = gs, param = gp)
 end
 
 # logpdf and its gradient for several INDEPENDENT models in one call (sgp_logpdf_grad_batch): one step of B hyper-parameter

@@ -8,8 +8,9 @@ through the C-ABI of include/sthenomi.h.  Import name: `stheno_jl_amd` (see __gr
 from . import lib  # noqa: F401
 from .lib import PosDefException, SthenoMIError  # noqa: F401
 from .inputs import BlockData, ColVecs, GPPPInput, ImageVector, blocks, split, vcat  # noqa: F401
-from .kernels import (ConstantKernel, ExponentialKernel, KernelSum, Matern12Kernel,  # noqa: F401
-                      Matern32Kernel, Matern52Kernel, PeriodicTransform, ScaledKernel, ScaleTransform,
+from .kernels import (ConstantKernel, ExponentialKernel, KernelProduct, KernelSum, LinearKernel, Matern12Kernel,  # noqa: F401
+                      Matern32Kernel, Matern52Kernel, PeriodicKernel, PeriodicTransform, PolynomialKernel,
+                      RationalQuadraticKernel, ScaledKernel, ScaleTransform,
                       ScaleTransformedKernel, TransformedKernel,
                       SEKernel, SqExponentialKernel, WhiteKernel, with_lengthscale)
 from .gp import (GP, GPC, AtomicGP, DerivedGP, Periodic, Select, Shift, Stretch,  # noqa: F401

@@ -6,6 +6,7 @@
 #include "sz_pattern.h"
 #include "df_tasks.h"
 #include "df_pool.h"
+#include "../../include/sthenomi_kprod.h"
 #include <limits>
 
 #include <algorithm>
@@ -35,6 +36,11 @@ constexpr long WOUT_LARGE = 1024;  // ... for n_pad >= 32768 (halves the C-tile 
 }  // namespace sgp
 
 using namespace sgp;
+
+// product chains (include/sthenomi_kprod.h) have no sharded instantiation: refused before a multi-GPU context's ranks see them
+#define REFUSE_KPROD_MULTI(ctx, sp)                        \
+  CHECK_ARG(!((ctx)->multi && spec_has_kprod(sp)), \
+            "spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context")
 
 #define CHECK_ARG(cond, msg)       \
   do {                             \
@@ -363,12 +369,45 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   const int nterms = sp->term_ptr[npairs];
   std::vector<size_t> rs_off(nterms, (size_t)-1), cs_off(nterms, (size_t)-1);
   std::vector<long> rs_len(nterms, 0), cs_len(nterms, 0);
+  // product chains and terms of the RQ / LINEAR kinds (include/sthenomi_kprod.h): a class of their own (kprod.hip)
+  std::vector<char> is_kp(std::max(1, nterms), 0);
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
+      int chain_len = 0, chain_dmax = 1;
       for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t) {
         const sgp_term& T = sp->terms[t];
-        if (T.kind < 0 || T.kind > SGP_CONST) return fail("spec: unknown kernel kind");
+        if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) || (T.kind & 0xff) > SGP_LINEAR)
+          return fail("spec: unknown kernel kind");
+        const bool cont = (T.kind & SGP_KIND_TIMES_PREV) != 0;
+        const bool next_cont = t + 1 < sp->term_ptr[p + 1] && sp->terms[t + 1].kind >= 0 &&
+                               (sp->terms[t + 1].kind & SGP_KIND_TIMES_PREV);
+        is_kp[t] = cont || next_cont || (T.kind & 0xff) > SGP_CONST;
+        if (is_kp[t]) {
+          if (cont && t == sp->term_ptr[p])
+            return fail("spec: product chain: a continuation (SGP_KIND_TIMES_PREV) cannot be the first term of a block pair");
+          if (T.reserved)
+            return fail("spec: product chain: reserved must be 0 (no products with patch or stencil sides, none for the RQ / "
+                        "LINEAR kinds)");
+          if (cont && (T.coef != 1.0 || T.row_scale || T.col_scale))
+            return fail("spec: product chain: a continuation must have coef == 1.0 and NULL scales (the head carries them)");
+          if ((T.kind & 0xff) == SGP_RQ && !(T.param > 0.0 && T.param < 1e300))
+            return fail("spec: SGP_RQ (product path): param = alpha must be > 0 and finite");
+          if ((T.kind & 0xff) == SGP_LINEAR && !(T.param >= 0.0 && T.param < 1e300))
+            return fail("spec: SGP_LINEAR (product path): param = c must be >= 0 and finite");
+          if (T.row_input >= 0 && T.row_input < sp->n_inputs) {
+            const int64_t dim = sp->inputs[T.row_input].dim;
+            if (dim > SGP_KPROD_MAX_DIM)
+              return fail("spec: product chain: the input dimension of a factor (or of an RQ / LINEAR term) must be <= 16");
+            if (!cont) chain_len = 0, chain_dmax = 1;
+            ++chain_len;
+            chain_dmax = std::max(chain_dmax, pow2ceil((int)std::max<int64_t>(dim, 1)));
+            if (chain_len > SGP_KPROD_MAX_FACTORS || chain_len * chain_dmax > 64)
+              return fail("spec: product chain beyond the limits: at most 8 factors, and factors x (largest factor dimension "
+                          "rounded up to a power of two) <= 64");
+          }
+          ++ds->n_kprod;
+        }
         if (T.row_input < 0 || T.row_input >= sp->n_inputs || T.col_input < 0 ||
             T.col_input >= sp->n_inputs)
           return fail("spec: term input index out of range");
@@ -418,9 +457,11 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           cs_len[t] = ds->col_len[J];
           cs_off[t] = place(sizeof(double) * (size_t)cs_len[t]);
         }
-        if (!T.reserved) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
+        if (!T.reserved && !is_kp[t]) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
       }
     }
+  if (ds->n_kprod && (ctx->multi || ctx->multi_rank))
+    return fail("spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context");
   const size_t terms_off = place(sizeof(DevTerm) * (size_t)std::max(1, nterms));
   // ---- one cached device block, one pinned staging buffer
   char* d_base = (char*)pool_alloc(ctx, total);
@@ -455,20 +496,23 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
-      // plain | patch | stencil within every pair (the caller's order when the spec has neither)
+      // plain | patch | stencil | product chains within every pair (the caller's order when the spec has none of the last three;
+      // chains stay contiguous and in the caller's order: the passes below are stable)
       auto cls = [&](int t) {
+        if (is_kp[t]) return 3;
         const uint32_t code = (uint32_t)sp->terms[t].reserved;
         if (!code) return 0;
         const uint32_t id = (code & 0xffffu) ? (code & 0xffffu) : (code >> 16);
         return ctx->conv_geoms[id - 1].st > 0 ? 2 : 1;
       };
       std::vector<int> order;
-      int ncls[3] = {0, 0, 0};
-      for (int pass = 0; pass < 3; ++pass)
+      int ncls[4] = {0, 0, 0, 0};
+      for (int pass = 0; pass < 4; ++pass)
         for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t)
           if (cls(t) == pass) order.push_back(t), ++ncls[pass];
       ds->pair_nplain.push_back(ncls[0]);
       ds->pair_npatch.push_back(ncls[1]);
+      ds->pair_nkprod.push_back(ncls[3]);
       for (size_t k = 0; k < order.size(); ++k) {
         const int t = order[k], pos = sp->term_ptr[p] + (int)k;
         const sgp_term& T = sp->terms[t];
@@ -517,6 +561,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
         }
         h_terms[pos] = D;
         ds->h_terms.push_back(D);
+        ds->term_src.push_back(t);
         ds->term_row_input.push_back(T.row_input);
         ds->term_col_input.push_back(T.col_input);
       }
@@ -583,9 +628,10 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
                                        sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
         continue;
       }
-      const bool structured = ds->n_patch || ds->n_stencil;
-      const int tp = structured ? t0 + ds->pair_nplain[p] : t1;        // patch terms: [tp, ts), conv.hip
-      const int ts = ds->n_stencil ? tp + ds->pair_npatch[p] : t1;    // stencil terms: [ts, t1), stencil.hip
+      const bool structured = ds->n_patch || ds->n_stencil || ds->n_kprod;
+      const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;             // product chains: [tk, t1), kprod.hip
+      const int tp = structured ? t0 + ds->pair_nplain[p] : t1;              // patch terms: [tp, ts), conv.hip
+      const int ts = (ds->n_stencil || ds->n_kprod) ? tp + ds->pair_npatch[p] : t1;   // stencil terms: [ts, tk), stencil.hip
       for (int t = t0; t < tp; t += per) {
         int cnt = std::min(per, tp - t);
         CHECK_RC(launch_assemble_block(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax,
@@ -595,10 +641,17 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       for (int t = tp; t < ts; ++t)
         CHECK_RC(launch_assemble_conv(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only, t > t0 ? 1 : 0,
                                       t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
-      for (int t = ts; t < t1; ++t)
+      for (int t = ts; t < tk; ++t)
         CHECK_RC(launch_assemble_stencil(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only,
                                          t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf,
                                          tcl - tcf, s));
+      for (int t = tk; t < t1;) {   // whole chains per launch, as many as fit its LDS (kprod.hip: kprod_group)
+        int kdmax = 1;
+        const int cnt = kprod_group(ds->h_terms.data(), t, t1, &kdmax);
+        CHECK_RC(launch_assemble_kprod(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, kdmax, lower_only, t > t0 ? 1 : 0,
+                                       t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+        t += cnt;
+      }
     }
   }
   return 0;
@@ -1523,6 +1576,7 @@ static int upload_noise(NoiseDev& nd, int kind, const double* noise, long N) {
 extern "C" int sgp_kernelmatrix(sgp_ctx* ctx, const sgp_cov_spec* spec, double* K, int64_t ldk) {
   CHECK_ARG(ctx && spec && K, "sgp_kernelmatrix: NULL argument");
   CtxScope scope(ctx);
+  REFUSE_KPROD_MULTI(ctx, spec);
   if (ctx->multi) return sgp_multi_kernelmatrix(ctx, spec, K, ldk);
   SpecGuard g;
   CHECK_RC(dspec_create(ctx, spec, &g.ds));
@@ -1546,9 +1600,10 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag: block lengths differ");
     int p = I * ds->ncb + I;
-    int t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
-    const int np = (ds->n_patch || ds->n_stencil) ? ds->pair_nplain[p] : t1 - t0;
-    const int te = ds->n_stencil ? t0 + np + ds->pair_npatch[p] : t1;   // plain + patch terms: [t0, te)
+    int t0 = ds->term_ptr[p], t1k = ds->term_ptr[p + 1];
+    const int t1 = ds->n_kprod ? t1k - ds->pair_nkprod[p] : t1k;        // product chains: [t1, t1k), kprod.hip
+    const int np = (ds->n_patch || ds->n_stencil || ds->n_kprod) ? ds->pair_nplain[p] : t1 - t0;
+    const int te = (ds->n_stencil || ds->n_kprod) ? t0 + np + ds->pair_npatch[p] : t1;   // plain + patch terms: [t0, te)
     if (np < te - t0) {   // patch terms (conv.hip)
       int max_d = 1, d_all = -1, max_px = 1;
       for (int t = t0 + np; t < te; ++t) {
@@ -1567,6 +1622,12 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
       for (int t = te; t < t1; ++t) max_dim = std::max(max_dim, ds->h_terms[t].dim);
       CHECK_RC(launch_diag_stencil(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + te, t1 - te, max_dim, s));
     }
+    for (int t = t1; t < t1k;) {   // product chains, in the launch groups of the matrix assembly: the same sums
+      int kdmax = 1;
+      const int cnt = kprod_group(ds->h_terms.data(), t, t1k, &kdmax);
+      CHECK_RC(launch_diag_kprod(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t, cnt, 1, s));
+      t += cnt;
+    }
   }
   return 0;
 }
@@ -1574,6 +1635,7 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
 extern "C" int sgp_kernelmatrix_diag(sgp_ctx* ctx, const sgp_cov_spec* spec, double* out) {
   CHECK_ARG(ctx && spec && out, "sgp_kernelmatrix_diag: NULL argument");
   CtxScope scope(ctx);
+  REFUSE_KPROD_MULTI(ctx, spec);
   if (ctx->multi) return sgp_multi_kernelmatrix_diag(ctx, spec, out);
   SpecGuard g;
   CHECK_RC(dspec_create(ctx, spec, &g.ds));
@@ -1595,6 +1657,7 @@ static int sgp_logpdf_impl(sgp_ctx* ctx, const sgp_cov_spec* spec, const double*
   CtxScope scope(ctx);
   // a multi-GPU context (sgp_ctx_create_multi) shards the covariance over its devices
   // (dense Sigma_y is an N x N host matrix: that case stays on devices[0])
+  REFUSE_KPROD_MULTI(ctx, spec);
   if (ctx->multi && ncols >= 1 && noise)
     return sgp_multi_logpdf(ctx, spec, mean, noise_kind, noise, Y, ldy, ncols, out);
   SpecGuard g;
@@ -1632,6 +1695,7 @@ static int sgp_rand_impl(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* m
   CHECK_ARG(ctx && spec && Z && out, "sgp_rand: NULL argument");
   CHECK_ARG(spec->symmetric, "sgp_rand: spec must be symmetric");
   CtxScope scope(ctx);
+  REFUSE_KPROD_MULTI(ctx, spec);
   if (ctx->multi && noise)
     return sgp_multi_rand(ctx, spec, mean, noise_kind, noise, Z, ldz, S, out, ldo);
   SpecGuard g;
@@ -1682,11 +1746,16 @@ extern "C" int sgp_rand(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* me
 
 // sum_ij G_ij dC_ij / d theta per flattened term of every block pair of `ds` (grad.hip):
 // G = (alpha alpha' - Kinv) / 2 when alpha != nullptr, else G = the matrix at `Gm` itself.
+// Product chains (ds->n_kprod; kprod.hip) are contracted one chain per launch, only where the caller says it carries them
+// (kprod_ok: sgp_logpdf_grad / sgp_logpdf_grad_param); dgp (optional): d / d param per term, which for the plain terms is
+// non-zero for SGP_CONST alone -- those run through the chain kernel once more, as chains of length one, for that entry.
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr,
-                         long n_tc, DevBuf& dpart, double* dgc, double* dgs, hipStream_t s) {
+                         long n_tc, DevBuf& dpart, double* dgc, double* dgs, hipStream_t s, bool kprod_ok = false,
+                         double* dgp = nullptr) {
   CHECK_ARG(!ds->n_stencil, "gradient contraction: stencil terms are not supported");
   CHECK_ARG(!ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
-  CHECK_RC(dpart.alloc((size_t)std::max<long>(1, n_tr * n_tc) * 16));
+  CHECK_ARG(kprod_ok || !ds->n_kprod, "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
+  CHECK_RC(dpart.alloc((size_t)std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16)));
   for (int I = 0; I < ds->nrb; ++I) {
     if (ds->row_len[I] == 0) continue;
     for (int J = 0; J < ds->ncb; ++J) {
@@ -1697,10 +1766,23 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       int t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
       int dmax = ds->pair_dmax[p];
       int per = std::min(8, std::max(1, 64 / dmax));
-      for (int t = t0; t < t1; t += per) {
-        int cnt = std::min(per, t1 - t);
+      const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
+      for (int t = t0; t < tk; t += per) {
+        int cnt = std::min(per, tk - t);
         CHECK_RC(launch_grad_block(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax, trf, tcf,
                                    trl - trf, tcl - tcf, dpart.p, dgc + t, dgs + t, s));
+      }
+      for (int t = t0; dgp && t < tk; ++t)
+        if (ds->h_terms[t].kind == SGP_CONST)
+          CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, 1, 1, trf, tcf, trl - trf, tcl - tcf,
+                                     dpart.p, nullptr, nullptr, dgp + t, s));
+      for (int t = tk; t < t1;) {
+        int e = t + 1, cdmax = 1;
+        while (e < t1 && (ds->h_terms[e].kind & SGP_KIND_TIMES_PREV)) ++e;
+        for (int f = t; f < e; ++f) cdmax = std::max(cdmax, pow2ceil(ds->h_terms[f].dim));
+        CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, e - t, cdmax, trf, tcf, trl - trf,
+                                   tcl - tcf, dpart.p, dgc + t, dgs + t, dgp ? dgp + t : nullptr, s));
+        t = e;
       }
     }
   }
@@ -1715,15 +1797,21 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
 static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
                             const double* noise, const double* y, double* logpdf_out, double* grad_y,
                             double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
-                            double* const* grad_inputs, double* const* grad_rowscale = nullptr) {
+                            double* const* grad_inputs, double* const* grad_rowscale = nullptr,
+                            double* grad_param = nullptr, bool with_param = false) {
   CHECK_ARG(ctx && spec && noise && y && logpdf_out, "sgp_logpdf_grad: NULL argument");
   CHECK_ARG(spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
   CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
   CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
+  CHECK_ARG(!(grad_inputs || grad_rowscale) || !spec_has_kprod(spec),
+            "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
+            "not supported");
+  CHECK_ARG(!(with_param && ctx->multi), "sgp_logpdf_grad_param: not supported on a multi-GPU context");
   CtxScope scope(ctx);
   // a multi-GPU context shards the gradient -- kernel terms, noise, y, the mean and (round 6) the input points and function
   // scales, a dense Sigma_y (multi.hip)
+  REFUSE_KPROD_MULTI(ctx, spec);
   if (ctx->multi)
     return sgp_multi_logpdf_grad(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                                  grad_inscale, grad_inputs, grad_rowscale);
@@ -1737,7 +1825,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   long nrows = TILE + n_pad;            // the (y - m)' row (+ zero padding), then the identity rows
   long m_tot = n_pad + nrows;
   hipStream_t s = ctx->stream;
-  DevBuf dA, dKinv, dmean, dy, dalpha, dpart, dgc, dgs, dgn;
+  DevBuf dA, dKinv, dmean, dy, dalpha, dpart, dgc, dgs, dgn, dgp;
   NoiseDev nd;
   CHECK_RC(dA.alloc((size_t)m_tot * n_pad));
   CHECK_RC(dKinv.alloc((size_t)n_pad * n_pad));
@@ -1753,6 +1841,10 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   SGP_HIP(hipMemsetAsync(dalpha.p, 0, sizeof(double) * n_pad, s));
   SGP_HIP(hipMemsetAsync(dgc.p, 0, sizeof(double) * std::max<size_t>(1, nterms_total), s));
   SGP_HIP(hipMemsetAsync(dgs.p, 0, sizeof(double) * std::max<size_t>(1, nterms_total), s));
+  if (grad_param) {
+    CHECK_RC(dgp.alloc(std::max<size_t>(1, nterms_total)));
+    SGP_HIP(hipMemsetAsync(dgp.p, 0, sizeof(double) * std::max<size_t>(1, nterms_total), s));
+  }
   // K + Sigma_y, identity padding, bordered rows [(y - m)' ; I].  The identity rows come last so
   // that the rows a panel touches (K rows below it, the y row, identity rows above its last
   // column) are contiguous: the factorisation + inv(L) cost 2/3 N^3 instead of 4/3 N^3.
@@ -1801,8 +1893,9 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   CHECK_RC(launch_mirror_lower(dKinv.p, n_pad, n_pad, s));
   if (grad_noise && dense_noise) CHECK_RC(launch_grad_noise_dense(dKinv.p, n_pad, dalpha.p, N, dgn.p, s));
   else if (grad_noise) CHECK_RC(launch_grad_noise(dKinv.p, n_pad, dalpha.p, N, nd.kind == SGP_NOISE_DIAG, dgn.p, s));
-  if (grad_coef || grad_inscale)
-    CHECK_RC(contract_spec(ds, dKinv.p, n_pad, dalpha.p, n_pad / TILE, n_pad / TILE, dpart, dgc.p, dgs.p, s));
+  if (grad_coef || grad_inscale || grad_param)
+    CHECK_RC(contract_spec(ds, dKinv.p, n_pad, dalpha.p, n_pad / TILE, n_pad / TILE, dpart, dgc.p, dgs.p, s, true,
+                           grad_param ? dgp.p : nullptr));
   // gradient w.r.t. the input points: row-side contraction over every block pair; the spec is
   // symmetric (block (J, I) mirrors (I, J)) and so is G, hence the column side equals the row side of
   // the mirror block and the total is twice the row-side sum
@@ -1855,10 +1948,22 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
     SGP_HIP(hipMemcpy(grad_noise, dgn.p,
                       sizeof(double) * (dense_noise ? (size_t)N * N : (nd.kind == SGP_NOISE_DIAG ? (size_t)N : (size_t)1)),
                       hipMemcpyDeviceToHost));
-  if (grad_coef && nterms_total)
-    SGP_HIP(hipMemcpy(grad_coef, dgc.p, sizeof(double) * nterms_total, hipMemcpyDeviceToHost));
-  if (grad_inscale && nterms_total)
-    SGP_HIP(hipMemcpy(grad_inscale, dgs.p, sizeof(double) * nterms_total, hipMemcpyDeviceToHost));
+  // one entry per element of spec->terms, in the CALLER's order: a spec with product chains keeps its plain terms in front of
+  // them on the device (dspec_create), so its entries go back through term_src
+  auto fetch_terms = [&](double* dst, const double* d_src) -> int {
+    if (!dst || !nterms_total) return 0;
+    if (!ds->n_kprod) {
+      SGP_HIP(hipMemcpy(dst, d_src, sizeof(double) * nterms_total, hipMemcpyDeviceToHost));
+      return 0;
+    }
+    std::vector<double> tmp(nterms_total);
+    SGP_HIP(hipMemcpy(tmp.data(), d_src, sizeof(double) * nterms_total, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nterms_total; ++k) dst[ds->term_src[k]] = tmp[k];
+    return 0;
+  };
+  CHECK_RC(fetch_terms(grad_coef, dgc.p));
+  CHECK_RC(fetch_terms(grad_inscale, dgs.p));
+  if (grad_param) CHECK_RC(fetch_terms(grad_param, dgp.p));
   if (grad_inputs) {
     for (int k = 0; k < spec->n_inputs; ++k) {
       const sgp_input& in = spec->inputs[k];
@@ -1893,6 +1998,16 @@ extern "C" int sgp_logpdf_grad(sgp_ctx* ctx, const sgp_cov_spec* spec, const dou
   return with_df_fallback(ctx, [&]() {
     return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
                             grad_coef, grad_inscale, nullptr);
+  });
+}
+
+// include/sthenomi_kprod.h: sgp_logpdf_grad_param (its C entry point, in libsthenomi_kprod.so, forwards here)
+int sgp::drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
+                               const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
+                               double* grad_coef, double* grad_inscale, double* grad_param) {
+  return with_df_fallback(ctx, [&]() {
+    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                            grad_inscale, nullptr, nullptr, grad_param, true);
   });
 }
 
@@ -2333,6 +2448,7 @@ static int logpdf_grad_batch_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* c
     CHECK_ARG(specs[b]->symmetric, "sgp_logpdf_grad_batch: specs must be symmetric");
     CHECK_ARG(!spec_has_stencil(ctx, specs[b]), "sgp_logpdf_grad_batch: gradients through stencil terms are not supported");
     CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_batch: gradients through patch (convolutional) terms are not supported");
+    CHECK_ARG(!spec_has_kprod(specs[b]), "sgp_logpdf_grad_batch: gradients through product chains and the RQ / LINEAR kinds are not supported: call sgp_logpdf_grad per member");
     if (infos) infos[b] = 0;
   }
   PoolCall call{"batch", true, specs, means, nullptr, noise_kind, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
@@ -2410,6 +2526,7 @@ static int logpdf_grad_pool_impl(sgp_ctx* ctx, int nspec, const sgp_cov_spec* co
     CHECK_ARG(kinds[b] >= SGP_NOISE_SCALAR && kinds[b] <= SGP_NOISE_DENSE, "sgp_logpdf_grad_pool: bad noise kind");
     CHECK_ARG(!spec_has_stencil(ctx, specs[b]), "sgp_logpdf_grad_pool: gradients through stencil terms are not supported");
     CHECK_ARG(!spec_has_patch(specs[b]), "sgp_logpdf_grad_pool: gradients through patch (convolutional) terms are not supported");
+    CHECK_ARG(!spec_has_kprod(specs[b]), "sgp_logpdf_grad_pool: gradients through product chains and the RQ / LINEAR kinds are not supported: call sgp_logpdf_grad per member");
     if (infos) infos[b] = 0;
   }
   PoolCall call{"pool", true, specs, means, kinds, 0, noises, ys, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef, grad_inscale,
@@ -2560,6 +2677,7 @@ static int sgp_posterior_create_impl(sgp_ctx* ctx, const sgp_cov_spec* spec, con
   CHECK_ARG(ctx && spec && y && out, "sgp_posterior_create: NULL argument");
   CHECK_ARG(spec->symmetric, "sgp_posterior_create: spec must be symmetric");
   CtxScope scope(ctx);
+  REFUSE_KPROD_MULTI(ctx, spec);
   if (ctx->multi && noise) {
     sgp_mpost* mp = nullptr;
     CHECK_RC(sgp_multi_posterior_create(ctx, spec, mean, noise_kind, noise, y, alpha_out, &mp));
@@ -3288,6 +3406,8 @@ static int sgp_elbo_impl(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spe
                         const double* noise_x, int z_noise_kind, const double* z_noise,
                         const double* y, double* out) {
   CHECK_ARG(ctx && zz && xz && var_x && noise_x && z_noise && y && out, "sgp_elbo: NULL argument");
+  REFUSE_KPROD_MULTI(ctx, zz);
+  REFUSE_KPROD_MULTI(ctx, xz);
   CtxScope scope(ctx);
   if (ctx->multi && ctx->multi_nranks > 1)   // data points sharded over the ranks, one reduction of M^2 + M + 2 doubles
   {
@@ -3654,6 +3774,8 @@ static int elbo_grad_entry(sgp_ctx* ctx, const sgp::ElboGradArgs& a) {
             "sgp_elbo_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(a.zz) && !spec_has_patch(a.xz),
             "sgp_elbo_grad: gradients through patch (convolutional) terms are not supported");
+  CHECK_ARG(!spec_has_kprod(a.zz) && !spec_has_kprod(a.xz),
+            "sgp_elbo_grad: gradients through product chains and the RQ / LINEAR kinds are not supported");
   if (ctx->multi && ctx->multi_nranks > 1) return sgp_multi_elbo_grad(ctx, a);
   return sgp::drv_elbo_grad(ctx, a, nullptr);
 }
@@ -3710,6 +3832,7 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
   CHECK_ARG(ctx && spec && w && grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad: NULL argument");
   CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_diag_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_diag_grad: gradients through patch (convolutional) terms are not supported");
+  CHECK_ARG(!spec_has_kprod(spec), "sgp_kernelmatrix_diag_grad: gradients through product chains and the RQ / LINEAR kinds are not supported");
   CtxScope scope(ctx);
   SpecGuard g;
   CHECK_RC(dspec_create(ctx, spec, &g.ds));
@@ -3811,6 +3934,8 @@ static int sgp_sparse_posterior_create_impl(sgp_ctx* ctx, const sgp_cov_spec* zz
                                            const double* z_noise, const double* y,
                                            sgp_sparse_post** out) {
   CHECK_ARG(ctx && zz && xz && noise_x && z_noise && y && out, "sgp_sparse_posterior_create: NULL argument");
+  REFUSE_KPROD_MULTI(ctx, zz);
+  REFUSE_KPROD_MULTI(ctx, xz);
   CtxScope scope(ctx);
   sgp_sparse_post* p = new sgp_sparse_post();
   double h[6];

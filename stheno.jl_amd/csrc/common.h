@@ -131,6 +131,22 @@ int launch_assemble_stencil(double* K, long ld, long r0, long nr, long c0, long 
 // sums entry (i, i); out holds the pair's plain and patch diagonal.  max_dim: the largest input dimension of those terms
 int launch_diag_stencil(double* out, long n, const DevTerm* d_terms, int nterms, int max_dim, hipStream_t s);
 
+// kprod.hip: product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h).  The terms of one launch are whole chains;
+// kprod_group cuts a pair's chain terms [t, t1) into launches (returns how many terms the launch at t carries, *dmax_out = its
+// DMAX) for the matrix and the diagonal alike.  Arguments of launch_assemble_kprod as launch_assemble_block.
+int kprod_group(const DevTerm* h_terms, int t, int t1, int* dmax_out);
+int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* d_terms, int nterms,
+                          int dmax, int lower_only, int accumulate, int noise_kind, double sigma2,
+                          const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
+                          long tile_c_cnt, hipStream_t s);
+// out[i] (i < n) = (accumulate ? out[i] : 0) + the chains of one launch group, summed as launch_assemble_kprod sums entry (i, i)
+int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int accumulate, hipStream_t s);
+// gradient contraction of ONE chain (nf factors at d_terms): out_coef / out_scale / out_param point at the chain's first entry
+// (nf each; any may be NULL); partials: tile rows x tile columns x 24 doubles
+int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
+                      const DevTerm* d_terms, int nf, int dmax, long trf, long tcf, long trc, long tcc, double* partials,
+                      double* out_coef, double* out_scale, double* out_param, hipStream_t s);
+
 void set_error(const std::string& s);
 
 #define SGP_HIP(expr)                                                                     \

@@ -87,6 +87,7 @@ struct sgp_ctx {
   long serial = 0;                // unique per created context (capi.hip: ctx_is_live)
   sgp_multi* multi = nullptr;     // non-null: the operators shard over several GPUs (sgp_ctx_create_multi)
   int multi_nranks = 0;
+  bool multi_rank = false;        // a rank's own context inside a multi-GPU context (multi.hip)
   // patch geometries registered on this context (include/sthenomi_conv.h: sgp_conv_geom): id k >= 1 is conv_geoms[k - 1]
   std::vector<sgp::PatchGeom> conv_geoms;
   // stencils registered on this context (include/sthenomi_stencil.h): named by the conv_geoms entries with st > 0
@@ -334,6 +335,15 @@ inline bool spec_has_stencil(const sgp_ctx* ctx, const sgp_cov_spec* sp) {
   return false;
 }
 
+// a term of a product chain (include/sthenomi_kprod.h) or of a kind only kprod.hip evaluates
+inline bool spec_has_kprod(const sgp_cov_spec* sp) {
+  if (!sp || !sp->term_ptr || !sp->terms) return false;
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t)
+    if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || (sp->terms[t].kind & 0xff) > SGP_CONST) return true;
+  return false;
+}
+
 struct sgp_dspec {
   sgp_ctx* ctx = nullptr;
   int nrb = 0, ncb = 0, symmetric = 0;
@@ -355,4 +365,9 @@ struct sgp_dspec {
   // stencil terms (DevTerm::qr or qc > 0): after the patch terms of their pair (pair_npatch of those); n_stencil == 0: none
   std::vector<int> pair_npatch;
   int n_stencil = 0;
+  // product chains and terms of the RQ / LINEAR kinds (kprod.hip): the last pair_nkprod terms of their pair, chains contiguous
+  // and in the caller's order; n_kprod == 0: none
+  std::vector<int> pair_nkprod;
+  int n_kprod = 0;
+  std::vector<int> term_src;           // index in the caller's spec->terms of the term at each device position
 };

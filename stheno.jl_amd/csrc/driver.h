@@ -46,6 +46,10 @@ int drv_posterior_extend(sgp_post* post, const sgp_cov_spec* spec_all, const dou
                          double* logpdf_out);
 // times the row solve of `tile_rows` 128-row tiles against the kept factor by one schedule (sthenomi_extend_bench.h: sgp_bench_extend_row_solve)
 int drv_extend_row_solve_ms(sgp_post* post, int64_t tile_rows, int schedule, int reps, double* ms_out);
+// include/sthenomi_kprod.h: sgp_logpdf_grad_param, forwarded from libsthenomi_kprod.so; takes the context itself
+int drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
+                          const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
+                          double* grad_coef, double* grad_inscale, double* grad_param);
 int drv_diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStream_t s);
 int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out);   // caller holds the context
 // register a patch geometry on ctx (include/sthenomi_conv.h: sgp_conv_geom, whose C entry point in libsthenomi_conv.so

@@ -518,6 +518,7 @@ extern "C" int sgp_logpdf_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const doub
               "sgp_logpdf_f32: noise kind must be SCALAR or DIAG");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_kprod(spec), "sgp_logpdf_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   sgp_dspec* ds = nullptr;
   if (int rc = sgp_dspec_create_nolock(ctx, spec, &ds)) return rc;
@@ -593,6 +594,7 @@ extern "C" int sgp_kernelmatrix_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, floa
   F_CHECK_ARG(ctx && spec && K, "sgp_kernelmatrix_f32: NULL argument");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_kprod(spec), "sgp_kernelmatrix_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   sgp_dspec* ds = nullptr;
   if (int rc = sgp_dspec_create_nolock(ctx, spec, &ds)) return rc;
@@ -700,6 +702,7 @@ extern "C" int sgp_rand_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG, "sgp_rand_f32: noise kind must be SCALAR or DIAG");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_rand_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_rand_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_kprod(spec), "sgp_rand_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   SpecG g;
   if (int rc = sgp_dspec_create_nolock(ctx, spec, &g.d)) return rc;
@@ -755,6 +758,7 @@ extern "C" int sgp_posterior_mean_var_f32(sgp_ctx* ctx, const sgp_cov_spec* spec
   F_CHECK_ARG(!var_out || prior_ss, "sgp_posterior_mean_var_f32: prior_ss spec required for var");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec) && !spec_has_stencil(ctx, cross) && !spec_has_stencil(ctx, prior_ss), "sgp_posterior_mean_var_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec) && !spec_has_patch(cross) && !spec_has_patch(prior_ss), "sgp_posterior_mean_var_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_kprod(spec) && !spec_has_kprod(cross) && !spec_has_kprod(prior_ss), "sgp_posterior_mean_var_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");
   CtxScope scope(ctx);
   SpecG g, gc, gp;
   if (int rc = sgp_dspec_create_nolock(ctx, spec, &g.d)) return rc;

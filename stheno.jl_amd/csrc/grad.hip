@@ -11,51 +11,14 @@
 // x 64 columns, column points broadcast from LDS.  Partials per workgroup are reduced in fixed
 // order by a second kernel (deterministic).
 #include "common.h"
+#include "kern_grad.h"
 #include <algorithm>
 
 namespace sgp {
 
-enum { G_SE = 0, G_M12 = 1, G_M32 = 2, G_M52 = 3, G_WHITE = 4, G_CONST = 5 };
 constexpr int GRAD_MAXT = 8;  // terms per launch
 
-// k and d k / d g (input scale, at g = 1) from the squared distance.  d2 is clamped to 1e150: every kernel and
-// derivative is an exact 0 long before, and a squared distance that overflowed would make them inf * 0 = NaN
-__device__ __forceinline__ void kern_and_dscale(int kind, double d2, double param, double& k, double& dk) {
-  d2 = fmin(d2, 1e150);
-  switch (kind) {
-    case G_SE:
-      k = exp(-0.5 * d2);
-      dk = -d2 * k;
-      return;
-    case G_M12: {
-      double d = sqrt(d2);
-      k = exp(-d);
-      dk = -d * k;
-      return;
-    }
-    case G_M32: {
-      double l = 1.7320508075688772 * sqrt(d2);
-      double e = exp(-l);
-      k = (1.0 + l) * e;
-      dk = -3.0 * d2 * e;
-      return;
-    }
-    case G_M52: {
-      double l = 2.23606797749979 * sqrt(d2);
-      double e = exp(-l);
-      k = (1.0 + l + l * l / 3.0) * e;
-      dk = -(5.0 * d2 / 3.0) * (1.0 + l) * e;
-      return;
-    }
-    case G_WHITE:
-      k = d2 == 0.0 ? 1.0 : 0.0;
-      dk = 0.0;
-      return;
-    default:
-      k = param;
-      dk = 0.0;
-  }
-}
+// (k and d k / d g of every kind: kern_grad.h, shared with the product chains of kprod.hip)
 
 template <int DMAX>
 __global__ __launch_bounds__(256) void grad_block_kernel(const double* Kinv, long ldk, const double* alpha,

@@ -502,6 +502,7 @@ extern "C" int sgp_ctx_create_multi(const int* devices, int ndev, sgp_ctx** out)
     k.dev = devices[i];
     int rc = sgp_ctx_create(devices[i], &k.ctx);
     if (rc) return fail(rc);
+    k.ctx->multi_rank = true;     // (dspec_create refuses what has no sharded instantiation: product chains)
     k.s_panel = k.ctx->stream;    // high priority
     k.s_upd = k.ctx->stream2;
     if (hipSetDevice(k.dev) != hipSuccess) return fail(-2);

@@ -46,6 +46,13 @@ def _refuse_patch_gradient(*specs):
         raise NotImplementedError("gradients through patch_convolve (convolutional) covariance terms are not supported")
 
 
+def _refuse_product_gradient(what, *specs):
+    """`what` through product chains / the RQ and LINEAR kinds is not implemented (the library refuses it too)"""
+    if any(sp.has_kprod for sp in specs):
+        raise NotImplementedError(f"{what} through a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel, "
+                                  "which runs on the product path) is not supported: logpdf_and_gradient(fx, y) is")
+
+
 def _is_prior(f):
     return isinstance(f, (GPPP, SthenoAbstractGP))
 
@@ -261,6 +268,7 @@ def _members(name, fxs, ys, grad, divert_f32):
             kind, nbuf = _lib._noise_args(fx.noise, len(fx))
             spec = _prior_spec(fx.f, fx.x)
             _refuse_patch_gradient(spec)
+            _refuse_product_gradient(f"{name}: the gradient batch / pool", spec)
             if f32:
                 continue
             m = mean_vector(fx.f, fx.x)
@@ -298,11 +306,13 @@ def _grad_buffers(spec, kind, n):
     return np.zeros(n), np.zeros(n), gn, np.zeros(nt), np.zeros(nt)
 
 
-def _grad_record(spec, kind, lp, bufs, inputs=None, x=None, scales=None, rowscale=None):
+def _grad_record(spec, kind, lp, bufs, inputs=None, x=None, scales=None, rowscale=None, gp=None):
+    """gp: the d / d param array of sgp_logpdf_grad_param (specs with product chains): the term records then carry d_param
+    and `_raw` gains the array"""
     gy, gm, gn, gc, gs = bufs
     return dict(logpdf=float(lp), y=gy, mean=gm, noise=(gn if kind != _lib.NOISE_SCALAR else float(gn[0])),
-                terms=_term_records(spec, gc, gs, True), inputs=inputs, x=x, scales=scales, _raw=(gc, gs),
-                _rowscale=rowscale, _spec=spec)
+                terms=_term_records(spec, gc, gs, True, gp), inputs=inputs, x=x, scales=scales,
+                _raw=(gc, gs) if gp is None else (gc, gs, gp), _rowscale=rowscale, _spec=spec)
 
 
 def _grad_failed(spec, info):
@@ -367,6 +377,9 @@ def logpdf_f32(fx, y):
     spec = _prior_spec(fx.f, fx.x)
     if spec.has_stencil:
         raise NotImplementedError("stencil terms have no fp32 path: call logpdf, which runs them in fp64")
+    if spec.has_kprod:
+        raise NotImplementedError("a product of kernels (and the RationalQuadratic / Linear / Polynomial kernels, which run "
+                                  "on the product path) has no fp32 path: call logpdf, which runs them in fp64")
     m = _f64(mean_vector(fx.f, fx.x))
     kind, nbuf = _lib._noise_args(fx.noise, n)
     if kind == _lib.NOISE_DENSE:
@@ -425,13 +438,21 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     f(x, v)); terms: one record per flattened covariance term of the lower block pairs
     {I, J, kind, coef, row_input, col_input, d_coef, d_inscale} where d_coef / d_inscale already
     include the mirror-image pair (J, I).  d_inscale is the derivative w.r.t. a common scale g of the
-    term's inputs (stretch(f, g)); a lengthscale l = 1/g gives d/dl = -g^2 d_inscale."""
+    term's inputs (stretch(f, g)); a lengthscale l = 1/g gives d/dl = -g^2 d_inscale.
+
+    A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
+    sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
+    index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
+    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, c of Linear / Constant).  inputs / scales are not
+    implemented for such models."""
     if not _is_prior(fx.f):
         raise NotImplementedError("gradients are implemented for prior Stheno processes")
     n = len(fx)
     yv = _f64(np.asarray(y, dtype=np.float64).ravel())
     spec = _prior_spec(fx.f, fx.x)
     _refuse_patch_gradient(spec)
+    if inputs or scales:
+        _refuse_product_gradient("logpdf_and_gradient: inputs=True / scales=True", spec)
     m = _f64(mean_vector(fx.f, fx.x))
     kind, nbuf = _lib._noise_args(fx.noise, n)
     lp = np.zeros(1)
@@ -439,6 +460,15 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     nt = max(1, spec.n_terms)
     gx = None
     grs = None
+    if spec.has_kprod:
+        if _ctx().is_multi:
+            raise NotImplementedError("a product of kernels is not supported on a multi-GPU context")
+        gp = np.zeros(nt)
+        rc = _ctx().kprod.sgp_logpdf_grad_param(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
+                                                _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
+                                                _lib.dptr(gc), _lib.dptr(gs), _lib.dptr(gp))
+        _lib.check(rc, "sgp_logpdf_grad_param")
+        return _grad_record(spec, kind, lp[0], bufs, gp=gp)
     if scales:
         if inputs:
             gx = [np.zeros(np.asarray(a).shape, order="F") for a in spec.inputs]
@@ -893,12 +923,63 @@ def elbo(vfe, fx, y=None):
     return float(out[0])
 
 
-def _term_records(spec, gc, gs, symmetric):
+def _chain_keys(spec):
+    """per term: (signature of its chain = the (kind, row_input, col_input, param) of every factor, its position in the chain,
+    the index of the chain's head) -- a plain term is a chain of one.  Two chains of a pair may share a factor, so a factor is
+    identified by its chain."""
+    tp, keys = spec._term_ptr, [None] * spec.n_terms
+    for p in range(len(tp) - 1):
+        t = int(tp[p])
+        while t < int(tp[p + 1]):
+            e = t + 1
+            while e < int(tp[p + 1]) and (spec._terms[e].kind & _lib.KIND_TIMES_PREV):
+                e += 1
+            sig = tuple((spec._terms[f].kind, spec._terms[f].row_input, spec._terms[f].col_input, spec._terms[f].param)
+                        for f in range(t, e))
+            for f in range(t, e):
+                keys[f] = (sig, f - t, t)
+            t = e
+    return keys
+
+
+def _term_records_kprod(spec, gc, gs, gp):
+    """_term_records for a symmetric spec with product chains: one record per factor"""
+    nrb, ncb = len(spec.row_len), len(spec.col_len)
+    tp, out, index, rec_of = spec._term_ptr, [], {}, {}
+    sid, keys = spec.term_scale_ids, _chain_keys(spec)
+    for I in range(nrb):
+        for J in range(min(I + 1, ncb)):
+            for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
+                T = spec._terms[t]
+                sig, pos, head = keys[t]
+                index[(I, J, sig, pos, sid[head][0], sid[head][1])] = rec_of[t] = len(out)
+                out.append(dict(I=I, J=J, kind=T.kind & _lib.KIND_MASK, coef=spec._terms[head].coef, param=T.param,
+                                row_input=T.row_input, col_input=T.col_input, row_scaled=sid[head][0] is not None,
+                                col_scaled=sid[head][1] is not None, t=t, mirror_t=None, chain=rec_of[head], factor=pos,
+                                d_coef=float(gc[t]), d_inscale=float(gs[t]), d_param=float(gp[t])))
+    for I in range(nrb):
+        for J in range(I + 1, ncb):
+            for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
+                sig, pos, head = keys[t]
+                msig = tuple((k, ci, ri, prm) for (k, ri, ci, prm) in sig)
+                k = index.get((J, I, msig, pos, sid[head][1], sid[head][0]))
+                if k is None:
+                    raise AssertionError("symmetric spec without a mirror term: flattener invariant broken")
+                out[k]["mirror_t"] = t
+                out[k]["d_coef"] += float(gc[t])
+                out[k]["d_inscale"] += float(gs[t])
+                out[k]["d_param"] += float(gp[t])
+    return out
+
+
+def _term_records(spec, gc, gs, symmetric, gp=None):
     """One record per flattened term.  For a symmetric spec the mirror-image pair (J, I) is folded
     into the lower pair (I >= J).  The mirror of a term with row / column scale vectors (rs, cs) is
     the term of (J, I) with the inputs AND the scales swapped -- several terms of one block pair may
     differ only in their scales (f3 = f1 + sin * f1 over two blocks), so the scale identities are
     part of the match."""
+    if gp is not None:
+        return _term_records_kprod(spec, gc, gs, gp)
     nrb, ncb = len(spec.row_len), len(spec.col_len)
     tp, out, index = spec._term_ptr, [], {}
     sid = spec.term_scale_ids
@@ -958,6 +1039,7 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
     yv = _f64(np.asarray(y, dtype=np.float64).ravel())
     xx = _prior_spec(fx.f, fx.x)
     _refuse_patch_gradient(zz, xz, xx)
+    _refuse_product_gradient("elbo_and_gradient", zz, xz, xx)
     var_x = _f64(_kernelmatrix_diag(xx))
     out = np.zeros(1)
     gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)

@@ -18,7 +18,8 @@ with  +            -> union of paths                 (addition.jl:20-47; known-f
       stencil      -> the path carries (offsets, weights): ONE term per pair of paths, the library sums the
                       shifted evaluations (include/sthenomi_stencil.h)
 and the leaf kernel expanded into SimpleKernel terms (ScaledKernel -> coefficient, KernelSum ->
-several terms, ScaleTransform -> input scale).  Block pairs without a common atom get no
+several terms, ScaleTransform -> input scale, KernelProduct -> a chain of terms the library multiplies entry by
+entry: include/sthenomi_kprod.h).  Block pairs without a common atom get no
 terms, which the library writes as exact zeros (test/gp/atomic_gp.jl:33).
 """
 from __future__ import annotations
@@ -322,7 +323,34 @@ def build_spec(f, x, f2=None, x2=None):
                     if has_st and (p.geom is not None or q.geom is not None):
                         raise NotImplementedError("a covariance between a patch_convolve view and a stencil view of one "
                                                   "process is not supported")
-                    for (kind, kc, param, s) in p.atom.gp.kernel.leaf_terms():
+                    for (kc, factors) in p.atom.gp.kernel.leaf_products():
+                        if len(factors) > 1 or factors[0][0] > _lib.CONST:
+                            # a product of kernels, or a kind that exists on the product path only: a chain of terms
+                            # (include/sthenomi_kprod.h), each factor reading its own view of the points
+                            if has_st or p.geom is not None or q.geom is not None:
+                                raise NotImplementedError("a product of kernels (or a RationalQuadratic / Linear / Polynomial "
+                                                          "kernel, which runs on the product path) below patch_convolve or a "
+                                                          "stencil is not supported")
+                            if len(factors) > _lib.KPROD_MAX_FACTORS:
+                                raise NotImplementedError(f"a product of {len(factors)} kernels is beyond the library's limit "
+                                                          f"of {_lib.KPROD_MAX_FACTORS} factors")
+                            chain = []
+                            for (kind, param, s) in factors:
+                                ri = table.get(p.X, s, ("row", I, p.chain))
+                                ci = table.get(q.X, s, ("row" if symmetric else "col", J, q.chain))
+                                chain.append((kind, param, ri, ci))
+                            k = ("product", tuple(chain), id(p.r) if p.r is not None else None,
+                                 id(q.r) if q.r is not None else None)
+                            if k in merged:
+                                merged[k][0][0][3] += p.c * q.c * kc
+                            else:
+                                terms = [[chain[0][0], chain[0][2], chain[0][3], p.c * q.c * kc, chain[0][1], p.r, q.r]]
+                                terms += [[kind | _lib.KIND_TIMES_PREV, ri, ci, 1.0, param, None, None]
+                                          for (kind, param, ri, ci) in chain[1:]]
+                                merged[k] = (terms, (None, None), (None, None))
+                                order.append(k)
+                            continue
+                        (kind, param, s), = factors
                         if (p.geom is not None or q.geom is not None) and _kernels.chain_scale(s) is None:
                             raise NotImplementedError("patch_convolve: the kernel's input transform does not commute with "
                                                       "patch extraction (only a scalar ScaleTransform / with_lengthscale "
@@ -341,16 +369,18 @@ def build_spec(f, x, f2=None, x2=None):
                         k = (kind, param, ri, ci, id(p.r) if p.r is not None else None,
                              id(q.r) if q.r is not None else None, p.geom, q.geom, _st_key(sts[0]), _st_key(sts[1]))
                         if k in merged:
-                            merged[k][0][3] += p.c * q.c * kc
+                            merged[k][0][0][3] += p.c * q.c * kc
                         else:
-                            merged[k] = ([kind, ri, ci, p.c * q.c * kc, param, p.r, q.r], (p.geom, q.geom), sts)
+                            merged[k] = ([[kind, ri, ci, p.c * q.c * kc, param, p.r, q.r]], (p.geom, q.geom), sts)
                             order.append(k)
             if order:
-                pairs[(I, J)] = [tuple(merged[k][0]) for k in order]
-                if any(merged[k][1] != (None, None) for k in order):
-                    geoms[(I, J)] = [merged[k][1] for k in order]
-                if any(merged[k][2] != (None, None) for k in order):
-                    stencils[(I, J)] = [merged[k][2] for k in order]
+                # (a key holds one term, or the terms of one chain: a head and its continuations, which have plain sides)
+                pairs[(I, J)] = [tuple(t) for k in order for t in merged[k][0]]
+                plain = (None, None)
+                if any(merged[k][1] != plain for k in order):
+                    geoms[(I, J)] = [merged[k][1] if n == 0 else plain for k in order for n in range(len(merged[k][0]))]
+                if any(merged[k][2] != plain for k in order):
+                    stencils[(I, J)] = [merged[k][2] if n == 0 else plain for k in order for n in range(len(merged[k][0]))]
     spec = _lib.Spec([len(v) for _, v in rows], [len(v) for _, v in cols], table.arrays, pairs, symmetric,
                      geoms=geoms or None, stencils=stencils or None)
     spec._mat_keep = mat  # keep the source arrays alive (ids are identity keys)

@@ -4,8 +4,12 @@ expands into (kind, coef, param, input_chain) leaf terms that the HIP assembly k
 evaluates (stheno.jl_amd/csrc/kernelmatrix.hip).  `input_chain` is the kernel-level input
 transformation (KernelFunctions `TransformedKernel`): a tuple of steps applied to the raw points in
 order -- ("scale", s) for ScaleTransform(s) / with_lengthscale, ("periodic", f) for
-PeriodicTransform(f) (/root/reference/examples/extended_mauna_loa/script.jl:129) -- evaluated on the
-host (O(N D)) when the spec is built.
+PeriodicTransform(f) (/root/reference/examples/extended_mauna_loa/script.jl:129), ("sincos", r) for the
+embedding behind PeriodicKernel(r) -- evaluated on the host (O(N D)) when the spec is built.
+
+Products of kernels (`k1 * k2`, KernelFunctions KernelProduct) expand into chains of such leaves:
+`leaf_products()` returns [(coef, [(kind, param, input_chain), ...])], one entry per product of primitives,
+which the library multiplies entry by entry (include/sthenomi_kprod.h, csrc/kprod.hip).
 """
 from __future__ import annotations
 
@@ -35,6 +39,12 @@ def apply_chain(chain, X):
                 raise ValueError("PeriodicTransform acts on 1-D inputs")
             t = (2.0 * np.pi * v) * X
             X = np.vstack([np.sin(t), np.cos(t)])      # KernelFunctions order: [sin, cos]
+        elif kind == "sincos":
+            # x_d -> [sin 2 pi x_d, cos 2 pi x_d] / (2 r_d): squared distances become sum_d sin^2(pi (x_d - y_d)) / r_d^2,
+            # so SE over these points is KernelFunctions' PeriodicKernel(r); rows: the D sines, then the D cosines
+            h = 0.5 / _sincos_r(v, X.shape[0])[:, None]
+            t = (2.0 * np.pi) * X
+            X = np.vstack([np.sin(t) * h, np.cos(t) * h])
         else:
             raise ValueError(kind)
     return np.asfortranarray(X)
@@ -49,10 +59,23 @@ def chain_vjp(chain, X, gout):
     for (kind, v), xin in zip(reversed(chain), reversed(stack)):
         if kind == "scale":
             g = v * g
+        elif kind == "sincos":
+            D = xin.shape[0]
+            h = (np.pi / _sincos_r(v, D))[:, None]          # 2 pi / (2 r_d)
+            t = (2.0 * np.pi) * xin
+            g = h * (np.cos(t) * g[:D, :] - np.sin(t) * g[D:, :])
         else:
             t = (2.0 * np.pi * v) * xin
             g = (2.0 * np.pi * v) * (np.cos(t) * g[0:1, :] - np.sin(t) * g[1:2, :])
     return g
+
+
+def _sincos_r(v, D):
+    """the D lengthscales of a ("sincos", r) step: r a float or a tuple of D floats"""
+    r = np.full(D, float(v)) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)
+    if r.shape != (D,):
+        raise ValueError(f"PeriodicKernel: {r.size} lengthscales for inputs of dimension {D}")
+    return r
 
 
 def chain_scale(chain):
@@ -69,17 +92,31 @@ class Kernel:
         return KernelSum([self, other])
 
     def __mul__(self, s):
+        if isinstance(s, Kernel):
+            return KernelProduct([self, s])          # k1 * k2 (KernelFunctions KernelProduct)
         return ScaledKernel(self, float(s))
 
-    __rmul__ = __mul__
+    def __rmul__(self, s):
+        return ScaledKernel(self, float(s))
 
     def __matmul__(self, transform):
         """k @ t  ==  k ∘ t  (TransformedKernel)"""
         return TransformedKernel(self, transform)
 
     def leaf_terms(self):
-        """list of (kind, coef, param, input_chain)"""
-        raise NotImplementedError
+        """list of (kind, coef, param, input_chain): the leaves of a product-free kernel"""
+        out = []
+        for coef, factors in self.leaf_products():
+            if len(factors) != 1:
+                raise NotImplementedError("leaf_terms: this kernel contains a product of kernels; use leaf_products()")
+            (kind, param, chain), = factors
+            out.append((kind, coef, param, chain))
+        return out
+
+    def leaf_products(self):
+        """list of (coef, [(kind, param, input_chain), ...]): the kernel as a sum of products of primitives.  Products of
+        sums are distributed, scalings are pulled into coef, transforms are pushed onto every factor below them."""
+        return [(c, [(k, p, ch)]) for (k, c, p, ch) in self.leaf_terms()]
 
 
 class _Simple(Kernel):
@@ -130,6 +167,9 @@ class ScaledKernel(Kernel):
     def leaf_terms(self):
         return [(k, c * self.s2, p, s) for (k, c, p, s) in self.kernel.leaf_terms()]
 
+    def leaf_products(self):
+        return [(c * self.s2, fs) for (c, fs) in self.kernel.leaf_products()]
+
 
 class KernelSum(Kernel):
     def __init__(self, kernels):
@@ -141,6 +181,78 @@ class KernelSum(Kernel):
             out.extend(k.leaf_terms())
         return out
 
+    def leaf_products(self):
+        out = []
+        for k in self.kernels:
+            out.extend(k.leaf_products())
+        return out
+
+
+class KernelProduct(Kernel):
+    """k1 * k2 * ...: the entrywise product (KernelFunctions KernelProduct)"""
+
+    def __init__(self, kernels):
+        self.kernels = []
+        for k in kernels:
+            self.kernels.extend(k.kernels if isinstance(k, KernelProduct) else [k])
+
+    def leaf_products(self):
+        out = [(1.0, [])]
+        for k in self.kernels:
+            out = [(c * kc, fs + kfs) for (c, fs) in out for (kc, kfs) in k.leaf_products()]
+        return out
+
+
+class RationalQuadraticKernel(Kernel):
+    """(1 + d^2 / (2 alpha))^-alpha"""
+
+    def __init__(self, alpha=2.0):
+        self.alpha = float(alpha)
+        if not self.alpha > 0.0:
+            raise ValueError("RationalQuadraticKernel: alpha must be > 0")
+
+    def leaf_terms(self):
+        return [(_lib.RQ, 1.0, self.alpha, ())]
+
+
+class LinearKernel(Kernel):
+    """x'y + c"""
+
+    def __init__(self, c=0.0):
+        self.c = float(c)
+        if not self.c >= 0.0:
+            raise ValueError("LinearKernel: c must be >= 0")
+
+    def leaf_terms(self):
+        return [(_lib.LINEAR, 1.0, self.c, ())]
+
+
+class PolynomialKernel(Kernel):
+    """(x'y + c)^degree: a chain of `degree` LINEAR factors"""
+
+    def __init__(self, degree=2, c=0.0):
+        self.degree, self.c = int(degree), float(c)
+        if self.degree < 1 or self.degree != degree:
+            raise ValueError("PolynomialKernel: degree must be a positive integer")
+        if not self.c >= 0.0:
+            raise ValueError("PolynomialKernel: c must be >= 0")
+
+    def leaf_products(self):
+        return [(1.0, [(_lib.LINEAR, self.c, ())] * self.degree)]
+
+
+class PeriodicKernel(Kernel):
+    """exp(-sum_d sin^2(pi (x_d - y_d)) / r_d^2 / 2) (KernelFunctions PeriodicKernel; period 1): SE over the host-side
+    embedding x_d -> [sin 2 pi x_d, cos 2 pi x_d] / (2 r_d).  No device work of its own."""
+
+    def __init__(self, r=1.0):
+        self.r = float(r) if np.ndim(r) == 0 else tuple(float(v) for v in np.asarray(r, dtype=np.float64).ravel())
+        if not np.all(np.asarray(self.r) > 0.0):
+            raise ValueError("PeriodicKernel: r must be > 0")
+
+    def leaf_terms(self):
+        return [(_lib.SE, 1.0, 0.0, (("sincos", self.r),))]
+
 
 class ScaleTransformedKernel(Kernel):
     """k o ScaleTransform(s)"""
@@ -150,6 +262,9 @@ class ScaleTransformedKernel(Kernel):
 
     def leaf_terms(self):
         return [(k, c, p, _push(("scale", self.s), ch)) for (k, c, p, ch) in self.kernel.leaf_terms()]
+
+    def leaf_products(self):
+        return [(c, [(k, p, _push(("scale", self.s), ch)) for (k, p, ch) in fs]) for (c, fs) in self.kernel.leaf_products()]
 
 
 class ScaleTransform:
@@ -180,6 +295,10 @@ class TransformedKernel(Kernel):
     def leaf_terms(self):
         st = self.transform.step()
         return [(k, c, p, _push(st, ch)) for (k, c, p, ch) in self.kernel.leaf_terms()]
+
+    def leaf_products(self):
+        st = self.transform.step()
+        return [(c, [(k, p, _push(st, ch)) for (k, p, ch) in fs]) for (c, fs) in self.kernel.leaf_products()]
 
 
 def with_lengthscale(kernel, l):

@@ -21,9 +21,14 @@ EXTEND_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend.so")
 EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
+KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
 
 # kernel kinds / noise kinds (sthenomi.h enums)
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
+RQ, LINEAR = 6, 7                  # evaluated by the product-chain path only (include/sthenomi_kprod.h)
+KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
+KIND_MASK = 0xff
+KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain
 NOISE_SCALAR, NOISE_DIAG, NOISE_DENSE = range(3)
 
 
@@ -237,6 +242,19 @@ _SIGS_STENCIL = {
 }
 
 
+# include/sthenomi_kprod.h: the parameter gradient through product chains and plain terms alike, exported by
+# libsthenomi_kprod.so (links against the product library and works on its contexts) -- logpdf_and_gradient reaches it through
+# kprod_lib()
+_SIGS_KPROD = {
+    "sgp_logpdf_grad_param": (C.c_int, [_P, C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
+}
+
+
+def kprod_symbols():
+    """Names include/sthenomi_kprod.h declares: the entry points of libsthenomi_kprod.so."""
+    return sorted(_SIGS_KPROD)
+
+
 def stencil_symbols():
     """Names include/sthenomi_stencil.h declares: the entry points of libsthenomi_stencil.so."""
     return sorted(_SIGS_STENCIL)
@@ -420,6 +438,27 @@ def stencil_lib():
         return lib
 
 
+_kprod = None
+
+
+def kprod_lib():
+    """dlopen libsthenomi_kprod.so (include/sthenomi_kprod.h) after the product library it links against."""
+    global _kprod
+    load()
+    with _lib_lock:
+        if _kprod is not None:
+            return _kprod
+        if not os.path.exists(KPROD_LIB_PATH):
+            raise SthenoMIError(f"{KPROD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(KPROD_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_KPROD.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _kprod = lib
+        return lib
+
+
 def load():
     """dlopen libsthenomi.so (after torch, so both share one HIP runtime) and type its symbols."""
     global _lib
@@ -499,6 +538,11 @@ class Context:
     def pool(self):
         """libsthenomi_pool.so (sthenomi_pool.h): `ctx.pool.sgp_logpdf_pool(ctx.handle, ...)`"""
         return pool_lib()
+
+    @property
+    def kprod(self):
+        """libsthenomi_kprod.so (sthenomi_kprod.h): `ctx.kprod.sgp_logpdf_grad_param(ctx.handle, ...)`"""
+        return kprod_lib()
 
     @property
     def extend(self):
@@ -613,6 +657,9 @@ class Spec:
                 term_ptr.append(len(terms))
         self.has_patch = any(g != (None, None) for g in self.term_geoms)
         self.has_stencil = any(st != (None, None) for st in self.term_stencils)
+        # product chains / the RQ and LINEAR kinds (include/sthenomi_kprod.h): a term whose kind carries KIND_TIMES_PREV
+        # continues the chain of the term before it
+        self.has_kprod = any((int(t[0]) & KIND_TIMES_PREV) or (int(t[0]) & KIND_MASK) > CONST for t in terms)
         self._bound = None
         self.n_terms = len(terms)
         self._term_ptr = np.asarray(term_ptr, dtype=np.int32)
@@ -689,8 +736,8 @@ class Spec:
     def f32_supported(self):
         """The fp32 device kernels (csrc/f32.hip: assemble_f32) take input dimension <= 16 and, per block pair,
         (number of terms) x (dimension rounded up to a power of two) <= 64; anything else runs on the fp64 path."""
-        if self.has_patch or self.has_stencil:
-            return False                 # patch / stencil terms: fp64 only (a Float32 model runs there and is rounded back)
+        if self.has_patch or self.has_stencil or self.has_kprod:
+            return False                 # patch / stencil / product terms: fp64 only (a Float32 model runs there and is rounded back)
         tp = self._term_ptr
         for p in range(len(tp) - 1):
             t0, t1 = int(tp[p]), int(tp[p + 1])
