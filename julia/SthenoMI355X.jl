@@ -20,6 +20,8 @@ const LIB_BATCH = get(ENV, "STHENOMI_BATCH_LIB", joinpath(dirname(LIB), "libsthe
 const LIB_POOL = get(ENV, "STHENOMI_POOL_LIB", joinpath(dirname(LIB), "libsthenomi_pool.so"))
 # include/sthenomi_extend.h (sgp_posterior_extend): likewise
 const LIB_EXTEND = get(ENV, "STHENOMI_EXTEND_LIB", joinpath(dirname(LIB), "libsthenomi_extend.so"))
+# include/sthenomi_postfx.h (sgp_posterior_rand / _logpdf and their sparse forms: rand / logpdf of f_post(x*, Σ*)): likewise
+const LIB_POSTFX = get(ENV, "STHENOMI_POSTFX_LIB", joinpath(dirname(LIB), "libsthenomi_postfx.so"))
 # include/sthenomi_kprod.h (sgp_logpdf_grad_param: + d / d kernel parameters, through product chains and plain terms): likewise
 const LIB_KPROD = get(ENV, "STHENOMI_KPROD_LIB", joinpath(dirname(LIB), "libsthenomi_kprod.so"))
 const SthenoFGP = FiniteGP{<:Union{GPPP,SthenoAbstractGP}}
@@ -578,6 +580,51 @@ AbstractGPs.mean(p::MI355XSparsePosterior, xs::AbstractVector) = predict(p, xs)[
 AbstractGPs.var(p::MI355XSparsePosterior, xs::AbstractVector) = predict(p, xs)[2]
 AbstractGPs.cov(p::MI355XSparsePosterior, xs::AbstractVector) = predict(p, xs; want_cov = true)[3]
 AbstractGPs.mean_and_var(p::MI355XSparsePosterior, xs::AbstractVector) = predict(p, xs)[1:2]
+
+# ---- rand / logpdf of f_post(x*, Σ*) against the kept factor (include/sthenomi_postfx.h) -----------------------------
+# `rand(rng, f_post(xp, 1e-9), S)` and `logpdf(f_post(xp, σ²), y*)`, how every reference example ends: the posterior
+# covariance is formed, Σ* added and the sum factored on the device; only x*, Σ*, Z / Y and the result cross.  On a
+# multi-GPU context the library refuses (the factor is sharded): condition on one device to sample there.
+const PostFGP = FiniteGP{<:MI355XPosterior}
+const SparsePostFGP = FiniteGP{<:MI355XSparsePosterior}
+postfx_specs(p::MI355XPosterior, xs) = (build_spec(p.prior, xs, p.prior, p.x), build_spec(p.prior, xs), collect(Float64, mean(p.prior, xs)))
+postfx_specs(p::MI355XSparsePosterior, xs) = (build_spec(p.prior, xs, p.prior, p.z), build_spec(p.prior, xs), collect(Float64, mean(p.prior, xs)))
+function logpdf(fx::PostFGP, Y::AbstractMatrix{<:Real})
+    cr, ss, ms = postfx_specs(fx.f, fx.x); kind, nz = noise_args(fx.Σy); Yd = Matrix{Float64}(Y); out = zeros(size(Yd, 2))
+    GC.@preserve cr ss ms nz Yd out check(
+        @ccall LIB_POSTFX.sgp_posterior_logpdf(fx.f.handle::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec}, ms::Ptr{Float64},
+                                               kind::Cint, nz::Ptr{Float64}, Yd::Ptr{Float64}, size(Yd, 1)::Int64,
+                                               size(Yd, 2)::Int64, out::Ptr{Float64})::Cint)
+    return out
+end
+function logpdf(fx::SparsePostFGP, Y::AbstractMatrix{<:Real})
+    cr, ss, ms = postfx_specs(fx.f, fx.x); kind, nz = noise_args(fx.Σy); Yd = Matrix{Float64}(Y); out = zeros(size(Yd, 2))
+    GC.@preserve cr ss ms nz Yd out check(
+        @ccall LIB_POSTFX.sgp_sparse_posterior_logpdf(fx.f.handle::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
+                                                      ms::Ptr{Float64}, kind::Cint, nz::Ptr{Float64}, Yd::Ptr{Float64},
+                                                      size(Yd, 1)::Int64, size(Yd, 2)::Int64, out::Ptr{Float64})::Cint)
+    return out
+end
+logpdf(fx::Union{PostFGP,SparsePostFGP}, y::AbstractVector{<:Real}) = only(logpdf(fx, reshape(y, :, 1)))
+function rand_with(fx::PostFGP, Z::Matrix{Float64})           # m* .+ L* Z for a given draw
+    cr, ss, ms = postfx_specs(fx.f, fx.x); kind, nz = noise_args(fx.Σy); out = similar(Z)
+    GC.@preserve cr ss ms nz Z out check(
+        @ccall LIB_POSTFX.sgp_posterior_rand(fx.f.handle::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec}, ms::Ptr{Float64},
+                                             kind::Cint, nz::Ptr{Float64}, Z::Ptr{Float64}, size(Z, 1)::Int64,
+                                             size(Z, 2)::Int64, out::Ptr{Float64}, size(out, 1)::Int64)::Cint)
+    return out
+end
+function rand_with(fx::SparsePostFGP, Z::Matrix{Float64})
+    cr, ss, ms = postfx_specs(fx.f, fx.x); kind, nz = noise_args(fx.Σy); out = similar(Z)
+    GC.@preserve cr ss ms nz Z out check(
+        @ccall LIB_POSTFX.sgp_sparse_posterior_rand(fx.f.handle::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
+                                                    ms::Ptr{Float64}, kind::Cint, nz::Ptr{Float64}, Z::Ptr{Float64},
+                                                    size(Z, 1)::Int64, size(Z, 2)::Int64, out::Ptr{Float64},
+                                                    size(out, 1)::Int64)::Cint)
+    return out
+end
+rand(rng::AbstractRNG, fx::Union{PostFGP,SparsePostFGP}, S::Int) = rand_with(fx, randn(rng, Float64, length(fx), S))
+rand(rng::AbstractRNG, fx::Union{PostFGP,SparsePostFGP}) = vec(rand(rng, fx, 1))
 
 # ---- ChainRulesCore.rrule for logpdf(fx, y): what `Zygote.gradient(θ -> logpdf(build_gp(θ)(x, σ²), y), θ)`
 # needs (reference contract: test/gaussian_process_probabilistic_programme.jl:99-104 "does not error";

@@ -2984,16 +2984,7 @@ __global__ void set_row_kernel(double* G, long ld, long row, const double* v, lo
   if (i < n) G[row + i * ld] = v[i];
 }
 
-struct sgp_sparse_post {
-  sgp_ctx* ctx = nullptr;
-  long ctx_serial = 0;
-  long M = 0, m_pad = 0;
-  double* dLz = nullptr;   // m_pad x m_pad factor of Kzz + Sigma_z (ld = m_pad)
-  double* d_wz = nullptr;  // inverse diagonal blocks of Lz
-  double* dG = nullptr;    // (m_pad + 128) x m_pad: factor of A A' + I, row m_pad = (Le^-1 A delta)'
-  double* d_wg = nullptr;
-  long ldg = 0;
-};
+// (struct sgp_sparse_post: ctx.h -- postfx.hip reads the kept factors)
 
 extern "C" int sgp_sparse_posterior_destroy(sgp_sparse_post* p) {
   if (!p) return 0;

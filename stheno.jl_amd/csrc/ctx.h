@@ -211,6 +211,19 @@ struct sgp_post {
   sgp_mpost* mp = nullptr;  // non-null: the factor is sharded over the ranks of a multi-GPU context (multi.hip)
 };
 
+// the kept M x M factors of a sparse (VFE) posterior (sgp_sparse_posterior_create; capi.hip) -- postfx.hip reads them
+// (include/sthenomi_postfx.h)
+struct sgp_sparse_post {
+  sgp_ctx* ctx = nullptr;
+  long ctx_serial = 0;
+  long M = 0, m_pad = 0;
+  double* dLz = nullptr;   // m_pad x m_pad factor of Kzz + Sigma_z (ld = m_pad)
+  double* d_wz = nullptr;  // inverse diagonal blocks of Lz
+  double* dG = nullptr;    // (m_pad + 128) x m_pad: factor of A A' + I, row m_pad = (Le^-1 A delta)'
+  double* d_wg = nullptr;
+  long ldg = 0;
+};
+
 namespace sgp {
 
 extern thread_local sgp_ctx* tl_ctx;  // the context whose entry point this thread is inside

@@ -46,6 +46,18 @@ int drv_posterior_extend(sgp_post* post, const sgp_cov_spec* spec_all, const dou
                          double* logpdf_out);
 // times the row solve of `tile_rows` 128-row tiles against the kept factor by one schedule (sthenomi_extend_bench.h: sgp_bench_extend_row_solve)
 int drv_extend_row_solve_ms(sgp_post* post, int64_t tile_rows, int schedule, int reps, double* ms_out);
+// rand / logpdf of a posterior FiniteGP against the kept factor (include/sthenomi_postfx.h, forwarded from
+// libsthenomi_postfx.so) -- postfx.hip; Z / Y: N* x cols with leading dimension ldin, rand's result N* x cols with ldo
+int drv_posterior_rand(sgp_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss, const double* mean_s,
+                       int noise_kind, const double* noise, const double* Z, int64_t ldz, int64_t S, double* out, int64_t ldo);
+int drv_posterior_logpdf(sgp_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss, const double* mean_s,
+                         int noise_kind, const double* noise, const double* Y, int64_t ldy, int64_t ncols, double* out);
+int drv_sparse_posterior_rand(sgp_sparse_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss,
+                              const double* mean_s, int noise_kind, const double* noise, const double* Z, int64_t ldz,
+                              int64_t S, double* out, int64_t ldo);
+int drv_sparse_posterior_logpdf(sgp_sparse_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss,
+                                const double* mean_s, int noise_kind, const double* noise, const double* Y, int64_t ldy,
+                                int64_t ncols, double* out);
 // include/sthenomi_kprod.h: sgp_logpdf_grad_param, forwarded from libsthenomi_kprod.so; takes the context itself
 int drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
                           const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,

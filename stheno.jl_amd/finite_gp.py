@@ -220,6 +220,34 @@ def _spec_mean_noise(fx):
     return zero_spec(n), fx.f.mean(fx.x), _lib.NOISE_DENSE, np.asfortranarray(Cm)
 
 
+def _postfx_route(fx):
+    """rand / logpdf of a posterior FiniteGP against the kept factor (include/sthenomi_postfx.h): the posterior covariance
+    is formed, S* added and the sum factored where the factor lives, instead of cov(f_post, x*) coming down to the host
+    and going back up as dense noise (_spec_mean_noise).  The values are those of that route bit for bit.
+
+    Returns (library, entry-point stem, handle, cross, prior_ss, mean_s, noise kind, noise buffer), or None where the host
+    route stays: a process that is neither the exact nor the VFE posterior, a multi-GPU context (the factor is sharded),
+    a context without the library (the NumPy double of the CPU suites), and a model all of whose inputs are Float32 --
+    there the one output-type rule rounds mean and covariance to Float32 BEFORE they are factored, which only the host
+    route reproduces."""
+    f = fx.f
+    if not isinstance(f, (PosteriorGP, ApproxPosteriorGP)):
+        return None
+    ctx = _ctx()
+    lib = None if getattr(ctx, "is_multi", False) else getattr(ctx, "postfx", None)
+    if lib is None:
+        return None
+    if all(_eltype(x) == np.float32 for x in (fx.x, *f._train_inputs())):
+        return None
+    kind, nbuf = _lib._noise_args(fx.noise, len(fx))
+    cross, _, _ = build_spec(f.prior, fx.x, f.prior, f._train_inputs()[0])
+    pss = _prior_spec(f.prior, fx.x)
+    ms = _f64(mean_vector(f.prior, fx.x))
+    if isinstance(f, PosteriorGP):
+        return lib, "sgp_posterior", f._ensure(), cross, pss, ms, kind, nbuf
+    return lib, "sgp_sparse_posterior", f._h, cross, pss, ms, kind, nbuf
+
+
 def logpdf(fx, y):
     """logpdf(fx, y::Vector) -> float;  logpdf(fx, Y::Matrix) -> one value per column."""
     if isinstance(fx, SparseFiniteGP):
@@ -238,9 +266,16 @@ def logpdf(fx, y):
     Y = _f64(Y.reshape(len(fx), -1))
     if Y.shape[0] != len(fx):
         raise ValueError("length(y) != length(fx)")
+    out = np.zeros(Y.shape[1])
+    route = _postfx_route(fx)
+    if route is not None:
+        lib, stem, h, cross, pss, ms, kind, nbuf = route
+        rc = getattr(lib, stem + "_logpdf")(h, cross.ref(), pss.ref(), _lib.dptr(ms), kind, _lib.dptr(nbuf), _lib.dptr(Y),
+                                            Y.shape[0], Y.shape[1], _lib.dptr(out))
+        _lib.check(rc, stem + "_logpdf")
+        return float(out[0]) if vec else out
     spec, m, kind, nbuf = _spec_mean_noise(fx)
     m = _f64(m)
-    out = np.zeros(Y.shape[1])
     rc = _ctx().lib.sgp_logpdf(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf), _lib.dptr(Y),
                                Y.shape[0], Y.shape[1], _lib.dptr(out))
     _lib.check(rc, "sgp_logpdf")
@@ -650,6 +685,16 @@ def rand(rng, fx, S=None, Z=None):
     if Z is None:
         Z = _draw(rng, n, s)
     Z = _f64(np.asarray(Z, dtype=np.float64).reshape(n, s))
+    route = _postfx_route(fx)
+    if route is not None:
+        lib, stem, h, cross, pss, ms, kind, nbuf = route
+        out = np.zeros((n, s), order="F")
+        rc = getattr(lib, stem + "_rand")(h, cross.ref(), pss.ref(), _lib.dptr(ms), kind, _lib.dptr(nbuf), _lib.dptr(Z), n, s,
+                                          _lib.dptr(out), n)
+        _lib.check(rc, stem + "_rand")
+        if _eltype(fx.x) == np.float32:      # (as below: returned in the model's type)
+            out = out.astype(np.float32)
+        return out[:, 0].copy() if S is None else out
     spec, m, kind, nbuf = _spec_mean_noise(fx)
     m = _f64(m)
     if _is_prior(fx.f) and _eltype(fx.x) == np.float32 and kind != _lib.NOISE_DENSE and spec.f32_supported():

@@ -19,6 +19,7 @@ BATCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_batch.so")
 POOL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_pool.so")
 EXTEND_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend.so")
 EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so")
+POSTFX_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_postfx.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
 KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
@@ -210,6 +211,18 @@ _SIGS_EXTEND = {
     "sgp_posterior_extend": (C.c_int, [_P, C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, C.c_int64, C.c_int64, _D, _D]),
 }
 
+# include/sthenomi_postfx.h: rand / logpdf of a posterior FiniteGP against the kept factor, exported by libsthenomi_postfx.so (it
+# links against the product library and works on its posteriors) -- rand / logpdf reach it through postfx_lib() / Context.postfx
+_POSTFX_RAND = (C.c_int, [_P, C.POINTER(sgp_cov_spec), C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, C.c_int64, C.c_int64, _D,
+                          C.c_int64])
+_POSTFX_LOGPDF = (C.c_int, [_P, C.POINTER(sgp_cov_spec), C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, C.c_int64, C.c_int64, _D])
+_SIGS_POSTFX = {
+    "sgp_posterior_rand": _POSTFX_RAND,
+    "sgp_posterior_logpdf": _POSTFX_LOGPDF,
+    "sgp_sparse_posterior_rand": _POSTFX_RAND,
+    "sgp_sparse_posterior_logpdf": _POSTFX_LOGPDF,
+}
+
 # include/sthenomi_extend_bench.h: the measurement hook of the extension (libsthenomi_extend_bench.so; tools and tests only)
 _SIGS_EXTEND_BENCH = {
     "sgp_bench_extend_row_solve": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D]),
@@ -268,6 +281,11 @@ def conv_symbols():
 def extend_symbols():
     """Names include/sthenomi_extend.h declares: the entry points of libsthenomi_extend.so."""
     return sorted(_SIGS_EXTEND)
+
+
+def postfx_symbols():
+    """Names include/sthenomi_postfx.h declares: the entry points of libsthenomi_postfx.so."""
+    return sorted(_SIGS_POSTFX)
 
 
 def batch_symbols():
@@ -372,6 +390,27 @@ def extend_lib():
             fn.restype = res
             fn.argtypes = args
         _extend = lib
+        return lib
+
+
+_postfx = None
+
+
+def postfx_lib():
+    """dlopen libsthenomi_postfx.so (include/sthenomi_postfx.h) after the product library it links against."""
+    global _postfx
+    load()
+    with _lib_lock:
+        if _postfx is not None:
+            return _postfx
+        if not os.path.exists(POSTFX_LIB_PATH):
+            raise SthenoMIError(f"{POSTFX_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(POSTFX_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_POSTFX.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _postfx = lib
         return lib
 
 
@@ -548,6 +587,11 @@ class Context:
     def extend(self):
         """libsthenomi_extend.so (sthenomi_extend.h): `ctx.extend.sgp_posterior_extend(post_handle, ...)`"""
         return extend_lib()
+
+    @property
+    def postfx(self):
+        """libsthenomi_postfx.so (sthenomi_postfx.h): `ctx.postfx.sgp_posterior_logpdf(post_handle, ...)`"""
+        return postfx_lib()
 
     @property
     def ndev(self):
