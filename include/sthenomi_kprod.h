@@ -31,9 +31,13 @@
  * sgp_logpdf_grad, whose outputs keep one entry per element of spec->terms: for a chain with head h
  *     grad_coef[h]       = sum_ij G_ij rs_i cs_j prod_f k_f        grad_coef[continuation] = 0
  *     grad_inscale[f]    = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != f} k_f') d k_f(g x, g x') / dg at g = 1
- * (LINEAR: 2 x'y;  RQ: -d^2 (1 + d^2 / (2 alpha))^(-alpha - 1)).  These refuse them with rc < 0 and a message naming
- * "product": sgp_logpdf_grad_x / _xs, every sgp_elbo_grad*, sgp_kernelmatrix_diag_grad*, sgp_logpdf_grad_batch,
- * sgp_logpdf_grad_pool, the fp32 entry points (sgp_*_f32) and every multi-GPU context. */
+ * (LINEAR: 2 x'y;  RQ: -d^2 (1 + d^2 / (2 alpha))^(-alpha - 1)).  The gradients with respect to the points the factors read,
+ * to function-valued scales and everything behind the ELBO come from the superset family of include/sthenomi_kprod_grad.h
+ * (sgp_logpdf_grad_param_xs, sgp_kernelmatrix_diag_grad_param, sgp_elbo_grad_param; libsthenomi_kprod_grad.so).  The entry points of include/sthenomi.h
+ * for those gradients keep refusing chains with rc < 0 and a message naming "product" and the function to call instead:
+ * sgp_logpdf_grad_x / _xs, every sgp_elbo_grad*, sgp_kernelmatrix_diag_grad*.  What still refuses outright, each a pull request
+ * of its own: sgp_logpdf_grad_batch, sgp_logpdf_grad_pool, the fp32 entry points (sgp_*_f32), every multi-GPU context, and
+ * products with patch or stencil sides. */
 #ifndef STHENOMI_KPROD_H
 #define STHENOMI_KPROD_H
 

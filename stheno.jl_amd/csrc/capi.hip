@@ -1744,6 +1744,34 @@ extern "C" int sgp_rand(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* me
   return with_df_fallback(ctx, [&]() { return sgp_rand_impl(ctx, spec, mean, noise_kind, noise, Z, ldz, S, out, ldo); });
 }
 
+// the caller's index of the term at device position t (a spec with product chains keeps its plain terms in front: dspec_create)
+static inline int term_src_of(const sgp_dspec* ds, int t) { return ds->n_kprod ? ds->term_src[t] : t; }
+// the chain whose head sits at device position t: one past its last factor, and its DMAX
+static inline int chain_end(const sgp_dspec* ds, int t, int t1) {
+  int e = t + 1;
+  while (e < t1 && (ds->h_terms[e].kind & SGP_KIND_TIMES_PREV)) ++e;
+  return e;
+}
+static inline int chain_dmax(const sgp_dspec* ds, int t, int e) {
+  int dm = 1;
+  for (int f = t; f < e; ++f) dm = std::max(dm, pow2ceil(ds->h_terms[f].dim));
+  return dm;
+}
+
+// per-term results back to the host (dst == NULL: not asked for), in the caller's order
+static int fetch_terms(const sgp_dspec* ds, double* dst, const double* d_src) {
+  const size_t nt = ds->h_terms.size();
+  if (!dst || !nt) return 0;
+  if (!ds->n_kprod) {
+    SGP_HIP(hipMemcpy(dst, d_src, sizeof(double) * nt, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  std::vector<double> tmp(nt);
+  SGP_HIP(hipMemcpy(tmp.data(), d_src, sizeof(double) * nt, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < nt; ++k) dst[ds->term_src[k]] = tmp[k];
+  return 0;
+}
+
 // sum_ij G_ij dC_ij / d theta per flattened term of every block pair of `ds` (grad.hip):
 // G = (alpha alpha' - Kinv) / 2 when alpha != nullptr, else G = the matrix at `Gm` itself.
 // Product chains (ds->n_kprod; kprod.hip) are contracted one chain per launch, only where the caller says it carries them
@@ -1777,9 +1805,7 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
           CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, 1, 1, trf, tcf, trl - trf, tcl - tcf,
                                      dpart.p, nullptr, nullptr, dgp + t, s));
       for (int t = tk; t < t1;) {
-        int e = t + 1, cdmax = 1;
-        while (e < t1 && (ds->h_terms[e].kind & SGP_KIND_TIMES_PREV)) ++e;
-        for (int f = t; f < e; ++f) cdmax = std::max(cdmax, pow2ceil(ds->h_terms[f].dim));
+        const int e = chain_end(ds, t, t1), cdmax = chain_dmax(ds, t, e);
         CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, e - t, cdmax, trf, tcf, trl - trf,
                                    tcl - tcf, dpart.p, dgc + t, dgs + t, dgp ? dgp + t : nullptr, s));
         t = e;
@@ -1804,9 +1830,9 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
   CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
-  CHECK_ARG(!(grad_inputs || grad_rowscale) || !spec_has_kprod(spec),
+  CHECK_ARG(!(grad_inputs || grad_rowscale) || with_param || !spec_has_kprod(spec),
             "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
-            "not supported");
+            "not supported: call sgp_logpdf_grad_param_xs (include/sthenomi_kprod_grad.h)");
   CHECK_ARG(!(with_param && ctx->multi), "sgp_logpdf_grad_param: not supported on a multi-GPU context");
   CtxScope scope(ctx);
   // a multi-GPU context shards the gradient -- kernel terms, noise, y, the mean and (round 6) the input points and function
@@ -1914,18 +1940,32 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
       for (int J = 0; J < ds->ncb; ++J) {
         if (ds->row_len[I] == 0 || ds->col_len[J] == 0) continue;
         int p = I * ds->ncb + J;
-        for (int t = ds->term_ptr[p]; t < ds->term_ptr[p + 1]; ++t) {
+        const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
+        for (int t = ds->term_ptr[p]; t < t1;) {
           int a = ds->term_row_input[t];
           double* gsv = nullptr;
-          if (grad_rowscale && grad_rowscale[t] && ds->h_terms[t].rs) {
+          if (grad_rowscale && grad_rowscale[term_src_of(ds, t)] && ds->h_terms[t].rs) {
             CHECK_RC(dgr[t].alloc((size_t)ds->row_len[I]));
             SGP_HIP(hipMemsetAsync(dgr[t].p, 0, sizeof(double) * ds->row_len[I], s));
             gsv = dgr[t].p;
           }
-          if (!grad_inputs && !gsv) continue;
-          CHECK_RC(launch_grad_inputs(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                      ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
-                                      grad_inputs ? dgx[a].p : nullptr, s, gsv));
+          if (t >= tk) {   // a chain: every factor's row input and the head's row scale in one pass (kprod.hip)
+            const int e = chain_end(ds, t, t1);
+            if (grad_inputs || gsv) {
+              double* gxf[SGP_KPROD_MAX_FACTORS];
+              for (int f = t; f < e; ++f) gxf[f - t] = grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
+              CHECK_RC(launch_grad_kprod_inputs(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                                ds->col_len[J], &ds->h_terms[t], e - t, chain_dmax(ds, t, e), 0, 2.0, gxf, gsv,
+                                                s));
+            }
+            t = e;
+            continue;
+          }
+          if (grad_inputs || gsv)
+            CHECK_RC(launch_grad_inputs(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                        ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
+                                        grad_inputs ? dgx[a].p : nullptr, s, gsv));
+          ++t;
         }
       }
     }
@@ -1950,20 +1990,9 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
                       hipMemcpyDeviceToHost));
   // one entry per element of spec->terms, in the CALLER's order: a spec with product chains keeps its plain terms in front of
   // them on the device (dspec_create), so its entries go back through term_src
-  auto fetch_terms = [&](double* dst, const double* d_src) -> int {
-    if (!dst || !nterms_total) return 0;
-    if (!ds->n_kprod) {
-      SGP_HIP(hipMemcpy(dst, d_src, sizeof(double) * nterms_total, hipMemcpyDeviceToHost));
-      return 0;
-    }
-    std::vector<double> tmp(nterms_total);
-    SGP_HIP(hipMemcpy(tmp.data(), d_src, sizeof(double) * nterms_total, hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < nterms_total; ++k) dst[ds->term_src[k]] = tmp[k];
-    return 0;
-  };
-  CHECK_RC(fetch_terms(grad_coef, dgc.p));
-  CHECK_RC(fetch_terms(grad_inscale, dgs.p));
-  if (grad_param) CHECK_RC(fetch_terms(grad_param, dgp.p));
+  CHECK_RC(fetch_terms(ds, grad_coef, dgc.p));
+  CHECK_RC(fetch_terms(ds, grad_inscale, dgs.p));
+  if (grad_param) CHECK_RC(fetch_terms(ds, grad_param, dgp.p));
   if (grad_inputs) {
     for (int k = 0; k < spec->n_inputs; ++k) {
       const sgp_input& in = spec->inputs[k];
@@ -1976,7 +2005,8 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
       for (int J = 0; J < ds->ncb; ++J)
         for (int t = ds->term_ptr[I * ds->ncb + J]; t < ds->term_ptr[I * ds->ncb + J + 1]; ++t)
           if (dgr[t].p && ds->row_len[I] > 0)
-            SGP_HIP(hipMemcpy(grad_rowscale[t], dgr[t].p, sizeof(double) * ds->row_len[I], hipMemcpyDeviceToHost));
+            SGP_HIP(hipMemcpy(grad_rowscale[term_src_of(ds, t)], dgr[t].p, sizeof(double) * ds->row_len[I],
+                              hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -2008,6 +2038,17 @@ int sgp::drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const dou
   return with_df_fallback(ctx, [&]() {
     return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                             grad_inscale, nullptr, nullptr, grad_param, true);
+  });
+}
+
+// include/sthenomi_kprod_grad.h: sgp_logpdf_grad_param_xs -- the same with the input points and the row scales
+int sgp::drv_logpdf_grad_param_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
+                                  const double* noise, const double* y, double* logpdf_out, double* grad_y, double* grad_mean,
+                                  double* grad_noise, double* grad_coef, double* grad_inscale, double* grad_param,
+                                  double* const* grad_inputs, double* const* grad_rowscale) {
+  return with_df_fallback(ctx, [&]() {
+    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                            grad_inscale, grad_inputs, grad_rowscale, grad_param, true);
   });
 }
 
@@ -3442,7 +3483,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
                           double* grad_coef_zz, double* grad_inscale_zz, double* grad_coef_xz,
                           double* grad_inscale_xz, double* const* grad_inputs_zz, double* const* grad_inputs_xz,
                           double* const* grad_rowscale_zz = nullptr, double* const* grad_rowscale_xz = nullptr,
-                          double* const* grad_colscale_xz = nullptr, const sgp::ElboGradShard* shard = nullptr) {
+                          double* const* grad_colscale_xz = nullptr, const sgp::ElboGradShard* shard = nullptr,
+                          double* grad_param_zz = nullptr, double* grad_param_xz = nullptr, bool kprod_ok = false) {
   // shard (round 6, multi.hip: sgp_multi_elbo_grad): this call sees ONE rank's slice of the data points (xz, var_x, mean_x, a
   // diagonal noise_x, y and the per-point results are the slice's).  The sums over data points -- A A', A delta, the four
   // scalar sums -- are added up over the ranks by shard->reduce (every rank gets the total), the M x M stage runs replicated
@@ -3464,7 +3506,7 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   const long ldg = m_pad + TILE + m_pad;    // [A A' + I ; (A delta)' ; I]
   hipStream_t s = ctx->stream;
   DevBuf dA, dG, dB, dBinv, dZ, dS, dRZ, dT1, dGzz, dy, dmean, dvar, ddelta, drsig, dots, sq, du, dut, dgy, dgsy,
-      dpart, dgcz, dgsz, dgcx, dgsx;
+      dpart, dgcz, dgsz, dgcx, dgsx, dgpz, dgpx;
   NoiseDev ndx, ndz;
   CHECK_RC(dA.alloc((size_t)ld * m_pad));
   CHECK_RC(dG.alloc((size_t)ldg * m_pad));
@@ -3497,6 +3539,14 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   SGP_HIP(hipMemsetAsync(dgsz.p, 0, sizeof(double) * ntz, s));
   SGP_HIP(hipMemsetAsync(dgcx.p, 0, sizeof(double) * ntx, s));
   SGP_HIP(hipMemsetAsync(dgsx.p, 0, sizeof(double) * ntx, s));
+  if (grad_param_zz) {
+    CHECK_RC(dgpz.alloc(ntz));
+    SGP_HIP(hipMemsetAsync(dgpz.p, 0, sizeof(double) * ntz, s));
+  }
+  if (grad_param_xz) {
+    CHECK_RC(dgpx.alloc(ntx));
+    SGP_HIP(hipMemsetAsync(dgpx.p, 0, sizeof(double) * ntx, s));
+  }
   double* d_o = ctx->d_scal + 1;  // h[0..2]; h[3] at +4, h[4] at +5, h[5] at +6
   SGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
   SGP_HIP(hipMemsetAsync(ddelta.p, 0, sizeof(double) * n_rows, s));
@@ -3611,10 +3661,12 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
     CHECK_RC(launch_gemm_nt(dT1.p, m_pad, Jm, ld, dGzz.p, m_pad, m_pad, m_pad, m_pad, -0.5, 0.0, NOMASK, 0, 0, s));
   }
   // ---- contractions against the flattened terms
-  if (grad_coef_xz || grad_inscale_xz)
-    CHECK_RC(contract_spec(gx.ds, dE.p, n_rows, nullptr, n_rows / TILE, m_pad / TILE, dpart, dgcx.p, dgsx.p, s));
-  if (grad_coef_zz || grad_inscale_zz)
-    CHECK_RC(contract_spec(gz.ds, dGzz.p, m_pad, nullptr, m_pad / TILE, m_pad / TILE, dpart, dgcz.p, dgsz.p, s));
+  if (grad_coef_xz || grad_inscale_xz || grad_param_xz)
+    CHECK_RC(contract_spec(gx.ds, dE.p, n_rows, nullptr, n_rows / TILE, m_pad / TILE, dpart, dgcx.p, dgsx.p, s, kprod_ok,
+                           dgpx.p));
+  if (grad_coef_zz || grad_inscale_zz || grad_param_zz)
+    CHECK_RC(contract_spec(gz.ds, dGzz.p, m_pad, nullptr, m_pad / TILE, m_pad / TILE, dpart, dgcz.p, dgsz.p, s, kprod_ok,
+                           dgpz.p));
   // ---- input points: zz is symmetric (twice the row side, as in logpdf_grad_core); xz is
   // rectangular: row side for the x inputs, and the transposed contraction for the z inputs
   std::vector<DevBuf> dgz(grad_inputs_zz ? zz->n_inputs : 0), dgxz(grad_inputs_xz ? xz->n_inputs : 0);
@@ -3631,9 +3683,10 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   // mirror term; xz: the row side gives d / d rs (scales at x), the transposed pass d / d cs (scales at z)).
   const size_t ntz_s = gz.ds->h_terms.size(), ntx_s = gx.ds->h_terms.size();
   std::vector<DevBuf> drz(grad_rowscale_zz ? ntz_s : 0), drx(grad_rowscale_xz ? ntx_s : 0), dcx(grad_colscale_xz ? ntx_s : 0);
-  auto scale_buf = [&](std::vector<DevBuf>& v, double* const* want, size_t t, const double* vec, long len, double** out) -> int {
+  auto scale_buf = [&](std::vector<DevBuf>& v, double* const* want, const sgp_dspec* ds, size_t t, const double* vec, long len,
+                       double** out) -> int {
     *out = nullptr;
-    if (!want || !want[t] || !vec || len <= 0) return 0;
+    if (!want || !want[term_src_of(ds, (int)t)] || !vec || len <= 0) return 0;
     CHECK_RC(v[t].alloc((size_t)len));
     SGP_HIP(hipMemsetAsync(v[t].p, 0, sizeof(double) * len, s));
     *out = v[t].p;
@@ -3646,13 +3699,27 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
       for (int J = 0; J < ds->ncb; ++J) {
         if (ds->row_len[I] == 0 || ds->col_len[J] == 0) continue;
         int p = I * ds->ncb + J;
-        for (int t = ds->term_ptr[p]; t < ds->term_ptr[p + 1]; ++t) {
+        const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
+        for (int t = ds->term_ptr[p]; t < t1;) {
           double* gsv = nullptr;
-          CHECK_RC(scale_buf(drz, grad_rowscale_zz, t, ds->h_terms[t].rs, ds->row_len[I], &gsv));
-          if (!grad_inputs_zz && !gsv) continue;
-          CHECK_RC(launch_grad_inputs(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                      ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
-                                      grad_inputs_zz ? dgz[ds->term_row_input[t]].p : nullptr, s, gsv));
+          CHECK_RC(scale_buf(drz, grad_rowscale_zz, ds, t, ds->h_terms[t].rs, ds->row_len[I], &gsv));
+          if (t >= tk) {   // a chain: one pass for every factor's row input and the head's row scale (kprod.hip)
+            const int e = chain_end(ds, t, t1);
+            if (grad_inputs_zz || gsv) {
+              double* gxf[SGP_KPROD_MAX_FACTORS];
+              for (int f = t; f < e; ++f) gxf[f - t] = grad_inputs_zz ? dgz[ds->term_row_input[f]].p : nullptr;
+              CHECK_RC(launch_grad_kprod_inputs(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                                ds->col_len[J], &ds->h_terms[t], e - t, chain_dmax(ds, t, e), 0, 2.0, gxf, gsv,
+                                                s));
+            }
+            t = e;
+            continue;
+          }
+          if (grad_inputs_zz || gsv)
+            CHECK_RC(launch_grad_inputs(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                        ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
+                                        grad_inputs_zz ? dgz[ds->term_row_input[t]].p : nullptr, s, gsv));
+          ++t;
         }
       }
   }
@@ -3663,11 +3730,28 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
       for (int J = 0; J < ds->ncb; ++J) {
         if (ds->row_len[I] == 0 || ds->col_len[J] == 0) continue;
         int p = I * ds->ncb + J;
-        for (int t = ds->term_ptr[p]; t < ds->term_ptr[p + 1]; ++t) {
+        const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
+        for (int t = ds->term_ptr[p]; t < t1; ++t) {
           const DevTerm& T = ds->h_terms[t];
           double *gsr = nullptr, *gsc = nullptr;
-          CHECK_RC(scale_buf(drx, grad_rowscale_xz, t, T.rs, ds->row_len[I], &gsr));
-          CHECK_RC(scale_buf(dcx, grad_colscale_xz, t, T.cs, ds->col_len[J], &gsc));
+          CHECK_RC(scale_buf(drx, grad_rowscale_xz, ds, t, T.rs, ds->row_len[I], &gsr));
+          CHECK_RC(scale_buf(dcx, grad_colscale_xz, ds, t, T.cs, ds->col_len[J], &gsc));
+          if (t >= tk) {   // a chain: the row pass for x, the transposed pass for z, every factor in each (kprod.hip)
+            const int e = chain_end(ds, t, t1), cdm = chain_dmax(ds, t, e);
+            double *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
+            for (int f = t; f < e; ++f) {
+              gxr[f - t] = grad_inputs_xz ? dgxz[ds->term_row_input[f]].p : nullptr;
+              gxc[f - t] = grad_inputs_xz ? dgxz[ds->term_col_input[f]].p : nullptr;
+            }
+            if (grad_inputs_xz || gsr)
+              CHECK_RC(launch_grad_kprod_inputs(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                                ds->col_len[J], &ds->h_terms[t], e - t, cdm, 0, 1.0, gxr, gsr, s));
+            if (grad_inputs_xz || gsc)
+              CHECK_RC(launch_grad_kprod_inputs(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
+                                                ds->row_len[I], &ds->h_terms[t], e - t, cdm, 1, 1.0, gxc, gsc, s));
+            t = e - 1;
+            continue;
+          }
           if (grad_inputs_xz || gsr || gsc)
             if (grad_inputs_xz || gsr)
             CHECK_RC(launch_grad_inputs(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
@@ -3728,12 +3812,12 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
       grad_z_noise[0] = acc;
     }
   }
-  if (grad_coef_zz) SGP_HIP(hipMemcpy(grad_coef_zz, dgcz.p, sizeof(double) * gz.ds->h_terms.size(), hipMemcpyDeviceToHost));
-  if (grad_inscale_zz)
-    SGP_HIP(hipMemcpy(grad_inscale_zz, dgsz.p, sizeof(double) * gz.ds->h_terms.size(), hipMemcpyDeviceToHost));
-  if (grad_coef_xz) SGP_HIP(hipMemcpy(grad_coef_xz, dgcx.p, sizeof(double) * gx.ds->h_terms.size(), hipMemcpyDeviceToHost));
-  if (grad_inscale_xz)
-    SGP_HIP(hipMemcpy(grad_inscale_xz, dgsx.p, sizeof(double) * gx.ds->h_terms.size(), hipMemcpyDeviceToHost));
+  CHECK_RC(fetch_terms(gz.ds, grad_coef_zz, dgcz.p));
+  CHECK_RC(fetch_terms(gz.ds, grad_inscale_zz, dgsz.p));
+  CHECK_RC(fetch_terms(gz.ds, grad_param_zz, dgpz.p));
+  CHECK_RC(fetch_terms(gx.ds, grad_coef_xz, dgcx.p));
+  CHECK_RC(fetch_terms(gx.ds, grad_inscale_xz, dgsx.p));
+  CHECK_RC(fetch_terms(gx.ds, grad_param_xz, dgpx.p));
   for (size_t k = 0; k < dgz.size(); ++k)
     if (grad_inputs_zz[k] && zz->inputs[k].n > 0)
       SGP_HIP(hipMemcpy(grad_inputs_zz[k], dgz[k].p, sizeof(double) * zz->inputs[k].dim * zz->inputs[k].n,
@@ -3747,8 +3831,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
     for (int I = 0; I < ds->nrb; ++I)
       for (int J = 0; J < ds->ncb; ++J)
         for (int t = ds->term_ptr[I * ds->ncb + J]; t < ds->term_ptr[I * ds->ncb + J + 1]; ++t)
-          if (want[t] && v[t].p)
-            SGP_HIP(hipMemcpy(want[t], v[t].p, sizeof(double) * (cols ? ds->col_len[J] : ds->row_len[I]),
+          if (v[t].p)
+            SGP_HIP(hipMemcpy(want[term_src_of(ds, t)], v[t].p, sizeof(double) * (cols ? ds->col_len[J] : ds->row_len[I]),
                               hipMemcpyDeviceToHost));
     return 0;
   };
@@ -3765,8 +3849,10 @@ static int elbo_grad_entry(sgp_ctx* ctx, const sgp::ElboGradArgs& a) {
             "sgp_elbo_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(a.zz) && !spec_has_patch(a.xz),
             "sgp_elbo_grad: gradients through patch (convolutional) terms are not supported");
-  CHECK_ARG(!spec_has_kprod(a.zz) && !spec_has_kprod(a.xz),
-            "sgp_elbo_grad: gradients through product chains and the RQ / LINEAR kinds are not supported");
+  CHECK_ARG(a.kprod_ok || (!spec_has_kprod(a.zz) && !spec_has_kprod(a.xz)),
+            "sgp_elbo_grad: gradients through product chains and the RQ / LINEAR kinds are not supported: call "
+            "sgp_elbo_grad_param (include/sthenomi_kprod_grad.h)");
+  CHECK_ARG(!(a.kprod_ok && ctx->multi), "sgp_elbo_grad_param: not supported on a multi-GPU context");
   if (ctx->multi && ctx->multi_nranks > 1) return sgp_multi_elbo_grad(ctx, a);
   return sgp::drv_elbo_grad(ctx, a, nullptr);
 }
@@ -3815,37 +3901,57 @@ extern "C" int sgp_elbo_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_
   return elbo_grad_entry(ctx, a);
 }
 #undef SGP_ELBO_GRAD_ARGS
+// include/sthenomi_kprod_grad.h: sgp_elbo_grad_param (its C entry point, in libsthenomi_kprod_grad.so, forwards here)
+int sgp::drv_elbo_grad_param(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
 
 // sum_i w[i] d var_i / d theta over the diagonal of `spec` (the blocks (I, I) kernelmatrix_diag reads)
 static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
                           double* grad_inscale, double* const* grad_inputs, double* const* grad_rowscale = nullptr,
-                          double* const* grad_colscale = nullptr) {
-  CHECK_ARG(ctx && spec && w && grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad: NULL argument");
+                          double* const* grad_colscale = nullptr, double* grad_param = nullptr, bool kprod_ok = false) {
+  // (kprod_ok: sgp_kernelmatrix_diag_grad_param, include/sthenomi_kprod_grad.h -- every output may be NULL there)
+  CHECK_ARG(ctx && spec && w && (kprod_ok || (grad_coef && grad_inscale)), "sgp_kernelmatrix_diag_grad: NULL argument");
   CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_diag_grad: gradients through stencil terms are not supported");
   CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_diag_grad: gradients through patch (convolutional) terms are not supported");
-  CHECK_ARG(!spec_has_kprod(spec), "sgp_kernelmatrix_diag_grad: gradients through product chains and the RQ / LINEAR kinds are not supported");
+  CHECK_ARG(kprod_ok || !spec_has_kprod(spec),
+            "sgp_kernelmatrix_diag_grad: gradients through product chains and the RQ / LINEAR kinds are not supported: call "
+            "sgp_kernelmatrix_diag_grad_param (include/sthenomi_kprod_grad.h)");
+  CHECK_ARG(!(kprod_ok && ctx->multi), "sgp_kernelmatrix_diag_grad_param: not supported on a multi-GPU context");
   CtxScope scope(ctx);
   SpecGuard g;
   CHECK_RC(dspec_create(ctx, spec, &g.ds));
   const sgp_dspec* ds = g.ds;
   CHECK_ARG(ds->nrb == ds->ncb, "kernelmatrix_diag_grad: row / col block counts differ");
   size_t nt = ds->h_terms.size();
-  for (size_t t = 0; t < nt; ++t) grad_coef[t] = grad_inscale[t] = 0.0;
+  for (size_t t = 0; t < nt; ++t) {
+    if (grad_coef) grad_coef[t] = 0.0;
+    if (grad_inscale) grad_inscale[t] = 0.0;
+    if (grad_param) grad_param[t] = 0.0;
+  }
   if (ds->N == 0 || nt == 0) return 0;
-  DevBuf dw, dgc, dgs;
+  DevBuf dw, dgc, dgs, dgp;
   CHECK_RC(dw.upload(w, ds->N));
   CHECK_RC(dgc.alloc(nt));
   CHECK_RC(dgs.alloc(nt));
   hipStream_t s = ctx->stream;
   SGP_HIP(hipMemsetAsync(dgc.p, 0, sizeof(double) * nt, s));
   SGP_HIP(hipMemsetAsync(dgs.p, 0, sizeof(double) * nt, s));
+  if (grad_param) {
+    CHECK_RC(dgp.alloc(nt));
+    SGP_HIP(hipMemsetAsync(dgp.p, 0, sizeof(double) * nt, s));
+  }
+  // the plain terms of a diagonal pair: [term_ptr, diag_tk); its product chains behind them (kprod.hip)
+  auto diag_tk = [&](int p) { return ds->n_kprod ? ds->term_ptr[p + 1] - ds->pair_nkprod[p] : ds->term_ptr[p + 1]; };
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag_grad: block lengths differ");
     int p = I * ds->ncb + I;
-    int t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
+    int t0 = ds->term_ptr[p], t1 = diag_tk(p);
     if (ds->row_len[I] == 0 || t1 == t0) continue;
     CHECK_RC(launch_diag_grad(dw.p + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, t1 - t0, dgc.p + t0,
                               dgs.p + t0, s));
+    for (int t = t0; grad_param && t < t1; ++t)   // d / d param of a plain term: SGP_CONST alone, as a chain of length one
+      if (ds->h_terms[t].kind == SGP_CONST)
+        CHECK_RC(launch_diag_grad_kprod(dw.p + ds->row_off[I], ds->row_len[I], &ds->h_terms[t], 1, nullptr, nullptr,
+                                        dgp.p + t, nullptr, nullptr, nullptr, nullptr, s));
   }
   std::vector<DevBuf> dgx(grad_inputs ? spec->n_inputs : 0);
   if (grad_inputs) {
@@ -3857,42 +3963,67 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
     for (int I = 0; I < ds->nrb; ++I) {
       int p = I * ds->ncb + I;
       if (ds->row_len[I] == 0) continue;
-      for (int t = ds->term_ptr[p]; t < ds->term_ptr[p + 1]; ++t)
+      for (int t = ds->term_ptr[p]; t < diag_tk(p); ++t)
         CHECK_RC(launch_diag_grad_inputs(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t],
                                          dgx[ds->term_row_input[t]].p, dgx[ds->term_col_input[t]].p, s));
     }
   }
   std::vector<DevBuf> drs(grad_rowscale ? nt : 0), dcs(grad_colscale ? nt : 0);
+  auto scale_bufs = [&](int t, long len, double** o_r, double** o_c) -> int {
+    const DevTerm& T = ds->h_terms[t];
+    *o_r = *o_c = nullptr;
+    if (grad_rowscale && grad_rowscale[term_src_of(ds, t)] && T.rs) {
+      CHECK_RC(drs[t].alloc((size_t)len));
+      SGP_HIP(hipMemsetAsync(drs[t].p, 0, sizeof(double) * len, s));
+      *o_r = drs[t].p;
+    }
+    if (grad_colscale && grad_colscale[term_src_of(ds, t)] && T.cs) {
+      CHECK_RC(dcs[t].alloc((size_t)len));
+      SGP_HIP(hipMemsetAsync(dcs[t].p, 0, sizeof(double) * len, s));
+      *o_c = dcs[t].p;
+    }
+    return 0;
+  };
   if (grad_rowscale || grad_colscale)
     for (int I = 0; I < ds->nrb; ++I) {
       const long len = ds->row_len[I];
       if (len == 0) continue;
-      for (int t = ds->term_ptr[I * ds->ncb + I]; t < ds->term_ptr[I * ds->ncb + I + 1]; ++t) {
-        const DevTerm& T = ds->h_terms[t];
+      for (int t = ds->term_ptr[I * ds->ncb + I]; t < diag_tk(I * ds->ncb + I); ++t) {
         double *o_r = nullptr, *o_c = nullptr;
-        if (grad_rowscale && grad_rowscale[t] && T.rs) {
-          CHECK_RC(drs[t].alloc((size_t)len));
-          SGP_HIP(hipMemsetAsync(drs[t].p, 0, sizeof(double) * len, s));
-          o_r = drs[t].p;
-        }
-        if (grad_colscale && grad_colscale[t] && T.cs) {
-          CHECK_RC(dcs[t].alloc((size_t)len));
-          SGP_HIP(hipMemsetAsync(dcs[t].p, 0, sizeof(double) * len, s));
-          o_c = dcs[t].p;
-        }
+        CHECK_RC(scale_bufs(t, len, &o_r, &o_c));
         if (!o_r && !o_c) continue;
-        CHECK_RC(launch_diag_scale_grad(dw.p + ds->row_off[I], len, T, o_r, o_c, s));
+        CHECK_RC(launch_diag_scale_grad(dw.p + ds->row_off[I], len, ds->h_terms[t], o_r, o_c, s));
       }
     }
+  // product chains: every gradient of a chain in one launch
+  for (int I = 0; ds->n_kprod && I < ds->nrb; ++I) {
+    const long len = ds->row_len[I];
+    const int p = I * ds->ncb + I, t1 = ds->term_ptr[p + 1];
+    if (len == 0) continue;
+    for (int t = diag_tk(p); t < t1;) {
+      const int e = chain_end(ds, t, t1);
+      double *o_r = nullptr, *o_c = nullptr;
+      CHECK_RC(scale_bufs(t, len, &o_r, &o_c));
+      double *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
+      for (int f = t; f < e; ++f) {
+        gxr[f - t] = grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
+        gxc[f - t] = grad_inputs ? dgx[ds->term_col_input[f]].p : nullptr;
+      }
+      CHECK_RC(launch_diag_grad_kprod(dw.p + ds->row_off[I], len, &ds->h_terms[t], e - t, dgc.p + t, dgs.p + t,
+                                      grad_param ? dgp.p + t : nullptr, gxr, gxc, o_r, o_c, s));
+      t = e;
+    }
+  }
   SGP_HIP(hipStreamSynchronize(s));
-  SGP_HIP(hipMemcpy(grad_coef, dgc.p, sizeof(double) * nt, hipMemcpyDeviceToHost));
-  SGP_HIP(hipMemcpy(grad_inscale, dgs.p, sizeof(double) * nt, hipMemcpyDeviceToHost));
+  CHECK_RC(fetch_terms(ds, grad_coef, dgc.p));
+  CHECK_RC(fetch_terms(ds, grad_inscale, dgs.p));
+  CHECK_RC(fetch_terms(ds, grad_param, dgp.p));
   for (int I = 0; I < ds->nrb && (grad_rowscale || grad_colscale); ++I)
     for (int t = ds->term_ptr[I * ds->ncb + I]; t < ds->term_ptr[I * ds->ncb + I + 1]; ++t) {
-      if (grad_rowscale && grad_rowscale[t] && drs[t].p)
-        SGP_HIP(hipMemcpy(grad_rowscale[t], drs[t].p, sizeof(double) * ds->row_len[I], hipMemcpyDeviceToHost));
-      if (grad_colscale && grad_colscale[t] && dcs[t].p)
-        SGP_HIP(hipMemcpy(grad_colscale[t], dcs[t].p, sizeof(double) * ds->row_len[I], hipMemcpyDeviceToHost));
+      if (grad_rowscale && drs[t].p)
+        SGP_HIP(hipMemcpy(grad_rowscale[term_src_of(ds, t)], drs[t].p, sizeof(double) * ds->row_len[I], hipMemcpyDeviceToHost));
+      if (grad_colscale && dcs[t].p)
+        SGP_HIP(hipMemcpy(grad_colscale[term_src_of(ds, t)], dcs[t].p, sizeof(double) * ds->row_len[I], hipMemcpyDeviceToHost));
     }
   for (size_t k = 0; k < dgx.size(); ++k)
     if (grad_inputs[k] && spec->inputs[k].n > 0)
@@ -3917,6 +4048,13 @@ extern "C" int sgp_kernelmatrix_diag_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* s
                                              double* grad_coef, double* grad_inscale, double* const* grad_inputs,
                                              double* const* grad_rowscale, double* const* grad_colscale) {
   return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, grad_rowscale, grad_colscale);
+}
+
+// include/sthenomi_kprod_grad.h: sgp_kernelmatrix_diag_grad_param (its C entry point, in libsthenomi_kprod_grad.so, forwards here)
+int sgp::drv_diag_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
+                             double* grad_param, double* const* grad_inputs, double* const* grad_rowscale,
+                             double* const* grad_colscale) {
+  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, grad_rowscale, grad_colscale, grad_param, true);
 }
 
 static int sgp_sparse_posterior_create_impl(sgp_ctx* ctx, const sgp_cov_spec* zz,
@@ -4321,7 +4459,8 @@ int drv_elbo_grad(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shar
     return elbo_grad_core(ctx, a.zz, a.xz, a.var_x, a.mean_x, a.noise_kind, a.noise_x, a.z_noise_kind, a.z_noise, a.y,
                           a.elbo_out, a.grad_y, a.grad_mean, a.grad_noise, a.grad_var_x, a.grad_z_noise, a.grad_coef_zz,
                           a.grad_inscale_zz, a.grad_coef_xz, a.grad_inscale_xz, a.grad_inputs_zz, a.grad_inputs_xz,
-                          a.grad_rowscale_zz, a.grad_rowscale_xz, a.grad_colscale_xz, shard);
+                          a.grad_rowscale_zz, a.grad_rowscale_xz, a.grad_colscale_xz, shard, a.grad_param_zz, a.grad_param_xz,
+                          a.kprod_ok);
   };
   // (a rank of a sharded call cannot rerun on its own -- the reduction is collective: multi.hip reruns all of them)
   return shard ? run() : with_df_fallback(ctx, run);

@@ -147,6 +147,17 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
                       const DevTerm* d_terms, int nf, int dmax, long trf, long tcf, long trc, long tcc, double* partials,
                       double* out_coef, double* out_scale, double* out_param, hipStream_t s);
 
+// input-point gradients and the head's row-scale sums of ONE chain over one block pair (kprod.hip: grad_kprod_inputs_kernel):
+// h_terms the chain's nf factors (host copies), gx[f] the gradient of factor f's row input (NULL: not asked for), G addressed
+// as for launch_grad_inputs; transpose != 0: every factor seen from its column points (column side of a rectangular block)
+int launch_grad_kprod_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                             const DevTerm* h_terms, int nf, int dmax, int transpose, double scale, double* const* gx,
+                             double* gsv, hipStream_t s);
+// sum_i w_i d var_i / d theta of ONE chain on the diagonal (kprod.hip: diag_grad_kprod_kernel); every output may be NULL
+int launch_diag_grad_kprod(const double* w, long n, const DevTerm* h_terms, int nf, double* out_coef, double* out_scale,
+                           double* out_param, double* const* gxr, double* const* gxc, double* out_rs, double* out_cs,
+                           hipStream_t s);
+
 void set_error(const std::string& s);
 
 #define SGP_HIP(expr)                                                                     \

@@ -65,6 +65,9 @@ struct ElboGradArgs {
   double* const* grad_rowscale_zz = nullptr;
   double* const* grad_rowscale_xz = nullptr;
   double* const* grad_colscale_xz = nullptr;
+  // sgp_elbo_grad_param (include/sthenomi_kprod_grad.h): d / d param per term, and the leave to carry product chains
+  double *grad_param_zz = nullptr, *grad_param_xz = nullptr;
+  bool kprod_ok = false;
 };
 struct ElboGradShard {
   bool primary = false;   // the rank that also produces the zz-side results (G_zz and its contractions)

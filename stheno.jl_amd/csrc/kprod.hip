@@ -499,4 +499,365 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
   return 0;
 }
 
+
+// ---- input-point and scale gradients of ONE chain ---------------------------------------------------------------------
+// k and d k / d x of one factor from its row point and a column point: a distance kind has d k / d x = 2 kx (x - x') with
+// kx = kappa'(d2) (kern_grad.h: kern_val_dd2; RQ: -1/2 (1 + u)^(-alpha - 1) = -1/2 exp(-(alpha + 1) log1p(u)), an exact 0 --
+// never NaN -- where d2 overflowed, finite where only u did: rq_log1p_u), LINEAR has d k / d x = x' and kx stands for nothing
+template <int DMAX>
+__device__ __forceinline__ void kp_factor_dx(int kind, double param, const double* xr, const double* sp, double& k,
+                                             double& kx) {
+  if (kind == K_LINEAR) {
+    double s = 0.0;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) s = fma(xr[d], sp[d], s);
+    k = s + param;
+    kx = 0.0;
+    return;
+  }
+  double d2 = 0.0;
+#pragma unroll
+  for (int d = 0; d < DMAX; ++d) {
+    const double df = xr[d] - sp[d];
+    d2 = fma(df, df, d2);
+  }
+  if (kind == K_RQ) {
+    double u;
+    const double l = rq_log1p_u(d2, param, u);
+    k = exp(-param * l);
+    kx = -0.5 * exp(-(param + 1.0) * l);
+    return;
+  }
+  kern_val_dd2(kind, d2, param, k, kx);
+}
+
+// Row side of one chain over one block pair, grad_inputs_kernel's tiling (grad.hip): a workgroup owns 128 rows and walks the
+// column tiles, thread = one row x one half of a tile's columns, the column points of every factor in LDS, the row points and
+// one accumulator per (factor, coordinate) in registers.  Per entry every factor is evaluated once (k and kx), the products
+// with one factor left out come from prefix and suffix products (no division), and factor f adds
+//     W_ij E^f_ij 2 kx_f (x^f_i - x'^f_j)   (distance kinds)       W_ij E^f_ij x'^f_j   (LINEAR)
+// into its own accumulators.  The two column halves are combined in a fixed order through LDS (the column points' storage,
+// no longer needed) and the owner adds into the gradient of each factor's row input, in factor order: no atomics.
+// G as in grad_inputs_kernel: Gm[(r0 + i) * sr + (c0 + j) * sc], alpha != NULL: G = (alpha alpha' - Gm) / 2.
+struct KpChainArgs {
+  DevTerm t[KP_MAXF];
+  double* gx[KP_MAXF];   // gradient of factor f's row input (dim x nr, packed) or NULL
+};
+
+template <int DMAX>
+__global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm, long sr, long sc, const double* alpha,
+                                                                long r0, long nr, long c0, long nc, KpChainArgs C, int nf,
+                                                                double scale, double* gsv /* nr, or NULL */) {
+  constexpr int TMAX = (64 / DMAX < KP_MAXF) ? 64 / DMAX : KP_MAXF;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double* sx = smem;                         // [TMAX][128][DMAX] column points; afterwards [TMAX * DMAX][128] half sums
+  double* scs = smem + TMAX * TILE * DMAX;   // [128] column scale of the head; afterwards the half sums of gsv
+  const int t = threadIdx.x;
+  const int trow = t & 127, th = t >> 7;
+  const long lrow = (long)blockIdx.x * TILE + trow;
+  const bool live = lrow < nr;
+  const long grow = r0 + lrow;
+  double xr[TMAX * DMAX], acc[TMAX * DMAX], param[TMAX];
+  int kind[TMAX];
+#pragma unroll
+  for (int f = 0; f < TMAX; ++f) {
+    kind[f] = G_CONST;
+    param[f] = 1.0;
+    const bool on = live && f < nf;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) {
+      xr[f * DMAX + d] = (on && d < C.t[f].dim) ? C.t[f].xr[lrow * C.t[f].ldr + d] : 0.0;
+      acc[f * DMAX + d] = 0.0;
+    }
+    if (f < nf) {
+      kind[f] = C.t[f].kind & KP_KIND_MASK;
+      param[f] = C.t[f].param;
+    }
+  }
+  double accs = 0.0;
+  const double coef = C.t[0].coef;
+  const double ai = (alpha && live) ? alpha[grow] : 0.0;
+  const double wrow = live ? coef * (C.t[0].rs ? C.t[0].rs[lrow] : 1.0) : 0.0;
+  for (long ct = 0; ct * TILE < nc; ++ct) {
+    __syncthreads();
+#pragma unroll
+    for (int f = 0; f < TMAX; ++f) {
+      if (f >= nf) break;
+      for (int idx = t; idx < TILE * DMAX; idx += 256) {
+        const int p = idx / DMAX, d = idx % DMAX;
+        const long lc = ct * TILE + p;
+        sx[f * TILE * DMAX + idx] = (lc < nc && d < C.t[f].dim) ? C.t[f].xc[lc * C.t[f].ldc + d] : 0.0;
+      }
+    }
+    if (t < TILE) {
+      const long lc = ct * TILE + t;
+      scs[t] = (lc < nc) ? (C.t[0].cs ? C.t[0].cs[lc] : 1.0) : 0.0;
+    }
+    __syncthreads();
+    if (live) {
+      for (int p = th * 64; p < th * 64 + 64; ++p) {
+        const long lc = ct * TILE + p;
+        if (lc >= nc) break;
+        const long gc = c0 + lc;
+        const double gm = Gm[grow * sr + gc * sc];
+        const double g = alpha ? 0.5 * (ai * alpha[gc] - gm) : gm;
+        double k[TMAX], kx[TMAX], pre[TMAX + 1];
+        pre[0] = 1.0;
+#pragma unroll
+        for (int f = 0; f < TMAX; ++f) {
+          k[f] = 1.0;
+          kx[f] = 0.0;
+          if (f < nf) kp_factor_dx<DMAX>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], kx[f]);
+          pre[f + 1] = pre[f] * k[f];
+        }
+        const double gcs = g * scs[p];
+        accs = fma(gcs * coef, pre[TMAX], accs);
+        const double w = gcs * wrow;
+        double suf = 1.0;   // the product of the factors behind f
+#pragma unroll
+        for (int f = TMAX - 1; f >= 0; --f) {
+          if (f < nf) {
+            const double excl = w * (pre[f] * suf);
+            const double* sp = &sx[(f * TILE + p) * DMAX];
+            if (kind[f] == K_LINEAR) {
+#pragma unroll
+              for (int d = 0; d < DMAX; ++d) acc[f * DMAX + d] = fma(excl, sp[d], acc[f * DMAX + d]);
+            } else {
+              const double c2 = 2.0 * excl * kx[f];
+#pragma unroll
+              for (int d = 0; d < DMAX; ++d) acc[f * DMAX + d] = fma(c2, xr[f * DMAX + d] - sp[d], acc[f * DMAX + d]);
+            }
+          }
+          suf = suf * k[f];
+        }
+      }
+    }
+  }
+  // combine the two column halves in fixed order, then add into the inputs' gradients
+  __syncthreads();
+  if (th == 1) {
+#pragma unroll
+    for (int q = 0; q < TMAX * DMAX; ++q) sx[q * TILE + trow] = acc[q];
+    scs[trow] = accs;
+  }
+  __syncthreads();
+  if (th == 0 && live) {
+#pragma unroll
+    for (int f = 0; f < TMAX; ++f) {
+      if (f >= nf || !C.gx[f]) continue;
+      const int dim = C.t[f].dim;
+      double* o = C.gx[f] + lrow * dim;
+#pragma unroll
+      for (int d = 0; d < DMAX; ++d)
+        if (d < dim) o[d] += scale * (acc[f * DMAX + d] + sx[(f * DMAX + d) * TILE + trow]);
+    }
+    if (gsv) gsv[lrow] += scale * (accs + scs[trow]);
+  }
+}
+
+template <int DMAX>
+static int launch_grad_kprod_inputs_t(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0,
+                                      long nc, const KpChainArgs& C, int nf, double scale, double* gsv, hipStream_t s) {
+  constexpr int TMAX = (64 / DMAX < KP_MAXF) ? 64 / DMAX : KP_MAXF;
+  if (nf > TMAX) {
+    set_error("grad: a product chain beyond factors x dimension <= 64");
+    return -1;
+  }
+  const size_t lds = (size_t)(TMAX * TILE * DMAX + TILE) * sizeof(double);
+  SGP_LDS_ATTR_ONCE(grad_kprod_inputs_kernel<DMAX>, lds);
+  hipLaunchKernelGGL(grad_kprod_inputs_kernel<DMAX>, dim3((unsigned)((nr + TILE - 1) / TILE)), dim3(256), lds, s, Gm, sr, sc,
+                     alpha, r0, nr, c0, nc, C, nf, scale, gsv);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+// h_terms: the chain's nf factors (host copies); gx[f]: where factor f's row-input gradient goes (NULL: not asked for);
+// gsv: the head's row-scale sums (NULL: not asked for).  transpose != 0: every factor is seen from its column points (the
+// caller passes (sr, sc), the offsets and lengths of the transposed block itself, as for launch_grad_inputs)
+int launch_grad_kprod_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                             const DevTerm* h_terms, int nf, int dmax, int transpose, double scale, double* const* gx,
+                             double* gsv, hipStream_t s) {
+  if (nf <= 0 || nr <= 0 || nc <= 0) return 0;
+  if (nf > KP_MAXF || dmax > 16) {
+    set_error("grad: a product chain beyond the limits of include/sthenomi_kprod.h");
+    return -1;
+  }
+  KpChainArgs C;
+  for (int f = 0; f < KP_MAXF; ++f) {
+    C.t[f] = h_terms[f < nf ? f : 0];
+    C.gx[f] = (f < nf && gx) ? gx[f] : nullptr;
+    if (transpose) {
+      std::swap(C.t[f].xr, C.t[f].xc);
+      std::swap(C.t[f].ldr, C.t[f].ldc);
+      std::swap(C.t[f].rs, C.t[f].cs);
+    }
+  }
+  int rc;
+#define SGP_KI(DM) rc = launch_grad_kprod_inputs_t<DM>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)
+  if (dmax <= 1) SGP_KI(1);
+  else if (dmax <= 2) SGP_KI(2);
+  else if (dmax <= 4) SGP_KI(4);
+  else if (dmax <= 8) SGP_KI(8);
+  else SGP_KI(16);
+#undef SGP_KI
+  return rc;
+}
+
+// ---- the diagonal of ONE chain: sum_i w_i d var_i / d theta, var_i = coef rs_i cs_i prod_f k_f(xr^f_i, xc^f_i) -----------
+// One workgroup, every point handled by exactly one thread: the per-point outputs (row / column scale, input points) are
+// added by that thread, the sums over points (d / d coef of the head, d / d inscale and d / d param of every factor) are
+// reduced in a fixed order.  Inputs: a distance kind gives the row input + and the column input - 2 kx (xr - xc) (they cancel
+// when both are one array, which is skipped); LINEAR gives the row input xc and the column input xr, both added when they are
+// one array.
+struct KpDiagArgs {
+  DevTerm t[KP_MAXF];
+  double* gxr[KP_MAXF];
+  double* gxc[KP_MAXF];
+};
+
+__global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, long n, KpDiagArgs C, int nf, double* out_coef,
+                                                              double* out_scale, double* out_param, double* out_rs,
+                                                              double* out_cs) {
+  __shared__ double sh[256];
+  double g_coef = 0.0, gs_acc[KP_MAXF], gp_acc[KP_MAXF];
+#pragma unroll
+  for (int f = 0; f < KP_MAXF; ++f) gs_acc[f] = gp_acc[f] = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    double k[KP_MAXF], dk[KP_MAXF], dp[KP_MAXF], kx[KP_MAXF], pre[KP_MAXF + 1];
+    pre[0] = 1.0;
+#pragma unroll
+    for (int f = 0; f < KP_MAXF; ++f) {
+      k[f] = 1.0;
+      dk[f] = dp[f] = kx[f] = 0.0;
+      if (f < nf) {
+        const DevTerm& T = C.t[f];
+        const int kind = T.kind & KP_KIND_MASK;
+        const double* a = T.xr + i * T.ldr;
+        const double* b = T.xc + i * T.ldc;
+        if (kind == K_LINEAR) {
+          double s = 0.0;
+          for (int d = 0; d < T.dim; ++d) s = fma(a[d], b[d], s);
+          k[f] = s + T.param;
+          dk[f] = 2.0 * s;
+          dp[f] = 1.0;
+        } else {
+          double d2 = 0.0;
+          for (int d = 0; d < T.dim; ++d) {
+            const double df = a[d] - b[d];
+            d2 = fma(df, df, d2);
+          }
+          if (kind == K_RQ) {
+            double u;
+            const double l = rq_log1p_u(d2, T.param, u);
+            k[f] = exp(-T.param * l);
+            const double r = u < 1e300 ? u / (1.0 + u) : 1.0;
+            dk[f] = -(2.0 * T.param) * r * k[f];
+            dp[f] = k[f] == 0.0 ? 0.0 : k[f] * (r - l);
+            kx[f] = -0.5 * exp(-(T.param + 1.0) * l);
+          } else {
+            double kk;
+            kern_and_dscale(kind, d2, T.param, k[f], dk[f]);
+            kern_val_dd2(kind, d2, T.param, kk, kx[f]);
+            dp[f] = kind == G_CONST ? 1.0 : 0.0;
+          }
+        }
+      }
+      pre[f + 1] = pre[f] * k[f];
+    }
+    const DevTerm& H = C.t[0];
+    const double rsv = H.rs ? H.rs[i] : 1.0, csv = H.cs ? H.cs[i] : 1.0;
+    const double wi = w[i];
+    g_coef = fma(wi * rsv * csv, pre[KP_MAXF], g_coef);
+    if (out_rs) out_rs[i] += wi * H.coef * csv * pre[KP_MAXF];
+    if (out_cs) out_cs[i] += wi * H.coef * rsv * pre[KP_MAXF];
+    const double wc = wi * rsv * csv * H.coef;
+    double suf = 1.0;
+    double excl[KP_MAXF];
+#pragma unroll
+    for (int f = KP_MAXF - 1; f >= 0; --f) {
+      excl[f] = wc * (pre[f] * suf);
+      if (f < nf) {
+        gs_acc[f] = fma(excl[f], dk[f], gs_acc[f]);
+        gp_acc[f] = fma(excl[f], dp[f], gp_acc[f]);
+      }
+      suf = suf * k[f];
+    }
+#pragma unroll
+    for (int f = 0; f < KP_MAXF; ++f) {   // factor order: several factors may add into one array
+      if (f >= nf || !C.gxr[f]) continue;
+      const DevTerm& T = C.t[f];
+      const double* a = T.xr + i * T.ldr;
+      const double* b = T.xc + i * T.ldc;
+      double* orow = C.gxr[f] + i * T.dim;
+      double* ocol = C.gxc[f] + i * T.dim;
+      if ((T.kind & KP_KIND_MASK) == K_LINEAR) {
+        for (int d = 0; d < T.dim; ++d) {
+          const double av = a[d], bv = b[d];
+          orow[d] += excl[f] * bv;
+          ocol[d] += excl[f] * av;
+        }
+      } else if (ocol != orow) {
+        const double c2 = 2.0 * excl[f] * kx[f];
+        for (int d = 0; d < T.dim; ++d) {
+          const double df = a[d] - b[d];
+          orow[d] += c2 * df;
+          ocol[d] -= c2 * df;
+        }
+      }
+    }
+  }
+  // fixed-order tree per output
+  for (int q = 0; q < 1 + 2 * KP_MAXF; ++q) {
+    double v = 0.0;
+    if (q == 0) v = g_coef;
+#pragma unroll
+    for (int f = 0; f < KP_MAXF; ++f) {
+      if (q == 1 + f) v = gs_acc[f];
+      if (q == 1 + KP_MAXF + f) v = gp_acc[f];
+    }
+    __syncthreads();
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+      if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      if (q == 0) {
+        if (out_coef) {
+          out_coef[0] = sh[0];
+          for (int f = 1; f < nf; ++f) out_coef[f] = 0.0;
+        }
+      } else if (q <= KP_MAXF) {
+        if (out_scale && q - 1 < nf) out_scale[q - 1] = sh[0];
+      } else if (out_param && q - 1 - KP_MAXF < nf) {
+        out_param[q - 1 - KP_MAXF] = sh[0];
+      }
+    }
+  }
+}
+
+// out_coef / out_scale / out_param: the chain's first entry (nf each, device; any may be NULL); gxr / gxc: per factor, the
+// gradient arrays of its row / column input at the block's first point (both or neither; NULL arrays: not asked for);
+// out_rs / out_cs: the head's row / column scale sums (NULL: not asked for)
+int launch_diag_grad_kprod(const double* w, long n, const DevTerm* h_terms, int nf, double* out_coef, double* out_scale,
+                           double* out_param, double* const* gxr, double* const* gxc, double* out_rs, double* out_cs,
+                           hipStream_t s) {
+  if (nf <= 0 || n <= 0) return 0;
+  if (nf > KP_MAXF) {
+    set_error("grad: a product chain beyond the limits of include/sthenomi_kprod.h");
+    return -1;
+  }
+  KpDiagArgs C;
+  for (int f = 0; f < KP_MAXF; ++f) {
+    C.t[f] = h_terms[f < nf ? f : 0];
+    C.gxr[f] = (f < nf && gxr) ? gxr[f] : nullptr;
+    C.gxc[f] = (f < nf && gxc) ? gxc[f] : nullptr;
+  }
+  hipLaunchKernelGGL(diag_grad_kprod_kernel, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param, out_rs,
+                     out_cs);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace sgp

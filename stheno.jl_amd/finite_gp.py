@@ -50,7 +50,8 @@ def _refuse_product_gradient(what, *specs):
     """`what` through product chains / the RQ and LINEAR kinds is not implemented (the library refuses it too)"""
     if any(sp.has_kprod for sp in specs):
         raise NotImplementedError(f"{what} through a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel, "
-                                  "which runs on the product path) is not supported: logpdf_and_gradient(fx, y) is")
+                                  "which runs on the product path) is not supported: logpdf_and_gradient(fx, y) is, and "
+                                  "logpdf_and_gradient_param / elbo_and_gradient_param carry inputs, scales and the ELBO")
 
 
 def _is_prior(f):
@@ -478,8 +479,8 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
     sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
     index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
-    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, c of Linear / Constant).  inputs / scales are not
-    implemented for such models."""
+    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, c of Linear / Constant).  inputs / scales of such
+    models come from logpdf_and_gradient_param."""
     if not _is_prior(fx.f):
         raise NotImplementedError("gradients are implemented for prior Stheno processes")
     n = len(fx)
@@ -539,6 +540,46 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     # the first of them)
     xb = chain_input_gradients(spec, gx)[0] if inputs else None
     return _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs)
+
+
+def _refuse_param_family(what, *specs):
+    """what the superset family of include/sthenomi_kprod_grad.h does not carry: patch / stencil sides, a multi-GPU context"""
+    _refuse_patch_gradient(*specs)
+    if getattr(_ctx(), "is_multi", False):
+        raise NotImplementedError(f"{what}: a product of kernels (the gradients of include/sthenomi_kprod_grad.h) is not "
+                                  "supported on a multi-GPU context")
+
+
+def logpdf_and_gradient_param(fx, y, inputs=False, scales=False):
+    """logpdf_and_gradient for every model it takes AND for models with a product of kernels (or a RationalQuadratic /
+    Linear / Polynomial / Periodic kernel), through sgp_logpdf_grad_param_xs (include/sthenomi_kprod_grad.h): the same dict,
+    with every term record in the chain form -- `chain`, `factor`, `d_param` (see logpdf_and_gradient) -- and inputs=True /
+    scales=True carried through the factors of a product: `inputs` holds d logpdf / d (the view each factor reads), `x` the
+    same mapped back onto the blocks of fx.x through every factor's own transform (with_lengthscale, the periodic embedding)
+    and the model's warps, `scales` one record per function-valued scale.  Single-GPU contexts; no patch / stencil terms."""
+    if not _is_prior(fx.f):
+        raise NotImplementedError("gradients are implemented for prior Stheno processes")
+    n = len(fx)
+    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+    spec = _prior_spec(fx.f, fx.x)
+    _refuse_param_family("logpdf_and_gradient_param", spec)
+    m = _f64(mean_vector(fx.f, fx.x))
+    kind, nbuf = _lib._noise_args(fx.noise, n)
+    lp = np.zeros(1)
+    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
+    gp = np.zeros(max(1, spec.n_terms))
+    gx = ptrs = grs = sptrs = None
+    if inputs:
+        gx = [np.zeros(np.asarray(a).shape, order="F") for a in spec.inputs]
+        ptrs = (C.POINTER(C.c_double) * max(1, len(gx)))(*[_lib.dptr(a) for a in gx])
+    if scales:
+        grs, sptrs = _scale_arrays(spec, "row")
+    rc = _ctx().kprod_grad.sgp_logpdf_grad_param_xs(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
+                                                    _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
+                                                    _lib.dptr(gc), _lib.dptr(gs), _lib.dptr(gp), ptrs, sptrs)
+    _lib.check(rc, "sgp_logpdf_grad_param_xs")
+    xb = chain_input_gradients(spec, gx)[0] if inputs else None
+    return _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs, gp=gp)
 
 
 def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
@@ -987,13 +1028,14 @@ def _chain_keys(spec):
     return keys
 
 
-def _term_records_kprod(spec, gc, gs, gp):
-    """_term_records for a symmetric spec with product chains: one record per factor"""
+def _term_records_kprod(spec, gc, gs, gp, symmetric=True):
+    """_term_records in the chain form (a spec with product chains, or any spec of the *_param functions): one record per
+    factor.  symmetric=False: every pair keeps its own records (K(x, z) of the ELBO, the diagonal)."""
     nrb, ncb = len(spec.row_len), len(spec.col_len)
     tp, out, index, rec_of = spec._term_ptr, [], {}, {}
     sid, keys = spec.term_scale_ids, _chain_keys(spec)
     for I in range(nrb):
-        for J in range(min(I + 1, ncb)):
+        for J in range(min(I + 1, ncb) if symmetric else ncb):
             for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
                 T = spec._terms[t]
                 sig, pos, head = keys[t]
@@ -1002,7 +1044,7 @@ def _term_records_kprod(spec, gc, gs, gp):
                                 row_input=T.row_input, col_input=T.col_input, row_scaled=sid[head][0] is not None,
                                 col_scaled=sid[head][1] is not None, t=t, mirror_t=None, chain=rec_of[head], factor=pos,
                                 d_coef=float(gc[t]), d_inscale=float(gs[t]), d_param=float(gp[t])))
-    for I in range(nrb):
+    for I in range(nrb if symmetric else 0):
         for J in range(I + 1, ncb):
             for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
                 sig, pos, head = keys[t]
@@ -1144,6 +1186,67 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
                 scales=(_scale_records(zz, srz, more=((xz, srx, "row"), (xz, scx, "col"), (xx, sdr, "row"), (xx, sdc, "col")))
                         if scales else None),
                 _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
+                _specs=dict(zz=zz, xz=xz, xx=xx))
+
+
+def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):
+    """elbo_and_gradient for every model it takes AND for models with a product of kernels, through sgp_elbo_grad_param and
+    sgp_kernelmatrix_diag_grad_param (include/sthenomi_kprod_grad.h): the same dict, with zz_terms / xz_terms / xx_terms in
+    the chain form (`chain`, `factor`, `d_param`; see logpdf_and_gradient) and `_raw` carrying the d / d param arrays.
+    Single-GPU contexts; no patch / stencil terms."""
+    if isinstance(vfe, SparseFiniteGP):
+        return elbo_and_gradient_param(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, scales=scales)
+    zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
+    n, m = len(fx), len(vfe.fz)
+    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+    xx = _prior_spec(fx.f, fx.x)
+    _refuse_param_family("elbo_and_gradient_param", zz, xz, xx)
+    var_x = _f64(_kernelmatrix_diag(xx))
+    out = np.zeros(1)
+    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
+    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
+    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
+    gcz, gsz, gpz = (np.zeros(max(1, zz.n_terms)) for _ in range(3))
+    gcx, gsx, gpx = (np.zeros(max(1, xz.n_terms)) for _ in range(3))
+    gcd, gsd, gpd = (np.zeros(max(1, xx.n_terms)) for _ in range(3))
+    lib = _ctx().kprod_grad
+    gxz = gxx = gdx = pz = px = pd = None
+    if inputs:
+        gxz = [np.zeros(a.shape, order="F") for a in zz.inputs]
+        gxx = [np.zeros(a.shape, order="F") for a in xz.inputs]
+        gdx = [np.zeros(a.shape, order="F") for a in xx.inputs]     # var(f, x) depends on x where a factor reads two views
+        pz = (C.POINTER(C.c_double) * max(1, len(gxz)))(*[_lib.dptr(a) for a in gxz])
+        px = (C.POINTER(C.c_double) * max(1, len(gxx)))(*[_lib.dptr(a) for a in gxx])
+        pd = (C.POINTER(C.c_double) * max(1, len(gdx)))(*[_lib.dptr(a) for a in gdx])
+    srz = srx = scx = sdr = sdc = prz = prx = pcx = pdr = pdc = None
+    if scales:
+        srz, prz = _scale_arrays(zz, "row")
+        srx, prx = _scale_arrays(xz, "row")
+        scx, pcx = _scale_arrays(xz, "col")
+        sdr, pdr = _scale_arrays(xx, "row")
+        sdc, pdc = _scale_arrays(xx, "col")
+    d = _lib.dptr
+    rc = lib.sgp_elbo_grad_param(_ctx().handle, zz.ref(), xz.ref(), d(var_x), d(mean_x), nk, d(nbuf), zk, d(zbuf), d(yv),
+                                 d(out), d(gy), d(gm), d(gn), d(gv), d(gzn), d(gcz), d(gsz), d(gpz), d(gcx), d(gsx), d(gpx),
+                                 pz, px, prz, prx, pcx)
+    _lib.check(rc, "sgp_elbo_grad_param")
+    rc = lib.sgp_kernelmatrix_diag_grad_param(_ctx().handle, xx.ref(), d(gv), d(gcd), d(gsd), d(gpd), pd, pdr, pdc)
+    _lib.check(rc, "sgp_kernelmatrix_diag_grad_param")
+    nb = len(xx.row_len)
+    xx_terms = [r for r in _term_records_kprod(xx, gcd, gsd, gpd, False) if r["I"] == r["J"]] if nb else []
+    xb = zb = None
+    if inputs:   # chain rule back onto the blocks of fx.x and fz.x, through every factor's own view
+        zr, _ = chain_input_gradients(zz, gxz)
+        xr, zc = chain_input_gradients(xz, gxx)
+        xd, _ = chain_input_gradients(xx, gdx)
+        xb, zb = [a + b for a, b in zip(xr, xd)], [a + b for a, b in zip(zr, zc)]
+    return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
+                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
+                zz_terms=_term_records_kprod(zz, gcz, gsz, gpz, True), xz_terms=_term_records_kprod(xz, gcx, gsx, gpx, False),
+                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx,
+                scales=(_scale_records(zz, srz, more=((xz, srx, "row"), (xz, scx, "col"), (xx, sdr, "row"), (xx, sdc, "col")))
+                        if scales else None),
+                _raw=dict(zz=(gcz, gsz, gpz), xz=(gcx, gsx, gpx), xx=(gcd, gsd, gpd)),
                 _specs=dict(zz=zz, xz=xz, xx=xx))
 
 

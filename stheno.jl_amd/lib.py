@@ -23,6 +23,7 @@ POSTFX_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_postfx.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
 KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
+KPROD_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod_grad.so")
 
 # kernel kinds / noise kinds (sthenomi.h enums)
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
@@ -263,6 +264,24 @@ _SIGS_KPROD = {
 }
 
 
+# include/sthenomi_kprod_grad.h: the supersets of sgp_logpdf_grad_xs / sgp_kernelmatrix_diag_grad_xs / sgp_elbo_grad_xs that carry
+# product chains and return d / d param, exported by libsthenomi_kprod_grad.so -- logpdf_and_gradient_param and
+# elbo_and_gradient_param reach them through kprod_grad_lib() / Context.kprod_grad
+_SPEC = C.POINTER(sgp_cov_spec)
+_DD = C.POINTER(_D)
+_SIGS_KPROD_GRAD = {
+    "sgp_logpdf_grad_param_xs": (C.c_int, [_P, _SPEC, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _D, _DD, _DD]),
+    "sgp_kernelmatrix_diag_grad_param": (C.c_int, [_P, _SPEC, _D, _D, _D, _D, _DD, _DD, _DD]),
+    "sgp_elbo_grad_param": (C.c_int, [_P, _SPEC, _SPEC, _D, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D,
+                                      _D, _D, _D, _D, _D, _D, _DD, _DD, _DD, _DD, _DD]),
+}
+
+
+def kprod_grad_symbols():
+    """Names include/sthenomi_kprod_grad.h declares: the entry points of libsthenomi_kprod_grad.so."""
+    return sorted(_SIGS_KPROD_GRAD)
+
+
 def kprod_symbols():
     """Names include/sthenomi_kprod.h declares: the entry points of libsthenomi_kprod.so."""
     return sorted(_SIGS_KPROD)
@@ -498,6 +517,27 @@ def kprod_lib():
         return lib
 
 
+_kprod_grad = None
+
+
+def kprod_grad_lib():
+    """dlopen libsthenomi_kprod_grad.so (include/sthenomi_kprod_grad.h) after the product library it links against."""
+    global _kprod_grad
+    load()
+    with _lib_lock:
+        if _kprod_grad is not None:
+            return _kprod_grad
+        if not os.path.exists(KPROD_GRAD_LIB_PATH):
+            raise SthenoMIError(f"{KPROD_GRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(KPROD_GRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_KPROD_GRAD.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _kprod_grad = lib
+        return lib
+
+
 def load():
     """dlopen libsthenomi.so (after torch, so both share one HIP runtime) and type its symbols."""
     global _lib
@@ -582,6 +622,11 @@ class Context:
     def kprod(self):
         """libsthenomi_kprod.so (sthenomi_kprod.h): `ctx.kprod.sgp_logpdf_grad_param(ctx.handle, ...)`"""
         return kprod_lib()
+
+    @property
+    def kprod_grad(self):
+        """libsthenomi_kprod_grad.so (sthenomi_kprod_grad.h): `ctx.kprod_grad.sgp_elbo_grad_param(ctx.handle, ...)`"""
+        return kprod_grad_lib()
 
     @property
     def extend(self):
