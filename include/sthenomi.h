@@ -47,7 +47,10 @@ enum {
   SGP_CONST = 5,    /* ConstantKernel(c): param                                          */
   /* the kinds below are evaluated by the product-chain path only (include/sthenomi_kprod.h) */
   SGP_RQ = 6,       /* RationalQuadraticKernel(alpha): (1 + d^2 / (2 alpha))^-alpha, param = alpha > 0 */
-  SGP_LINEAR = 7    /* LinearKernel(c): x'y + c, param = c >= 0                          */
+  SGP_LINEAR = 7,   /* LinearKernel(c): x'y + c, param = c >= 0                          */
+  /* 8 .. 15 are no kinds: a spec that names one is refused ("unknown kernel kind") */
+  SGP_COSINE = 16,  /* CosineKernel: cos(pi d), param ignored                            */
+  SGP_GAMMAEXP = 17 /* GammaExponentialKernel(gamma): exp(-d^gamma), param = gamma in (0, 2] */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -78,7 +81,7 @@ typedef struct {
                          Stencil terms: the same encoding, ids of the same table registered by
                          sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
-  double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c                      */
+  double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

@@ -93,6 +93,9 @@ leaf(::Matern32Kernel) = [(2, 1.0, 0.0, Chain())]
 leaf(::Matern52Kernel) = [(3, 1.0, 0.0, Chain())]
 leaf(::WhiteKernel) = [(4, 1.0, 0.0, Chain())]
 leaf(k::ConstantKernel) = [(5, 1.0, only(k.c), Chain())]
+# kinds of the product path (include/sthenomi_kprod.h): a term of its own is a chain of length one
+leaf(::CosineKernel) = [(16, 1.0, 0.0, Chain())]
+leaf(k::GammaExponentialKernel) = [(17, 1.0, Float64(only(k.γ)), Chain())]
 leaf(k::ScaledKernel) = [(a, c * only(k.σ²), p, ch) for (a, c, p, ch) in leaf(k.kernel)]
 leaf(k::KernelSum) = reduce(vcat, leaf.(k.kernels))
 # k o t evaluates k(t(x), t(y)): t is applied to the raw points first, the inner kernel's own chain after it

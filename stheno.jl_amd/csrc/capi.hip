@@ -308,6 +308,9 @@ extern "C" int sgp_ctx_destroy(sgp_ctx* c) {
 // ---------------------------------------------------------------------------------------
 // device-resident specs
 // ---------------------------------------------------------------------------------------
+// the kinds of include/sthenomi.h: 0 .. 7, and 16 / 17 (8 .. 15 and everything above stay unknown)
+static bool kind_known(int k) { return (k >= SGP_SE && k <= SGP_LINEAR) || k == SGP_COSINE || k == SGP_GAMMAEXP; }
+
 static int pow2ceil(int d) {
   int p = 1;
   while (p < d) p <<= 1;
@@ -369,7 +372,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   const int nterms = sp->term_ptr[npairs];
   std::vector<size_t> rs_off(nterms, (size_t)-1), cs_off(nterms, (size_t)-1);
   std::vector<long> rs_len(nterms, 0), cs_len(nterms, 0);
-  // product chains and terms of the RQ / LINEAR kinds (include/sthenomi_kprod.h): a class of their own (kprod.hip)
+  // product chains and terms of the RQ / LINEAR / COSINE / GAMMAEXP kinds (include/sthenomi_kprod.h): a class of their own
+  // (kprod.hip)
   std::vector<char> is_kp(std::max(1, nterms), 0);
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
@@ -377,7 +381,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
       int chain_len = 0, chain_dmax = 1;
       for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t) {
         const sgp_term& T = sp->terms[t];
-        if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) || (T.kind & 0xff) > SGP_LINEAR)
+        if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) || !kind_known(T.kind & 0xff))
           return fail("spec: unknown kernel kind");
         const bool cont = (T.kind & SGP_KIND_TIMES_PREV) != 0;
         const bool next_cont = t + 1 < sp->term_ptr[p + 1] && sp->terms[t + 1].kind >= 0 &&
@@ -393,6 +397,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
             return fail("spec: product chain: a continuation must have coef == 1.0 and NULL scales (the head carries them)");
           if ((T.kind & 0xff) == SGP_RQ && !(T.param > 0.0 && T.param < 1e300))
             return fail("spec: SGP_RQ (product path): param = alpha must be > 0 and finite");
+          if ((T.kind & 0xff) == SGP_GAMMAEXP && !(T.param > 0.0 && T.param <= 2.0))
+            return fail("spec: SGP_GAMMAEXP (product path): param = gamma must be in (0, 2]");
           if ((T.kind & 0xff) == SGP_LINEAR && !(T.param >= 0.0 && T.param < 1e300))
             return fail("spec: SGP_LINEAR (product path): param = c must be >= 0 and finite");
           if (T.row_input >= 0 && T.row_input < sp->n_inputs) {

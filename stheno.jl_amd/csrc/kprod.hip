@@ -1,5 +1,5 @@
 // Product chains (include/sthenomi_kprod.h): covariance terms that multiply several leaf kernels, each on its own view of
-// the points, and the kinds that exist only here, RationalQuadratic and Linear.
+// the points, and the kinds that exist only here: RationalQuadratic, Linear, Cosine and GammaExponential.
 //     chain value (i, j) = coef_head rs_i cs_j  prod_f k_f(x^f_i, x'^f_j)
 // KernelFunctions' KernelProduct [EXT] (`k1 * k2`, reached through src/Stheno.jl:4-6); the locally periodic kernel of the
 // Mauna-Loa models and the sums of products of the neural-kernel-network example are such chains.
@@ -25,7 +25,7 @@
 
 namespace sgp {
 
-enum { K_RQ = 6, K_LINEAR = 7 };
+enum { K_RQ = 6, K_LINEAR = 7, K_COSINE = 16, K_GAMMAEXP = 17 };
 constexpr int KP_KIND_MASK = 0xff, KP_TIMES_PREV = 0x100;   // sthenomi.h: SGP_KIND_TIMES_PREV
 constexpr int KP_MAXF = 8;                                  // sthenomi_kprod.h: SGP_KPROD_MAX_FACTORS
 constexpr int KP_CHUNK = 8;                                 // columns per accumulator chunk
@@ -43,6 +43,49 @@ __device__ __forceinline__ double rq_log1p_u(double d2, double alpha, double& u)
 __device__ __forceinline__ double rq_eval(double d2, double alpha) {
   double u;
   return exp_nonpos(-alpha * rq_log1p_u(d2, alpha, u));
+}
+
+// Cosine cos(pi d), d = sqrt(d2): cospi / sinpi reduce their argument exactly, so the only error that grows with d is the half
+// ulp of the square root (pi d |sin pi d| units of 2^-53).  An overflowed d2 gives exactly 1 and exact-zero derivatives: every
+// double >= 2^53 is an even integer, so 1 is the limit, while cospi(inf) is NaN.  No 1e150 clamp: the factor never decays.
+// dk = d k / d g = -pi d sin(pi d); kx = d k / d (d2) = -pi sin(pi d) / (2 d), at d == 0 its limit -pi^2 / 2 by a branch.
+// Both kinds are kept out of line (cospi, sinpi, pow and log are long routines: inlined into the per-kind switches they cost
+// the assembly kernels a wave of occupancy and put the contractions' old kinds into scratch); values come back in registers.
+constexpr double KP_PI = 3.14159265358979323846, KP_DBL_MAX = 1.7976931348623157e308;
+struct KpDerivs {
+  double k, dk, kx, dp;
+};
+__device__ __noinline__ double cosine_eval(double d2) { return d2 > KP_DBL_MAX ? 1.0 : cospi(sqrt(d2)); }
+__device__ __forceinline__ KpDerivs cosine_derivs(double d2) {
+  KpDerivs r = {1.0, 0.0, 0.0, 0.0};
+  if (d2 > KP_DBL_MAX) return r;
+  const double d = sqrt(d2), sn = sinpi(d);
+  r.k = cospi(d);
+  r.dk = -(KP_PI * d) * sn;
+  r.kx = d > 0.0 ? -KP_PI * sn / (2.0 * d) : -0.5 * KP_PI * KP_PI;
+  return r;
+}
+
+// GammaExponential exp(-d^gamma) = exp(-a), a = pow(d2, gamma / 2): a = 0 and k = 1 exactly at d2 == 0, a = inf and k = 0
+// exactly -- never NaN -- where d2 overflowed (exp_nonpos clamps its argument).  pow, not exp(h log d2): the latter's error
+// grows with a |log d2|.  dk = d k / d g = -gamma a k; kx = d k / d (d2) = -(gamma / 2) a k / d2 (0 at coincident points, the
+// subgradient kern_val_dd2 uses for Matern-1/2); dp = d k / d gamma = -k a log(d2) / 2 (0 at d2 == 0, its limit).  Where k is
+// an exact 0 every derivative is an exact 0, as for RQ.
+__device__ __noinline__ double gexp_eval(double d2, double gamma) { return exp_nonpos(-pow(d2, 0.5 * gamma)); }
+__device__ __forceinline__ KpDerivs gexp_derivs(double d2, double gamma) {
+  const double a = pow(d2, 0.5 * gamma);
+  KpDerivs r = {exp_nonpos(-a), 0.0, 0.0, 0.0};
+  if (r.k == 0.0 || !(d2 > 0.0)) return r;
+  const double ak = a * r.k;
+  r.dk = -gamma * ak;
+  r.kx = -(0.5 * gamma) * ak / d2;
+  r.dp = -0.5 * (ak * log(d2));   // (the halving last: exact, where ak is subnormal too)
+  return r;
+}
+
+// one call site per factor in the contractions: the two kinds behind one out-of-line routine
+__device__ __noinline__ KpDerivs newkind_derivs(int kind, double d2, double param) {
+  return kind == K_COSINE ? cosine_derivs(d2) : gexp_derivs(d2, param);
 }
 
 template <int DMAX>
@@ -73,6 +116,8 @@ __device__ __forceinline__ void factor_chunk(double (&prod)[KP_CHUNK], const dou
     double k;
     if (KIND == K_LINEAR) k = kp_dot<DMAX>(xi, sp + q * DMAX) + param;
     else if (KIND == K_RQ) k = rq_eval(kp_d2<DMAX>(xi, sp + q * DMAX), param);
+    else if (KIND == K_COSINE) k = cosine_eval(kp_d2<DMAX>(xi, sp + q * DMAX));
+    else if (KIND == K_GAMMAEXP) k = gexp_eval(kp_d2<DMAX>(xi, sp + q * DMAX), param);
     else k = kern_eval_t<KIND>(kp_d2<DMAX>(xi, sp + q * DMAX), param);
     prod[q] = head ? k : prod[q] * k;
   }
@@ -89,6 +134,8 @@ __device__ __forceinline__ void factor_chunk_any(int kind, double (&prod)[KP_CHU
     case K_WHITE: factor_chunk<DMAX, K_WHITE>(prod, xi, sp, param, head); break;
     case K_RQ: factor_chunk<DMAX, K_RQ>(prod, xi, sp, param, head); break;
     case K_LINEAR: factor_chunk<DMAX, K_LINEAR>(prod, xi, sp, param, head); break;
+    case K_COSINE: factor_chunk<DMAX, K_COSINE>(prod, xi, sp, param, head); break;
+    case K_GAMMAEXP: factor_chunk<DMAX, K_GAMMAEXP>(prod, xi, sp, param, head); break;
     default: factor_chunk<DMAX, K_CONST>(prod, xi, sp, param, head); break;
   }
 }
@@ -245,6 +292,8 @@ __device__ __forceinline__ double kp_factor_diag(const DevTerm& T, long i) {
     d2 = fma(df, df, d2);
   }
   if (kind == K_RQ) return rq_eval(d2, T.param);
+  if (kind == K_COSINE) return cosine_eval(d2);
+  if (kind == K_GAMMAEXP) return gexp_eval(d2, T.param);
   return kern_eval(kind, d2, T.param);
 }
 
@@ -307,6 +356,13 @@ __device__ __forceinline__ void kp_factor_grad(int kind, double param, const dou
     const double r = u < 1e300 ? u / (1.0 + u) : 1.0;
     dk = -(2.0 * param) * r * k;      // -d2 (1 + u)^(-alpha - 1), d2 = 2 alpha u
     dp = k == 0.0 ? 0.0 : k * (r - l);
+    return;
+  }
+  if (kind == K_COSINE || kind == K_GAMMAEXP) {
+    const KpDerivs r = newkind_derivs(kind, d2, param);
+    k = r.k;
+    dk = r.dk;
+    dp = r.dp;
     return;
   }
   kern_and_dscale(kind, d2, param, k, dk);
@@ -502,9 +558,13 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
 
 // ---- input-point and scale gradients of ONE chain ---------------------------------------------------------------------
 // k and d k / d x of one factor from its row point and a column point: a distance kind has d k / d x = 2 kx (x - x') with
-// kx = kappa'(d2) (kern_grad.h: kern_val_dd2; RQ: -1/2 (1 + u)^(-alpha - 1) = -1/2 exp(-(alpha + 1) log1p(u)), an exact 0 --
-// never NaN -- where d2 overflowed, finite where only u did: rq_log1p_u), LINEAR has d k / d x = x' and kx stands for nothing
-template <int DMAX>
+// kx = kappa'(d2) (kern_grad.h: kern_val_dd2; COSINE / GAMMAEXP: cosine_derivs / gexp_derivs above; RQ: -1/2 (1 + u)^(-alpha - 1)
+// = -1/2 exp(-(alpha + 1) log1p(u)), an exact 0 -- never NaN -- where d2 overflowed, finite where only u did: rq_log1p_u),
+// LINEAR has d k / d x = x' and kx stands for nothing.
+// NK: whether the chain holds a COSINE / GAMMAEXP factor.  The call of their out-of-line routine costs the row-side kernel
+// below registers at every factor (DMAX = 1: 2 waves per SIMD become 1), so chains of the older kinds run an instantiation
+// without it
+template <int DMAX, bool NK>
 __device__ __forceinline__ void kp_factor_dx(int kind, double param, const double* xr, const double* sp, double& k,
                                              double& kx) {
   if (kind == K_LINEAR) {
@@ -528,6 +588,12 @@ __device__ __forceinline__ void kp_factor_dx(int kind, double param, const doubl
     kx = -0.5 * exp(-(param + 1.0) * l);
     return;
   }
+  if (NK && (kind == K_COSINE || kind == K_GAMMAEXP)) {
+    const KpDerivs r = newkind_derivs(kind, d2, param);
+    k = r.k;
+    kx = r.kx;
+    return;
+  }
   kern_val_dd2(kind, d2, param, k, kx);
 }
 
@@ -544,7 +610,7 @@ struct KpChainArgs {
   double* gx[KP_MAXF];   // gradient of factor f's row input (dim x nr, packed) or NULL
 };
 
-template <int DMAX>
+template <int DMAX, bool NK>
 __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm, long sr, long sc, const double* alpha,
                                                                 long r0, long nr, long c0, long nc, KpChainArgs C, int nf,
                                                                 double scale, double* gsv /* nr, or NULL */) {
@@ -607,7 +673,7 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
         for (int f = 0; f < TMAX; ++f) {
           k[f] = 1.0;
           kx[f] = 0.0;
-          if (f < nf) kp_factor_dx<DMAX>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], kx[f]);
+          if (f < nf) kp_factor_dx<DMAX, NK>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], kx[f]);
           pre[f + 1] = pre[f] * k[f];
         }
         const double gcs = g * scs[p];
@@ -655,7 +721,7 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
   }
 }
 
-template <int DMAX>
+template <int DMAX, bool NK>
 static int launch_grad_kprod_inputs_t(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0,
                                       long nc, const KpChainArgs& C, int nf, double scale, double* gsv, hipStream_t s) {
   constexpr int TMAX = (64 / DMAX < KP_MAXF) ? 64 / DMAX : KP_MAXF;
@@ -664,9 +730,9 @@ static int launch_grad_kprod_inputs_t(const double* Gm, long sr, long sc, const 
     return -1;
   }
   const size_t lds = (size_t)(TMAX * TILE * DMAX + TILE) * sizeof(double);
-  SGP_LDS_ATTR_ONCE(grad_kprod_inputs_kernel<DMAX>, lds);
-  hipLaunchKernelGGL(grad_kprod_inputs_kernel<DMAX>, dim3((unsigned)((nr + TILE - 1) / TILE)), dim3(256), lds, s, Gm, sr, sc,
-                     alpha, r0, nr, c0, nc, C, nf, scale, gsv);
+  SGP_LDS_ATTR_ONCE((grad_kprod_inputs_kernel<DMAX, NK>), lds);
+  hipLaunchKernelGGL((grad_kprod_inputs_kernel<DMAX, NK>), dim3((unsigned)((nr + TILE - 1) / TILE)), dim3(256), lds, s, Gm,
+                     sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv);
   SGP_HIP(hipGetLastError());
   return 0;
 }
@@ -693,7 +759,14 @@ int launch_grad_kprod_inputs(const double* Gm, long sr, long sc, const double* a
     }
   }
   int rc;
-#define SGP_KI(DM) rc = launch_grad_kprod_inputs_t<DM>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)
+  bool nk = false;
+  for (int f = 0; f < nf; ++f) {
+    const int kind = h_terms[f].kind & KP_KIND_MASK;
+    nk = nk || kind == K_COSINE || kind == K_GAMMAEXP;
+  }
+#define SGP_KI(DM)                                                                                                     \
+  rc = nk ? launch_grad_kprod_inputs_t<DM, true>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)              \
+          : launch_grad_kprod_inputs_t<DM, false>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)
   if (dmax <= 1) SGP_KI(1);
   else if (dmax <= 2) SGP_KI(2);
   else if (dmax <= 4) SGP_KI(4);
@@ -754,6 +827,12 @@ __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, l
             dk[f] = -(2.0 * T.param) * r * k[f];
             dp[f] = k[f] == 0.0 ? 0.0 : k[f] * (r - l);
             kx[f] = -0.5 * exp(-(T.param + 1.0) * l);
+          } else if (kind == K_COSINE || kind == K_GAMMAEXP) {
+            const KpDerivs r = newkind_derivs(kind, d2, T.param);
+            k[f] = r.k;
+            dk[f] = r.dk;
+            kx[f] = r.kx;
+            dp[f] = r.dp;
           } else {
             double kk;
             kern_and_dscale(kind, d2, T.param, k[f], dk[f]);

@@ -11,6 +11,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import kernels as _kernels
 from . import lib as _lib
 from .flatten import build_spec, chain_input_gradients, zero_spec
 from .gp import SthenoAbstractGP, mean_vector
@@ -479,7 +480,7 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
     sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
     index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
-    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, c of Linear / Constant).  inputs / scales of such
+    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, gamma of GammaExponential, c of Linear / Constant).  inputs / scales of such
     models come from logpdf_and_gradient_param."""
     if not _is_prior(fx.f):
         raise NotImplementedError("gradients are implemented for prior Stheno processes")
@@ -542,6 +543,32 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     return _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs)
 
 
+def _attach_d_transform(records, spec, gx):
+    """`d_transform` on every factor record whose kernel-level input chain holds a ("linear", A) or ("ard", v) step
+    (kernels.LinearTransform / ARDTransform): the cotangent of that step's matrix (d x D) or vector, formed on the host from
+    the cotangents gx of the views the library returned -- g X_in' per view (O(N D d)), summed over every view of the spec
+    that was made by this chain.  It belongs to the transform, not to the block pair: records whose factors read through one
+    chain carry one and the same array (do not add them up).  A chain with several such steps gives a tuple, in chain
+    order."""
+    totals = {}
+    for k, g in enumerate(gx):
+        org = spec.input_origin[k] if spec.input_origin is not None else None
+        if org is None or g is None or not any(st[0] in ("linear", "ard") for st in org[3]):
+            continue
+        found = []
+        _kernels.chain_vjp(org[3], org[4], g, found)
+        if org[3] in totals:
+            totals[org[3]] = [a + b for a, b in zip(totals[org[3]], found)]
+        else:
+            totals[org[3]] = found
+    for r in records:
+        org = spec.input_origin[r["row_input"]] if spec.input_origin is not None else None
+        if org is not None and org[3] in totals:
+            t = totals[org[3]]
+            r["d_transform"] = t[0] if len(t) == 1 else tuple(t)
+    return records
+
+
 def _refuse_param_family(what, *specs):
     """what the superset family of include/sthenomi_kprod_grad.h does not carry: patch / stencil sides, a multi-GPU context"""
     _refuse_patch_gradient(*specs)
@@ -556,7 +583,10 @@ def logpdf_and_gradient_param(fx, y, inputs=False, scales=False):
     with every term record in the chain form -- `chain`, `factor`, `d_param` (see logpdf_and_gradient) -- and inputs=True /
     scales=True carried through the factors of a product: `inputs` holds d logpdf / d (the view each factor reads), `x` the
     same mapped back onto the blocks of fx.x through every factor's own transform (with_lengthscale, the periodic embedding)
-    and the model's warps, `scales` one record per function-valued scale.  Single-GPU contexts; no patch / stencil terms."""
+    and the model's warps, `scales` one record per function-valued scale.  With inputs=True a factor that reads its points
+    through a LinearTransform or an ARDTransform also carries `d_transform`, the derivative with respect to that transform's
+    matrix or vector (_attach_d_transform): the frequencies and bandwidths of a spectral mixture.  Single-GPU contexts; no
+    patch / stencil terms."""
     if not _is_prior(fx.f):
         raise NotImplementedError("gradients are implemented for prior Stheno processes")
     n = len(fx)
@@ -579,7 +609,10 @@ def logpdf_and_gradient_param(fx, y, inputs=False, scales=False):
                                                     _lib.dptr(gc), _lib.dptr(gs), _lib.dptr(gp), ptrs, sptrs)
     _lib.check(rc, "sgp_logpdf_grad_param_xs")
     xb = chain_input_gradients(spec, gx)[0] if inputs else None
-    return _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs, gp=gp)
+    rec = _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs, gp=gp)
+    if inputs:
+        _attach_d_transform(rec["terms"], spec, gx)
+    return rec
 
 
 def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
@@ -1193,6 +1226,8 @@ def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):
     """elbo_and_gradient for every model it takes AND for models with a product of kernels, through sgp_elbo_grad_param and
     sgp_kernelmatrix_diag_grad_param (include/sthenomi_kprod_grad.h): the same dict, with zz_terms / xz_terms / xx_terms in
     the chain form (`chain`, `factor`, `d_param`; see logpdf_and_gradient) and `_raw` carrying the d / d param arrays.
+    With inputs=True the records of factors behind a LinearTransform / ARDTransform carry `d_transform` per spec (see
+    logpdf_and_gradient_param): the derivative of the bound is the sum over the three specs' distinct chains.
     Single-GPU contexts; no patch / stencil terms."""
     if isinstance(vfe, SparseFiniteGP):
         return elbo_and_gradient_param(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, scales=scales)
@@ -1233,7 +1268,13 @@ def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):
     rc = lib.sgp_kernelmatrix_diag_grad_param(_ctx().handle, xx.ref(), d(gv), d(gcd), d(gsd), d(gpd), pd, pdr, pdc)
     _lib.check(rc, "sgp_kernelmatrix_diag_grad_param")
     nb = len(xx.row_len)
-    xx_terms = [r for r in _term_records_kprod(xx, gcd, gsd, gpd, False) if r["I"] == r["J"]] if nb else []
+    xx_all = _term_records_kprod(xx, gcd, gsd, gpd, False) if nb else []
+    zz_terms, xz_terms = _term_records_kprod(zz, gcz, gsz, gpz, True), _term_records_kprod(xz, gcx, gsx, gpx, False)
+    if inputs:
+        _attach_d_transform(zz_terms, zz, gxz)
+        _attach_d_transform(xz_terms, xz, gxx)
+        _attach_d_transform(xx_all, xx, gdx)
+    xx_terms = [r for r in xx_all if r["I"] == r["J"]]
     xb = zb = None
     if inputs:   # chain rule back onto the blocks of fx.x and fz.x, through every factor's own view
         zr, _ = chain_input_gradients(zz, gxz)
@@ -1242,7 +1283,7 @@ def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):
         xb, zb = [a + b for a, b in zip(xr, xd)], [a + b for a, b in zip(zr, zc)]
     return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
                 z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
-                zz_terms=_term_records_kprod(zz, gcz, gsz, gpz, True), xz_terms=_term_records_kprod(xz, gcx, gsx, gpx, False),
+                zz_terms=zz_terms, xz_terms=xz_terms,
                 xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx,
                 scales=(_scale_records(zz, srz, more=((xz, srx, "row"), (xz, scx, "col"), (xx, sdr, "row"), (xx, sdc, "col")))
                         if scales else None),

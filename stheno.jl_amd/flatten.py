@@ -328,8 +328,8 @@ def build_spec(f, x, f2=None, x2=None):
                             # a product of kernels, or a kind that exists on the product path only: a chain of terms
                             # (include/sthenomi_kprod.h), each factor reading its own view of the points
                             if has_st or p.geom is not None or q.geom is not None:
-                                raise NotImplementedError("a product of kernels (or a RationalQuadratic / Linear / Polynomial "
-                                                          "kernel, which runs on the product path) below patch_convolve or a "
+                                raise NotImplementedError("a product of kernels (or a RationalQuadratic / Linear / Polynomial / "
+                                                          "Cosine / GammaExponential kernel, which runs on the product path) below patch_convolve or a "
                                                           "stencil is not supported")
                             if len(factors) > _lib.KPROD_MAX_FACTORS:
                                 raise NotImplementedError(f"a product of {len(factors)} kernels is beyond the library's limit "

@@ -5,7 +5,9 @@ evaluates (stheno.jl_amd/csrc/kernelmatrix.hip).  `input_chain` is the kernel-le
 transformation (KernelFunctions `TransformedKernel`): a tuple of steps applied to the raw points in
 order -- ("scale", s) for ScaleTransform(s) / with_lengthscale, ("periodic", f) for
 PeriodicTransform(f) (/root/reference/examples/extended_mauna_loa/script.jl:129), ("sincos", r) for the
-embedding behind PeriodicKernel(r) -- evaluated on the host (O(N D)) when the spec is built.
+embedding behind PeriodicKernel(r), ("linear", A) / ("ard", v) / ("select", idx) for KernelFunctions' LinearTransform,
+ARDTransform and SelectTransform -- evaluated on the host (O(N D)) when the spec is built.  Matrices, vectors and index
+lists are stored as tuples of floats / ints: equal maps give equal (hashable) chains, so equal views are uploaded once.
 
 Products of kernels (`k1 * k2`, KernelFunctions KernelProduct) expand into chains of such leaves:
 `leaf_products()` returns [(coef, [(kind, param, input_chain), ...])], one entry per product of primitives,
@@ -20,7 +22,10 @@ from . import lib as _lib
 
 def _push(step, chain):
     """chain with `step` applied FIRST (outer transforms act on the raw input before inner ones);
-    adjacent scalings are merged so that equal maps get equal chains."""
+    adjacent scalings are merged so that equal maps get equal chains.  ("linear", A), ("ard", v) and ("select", idx) steps
+    arrive with canonical payloads (tuples of floats / ints, from the transforms' step()), so equal matrices, vectors and index
+    lists compare and hash equal as they are; they are kept apart from the scalings around them, so that `d_transform` stays
+    the derivative with respect to the matrix or vector the caller wrote."""
     if chain and step[0] == "scale" and chain[0][0] == "scale":
         s = step[1] * chain[0][1]
         return ((("scale", s),) if s != 1.0 else ()) + tuple(chain[1:])
@@ -39,6 +44,13 @@ def apply_chain(chain, X):
                 raise ValueError("PeriodicTransform acts on 1-D inputs")
             t = (2.0 * np.pi * v) * X
             X = np.vstack([np.sin(t), np.cos(t)])      # KernelFunctions order: [sin, cos]
+        elif kind == "linear":
+            A = _linear_A(v, X.shape[0])
+            X = A @ X
+        elif kind == "ard":
+            X = _ard_v(v, X.shape[0])[:, None] * X
+        elif kind == "select":
+            X = X[list(v), :]
         elif kind == "sincos":
             # x_d -> [sin 2 pi x_d, cos 2 pi x_d] / (2 r_d): squared distances become sum_d sin^2(pi (x_d - y_d)) / r_d^2,
             # so SE over these points is KernelFunctions' PeriodicKernel(r); rows: the D sines, then the D cosines
@@ -50,15 +62,44 @@ def apply_chain(chain, X):
     return np.asfortranarray(X)
 
 
-def chain_vjp(chain, X, gout):
-    """cotangent of the raw points given the cotangent of apply_chain(chain, X)"""
-    stack = [X]
+def _linear_A(v, D):
+    """the d x D matrix of a ("linear", A) step"""
+    A = np.asarray(v, dtype=np.float64)
+    if A.ndim != 2 or A.shape[1] != D:
+        raise ValueError(f"LinearTransform: a matrix of shape {A.shape} for inputs of dimension {D}")
+    return A
+
+
+def _ard_v(v, D):
+    """the D factors of an ("ard", v) step"""
+    a = np.asarray(v, dtype=np.float64)
+    if a.shape != (D,):
+        raise ValueError(f"ARDTransform: {a.size} factors for inputs of dimension {D}")
+    return a
+
+
+def chain_vjp(chain, X, gout, transforms=None):
+    """cotangent of the raw points given the cotangent of apply_chain(chain, X).  transforms: a list that receives, in
+    chain order, the cotangent of every ("linear", A) step's matrix (g X_in') and every ("ard", v) step's vector
+    (the row sums of g * X_in), X_in the points that step reads and g the cotangent of what it returns"""
+    stack = [np.asarray(X, dtype=np.float64)]
     for kind, v in chain[:-1]:
         stack.append(apply_chain(((kind, v),), stack[-1]))
     g = np.asarray(gout, dtype=np.float64)
+    found = []
     for (kind, v), xin in zip(reversed(chain), reversed(stack)):
         if kind == "scale":
             g = v * g
+        elif kind == "linear":
+            found.append(g @ xin.T)
+            g = _linear_A(v, xin.shape[0]).T @ g
+        elif kind == "ard":
+            found.append(np.sum(g * xin, axis=1))
+            g = _ard_v(v, xin.shape[0])[:, None] * g
+        elif kind == "select":
+            gin = np.zeros(xin.shape)
+            np.add.at(gin, list(v), g)
+            g = gin
         elif kind == "sincos":
             D = xin.shape[0]
             h = (np.pi / _sincos_r(v, D))[:, None]          # 2 pi / (2 r_d)
@@ -67,6 +108,8 @@ def chain_vjp(chain, X, gout):
         else:
             t = (2.0 * np.pi * v) * xin
             g = (2.0 * np.pi * v) * (np.cos(t) * g[0:1, :] - np.sin(t) * g[1:2, :])
+    if transforms is not None:
+        transforms.extend(reversed(found))
     return g
 
 
@@ -150,6 +193,34 @@ class Matern52Kernel(_Simple):
 
 class WhiteKernel(_Simple):
     kind = _lib.WHITE
+
+
+def MaternKernel(nu=1.5):
+    """KernelFunctions' MaternKernel(nu) at the three half-integer orders with a closed form: the existing kinds.  Any other
+    nu needs a Bessel-K routine on the device and is not built."""
+    kinds = {0.5: Matern12Kernel, 1.5: Matern32Kernel, 2.5: Matern52Kernel}
+    if float(nu) not in kinds:
+        raise NotImplementedError(f"MaternKernel(nu = {nu!r}): the general-nu Matern kernel is not built; nu must be "
+                                  "1/2, 3/2 or 5/2")
+    return kinds[float(nu)]()
+
+
+class CosineKernel(_Simple):
+    """cos(pi d) (KernelFunctions CosineKernel); evaluated on the product path (include/sthenomi_kprod.h)"""
+    kind = _lib.COSINE
+
+
+class GammaExponentialKernel(Kernel):
+    """exp(-d^gamma), d the Euclidean distance, gamma in (0, 2] (KernelFunctions >= 0.9): gamma = 1 is ExponentialKernel,
+    gamma = 2 is SEKernel o ScaleTransform(sqrt 2)"""
+
+    def __init__(self, gamma=2.0):
+        self.gamma = float(gamma)
+        if not 0.0 < self.gamma <= 2.0:
+            raise ValueError("GammaExponentialKernel: gamma must be in (0, 2]")
+
+    def leaf_terms(self):
+        return [(_lib.GAMMAEXP, 1.0, self.gamma, ())]
 
 
 class ConstantKernel(Kernel):
@@ -286,8 +357,48 @@ class PeriodicTransform:
         return ("periodic", self.f)
 
 
+class LinearTransform:
+    """x -> A x, A of shape d x D (KernelFunctions.LinearTransform)"""
+
+    def __init__(self, A):
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.size == 0:
+            raise ValueError("LinearTransform: A must be a non-empty matrix")
+        self.A = A
+
+    def step(self):
+        return ("linear", tuple(tuple(float(a) for a in row) for row in self.A))
+
+
+class ARDTransform:
+    """x -> v .* x (KernelFunctions.ARDTransform)"""
+
+    def __init__(self, v):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim != 1 or v.size == 0:
+            raise ValueError("ARDTransform: v must be a non-empty vector")
+        self.v = v
+
+    def step(self):
+        return ("ard", tuple(float(a) for a in self.v))
+
+
+class SelectTransform:
+    """x -> x[idx] (KernelFunctions.SelectTransform; 0-based here)"""
+
+    def __init__(self, idx):
+        raw = np.asarray(idx).ravel()
+        if raw.size == 0 or np.any(raw != np.floor(raw)) or np.any(raw < 0):
+            raise ValueError("SelectTransform: idx must be a non-empty list of coordinates >= 0")
+        self.idx = tuple(int(i) for i in raw)
+
+    def step(self):
+        return ("select", self.idx)
+
+
 class TransformedKernel(Kernel):
-    """k ∘ t for t a ScaleTransform or PeriodicTransform (written `k @ t` here)."""
+    """k ∘ t for t a ScaleTransform, PeriodicTransform, LinearTransform, ARDTransform or SelectTransform (written
+    `k @ t` here)."""
 
     def __init__(self, kernel, transform):
         self.kernel, self.transform = kernel, transform
@@ -303,3 +414,44 @@ class TransformedKernel(Kernel):
 
 def with_lengthscale(kernel, l):
     return ScaleTransformedKernel(kernel, 1.0 / float(l))
+
+
+def gaborkernel(sqexponential_transform=None, cosine_transform=None):
+    """(SEKernel o sqexponential_transform) * (CosineKernel o cosine_transform) (KernelFunctions.gaborkernel); None: the
+    identity"""
+    a, b = SEKernel(), CosineKernel()
+    if sqexponential_transform is not None:
+        a = a @ sqexponential_transform
+    if cosine_transform is not None:
+        b = b @ cosine_transform
+    return a * b
+
+
+def _mixture_args(alphas, gammas, omegas, alpha_ndim):
+    al = np.asarray(alphas, dtype=np.float64)
+    ga, om = np.asarray(gammas, dtype=np.float64), np.asarray(omegas, dtype=np.float64)
+    if ga.ndim != 2 or ga.shape != om.shape or al.ndim != alpha_ndim or al.shape[-1] != ga.shape[1] or ga.size == 0:
+        raise ValueError("spectral mixture: gammas and omegas must be D x Q, alphas of length Q (product kernel: D x Q)")
+    return al, ga, om
+
+
+def spectral_mixture_kernel(alphas, gammas, omegas, h=None):
+    """k(x, y) = sum_q alpha_q h(gamma_q' t) cos(pi omega_q' t),  t = x - y,  h(s) = h(s, 0) (default SEKernel: exp(-s^2 / 2))
+    with gammas, omegas of shape D x Q and alphas of length Q (KernelFunctions.spectral_mixture_kernel): a sum of Q products
+    of two one-dimensional factors, h on the projection gamma_q' x and CosineKernel on omega_q' x."""
+    al, ga, om = _mixture_args(alphas, gammas, omegas, 1)
+    h = SEKernel() if h is None else h
+    row = lambda M, q: LinearTransform(M[:, q][None, :])      # noqa: E731  (the projection x -> M_q' x)
+    return KernelSum([float(al[q]) * ((h @ row(ga, q)) * (CosineKernel() @ row(om, q))) for q in range(ga.shape[1])])
+
+
+def spectral_mixture_product_kernel(alphas, gammas, omegas, h=None):
+    """k(x, y) = prod_d sum_q alpha_dq h(gamma_dq t_d) cos(pi omega_dq t_d),  t = x - y, with alphas, gammas, omegas of shape
+    D x Q (KernelFunctions.spectral_mixture_product_kernel): the product over the coordinates of one-dimensional spectral
+    mixtures.  leaf_products() distributes it into Q^D chains of 2 D factors; beyond the limits of a chain (8 factors) the
+    library refuses it."""
+    al, ga, om = _mixture_args(alphas, gammas, omegas, 2)
+    if al.shape != ga.shape:
+        raise ValueError("spectral_mixture_product_kernel: alphas, gammas and omegas must all be D x Q")
+    return KernelProduct([spectral_mixture_kernel(al[d], ga[d:d + 1], om[d:d + 1], h) @ SelectTransform([d])
+                          for d in range(ga.shape[0])])

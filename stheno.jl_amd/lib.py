@@ -28,6 +28,7 @@ KPROD_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod_grad.so")
 # kernel kinds / noise kinds (sthenomi.h enums)
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
 RQ, LINEAR = 6, 7                  # evaluated by the product-chain path only (include/sthenomi_kprod.h)
+COSINE, GAMMAEXP = 16, 17          # the same path (8 .. 15 are no kinds)
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
 KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain
@@ -746,7 +747,7 @@ class Spec:
                 term_ptr.append(len(terms))
         self.has_patch = any(g != (None, None) for g in self.term_geoms)
         self.has_stencil = any(st != (None, None) for st in self.term_stencils)
-        # product chains / the RQ and LINEAR kinds (include/sthenomi_kprod.h): a term whose kind carries KIND_TIMES_PREV
+        # product chains / the RQ, LINEAR, COSINE and GAMMAEXP kinds (include/sthenomi_kprod.h): a term whose kind carries KIND_TIMES_PREV
         # continues the chain of the term before it
         self.has_kprod = any((int(t[0]) & KIND_TIMES_PREV) or (int(t[0]) & KIND_MASK) > CONST for t in terms)
         self._bound = None
