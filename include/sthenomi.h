@@ -50,7 +50,9 @@ enum {
   SGP_LINEAR = 7,   /* LinearKernel(c): x'y + c, param = c >= 0                          */
   /* 8 .. 15 are no kinds: a spec that names one is refused ("unknown kernel kind") */
   SGP_COSINE = 16,  /* CosineKernel: cos(pi d), param ignored                            */
-  SGP_GAMMAEXP = 17 /* GammaExponentialKernel(gamma): exp(-d^gamma), param = gamma in (0, 2] */
+  SGP_GAMMAEXP = 17, /* GammaExponentialKernel(gamma): exp(-d^gamma), param = gamma in (0, 2] */
+  /* 18 and 19 are no kinds either */
+  SGP_MATERN_NU = 20 /* MaternKernel(nu): 2^(1-nu) / Gamma(nu) x^nu K_nu(x), x = sqrt(2 nu) d, param = nu in (0, 32] */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -81,7 +83,7 @@ typedef struct {
                          Stencil terms: the same encoding, ids of the same table registered by
                          sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
-  double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma */
+  double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

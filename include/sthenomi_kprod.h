@@ -1,4 +1,5 @@
-/* sthenomi_kprod.h -- product chains of kernels, the RationalQuadratic, Linear, Cosine and GammaExponential kinds, and the
+/* sthenomi_kprod.h -- product chains of kernels, the RationalQuadratic, Linear, Cosine, GammaExponential and general-nu
+ * Matern kinds, and the
  * gradient of logpdf with respect to kernel parameters, through libsthenomi_kprod.so.
  *
  * An extension of the drop-in boundary (include/sthenomi.h), in a header and a library of its own, as
@@ -14,9 +15,9 @@
  *   - every factor names its own row_input / col_input (the factors of one product read differently scaled or transformed
  *     views of the points); the two inputs of a factor have one dimension;
  *   - a continuation has coef == 1.0, NULL row_scale / col_scale and reserved == 0, and is never the first term of a pair;
- *   - the head of a chain, and any term of the kinds SGP_RQ / SGP_LINEAR / SGP_COSINE / SGP_GAMMAEXP (a chain of length
- *     one), has reserved == 0: there are no products with patch or stencil sides.
- * Kinds that exist on this path only (codes 6, 7, 16, 17; 8 .. 15 and everything above 17 are refused as unknown):
+ *   - the head of a chain, and any term of the kinds SGP_RQ / SGP_LINEAR / SGP_COSINE / SGP_GAMMAEXP / SGP_MATERN_NU (a chain
+ *     of length one), has reserved == 0: there are no products with patch or stencil sides.
+ * Kinds that exist on this path only (codes 6, 7, 16, 17, 20; 8 .. 15, 18, 19 and everything above 20 are refused as unknown):
  *   SGP_RQ        param = alpha > 0:  (1 + d^2 / (2 alpha))^-alpha       (RationalQuadraticKernel)
  *   SGP_LINEAR    param = c >= 0:     x'y + c                            (LinearKernel; PolynomialKernel(n, c) is a chain of
  *                                                                         n such factors)
@@ -26,14 +27,27 @@
  *                                                                        (GammaExponentialKernel, KernelFunctions >= 0.9: Euclidean
  *                                                                         d; gamma = 1 is ExponentialKernel, gamma = 2 is
  *                                                                         SEKernel o ScaleTransform(sqrt 2))
+ *   SGP_MATERN_NU param = nu, finite and in (0, SGP_MATERN_NU_MAX]:  2^(1-nu) / Gamma(nu) x^nu K_nu(x), x = sqrt(2 nu) d
+ *                                                                        (MaternKernel(nu): Euclidean d, as in KernelFunctions and
+ *                                                                         scikit-learn; nu = 1/2, 3/2, 5/2 are SGP_MATERN12 / 32 /
+ *                                                                         52, which stay the faster closed forms)
+ * General-nu Matern has no library call to lean on: K_nu is evaluated in fp64 by Temme's series (x <= 2) or Steed's second
+ * continued fraction (x > 2) at the order mu = nu - n in [-1/2, 1/2), followed by n - 1 steps of the upward recurrence, on
+ * quantities scaled by the power of x and by e^x so that nothing overflows or underflows before the last product; what depends
+ * on nu alone (Temme's coefficients, the normalisation) is computed once per term when the spec is uploaded.  The cap on nu
+ * bounds the recurrence's trip count.  The relative error is at most (128 + 4 x + 3 n) 2^-53, n = floor(nu + 1/2)
+ * (tests/matern_nu_truth.py derives the constants; docs/03_kernels.md section 3.2e has the measured maxima).  nu is held fixed:
+ * d k / d nu is not formed and grad_param of such a term is 0.
  * Cosine is evaluated with cospi / sinpi (exact argument reduction: the only error that grows with d is the square root's half
  * ulp, pi d |sin pi d| units of 2^-53) and is the one factor that changes sign and passes through zero.  Rules at the ends:
- *   d^2 == 0      both kinds are exactly 1.  d k / d (d^2) of Cosine takes its limit -pi^2 / 2 (by a branch, not 0 / 0); that of
+ *   d^2 == 0      all three kinds are exactly 1.  d k / d (d^2) of general-nu Matern is -nu / (2 (nu - 1)) for nu > 1 and, where
+ *                 it diverges (nu <= 1), 0, the same subgradient.  Of the other two:  d k / d (d^2) of Cosine takes its limit -pi^2 / 2 (by a branch, not 0 / 0); that of
  *                 GammaExponential, which diverges for gamma < 2, is taken as 0 -- the subgradient Matern-1/2 has there -- and
  *                 d k / d gamma as its limit 0.
  *   d^2 == +inf   (an overflowed squared distance) Cosine is exactly 1 with derivatives exactly 0 (every double >= 2^53 is an
  *                 even integer, and cospi(inf) would be NaN): an underflowed SE times a Cosine is an exact 0, never NaN.
- *                 GammaExponential is exactly 0 there and wherever exp(-d^gamma) underflows, and then so are its derivatives.
+ *                 GammaExponential is exactly 0 there and wherever exp(-d^gamma) underflows, and then so are its derivatives;
+ *                 the same holds for general-nu Matern (an underflowed SE times it is an exact 0).
  * Limits, from the assembly and contraction kernels' 64 KiB of column points in LDS and their registers
  * (stheno.jl_amd/csrc/kprod.hip): at most SGP_KPROD_MAX_FACTORS factors in a chain, factor input dimension at most
  * SGP_KPROD_MAX_DIM, and factors x (the chain's largest factor dimension rounded up to a power of two) <= 64 -- 8 factors up
@@ -45,9 +59,10 @@
  * sgp_logpdf_grad, whose outputs keep one entry per element of spec->terms: for a chain with head h
  *     grad_coef[h]       = sum_ij G_ij rs_i cs_j prod_f k_f        grad_coef[continuation] = 0
  *     grad_inscale[f]    = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != f} k_f') d k_f(g x, g x') / dg at g = 1
- * (LINEAR: 2 x'y;  RQ: -d^2 (1 + d^2 / (2 alpha))^(-alpha - 1);  COSINE: -pi d sin(pi d);  GAMMAEXP: -gamma d^gamma k).  With
+ * (LINEAR: 2 x'y;  RQ: -d^2 (1 + d^2 / (2 alpha))^(-alpha - 1);  COSINE: -pi d sin(pi d);  GAMMAEXP: -gamma d^gamma k;
+ * MATERN_NU: -C x^(nu+1) K_(nu-1)(x), C = 2^(1-nu) / Gamma(nu)).  With
  * respect to the points a distance kind contributes 2 kappa' (x - x'), kappa' = d k / d (d^2): COSINE -pi sin(pi d) / (2 d),
- * GAMMAEXP -(gamma / 2) d^gamma k / d^2.  The gradients with respect to the points the factors read,
+ * GAMMAEXP -(gamma / 2) d^gamma k / d^2, MATERN_NU -(nu / x) C x^nu K_(nu-1)(x).  The gradients with respect to the points the factors read,
  * to function-valued scales and everything behind the ELBO come from the superset family of include/sthenomi_kprod_grad.h
  * (sgp_logpdf_grad_param_xs, sgp_kernelmatrix_diag_grad_param, sgp_elbo_grad_param; libsthenomi_kprod_grad.so).  The entry points of include/sthenomi.h
  * for those gradients keep refusing chains with rc < 0 and a message naming "product" and the function to call instead:
@@ -65,12 +80,14 @@ extern "C" {
 
 #define SGP_KPROD_MAX_FACTORS 8
 #define SGP_KPROD_MAX_DIM 16
+#define SGP_MATERN_NU_MAX 32.0
 
 /* sgp_logpdf_grad plus the gradient with respect to the kernel parameters: grad_param (may be NULL, like every output) has
  * one entry per element of spec->terms,
  *     grad_param[t] = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != t} k_f') d k_t / d param
  * with d k / d param = k (u / (1 + u) - log1p(u)), u = d^2 / (2 alpha), for SGP_RQ; d k / d gamma = -k d^gamma log(d^2) / 2 for
- * SGP_GAMMAEXP; 1 for SGP_LINEAR and SGP_CONST; 0 for the kinds without a parameter (SGP_COSINE among them).  Plain terms (outside any chain) get their entries too.  Every other output is bit for bit what
+ * SGP_GAMMAEXP; 1 for SGP_LINEAR and SGP_CONST; 0 for the kinds without a parameter (SGP_COSINE among them) and for
+ * SGP_MATERN_NU, whose nu is held fixed.  Plain terms (outside any chain) get their entries too.  Every other output is bit for bit what
  * sgp_logpdf_grad returns for the same arguments.  Any spec sgp_logpdf_grad takes, on a single-GPU context: a multi-GPU
  * context refuses this entry point (rc < 0) whatever the spec holds, product chains or not. */
 int sgp_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,

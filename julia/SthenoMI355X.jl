@@ -96,6 +96,8 @@ leaf(k::ConstantKernel) = [(5, 1.0, only(k.c), Chain())]
 # kinds of the product path (include/sthenomi_kprod.h): a term of its own is a chain of length one
 leaf(::CosineKernel) = [(16, 1.0, 0.0, Chain())]
 leaf(k::GammaExponentialKernel) = [(17, 1.0, Float64(only(k.γ)), Chain())]
+# SGP_MATERN_NU = 20: any order in (0, 32] (a Bessel function per entry); 1/2, 3/2, 5/2 are Matern12Kernel .. Matern52Kernel
+leaf(k::MaternKernel) = [(20, 1.0, Float64(only(k.ν)), Chain())]
 leaf(k::ScaledKernel) = [(a, c * only(k.σ²), p, ch) for (a, c, p, ch) in leaf(k.kernel)]
 leaf(k::KernelSum) = reduce(vcat, leaf.(k.kernels))
 # k o t evaluates k(t(x), t(y)): t is applied to the raw points first, the inner kernel's own chain after it

@@ -308,8 +308,10 @@ extern "C" int sgp_ctx_destroy(sgp_ctx* c) {
 // ---------------------------------------------------------------------------------------
 // device-resident specs
 // ---------------------------------------------------------------------------------------
-// the kinds of include/sthenomi.h: 0 .. 7, and 16 / 17 (8 .. 15 and everything above stay unknown)
-static bool kind_known(int k) { return (k >= SGP_SE && k <= SGP_LINEAR) || k == SGP_COSINE || k == SGP_GAMMAEXP; }
+// the kinds of include/sthenomi.h: 0 .. 7, 16 / 17 and 20 (8 .. 15, 18, 19 and everything above stay unknown)
+static bool kind_known(int k) {
+  return (k >= SGP_SE && k <= SGP_LINEAR) || k == SGP_COSINE || k == SGP_GAMMAEXP || k == SGP_MATERN_NU;
+}
 
 static int pow2ceil(int d) {
   int p = 1;
@@ -375,6 +377,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   // product chains and terms of the RQ / LINEAR / COSINE / GAMMAEXP kinds (include/sthenomi_kprod.h): a class of their own
   // (kprod.hip)
   std::vector<char> is_kp(std::max(1, nterms), 0);
+  std::vector<size_t> nuc_off(std::max(1, nterms), (size_t)-1);   // SGP_MATERN_NU: the term's constants of nu (kprod.hip)
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
@@ -399,6 +402,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
             return fail("spec: SGP_RQ (product path): param = alpha must be > 0 and finite");
           if ((T.kind & 0xff) == SGP_GAMMAEXP && !(T.param > 0.0 && T.param <= 2.0))
             return fail("spec: SGP_GAMMAEXP (product path): param = gamma must be in (0, 2]");
+          if ((T.kind & 0xff) == SGP_MATERN_NU && !(T.param > 0.0 && T.param <= SGP_MATERN_NU_MAX))
+            return fail("spec: SGP_MATERN_NU (product path): param = nu must be finite and in (0, 32]");
           if ((T.kind & 0xff) == SGP_LINEAR && !(T.param >= 0.0 && T.param < 1e300))
             return fail("spec: SGP_LINEAR (product path): param = c must be >= 0 and finite");
           if (T.row_input >= 0 && T.row_input < sp->n_inputs) {
@@ -412,6 +417,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
               return fail("spec: product chain beyond the limits: at most 8 factors, and factors x (largest factor dimension "
                           "rounded up to a power of two) <= 64");
           }
+          if ((T.kind & 0xff) == SGP_MATERN_NU) nuc_off[t] = place(sizeof(double) * MN_COUNT);
           ++ds->n_kprod;
         }
         if (T.row_input < 0 || T.row_input >= sp->n_inputs || T.col_input < 0 ||
@@ -565,6 +571,10 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           memcpy(h_base + cs_off[t], T.col_scale, sizeof(double) * (size_t)cs_len[t]);
           D.cs = (const double*)(d_base + cs_off[t]);
         }
+        if (nuc_off[t] != (size_t)-1) {
+          matern_nu_constants(T.param, (double*)(h_base + nuc_off[t]));
+          D.nuc = (const double*)(d_base + nuc_off[t]);
+        }
         h_terms[pos] = D;
         ds->h_terms.push_back(D);
         ds->term_src.push_back(t);
@@ -654,7 +664,8 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       for (int t = tk; t < t1;) {   // whole chains per launch, as many as fit its LDS (kprod.hip: kprod_group)
         int kdmax = 1;
         const int cnt = kprod_group(ds->h_terms.data(), t, t1, &kdmax);
-        CHECK_RC(launch_assemble_kprod(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, kdmax, lower_only, t > t0 ? 1 : 0,
+        CHECK_RC(launch_assemble_kprod(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, kdmax,
+                                       kprod_has_matern_nu(ds->h_terms.data() + t, cnt), lower_only, t > t0 ? 1 : 0,
                                        t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
         t += cnt;
       }
@@ -1631,7 +1642,8 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
     for (int t = t1; t < t1k;) {   // product chains, in the launch groups of the matrix assembly: the same sums
       int kdmax = 1;
       const int cnt = kprod_group(ds->h_terms.data(), t, t1k, &kdmax);
-      CHECK_RC(launch_diag_kprod(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t, cnt, 1, s));
+      CHECK_RC(launch_diag_kprod(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t, cnt,
+                                 kprod_has_matern_nu(ds->h_terms.data() + t, cnt), 1, s));
       t += cnt;
     }
   }
@@ -1808,11 +1820,12 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       }
       for (int t = t0; dgp && t < tk; ++t)
         if (ds->h_terms[t].kind == SGP_CONST)
-          CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, 1, 1, trf, tcf, trl - trf, tcl - tcf,
+          CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, 1, 1, 0, trf, tcf, trl - trf, tcl - tcf,
                                      dpart.p, nullptr, nullptr, dgp + t, s));
       for (int t = tk; t < t1;) {
         const int e = chain_end(ds, t, t1), cdmax = chain_dmax(ds, t, e);
-        CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, e - t, cdmax, trf, tcf, trl - trf,
+        CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, e - t, cdmax,
+                                   kprod_has_matern_nu(ds->h_terms.data() + t, e - t), trf, tcf, trl - trf,
                                    tcl - tcf, dpart.p, dgc + t, dgs + t, dgp ? dgp + t : nullptr, s));
         t = e;
       }

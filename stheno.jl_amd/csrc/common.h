@@ -91,9 +91,20 @@ struct DevTerm {
   // stencil term (stencil.hip): a side with qr / qc > 0 reads its points shifted by a registered stencil -- str (stc)
   // holds its offsets (dim x qr, column-major) followed by its qr weights on the device; qr == 0: that side is plain
   int qr, qc;
-  const double* str;
+  // a term of the kind SGP_MATERN_NU (kprod.hip; never a stencil term, qr == 0): nuc points at the MN_COUNT numbers that
+  // depend on nu alone, computed on the host when the spec is uploaded (matern_nu_constants) and laid out in the spec's block
+  union {
+    const double* str;
+    const double* nuc;
+  };
   const double* stc;
 };
+
+// the constants of one SGP_MATERN_NU term: nu = mu + n (n = 0: nu < 1/2 and mu = -nu), pi mu / sin(pi mu), Temme's Gamma_1 and
+// Gamma_2, 1 / (2 Gamma^-1(1 + mu)) and 1 / (2 Gamma^-1(1 - mu)), 1/4 - mu^2, 2^(1-n) / Gamma(nu) and nu times it, sqrt(2 nu),
+// and d k / d (d^2) at coincident points
+enum { MN_N = 0, MN_MU, MN_FACT, MN_GAM1, MN_GAM2, MN_PH, MN_QH, MN_A1, MN_CA, MN_CK, MN_SQ, MN_KX0, MN_COUNT };
+void matern_nu_constants(double nu, double* out /* MN_COUNT */);
 
 // a patch geometry registered on a context (sgp_conv_geom).  Stencils (sgp_stencil_register) take their ids from the same
 // table: an entry with st > 0 names the context's stencil st - 1 and no geometry (h == 0)
@@ -134,18 +145,21 @@ int launch_diag_stencil(double* out, long n, const DevTerm* d_terms, int nterms,
 // kprod.hip: product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h).  The terms of one launch are whole chains;
 // kprod_group cuts a pair's chain terms [t, t1) into launches (returns how many terms the launch at t carries, *dmax_out = its
 // DMAX) for the matrix and the diagonal alike.  Arguments of launch_assemble_kprod as launch_assemble_block.
+// mn: whether those terms hold a SGP_MATERN_NU factor (kprod_has_matern_nu of their host copies): the kernels are instantiated
+// with and without the Bessel routine
 int kprod_group(const DevTerm* h_terms, int t, int t1, int* dmax_out);
+bool kprod_has_matern_nu(const DevTerm* h_terms, int n);
 int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* d_terms, int nterms,
-                          int dmax, int lower_only, int accumulate, int noise_kind, double sigma2,
+                          int dmax, int mn, int lower_only, int accumulate, int noise_kind, double sigma2,
                           const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
                           long tile_c_cnt, hipStream_t s);
 // out[i] (i < n) = (accumulate ? out[i] : 0) + the chains of one launch group, summed as launch_assemble_kprod sums entry (i, i)
-int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int accumulate, hipStream_t s);
+int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int mn, int accumulate, hipStream_t s);
 // gradient contraction of ONE chain (nf factors at d_terms): out_coef / out_scale / out_param point at the chain's first entry
 // (nf each; any may be NULL); partials: tile rows x tile columns x 24 doubles
 int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
-                      const DevTerm* d_terms, int nf, int dmax, long trf, long tcf, long trc, long tcc, double* partials,
-                      double* out_coef, double* out_scale, double* out_param, hipStream_t s);
+                      const DevTerm* d_terms, int nf, int dmax, int mn, long trf, long tcf, long trc, long tcc,
+                      double* partials, double* out_coef, double* out_scale, double* out_param, hipStream_t s);
 
 // input-point gradients and the head's row-scale sums of ONE chain over one block pair (kprod.hip: grad_kprod_inputs_kernel):
 // h_terms the chain's nf factors (host copies), gx[f] the gradient of factor f's row input (NULL: not asked for), G addressed

@@ -1,5 +1,5 @@
 // Product chains (include/sthenomi_kprod.h): covariance terms that multiply several leaf kernels, each on its own view of
-// the points, and the kinds that exist only here: RationalQuadratic, Linear, Cosine and GammaExponential.
+// the points, and the kinds that exist only here: RationalQuadratic, Linear, Cosine, GammaExponential and general-nu Matern.
 //     chain value (i, j) = coef_head rs_i cs_j  prod_f k_f(x^f_i, x'^f_j)
 // KernelFunctions' KernelProduct [EXT] (`k1 * k2`, reached through src/Stheno.jl:4-6); the locally periodic kernel of the
 // Mauna-Loa models and the sums of products of the neural-kernel-network example are such chains.
@@ -25,7 +25,7 @@
 
 namespace sgp {
 
-enum { K_RQ = 6, K_LINEAR = 7, K_COSINE = 16, K_GAMMAEXP = 17 };
+enum { K_RQ = 6, K_LINEAR = 7, K_COSINE = 16, K_GAMMAEXP = 17, K_MATERN_NU = 20 };
 constexpr int KP_KIND_MASK = 0xff, KP_TIMES_PREV = 0x100;   // sthenomi.h: SGP_KIND_TIMES_PREV
 constexpr int KP_MAXF = 8;                                  // sthenomi_kprod.h: SGP_KPROD_MAX_FACTORS
 constexpr int KP_CHUNK = 8;                                 // columns per accumulator chunk
@@ -83,9 +83,173 @@ __device__ __forceinline__ KpDerivs gexp_derivs(double d2, double gamma) {
   return r;
 }
 
+// General-nu Matern  k = C x^nu K_nu(x),  x = sqrt(2 nu) d,  C = 2^(1-nu) / Gamma(nu)  (param = nu in (0, SGP_MATERN_NU_MAX]).
+// nu = mu + n, n = floor(nu + 1/2) >= 1, mu in [-1/2, 1/2); nu < 1/2 takes mu = -nu, n = 0 (K is even in its order: the pair
+// (K_mu, K_(mu+1)) is then (K_nu, K_(nu-1)), the value and what the derivative needs, without a cancelling downward step).
+// Everything is carried as  Q_j = (x / 2)^mu x^j K_(mu+j)(x)  (times e^x beyond x = 2): K_(mu+j) ~ x^-(mu+j) at small x and
+// ~ e^-x at large x, Q_j does neither, so nothing overflows or underflows before the last product.
+//   x <= 2   Temme's series for K_mu and K_(mu+1) (N. M. Temme, J. Comput. Phys. 19 (1975) 324), each term times (x / 2)^mu:
+//            the powers (2 / x)^(+-mu) of the textbook form become 1 and E = (x / 2)^(2 mu), taken with pow -- as
+//            exp(2 mu log(x / 2)) its error would grow with |log x|; sinh(e) / e log(2 / x) becomes (1 - E) / (2 mu), or
+//            expm1(g) / g log(2 / x), g = 2 mu log(x / 2), where |g| < 1 (mu -> 0)
+//   x > 2    Steed's second continued fraction (the same paper; Thompson & Barnett 1987) for e^x K_mu and the ratio
+//            K_(mu+1) / K_mu, with b d - 1 written as -a d d' (no cancellation); at mu = -1/2 it is the closed form
+//   then     Q_(j+1) = x^2 Q_(j-1) + 2 (mu + j) Q_j, j = 1 .. n - 1: positive terms, 2 (mu + j) = 2 (nu - (n - j)) exact
+//   k = ca Q_n [e^-x],  kx = d k / d (d2) = -nu ca Q_(n-1) [e^-x]  (d / dx x^nu K_nu = -x^nu K_(nu-1), dx / d(d2) = nu / x),
+//   dk = d k / d g = 2 d2 kx;   nu < 1/2:  k = ca Q_0 / E,  kx = -nu ca Q_1 / (E x^2).   dp = 0: nu is held fixed.
+// e^-x is applied once, through exp_nonpos; beyond x = 600 as e^-600 e^-(x - 600) (x - 600 is exact), since e^-x is subnormal
+// from 708 on while its product with x^nu still is a normal number.  What depends on nu alone comes from the host
+// (matern_nu_constants below, uploaded with the spec: DevTerm::nuc).  Ends, each a branch:
+//   d2 == 0             k = 1, dk = 0, kx = -nu / (2 (nu - 1)) for nu > 1 and 0 for nu <= 1 (it diverges: the subgradient)
+//   x >= 1000 (or inf)  k < 2^-1076 for every nu <= 32: k and every derivative exactly 0, as wherever k rounds to 0
+// Error model and measured maxima: tests/matern_nu_truth.py, docs/03_kernels.md section 3.2e.
+constexpr double MN_E600 = 2.6503965530043108e-261, MN_EPS = 1.1102230246251565e-16;
+constexpr int MN_TEMME_MAXIT = 30, MN_CF2_MAXIT = 200;   // (13 and 79 are the most any argument takes)
+__device__ __noinline__ KpDerivs matern_nu_derivs(double d2, double nu, const double* __restrict__ c) {
+  KpDerivs r = {1.0, 0.0, c[MN_KX0], 0.0};
+  if (!(d2 > 0.0)) return r;
+  r.k = r.kx = 0.0;
+  const double x = c[MN_SQ] * sqrt(d2);
+  if (!(x < 1000.0)) return r;
+  const double mu = c[MN_MU];
+  const int n = (int)c[MN_N];
+  double qa, qb, E;   // Q_0, Q_1, (x / 2)^(2 mu)
+  if (x <= 2.0) {
+    const double xh = 0.5 * x, dl = -log(xh), mu2 = mu * mu;
+    E = pow(xh, 2.0 * mu);
+    const double g = -(2.0 * mu) * dl;
+    double t2;
+    if (fabs(g) < 1.0) t2 = (g != 0.0 ? expm1(g) / g : 1.0) * dl;
+    else t2 = (1.0 - E) / (2.0 * mu);
+    double ff = c[MN_FACT] * (c[MN_GAM1] * (0.5 * (1.0 + E)) + c[MN_GAM2] * t2);
+    double p = c[MN_PH], q = c[MN_QH] * E;
+    double s0 = ff, s1 = p, cc = 1.0;
+    const double dd = xh * xh;
+    for (int i = 1; i <= MN_TEMME_MAXIT; ++i) {
+      const double di = (double)i;
+      ff = (di * ff + p + q) / (di * di - mu2);
+      cc = cc * (dd / di);
+      p = p / (di - mu);
+      q = q / (di + mu);
+      const double de0 = cc * ff, de1 = cc * (p - di * ff);
+      s0 += de0;
+      s1 += de1;
+      if (fabs(de0) < fabs(s0) * MN_EPS && fabs(de1) < fabs(s1) * MN_EPS) break;
+    }
+    qa = s0;
+    qb = 2.0 * s1;
+  } else {
+    const double a1 = c[MN_A1];
+    double b = 2.0 * (1.0 + x), d = 1.0 / b, h = d, delh = d, q1 = 0.0, q2 = 1.0, q = a1, cc = a1, a = -a1;
+    double s = 1.0 + q * delh;
+    if (a1 != 0.0) {
+      for (int i = 2; i <= MN_CF2_MAXIT; ++i) {
+        a = a - 2.0 * (double)(i - 1);
+        cc = -a * cc / (double)i;
+        const double qn = (q1 - b * q2) / a;
+        q1 = q2;
+        q2 = qn;
+        q = q + cc * qn;
+        b = b + 2.0;
+        const double dn = 1.0 / (b + a * d);
+        delh = (-a * d * dn) * delh;
+        d = dn;
+        h += delh;
+        const double dels = q * delh;
+        s += dels;
+        if (fabs(dels) < fabs(s) * MN_EPS) break;
+      }
+    }
+    h = a1 * h;
+    const double w = pow(0.5 * x, mu);
+    qa = w * (sqrt(1.5707963267948966 / x) / s);
+    qb = qa * (mu + x + 0.5 - h);
+    E = w * w;
+  }
+  double tk, tx;
+  if (n == 0) {
+    tk = c[MN_CA] * (qa / E);
+    tx = c[MN_CK] * ((qb / (x * E)) / x);
+  } else {
+    const double x2 = x * x;
+    for (int j = 1; j < n; ++j) {
+      const double qn = x2 * qa + (2.0 * (nu - (double)(n - j))) * qb;
+      qa = qb;
+      qb = qn;
+    }
+    tk = c[MN_CA] * qb;
+    tx = c[MN_CK] * qa;
+  }
+  if (x > 2.0) {
+    double xe = x;
+    if (x > 600.0) {
+      tk *= MN_E600;
+      tx *= MN_E600;
+      xe = x - 600.0;
+    }
+    const double ex = exp_nonpos(-xe);
+    tk *= ex;
+    tx *= ex;
+  }
+  r.k = fmin(tk, 1.0);
+  if (r.k == 0.0) return r;
+  r.kx = -tx;
+  r.dk = 2.0 * d2 * r.kx;
+  return r;
+}
+__device__ __forceinline__ double matern_nu_eval(double d2, double nu, const double* c) { return matern_nu_derivs(d2, nu, c).k; }
+
+// 1 / Gamma(1 + z) = sum_k a_k z^k (Abramowitz & Stegun 6.1.34): Gamma_2 = (1 / Gamma(1 - mu) + 1 / Gamma(1 + mu)) / 2 is its
+// even part at mu, Gamma_1 = (1 / Gamma(1 - mu) - 1 / Gamma(1 + mu)) / (2 mu) minus its odd part over mu: no cancellation at
+// small mu.  |mu| <= 1/2: 28 coefficients leave 1e-27.  Evaluated in long double, rounded once.
+void matern_nu_constants(double nu, double* out) {
+  static const long double a[28] = {
+      1.0L, 0.57721566490153286061L, -0.65587807152025388108L, -0.042002635034095235529L, 0.1665386113822914895L,
+      -0.042197734555544336748L, -0.0096219715278769735621L, 0.0072189432466630995424L, -0.0011651675918590651121L,
+      -0.00021524167411495097282L, 0.00012805028238811618615L, -0.000020134854780788238656L, -1.2504934821426706573e-6L,
+      1.1330272319816958824e-6L, -2.0563384169776071035e-7L, 6.1160951044814158179e-9L, 5.0020076444692229301e-9L,
+      -1.1812745704870201446e-9L, 1.0434267116911005105e-10L, 7.782263439905071254e-12L, -3.6968056186422057082e-12L,
+      5.100370287454475979e-13L, -2.0583260535665067832e-14L, -5.3481225394230179824e-15L, 1.2267786282382607902e-15L,
+      -1.1812593016974587695e-16L, 1.1866922547516003326e-18L, 1.4123806553180317816e-18L};
+  const int n = nu < 0.5 ? 0 : (int)floor(nu + 0.5);
+  const long double mu = n == 0 ? -(long double)nu : (long double)nu - n, m2 = mu * mu;
+  long double g1 = 0.0L, g2 = 0.0L;
+  for (int j = 13; j >= 0; --j) {
+    g2 = g2 * m2 + a[2 * j];
+    g1 = g1 * m2 - a[2 * j + 1];
+  }
+  const long double pi = 3.14159265358979323846264338327950288L;
+  const long double ca = ldexpl(1.0L, 1 - n) / tgammal((long double)nu);
+  out[MN_N] = (double)n;
+  out[MN_MU] = (double)mu;
+  out[MN_FACT] = mu == 0.0L ? 1.0 : (double)(pi * mu / sinl(pi * mu));
+  out[MN_GAM1] = (double)g1;
+  out[MN_GAM2] = (double)g2;
+  out[MN_PH] = (double)(0.5L / (g2 - mu * g1));
+  out[MN_QH] = (double)(0.5L / (g2 + mu * g1));
+  out[MN_A1] = (double)((0.5L - mu) * (0.5L + mu));
+  out[MN_CA] = (double)ca;
+  out[MN_CK] = (double)((long double)nu * ca);
+  out[MN_SQ] = (double)sqrtl(2.0L * (long double)nu);
+  out[MN_KX0] = nu > 1.0 ? (double)(-(long double)nu / (2.0L * ((long double)nu - 1.0L))) : 0.0;
+}
+
 // one call site per factor in the contractions: the two kinds behind one out-of-line routine
 __device__ __noinline__ KpDerivs newkind_derivs(int kind, double d2, double param) {
   return kind == K_COSINE ? cosine_derivs(d2) : gexp_derivs(d2, param);
+}
+// MN: whether the chains of a launch hold a MATERN_NU factor.  The Bessel routine's registers count against every kernel that
+// can call it (the assembly: 3 waves per SIMD become 2; the contractions go to scratch), so every kernel below is instantiated
+// with and without it, and chains without the kind run what they ran before it existed (docs/03_kernels.md section 3.2e).
+// With MN the three kinds sit behind one call site (nuc: MATERN_NU only)
+__device__ __noinline__ KpDerivs newkind_derivs_mn(int kind, double d2, double param, const double* nuc) {
+  if (kind == K_MATERN_NU) return matern_nu_derivs(d2, param, nuc);
+  return kind == K_COSINE ? cosine_derivs(d2) : gexp_derivs(d2, param);
+}
+bool kprod_has_matern_nu(const DevTerm* h_terms, int n) {
+  for (int t = 0; t < n; ++t)
+    if ((h_terms[t].kind & KP_KIND_MASK) == K_MATERN_NU) return true;
+  return false;
 }
 
 template <int DMAX>
@@ -110,7 +274,7 @@ __device__ __forceinline__ double kp_dot(const double (&xi)[DMAX], const double*
 // each case is straight-line code over the KP_CHUNK independent entries, as in the plain assembly
 template <int DMAX, int KIND>
 __device__ __forceinline__ void factor_chunk(double (&prod)[KP_CHUNK], const double (&xi)[DMAX], const double* sp,
-                                             double param, bool head) {
+                                             double param, bool head, const double* nuc) {
 #pragma unroll
   for (int q = 0; q < KP_CHUNK; ++q) {
     double k;
@@ -118,30 +282,35 @@ __device__ __forceinline__ void factor_chunk(double (&prod)[KP_CHUNK], const dou
     else if (KIND == K_RQ) k = rq_eval(kp_d2<DMAX>(xi, sp + q * DMAX), param);
     else if (KIND == K_COSINE) k = cosine_eval(kp_d2<DMAX>(xi, sp + q * DMAX));
     else if (KIND == K_GAMMAEXP) k = gexp_eval(kp_d2<DMAX>(xi, sp + q * DMAX), param);
+    else if (KIND == K_MATERN_NU) k = matern_nu_eval(kp_d2<DMAX>(xi, sp + q * DMAX), param, nuc);
     else k = kern_eval_t<KIND>(kp_d2<DMAX>(xi, sp + q * DMAX), param);
     prod[q] = head ? k : prod[q] * k;
   }
 }
 
-template <int DMAX>
+template <int DMAX, bool MN>
 __device__ __forceinline__ void factor_chunk_any(int kind, double (&prod)[KP_CHUNK], const double (&xi)[DMAX],
-                                                 const double* sp, double param, bool head) {
+                                                 const double* sp, double param, bool head, const double* nuc) {
+  if (MN && kind == K_MATERN_NU) {
+    factor_chunk<DMAX, K_MATERN_NU>(prod, xi, sp, param, head, nuc);
+    return;
+  }
   switch (kind) {
-    case K_SE: factor_chunk<DMAX, K_SE>(prod, xi, sp, param, head); break;
-    case K_M12: factor_chunk<DMAX, K_M12>(prod, xi, sp, param, head); break;
-    case K_M32: factor_chunk<DMAX, K_M32>(prod, xi, sp, param, head); break;
-    case K_M52: factor_chunk<DMAX, K_M52>(prod, xi, sp, param, head); break;
-    case K_WHITE: factor_chunk<DMAX, K_WHITE>(prod, xi, sp, param, head); break;
-    case K_RQ: factor_chunk<DMAX, K_RQ>(prod, xi, sp, param, head); break;
-    case K_LINEAR: factor_chunk<DMAX, K_LINEAR>(prod, xi, sp, param, head); break;
-    case K_COSINE: factor_chunk<DMAX, K_COSINE>(prod, xi, sp, param, head); break;
-    case K_GAMMAEXP: factor_chunk<DMAX, K_GAMMAEXP>(prod, xi, sp, param, head); break;
-    default: factor_chunk<DMAX, K_CONST>(prod, xi, sp, param, head); break;
+    case K_SE: factor_chunk<DMAX, K_SE>(prod, xi, sp, param, head, nuc); break;
+    case K_M12: factor_chunk<DMAX, K_M12>(prod, xi, sp, param, head, nuc); break;
+    case K_M32: factor_chunk<DMAX, K_M32>(prod, xi, sp, param, head, nuc); break;
+    case K_M52: factor_chunk<DMAX, K_M52>(prod, xi, sp, param, head, nuc); break;
+    case K_WHITE: factor_chunk<DMAX, K_WHITE>(prod, xi, sp, param, head, nuc); break;
+    case K_RQ: factor_chunk<DMAX, K_RQ>(prod, xi, sp, param, head, nuc); break;
+    case K_LINEAR: factor_chunk<DMAX, K_LINEAR>(prod, xi, sp, param, head, nuc); break;
+    case K_COSINE: factor_chunk<DMAX, K_COSINE>(prod, xi, sp, param, head, nuc); break;
+    case K_GAMMAEXP: factor_chunk<DMAX, K_GAMMAEXP>(prod, xi, sp, param, head, nuc); break;
+    default: factor_chunk<DMAX, K_CONST>(prod, xi, sp, param, head, nuc); break;
   }
 }
 
 // terms [0, nterms): whole chains (a term with KP_TIMES_PREV continues the chain of the nearest term before it without)
-template <int DMAX>
+template <int DMAX, bool MN>
 __global__ __launch_bounds__(256) void assemble_kprod_kernel(
     double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* terms, int nterms, int lower_only,
     int accumulate, int noise_kind, double sigma2, const double* noise_diag, long tile_r_first, long tile_c_first) {
@@ -207,7 +376,7 @@ __global__ __launch_bounds__(256) void assemble_kprod_kernel(
 #pragma unroll
           for (int d = 0; d < DMAX; ++d) xi[d] = (d < T.dim) ? xr[d] : 0.0;
         }
-        factor_chunk_any<DMAX>(T.kind & KP_KIND_MASK, prod, xi, &smem[(f * TILE + pbase) * DMAX], T.param, f == tm);
+        factor_chunk_any<DMAX, MN>(T.kind & KP_KIND_MASK, prod, xi, &smem[(f * TILE + pbase) * DMAX], T.param, f == tm, T.nuc);
         ++f;
         if (f >= nterms || !(terms[f].kind & KP_TIMES_PREV)) break;
       }
@@ -251,7 +420,7 @@ int kprod_group(const DevTerm* h_terms, int t, int t1, int* dmax_out) {
 }
 
 int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* d_terms, int nterms,
-                          int dmax, int lower_only, int accumulate, int noise_kind, double sigma2,
+                          int dmax, int mn, int lower_only, int accumulate, int noise_kind, double sigma2,
                           const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
                           long tile_c_cnt, hipStream_t s) {
   if (tile_r_cnt <= 0 || tile_c_cnt <= 0 || nterms <= 0) return 0;
@@ -263,8 +432,12 @@ int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc
 #define SGP_KP(DM)                                                                                                     \
   do {                                                                                                                 \
     const size_t lds = (size_t)nterms * TILE * DM * sizeof(double);                                                    \
-    hipLaunchKernelGGL(assemble_kprod_kernel<DM>, grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms,         \
-                       lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first);          \
+    if (mn)                                                                                                            \
+      hipLaunchKernelGGL((assemble_kprod_kernel<DM, true>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms, \
+                         lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first);        \
+    else                                                                                                               \
+      hipLaunchKernelGGL((assemble_kprod_kernel<DM, false>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms,      \
+                         nterms, lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first); \
   } while (0)
   if (dmax <= 1) SGP_KP(1);
   else if (dmax <= 2) SGP_KP(2);
@@ -277,6 +450,7 @@ int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc
 }
 
 // ---- the diagonal: out[i] (+)= the sum of the chains of one launch group, in the assembly's operation order ------------
+template <bool MN>
 __device__ __forceinline__ double kp_factor_diag(const DevTerm& T, long i) {
   const int kind = T.kind & KP_KIND_MASK;
   const double* a = T.xr + i * T.ldr;
@@ -294,9 +468,11 @@ __device__ __forceinline__ double kp_factor_diag(const DevTerm& T, long i) {
   if (kind == K_RQ) return rq_eval(d2, T.param);
   if (kind == K_COSINE) return cosine_eval(d2);
   if (kind == K_GAMMAEXP) return gexp_eval(d2, T.param);
+  if (MN && kind == K_MATERN_NU) return matern_nu_eval(d2, T.param, T.nuc);
   return kern_eval(kind, d2, T.param);
 }
 
+template <bool MN>
 __global__ void diag_kprod_kernel(double* out, long n, const DevTerm* terms, int nterms, int accumulate) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -306,11 +482,11 @@ __global__ void diag_kprod_kernel(double* out, long n, const DevTerm* terms, int
     const DevTerm H = terms[tm];
     double cw = H.coef * (H.rs ? H.rs[i] : 1.0);
     if (H.cs) cw = cw * H.cs[i];
-    double prod = kp_factor_diag(H, i);
+    double prod = kp_factor_diag<MN>(H, i);
     int f = tm + 1;
     while (f < nterms && (terms[f].kind & KP_TIMES_PREV)) {
       const DevTerm T = terms[f];
-      prod = prod * kp_factor_diag(T, i);
+      prod = prod * kp_factor_diag<MN>(T, i);
       ++f;
     }
     acc = fma(prod, cw, acc);
@@ -319,19 +495,23 @@ __global__ void diag_kprod_kernel(double* out, long n, const DevTerm* terms, int
   out[i] = accumulate ? acc + out[i] : acc;
 }
 
-int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int accumulate, hipStream_t s) {
+int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int mn, int accumulate, hipStream_t s) {
   if (n <= 0 || nterms <= 0) return 0;
-  hipLaunchKernelGGL(diag_kprod_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
-                     accumulate);
+  if (mn)
+    hipLaunchKernelGGL(diag_kprod_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
+                       accumulate);
+  else
+    hipLaunchKernelGGL(diag_kprod_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
+                       accumulate);
   SGP_HIP(hipGetLastError());
   return 0;
 }
 
 // ---- gradient contraction of ONE chain --------------------------------------------------------------------------------
 // k, d k / d g (both inputs scaled by g, at g = 1) and d k / d param of one factor
-template <int DMAX>
+template <int DMAX, bool MN>
 __device__ __forceinline__ void kp_factor_grad(int kind, double param, const double* xr, const double* sp, double& k,
-                                               double& dk, double& dp) {
+                                               double& dk, double& dp, const DevTerm* term) {
   if (kind == K_LINEAR) {
     double s = 0.0;
 #pragma unroll
@@ -358,8 +538,9 @@ __device__ __forceinline__ void kp_factor_grad(int kind, double param, const dou
     dp = k == 0.0 ? 0.0 : k * (r - l);
     return;
   }
-  if (kind == K_COSINE || kind == K_GAMMAEXP) {
-    const KpDerivs r = newkind_derivs(kind, d2, param);
+  if (kind == K_COSINE || kind == K_GAMMAEXP || (MN && kind == K_MATERN_NU)) {
+    const KpDerivs r = MN ? newkind_derivs_mn(kind, d2, param, kind == K_MATERN_NU ? term->nuc : nullptr)
+                          : newkind_derivs(kind, d2, param);
     k = r.k;
     dk = r.dk;
     dp = r.dp;
@@ -369,7 +550,7 @@ __device__ __forceinline__ void kp_factor_grad(int kind, double param, const dou
   dp = kind == G_CONST ? 1.0 : 0.0;
 }
 
-template <int DMAX>
+template <int DMAX, bool MN>
 __global__ __launch_bounds__(256) void grad_kprod_kernel(const double* Kinv, long ldk, const double* alpha, long r0, long nr,
                                                          long c0, long nc, const DevTerm* terms, int nf,
                                                          long tile_r_first, long tile_c_first,
@@ -446,7 +627,7 @@ __global__ __launch_bounds__(256) void grad_kprod_kernel(const double* Kinv, lon
       for (int f = 0; f < TMAX; ++f) {
         k[f] = 1.0;
         dk[f] = dp[f] = 0.0;
-        if (f < nf) kp_factor_grad<DMAX>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], dk[f], dp[f]);
+        if (f < nf) kp_factor_grad<DMAX, MN>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], dk[f], dp[f], terms + f);
         pre[f + 1] = pre[f] * k[f];
       }
       const double w = g * rsv * scs[p];
@@ -514,7 +695,7 @@ __global__ __launch_bounds__(256) void grad_kprod_reduce_kernel(const double* pa
   }
 }
 
-template <int DMAX>
+template <int DMAX, bool MN>
 static int launch_grad_kprod_t(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
                                const DevTerm* d_terms, int nf, long trf, long tcf, long trc, long tcc, double* partials,
                                hipStream_t s) {
@@ -524,8 +705,8 @@ static int launch_grad_kprod_t(const double* Kinv, long ldk, const double* alpha
     return -1;
   }
   const size_t lds = (size_t)(TMAX * TILE * DMAX + TILE) * sizeof(double);
-  SGP_LDS_ATTR_ONCE(grad_kprod_kernel<DMAX>, lds);
-  hipLaunchKernelGGL(grad_kprod_kernel<DMAX>, dim3((unsigned)trc, (unsigned)tcc), dim3(256), lds, s, Kinv, ldk, alpha, r0,
+  SGP_LDS_ATTR_ONCE((grad_kprod_kernel<DMAX, MN>), lds);
+  hipLaunchKernelGGL((grad_kprod_kernel<DMAX, MN>), dim3((unsigned)trc, (unsigned)tcc), dim3(256), lds, s, Kinv, ldk, alpha, r0,
                      nr, c0, nc, d_terms, nf, trf, tcf, partials);
   SGP_HIP(hipGetLastError());
   return 0;
@@ -533,15 +714,17 @@ static int launch_grad_kprod_t(const double* Kinv, long ldk, const double* alpha
 
 // partials: trc x tcc x 24 doubles.  out_coef / out_scale / out_param: the chain's first entry (nf each; any may be NULL)
 int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
-                      const DevTerm* d_terms, int nf, int dmax, long trf, long tcf, long trc, long tcc, double* partials,
-                      double* out_coef, double* out_scale, double* out_param, hipStream_t s) {
+                      const DevTerm* d_terms, int nf, int dmax, int mn, long trf, long tcf, long trc, long tcc,
+                      double* partials, double* out_coef, double* out_scale, double* out_param, hipStream_t s) {
   if (nf <= 0 || trc <= 0 || tcc <= 0) return 0;
   if (nf > KP_MAXF || dmax > 16) {
     set_error("grad: a product chain beyond the limits of include/sthenomi_kprod.h");
     return -1;
   }
   int rc;
-#define SGP_KG(DM) rc = launch_grad_kprod_t<DM>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s)
+#define SGP_KG(DM)                                                                                                     \
+  rc = mn ? launch_grad_kprod_t<DM, true>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s)  \
+          : launch_grad_kprod_t<DM, false>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s)
   if (dmax <= 1) SGP_KG(1);
   else if (dmax <= 2) SGP_KG(2);
   else if (dmax <= 4) SGP_KG(4);
@@ -558,15 +741,15 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
 
 // ---- input-point and scale gradients of ONE chain ---------------------------------------------------------------------
 // k and d k / d x of one factor from its row point and a column point: a distance kind has d k / d x = 2 kx (x - x') with
-// kx = kappa'(d2) (kern_grad.h: kern_val_dd2; COSINE / GAMMAEXP: cosine_derivs / gexp_derivs above; RQ: -1/2 (1 + u)^(-alpha - 1)
+// kx = kappa'(d2) (kern_grad.h: kern_val_dd2; COSINE / GAMMAEXP / MATERN_NU: their _derivs above; RQ: -1/2 (1 + u)^(-alpha - 1)
 // = -1/2 exp(-(alpha + 1) log1p(u)), an exact 0 -- never NaN -- where d2 overflowed, finite where only u did: rq_log1p_u),
 // LINEAR has d k / d x = x' and kx stands for nothing.
-// NK: whether the chain holds a COSINE / GAMMAEXP factor.  The call of their out-of-line routine costs the row-side kernel
+// NK: 1 if the chain holds a COSINE / GAMMAEXP factor, 2 if it holds a MATERN_NU factor (and possibly those), else 0.  The call of their out-of-line routine costs the row-side kernel
 // below registers at every factor (DMAX = 1: 2 waves per SIMD become 1), so chains of the older kinds run an instantiation
 // without it
-template <int DMAX, bool NK>
+template <int DMAX, int NK>
 __device__ __forceinline__ void kp_factor_dx(int kind, double param, const double* xr, const double* sp, double& k,
-                                             double& kx) {
+                                             double& kx, const double* nuc) {
   if (kind == K_LINEAR) {
     double s = 0.0;
 #pragma unroll
@@ -588,8 +771,8 @@ __device__ __forceinline__ void kp_factor_dx(int kind, double param, const doubl
     kx = -0.5 * exp(-(param + 1.0) * l);
     return;
   }
-  if (NK && (kind == K_COSINE || kind == K_GAMMAEXP)) {
-    const KpDerivs r = newkind_derivs(kind, d2, param);
+  if (NK && (kind == K_COSINE || kind == K_GAMMAEXP || (NK == 2 && kind == K_MATERN_NU))) {
+    const KpDerivs r = NK == 2 ? newkind_derivs_mn(kind, d2, param, nuc) : newkind_derivs(kind, d2, param);
     k = r.k;
     kx = r.kx;
     return;
@@ -610,7 +793,7 @@ struct KpChainArgs {
   double* gx[KP_MAXF];   // gradient of factor f's row input (dim x nr, packed) or NULL
 };
 
-template <int DMAX, bool NK>
+template <int DMAX, int NK>
 __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm, long sr, long sc, const double* alpha,
                                                                 long r0, long nr, long c0, long nc, KpChainArgs C, int nf,
                                                                 double scale, double* gsv /* nr, or NULL */) {
@@ -673,7 +856,8 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
         for (int f = 0; f < TMAX; ++f) {
           k[f] = 1.0;
           kx[f] = 0.0;
-          if (f < nf) kp_factor_dx<DMAX, NK>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], kx[f]);
+          if (f < nf) kp_factor_dx<DMAX, NK>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], kx[f],
+                                              NK == 2 ? C.t[f].nuc : nullptr);
           pre[f + 1] = pre[f] * k[f];
         }
         const double gcs = g * scs[p];
@@ -721,7 +905,7 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
   }
 }
 
-template <int DMAX, bool NK>
+template <int DMAX, int NK>
 static int launch_grad_kprod_inputs_t(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0,
                                       long nc, const KpChainArgs& C, int nf, double scale, double* gsv, hipStream_t s) {
   constexpr int TMAX = (64 / DMAX < KP_MAXF) ? 64 / DMAX : KP_MAXF;
@@ -759,14 +943,15 @@ int launch_grad_kprod_inputs(const double* Gm, long sr, long sc, const double* a
     }
   }
   int rc;
-  bool nk = false;
+  int nk = 0;
   for (int f = 0; f < nf; ++f) {
     const int kind = h_terms[f].kind & KP_KIND_MASK;
-    nk = nk || kind == K_COSINE || kind == K_GAMMAEXP;
+    nk = std::max(nk, kind == K_MATERN_NU ? 2 : (kind == K_COSINE || kind == K_GAMMAEXP) ? 1 : 0);
   }
 #define SGP_KI(DM)                                                                                                     \
-  rc = nk ? launch_grad_kprod_inputs_t<DM, true>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)              \
-          : launch_grad_kprod_inputs_t<DM, false>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)
+  rc = nk == 2 ? launch_grad_kprod_inputs_t<DM, 2>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
+       : nk    ? launch_grad_kprod_inputs_t<DM, 1>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
+               : launch_grad_kprod_inputs_t<DM, 0>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)
   if (dmax <= 1) SGP_KI(1);
   else if (dmax <= 2) SGP_KI(2);
   else if (dmax <= 4) SGP_KI(4);
@@ -788,6 +973,7 @@ struct KpDiagArgs {
   double* gxc[KP_MAXF];
 };
 
+template <bool MN>
 __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, long n, KpDiagArgs C, int nf, double* out_coef,
                                                               double* out_scale, double* out_param, double* out_rs,
                                                               double* out_cs) {
@@ -827,8 +1013,9 @@ __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, l
             dk[f] = -(2.0 * T.param) * r * k[f];
             dp[f] = k[f] == 0.0 ? 0.0 : k[f] * (r - l);
             kx[f] = -0.5 * exp(-(T.param + 1.0) * l);
-          } else if (kind == K_COSINE || kind == K_GAMMAEXP) {
-            const KpDerivs r = newkind_derivs(kind, d2, T.param);
+          } else if (kind == K_COSINE || kind == K_GAMMAEXP || (MN && kind == K_MATERN_NU)) {
+            const KpDerivs r = MN ? newkind_derivs_mn(kind, d2, T.param, kind == K_MATERN_NU ? T.nuc : nullptr)
+                                  : newkind_derivs(kind, d2, T.param);
             k[f] = r.k;
             dk[f] = r.dk;
             kx[f] = r.kx;
@@ -933,8 +1120,12 @@ int launch_diag_grad_kprod(const double* w, long n, const DevTerm* h_terms, int 
     C.gxr[f] = (f < nf && gxr) ? gxr[f] : nullptr;
     C.gxc[f] = (f < nf && gxc) ? gxc[f] : nullptr;
   }
-  hipLaunchKernelGGL(diag_grad_kprod_kernel, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param, out_rs,
-                     out_cs);
+  if (kprod_has_matern_nu(h_terms, nf))
+    hipLaunchKernelGGL(diag_grad_kprod_kernel<true>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
+                       out_rs, out_cs);
+  else
+    hipLaunchKernelGGL(diag_grad_kprod_kernel<false>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
+                       out_rs, out_cs);
   SGP_HIP(hipGetLastError());
   return 0;
 }

@@ -480,7 +480,8 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
     sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
     index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
-    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, gamma of GammaExponential, c of Linear / Constant).  inputs / scales of such
+    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, gamma of GammaExponential, c of Linear / Constant; 0 for nu
+    of GeneralMaternKernel, which is held fixed).  inputs / scales of such
     models come from logpdf_and_gradient_param."""
     if not _is_prior(fx.f):
         raise NotImplementedError("gradients are implemented for prior Stheno processes")

@@ -197,12 +197,26 @@ class WhiteKernel(_Simple):
 
 def MaternKernel(nu=1.5):
     """KernelFunctions' MaternKernel(nu) at the three half-integer orders with a closed form: the existing kinds.  Any other
-    nu needs a Bessel-K routine on the device and is not built."""
+    nu is GeneralMaternKernel(nu), which evaluates a Bessel function per entry on the product path."""
     kinds = {0.5: Matern12Kernel, 1.5: Matern32Kernel, 2.5: Matern52Kernel}
     if float(nu) not in kinds:
-        raise NotImplementedError(f"MaternKernel(nu = {nu!r}): the general-nu Matern kernel is not built; nu must be "
-                                  "1/2, 3/2 or 5/2")
+        raise NotImplementedError(f"MaternKernel(nu = {nu!r}): this constructor maps to the closed-form Matern kinds, nu must "
+                                  "be 1/2, 3/2 or 5/2; GeneralMaternKernel(nu) takes any nu in (0, 32]")
     return kinds[float(nu)]()
+
+
+class GeneralMaternKernel(Kernel):
+    """2^(1-nu) / Gamma(nu) x^nu K_nu(x), x = sqrt(2 nu) d, d the Euclidean distance, nu in (0, 32] (KernelFunctions
+    MaternKernel(nu), scikit-learn Matern(nu=nu)); evaluated on the product path (include/sthenomi_kprod.h: SGP_MATERN_NU).
+    nu is held fixed: gradient records carry d_param = 0 for it."""
+
+    def __init__(self, nu=1.5):
+        self.nu = float(nu)
+        if not 0.0 < self.nu <= _lib.MATERN_NU_MAX:
+            raise ValueError(f"GeneralMaternKernel: nu must be finite and in (0, {_lib.MATERN_NU_MAX:g}]")
+
+    def leaf_terms(self):
+        return [(_lib.MATERN_NU, 1.0, self.nu, ())]
 
 
 class CosineKernel(_Simple):

@@ -29,6 +29,8 @@ KPROD_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod_grad.so")
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
 RQ, LINEAR = 6, 7                  # evaluated by the product-chain path only (include/sthenomi_kprod.h)
 COSINE, GAMMAEXP = 16, 17          # the same path (8 .. 15 are no kinds)
+MATERN_NU = 20                     # general-nu Matern, the same path (18, 19 are no kinds); nu in (0, MATERN_NU_MAX]
+MATERN_NU_MAX = 32.0
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
 KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain

@@ -10,7 +10,10 @@ Model: the scikit-learn golden's kernel (tests/golden/make_kprod_golden.py),
           constant stand in for the two kinds the plain path does not have), multiplied and added on the host.
 And logpdf + gradient over logpdf at N = 4096 for the model (sgp_logpdf_grad_param) against the same ratio for a four-term
 KernelSum (sgp_logpdf_grad), same run.  Medians of repeats after a warm-up.
-usage: python tools/gpu_kprod_time.py [--out FILE] [--quick]      -> JSON on stdout (and in FILE)"""
+--matern-nu: instead, the general-nu Matern kind (SGP_MATERN_NU: a Bessel function per entry) -- the assembly of
+GeneralMaternKernel(1.25) and GeneralMaternKernel(25) at N = 4096 and 16 384, D = 8, against plain Matern-5/2 and
+GammaExponential(1.3) in the same process, and the assembly's share of logpdf at both sizes.
+usage: python tools/gpu_kprod_time.py [--out FILE] [--quick] [--matern-nu]      -> JSON on stdout (and in FILE)"""
 import ctypes as C
 import hashlib
 import json
@@ -33,6 +36,7 @@ if "--out" in argv:
     out_path = argv[i + 1]
     del argv[i:i + 2]
 QUICK = "--quick" in argv
+MATERN_NU = "--matern-nu" in argv
 N_K, N_G = (2048, 1024) if QUICK else (16384, 4096)
 
 
@@ -85,7 +89,42 @@ def assemble_ms(ctx, spec, reps=5):
     return float(np.median(got))
 
 
+def finish(res):
+    res["build"] = dict(libsthenomi_sha16=hashlib.sha256(open(L.LIB_PATH, "rb").read()).hexdigest()[:16],
+                        kprod_hip_sha16=hashlib.sha256(open(os.path.join(ROOT, "stheno.jl_amd", "csrc", "kprod.hip"), "rb").read()).hexdigest()[:16])
+    out = json.dumps(res, indent=1)
+    print(out)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(out + "\n")
+
+
+def main_matern_nu():
+    """one term each, lengthscale 1 on points of unit variance per coordinate / sqrt(D): x = sqrt(2 nu) d spreads over both
+    branches of the routine (Temme's series up to x = 2, the continued fraction beyond)"""
+    ctx = L.default_context()
+    rng = np.random.default_rng(0)
+    kernels = (("GeneralMaternKernel(1.25)", P.GeneralMaternKernel(1.25)), ("GeneralMaternKernel(25)", P.GeneralMaternKernel(25.0)),
+               ("Matern52Kernel (plain assembly)", P.Matern52Kernel()), ("GammaExponentialKernel(1.3)", P.GammaExponentialKernel(1.3)))
+    res = dict(shape=dict(N=[1024, 2048] if QUICK else [4096, 16384], D=8), runs={})
+    for N in res["shape"]["N"]:
+        X = P.ColVecs(np.asfortranarray(rng.standard_normal((8, N)) / np.sqrt(8.0)))
+        y = rng.standard_normal(N)
+        for label, k in kernels:
+            spec = P.build_spec(atom(k), X)[0]
+            fx = atom(k)(X, 0.1)
+            a_ms, lp_s = assemble_ms(ctx, spec), med(lambda: P.logpdf(fx, y), reps=3)
+            res["runs"][f"{label}, N = {N}"] = dict(assemble_ms=a_ms, logpdf_s=lp_s, assembly_share_of_logpdf=a_ms / (1e3 * lp_s))
+        for nu in ("1.25", "25"):
+            a = res["runs"][f"GeneralMaternKernel({nu}), N = {N}"]["assemble_ms"]
+            res[f"assembly ratio nu = {nu} / Matern52, N = {N}"] = a / res["runs"][f"Matern52Kernel (plain assembly), N = {N}"]["assemble_ms"]
+            res[f"assembly ratio nu = {nu} / GammaExponential, N = {N}"] = a / res["runs"][f"GammaExponentialKernel(1.3), N = {N}"]["assemble_ms"]
+    finish(res)
+
+
 def main():
+    if MATERN_NU:
+        return main_matern_nu()
     ctx = L.default_context()
     rng = np.random.default_rng(0)
     x = np.sort(rng.uniform(-3.0, 3.0, N_K))
@@ -130,13 +169,7 @@ def main():
         t_lp = med(lambda: P.logpdf(fx, yg), reps=5)
         t_g = med(lambda: P.logpdf_and_gradient(fx, yg), reps=5)
         res["runs"][f"logpdf + gradient / logpdf, {label}, N = {N_G}"] = dict(logpdf_s=t_lp, logpdf_and_gradient_s=t_g, ratio=t_g / t_lp)
-    res["build"] = dict(libsthenomi_sha16=hashlib.sha256(open(L.LIB_PATH, "rb").read()).hexdigest()[:16],
-                        kprod_hip_sha16=hashlib.sha256(open(os.path.join(ROOT, "stheno.jl_amd", "csrc", "kprod.hip"), "rb").read()).hexdigest()[:16])
-    out = json.dumps(res, indent=1)
-    print(out)
-    if out_path:
-        with open(out_path, "w") as fh:
-            fh.write(out + "\n")
+    finish(res)
 
 
 if __name__ == "__main__":
