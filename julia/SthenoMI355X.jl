@@ -22,6 +22,8 @@ const LIB_POOL = get(ENV, "STHENOMI_POOL_LIB", joinpath(dirname(LIB), "libstheno
 const LIB_EXTEND = get(ENV, "STHENOMI_EXTEND_LIB", joinpath(dirname(LIB), "libsthenomi_extend.so"))
 # include/sthenomi_postfx.h (sgp_posterior_rand / _logpdf and their sparse forms: rand / logpdf of f_post(x*, Σ*)): likewise
 const LIB_POSTFX = get(ENV, "STHENOMI_POSTFX_LIB", joinpath(dirname(LIB), "libsthenomi_postfx.so"))
+# include/sthenomi_vfe_update.h (sgp_sparse_posterior_update / _count: new data into a kept sparse posterior): likewise
+const LIB_VFE_UPDATE = get(ENV, "STHENOMI_VFE_UPDATE_LIB", joinpath(dirname(LIB), "libsthenomi_vfe_update.so"))
 # include/sthenomi_kprod.h (sgp_logpdf_grad_param: + d / d kernel parameters, through product chains and plain terms): likewise
 const LIB_KPROD = get(ENV, "STHENOMI_KPROD_LIB", joinpath(dirname(LIB), "libsthenomi_kprod.so"))
 const SthenoFGP = FiniteGP{<:Union{GPPP,SthenoAbstractGP}}
@@ -557,20 +559,78 @@ AbstractGPs.marginals(fx::SthenoFGP) = ((m, v) = mean_and_var(fx); AbstractGPs.N
 # ---- posterior(VFE(fz), fx, y) (src/gp/sparse_finite_gp.jl:60-62) ------------------------------------------
 # Stheno's SparseFiniteGP methods (sparse_finite_gp.jl:52-62) call elbo(VFE(f.finducing), f.fobs, y) and
 # posterior(VFE(f.finducing), f.fobs, y): both land on the overloads of this module, nothing to add.
+# fz and the observation batches (x, Σy, y) are kept by reference: update_posterior(p, fz_new) re-conditions them, and an
+# object whose handle update_posterior handed to its successor rebuilds one of its own from them the next time it is asked
+# something (handle!), as the Python mirror does.  created: the leading batches that went through the handle's create call
+# (the later ones through updates); trace0 = Σ var(f, xₙ) / s²ₙ over them is the term the device cannot know
+# (sgp_sparse_posterior_create takes no var_x; include/sthenomi_vfe_update.h: elbo_out) -- NaN until an update asks for it.
 mutable struct MI355XSparsePosterior{Tf,Tz} <: AbstractGPs.AbstractGP
-    prior::Tf; z::Tz; handle::Ptr{Cvoid}
+    prior::Tf; z::Tz; handle::Ptr{Cvoid}; fz::Any; batches::Vector{Any}; created::Int; trace0::Float64; elbo::Float64
 end
-function posterior(v::VFE, fx::SthenoFGP, y::AbstractVector{<:Real})
-    fz = v.fz; @assert fz.f === fx.f
+function sparse_create(fz, fx::SthenoFGP, yd::Vector{Float64})
+    @assert fz.f === fx.f
     zz = build_spec(fz.f, fz.x); xz = build_spec(fx.f, fx.x, fz.f, fz.x)
     m = collect(Float64, mean(fx.f, fx.x)); kx, nx = noise_args(fx.Σy); kz, nz = noise_args(fz.Σy)
-    yd = collect(Float64, y); h = Ref{Ptr{Cvoid}}(C_NULL)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve zz xz m nx nz yd check(ccall((:sgp_sparse_posterior_create, LIB), Cint,
         (Ptr{Cvoid}, Ref{CSpec}, Ref{CSpec}, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
          Ptr{Ptr{Cvoid}}), ctx(), zz.c, xz.c, m, kx, nx, kz, nz, yd, h))
-    post = MI355XSparsePosterior(fx.f, fz.x, h[])
+    return h[]
+end
+function sparse_posterior_on(fz, prior, batches::Vector{Any})      # every batch goes through the handle's create call
+    xx = length(batches) == 1 ? batches[1][1] : reduce(stack_inputs, (b[1] for b in batches))
+    Σy = length(batches) == 1 ? batches[1][2] : Diagonal(reduce(vcat, (collect(Float64, diag(b[2])) for b in batches)))
+    h = sparse_create(fz, FiniteGP(prior, xx, Σy), reduce(vcat, (b[3] for b in batches)))
+    post = MI355XSparsePosterior(prior, fz.x, h, fz, batches, length(batches), NaN, NaN)
     finalizer(p -> ccall((:sgp_sparse_posterior_destroy, LIB), Cint, (Ptr{Cvoid},), p.handle), post)
     return post
+end
+posterior(v::VFE, fx::SthenoFGP, y::AbstractVector{<:Real}) =
+    sparse_posterior_on(v.fz, fx.f, Any[(fx.x, fx.Σy, collect(Float64, y))])
+function handle!(p::MI355XSparsePosterior)                         # the factors in HBM, rebuilt from the kept batches if they moved on
+    if p.handle == C_NULL
+        q = sparse_posterior_on(p.fz, p.prior, p.batches)
+        p.handle = q.handle; q.handle = C_NULL                     # (sgp_sparse_posterior_destroy(NULL) is a no-op)
+        p.created = length(p.batches); p.trace0 = NaN
+    end
+    return p.handle
+end
+function create_trace!(p::MI355XSparsePosterior)
+    if isnan(p.trace0)
+        p.trace0 = sum(sum(var(p.prior, b[1]) ./ diag(b[2])) for b in p.batches[1:p.created])
+    end
+    return p.trace0
+end
+# update_posterior(f_post_approx, fx2, y2) [AbstractGPs, VFE]: the new rows join the sums the posterior keeps and A A' + I is
+# factored afresh (sgp_sparse_posterior_update: O(n M² + M³ / 3), whatever came before); the inducing points stay.  The
+# returned object takes the handle over and carries `elbo`, the ELBO of all the data; `p` stays usable (handle!).
+# Σy of the batch: a ScalMat or a Diagonal.
+function AbstractGPs.update_posterior(p::MI355XSparsePosterior, fx::SthenoFGP, y::AbstractVector{<:Real})
+    @assert fx.f === p.prior
+    kind, nz = noise_args(fx.Σy)
+    @assert kind != 2 "elbo needs isotropic or diagonal observation noise"
+    xz = build_spec(fx.f, fx.x, p.prior, p.z)
+    varx = collect(Float64, var(fx.f, fx.x)); m = collect(Float64, mean(fx.f, fx.x)); yd = collect(Float64, y); out = zeros(1)
+    h = handle!(p); t0 = create_trace!(p)
+    GC.@preserve xz varx m nz yd out check(
+        @ccall LIB_VFE_UPDATE.sgp_sparse_posterior_update(h::Ptr{Cvoid}, xz.c::Ref{CSpec}, varx::Ptr{Float64},
+                                                          m::Ptr{Float64}, kind::Cint, nz::Ptr{Float64}, yd::Ptr{Float64},
+                                                          out::Ptr{Float64})::Cint)
+    post = MI355XSparsePosterior(p.prior, p.z, h, p.fz, vcat(p.batches, Any[(fx.x, fx.Σy, yd)]), p.created, t0, out[1] - t0 / 2)
+    p.handle = C_NULL                                              # the new object owns the factors
+    finalizer(q -> ccall((:sgp_sparse_posterior_destroy, LIB), Cint, (Ptr{Cvoid},), q.handle), post)
+    return post
+end
+# update_posterior(f_post_approx, fz_new): the data already seen, conditioned on new inducing points -- posterior(VFE(fz_new), ...)
+# on the stacked kept batches
+function AbstractGPs.update_posterior(p::MI355XSparsePosterior, fz_new::SthenoFGP)
+    @assert fz_new.f === p.prior
+    return sparse_posterior_on(fz_new, p.prior, copy(p.batches))
+end
+function absorbed(p::MI355XSparsePosterior)                        # data points absorbed so far
+    n = Ref{Int64}(0)
+    check(@ccall LIB_VFE_UPDATE.sgp_sparse_posterior_count(handle!(p)::Ptr{Cvoid}, n::Ref{Int64})::Cint)
+    return n[]
 end
 function predict(p::MI355XSparsePosterior, xs; want_cov = false)
     cr = build_spec(p.prior, xs, p.prior, p.z); ss = build_spec(p.prior, xs)
@@ -578,7 +638,7 @@ function predict(p::MI355XSparsePosterior, xs; want_cov = false)
     μ = zeros(n); v = zeros(n); C = want_cov ? zeros(n, n) : zeros(0, 0)
     GC.@preserve cr ss ms μ v C check(ccall((:sgp_sparse_posterior_predict, LIB), Cint,
         (Ptr{Cvoid}, Ref{CSpec}, Ref{CSpec}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
-        p.handle, cr.c, ss.c, ms, μ, v, want_cov ? pointer(C) : C_NULL, max(n, 1)))
+        handle!(p), cr.c, ss.c, ms, μ, v, want_cov ? pointer(C) : C_NULL, max(n, 1)))
     return μ, v, C
 end
 AbstractGPs.mean(p::MI355XSparsePosterior, xs::AbstractVector) = predict(p, xs)[1]
@@ -605,7 +665,7 @@ end
 function logpdf(fx::SparsePostFGP, Y::AbstractMatrix{<:Real})
     cr, ss, ms = postfx_specs(fx.f, fx.x); kind, nz = noise_args(fx.Σy); Yd = Matrix{Float64}(Y); out = zeros(size(Yd, 2))
     GC.@preserve cr ss ms nz Yd out check(
-        @ccall LIB_POSTFX.sgp_sparse_posterior_logpdf(fx.f.handle::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
+        @ccall LIB_POSTFX.sgp_sparse_posterior_logpdf(handle!(fx.f)::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
                                                       ms::Ptr{Float64}, kind::Cint, nz::Ptr{Float64}, Yd::Ptr{Float64},
                                                       size(Yd, 1)::Int64, size(Yd, 2)::Int64, out::Ptr{Float64})::Cint)
     return out
@@ -622,7 +682,7 @@ end
 function rand_with(fx::SparsePostFGP, Z::Matrix{Float64})
     cr, ss, ms = postfx_specs(fx.f, fx.x); kind, nz = noise_args(fx.Σy); out = similar(Z)
     GC.@preserve cr ss ms nz Z out check(
-        @ccall LIB_POSTFX.sgp_sparse_posterior_rand(fx.f.handle::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
+        @ccall LIB_POSTFX.sgp_sparse_posterior_rand(handle!(fx.f)::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
                                                     ms::Ptr{Float64}, kind::Cint, nz::Ptr{Float64}, Z::Ptr{Float64},
                                                     size(Z, 1)::Int64, size(Z, 2)::Int64, out::Ptr{Float64},
                                                     size(out, 1)::Int64)::Cint)

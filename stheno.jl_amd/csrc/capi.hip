@@ -3052,6 +3052,7 @@ extern "C" int sgp_sparse_posterior_destroy(sgp_sparse_post* p) {
   if (p->d_wz) hipFree(p->d_wz);
   if (p->dG) hipFree(p->dG);
   if (p->d_wg) hipFree(p->d_wg);
+  if (p->d_sums) hipFree(p->d_sums);
   delete p;
   return 0;
 }
@@ -3085,38 +3086,126 @@ static void vfe_chunking(long* chunk_rows, long* above) {
 //   scal 8: [0] sum log s2_n, [1] delta' delta, [2] sum var_n / s2_n, [3] |A|_F^2
 static long vfe_part_len(long m_pad) { return (m_pad + TILE) * m_pad + m_pad + 8; }
 
+// dst[i] += src[i], i < n (n <= 8): the scalars of an appended batch join the kept ones
+__global__ void accum_n_kernel(double* dst, const double* src, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] += src[threadIdx.x];
+}
+
+// The row half of vfe_rows_partial: the rows of `dx` (with their y, mean, var, noise) are turned into sums against a GIVEN
+// factor Lz.  begin() uploads the rows' vectors and leaves their scalars, chunks() runs the row-chunk loop.
+// append == 0: d_part is cleared and written (the first chunk overwrites, the later ones accumulate).
+// append != 0: d_part holds the sums of earlier data (sgp_sparse_post::d_sums) and every chunk accumulates onto them from
+// the first one on; the batch's four scalars are formed on their own and added to the kept ones.
+struct VfeRows {
+  sgp_ctx* ctx;
+  const sgp_dspec* dx;
+  long M, N, m_pad, n_rows, ldg;
+  double *dG, *d_dots, *d_sc;
+  int append;
+  DevBuf dR, dAt, dPart, dy, dmean, dvar, ddelta, drsig, sq, dCs, sc_new;
+  NoiseDev ndx;
+  VfeRows(sgp_ctx* c, const sgp_dspec* x, long M_, double* d_part, int append_)
+      : ctx(c), dx(x), M(M_), N(x->N), m_pad(rup(M_, TILE)), n_rows(rup(x->N, TILE)), ldg(rup(M_, TILE) + TILE),
+        dG(d_part), d_dots(d_part + (rup(M_, TILE) + TILE) * rup(M_, TILE)), d_sc(d_dots + rup(M_, TILE)), append(append_) {}
+  int upload(const double* var_x, const double* mean_x, int noise_kind, const double* noise_x, const double* y) {
+    CHECK_RC(dy.upload(y, N));
+    if (mean_x) CHECK_RC(dmean.upload(mean_x, N));
+    if (var_x) CHECK_RC(dvar.upload(var_x, N));
+    CHECK_RC(upload_noise(ndx, noise_kind, noise_x, N));
+    return 0;
+  }
+  int alloc_rows() {
+    CHECK_RC(ddelta.alloc(n_rows));
+    CHECK_RC(drsig.alloc(n_rows));
+    CHECK_RC(sq.alloc(m_pad));
+    if (append) CHECK_RC(sc_new.alloc(8));
+    return 0;
+  }
+  int scalars(bool has_mean, bool has_var) {
+    hipStream_t s = ctx->stream;
+    if (!append) SGP_HIP(hipMemsetAsync(dG, 0, sizeof(double) * vfe_part_len(m_pad), s));
+    SGP_HIP(hipMemsetAsync(sq.p, 0, sizeof(double) * m_pad, s));
+    SGP_HIP(hipMemsetAsync(ddelta.p, 0, sizeof(double) * n_rows, s));
+    SGP_HIP(hipMemsetAsync(drsig.p, 0, sizeof(double) * n_rows, s));
+    CHECK_RC(launch_elbo_scalars(ctx, dy.p, has_mean ? dmean.p : nullptr, has_var ? dvar.p : nullptr, ndx.kind, ndx.sigma2,
+                                 ndx.diag.p, N, ddelta.p, drsig.p, append ? sc_new.p : d_sc, s));
+    return 0;
+  }
+  int chunks(const double* dLz, const double* d_wz, StageTimer& tm) {
+    hipStream_t s = ctx->stream;
+    long CH, ch_above;
+    vfe_chunking(&CH, &ch_above);
+    CH = std::min(CH, n_rows);
+    const int nsplit = 8;  // one K slice per XCD (gemm_nt.hip, klo == 3)
+    const long stride = ldg * m_pad;
+    CHECK_RC(dR.alloc((size_t)CH * m_pad));
+    // (Round 4 also built "two chunks in flight" -- the Gram product of chunk c on the second stream while chunk c + 1 is assembled
+    // and solved on the first; measured on the N = 262144, M = 4096 bound, profiles/r04_experiments/elbo_c4.txt: 159.7 -> 161.5 ms,
+    // two MFMA-bound streams lose more to each other than the solve's substitutions leave idle.  Removed in round 6.)
+    CHECK_RC(dAt.alloc((size_t)m_pad * CH));
+    CHECK_RC(dCs.alloc((size_t)transpose_colsum_scratch(CH, m_pad)));
+    {   // slabs of the chunk lengths actually used: the `sub` split depends on K % (8 sub 16), so a shorter LAST chunk can
+        // need more slabs than a full one (advisor, round 4: SGP_VFE_CHUNK = 768, M = 4096, 1280 rows -> 8 vs 32)
+      const long last = n_rows % CH == 0 ? std::min(CH, n_rows) : n_rows % CH;
+      const long slabs = std::max(splitk_slabs(m_pad, std::min(CH, n_rows), nsplit), splitk_slabs(m_pad, last, nsplit));
+      CHECK_RC(dPart.alloc((size_t)slabs * stride));
+    }
+    // ---- row chunks
+    long chunk = 0;
+    for (long r0 = 0; r0 < n_rows; r0 += CH, ++chunk) {
+      const long ch = std::min(CH, n_rows - r0);            // rows of this chunk (multiple of 128)
+      const long nv = std::max<long>(0, std::min(N - r0, ch));  // of which real data points
+      const int acc = (append || r0 > 0) ? 1 : 0;
+      double* At = dAt.p;
+      tm.mark(1);
+      // (a full chunk of an unpadded M is written entry for entry by the assembly: nothing to clear)
+      if (nv < ch || M < m_pad) SGP_HIP(hipMemsetAsync(dR.p, 0, sizeof(double) * ch * m_pad, s));
+      // global row r of K(x,z) lands at dR[(r - r0) + c * ch]
+      CHECK_RC(assemble(dx, dR.p - r0, ch, r0 / TILE, (r0 + ch) / TILE, 0, m_pad / TILE, 0, -1, 0.0, nullptr, s));
+      tm.mark(2);
+      // The rows' Lambda_y^-1/2 factors commute with the solve (it acts on the inducing dimension): instead of a pass of
+      // their own over the chunk before it (2 x 2.1 GB at N = 262 144, M = 4096: 0.9 ms per chunk) they are applied where
+      // the solved rows are read anyway -- the column sums and the transposition (padded rows carry the factor 0)
+      CHECK_RC(row_trsm(ctx, dR.p, ch, ch, dLz, m_pad, d_wz, m_pad, s));
+      tm.mark(3);
+      // (round 6: ONE pass over the solved rows -- the column sums ride with the transposition, 6.0 -> 3.6 ms per step at
+      // N = 262 144, M = 4096)
+      // (append: sq was cleared and counts this call's rows only -- accumulating onto its zeros from the first chunk on gives
+      // the bits that writing gives, a sum of squares is never -0)
+      CHECK_RC(launch_transpose_colsum(dR.p, ch, ch, m_pad, At, m_pad, drsig.p + r0, ddelta.p + r0, d_dots, sq.p, acc, dCs.p, s));
+      tm.mark(4);
+      // (the split-K slices need ch to be a multiple of 16 * nsplit = 128: it is)
+      CHECK_RC(launch_gemm_nt_splitk(At, m_pad, At, m_pad, dPart.p, ldg, m_pad, m_pad, ch, nsplit, stride, 1, s));
+      CHECK_RC(launch_splitk_reduce(dPart.p, stride, nsplit, dG, ldg, m_pad, m_pad, 1.0, acc ? 1.0 : 0.0, 1, s, ch));
+    }
+    tm.mark(5);
+    if (append) {
+      CHECK_RC(launch_sum_array(sq.p, m_pad, sc_new.p + 3, s));
+      hipLaunchKernelGGL(accum_n_kernel, dim3(1), dim3(64), 0, s, d_sc, (const double*)sc_new.p, 4);
+      SGP_HIP(hipGetLastError());
+    } else {
+      CHECK_RC(launch_sum_array(sq.p, m_pad, d_sc + 3, s));
+    }
+    SGP_HIP(hipStreamSynchronize(s));  // chunk buffers go back to the cache at scope exit
+    return 0;
+  }
+};
+
 static int vfe_rows_partial(sgp_ctx* ctx, const sgp_dspec* dz, const sgp_dspec* dx, const double* var_x,
                             const double* mean_x, int noise_kind, const double* noise_x, int z_noise_kind,
                             const double* z_noise, const double* y, double* dLz, double* d_wz, double* d_part,
                             StageTimer& tm) {
   const long M = dz->N, N = dx->N;
-  const long m_pad = rup(M, TILE), n_rows = rup(N, TILE);
-  const long ldg = m_pad + TILE;
-  double* dG = d_part;
-  double* d_dots = d_part + ldg * m_pad;
-  double* d_sc = d_dots + m_pad;
-  long CH, ch_above;
-  vfe_chunking(&CH, &ch_above);
-  CH = std::min(CH, n_rows);
+  const long m_pad = rup(M, TILE);
   hipStream_t s = ctx->stream;
-  DevBuf dR, dAt, dPart, dy, dmean, dvar, ddelta, drsig, sq;
-  NoiseDev ndx, ndz;
-  CHECK_RC(dy.upload(y, N));
-  if (mean_x) CHECK_RC(dmean.upload(mean_x, N));
-  if (var_x) CHECK_RC(dvar.upload(var_x, N));
-  CHECK_RC(upload_noise(ndx, noise_kind, noise_x, N));
+  VfeRows rows(ctx, dx, M, d_part, 0);
+  NoiseDev ndz;
+  CHECK_RC(rows.upload(var_x, mean_x, noise_kind, noise_x, y));
   CHECK_RC(upload_noise(ndz, z_noise_kind, z_noise, M));
-  CHECK_RC(ddelta.alloc(n_rows));
-  CHECK_RC(drsig.alloc(n_rows));
-  CHECK_RC(sq.alloc(m_pad));
+  CHECK_RC(rows.alloc_rows());
   tm.mark(0);
   SGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
-  SGP_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * vfe_part_len(m_pad), s));
-  SGP_HIP(hipMemsetAsync(sq.p, 0, sizeof(double) * m_pad, s));
-  SGP_HIP(hipMemsetAsync(ddelta.p, 0, sizeof(double) * n_rows, s));
-  SGP_HIP(hipMemsetAsync(drsig.p, 0, sizeof(double) * n_rows, s));
-  CHECK_RC(launch_elbo_scalars(ctx, dy.p, mean_x ? dmean.p : nullptr,
-                     var_x ? dvar.p : nullptr, ndx.kind, ndx.sigma2, ndx.diag.p, N, ddelta.p, drsig.p, d_sc, s));
+  CHECK_RC(rows.scalars(mean_x != nullptr, var_x != nullptr));
   // ---- Lz (replicated on every rank of a sharded run: M^3 / 3 flops, no communication)
   int nkz = ndz.kind == SGP_NOISE_DENSE ? -1 : ndz.kind;
   CHECK_RC(assemble(dz, dLz, m_pad, 0, m_pad / TILE, 0, m_pad / TILE, 1, nkz, ndz.sigma2, ndz.diag.p, s));
@@ -3136,51 +3225,7 @@ static int vfe_rows_partial(sgp_ctx* ctx, const sgp_dspec* dz, const sgp_dspec* 
     return info;
   }
   if (N == 0) return 0;
-  const int nsplit = 8;  // one K slice per XCD (gemm_nt.hip, klo == 3)
-  const long stride = ldg * m_pad;
-  CHECK_RC(dR.alloc((size_t)CH * m_pad));
-  // (Round 4 also built "two chunks in flight" -- the Gram product of chunk c on the second stream while chunk c + 1 is assembled
-  // and solved on the first; measured on the N = 262144, M = 4096 bound, profiles/r04_experiments/elbo_c4.txt: 159.7 -> 161.5 ms,
-  // two MFMA-bound streams lose more to each other than the solve's substitutions leave idle.  Removed in round 6.)
-  CHECK_RC(dAt.alloc((size_t)m_pad * CH));
-  DevBuf dCs;
-  CHECK_RC(dCs.alloc((size_t)transpose_colsum_scratch(CH, m_pad)));
-  {   // slabs of the chunk lengths actually used: the `sub` split depends on K % (8 sub 16), so a shorter LAST chunk can
-      // need more slabs than a full one (advisor, round 4: SGP_VFE_CHUNK = 768, M = 4096, 1280 rows -> 8 vs 32)
-    const long last = n_rows % CH == 0 ? std::min(CH, n_rows) : n_rows % CH;
-    const long slabs = std::max(splitk_slabs(m_pad, std::min(CH, n_rows), nsplit), splitk_slabs(m_pad, last, nsplit));
-    CHECK_RC(dPart.alloc((size_t)slabs * stride));
-  }
-  // ---- row chunks
-  long chunk = 0;
-  for (long r0 = 0; r0 < n_rows; r0 += CH, ++chunk) {
-    const long ch = std::min(CH, n_rows - r0);            // rows of this chunk (multiple of 128)
-    const long nv = std::max<long>(0, std::min(N - r0, ch));  // of which real data points
-    double* At = dAt.p;
-    tm.mark(1);
-    // (a full chunk of an unpadded M is written entry for entry by the assembly: nothing to clear)
-    if (nv < ch || M < m_pad) SGP_HIP(hipMemsetAsync(dR.p, 0, sizeof(double) * ch * m_pad, s));
-    // global row r of K(x,z) lands at dR[(r - r0) + c * ch]
-    CHECK_RC(assemble(dx, dR.p - r0, ch, r0 / TILE, (r0 + ch) / TILE, 0, m_pad / TILE, 0, -1, 0.0, nullptr, s));
-    tm.mark(2);
-    // The rows' Lambda_y^-1/2 factors commute with the solve (it acts on the inducing dimension): instead of a pass of
-    // their own over the chunk before it (2 x 2.1 GB at N = 262 144, M = 4096: 0.9 ms per chunk) they are applied where
-    // the solved rows are read anyway -- the column sums and the transposition (padded rows carry the factor 0)
-    CHECK_RC(row_trsm(ctx, dR.p, ch, ch, dLz, m_pad, d_wz, m_pad, s));
-    tm.mark(3);
-    // (round 6: ONE pass over the solved rows -- the column sums ride with the transposition, 6.0 -> 3.6 ms per step at
-    // N = 262 144, M = 4096)
-    CHECK_RC(launch_transpose_colsum(dR.p, ch, ch, m_pad, At, m_pad, drsig.p + r0, ddelta.p + r0, d_dots, sq.p, r0 > 0 ? 1 : 0,
-                                     dCs.p, s));
-    tm.mark(4);
-    // (the split-K slices need ch to be a multiple of 16 * nsplit = 128: it is)
-    CHECK_RC(launch_gemm_nt_splitk(At, m_pad, At, m_pad, dPart.p, ldg, m_pad, m_pad, ch, nsplit, stride, 1, s));
-    CHECK_RC(launch_splitk_reduce(dPart.p, stride, nsplit, dG, ldg, m_pad, m_pad, 1.0, r0 > 0 ? 1.0 : 0.0, 1, s, ch));
-  }
-  tm.mark(5);
-  CHECK_RC(launch_sum_array(sq.p, m_pad, d_sc + 3, s));
-  SGP_HIP(hipStreamSynchronize(s));  // chunk buffers go back to the cache at scope exit
-  return 0;
+  return rows.chunks(dLz, d_wz, tm);
 }
 
 // h[0..5] as documented at vfe_pipeline; d_wg (optional) keeps the inverse diagonal blocks of Le
@@ -3236,6 +3281,11 @@ static int vfe_pipeline_chunked(sgp_ctx* ctx, const sgp_dspec* dz, const sgp_dsp
   StageTimer tm(ctx, ctx->stream);
   CHECK_RC(vfe_rows_partial(ctx, dz, dx, var_x, mean_x, noise_kind, noise_x, z_noise_kind, z_noise, y, dLz, d_wz,
                             d_part, tm));
+  if (keep) {   // the sums, before the identity is added and the buffer factored (sgp_sparse_post::d_sums)
+    SGP_HIP(hipMalloc(&keep->d_sums, sizeof(double) * vfe_part_len(m_pad)));
+    SGP_HIP(hipMemcpyAsync(keep->d_sums, d_part, sizeof(double) * vfe_part_len(m_pad), hipMemcpyDeviceToDevice, ctx->stream));
+    keep->n_total = dx->N;
+  }
   CHECK_RC(vfe_finish(ctx, d_part, m_pad, keep ? keep->d_wg : nullptr, h, tm));
   if (keep) {
     keep->ctx = ctx;
@@ -3420,6 +3470,15 @@ static int vfe_pipeline(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec
                                    stride, 1, s));
     CHECK_RC(launch_splitk_reduce(dPart.p, stride, nsplit, dG, ldg, m_pad, m_pad, 1.0, 0.0, 1, s, n_rows));
     SGP_HIP(hipStreamSynchronize(s));  // dAt / dPart are freed at scope exit
+  }
+  if (keep) {   // the sums in the part layout (vfe_part_len), before the identity is added and the buffer factored
+    SGP_HIP(hipMalloc(&keep->d_sums, sizeof(double) * vfe_part_len(m_pad)));
+    double* d_sd = keep->d_sums + ldg * m_pad;
+    SGP_HIP(hipMemcpyAsync(keep->d_sums, dG, sizeof(double) * ldg * m_pad, hipMemcpyDeviceToDevice, s));
+    SGP_HIP(hipMemcpyAsync(d_sd, dots.p, sizeof(double) * m_pad, hipMemcpyDeviceToDevice, s));
+    SGP_HIP(hipMemsetAsync(d_sd + m_pad, 0, sizeof(double) * 8, s));
+    SGP_HIP(hipMemcpyAsync(d_sd + m_pad, ctx->d_scal + 1, sizeof(double) * 4, hipMemcpyDeviceToDevice, s));
+    keep->n_total = N;
   }
   hipLaunchKernelGGL(add_identity_kernel, dim3((unsigned)((m_pad + 255) / 256)), dim3(256), 0, s, dG,
                      ldg, m_pad);
@@ -4486,6 +4545,16 @@ int drv_elbo_grad(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shar
 }
 int drv_vfe_finish(sgp_ctx* ctx, long M, double* d_part, double* d_wg, double* h6) {
   return elbo_finish_core(ctx, M, d_part, d_wg, h6);
+}
+int drv_vfe_rows_append(sgp_ctx* ctx, const sgp_dspec* dx, long M, const double* var_x, const double* mean_x, int noise_kind,
+                        const double* noise_x, const double* y, const double* dLz, const double* d_wz, double* d_part,
+                        StageTimer& tm) {
+  VfeRows rows(ctx, dx, M, d_part, 1);
+  CHECK_RC(rows.upload(var_x, mean_x, noise_kind, noise_x, y));
+  CHECK_RC(rows.alloc_rows());
+  tm.mark(0);
+  CHECK_RC(rows.scalars(mean_x != nullptr, var_x != nullptr));
+  return rows.chunks(dLz, d_wz, tm);
 }
 // the multi-GPU driver's view (multi.hip): rank 0's context computes the pattern, every rank uploads it
 int drv_sz_pattern(sgp_ctx* ctx, const sgp_dspec* ds, int noise_kind, long n_pad, long m_tot, int* words) {

@@ -225,6 +225,14 @@ struct sgp_sparse_post {
   double* dG = nullptr;    // (m_pad + 128) x m_pad: factor of A A' + I, row m_pad = (Le^-1 A delta)'
   double* d_wg = nullptr;
   long ldg = 0;
+  // what sgp_sparse_posterior_update (include/sthenomi_vfe_update.h; vfe_update.hip) absorbs new data into: the sums over the
+  // data points the factors were made from, in the part layout of vfe_part_len(m_pad) (capi.hip) -- the lower tiles of
+  // sum_n a_n a_n' with no identity added, then A delta, then [sum log s2, delta' delta, sum var / s2, |A|_F^2] (the create
+  // call has no var_x: its points leave 0 in sum var / s2, the updates' points their terms).  One more
+  // (m_pad + 128) x m_pad buffer per kept posterior (138 MB at M = 4096), copied device to device once by the create call.
+  // nullptr: a posterior created on a multi-GPU context keeps none.
+  double* d_sums = nullptr;
+  long n_total = 0;        // data points absorbed so far
 };
 
 namespace sgp {

@@ -123,5 +123,18 @@ int drv_vfe_partial(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz
 int drv_elbo_grad(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shard);
 // h6: the six ELBO terms (see vfe_pipeline); d_wg (optional) keeps the inverse diagonal blocks of chol(A A' + I)
 int drv_vfe_finish(sgp_ctx* ctx, long M, double* d_part, double* d_wg, double* h6);
+// the row-chunk loop of the sparse pipeline in append mode (capi.hip: VfeRows): the rows of `dx` -- y, mean, var and noise
+// are host vectors of dx->N values -- are solved against the kept dLz / d_wz of M inducing points and their sums are ADDED
+// to the part d_part (the accumulate flags are on from the first chunk; the four scalars are added to the kept ones).
+// The caller holds the context; stage slots as vfe_rows_partial: 0 buffers, 1 assembly, 2 row solve, 3 transpose + column
+// sums, 4 Gram, 5 the scalars' sum
+int drv_vfe_rows_append(sgp_ctx* ctx, const sgp_dspec* dx, long M, const double* var_x, const double* mean_x, int noise_kind,
+                        const double* noise_x, const double* y, const double* dLz, const double* d_wz, double* d_part,
+                        StageTimer& tm);
+// sgp_sparse_posterior_update / _count (include/sthenomi_vfe_update.h, forwarded from libsthenomi_vfe_update.so) -- vfe_update.hip
+int drv_sparse_posterior_update(sgp_sparse_post* post, const sgp_cov_spec* xz_new, const double* var_x_new,
+                                const double* mean_x_new, int noise_kind, const double* noise_new, const double* y_new,
+                                double* elbo_out);
+int drv_sparse_posterior_count(sgp_sparse_post* post, int64_t* n_out);
 
 }  // namespace sgp

@@ -247,7 +247,7 @@ def _postfx_route(fx):
     ms = _f64(mean_vector(f.prior, fx.x))
     if isinstance(f, PosteriorGP):
         return lib, "sgp_posterior", f._ensure(), cross, pss, ms, kind, nbuf
-    return lib, "sgp_sparse_posterior", f._h, cross, pss, ms, kind, nbuf
+    return lib, "sgp_sparse_posterior", f._ensure(), cross, pss, ms, kind, nbuf
 
 
 def logpdf(fx, y):
@@ -929,7 +929,7 @@ def posterior(fx, y, y_vfe=None):
     return post
 
 
-def update_posterior(post, fx2, y2, reserve=None):
+def update_posterior(post, fx2, y2=None, reserve=None):
     """update_posterior(f_post, fx2, y2) [AbstractGPs]: the posterior given the data of `post` AND the observations y2 of
     fx2 = f(x2, s2), by extending the kept Cholesky factor with the rows of the new data (sgp_posterior_extend:
     O(N^2 k + N k^2 + k^3) for k new points) instead of factoring the stacked covariance from scratch.
@@ -938,9 +938,17 @@ def update_posterior(post, fx2, y2, reserve=None):
     of its own the next time it is asked something.  reserve: the number of points the factor buffer is sized for when it
     has to grow (a loop that keeps adding points passes the size it will reach and pays one reallocation).
     A dense Sigma_y on either side or a multi-GPU context go through the stacked one-shot `posterior` -- the same posterior, to rounding.  A stacked covariance that is not positive definite raises
-    PosDefException with the failing leading minor; `post` is then exactly what it was."""
+    PosDefException with the failing leading minor; `post` is then exactly what it was.
+
+    A VFE posterior (posterior(VFE(fz), fx, y)) takes the two AbstractGPs methods of its own: update_posterior(post, fx2, y2)
+    absorbs the new data with the inducing points fixed (_update_vfe_data), update_posterior(post, fz_new) re-conditions the
+    data already seen on new inducing points (_update_vfe_inducing)."""
+    if isinstance(post, ApproxPosteriorGP):
+        return _update_vfe_inducing(post, fx2) if y2 is None else _update_vfe_data(post, fx2, y2)
     if not isinstance(post, PosteriorGP):
-        raise TypeError("update_posterior extends an exact PosteriorGP (posterior(fx, y))")
+        raise TypeError("update_posterior extends an exact PosteriorGP (posterior(fx, y)) or a VFE posterior")
+    if y2 is None:
+        raise TypeError("update_posterior(f_post, fx2, y2): y2 is missing (only a VFE posterior takes update_posterior(post, fz_new))")
     if not isinstance(fx2, FiniteGP) or not (fx2.f is post.prior or fx2.f is post):
         raise ValueError("update_posterior: fx2 must be the posterior's prior process (or the posterior itself) at the new points")
     xx, noise, yy = _stack_observations(post, fx2, y2)
@@ -1293,8 +1301,36 @@ def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):
 
 
 class ApproxPosteriorGP:
-    def __init__(self, prior, z, handle):
+    """posterior(VFE(fz), fx, y): keeps Lz, the factor of A A' + I and the sums over the data points in HBM (sgp_sparse_post).
+    vfe / batches: the VFE object and the observation batches (x, Sigma_y, y) it was conditioned on, by reference -- what
+    update_posterior needs to rebuild a posterior whose handle moved on, or to re-condition on other inducing points."""
+
+    def __init__(self, prior, z, handle, vfe=None, batches=None, created=None):
         self.prior, self.z, self._h = prior, z, handle
+        self.vfe, self.batches = vfe, batches
+        # the leading batches that went through the handle's create call (the later ones through updates), and
+        # 1/2 sum var / s2 over them -- the term sgp_sparse_posterior_update's elbo_out cannot know (_create_trace)
+        self._created = len(batches) if (created is None and batches) else created
+        self._trace0 = None
+
+    def _ensure(self):
+        """The factors in HBM: a posterior whose handle update_posterior handed to its successor rebuilds one of its own
+        from the stacked batches the next time it is asked something."""
+        if self._h is None:
+            if self.vfe is None or not self.batches:
+                raise NotImplementedError("this sparse posterior does not carry its observations")
+            self._h = _vfe_create(self.vfe, _stacked_fx(self.prior, self.batches), _stacked_y(self.batches))
+            self._created, self._trace0 = len(self.batches), None
+        return self._h
+
+    def _create_trace(self):
+        """sum_n var(f, x_n) / s2_n over the points the handle's create call was given (it takes no var_x)"""
+        if self._trace0 is None:
+            t = 0.0
+            for x, s, _ in self.batches[:self._created]:
+                t += float(np.sum(np.asarray(prior_var(self.prior, x), dtype=np.float64) / _noise_diag(s, len(x))))
+            self._trace0 = t
+        return self._trace0
 
     def __del__(self):  # pragma: no cover
         try:
@@ -1318,7 +1354,7 @@ class ApproxPosteriorGP:
         mo = np.zeros(ns) if want_mean else None
         vo = np.zeros(ns) if want_var else None
         co = np.zeros((ns, ns), order="F") if want_cov else None
-        rc = _ctx().lib.sgp_sparse_posterior_predict(self._h, cross.ref(), pss.ref() if pss is not None else None,
+        rc = _ctx().lib.sgp_sparse_posterior_predict(self._ensure(), cross.ref(), pss.ref() if pss is not None else None,
                                                      _lib.dptr(ms), _lib.dptr(mo), _lib.dptr(vo), _lib.dptr(co),
                                                      max(ns, 1))
         _lib.check(rc, "sgp_sparse_posterior_predict")
@@ -1423,11 +1459,99 @@ class ExplicitPosteriorGP:
         return m, c
 
 
-def posterior_vfe(vfe, fx, y):
+def _vfe_create(vfe, fx, y):
     zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
     h = C.c_void_p()
     rc = _ctx().lib.sgp_sparse_posterior_create(_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(mean_x), nk,
                                                 _lib.dptr(nbuf), zk, _lib.dptr(zbuf), _lib.dptr(y), C.byref(h))
     _lib.check(rc, "sgp_sparse_posterior_create")
-    return ApproxPosteriorGP(fx.f, vfe.fz.x, h)
+    return h
+
+
+def posterior_vfe(vfe, fx, y):
+    h = _vfe_create(vfe, fx, y)
+    return ApproxPosteriorGP(fx.f, vfe.fz.x, h, vfe=vfe, batches=[(fx.x, fx.noise, y)])
+
+
+def _stacked_fx(prior, batches):
+    """FiniteGP of the prior at the stacked inputs of the batches: one batch as it came, several as a BlockData of their
+    blocks in order; two equal scalar noises stay a scalar, anything else becomes a diagonal."""
+    if len(batches) == 1:
+        return FiniteGP(prior, batches[0][0], batches[0][1])
+    blocks = []
+    for x, _, _ in batches:
+        blocks += list(x.X) if isinstance(x, BlockData) else [x]
+    ns = [np.asarray(s, dtype=np.float64) for _, s, _ in batches]
+    if all(a.ndim == 0 and float(a) == float(ns[0]) for a in ns):
+        noise = float(ns[0])
+    else:
+        noise = np.concatenate([_noise_diag(a, len(x)) for a, (x, _, _) in zip(ns, batches)])
+    return FiniteGP(prior, BlockData(blocks), noise)
+
+
+def _vfe_on_batches(vfe, prior, batches):
+    """posterior(vfe, f(x_all, Sigma_y), y_all) on the stacked batches, which the new object keeps one by one: ALL of them
+    went through its handle's create call (ApproxPosteriorGP._created, the points of _create_trace)."""
+    fx = _stacked_fx(prior, batches)
+    h = _vfe_create(vfe, fx, _stacked_y(batches))
+    return ApproxPosteriorGP(prior, vfe.fz.x, h, vfe=vfe, batches=batches)
+
+
+def _stacked_y(batches):
+    return np.concatenate([np.asarray(y, dtype=np.float64).ravel() for _, _, y in batches])
+
+
+def _check_vfe_batch(post, fx2):
+    if not isinstance(fx2, FiniteGP) or fx2.f is not post.prior:
+        raise ValueError("update_posterior: fx2 must be the sparse posterior's prior process at the new points")
+    if np.asarray(fx2.noise, dtype=np.float64).ndim > 1:
+        raise ValueError("elbo needs isotropic or diagonal observation noise")
+    if post.vfe is None or not post.batches:
+        raise NotImplementedError("this sparse posterior does not carry its observations")
+
+
+def _update_vfe_data(post, fx2, y2):
+    """update_posterior(f_post_approx, fx2, y2) [AbstractGPs, VFE]: the new rows join the sums the posterior keeps and
+    A A' + I is factored afresh (sgp_sparse_posterior_update: O(n_new M^2 + M^3 / 3), whatever came before).  The returned
+    ApproxPosteriorGP TAKES OVER the handle and carries elbo_y, the ELBO of all the data; `post` stays usable -- it rebuilds
+    factors of its own from its batches the next time it is asked something.  A multi-GPU context goes through the stacked
+    one-shot posterior(VFE, ...) and takes elbo_y from sgp_elbo on the stacked data."""
+    _check_vfe_batch(post, fx2)
+    y2 = _f64(np.asarray(y2, dtype=np.float64).ravel())
+    n2 = len(fx2)
+    if y2.shape[0] != n2:
+        raise ValueError("length(y2) != length(fx2)")
+    batches = list(post.batches) + [(fx2.x, fx2.noise, y2)]
+    if getattr(_ctx(), "is_multi", False):
+        new = _vfe_on_batches(post.vfe, post.prior, batches)
+        new.elbo_y = elbo(post.vfe, _stacked_fx(post.prior, batches), _stacked_y(batches))   # (no update ran: sgp_elbo)
+        return new
+    fz = post.vfe.fz
+    xz, _, _ = build_spec(fx2.f, fx2.x, fz.f, fz.x)
+    kind, nbuf = _lib._noise_args(fx2.noise, n2)
+    mean2 = _f64(mean_vector(fx2.f, fx2.x))
+    var2 = _f64(prior_var(fx2.f, fx2.x))
+    out = np.zeros(1)
+    h = post._ensure()
+    trace0 = post._create_trace()
+    rc = _ctx().vfe_update.sgp_sparse_posterior_update(h, xz.ref(), _lib.dptr(var2), _lib.dptr(mean2), kind, _lib.dptr(nbuf),
+                                                       _lib.dptr(y2), _lib.dptr(out))
+    _lib.check(rc, "sgp_sparse_posterior_update")   # rc > 0: PosDefException(info); the old posterior is untouched
+    post._h = None                                  # the new object owns the factors; the old one rebuilds its own on demand
+    new = ApproxPosteriorGP(post.prior, post.z, h, vfe=post.vfe, batches=batches, created=post._created)
+    new._trace0 = trace0
+    # elbo(VFE(fz), f(x_all, Sigma_y), y_all): the call computes it on the way, up to the trace term of the points the
+    # create call was given (it takes no var_x)
+    new.elbo_y = float(out[0]) - 0.5 * trace0
+    return new
+
+
+def _update_vfe_inducing(post, fz_new):
+    """update_posterior(f_post_approx, fz_new) [AbstractGPs, VFE]: the data already seen, conditioned on the inducing points
+    of fz_new -- posterior(VFE(fz_new), f(x_all, Sigma_y), y_all) on the stacked kept batches, and that very call."""
+    if not isinstance(fz_new, FiniteGP) or fz_new.f is not post.prior:
+        raise ValueError("update_posterior: fz_new must be the sparse posterior's prior process at the new inducing points")
+    if post.vfe is None or not post.batches:
+        raise NotImplementedError("this sparse posterior does not carry its observations")
+    return _vfe_on_batches(VFE(fz_new), post.prior, list(post.batches))

@@ -20,6 +20,7 @@ POOL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_pool.so")
 EXTEND_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend.so")
 EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so")
 POSTFX_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_postfx.so")
+VFE_UPDATE_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_vfe_update.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
 KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
@@ -227,6 +228,13 @@ _SIGS_POSTFX = {
     "sgp_sparse_posterior_logpdf": _POSTFX_LOGPDF,
 }
 
+# include/sthenomi_vfe_update.h: new data into a kept sparse (VFE) posterior, exported by libsthenomi_vfe_update.so (it links
+# against the product library and works on its posteriors) -- update_posterior reaches it through vfe_update_lib() / Context.vfe_update
+_SIGS_VFE_UPDATE = {
+    "sgp_sparse_posterior_update": (C.c_int, [_P, C.POINTER(sgp_cov_spec), _D, _D, C.c_int, _D, _D, _D]),
+    "sgp_sparse_posterior_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+}
+
 # include/sthenomi_extend_bench.h: the measurement hook of the extension (libsthenomi_extend_bench.so; tools and tests only)
 _SIGS_EXTEND_BENCH = {
     "sgp_bench_extend_row_solve": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D]),
@@ -308,6 +316,11 @@ def extend_symbols():
 def postfx_symbols():
     """Names include/sthenomi_postfx.h declares: the entry points of libsthenomi_postfx.so."""
     return sorted(_SIGS_POSTFX)
+
+
+def vfe_update_symbols():
+    """Names include/sthenomi_vfe_update.h declares: the entry points of libsthenomi_vfe_update.so."""
+    return sorted(_SIGS_VFE_UPDATE)
 
 
 def batch_symbols():
@@ -412,6 +425,28 @@ def extend_lib():
             fn.restype = res
             fn.argtypes = args
         _extend = lib
+        return lib
+
+
+_vfe_update = None
+
+
+def vfe_update_lib():
+    """dlopen libsthenomi_vfe_update.so (include/sthenomi_vfe_update.h) after the product library it links against."""
+    global _vfe_update
+    load()
+    with _lib_lock:
+        if _vfe_update is not None:
+            return _vfe_update
+        if not os.path.exists(VFE_UPDATE_LIB_PATH):
+            raise SthenoMIError(
+                f"{VFE_UPDATE_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(VFE_UPDATE_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_VFE_UPDATE.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _vfe_update = lib
         return lib
 
 
@@ -640,6 +675,11 @@ class Context:
     def postfx(self):
         """libsthenomi_postfx.so (sthenomi_postfx.h): `ctx.postfx.sgp_posterior_logpdf(post_handle, ...)`"""
         return postfx_lib()
+
+    @property
+    def vfe_update(self):
+        """libsthenomi_vfe_update.so (sthenomi_vfe_update.h): `ctx.vfe_update.sgp_sparse_posterior_update(post_handle, ...)`"""
+        return vfe_update_lib()
 
     @property
     def ndev(self):
