@@ -18,8 +18,10 @@
  * unknown one.  reserved == 0 everywhere is the product header's plain spec.
  *
  * Patch terms run on every fp64 operator of a single-GPU context: sgp_kernelmatrix / _diag, sgp_logpdf (_batch),
- * sgp_rand, the posterior, sgp_elbo and the sparse posterior.  These refuse them with rc < 0: the gradient entry points
- * (sgp_*_grad*, sgp_logpdf_grad_batch), the fp32 entry points (sgp_*_f32) and every multi-GPU context.
+ * sgp_rand, the posterior, sgp_elbo and the sparse posterior.  Their gradients come from include/sthenomi_conv_grad.h
+ * (sgp_logpdf_grad_conv, sgp_kernelmatrix_diag_grad_conv, sgp_elbo_grad_conv; libsthenomi_conv_grad.so).  These refuse them
+ * with rc < 0: the gradient entry points of the other headers (sgp_*_grad*, sgp_logpdf_grad_batch / _pool, the *_param
+ * family), the fp32 entry points (sgp_*_f32) and every multi-GPU context.
  * Limits: height * width <= 3072, patch_h * patch_w <= 64. */
 #ifndef STHENOMI_CONV_H
 #define STHENOMI_CONV_H

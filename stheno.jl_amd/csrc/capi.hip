@@ -1763,7 +1763,7 @@ extern "C" int sgp_rand(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* me
 }
 
 // the caller's index of the term at device position t (a spec with product chains keeps its plain terms in front: dspec_create)
-static inline int term_src_of(const sgp_dspec* ds, int t) { return ds->n_kprod ? ds->term_src[t] : t; }
+static inline int term_src_of(const sgp_dspec* ds, int t) { return (ds->n_kprod || ds->n_patch) ? ds->term_src[t] : t; }
 // the chain whose head sits at device position t: one past its last factor, and its DMAX
 static inline int chain_end(const sgp_dspec* ds, int t, int t1) {
   int e = t + 1;
@@ -1780,7 +1780,7 @@ static inline int chain_dmax(const sgp_dspec* ds, int t, int e) {
 static int fetch_terms(const sgp_dspec* ds, double* dst, const double* d_src) {
   const size_t nt = ds->h_terms.size();
   if (!dst || !nt) return 0;
-  if (!ds->n_kprod) {
+  if (!ds->n_kprod && !ds->n_patch) {   // (patch terms sit behind the pair's plain terms on the device, as chains do)
     SGP_HIP(hipMemcpy(dst, d_src, sizeof(double) * nt, hipMemcpyDeviceToHost));
     return 0;
   }
@@ -1795,13 +1795,19 @@ static int fetch_terms(const sgp_dspec* ds, double* dst, const double* d_src) {
 // Product chains (ds->n_kprod; kprod.hip) are contracted one chain per launch, only where the caller says it carries them
 // (kprod_ok: sgp_logpdf_grad / sgp_logpdf_grad_param); dgp (optional): d / d param per term, which for the plain terms is
 // non-zero for SGP_CONST alone -- those run through the chain kernel once more, as chains of length one, for that entry.
+// Patch terms (ds->n_patch; conv.hip) are contracted one term per launch, only where the caller carries them (patch_ok: the
+// entry points of include/sthenomi_conv_grad.h).
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr,
                          long n_tc, DevBuf& dpart, double* dgc, double* dgs, hipStream_t s, bool kprod_ok = false,
-                         double* dgp = nullptr) {
+                         double* dgp = nullptr, bool patch_ok = false) {
   CHECK_ARG(!ds->n_stencil, "gradient contraction: stencil terms are not supported");
-  CHECK_ARG(!ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
+  CHECK_ARG(patch_ok || !ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
   CHECK_ARG(kprod_ok || !ds->n_kprod, "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
-  CHECK_RC(dpart.alloc((size_t)std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16)));
+  long need = std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16);
+  for (int p = 0; ds->n_patch && p < ds->nrb * ds->ncb; ++p)
+    for (int t = ds->term_ptr[p] + ds->pair_nplain[p]; t < ds->term_ptr[p] + ds->pair_nplain[p] + ds->pair_npatch[p]; ++t)
+      need = std::max(need, grad_conv_partials(ds->row_len[p / ds->ncb], ds->col_len[p % ds->ncb], ds->h_terms[t]));
+  CHECK_RC(dpart.alloc((size_t)need));
   for (int I = 0; I < ds->nrb; ++I) {
     if (ds->row_len[I] == 0) continue;
     for (int J = 0; J < ds->ncb; ++J) {
@@ -1813,12 +1819,15 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       int dmax = ds->pair_dmax[p];
       int per = std::min(8, std::max(1, 64 / dmax));
       const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
-      for (int t = t0; t < tk; t += per) {
-        int cnt = std::min(per, tk - t);
+      const int tp = ds->n_patch ? t0 + ds->pair_nplain[p] : tk;   // patch terms: [tp, tk) (no stencil terms here)
+      for (int t = t0; t < tp; t += per) {
+        int cnt = std::min(per, tp - t);
         CHECK_RC(launch_grad_block(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax, trf, tcf,
                                    trl - trf, tcl - tcf, dpart.p, dgc + t, dgs + t, s));
       }
-      for (int t = t0; dgp && t < tk; ++t)
+      for (int t = tp; t < tk; ++t)
+        CHECK_RC(launch_grad_conv(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, dpart.p, dgc + t, dgs + t, s));
+      for (int t = t0; dgp && t < tp; ++t)
         if (ds->h_terms[t].kind == SGP_CONST)
           CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, 1, 1, 0, trf, tcf, trl - trf, tcl - tcf,
                                      dpart.p, nullptr, nullptr, dgp + t, s));
@@ -1843,12 +1852,16 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
                             const double* noise, const double* y, double* logpdf_out, double* grad_y,
                             double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
                             double* const* grad_inputs, double* const* grad_rowscale = nullptr,
-                            double* grad_param = nullptr, bool with_param = false) {
+                            double* grad_param = nullptr, bool with_param = false, bool patch_ok = false) {
+  // (patch_ok: sgp_logpdf_grad_conv, include/sthenomi_conv_grad.h -- patch terms are contracted, conv.hip)
   CHECK_ARG(ctx && spec && noise && y && logpdf_out, "sgp_logpdf_grad: NULL argument");
   CHECK_ARG(spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
   CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
-  CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_grad: gradients through stencil terms are not supported");
-  CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
+  CHECK_ARG(!(patch_ok && ctx->multi), "sgp_logpdf_grad_conv: not supported on a multi-GPU context");
+  CHECK_ARG(!spec_has_stencil(ctx, spec), patch_ok ? "sgp_logpdf_grad_conv: gradients through stencil terms are not supported"
+                                                   : "sgp_logpdf_grad: gradients through stencil terms are not supported");
+  CHECK_ARG(patch_ok || !spec_has_patch(spec),
+            "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
   CHECK_ARG(!(grad_inputs || grad_rowscale) || with_param || !spec_has_kprod(spec),
             "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
             "not supported: call sgp_logpdf_grad_param_xs (include/sthenomi_kprod_grad.h)");
@@ -1940,7 +1953,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   else if (grad_noise) CHECK_RC(launch_grad_noise(dKinv.p, n_pad, dalpha.p, N, nd.kind == SGP_NOISE_DIAG, dgn.p, s));
   if (grad_coef || grad_inscale || grad_param)
     CHECK_RC(contract_spec(ds, dKinv.p, n_pad, dalpha.p, n_pad / TILE, n_pad / TILE, dpart, dgc.p, dgs.p, s, true,
-                           grad_param ? dgp.p : nullptr));
+                           grad_param ? dgp.p : nullptr, patch_ok));
   // gradient w.r.t. the input points: row-side contraction over every block pair; the spec is
   // symmetric (block (J, I) mirrors (I, J)) and so is G, hence the column side equals the row side of
   // the mirror block and the total is twice the row-side sum
@@ -2061,6 +2074,16 @@ int sgp::drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const dou
 }
 
 // include/sthenomi_kprod_grad.h: sgp_logpdf_grad_param_xs -- the same with the input points and the row scales
+// include/sthenomi_conv_grad.h: sgp_logpdf_grad_conv (its C entry point, in libsthenomi_conv_grad.so, forwards here)
+int sgp::drv_logpdf_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
+                              const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
+                              double* grad_coef, double* grad_inscale) {
+  return with_df_fallback(ctx, [&]() {
+    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                            grad_inscale, nullptr, nullptr, nullptr, false, true);
+  });
+}
+
 int sgp::drv_logpdf_grad_param_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
                                   const double* noise, const double* y, double* logpdf_out, double* grad_y, double* grad_mean,
                                   double* grad_noise, double* grad_coef, double* grad_inscale, double* grad_param,
@@ -3562,7 +3585,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
                           double* grad_inscale_xz, double* const* grad_inputs_zz, double* const* grad_inputs_xz,
                           double* const* grad_rowscale_zz = nullptr, double* const* grad_rowscale_xz = nullptr,
                           double* const* grad_colscale_xz = nullptr, const sgp::ElboGradShard* shard = nullptr,
-                          double* grad_param_zz = nullptr, double* grad_param_xz = nullptr, bool kprod_ok = false) {
+                          double* grad_param_zz = nullptr, double* grad_param_xz = nullptr, bool kprod_ok = false,
+                          bool patch_ok = false) {
   // shard (round 6, multi.hip: sgp_multi_elbo_grad): this call sees ONE rank's slice of the data points (xz, var_x, mean_x, a
   // diagonal noise_x, y and the per-point results are the slice's).  The sums over data points -- A A', A delta, the four
   // scalar sums -- are added up over the ranks by shard->reduce (every rank gets the total), the M x M stage runs replicated
@@ -3577,6 +3601,17 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   CHECK_RC(dspec_create(ctx, zz, &gz.ds));
   CHECK_RC(dspec_create(ctx, xz, &gx.ds));
   const long M = gz.ds->N, N = gx.ds->N;
+  // a patched side reads images, and gradients with respect to those are not formed (include/sthenomi_conv_grad.h)
+  auto images_unasked = [](const sgp_dspec* ds, double* const* want) {
+    for (size_t t = 0; want && t < ds->h_terms.size(); ++t) {
+      const DevTerm& T = ds->h_terms[t];
+      if ((T.hr && want[ds->term_row_input[t]]) || (T.hc && want[ds->term_col_input[t]])) return false;
+    }
+    return true;
+  };
+  CHECK_ARG(images_unasked(gz.ds, grad_inputs_zz) && images_unasked(gx.ds, grad_inputs_xz),
+            "sgp_elbo_grad_conv: an input read by a patch (convolutional) side holds images, and gradients with respect to "
+            "images are not supported: its grad_inputs entry must be NULL");
   CHECK_ARG(gx.ds->M == M, "sgp_elbo_grad: xz spec columns != number of inducing points");
   CHECK_ARG(M >= 1 && N >= 1, "sgp_elbo_grad: empty inputs");
   const long m_pad = rup(M, TILE), n_rows = rup(N, TILE);
@@ -3741,10 +3776,10 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   // ---- contractions against the flattened terms
   if (grad_coef_xz || grad_inscale_xz || grad_param_xz)
     CHECK_RC(contract_spec(gx.ds, dE.p, n_rows, nullptr, n_rows / TILE, m_pad / TILE, dpart, dgcx.p, dgsx.p, s, kprod_ok,
-                           dgpx.p));
+                           dgpx.p, patch_ok));
   if (grad_coef_zz || grad_inscale_zz || grad_param_zz)
     CHECK_RC(contract_spec(gz.ds, dGzz.p, m_pad, nullptr, m_pad / TILE, m_pad / TILE, dpart, dgcz.p, dgsz.p, s, kprod_ok,
-                           dgpz.p));
+                           dgpz.p, patch_ok));
   // ---- input points: zz is symmetric (twice the row side, as in logpdf_grad_core); xz is
   // rectangular: row side for the x inputs, and the transposed contraction for the z inputs
   std::vector<DevBuf> dgz(grad_inputs_zz ? zz->n_inputs : 0), dgxz(grad_inputs_xz ? xz->n_inputs : 0);
@@ -3770,6 +3805,14 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
     *out = v[t].p;
     return 0;
   };
+  // d / d (plain side's points) of the one-sided patch term t of pair (I, J), into that side's input (conv.hip)
+  auto patch_points = [&](const sgp_dspec* ds, const double* Gm, long ldgm, int I, int J, int t, std::vector<DevBuf>& into) -> int {
+    const DevTerm& T = ds->h_terms[t];
+    if (into.empty() || (T.hr && T.hc)) return 0;
+    const int k = T.hr ? ds->term_col_input[t] : ds->term_row_input[t];
+    return launch_grad_conv_points(Gm, ldgm, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J], ds->col_len[J], T,
+                                   ds->d_terms + t, 1.0, into[k].p, s);
+  };
   if (grad_inputs_zz || grad_rowscale_zz) {
     if (grad_inputs_zz) CHECK_RC(zero_inputs(dgz, gz.ds));
     const sgp_dspec* ds = gz.ds;
@@ -3780,6 +3823,11 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
         const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
         for (int t = ds->term_ptr[p]; t < t1;) {
           double* gsv = nullptr;
+          if (ds->h_terms[t].ph) {   // a patch term: the plain side of a one-sided one (its mirror pair gives the other role)
+            CHECK_RC(patch_points(ds, dGzz.p, m_pad, I, J, t, dgz));
+            ++t;
+            continue;
+          }
           CHECK_RC(scale_buf(drz, grad_rowscale_zz, ds, t, ds->h_terms[t].rs, ds->row_len[I], &gsv));
           if (t >= tk) {   // a chain: one pass for every factor's row input and the head's row scale (kprod.hip)
             const int e = chain_end(ds, t, t1);
@@ -3812,6 +3860,10 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
         for (int t = ds->term_ptr[p]; t < t1; ++t) {
           const DevTerm& T = ds->h_terms[t];
           double *gsr = nullptr, *gsc = nullptr;
+          if (T.ph) {   // a patch term: the plain side of a one-sided one
+            CHECK_RC(patch_points(ds, dE.p, n_rows, I, J, t, dgxz));
+            continue;
+          }
           CHECK_RC(scale_buf(drx, grad_rowscale_xz, ds, t, T.rs, ds->row_len[I], &gsr));
           CHECK_RC(scale_buf(dcx, grad_colscale_xz, ds, t, T.cs, ds->col_len[J], &gsc));
           if (t >= tk) {   // a chain: the row pass for x, the transposed pass for z, every factor in each (kprod.hip)
@@ -3923,9 +3975,11 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
 // the three entry points: one record of arguments; a multi-GPU context shards the data points over its ranks (round 6)
 static int elbo_grad_entry(sgp_ctx* ctx, const sgp::ElboGradArgs& a) {
   CHECK_ARG(ctx, "sgp_elbo_grad: NULL context");
+  CHECK_ARG(!(a.patch_ok && ctx->multi), "sgp_elbo_grad_conv: not supported on a multi-GPU context");
   CHECK_ARG(!spec_has_stencil(ctx, a.zz) && !spec_has_stencil(ctx, a.xz),
-            "sgp_elbo_grad: gradients through stencil terms are not supported");
-  CHECK_ARG(!spec_has_patch(a.zz) && !spec_has_patch(a.xz),
+            a.patch_ok ? "sgp_elbo_grad_conv: gradients through stencil terms are not supported"
+                       : "sgp_elbo_grad: gradients through stencil terms are not supported");
+  CHECK_ARG(a.patch_ok || (!spec_has_patch(a.zz) && !spec_has_patch(a.xz)),
             "sgp_elbo_grad: gradients through patch (convolutional) terms are not supported");
   CHECK_ARG(a.kprod_ok || (!spec_has_kprod(a.zz) && !spec_has_kprod(a.xz)),
             "sgp_elbo_grad: gradients through product chains and the RQ / LINEAR kinds are not supported: call "
@@ -3981,15 +4035,23 @@ extern "C" int sgp_elbo_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_
 #undef SGP_ELBO_GRAD_ARGS
 // include/sthenomi_kprod_grad.h: sgp_elbo_grad_param (its C entry point, in libsthenomi_kprod_grad.so, forwards here)
 int sgp::drv_elbo_grad_param(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
+// include/sthenomi_conv_grad.h: sgp_elbo_grad_conv (its C entry point, in libsthenomi_conv_grad.so, forwards here)
+int sgp::drv_elbo_grad_conv(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
 
 // sum_i w[i] d var_i / d theta over the diagonal of `spec` (the blocks (I, I) kernelmatrix_diag reads)
 static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
                           double* grad_inscale, double* const* grad_inputs, double* const* grad_rowscale = nullptr,
-                          double* const* grad_colscale = nullptr, double* grad_param = nullptr, bool kprod_ok = false) {
-  // (kprod_ok: sgp_kernelmatrix_diag_grad_param, include/sthenomi_kprod_grad.h -- every output may be NULL there)
+                          double* const* grad_colscale = nullptr, double* grad_param = nullptr, bool kprod_ok = false,
+                          bool patch_ok = false) {
+  // (kprod_ok: sgp_kernelmatrix_diag_grad_param, include/sthenomi_kprod_grad.h -- every output may be NULL there;
+  // patch_ok: sgp_kernelmatrix_diag_grad_conv, include/sthenomi_conv_grad.h)
   CHECK_ARG(ctx && spec && w && (kprod_ok || (grad_coef && grad_inscale)), "sgp_kernelmatrix_diag_grad: NULL argument");
-  CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_diag_grad: gradients through stencil terms are not supported");
-  CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_diag_grad: gradients through patch (convolutional) terms are not supported");
+  CHECK_ARG(!(patch_ok && ctx->multi), "sgp_kernelmatrix_diag_grad_conv: not supported on a multi-GPU context");
+  CHECK_ARG(!spec_has_stencil(ctx, spec),
+            patch_ok ? "sgp_kernelmatrix_diag_grad_conv: gradients through stencil terms are not supported"
+                     : "sgp_kernelmatrix_diag_grad: gradients through stencil terms are not supported");
+  CHECK_ARG(patch_ok || !spec_has_patch(spec),
+            "sgp_kernelmatrix_diag_grad: gradients through patch (convolutional) terms are not supported");
   CHECK_ARG(kprod_ok || !spec_has_kprod(spec),
             "sgp_kernelmatrix_diag_grad: gradients through product chains and the RQ / LINEAR kinds are not supported: call "
             "sgp_kernelmatrix_diag_grad_param (include/sthenomi_kprod_grad.h)");
@@ -4018,7 +4080,18 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
     SGP_HIP(hipMemsetAsync(dgp.p, 0, sizeof(double) * nt, s));
   }
   // the plain terms of a diagonal pair: [term_ptr, diag_tk); its product chains behind them (kprod.hip)
-  auto diag_tk = [&](int p) { return ds->n_kprod ? ds->term_ptr[p + 1] - ds->pair_nkprod[p] : ds->term_ptr[p + 1]; };
+  // (and, where the caller carries them, its patch terms between the two: [diag_tk, diag_tp), conv.hip)
+  auto diag_tp = [&](int p) { return ds->n_kprod ? ds->term_ptr[p + 1] - ds->pair_nkprod[p] : ds->term_ptr[p + 1]; };
+  auto diag_tk = [&](int p) { return ds->n_patch ? ds->term_ptr[p] + ds->pair_nplain[p] : diag_tp(p); };
+  DevBuf dpart;
+  if (ds->n_patch) CHECK_RC(dpart.alloc((size_t)2 * ds->N));
+  for (int I = 0; ds->n_patch && I < ds->nrb; ++I) {
+    const int p = I * ds->ncb + I;
+    if (ds->row_len[I] == 0 || ds->row_len[I] != ds->col_len[I]) continue;
+    for (int t = diag_tk(p); t < diag_tp(p); ++t)
+      CHECK_RC(launch_diag_grad_conv(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t], ds->d_terms + t, dpart.p,
+                                     dgc.p + t, dgs.p + t, s));
+  }
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag_grad: block lengths differ");
     int p = I * ds->ncb + I;
@@ -4078,7 +4151,7 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
     const long len = ds->row_len[I];
     const int p = I * ds->ncb + I, t1 = ds->term_ptr[p + 1];
     if (len == 0) continue;
-    for (int t = diag_tk(p); t < t1;) {
+    for (int t = diag_tp(p); t < t1;) {
       const int e = chain_end(ds, t, t1);
       double *o_r = nullptr, *o_c = nullptr;
       CHECK_RC(scale_bufs(t, len, &o_r, &o_c));
@@ -4129,6 +4202,12 @@ extern "C" int sgp_kernelmatrix_diag_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* s
 }
 
 // include/sthenomi_kprod_grad.h: sgp_kernelmatrix_diag_grad_param (its C entry point, in libsthenomi_kprod_grad.so, forwards here)
+// include/sthenomi_conv_grad.h: sgp_kernelmatrix_diag_grad_conv (its C entry point, in libsthenomi_conv_grad.so, forwards here)
+int sgp::drv_diag_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale) {
+  CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_conv: NULL argument");
+  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, nullptr, nullptr, nullptr, nullptr, true, true);
+}
+
 int sgp::drv_diag_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
                              double* grad_param, double* const* grad_inputs, double* const* grad_rowscale,
                              double* const* grad_colscale) {
@@ -4538,7 +4617,7 @@ int drv_elbo_grad(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shar
                           a.elbo_out, a.grad_y, a.grad_mean, a.grad_noise, a.grad_var_x, a.grad_z_noise, a.grad_coef_zz,
                           a.grad_inscale_zz, a.grad_coef_xz, a.grad_inscale_xz, a.grad_inputs_zz, a.grad_inputs_xz,
                           a.grad_rowscale_zz, a.grad_rowscale_xz, a.grad_colscale_xz, shard, a.grad_param_zz, a.grad_param_xz,
-                          a.kprod_ok);
+                          a.kprod_ok, a.patch_ok);
   };
   // (a rank of a sharded call cannot rerun on its own -- the reduction is collective: multi.hip reruns all of them)
   return shard ? run() : with_df_fallback(ctx, run);

@@ -134,6 +134,21 @@ int launch_assemble_conv(double* K, long ld, long r0, long nr, long c0, long nc,
 int launch_diag_conv(double* out, long n, const DevTerm* d_terms, int nplain, int nterms, int max_d, int d_all,
                      int max_pixels, hipStream_t s);
 
+// conv.hip, the gradient contractions against ONE patch term of a block pair (include/sthenomi_conv_grad.h); G as in
+// launch_grad_block (alpha != nullptr: (alpha alpha' - Gm) / 2, else Gm itself), indexed globally: entry (i, j) of the pair at
+// Gm[r0 + i + (c0 + j) * ldg].  out_coef[0] = sum_ij G_ij rs_i cs_j sum_pq k, out_scale[0] = sum_ij G_ij coef rs_i cs_j
+// sum_pq dk/dg; `partials` holds grad_conv_partials(nr, nc, T) doubles (per-workgroup sums, reduced in a fixed order)
+long grad_conv_partials(long nr, long nc, const DevTerm& T);
+int launch_grad_conv(const double* Gm, long ldg, const double* alpha, long r0, long nr, long c0, long nc, const DevTerm& T,
+                     const DevTerm* dterm, double* partials, double* out_coef, double* out_scale, hipStream_t s);
+// ... on the diagonal: sum_i w_i d var_i / d theta of one patch term; `partials`: 2 n doubles
+int launch_diag_grad_conv(const double* w, long n, const DevTerm& T, const DevTerm* dterm, double* partials, double* out_coef,
+                          double* out_scale, hipStream_t s);
+// ... with respect to the PLAIN side's points of a one-sided term: gz (ph pw x points, packed) += scale * the sum over the
+// images and their patches; one wave owns a point (no atomics)
+int launch_grad_conv_points(const double* Gm, long ldg, const double* alpha, long r0, long nr, long c0, long nc,
+                            const DevTerm& T, const DevTerm* dterm, double scale, double* gz, hipStream_t s);
+
 // stencil.hip: stencil terms of one block pair, one launch per term, arguments as launch_assemble_conv
 int launch_assemble_stencil(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm& T, const DevTerm* dterm,
                             int lower_only, int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,

@@ -19,7 +19,9 @@
 // is written afresh, fma(s, w, 0) (+ the noise on the diagonal) by its first patch term.
 #include "common.h"
 #include "kern_eval.h"
+#include "kern_grad.h"
 #include <algorithm>
+#include <string>
 
 // sums of kernel values are exact IEEE adds in a fixed order: no contraction of a kernel value's last product into them
 #pragma clang fp contract(off)
@@ -354,6 +356,404 @@ int launch_diag_conv(double* out, long n, const DevTerm* d_terms, int nplain, in
   SGP_CONV_DISPATCH(max_d == 9 ? 16 : max_d, SGP_DIAG_CALL);
 #undef SGP_DIAG_CALL
   return 0;
+}
+
+// ======================================================================================================================
+// Gradient contractions against a patch term (include/sthenomi_conv_grad.h).  With a cotangent G (grad.hip's two forms:
+// (alpha alpha' - Kinv) / 2 when alpha is given, else the matrix itself) and s_k = sum_pq k, s_d = sum_pq dk/dg |_{g=1}
+// of an entry -- both from one kern_and_dscale evaluation per pair of patches, summed in the assembly's order --
+//   grad_coef    = sum_ij G_ij rs_i cs_j s_k,        grad_inscale = sum_ij G_ij coef rs_i cs_j s_d.
+//   conv2_grad_kernel   both sides patched: a workgroup owns one row and 128 columns of the pair; its row image stays in
+//                       LDS, the column images come four at a time, one wave per entry as in conv2_kernel; every wave adds
+//                       its entries up in column order, the four waves are added in wave order: one partial per workgroup;
+//   conv1_grad_kernel   one side patched: conv1_kernel's work split (CONV1_IMG staged images x 256 CONV1_CC plain points);
+//                       a thread adds its entries up in image order, then wave butterfly + the four waves in order;
+//   conv_diag_grad_kernel  one wave per diagonal entry, the sums by the same device functions; one partial per entry;
+//   conv_grad_reduce_kernel  partials -> the two outputs, 256 strided sums and a fixed tree (grad_reduce_kernel's order);
+//   conv1_points_kernel  d / d (plain side's points) of a one-sided term: one wave owns one plain point z_j, walks every
+//                       image (staged CONV1_IMG at a time), lanes take the patches p = lane, lane + 64, ..., a butterfly
+//                       per coordinate at the end: every output column is written by one wave -- no atomics.
+// Nothing here depends on the launch order of other workgroups: two calls give the same bits.
+// ======================================================================================================================
+template <int DMAX>
+__device__ __forceinline__ double pair_d2(const double (&r)[DMAX], const double (&c)[DMAX]) {
+  double d2 = 0.0;
+#pragma unroll
+  for (int d = 0; d < DMAX; ++d) {
+    const double df = r[d] - c[d];
+    d2 = fma(df, df, d2);
+  }
+  return d2;
+}
+
+__device__ __forceinline__ double cotangent(const double* Gm, long ld, const double* alpha, long r, long c) {
+  return alpha ? 0.5 * (alpha[r] * alpha[c] - Gm[r + c * ld]) : Gm[r + c * ld];
+}
+
+// conv2_sum with the derivative beside the value
+template <int DMAX, bool EXACT>
+__device__ __forceinline__ void conv2_sum_kd(const double* imr, const ConvSide& gr, const int (&offr)[DMAX], const double* imc,
+                                             const ConvSide& gc, const int (&offc)[DMAX], int D, int kind, double param,
+                                             int lane, double& sk, double& sd) {
+  sk = sd = 0.0;
+  for (int p = lane; p < gr.np; p += 64) {
+    double a[DMAX];
+    load_patch<DMAX, EXACT>(a, imr, (p % gr.np_r) + (p / gr.np_r) * gr.h, offr, D);
+    for (int qc = 0, base0 = 0; qc < gc.np / gc.np_r; ++qc, base0 += gc.h) {
+#pragma unroll 2
+      for (int qr = 0; qr < gc.np_r; ++qr) {
+        double b[DMAX], k, dk;
+        load_patch<DMAX, EXACT>(b, imc, base0 + qr, offc, D);
+        kern_and_dscale(kind, pair_d2<DMAX>(a, b), param, k, dk);
+        sk = sk + k;
+        sd = sd + dk;
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sk = sk + __shfl_xor(sk, m, 64);
+    sd = sd + __shfl_xor(sd, m, 64);
+  }
+}
+
+// conv1_sums with the derivative beside the value (the kernels are symmetric in their arguments: no orientation)
+template <int DMAX, bool EXACT, int CC>
+__device__ __forceinline__ void conv1_sums_kd(double (&sk)[CC], double (&sd)[CC], const double* img, const ConvSide& g,
+                                              const int (&off)[DMAX], int D, const double (&pt)[CC][DMAX], int kind,
+                                              double param) {
+  for (int pc = 0, base0 = 0; pc < g.np / g.np_r; ++pc, base0 += g.h) {
+    for (int pr = 0; pr < g.np_r; ++pr) {
+      double a[DMAX];
+      load_patch<DMAX, EXACT>(a, img, base0 + pr, off, D);
+#pragma unroll
+      for (int k = 0; k < CC; ++k) {
+        double kv, dk;
+        kern_and_dscale(kind, pair_d2<DMAX>(a, pt[k]), param, kv, dk);
+        sk[k] = sk[k] + kv;
+        sd[k] = sd[k] + dk;
+      }
+    }
+  }
+}
+
+// the four waves' sums (a, b), identical in every lane of a wave, added in wave order into partials[2 blk], [2 blk + 1]
+__device__ __forceinline__ void block_partial(double a, double b, double* red /* 8 doubles of LDS */, double* partials, long blk,
+                                              int t) {
+  __syncthreads();
+  if ((t & 63) == 0) {
+    red[(t >> 6) * 2 + 0] = a;
+    red[(t >> 6) * 2 + 1] = b;
+  }
+  __syncthreads();
+  if (t < 2) partials[blk * 2 + t] = ((red[t] + red[2 + t]) + red[4 + t]) + red[6 + t];
+}
+
+template <int DMAX, bool EXACT>
+__global__ __launch_bounds__(256) void conv2_grad_kernel(const double* __restrict__ Gm, long ldg,
+                                                         const double* __restrict__ alpha, long r0, long nr, long c0,
+                                                         long nc, const DevTerm* __restrict__ terms,
+                                                         double* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const DevTerm T = terms[0];
+  const int HWr = T.hr * T.wr, HWc = T.hc * T.wc, D = T.ph * T.pw;
+  double* red = smem + HWr + CONV2_WAVES * HWc;                 // 8 doubles behind the images (all of the LDS is dynamic)
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const long lr = blockIdx.x;                                   // row within the pair (< nr: the grid)
+  const long lc_beg = (long)blockIdx.y * TILE, lc_end = std::min<long>(nc, lc_beg + TILE);
+  const ConvSide gr = conv_side(T.hr, T.wr, T.ph, T.pw), gc = conv_side(T.hc, T.wc, T.ph, T.pw);
+  int offr[DMAX], offc[DMAX];
+  patch_offsets<DMAX>(offr, T.ph, T.hr, D);
+  patch_offsets<DMAX>(offc, T.ph, T.hc, D);
+  stage(smem, T.xr + lr * (long)HWr, HWr, t, 256);
+  const double wr = T.rs ? T.rs[lr] : 1.0;
+  double a = 0.0, b = 0.0;
+  for (long lc0 = lc_beg; lc0 < lc_end; lc0 += CONV2_WAVES) {
+    const int ncol = (int)std::min<long>(CONV2_WAVES, lc_end - lc0);
+    __syncthreads();     // the previous group's images are no longer read
+    for (int k = 0; k < ncol; ++k) stage(smem + HWr + k * HWc, T.xc + (lc0 + k) * (long)HWc, HWc, t, 256);
+    __syncthreads();
+    if (wv < ncol) {
+      const long lc = lc0 + wv;
+      double sk, sd;
+      conv2_sum_kd<DMAX, EXACT>(smem, gr, offr, smem + HWr + wv * HWc, gc, offc, D, T.kind, T.param, lane, sk, sd);
+      const double w = (cotangent(Gm, ldg, alpha, r0 + lr, c0 + lc) * wr) * (T.cs ? T.cs[lc] : 1.0);
+      a = fma(w, sk, a);
+      b = fma(w * T.coef, sd, b);
+    }
+  }
+  block_partial(a, b, red, partials, (long)blockIdx.y * gridDim.x + blockIdx.x, t);
+}
+
+template <int DMAX, bool EXACT>
+__global__ __launch_bounds__(256) void conv1_grad_kernel(const double* __restrict__ Gm, long ldg,
+                                                         const double* __restrict__ alpha, long r0, long nr, long c0,
+                                                         long nc, const DevTerm* __restrict__ terms,
+                                                         double* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const DevTerm T = terms[0];
+  const bool row_img = T.hr > 0;
+  const int H = row_img ? T.hr : T.hc, W = row_img ? T.wr : T.wc, HW = H * W;
+  double* red = smem + CONV1_IMG * HW;                           // 8 doubles behind the images
+  const int D = T.ph * T.pw;
+  const long na = row_img ? nr : nc, nb = row_img ? nc : nr;     // images / plain points of the pair (local indices)
+  const double* ximg = row_img ? T.xr : T.xc;
+  const double* xpt = row_img ? T.xc : T.xr;
+  const long ldpt = row_img ? T.ldc : T.ldr;
+  const int t = threadIdx.x;
+  const long a_first = (long)blockIdx.x * CONV1_IMG;
+  const int nimg = (int)std::min<long>(CONV1_IMG, na - a_first);
+  for (int k = 0; k < nimg; ++k) stage(smem + k * HW, ximg + (a_first + k) * (long)HW, HW, t, 256);
+  __syncthreads();
+  long bl[CONV1_CC];
+  double pt[CONV1_CC][DMAX];
+#pragma unroll
+  for (int k = 0; k < CONV1_CC; ++k) {
+    bl[k] = (long)blockIdx.y * (256 * CONV1_CC) + t + 256 * k;
+    load_point<DMAX, EXACT>(pt[k], xpt + (bl[k] < nb ? bl[k] : 0) * ldpt, D);   // (out of range: a valid point, weight 0)
+  }
+  const ConvSide g = conv_side(H, W, T.ph, T.pw);
+  int off[DMAX];
+  patch_offsets<DMAX>(off, T.ph, H, D);
+  double a = 0.0, b = 0.0;
+  if (bl[0] < nb) {
+    for (int k = 0; k < nimg; ++k) {
+      const long al = a_first + k;
+      double sk[CONV1_CC], sd[CONV1_CC];
+#pragma unroll
+      for (int j = 0; j < CONV1_CC; ++j) sk[j] = sd[j] = 0.0;
+      conv1_sums_kd<DMAX, EXACT, CONV1_CC>(sk, sd, smem + k * HW, g, off, D, pt, T.kind, T.param);
+#pragma unroll
+      for (int j = 0; j < CONV1_CC; ++j) {
+        if (bl[j] >= nb) continue;
+        const long lr = row_img ? al : bl[j], lc = row_img ? bl[j] : al;
+        const double w = (cotangent(Gm, ldg, alpha, r0 + lr, c0 + lc) * (T.rs ? T.rs[lr] : 1.0)) * (T.cs ? T.cs[lc] : 1.0);
+        a = fma(w, sk[j], a);
+        b = fma(w * T.coef, sd[j], b);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    a = a + __shfl_xor(a, m, 64);
+    b = b + __shfl_xor(b, m, 64);
+  }
+  block_partial(a, b, red, partials, (long)blockIdx.y * gridDim.x + blockIdx.x, t);
+}
+
+// sum_i w_i d var_i / d theta of ONE patch term of a diagonal pair: partials[2 i] / [2 i + 1] per entry
+template <int DMAX, bool EXACT>
+__global__ __launch_bounds__(64) void conv_diag_grad_kernel(const double* __restrict__ w, long n,
+                                                            const DevTerm* __restrict__ terms,
+                                                            double* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const DevTerm T = terms[0];
+  const long i = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int HWr = T.hr * T.wr, HWc = T.hc * T.wc, D = T.ph * T.pw;
+  if (T.hr) stage(smem, T.xr + i * (long)HWr, HWr, lane, 64);
+  if (T.hc) stage(smem + HWr, T.xc + i * (long)HWc, HWc, lane, 64);
+  __syncthreads();
+  const ConvSide gr = conv_side(T.hr, T.wr, T.ph, T.pw), gc = conv_side(T.hc, T.wc, T.ph, T.pw);
+  double sk, sd;
+  if (T.hr && T.hc) {
+    int offr[DMAX], offc[DMAX];
+    patch_offsets<DMAX>(offr, T.ph, T.hr, D);
+    patch_offsets<DMAX>(offc, T.ph, T.hc, D);
+    conv2_sum_kd<DMAX, EXACT>(smem, gr, offr, smem + HWr, gc, offc, D, T.kind, T.param, lane, sk, sd);
+  } else {   // one side: every lane runs the sum of conv1_grad_kernel's thread for this entry
+    const bool row_img = T.hr > 0;
+    int off[DMAX];
+    patch_offsets<DMAX>(off, T.ph, row_img ? T.hr : T.hc, D);
+    double pt[1][DMAX], s1[1] = {0.0}, s2[1] = {0.0};
+    load_point<DMAX, EXACT>(pt[0], row_img ? T.xc + i * T.ldc : T.xr + i * T.ldr, D);
+    conv1_sums_kd<DMAX, EXACT, 1>(s1, s2, row_img ? smem : smem + HWr, row_img ? gr : gc, off, D, pt, T.kind, T.param);
+    sk = s1[0], sd = s2[0];
+  }
+  if (lane == 0) {
+    const double ww = (w[i] * (T.rs ? T.rs[i] : 1.0)) * (T.cs ? T.cs[i] : 1.0);
+    partials[2 * i] = ww * sk;
+    partials[2 * i + 1] = (ww * T.coef) * sd;
+  }
+}
+
+// out_coef[0] / out_scale[0] = sum_b partials[2 b] / [2 b + 1] in a fixed order (blockIdx.x: the component)
+__global__ __launch_bounds__(256) void conv_grad_reduce_kernel(const double* __restrict__ partials, long nblocks,
+                                                               double* out_coef, double* out_scale) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (long b = threadIdx.x; b < nblocks; b += 256) s += partials[b * 2 + blockIdx.x];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *(blockIdx.x ? out_scale : out_coef) = sh[0];
+}
+
+// gz[:, j] += scale sum_i G_ij coef rs_i cs_j sum_p 2 kappa'(|patch_p x_i - z_j|^2) (z_j - patch_p x_i)  (gz: D x nb, packed)
+template <int DMAX, bool EXACT>
+__global__ __launch_bounds__(256) void conv1_points_kernel(const double* __restrict__ Gm, long ldg,
+                                                           const double* __restrict__ alpha, long r0, long nr, long c0,
+                                                           long nc, const DevTerm* __restrict__ terms, double scale,
+                                                           double* __restrict__ gz) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const DevTerm T = terms[0];
+  const bool row_img = T.hr > 0;
+  const int H = row_img ? T.hr : T.hc, W = row_img ? T.wr : T.wc, HW = H * W;
+  const int D = T.ph * T.pw;
+  const long na = row_img ? nr : nc, nb = row_img ? nc : nr;
+  const double* ximg = row_img ? T.xr : T.xc;
+  const double* xpt = row_img ? T.xc : T.xr;
+  const long ldpt = row_img ? T.ldc : T.ldr;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const long bl = (long)blockIdx.x * CONV2_WAVES + wv;           // this wave's plain point
+  const bool live = bl < nb;
+  double z[DMAX], acc[DMAX];
+  load_point<DMAX, EXACT>(z, xpt + (live ? bl : 0) * ldpt, D);
+#pragma unroll
+  for (int d = 0; d < DMAX; ++d) acc[d] = 0.0;
+  const ConvSide g = conv_side(H, W, T.ph, T.pw);
+  int off[DMAX];
+  patch_offsets<DMAX>(off, T.ph, H, D);
+  for (long a_first = 0; a_first < na; a_first += CONV1_IMG) {
+    const int nimg = (int)std::min<long>(CONV1_IMG, na - a_first);
+    __syncthreads();     // the previous images are no longer read
+    for (int k = 0; k < nimg; ++k) stage(smem + k * HW, ximg + (a_first + k) * (long)HW, HW, t, 256);
+    __syncthreads();
+    if (!live) continue;
+    for (int k = 0; k < nimg; ++k) {
+      const long al = a_first + k;
+      const long lr = row_img ? al : bl, lc = row_img ? bl : al;
+      const double w = 2.0 * cotangent(Gm, ldg, alpha, r0 + lr, c0 + lc) * entry_weight(T, lr, lc);
+      for (int p = lane; p < g.np; p += 64) {
+        double a[DMAX], df[DMAX], d2 = 0.0, kv, kx;
+        load_patch<DMAX, EXACT>(a, smem + k * HW, (p % g.np_r) + (p / g.np_r) * g.h, off, D);
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) {
+          df[d] = z[d] - a[d];
+          d2 = fma(df[d], df[d], d2);
+        }
+        kern_val_dd2(T.kind, d2, T.param, kv, kx);
+        const double wk = w * kx;
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) acc[d] = fma(wk, df[d], acc[d]);
+      }
+    }
+  }
+  if (!live) return;
+#pragma unroll
+  for (int d = 0; d < DMAX; ++d) {
+    double v = acc[d];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    if (lane == 0 && d < D) gz[bl * D + d] += scale * v;
+  }
+}
+
+static int conv_term_check(const DevTerm& T, const char* who) {
+  const int D = T.ph * T.pw;
+  if (!(T.hr || T.hc) || D < 1 || D > CONV_MAX_PATCH || T.hr * T.wr > CONV_MAX_PIXELS || T.hc * T.wc > CONV_MAX_PIXELS) {
+    set_error(std::string(who) + ": not a patch term within the limits of include/sthenomi_conv.h");
+    return -1;
+  }
+  return 0;
+}
+
+long grad_conv_partials(long nr, long nc, const DevTerm& T) {
+  if (T.hr && T.hc) return 2 * nr * ((nc + TILE - 1) / TILE);
+  const long na = T.hr ? nr : nc, nb = T.hr ? nc : nr;
+  return 2 * ((na + CONV1_IMG - 1) / CONV1_IMG) * ((nb + 256 * CONV1_CC - 1) / (256 * CONV1_CC));
+}
+
+template <int DMAX, bool EXACT>
+static int launch_grad_conv_t(const double* Gm, long ldg, const double* alpha, long r0, long nr, long c0, long nc,
+                              const DevTerm& T, const DevTerm* dterm, double* partials, hipStream_t s) {
+  if (T.hr && T.hc) {
+    const size_t lds = sizeof(double) * ((size_t)T.hr * T.wr + (size_t)CONV2_WAVES * T.hc * T.wc + 8);
+    SGP_LDS_ATTR_ONCE((conv2_grad_kernel<DMAX, EXACT>), 160 * 1024);
+    dim3 grid((unsigned)nr, (unsigned)((nc + TILE - 1) / TILE));
+    hipLaunchKernelGGL((conv2_grad_kernel<DMAX, EXACT>), grid, dim3(256), lds, s, Gm, ldg, alpha, r0, nr, c0, nc, dterm,
+                       partials);
+  } else {
+    const bool row_img = T.hr > 0;
+    const long na = row_img ? nr : nc, nb = row_img ? nc : nr;
+    const size_t lds = sizeof(double) * ((size_t)CONV1_IMG * (row_img ? T.hr * T.wr : T.hc * T.wc) + 8);
+    SGP_LDS_ATTR_ONCE((conv1_grad_kernel<DMAX, EXACT>), 160 * 1024);
+    dim3 grid((unsigned)((na + CONV1_IMG - 1) / CONV1_IMG), (unsigned)((nb + 256 * CONV1_CC - 1) / (256 * CONV1_CC)));
+    hipLaunchKernelGGL((conv1_grad_kernel<DMAX, EXACT>), grid, dim3(256), lds, s, Gm, ldg, alpha, r0, nr, c0, nc, dterm,
+                       partials);
+  }
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_grad_conv(const double* Gm, long ldg, const double* alpha, long r0, long nr, long c0, long nc, const DevTerm& T,
+                     const DevTerm* dterm, double* partials, double* out_coef, double* out_scale, hipStream_t s) {
+  if (nr <= 0 || nc <= 0) return 0;
+  if (conv_term_check(T, "grad")) return -1;
+  int rc = 0;
+#define SGP_CONV_CALL(DM, EX) rc = launch_grad_conv_t<DM, EX>(Gm, ldg, alpha, r0, nr, c0, nc, T, dterm, partials, s)
+  SGP_CONV_DISPATCH(T.ph * T.pw, SGP_CONV_CALL);
+#undef SGP_CONV_CALL
+  if (rc) return rc;
+  hipLaunchKernelGGL(conv_grad_reduce_kernel, dim3(2), dim3(256), 0, s, partials, grad_conv_partials(nr, nc, T) / 2, out_coef,
+                     out_scale);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+template <int DMAX, bool EXACT>
+static int launch_diag_grad_conv_t(const double* w, long n, const DevTerm& T, const DevTerm* dterm, double* partials,
+                                   hipStream_t s) {
+  const size_t lds = sizeof(double) * (size_t)std::max(1, T.hr * T.wr + T.hc * T.wc);
+  SGP_LDS_ATTR_ONCE((conv_diag_grad_kernel<DMAX, EXACT>), 160 * 1024);
+  hipLaunchKernelGGL((conv_diag_grad_kernel<DMAX, EXACT>), dim3((unsigned)n), dim3(64), lds, s, w, n, dterm, partials);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_diag_grad_conv(const double* w, long n, const DevTerm& T, const DevTerm* dterm, double* partials /* 2 n */,
+                          double* out_coef, double* out_scale, hipStream_t s) {
+  if (n <= 0) return 0;
+  if (conv_term_check(T, "kernelmatrix_diag_grad")) return -1;
+  int rc = 0;
+#define SGP_CONV_CALL(DM, EX) rc = launch_diag_grad_conv_t<DM, EX>(w, n, T, dterm, partials, s)
+  SGP_CONV_DISPATCH(T.ph * T.pw, SGP_CONV_CALL);
+#undef SGP_CONV_CALL
+  if (rc) return rc;
+  hipLaunchKernelGGL(conv_grad_reduce_kernel, dim3(2), dim3(256), 0, s, partials, n, out_coef, out_scale);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+template <int DMAX, bool EXACT>
+static int launch_grad_conv_points_t(const double* Gm, long ldg, const double* alpha, long r0, long nr, long c0, long nc,
+                                     const DevTerm& T, const DevTerm* dterm, double scale, double* gz, hipStream_t s) {
+  const bool row_img = T.hr > 0;
+  const long nb = row_img ? nc : nr;
+  const size_t lds = sizeof(double) * (size_t)CONV1_IMG * (row_img ? T.hr * T.wr : T.hc * T.wc);
+  SGP_LDS_ATTR_ONCE((conv1_points_kernel<DMAX, EXACT>), 160 * 1024);
+  hipLaunchKernelGGL((conv1_points_kernel<DMAX, EXACT>), dim3((unsigned)((nb + CONV2_WAVES - 1) / CONV2_WAVES)), dim3(256), lds,
+                     s, Gm, ldg, alpha, r0, nr, c0, nc, dterm, scale, gz);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_grad_conv_points(const double* Gm, long ldg, const double* alpha, long r0, long nr, long c0, long nc,
+                            const DevTerm& T, const DevTerm* dterm, double scale, double* gz, hipStream_t s) {
+  if (nr <= 0 || nc <= 0) return 0;
+  if (conv_term_check(T, "grad (points)")) return -1;
+  if (T.hr && T.hc) {
+    set_error("grad (points): both sides of the term are patched");
+    return -1;
+  }
+  int rc = 0;
+#define SGP_CONV_CALL(DM, EX) rc = launch_grad_conv_points_t<DM, EX>(Gm, ldg, alpha, r0, nr, c0, nc, T, dterm, scale, gz, s)
+  SGP_CONV_DISPATCH(T.ph * T.pw, SGP_CONV_CALL);
+#undef SGP_CONV_CALL
+  return rc;
 }
 
 }  // namespace sgp

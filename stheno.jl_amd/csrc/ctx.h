@@ -68,6 +68,8 @@ struct ElboGradArgs {
   // sgp_elbo_grad_param (include/sthenomi_kprod_grad.h): d / d param per term, and the leave to carry product chains
   double *grad_param_zz = nullptr, *grad_param_xz = nullptr;
   bool kprod_ok = false;
+  // sgp_elbo_grad_conv (include/sthenomi_conv_grad.h): the leave to carry patch terms
+  bool patch_ok = false;
 };
 struct ElboGradShard {
   bool primary = false;   // the rank that also produces the zz-side results (G_zz and its contractions)

@@ -44,7 +44,8 @@ def _refuse_patch_gradient(*specs):
     if any(sp.has_stencil for sp in specs):
         raise NotImplementedError("gradients through stencil covariance terms are not supported")
     if any(sp.has_patch for sp in specs):
-        raise NotImplementedError("gradients through patch_convolve (convolutional) covariance terms are not supported")
+        raise NotImplementedError("gradients through patch_convolve (convolutional) covariance terms are not supported "
+                                  "here: call logpdf_and_gradient_conv / elbo_and_gradient_conv")
 
 
 def _refuse_product_gradient(what, *specs):
@@ -616,6 +617,45 @@ def logpdf_and_gradient_param(fx, y, inputs=False, scales=False):
     return rec
 
 
+def _refuse_conv_family(what, *specs):
+    """what the entry points of include/sthenomi_conv_grad.h refuse: a multi-GPU context, stencil terms"""
+    if getattr(_ctx(), "is_multi", False):
+        raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
+    if any(sp.has_stencil for sp in specs):
+        raise NotImplementedError(f"{what}: gradients through stencil covariance terms are not supported")
+    if any(sp.has_patch for sp in specs) and any(sp.has_kprod for sp in specs):
+        raise NotImplementedError(f"{what}: a model with both patch_convolve terms and a product of kernels is not "
+                                  "supported (the records of a product carry d_param, which these calls do not return)")
+
+
+def logpdf_and_gradient_conv(fx, y):
+    """logpdf_and_gradient(fx, y) for every model it takes AND for models with patch_convolve (convolutional) terms, through
+    sgp_logpdf_grad_conv (include/sthenomi_conv_grad.h): the same dict -- logpdf, y, mean, noise, and one record per
+    flattened term of the lower block pairs with d_coef / d_inscale (the mirror pair folded in).  For a patch term
+    coef rs cs sum_pq k(patch_p x, patch_q x') the record's d_coef is the derivative w.r.t. that coefficient (the kernel's
+    variance times the model's scalings) and d_inscale the derivative w.r.t. a common scale g of the images (a scalar stretch
+    under patch_convolve; a lengthscale l = 1 / g gives d / dl = -g^2 d_inscale), exactly as for a plain term; the record also
+    carries row_geom / col_geom.  No inputs / scales: gradients with respect to images are not formed.  Single-GPU contexts,
+    no stencil terms."""
+    if not _is_prior(fx.f):
+        raise NotImplementedError("gradients are implemented for prior Stheno processes")
+    n = len(fx)
+    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+    spec = _prior_spec(fx.f, fx.x)
+    _refuse_conv_family("logpdf_and_gradient_conv", spec)
+    if spec.has_kprod:
+        return logpdf_and_gradient(fx, y)
+    m = _f64(mean_vector(fx.f, fx.x))
+    kind, nbuf = _lib._noise_args(fx.noise, n)
+    lp = np.zeros(1)
+    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
+    rc = _ctx().conv_grad.sgp_logpdf_grad_conv(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf), _lib.dptr(yv),
+                                               _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn), _lib.dptr(gc),
+                                               _lib.dptr(gs))
+    _lib.check(rc, "sgp_logpdf_grad_conv")
+    return _grad_record(spec, kind, lp[0], bufs)
+
+
 def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
     """[logpdf_and_gradient(fx, y) for fx, y in zip(fxs, ys)] in ONE library call (sgp_logpdf_grad_batch): the step of several
     independent hyper-parameter chains at once -- restarts, cross-validation folds, a population of candidates.  Members of one
@@ -1112,22 +1152,25 @@ def _term_records(spec, gc, gs, symmetric, gp=None):
     nrb, ncb = len(spec.row_len), len(spec.col_len)
     tp, out, index = spec._term_ptr, [], {}
     sid = spec.term_scale_ids
+    geo = [tuple(g) for g in spec.term_geoms]        # a patch term's geometries (None, None for a plain one) are part of it
     for I in range(nrb):
         for J in range(ncb):
             for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
                 T = spec._terms[t]
                 if symmetric and I < J:
                     continue
-                index[(I, J, T.kind, T.row_input, T.col_input, T.param, sid[t][0], sid[t][1])] = len(out)
+                index[(I, J, T.kind, T.row_input, T.col_input, T.param, sid[t][0], sid[t][1]) + geo[t]] = len(out)
                 out.append(dict(I=I, J=J, kind=T.kind, coef=T.coef, row_input=T.row_input, col_input=T.col_input,
                                 row_scaled=sid[t][0] is not None, col_scaled=sid[t][1] is not None,
                                 t=t, mirror_t=None, d_coef=float(gc[t]), d_inscale=float(gs[t])))
+                if spec.has_patch:
+                    out[-1].update(row_geom=geo[t][0], col_geom=geo[t][1])
     if symmetric:
         for I in range(nrb):
             for J in range(I + 1, ncb):
                 for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
                     T = spec._terms[t]
-                    k = index.get((J, I, T.kind, T.col_input, T.row_input, T.param, sid[t][1], sid[t][0]))
+                    k = index.get((J, I, T.kind, T.col_input, T.row_input, T.param, sid[t][1], sid[t][0]) + geo[t][::-1])
                     if k is None:
                         raise AssertionError("symmetric spec without a mirror term: flattener invariant broken")
                     out[k]["mirror_t"] = t
@@ -1227,6 +1270,70 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
                 xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx,
                 scales=(_scale_records(zz, srz, more=((xz, srx, "row"), (xz, scx, "col"), (xx, sdr, "row"), (xx, sdc, "col")))
                         if scales else None),
+                _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
+                _specs=dict(zz=zz, xz=xz, xx=xx))
+
+
+def _patched_inputs(spec):
+    """the inputs of `spec` that a patched side reads: they hold images"""
+    out = set()
+    for t, (rg, cg) in enumerate(spec.term_geoms):
+        if rg is not None:
+            out.add(int(spec._terms[t].row_input))
+        if cg is not None:
+            out.add(int(spec._terms[t].col_input))
+    return out
+
+
+def elbo_and_gradient_conv(vfe, fx, y=None, inputs=False):
+    """elbo_and_gradient for every model it takes (without a product of kernels) AND for models with patch_convolve
+    (convolutional) terms, through sgp_elbo_grad_conv and sgp_kernelmatrix_diag_grad_conv (include/sthenomi_conv_grad.h): the
+    same dict (see elbo_and_gradient; `scales` is None).  inputs=True adds zz_inputs / xz_inputs -- an entry that holds images
+    (an input read by a patched side) is None -- and `z`: the gradient with respect to the inducing points, block by block
+    of fz.x, for the blocks no patched side reads (the inducing patches of the plain process under patch_convolve); the
+    other blocks are zeros.  `x` is None: gradients with respect to the observed images are not formed.  Single-GPU
+    contexts, no stencil terms."""
+    if isinstance(vfe, SparseFiniteGP):
+        return elbo_and_gradient_conv(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs)
+    zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
+    n, m = len(fx), len(vfe.fz)
+    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+    xx = _prior_spec(fx.f, fx.x)
+    _refuse_conv_family("elbo_and_gradient_conv", zz, xz, xx)
+    _refuse_product_gradient("elbo_and_gradient_conv", zz, xz, xx)
+    var_x = _f64(_kernelmatrix_diag(xx))
+    out = np.zeros(1)
+    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
+    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
+    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
+    gcz, gsz = np.zeros(max(1, zz.n_terms)), np.zeros(max(1, zz.n_terms))
+    gcx, gsx = np.zeros(max(1, xz.n_terms)), np.zeros(max(1, xz.n_terms))
+    lib = _ctx().conv_grad
+    gxz = gxx = pz = px = None
+    if inputs:
+        gxz = [None if k in _patched_inputs(zz) else np.zeros(a.shape, order="F") for k, a in enumerate(zz.inputs)]
+        gxx = [None if k in _patched_inputs(xz) else np.zeros(a.shape, order="F") for k, a in enumerate(xz.inputs)]
+        pz = (C.POINTER(C.c_double) * max(1, len(gxz)))(*[_lib.dptr(a) for a in gxz])
+        px = (C.POINTER(C.c_double) * max(1, len(gxx)))(*[_lib.dptr(a) for a in gxx])
+    rc = lib.sgp_elbo_grad_conv(_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(var_x), _lib.dptr(mean_x), nk, _lib.dptr(nbuf), zk,
+                                _lib.dptr(zbuf), _lib.dptr(yv), _lib.dptr(out), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
+                                _lib.dptr(gv), _lib.dptr(gzn), _lib.dptr(gcz), _lib.dptr(gsz), _lib.dptr(gcx), _lib.dptr(gsx),
+                                pz, px)
+    _lib.check(rc, "sgp_elbo_grad_conv")
+    gcd, gsd = np.zeros(max(1, xx.n_terms)), np.zeros(max(1, xx.n_terms))
+    rc = lib.sgp_kernelmatrix_diag_grad_conv(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd))
+    _lib.check(rc, "sgp_kernelmatrix_diag_grad_conv")
+    nb = len(xx.row_len)
+    xx_terms = [r for r in _term_records(xx, gcd, gsd, False) if r["I"] == r["J"]] if nb else []
+    zb = None
+    if inputs:   # chain rule back onto the blocks of fz.x
+        zr, _ = chain_input_gradients(zz, gxz)
+        _, zc = chain_input_gradients(xz, gxx)
+        zb = [a + b for a, b in zip(zr, zc)]
+    return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=None, z=zb,
+                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
+                zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
+                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx, scales=None,
                 _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
                 _specs=dict(zz=zz, xz=xz, xx=xx))
 

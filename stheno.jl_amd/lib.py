@@ -22,6 +22,7 @@ EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so
 POSTFX_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_postfx.so")
 VFE_UPDATE_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_vfe_update.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
+CONV_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv_grad.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
 KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
 KPROD_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod_grad.so")
@@ -288,6 +289,22 @@ _SIGS_KPROD_GRAD = {
 }
 
 
+# include/sthenomi_conv_grad.h: sgp_logpdf_grad / sgp_kernelmatrix_diag_grad / sgp_elbo_grad_x with patch terms carried through,
+# exported by libsthenomi_conv_grad.so -- logpdf_and_gradient_conv and elbo_and_gradient_conv reach them through
+# conv_grad_lib() / Context.conv_grad
+_SIGS_CONV_GRAD = {
+    "sgp_logpdf_grad_conv": (C.c_int, [_P, _SPEC, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D]),
+    "sgp_kernelmatrix_diag_grad_conv": (C.c_int, [_P, _SPEC, _D, _D, _D]),
+    "sgp_elbo_grad_conv": (C.c_int, [_P, _SPEC, _SPEC, _D, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D,
+                                     _D, _D, _D, _D, _DD, _DD]),
+}
+
+
+def conv_grad_symbols():
+    """Names include/sthenomi_conv_grad.h declares: the entry points of libsthenomi_conv_grad.so."""
+    return sorted(_SIGS_CONV_GRAD)
+
+
 def kprod_grad_symbols():
     """Names include/sthenomi_kprod_grad.h declares: the entry points of libsthenomi_kprod_grad.so."""
     return sorted(_SIGS_KPROD_GRAD)
@@ -513,6 +530,27 @@ def conv_lib():
         return lib
 
 
+_conv_grad = None
+
+
+def conv_grad_lib():
+    """dlopen libsthenomi_conv_grad.so (include/sthenomi_conv_grad.h) after the product library it links against."""
+    global _conv_grad
+    load()
+    with _lib_lock:
+        if _conv_grad is not None:
+            return _conv_grad
+        if not os.path.exists(CONV_GRAD_LIB_PATH):
+            raise SthenoMIError(f"{CONV_GRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(CONV_GRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_CONV_GRAD.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _conv_grad = lib
+        return lib
+
+
 _stencil = None
 
 
@@ -665,6 +703,11 @@ class Context:
     def kprod_grad(self):
         """libsthenomi_kprod_grad.so (sthenomi_kprod_grad.h): `ctx.kprod_grad.sgp_elbo_grad_param(ctx.handle, ...)`"""
         return kprod_grad_lib()
+
+    @property
+    def conv_grad(self):
+        """libsthenomi_conv_grad.so (sthenomi_conv_grad.h): `ctx.conv_grad.sgp_logpdf_grad_conv(ctx.handle, ...)`"""
+        return conv_grad_lib()
 
     @property
     def extend(self):
