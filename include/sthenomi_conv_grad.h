@@ -13,7 +13,8 @@
  * reduced in a fixed order: two calls with the same arguments return the same bits.  The limits of sthenomi_conv.h hold
  * (height * width <= 3072, patch_h * patch_w <= 64).
  *
- * What these three refuse (rc < 0, each by name): stencil terms (include/sthenomi_stencil.h), a multi-GPU context, and --
+ * What these three refuse (rc < 0, each by name): stencil terms (include/sthenomi_stencil.h; include/sthenomi_stencil_grad.h
+ * carries them, and patch terms with them), a multi-GPU context, and --
  * sgp_elbo_grad_conv -- product chains, as sgp_elbo_grad does.  Gradients with respect to the images of a patched side are
  * not formed.  Everything else that takes a gradient keeps refusing patch terms: sgp_logpdf_grad*, sgp_elbo_grad*,
  * sgp_kernelmatrix_diag_grad*, the batch and pool gradients, the *_param family, fp32. */

@@ -1763,7 +1763,9 @@ extern "C" int sgp_rand(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* me
 }
 
 // the caller's index of the term at device position t (a spec with product chains keeps its plain terms in front: dspec_create)
-static inline int term_src_of(const sgp_dspec* ds, int t) { return (ds->n_kprod || ds->n_patch) ? ds->term_src[t] : t; }
+static inline int term_src_of(const sgp_dspec* ds, int t) {
+  return (ds->n_kprod || ds->n_patch || ds->n_stencil) ? ds->term_src[t] : t;
+}
 // the chain whose head sits at device position t: one past its last factor, and its DMAX
 static inline int chain_end(const sgp_dspec* ds, int t, int t1) {
   int e = t + 1;
@@ -1776,11 +1778,21 @@ static inline int chain_dmax(const sgp_dspec* ds, int t, int e) {
   return dm;
 }
 
+// whether no entry of `want` (NULL: none) asks for the gradient of an input that a patched side reads: those hold images
+static bool images_unasked(const sgp_dspec* ds, double* const* want) {
+  for (size_t t = 0; want && t < ds->h_terms.size(); ++t) {
+    const DevTerm& T = ds->h_terms[t];
+    if ((T.hr && want[ds->term_row_input[t]]) || (T.hc && want[ds->term_col_input[t]])) return false;
+  }
+  return true;
+}
+
 // per-term results back to the host (dst == NULL: not asked for), in the caller's order
 static int fetch_terms(const sgp_dspec* ds, double* dst, const double* d_src) {
   const size_t nt = ds->h_terms.size();
   if (!dst || !nt) return 0;
-  if (!ds->n_kprod && !ds->n_patch) {   // (patch terms sit behind the pair's plain terms on the device, as chains do)
+  if (!ds->n_kprod && !ds->n_patch && !ds->n_stencil) {   // (patch and stencil terms sit behind the pair's plain terms on the
+                                                          //  device, as chains do)
     SGP_HIP(hipMemcpy(dst, d_src, sizeof(double) * nt, hipMemcpyDeviceToHost));
     return 0;
   }
@@ -1796,17 +1808,24 @@ static int fetch_terms(const sgp_dspec* ds, double* dst, const double* d_src) {
 // (kprod_ok: sgp_logpdf_grad / sgp_logpdf_grad_param); dgp (optional): d / d param per term, which for the plain terms is
 // non-zero for SGP_CONST alone -- those run through the chain kernel once more, as chains of length one, for that entry.
 // Patch terms (ds->n_patch; conv.hip) are contracted one term per launch, only where the caller carries them (patch_ok: the
-// entry points of include/sthenomi_conv_grad.h).
+// entry points of include/sthenomi_conv_grad.h), and stencil terms (ds->n_stencil; stencil.hip) likewise (stencil_ok: the entry
+// points of include/sthenomi_stencil_grad.h): they occupy [ts, tk) of their pair, behind the patch terms [tp, ts).
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr,
                          long n_tc, DevBuf& dpart, double* dgc, double* dgs, hipStream_t s, bool kprod_ok = false,
-                         double* dgp = nullptr, bool patch_ok = false) {
-  CHECK_ARG(!ds->n_stencil, "gradient contraction: stencil terms are not supported");
+                         double* dgp = nullptr, bool patch_ok = false, bool stencil_ok = false) {
+  CHECK_ARG(stencil_ok || !ds->n_stencil, "gradient contraction: stencil terms are not supported");
   CHECK_ARG(patch_ok || !ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
   CHECK_ARG(kprod_ok || !ds->n_kprod, "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
   long need = std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16);
   for (int p = 0; ds->n_patch && p < ds->nrb * ds->ncb; ++p)
     for (int t = ds->term_ptr[p] + ds->pair_nplain[p]; t < ds->term_ptr[p] + ds->pair_nplain[p] + ds->pair_npatch[p]; ++t)
       need = std::max(need, grad_conv_partials(ds->row_len[p / ds->ncb], ds->col_len[p % ds->ncb], ds->h_terms[t]));
+  for (int p = 0; ds->n_stencil && p < ds->nrb * ds->ncb; ++p) {
+    const int I = p / ds->ncb, J = p % ds->ncb;
+    const int ts = ds->term_ptr[p] + ds->pair_nplain[p] + ds->pair_npatch[p], tk = ds->term_ptr[p + 1] - ds->pair_nkprod[p];
+    for (int t = ts; t < tk; ++t)
+      need = std::max(need, grad_stencil_partials(ds->row_off[I], ds->row_len[I], ds->col_off[J], ds->col_len[J], ds->h_terms[t]));
+  }
   CHECK_RC(dpart.alloc((size_t)need));
   for (int I = 0; I < ds->nrb; ++I) {
     if (ds->row_len[I] == 0) continue;
@@ -1819,14 +1838,18 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       int dmax = ds->pair_dmax[p];
       int per = std::min(8, std::max(1, 64 / dmax));
       const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
-      const int tp = ds->n_patch ? t0 + ds->pair_nplain[p] : tk;   // patch terms: [tp, tk) (no stencil terms here)
+      const int tp = (ds->n_patch || ds->n_stencil) ? t0 + ds->pair_nplain[p] : tk;   // patch terms: [tp, ts)
+      const int ts = ds->n_stencil ? tp + ds->pair_npatch[p] : tk;                    // stencil terms: [ts, tk)
       for (int t = t0; t < tp; t += per) {
         int cnt = std::min(per, tp - t);
         CHECK_RC(launch_grad_block(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax, trf, tcf,
                                    trl - trf, tcl - tcf, dpart.p, dgc + t, dgs + t, s));
       }
-      for (int t = tp; t < tk; ++t)
+      for (int t = tp; t < ts; ++t)
         CHECK_RC(launch_grad_conv(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, dpart.p, dgc + t, dgs + t, s));
+      for (int t = ts; t < tk; ++t)
+        CHECK_RC(launch_grad_stencil(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, dpart.p, dgc + t, dgs + t,
+                                     s));
       for (int t = t0; dgp && t < tp; ++t)
         if (ds->h_terms[t].kind == SGP_CONST)
           CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, 1, 1, 0, trf, tcf, trl - trf, tcl - tcf,
@@ -1852,17 +1875,21 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
                             const double* noise, const double* y, double* logpdf_out, double* grad_y,
                             double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
                             double* const* grad_inputs, double* const* grad_rowscale = nullptr,
-                            double* grad_param = nullptr, bool with_param = false, bool patch_ok = false) {
-  // (patch_ok: sgp_logpdf_grad_conv, include/sthenomi_conv_grad.h -- patch terms are contracted, conv.hip)
+                            double* grad_param = nullptr, bool with_param = false, bool patch_ok = false,
+                            bool stencil_ok = false) {
+  // (patch_ok: sgp_logpdf_grad_conv, include/sthenomi_conv_grad.h -- patch terms are contracted, conv.hip;
+  // stencil_ok: sgp_logpdf_grad_stencil, include/sthenomi_stencil_grad.h -- stencil terms too, stencil.hip; it sets patch_ok)
   CHECK_ARG(ctx && spec && noise && y && logpdf_out, "sgp_logpdf_grad: NULL argument");
   CHECK_ARG(spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
   CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
+  CHECK_ARG(!(stencil_ok && ctx->multi), "sgp_logpdf_grad_stencil: not supported on a multi-GPU context");
   CHECK_ARG(!(patch_ok && ctx->multi), "sgp_logpdf_grad_conv: not supported on a multi-GPU context");
-  CHECK_ARG(!spec_has_stencil(ctx, spec), patch_ok ? "sgp_logpdf_grad_conv: gradients through stencil terms are not supported"
-                                                   : "sgp_logpdf_grad: gradients through stencil terms are not supported");
+  CHECK_ARG(stencil_ok || !spec_has_stencil(ctx, spec),
+            patch_ok ? "sgp_logpdf_grad_conv: gradients through stencil terms are not supported"
+                     : "sgp_logpdf_grad: gradients through stencil terms are not supported");
   CHECK_ARG(patch_ok || !spec_has_patch(spec),
             "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
-  CHECK_ARG(!(grad_inputs || grad_rowscale) || with_param || !spec_has_kprod(spec),
+  CHECK_ARG(!(grad_inputs || grad_rowscale) || with_param || stencil_ok || !spec_has_kprod(spec),
             "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
             "not supported: call sgp_logpdf_grad_param_xs (include/sthenomi_kprod_grad.h)");
   CHECK_ARG(!(with_param && ctx->multi), "sgp_logpdf_grad_param: not supported on a multi-GPU context");
@@ -1878,6 +1905,9 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   const sgp_dspec* ds = g.ds;
   long N = ds->N;
   CHECK_ARG(N >= 1, "sgp_logpdf_grad: empty data");
+  CHECK_ARG(images_unasked(ds, grad_inputs),
+            "sgp_logpdf_grad_stencil: an input read by a patch (convolutional) side holds images, and gradients with respect to "
+            "images are not supported: its grad_inputs entry must be NULL");
   const bool dense_noise = noise_kind == SGP_NOISE_DENSE;   // grad_noise is then N x N (ld = N): the cotangent G itself
   long n_pad = rup(N, TILE);
   long nrows = TILE + n_pad;            // the (y - m)' row (+ zero padding), then the identity rows
@@ -1953,7 +1983,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   else if (grad_noise) CHECK_RC(launch_grad_noise(dKinv.p, n_pad, dalpha.p, N, nd.kind == SGP_NOISE_DIAG, dgn.p, s));
   if (grad_coef || grad_inscale || grad_param)
     CHECK_RC(contract_spec(ds, dKinv.p, n_pad, dalpha.p, n_pad / TILE, n_pad / TILE, dpart, dgc.p, dgs.p, s, true,
-                           grad_param ? dgp.p : nullptr, patch_ok));
+                           grad_param ? dgp.p : nullptr, patch_ok, stencil_ok));
   // gradient w.r.t. the input points: row-side contraction over every block pair; the spec is
   // symmetric (block (J, I) mirrors (I, J)) and so is G, hence the column side equals the row side of
   // the mirror block and the total is twice the row-side sum
@@ -1976,6 +2006,23 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
         for (int t = ds->term_ptr[p]; t < t1;) {
           int a = ds->term_row_input[t];
           double* gsv = nullptr;
+          const DevTerm& T = ds->h_terms[t];
+          if (T.ph) {   // a patch term (sgp_logpdf_grad_stencil alone asks here): the plain side of a one-sided one, once per
+                        // pair -- the mirror pair gives the other role, which makes the "x 2"
+            if (grad_inputs && !(T.hr && T.hc))
+              CHECK_RC(launch_grad_conv_points(dKinv.p, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                               ds->col_len[J], T, ds->d_terms + t, 1.0,
+                                               dgx[T.hr ? ds->term_col_input[t] : a].p, s));
+            ++t;
+            continue;
+          }
+          if (T.qr || T.qc) {   // a stencil term: the row side, twice (stencil.hip); its row scale is not formed
+            if (grad_inputs)
+              CHECK_RC(launch_grad_stencil_points(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                                  ds->col_len[J], T, 0, 2.0, dgx[a].p, s));
+            ++t;
+            continue;
+          }
           if (grad_rowscale && grad_rowscale[term_src_of(ds, t)] && ds->h_terms[t].rs) {
             CHECK_RC(dgr[t].alloc((size_t)ds->row_len[I]));
             SGP_HIP(hipMemsetAsync(dgr[t].p, 0, sizeof(double) * ds->row_len[I], s));
@@ -2081,6 +2128,16 @@ int sgp::drv_logpdf_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const doub
   return with_df_fallback(ctx, [&]() {
     return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                             grad_inscale, nullptr, nullptr, nullptr, false, true);
+  });
+}
+
+// include/sthenomi_stencil_grad.h: sgp_logpdf_grad_stencil (its C entry point, in libsthenomi_stencil_grad.so, forwards here)
+int sgp::drv_logpdf_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
+                                 const double* noise, const double* y, double* logpdf_out, double* grad_y, double* grad_mean,
+                                 double* grad_noise, double* grad_coef, double* grad_inscale, double* const* grad_inputs) {
+  return with_df_fallback(ctx, [&]() {
+    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                            grad_inscale, grad_inputs, nullptr, nullptr, false, true, true);
   });
 }
 
@@ -3586,7 +3643,7 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
                           double* const* grad_rowscale_zz = nullptr, double* const* grad_rowscale_xz = nullptr,
                           double* const* grad_colscale_xz = nullptr, const sgp::ElboGradShard* shard = nullptr,
                           double* grad_param_zz = nullptr, double* grad_param_xz = nullptr, bool kprod_ok = false,
-                          bool patch_ok = false) {
+                          bool patch_ok = false, bool stencil_ok = false) {
   // shard (round 6, multi.hip: sgp_multi_elbo_grad): this call sees ONE rank's slice of the data points (xz, var_x, mean_x, a
   // diagonal noise_x, y and the per-point results are the slice's).  The sums over data points -- A A', A delta, the four
   // scalar sums -- are added up over the ranks by shard->reduce (every rank gets the total), the M x M stage runs replicated
@@ -3602,13 +3659,6 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   CHECK_RC(dspec_create(ctx, xz, &gx.ds));
   const long M = gz.ds->N, N = gx.ds->N;
   // a patched side reads images, and gradients with respect to those are not formed (include/sthenomi_conv_grad.h)
-  auto images_unasked = [](const sgp_dspec* ds, double* const* want) {
-    for (size_t t = 0; want && t < ds->h_terms.size(); ++t) {
-      const DevTerm& T = ds->h_terms[t];
-      if ((T.hr && want[ds->term_row_input[t]]) || (T.hc && want[ds->term_col_input[t]])) return false;
-    }
-    return true;
-  };
   CHECK_ARG(images_unasked(gz.ds, grad_inputs_zz) && images_unasked(gx.ds, grad_inputs_xz),
             "sgp_elbo_grad_conv: an input read by a patch (convolutional) side holds images, and gradients with respect to "
             "images are not supported: its grad_inputs entry must be NULL");
@@ -3776,10 +3826,10 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   // ---- contractions against the flattened terms
   if (grad_coef_xz || grad_inscale_xz || grad_param_xz)
     CHECK_RC(contract_spec(gx.ds, dE.p, n_rows, nullptr, n_rows / TILE, m_pad / TILE, dpart, dgcx.p, dgsx.p, s, kprod_ok,
-                           dgpx.p, patch_ok));
+                           dgpx.p, patch_ok, stencil_ok));
   if (grad_coef_zz || grad_inscale_zz || grad_param_zz)
     CHECK_RC(contract_spec(gz.ds, dGzz.p, m_pad, nullptr, m_pad / TILE, m_pad / TILE, dpart, dgcz.p, dgsz.p, s, kprod_ok,
-                           dgpz.p, patch_ok));
+                           dgpz.p, patch_ok, stencil_ok));
   // ---- input points: zz is symmetric (twice the row side, as in logpdf_grad_core); xz is
   // rectangular: row side for the x inputs, and the transposed contraction for the z inputs
   std::vector<DevBuf> dgz(grad_inputs_zz ? zz->n_inputs : 0), dgxz(grad_inputs_xz ? xz->n_inputs : 0);
@@ -3828,6 +3878,13 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
             ++t;
             continue;
           }
+          if (ds->h_terms[t].qr || ds->h_terms[t].qc) {   // a stencil term: the row side, twice (stencil.hip)
+            if (grad_inputs_zz)
+              CHECK_RC(launch_grad_stencil_points(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                                  ds->col_len[J], ds->h_terms[t], 0, 2.0, dgz[ds->term_row_input[t]].p, s));
+            ++t;
+            continue;
+          }
           CHECK_RC(scale_buf(drz, grad_rowscale_zz, ds, t, ds->h_terms[t].rs, ds->row_len[I], &gsv));
           if (t >= tk) {   // a chain: one pass for every factor's row input and the head's row scale (kprod.hip)
             const int e = chain_end(ds, t, t1);
@@ -3862,6 +3919,16 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
           double *gsr = nullptr, *gsc = nullptr;
           if (T.ph) {   // a patch term: the plain side of a one-sided one
             CHECK_RC(patch_points(ds, dE.p, n_rows, I, J, t, dgxz));
+            continue;
+          }
+          if (T.qr || T.qc) {   // a stencil term: the row side for x, the transposed contraction (sides and stencils
+                                // swapped) for z (stencil.hip)
+            if (grad_inputs_xz) {
+              CHECK_RC(launch_grad_stencil_points(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
+                                                  ds->col_len[J], T, 0, 1.0, dgxz[ds->term_row_input[t]].p, s));
+              CHECK_RC(launch_grad_stencil_points(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
+                                                  ds->row_len[I], T, 1, 1.0, dgxz[ds->term_col_input[t]].p, s));
+            }
             continue;
           }
           CHECK_RC(scale_buf(drx, grad_rowscale_xz, ds, t, T.rs, ds->row_len[I], &gsr));
@@ -3975,8 +4042,9 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
 // the three entry points: one record of arguments; a multi-GPU context shards the data points over its ranks (round 6)
 static int elbo_grad_entry(sgp_ctx* ctx, const sgp::ElboGradArgs& a) {
   CHECK_ARG(ctx, "sgp_elbo_grad: NULL context");
+  CHECK_ARG(!(a.stencil_ok && ctx->multi), "sgp_elbo_grad_stencil: not supported on a multi-GPU context");
   CHECK_ARG(!(a.patch_ok && ctx->multi), "sgp_elbo_grad_conv: not supported on a multi-GPU context");
-  CHECK_ARG(!spec_has_stencil(ctx, a.zz) && !spec_has_stencil(ctx, a.xz),
+  CHECK_ARG(a.stencil_ok || (!spec_has_stencil(ctx, a.zz) && !spec_has_stencil(ctx, a.xz)),
             a.patch_ok ? "sgp_elbo_grad_conv: gradients through stencil terms are not supported"
                        : "sgp_elbo_grad: gradients through stencil terms are not supported");
   CHECK_ARG(a.patch_ok || (!spec_has_patch(a.zz) && !spec_has_patch(a.xz)),
@@ -4037,17 +4105,21 @@ extern "C" int sgp_elbo_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_
 int sgp::drv_elbo_grad_param(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
 // include/sthenomi_conv_grad.h: sgp_elbo_grad_conv (its C entry point, in libsthenomi_conv_grad.so, forwards here)
 int sgp::drv_elbo_grad_conv(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
+// include/sthenomi_stencil_grad.h: sgp_elbo_grad_stencil (its C entry point, in libsthenomi_stencil_grad.so, forwards here)
+int sgp::drv_elbo_grad_stencil(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
 
 // sum_i w[i] d var_i / d theta over the diagonal of `spec` (the blocks (I, I) kernelmatrix_diag reads)
 static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
                           double* grad_inscale, double* const* grad_inputs, double* const* grad_rowscale = nullptr,
                           double* const* grad_colscale = nullptr, double* grad_param = nullptr, bool kprod_ok = false,
-                          bool patch_ok = false) {
+                          bool patch_ok = false, bool stencil_ok = false) {
   // (kprod_ok: sgp_kernelmatrix_diag_grad_param, include/sthenomi_kprod_grad.h -- every output may be NULL there;
-  // patch_ok: sgp_kernelmatrix_diag_grad_conv, include/sthenomi_conv_grad.h)
+  // patch_ok: sgp_kernelmatrix_diag_grad_conv, include/sthenomi_conv_grad.h; stencil_ok: sgp_kernelmatrix_diag_grad_stencil,
+  // include/sthenomi_stencil_grad.h)
   CHECK_ARG(ctx && spec && w && (kprod_ok || (grad_coef && grad_inscale)), "sgp_kernelmatrix_diag_grad: NULL argument");
+  CHECK_ARG(!(stencil_ok && ctx->multi), "sgp_kernelmatrix_diag_grad_stencil: not supported on a multi-GPU context");
   CHECK_ARG(!(patch_ok && ctx->multi), "sgp_kernelmatrix_diag_grad_conv: not supported on a multi-GPU context");
-  CHECK_ARG(!spec_has_stencil(ctx, spec),
+  CHECK_ARG(stencil_ok || !spec_has_stencil(ctx, spec),
             patch_ok ? "sgp_kernelmatrix_diag_grad_conv: gradients through stencil terms are not supported"
                      : "sgp_kernelmatrix_diag_grad: gradients through stencil terms are not supported");
   CHECK_ARG(patch_ok || !spec_has_patch(spec),
@@ -4061,6 +4133,9 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
   CHECK_RC(dspec_create(ctx, spec, &g.ds));
   const sgp_dspec* ds = g.ds;
   CHECK_ARG(ds->nrb == ds->ncb, "kernelmatrix_diag_grad: row / col block counts differ");
+  CHECK_ARG(images_unasked(ds, grad_inputs),
+            "sgp_kernelmatrix_diag_grad_stencil: an input read by a patch (convolutional) side holds images, and gradients with "
+            "respect to images are not supported: its grad_inputs entry must be NULL");
   size_t nt = ds->h_terms.size();
   for (size_t t = 0; t < nt; ++t) {
     if (grad_coef) grad_coef[t] = 0.0;
@@ -4081,16 +4156,21 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
   }
   // the plain terms of a diagonal pair: [term_ptr, diag_tk); its product chains behind them (kprod.hip)
   // (and, where the caller carries them, its patch terms between the two: [diag_tk, diag_tp), conv.hip)
+  // (and, where the caller carries them, its stencil terms behind the patch terms: [diag_ts, diag_tp), stencil.hip)
   auto diag_tp = [&](int p) { return ds->n_kprod ? ds->term_ptr[p + 1] - ds->pair_nkprod[p] : ds->term_ptr[p + 1]; };
-  auto diag_tk = [&](int p) { return ds->n_patch ? ds->term_ptr[p] + ds->pair_nplain[p] : diag_tp(p); };
+  auto diag_tk = [&](int p) { return (ds->n_patch || ds->n_stencil) ? ds->term_ptr[p] + ds->pair_nplain[p] : diag_tp(p); };
+  auto diag_ts = [&](int p) { return ds->n_stencil ? diag_tk(p) + ds->pair_npatch[p] : diag_tp(p); };
   DevBuf dpart;
-  if (ds->n_patch) CHECK_RC(dpart.alloc((size_t)2 * ds->N));
-  for (int I = 0; ds->n_patch && I < ds->nrb; ++I) {
+  if (ds->n_patch || ds->n_stencil) CHECK_RC(dpart.alloc((size_t)2 * ds->N));
+  for (int I = 0; (ds->n_patch || ds->n_stencil) && I < ds->nrb; ++I) {
     const int p = I * ds->ncb + I;
     if (ds->row_len[I] == 0 || ds->row_len[I] != ds->col_len[I]) continue;
-    for (int t = diag_tk(p); t < diag_tp(p); ++t)
+    for (int t = diag_tk(p); t < diag_ts(p); ++t)
       CHECK_RC(launch_diag_grad_conv(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t], ds->d_terms + t, dpart.p,
                                      dgc.p + t, dgs.p + t, s));
+    for (int t = diag_ts(p); t < diag_tp(p); ++t)
+      CHECK_RC(launch_diag_grad_stencil(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t], ds->d_terms + t, dpart.p,
+                                        dgc.p + t, dgs.p + t, s));
   }
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag_grad: block lengths differ");
@@ -4117,6 +4197,15 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
       for (int t = ds->term_ptr[p]; t < diag_tk(p); ++t)
         CHECK_RC(launch_diag_grad_inputs(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t],
                                          dgx[ds->term_row_input[t]].p, dgx[ds->term_col_input[t]].p, s));
+      for (int t = diag_tk(p); t < diag_ts(p); ++t) {   // patch terms: the plain side of a one-sided one is not formed here
+        const DevTerm& T = ds->h_terms[t];
+        CHECK_ARG((T.hr && T.hc) || !grad_inputs[T.hr ? ds->term_col_input[t] : ds->term_row_input[t]],
+                  "sgp_kernelmatrix_diag_grad_stencil: the input-point gradient of a one-sided patch (convolutional) term on "
+                  "the diagonal is not supported: the grad_inputs entry of its plain side must be NULL");
+      }
+      for (int t = diag_ts(p); t < diag_tp(p); ++t)   // stencil terms: + on the row input, - on the column input (stencil.hip)
+        CHECK_RC(launch_diag_grad_stencil_points(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t],
+                                                 dgx[ds->term_row_input[t]].p, dgx[ds->term_col_input[t]].p, s));
     }
   }
   std::vector<DevBuf> drs(grad_rowscale ? nt : 0), dcs(grad_colscale ? nt : 0);
@@ -4206,6 +4295,14 @@ extern "C" int sgp_kernelmatrix_diag_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* s
 int sgp::drv_diag_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale) {
   CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_conv: NULL argument");
   return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, nullptr, nullptr, nullptr, nullptr, true, true);
+}
+
+// include/sthenomi_stencil_grad.h: sgp_kernelmatrix_diag_grad_stencil (its C entry point, in libsthenomi_stencil_grad.so,
+// forwards here)
+int sgp::drv_diag_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
+                               double* const* grad_inputs) {
+  CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_stencil: NULL argument");
+  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, nullptr, nullptr, nullptr, true, true, true);
 }
 
 int sgp::drv_diag_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
@@ -4617,7 +4714,7 @@ int drv_elbo_grad(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shar
                           a.elbo_out, a.grad_y, a.grad_mean, a.grad_noise, a.grad_var_x, a.grad_z_noise, a.grad_coef_zz,
                           a.grad_inscale_zz, a.grad_coef_xz, a.grad_inscale_xz, a.grad_inputs_zz, a.grad_inputs_xz,
                           a.grad_rowscale_zz, a.grad_rowscale_xz, a.grad_colscale_xz, shard, a.grad_param_zz, a.grad_param_xz,
-                          a.kprod_ok, a.patch_ok);
+                          a.kprod_ok, a.patch_ok, a.stencil_ok);
   };
   // (a rank of a sharded call cannot rerun on its own -- the reduction is collective: multi.hip reruns all of them)
   return shard ? run() : with_df_fallback(ctx, run);

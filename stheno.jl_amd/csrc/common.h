@@ -157,6 +157,24 @@ int launch_assemble_stencil(double* K, long ld, long r0, long nr, long c0, long 
 // sums entry (i, i); out holds the pair's plain and patch diagonal.  max_dim: the largest input dimension of those terms
 int launch_diag_stencil(double* out, long n, const DevTerm* d_terms, int nterms, int max_dim, hipStream_t s);
 
+// stencil.hip, the gradient contractions against ONE stencil term of a block pair (include/sthenomi_stencil_grad.h); G and
+// its indexing as for launch_grad_conv.  out_coef[0] = sum_ij G_ij rs_i cs_j sum_pq w_p v_q k, out_scale[0] = sum_ij G_ij
+// coef rs_i cs_j sum_pq w_p v_q dk/dg; `partials` holds grad_stencil_partials(r0, nr, c0, nc, T) doubles (per-workgroup
+// sums, reduced in a fixed order)
+long grad_stencil_partials(long r0, long nr, long c0, long nc, const DevTerm& T);
+int launch_grad_stencil(const double* Gm, long ldg, const double* alpha, long r0, long nr, long c0, long nc, const DevTerm& T,
+                        const DevTerm* dterm, double* partials, double* out_coef, double* out_scale, hipStream_t s);
+// ... on the diagonal: sum_i w_i d var_i / d theta of one stencil term; `partials`: 2 n doubles
+int launch_diag_grad_stencil(const double* w, long n, const DevTerm& T, const DevTerm* dterm, double* partials,
+                             double* out_coef, double* out_scale, hipStream_t s);
+// ... with respect to the row side's points: gx (dim x nr, packed) += scale * the row-side sum, G addressed as for
+// launch_grad_inputs; transpose != 0: the term seen from its column points (sides and stencils swapped; the caller passes the
+// column block as (r0, nr), the row block as (c0, nc) and the strides of the transposed cotangent)
+int launch_grad_stencil_points(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                               const DevTerm& T, int transpose, double scale, double* gx, hipStream_t s);
+// ... on the diagonal: gxr += / gxc -= the per-entry sums (either may be NULL; gxr == gxc: the two cancel, nothing is launched)
+int launch_diag_grad_stencil_points(const double* w, long n, const DevTerm& T, double* gxr, double* gxc, hipStream_t s);
+
 // kprod.hip: product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h).  The terms of one launch are whole chains;
 // kprod_group cuts a pair's chain terms [t, t1) into launches (returns how many terms the launch at t carries, *dmax_out = its
 // DMAX) for the matrix and the diagonal alike.  Arguments of launch_assemble_kprod as launch_assemble_block.

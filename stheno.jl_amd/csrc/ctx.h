@@ -70,6 +70,8 @@ struct ElboGradArgs {
   bool kprod_ok = false;
   // sgp_elbo_grad_conv (include/sthenomi_conv_grad.h): the leave to carry patch terms
   bool patch_ok = false;
+  // sgp_elbo_grad_stencil (include/sthenomi_stencil_grad.h): the leave to carry stencil terms (it sets patch_ok as well)
+  bool stencil_ok = false;
 };
 struct ElboGradShard {
   bool primary = false;   // the rank that also produces the zz-side results (G_zz and its contractions)

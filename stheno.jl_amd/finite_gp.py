@@ -42,7 +42,8 @@ def _refuse_patch_gradient(*specs):
     """gradients through patch_convolve or stencil terms are not implemented (the library refuses them too): never a
     silently wrong gradient"""
     if any(sp.has_stencil for sp in specs):
-        raise NotImplementedError("gradients through stencil covariance terms are not supported")
+        raise NotImplementedError("gradients through stencil covariance terms are not supported here: call "
+                                  "logpdf_and_gradient_stencil / elbo_and_gradient_stencil")
     if any(sp.has_patch for sp in specs):
         raise NotImplementedError("gradients through patch_convolve (convolutional) covariance terms are not supported "
                                   "here: call logpdf_and_gradient_conv / elbo_and_gradient_conv")
@@ -622,7 +623,8 @@ def _refuse_conv_family(what, *specs):
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_stencil for sp in specs):
-        raise NotImplementedError(f"{what}: gradients through stencil covariance terms are not supported")
+        raise NotImplementedError(f"{what}: gradients through stencil covariance terms are not supported here: call "
+                                  "logpdf_and_gradient_stencil / elbo_and_gradient_stencil")
     if any(sp.has_patch for sp in specs) and any(sp.has_kprod for sp in specs):
         raise NotImplementedError(f"{what}: a model with both patch_convolve terms and a product of kernels is not "
                                   "supported (the records of a product carry d_param, which these calls do not return)")
@@ -654,6 +656,55 @@ def logpdf_and_gradient_conv(fx, y):
                                                _lib.dptr(gs))
     _lib.check(rc, "sgp_logpdf_grad_conv")
     return _grad_record(spec, kind, lp[0], bufs)
+
+
+def _refuse_stencil_family(what, *specs):
+    """what the entry points of include/sthenomi_stencil_grad.h refuse: a multi-GPU context; and what their records cannot
+    carry"""
+    if getattr(_ctx(), "is_multi", False):
+        raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
+    if any(sp.has_patch or sp.has_stencil for sp in specs) and any(sp.has_kprod for sp in specs):
+        raise NotImplementedError(f"{what}: a model with both stencil or patch_convolve terms and a product of kernels is not "
+                                  "supported (the records of a product carry d_param, which these calls do not return)")
+
+
+def _input_buffers(spec):
+    """one zero (dim, n) array per spec input -- None for an input that a patched side reads (it holds images) -- and the
+    ctypes pointer table"""
+    img = _patched_inputs(spec) if spec.has_patch else ()
+    arrs = [None if k in img else np.zeros(np.asarray(a).shape, order="F") for k, a in enumerate(spec.inputs)]
+    return arrs, (C.POINTER(C.c_double) * max(1, len(arrs)))(*[_lib.dptr(a) for a in arrs])
+
+
+def logpdf_and_gradient_stencil(fx, y, inputs=False):
+    """logpdf_and_gradient(fx, y, inputs=inputs) for every model it takes AND for models with stencil terms (`stencil`,
+    `quadrature_convolve`) or patch_convolve terms, through sgp_logpdf_grad_stencil (include/sthenomi_stencil_grad.h): the
+    same dict.  For a stencil term coef rs cs sum_pq w_p v_q k(x - a_p, x' - b_q) the record's d_coef is the derivative
+    w.r.t. that coefficient (the kernel's variance times the model's scalings) and d_inscale the derivative w.r.t. a common
+    scale g of the points and the offsets (a lengthscale l = 1 / g gives d / dl = -g^2 d_inscale), exactly as for a plain
+    term; the record also carries row_stencil / col_stencil.  inputs=True adds `inputs` and `x`: the stored points of a
+    stencil side are the unshifted ones (shifting is a translation), so the chain back through Stretch / Shift / Select is
+    that of a plain term; the entry of an input that holds images is None.  Gradients with respect to a stencil's weights and
+    offsets are not formed.  Single-GPU contexts."""
+    if not _is_prior(fx.f):
+        raise NotImplementedError("gradients are implemented for prior Stheno processes")
+    n = len(fx)
+    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+    spec = _prior_spec(fx.f, fx.x)
+    _refuse_stencil_family("logpdf_and_gradient_stencil", spec)
+    if spec.has_kprod:
+        return logpdf_and_gradient_param(fx, y, inputs=True) if inputs else logpdf_and_gradient(fx, y)
+    m = _f64(mean_vector(fx.f, fx.x))
+    kind, nbuf = _lib._noise_args(fx.noise, n)
+    lp = np.zeros(1)
+    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
+    gx, ptrs = _input_buffers(spec) if inputs else (None, None)
+    rc = _ctx().stencil_grad.sgp_logpdf_grad_stencil(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
+                                                     _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm),
+                                                     _lib.dptr(gn), _lib.dptr(gc), _lib.dptr(gs), ptrs)
+    _lib.check(rc, "sgp_logpdf_grad_stencil")
+    xb = chain_input_gradients(spec, gx)[0] if inputs else None
+    return _grad_record(spec, kind, lp[0], bufs, gx, xb)
 
 
 def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
@@ -1141,6 +1192,11 @@ def _term_records_kprod(spec, gc, gs, gp, symmetric=True):
     return out
 
 
+def _swap_sides(key):
+    """(row, col[, row stencil, col stencil]) of a term's geometry key seen from the mirror pair"""
+    return key[1::-1] + key[:1:-1]
+
+
 def _term_records(spec, gc, gs, symmetric, gp=None):
     """One record per flattened term.  For a symmetric spec the mirror-image pair (J, I) is folded
     into the lower pair (I >= J).  The mirror of a term with row / column scale vectors (rs, cs) is
@@ -1153,6 +1209,9 @@ def _term_records(spec, gc, gs, symmetric, gp=None):
     tp, out, index = spec._term_ptr, [], {}
     sid = spec.term_scale_ids
     geo = [tuple(g) for g in spec.term_geoms]        # a patch term's geometries (None, None for a plain one) are part of it
+    if spec.has_stencil:                             # ... and so are a stencil term's stencils: several terms of one pair may
+        geo = [g + tuple(None if st is None else (st[0].shape, st[0].tobytes(), st[1].tobytes()) for st in sts)   # differ in
+               for g, sts in zip(geo, spec.term_stencils)]                                                        # them alone
     for I in range(nrb):
         for J in range(ncb):
             for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
@@ -1165,12 +1224,14 @@ def _term_records(spec, gc, gs, symmetric, gp=None):
                                 t=t, mirror_t=None, d_coef=float(gc[t]), d_inscale=float(gs[t])))
                 if spec.has_patch:
                     out[-1].update(row_geom=geo[t][0], col_geom=geo[t][1])
+                if spec.has_stencil:
+                    out[-1].update(row_stencil=spec.term_stencils[t][0], col_stencil=spec.term_stencils[t][1])
     if symmetric:
         for I in range(nrb):
             for J in range(I + 1, ncb):
                 for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
                     T = spec._terms[t]
-                    k = index.get((J, I, T.kind, T.col_input, T.row_input, T.param, sid[t][1], sid[t][0]) + geo[t][::-1])
+                    k = index.get((J, I, T.kind, T.col_input, T.row_input, T.param, sid[t][1], sid[t][0]) + _swap_sides(geo[t]))
                     if k is None:
                         raise AssertionError("symmetric spec without a mirror term: flattener invariant broken")
                     out[k]["mirror_t"] = t
@@ -1331,6 +1392,58 @@ def elbo_and_gradient_conv(vfe, fx, y=None, inputs=False):
         _, zc = chain_input_gradients(xz, gxx)
         zb = [a + b for a, b in zip(zr, zc)]
     return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=None, z=zb,
+                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
+                zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
+                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx, scales=None,
+                _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
+                _specs=dict(zz=zz, xz=xz, xx=xx))
+
+
+def elbo_and_gradient_stencil(vfe, fx, y=None, inputs=False):
+    """elbo_and_gradient for every model it takes (without a product of kernels) AND for models with stencil terms (`stencil`,
+    `quadrature_convolve`) or patch_convolve terms, through sgp_elbo_grad_stencil and sgp_kernelmatrix_diag_grad_stencil
+    (include/sthenomi_stencil_grad.h): the same dict (see elbo_and_gradient; `scales` is None).  inputs=True adds zz_inputs /
+    xz_inputs, `x` and `z` as elbo_and_gradient does -- a stencil side's stored points are the unshifted ones, so the chain back
+    onto the blocks of fx.x and fz.x is that of a plain term; an entry that holds images (an input read by a patched side) is
+    None and contributes nothing.  Single-GPU contexts."""
+    if isinstance(vfe, SparseFiniteGP):
+        return elbo_and_gradient_stencil(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs)
+    zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
+    n, m = len(fx), len(vfe.fz)
+    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+    xx = _prior_spec(fx.f, fx.x)
+    _refuse_stencil_family("elbo_and_gradient_stencil", zz, xz, xx)
+    _refuse_product_gradient("elbo_and_gradient_stencil", zz, xz, xx)
+    var_x = _f64(_kernelmatrix_diag(xx))
+    out = np.zeros(1)
+    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
+    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
+    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
+    gcz, gsz = np.zeros(max(1, zz.n_terms)), np.zeros(max(1, zz.n_terms))
+    gcx, gsx = np.zeros(max(1, xz.n_terms)), np.zeros(max(1, xz.n_terms))
+    lib = _ctx().stencil_grad
+    gxz = gxx = gdx = pz = px = pd = None
+    if inputs:
+        gxz, pz = _input_buffers(zz)
+        gxx, px = _input_buffers(xz)
+        gdx, pd = _input_buffers(xx)     # var(f, x) depends on x wherever a diagonal term reads two different views of x
+    rc = lib.sgp_elbo_grad_stencil(_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(var_x), _lib.dptr(mean_x), nk, _lib.dptr(nbuf),
+                                   zk, _lib.dptr(zbuf), _lib.dptr(yv), _lib.dptr(out), _lib.dptr(gy), _lib.dptr(gm),
+                                   _lib.dptr(gn), _lib.dptr(gv), _lib.dptr(gzn), _lib.dptr(gcz), _lib.dptr(gsz), _lib.dptr(gcx),
+                                   _lib.dptr(gsx), pz, px)
+    _lib.check(rc, "sgp_elbo_grad_stencil")
+    gcd, gsd = np.zeros(max(1, xx.n_terms)), np.zeros(max(1, xx.n_terms))
+    rc = lib.sgp_kernelmatrix_diag_grad_stencil(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd)
+    _lib.check(rc, "sgp_kernelmatrix_diag_grad_stencil")
+    nb = len(xx.row_len)
+    xx_terms = [r for r in _term_records(xx, gcd, gsd, False) if r["I"] == r["J"]] if nb else []
+    xb = zb = None
+    if inputs:   # chain rule back onto the blocks of fx.x and fz.x
+        zr, _ = chain_input_gradients(zz, gxz)
+        xr, zc = chain_input_gradients(xz, gxx)
+        xd, _ = chain_input_gradients(xx, gdx)
+        xb, zb = [a + b for a, b in zip(xr, xd)], [a + b for a, b in zip(zr, zc)]
+    return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
                 z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
                 zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
                 xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx, scales=None,

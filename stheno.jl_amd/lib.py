@@ -24,6 +24,7 @@ VFE_UPDATE_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_vfe_update.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 CONV_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv_grad.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
+STENCIL_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil_grad.so")
 KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
 KPROD_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod_grad.so")
 
@@ -300,6 +301,22 @@ _SIGS_CONV_GRAD = {
 }
 
 
+# include/sthenomi_stencil_grad.h: the same three with stencil terms carried through and the input points on both sides, exported
+# by libsthenomi_stencil_grad.so -- logpdf_and_gradient_stencil and elbo_and_gradient_stencil reach them through
+# stencil_grad_lib() / Context.stencil_grad
+_SIGS_STENCIL_GRAD = {
+    "sgp_logpdf_grad_stencil": (C.c_int, [_P, _SPEC, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _DD]),
+    "sgp_kernelmatrix_diag_grad_stencil": (C.c_int, [_P, _SPEC, _D, _D, _D, _DD]),
+    "sgp_elbo_grad_stencil": (C.c_int, [_P, _SPEC, _SPEC, _D, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D,
+                                        _D, _D, _D, _D, _DD, _DD]),
+}
+
+
+def stencil_grad_symbols():
+    """Names include/sthenomi_stencil_grad.h declares: the entry points of libsthenomi_stencil_grad.so."""
+    return sorted(_SIGS_STENCIL_GRAD)
+
+
 def conv_grad_symbols():
     """Names include/sthenomi_conv_grad.h declares: the entry points of libsthenomi_conv_grad.so."""
     return sorted(_SIGS_CONV_GRAD)
@@ -551,6 +568,27 @@ def conv_grad_lib():
         return lib
 
 
+_stencil_grad = None
+
+
+def stencil_grad_lib():
+    """dlopen libsthenomi_stencil_grad.so (include/sthenomi_stencil_grad.h) after the product library it links against."""
+    global _stencil_grad
+    load()
+    with _lib_lock:
+        if _stencil_grad is not None:
+            return _stencil_grad
+        if not os.path.exists(STENCIL_GRAD_LIB_PATH):
+            raise SthenoMIError(f"{STENCIL_GRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(STENCIL_GRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_STENCIL_GRAD.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _stencil_grad = lib
+        return lib
+
+
 _stencil = None
 
 
@@ -708,6 +746,11 @@ class Context:
     def conv_grad(self):
         """libsthenomi_conv_grad.so (sthenomi_conv_grad.h): `ctx.conv_grad.sgp_logpdf_grad_conv(ctx.handle, ...)`"""
         return conv_grad_lib()
+
+    @property
+    def stencil_grad(self):
+        """libsthenomi_stencil_grad.so (sthenomi_stencil_grad.h): `ctx.stencil_grad.sgp_logpdf_grad_stencil(ctx.handle, ...)`"""
+        return stencil_grad_lib()
 
     @property
     def extend(self):
