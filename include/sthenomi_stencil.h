@@ -20,7 +20,9 @@
  *
  * Stencil terms run on every fp64 operator of a single-GPU context: sgp_kernelmatrix / _diag, sgp_logpdf (_batch),
  * sgp_rand, the posterior, sgp_elbo and the sparse posterior.  Their gradients come from include/sthenomi_stencil_grad.h
- * (sgp_logpdf_grad_stencil, sgp_kernelmatrix_diag_grad_stencil, sgp_elbo_grad_stencil; libsthenomi_stencil_grad.so).  These
+ * (sgp_logpdf_grad_stencil, sgp_kernelmatrix_diag_grad_stencil, sgp_elbo_grad_stencil; libsthenomi_stencil_grad.so), and the
+ * gradients with respect to a stencil's own weights and offsets from include/sthenomi_stencil_wo.h (the same three names
+ * with _wo; libsthenomi_stencil_wo.so).  These
  * refuse them with rc < 0 and a message naming "stencil": the gradient entry points of the other headers (sgp_*_grad*,
  * sgp_logpdf_grad_batch / _pool, the *_conv and *_param families), the fp32 entry points (sgp_*_f32) and every multi-GPU
  * context (which registers none).

@@ -21,7 +21,8 @@
  * input-gradient column is written by one thread: two calls with the same arguments return the same bits.  The limits of
  * sthenomi_stencil.h hold (64 points, dimension 16).
  *
- * What is NOT formed, each a later extension: gradients with respect to a stencil's weights and offsets; row- and
+ * Gradients with respect to a stencil's own weights and offsets come from include/sthenomi_stencil_wo.h (the same three with
+ * two more tables, libsthenomi_stencil_wo.so).  What is NOT formed, each a later extension: row- and
  * column-scale gradients of stencil terms (the _xs family); the batch and pool gradients (sgp_logpdf_grad_batch / _pool); the
  * *_param family (d / d param, include/sthenomi_kprod_grad.h); fp32; multi-GPU contexts.  Everything else that takes a gradient
  * keeps refusing stencil terms by name: sgp_logpdf_grad*, sgp_elbo_grad*, sgp_kernelmatrix_diag_grad*, the *_conv and

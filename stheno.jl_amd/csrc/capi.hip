@@ -1802,6 +1802,122 @@ static int fetch_terms(const sgp_dspec* ds, double* dst, const double* d_src) {
   return 0;
 }
 
+// Gradients with respect to the stencils' own weights and offsets (include/sthenomi_stencil_wo.h): the caller's two tables
+// (2 pointers per element of spec->terms, [2 t] the row side, [2 t + 1] the column side; NULL: not asked for), checked
+// against the spec, contracted by stencil.hip at the stencil terms of the cores below and copied out after the stream has run.
+struct StencilWo {
+  struct Job { double *hw, *ho; size_t off; int q, dim; };
+  double* const* gw = nullptr;
+  double* const* go = nullptr;
+  DevBuf out, part;
+  std::vector<Job> jobs;
+  bool asked() const { return gw || go; }
+  double* want_w(const sgp_dspec* ds, int t, int side) const { return gw ? gw[2 * term_src_of(ds, t) + side] : nullptr; }
+  double* want_o(const sgp_dspec* ds, int t, int side) const { return go ? go[2 * term_src_of(ds, t) + side] : nullptr; }
+
+  // refuse what has no stencil of its own, and size the output and the scratch.  diag: the diagonal pairs alone are contracted
+  int prepare(const sgp_dspec* ds, const char* who, bool diag, hipStream_t s) {
+    if (!asked()) return 0;
+    size_t total = 0;
+    long need = 1;
+    for (int I = 0; I < ds->nrb; ++I)
+      for (int J = 0; J < ds->ncb; ++J) {
+        const int p = I * ds->ncb + J, t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
+        const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
+        for (int t = t0; t < t1; ++t) {
+          const DevTerm& T = ds->h_terms[t];
+          for (int side = 0; side < 2; ++side) {
+            double *hw = want_w(ds, t, side), *ho = want_o(ds, t, side);
+            if (!hw && !ho) continue;
+            if (t >= tk) {
+              set_error(std::string(who) + ": a grad_weights / grad_offsets entry of a product chain term must be NULL");
+              return -1;
+            }
+            if (T.ph) {
+              set_error(std::string(who) + ": a grad_weights / grad_offsets entry of a patch (convolutional) term must be NULL");
+              return -1;
+            }
+            const int q = side ? T.qc : T.qr;
+            if (q < 1) {
+              set_error(std::string(who) + ": plain side: a grad_weights / grad_offsets entry of a side without a stencil "
+                                           "must be NULL");
+              return -1;
+            }
+            jobs.push_back({hw, ho, total, q, T.dim});
+            total += (size_t)q * (1 + T.dim);
+            const long nr = ds->row_len[I], nc = ds->col_len[J];
+            need = std::max(need, diag ? diag_grad_stencil_wo_partials(nr, T, side)
+                                       : grad_stencil_wo_partials(side ? nc : nr, side ? nr : nc, T, side));
+          }
+        }
+      }
+    CHECK_RC(out.alloc(std::max<size_t>(1, total)));
+    CHECK_RC(part.alloc((size_t)need));
+    SGP_HIP(hipMemsetAsync(out.p, 0, sizeof(double) * std::max<size_t>(1, total), s));   // (an empty or off-diagonal pair: zeros)
+    return 0;
+  }
+  // the device slots of (t, side), in prepare's order of visit; NULL where not asked for
+  void slots(const sgp_dspec* ds, int t, int side, size_t& cursor, double** dw, double** dof) {
+    *dw = *dof = nullptr;
+    double *hw = want_w(ds, t, side), *ho = want_o(ds, t, side);
+    if (!hw && !ho) return;
+    const Job& j = jobs[cursor++];
+    if (hw) *dw = out.p + j.off;
+    if (ho) *dof = out.p + j.off + j.q;
+  }
+  // every stencil term of every pair: G(i, j) at Gm[i + j * ldg] (alpha as in contract_spec).  symmetric: G equals its
+  // transpose, and the column side reads it at the mirrored address, along the lanes
+  int contract(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, bool symmetric, hipStream_t s) {
+    if (!asked()) return 0;
+    size_t cursor = 0;
+    for (int I = 0; I < ds->nrb; ++I)
+      for (int J = 0; J < ds->ncb; ++J) {
+        const int p = I * ds->ncb + J;
+        for (int t = ds->term_ptr[p]; t < ds->term_ptr[p + 1]; ++t) {
+          const DevTerm& T = ds->h_terms[t];
+          double *dw, *dof;
+          slots(ds, t, 0, cursor, &dw, &dof);
+          CHECK_RC(launch_grad_stencil_wo(Gm, 1, ldg, alpha, ds->row_off[I], ds->row_len[I], ds->col_off[J], ds->col_len[J], T, 0,
+                                          part.p, dw, dof, s));
+          slots(ds, t, 1, cursor, &dw, &dof);
+          CHECK_RC(launch_grad_stencil_wo(Gm, symmetric ? 1 : ldg, symmetric ? ldg : 1, alpha, ds->col_off[J], ds->col_len[J],
+                                          ds->row_off[I], ds->row_len[I], T, 1, part.p, dw, dof, s));
+        }
+      }
+    return 0;
+  }
+  // the diagonal pairs: entries (i, i) with the weights dw_all (the whole diagonal, N doubles)
+  int contract_diag(const sgp_dspec* ds, const double* dw_all, hipStream_t s) {
+    if (!asked()) return 0;
+    size_t cursor = 0;
+    for (int I = 0; I < ds->nrb; ++I)
+      for (int J = 0; J < ds->ncb; ++J) {
+        const int p = I * ds->ncb + J;
+        for (int t = ds->term_ptr[p]; t < ds->term_ptr[p + 1]; ++t)
+          for (int side = 0; side < 2; ++side) {
+            double *dw, *dof;
+            slots(ds, t, side, cursor, &dw, &dof);
+            if (I != J || ds->row_len[I] != ds->col_len[J]) continue;
+            CHECK_RC(launch_diag_grad_stencil_wo(dw_all + ds->row_off[I], ds->row_len[I], ds->h_terms[t], side, part.p, dw, dof,
+                                                 s));
+          }
+      }
+    return 0;
+  }
+  // after the stream has run: the tables' entries, overwritten
+  int fetch() {
+    if (jobs.empty()) return 0;
+    const Job& last = jobs.back();
+    std::vector<double> h(last.off + (size_t)last.q * (1 + last.dim));
+    SGP_HIP(hipMemcpy(h.data(), out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    for (const Job& j : jobs) {
+      if (j.hw) std::copy(h.begin() + j.off, h.begin() + j.off + j.q, j.hw);
+      if (j.ho) std::copy(h.begin() + j.off + j.q, h.begin() + j.off + (size_t)j.q * (1 + j.dim), j.ho);
+    }
+    return 0;
+  }
+};
+
 // sum_ij G_ij dC_ij / d theta per flattened term of every block pair of `ds` (grad.hip):
 // G = (alpha alpha' - Kinv) / 2 when alpha != nullptr, else G = the matrix at `Gm` itself.
 // Product chains (ds->n_kprod; kprod.hip) are contracted one chain per launch, only where the caller says it carries them
@@ -1876,7 +1992,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
                             double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
                             double* const* grad_inputs, double* const* grad_rowscale = nullptr,
                             double* grad_param = nullptr, bool with_param = false, bool patch_ok = false,
-                            bool stencil_ok = false) {
+                            bool stencil_ok = false, StencilWo* wo = nullptr) {
   // (patch_ok: sgp_logpdf_grad_conv, include/sthenomi_conv_grad.h -- patch terms are contracted, conv.hip;
   // stencil_ok: sgp_logpdf_grad_stencil, include/sthenomi_stencil_grad.h -- stencil terms too, stencil.hip; it sets patch_ok)
   CHECK_ARG(ctx && spec && noise && y && logpdf_out, "sgp_logpdf_grad: NULL argument");
@@ -1913,6 +2029,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   long nrows = TILE + n_pad;            // the (y - m)' row (+ zero padding), then the identity rows
   long m_tot = n_pad + nrows;
   hipStream_t s = ctx->stream;
+  if (wo) CHECK_RC(wo->prepare(ds, "sgp_logpdf_grad_stencil_wo", false, s));   // (wo: include/sthenomi_stencil_wo.h)
   DevBuf dA, dKinv, dmean, dy, dalpha, dpart, dgc, dgs, dgn, dgp;
   NoiseDev nd;
   CHECK_RC(dA.alloc((size_t)m_tot * n_pad));
@@ -2049,6 +2166,8 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
       }
     }
   }
+  // the stencils' own weights and offsets: both sides of every stencil term against the same cotangent (stencil.hip)
+  if (wo) CHECK_RC(wo->contract(ds, dKinv.p, n_pad, dalpha.p, true, s));
   int info = fetch_info(ctx, s);
   if (info < 0) return -3;
   if (info > 0) {
@@ -2056,6 +2175,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
               std::to_string(info));
     return info;
   }
+  if (wo) CHECK_RC(wo->fetch());
   SGP_HIP(hipMemcpy(logpdf_out, d_out, sizeof(double), hipMemcpyDeviceToHost));
   std::vector<double> ha(N);
   SGP_HIP(hipMemcpy(ha.data(), dalpha.p, sizeof(double) * N, hipMemcpyDeviceToHost));
@@ -2138,6 +2258,19 @@ int sgp::drv_logpdf_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const d
   return with_df_fallback(ctx, [&]() {
     return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                             grad_inscale, grad_inputs, nullptr, nullptr, false, true, true);
+  });
+}
+
+// include/sthenomi_stencil_wo.h: sgp_logpdf_grad_stencil_wo (its C entry point, in libsthenomi_stencil_wo.so, forwards here)
+int sgp::drv_logpdf_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
+                                    const double* noise, const double* y, double* logpdf_out, double* grad_y,
+                                    double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
+                                    double* const* grad_inputs, double* const* grad_weights, double* const* grad_offsets) {
+  return with_df_fallback(ctx, [&]() {
+    StencilWo wo;
+    wo.gw = grad_weights, wo.go = grad_offsets;
+    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                            grad_inscale, grad_inputs, nullptr, nullptr, false, true, true, &wo);
   });
 }
 
@@ -3643,7 +3776,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
                           double* const* grad_rowscale_zz = nullptr, double* const* grad_rowscale_xz = nullptr,
                           double* const* grad_colscale_xz = nullptr, const sgp::ElboGradShard* shard = nullptr,
                           double* grad_param_zz = nullptr, double* grad_param_xz = nullptr, bool kprod_ok = false,
-                          bool patch_ok = false, bool stencil_ok = false) {
+                          bool patch_ok = false, bool stencil_ok = false, StencilWo* wo_zz = nullptr,
+                          StencilWo* wo_xz = nullptr) {
   // shard (round 6, multi.hip: sgp_multi_elbo_grad): this call sees ONE rank's slice of the data points (xz, var_x, mean_x, a
   // diagonal noise_x, y and the per-point results are the slice's).  The sums over data points -- A A', A delta, the four
   // scalar sums -- are added up over the ranks by shard->reduce (every rank gets the total), the M x M stage runs replicated
@@ -3668,6 +3802,9 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   const long ld = m_pad + n_rows + m_pad;   // [Kzz + Sigma_z ; K(x,z) Lambda ; I]
   const long ldg = m_pad + TILE + m_pad;    // [A A' + I ; (A delta)' ; I]
   hipStream_t s = ctx->stream;
+  // (wo_zz / wo_xz: include/sthenomi_stencil_wo.h, never on a sharded call)
+  if (wo_zz) CHECK_RC(wo_zz->prepare(gz.ds, "sgp_elbo_grad_stencil_wo", false, s));
+  if (wo_xz) CHECK_RC(wo_xz->prepare(gx.ds, "sgp_elbo_grad_stencil_wo", false, s));
   DevBuf dA, dG, dB, dBinv, dZ, dS, dRZ, dT1, dGzz, dy, dmean, dvar, ddelta, drsig, dots, sq, du, dut, dgy, dgsy,
       dpart, dgcz, dgsz, dgcx, dgsx, dgpz, dgpx;
   NoiseDev ndx, ndz;
@@ -3969,7 +4106,12 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
         }
       }
   }
+  // ---- the stencils' own weights and offsets: G_zz is symmetric, the xz cotangent is read transposed for its column side
+  if (wo_zz) CHECK_RC(wo_zz->contract(gz.ds, dGzz.p, m_pad, nullptr, true, s));
+  if (wo_xz) CHECK_RC(wo_xz->contract(gx.ds, dE.p, n_rows, nullptr, false, s));
   SGP_HIP(hipStreamSynchronize(s));
+  if (wo_zz) CHECK_RC(wo_zz->fetch());
+  if (wo_xz) CHECK_RC(wo_xz->fetch());
   // ---- results
   std::vector<double> hy(N), hs(N);
   SGP_HIP(hipMemcpy(hy.data(), dgy.p, sizeof(double) * N, hipMemcpyDeviceToHost));
@@ -4107,12 +4249,14 @@ int sgp::drv_elbo_grad_param(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return 
 int sgp::drv_elbo_grad_conv(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
 // include/sthenomi_stencil_grad.h: sgp_elbo_grad_stencil (its C entry point, in libsthenomi_stencil_grad.so, forwards here)
 int sgp::drv_elbo_grad_stencil(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
+// include/sthenomi_stencil_wo.h: sgp_elbo_grad_stencil_wo (its C entry point, in libsthenomi_stencil_wo.so, forwards here)
+int sgp::drv_elbo_grad_stencil_wo(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
 
 // sum_i w[i] d var_i / d theta over the diagonal of `spec` (the blocks (I, I) kernelmatrix_diag reads)
 static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
                           double* grad_inscale, double* const* grad_inputs, double* const* grad_rowscale = nullptr,
                           double* const* grad_colscale = nullptr, double* grad_param = nullptr, bool kprod_ok = false,
-                          bool patch_ok = false, bool stencil_ok = false) {
+                          bool patch_ok = false, bool stencil_ok = false, StencilWo* wo = nullptr) {
   // (kprod_ok: sgp_kernelmatrix_diag_grad_param, include/sthenomi_kprod_grad.h -- every output may be NULL there;
   // patch_ok: sgp_kernelmatrix_diag_grad_conv, include/sthenomi_conv_grad.h; stencil_ok: sgp_kernelmatrix_diag_grad_stencil,
   // include/sthenomi_stencil_grad.h)
@@ -4136,13 +4280,20 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
   CHECK_ARG(images_unasked(ds, grad_inputs),
             "sgp_kernelmatrix_diag_grad_stencil: an input read by a patch (convolutional) side holds images, and gradients with "
             "respect to images are not supported: its grad_inputs entry must be NULL");
+  if (wo) CHECK_RC(wo->prepare(ds, "sgp_kernelmatrix_diag_grad_stencil_wo", true, ctx->stream));   // (sthenomi_stencil_wo.h)
   size_t nt = ds->h_terms.size();
   for (size_t t = 0; t < nt; ++t) {
     if (grad_coef) grad_coef[t] = 0.0;
     if (grad_inscale) grad_inscale[t] = 0.0;
     if (grad_param) grad_param[t] = 0.0;
   }
-  if (ds->N == 0 || nt == 0) return 0;
+  if (ds->N == 0 || nt == 0) {
+    if (wo) {
+      SGP_HIP(hipStreamSynchronize(ctx->stream));
+      CHECK_RC(wo->fetch());
+    }
+    return 0;
+  }
   DevBuf dw, dgc, dgs, dgp;
   CHECK_RC(dw.upload(w, ds->N));
   CHECK_RC(dgc.alloc(nt));
@@ -4254,7 +4405,9 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
       t = e;
     }
   }
+  if (wo) CHECK_RC(wo->contract_diag(ds, dw.p, s));   // the stencils' own weights and offsets (stencil.hip)
   SGP_HIP(hipStreamSynchronize(s));
+  if (wo) CHECK_RC(wo->fetch());
   CHECK_RC(fetch_terms(ds, grad_coef, dgc.p));
   CHECK_RC(fetch_terms(ds, grad_inscale, dgs.p));
   CHECK_RC(fetch_terms(ds, grad_param, dgp.p));
@@ -4303,6 +4456,17 @@ int sgp::drv_diag_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const dou
                                double* const* grad_inputs) {
   CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_stencil: NULL argument");
   return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, nullptr, nullptr, nullptr, true, true, true);
+}
+
+// include/sthenomi_stencil_wo.h: sgp_kernelmatrix_diag_grad_stencil_wo (its C entry point, in libsthenomi_stencil_wo.so,
+// forwards here)
+int sgp::drv_diag_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
+                                  double* grad_inscale, double* const* grad_inputs, double* const* grad_weights,
+                                  double* const* grad_offsets) {
+  CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_stencil_wo: NULL argument");
+  StencilWo wo;
+  wo.gw = grad_weights, wo.go = grad_offsets;
+  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, nullptr, nullptr, nullptr, true, true, true, &wo);
 }
 
 int sgp::drv_diag_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
@@ -4710,11 +4874,13 @@ int drv_vfe_partial(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz
 }
 int drv_elbo_grad(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shard) {
   auto run = [&]() {
+    StencilWo wz, wx;
+    wz.gw = a.grad_weights_zz, wz.go = a.grad_offsets_zz, wx.gw = a.grad_weights_xz, wx.go = a.grad_offsets_xz;
     return elbo_grad_core(ctx, a.zz, a.xz, a.var_x, a.mean_x, a.noise_kind, a.noise_x, a.z_noise_kind, a.z_noise, a.y,
                           a.elbo_out, a.grad_y, a.grad_mean, a.grad_noise, a.grad_var_x, a.grad_z_noise, a.grad_coef_zz,
                           a.grad_inscale_zz, a.grad_coef_xz, a.grad_inscale_xz, a.grad_inputs_zz, a.grad_inputs_xz,
                           a.grad_rowscale_zz, a.grad_rowscale_xz, a.grad_colscale_xz, shard, a.grad_param_zz, a.grad_param_xz,
-                          a.kprod_ok, a.patch_ok, a.stencil_ok);
+                          a.kprod_ok, a.patch_ok, a.stencil_ok, wz.asked() ? &wz : nullptr, wx.asked() ? &wx : nullptr);
   };
   // (a rank of a sharded call cannot rerun on its own -- the reduction is collective: multi.hip reruns all of them)
   return shard ? run() : with_df_fallback(ctx, run);

@@ -174,6 +174,18 @@ int launch_grad_stencil_points(const double* Gm, long sr, long sc, const double*
                                const DevTerm& T, int transpose, double scale, double* gx, hipStream_t s);
 // ... on the diagonal: gxr += / gxc -= the per-entry sums (either may be NULL; gxr == gxc: the two cancel, nothing is launched)
 int launch_diag_grad_stencil_points(const double* w, long n, const DevTerm& T, double* gxr, double* gxc, hipStream_t s);
+// ... with respect to the weights and offsets of ONE side's stencil (include/sthenomi_stencil_wo.h): out_w[p] (npoints) and
+// out_o[p * dim + d] (the layout of sgp_stencil.offsets) on the device, overwritten; either may be NULL.  G addressed and
+// `transpose` as for launch_grad_stencil_points: 0 differentiates the row side's stencil, != 0 the column side's.  A plain
+// side is refused.  `partials` holds grad_stencil_wo_partials(nr, nc, T, transpose) doubles (nr, nc: the launch's, after the
+// swap), reduced in a fixed order
+long grad_stencil_wo_partials(long nr, long nc, const DevTerm& T, int transpose);
+int launch_grad_stencil_wo(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                           const DevTerm& T, int transpose, double* partials, double* out_w, double* out_o, hipStream_t s);
+// ... on the diagonal: `partials` holds diag_grad_stencil_wo_partials(n, T, transpose) doubles
+long diag_grad_stencil_wo_partials(long n, const DevTerm& T, int transpose);
+int launch_diag_grad_stencil_wo(const double* w, long n, const DevTerm& T, int transpose, double* partials, double* out_w,
+                                double* out_o, hipStream_t s);
 
 // kprod.hip: product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h).  The terms of one launch are whole chains;
 // kprod_group cuts a pair's chain terms [t, t1) into launches (returns how many terms the launch at t carries, *dmax_out = its

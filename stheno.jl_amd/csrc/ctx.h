@@ -72,6 +72,11 @@ struct ElboGradArgs {
   bool patch_ok = false;
   // sgp_elbo_grad_stencil (include/sthenomi_stencil_grad.h): the leave to carry stencil terms (it sets patch_ok as well)
   bool stencil_ok = false;
+  // sgp_elbo_grad_stencil_wo (include/sthenomi_stencil_wo.h): the stencils' own weights and offsets, two pointers per term
+  double* const* grad_weights_zz = nullptr;
+  double* const* grad_offsets_zz = nullptr;
+  double* const* grad_weights_xz = nullptr;
+  double* const* grad_offsets_xz = nullptr;
 };
 struct ElboGradShard {
   bool primary = false;   // the rank that also produces the zz-side results (G_zz and its contractions)

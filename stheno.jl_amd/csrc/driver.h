@@ -86,6 +86,15 @@ int drv_logpdf_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
 int drv_diag_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
                           double* const* grad_inputs);
 int drv_elbo_grad_stencil(sgp_ctx* ctx, const ElboGradArgs& a);   // a.patch_ok and a.stencil_ok set by the caller
+// sgp_logpdf_grad_stencil_wo, sgp_kernelmatrix_diag_grad_stencil_wo, sgp_elbo_grad_stencil_wo: the same with the gradients with
+// respect to the stencils' own weights and offsets (include/sthenomi_stencil_wo.h, forwarded from libsthenomi_stencil_wo.so)
+int drv_logpdf_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
+                               const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
+                               double* grad_coef, double* grad_inscale, double* const* grad_inputs,
+                               double* const* grad_weights, double* const* grad_offsets);
+int drv_diag_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
+                             double* const* grad_inputs, double* const* grad_weights, double* const* grad_offsets);
+int drv_elbo_grad_stencil_wo(sgp_ctx* ctx, const ElboGradArgs& a);   // a.grad_weights_* / a.grad_offsets_* as well
 int drv_diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStream_t s);
 int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out);   // caller holds the context
 // register a patch geometry on ctx (include/sthenomi_conv.h: sgp_conv_geom, whose C entry point in libsthenomi_conv.so

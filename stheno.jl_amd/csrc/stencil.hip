@@ -588,17 +588,21 @@ int launch_diag_grad_stencil(const double* w, long n, const DevTerm& T, const De
   return 0;
 }
 
+// the term seen from its column points: sides, scales and stencils swapped
+static DevTerm stencil_swapped(const DevTerm& T) {
+  DevTerm U = T;
+  U.xr = T.xc, U.ldr = T.ldc, U.xc = T.xr, U.ldc = T.ldr;
+  U.rs = T.cs, U.cs = T.rs;
+  U.qr = T.qc, U.qc = T.qr;
+  U.str = T.stc, U.stc = T.str;
+  return U;
+}
+
 int launch_grad_stencil_points(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
                                const DevTerm& T, int transpose, double scale, double* gx, hipStream_t s) {
   if (nr <= 0 || nc <= 0 || !gx) return 0;
   if (stencil_term_check(T, "grad (points)")) return -1;
-  DevTerm U = T;
-  if (transpose) {   // the same term seen from its column points: sides and stencils swapped
-    U.xr = T.xc, U.ldr = T.ldc, U.xc = T.xr, U.ldc = T.ldr;
-    U.rs = T.cs, U.cs = T.rs;
-    U.qr = T.qc, U.qc = T.qr;
-    U.str = T.stc, U.stc = T.str;
-  }
+  const DevTerm U = transpose ? stencil_swapped(T) : T;
   const dim3 grid((unsigned)((nr + ST_PROWS - 1) / ST_PROWS));
 #define SGP_STP_CALL(DM)                                                                                              \
   hipLaunchKernelGGL((stencil_points_kernel<DM>), grid, dim3(64 * st_pw<DM>()), 0, s, Gm, sr, sc, alpha, r0, nr, c0, nc, U, \
@@ -617,6 +621,224 @@ int launch_diag_grad_stencil_points(const double* w, long n, const DevTerm& T, d
 #define SGP_STDP_CALL(DM) hipLaunchKernelGGL((stencil_diag_points_kernel<DM>), grid, dim3(256), 0, s, w, n, T, gxr, gxc)
   SGP_STENCIL_DISPATCH(T.dim, SGP_STDP_CALL);
 #undef SGP_STDP_CALL
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+// ======================================================================================================================
+// Gradients with respect to a stencil's own weights and offsets (include/sthenomi_stencil_wo.h).  For the row side of a term,
+// with W_ij = G_ij coef rs_i cs_j and delta_pq = (x_i - a_p) - (y_j - b_q):
+//   grad_weights[p]    =  sum_ij W_ij sum_q v_q k(d2_pq)
+//   grad_offsets[:, p] = -w_p sum_ij W_ij sum_q v_q 2 kappa'(d2_pq) delta_pq
+// and the column side is the same pass on the transposed cotangent with the term's sides and stencils swapped (delta changes
+// its sign with the view, which gives the column side's +).  Q (1 + D) sums do not fit a thread, so the row side's stencil point
+// p is the outer loop:
+//   stencil_wo_kernel         a workgroup of 4 waves owns 64 rows (one per lane) x a strip of ST_WO_STRIP columns; wave w
+//                             takes the strip's columns j = w, w + 4, ..., so the column point is wave-uniform and the read of
+//                             G(:, j) runs along the lanes.  For each p a lane adds 1 + D sums over its columns (in column
+//                             order) and all q (in order); then a 64-lane butterfly, the four waves in wave order through
+//                             LDS, and one partial of 1 + DMAX doubles per (workgroup, p);
+//   stencil_wo_diag_kernel    one thread per diagonal entry, the same sums at (i, i), reduced the same way per workgroup;
+//   stencil_wo_reduce_kernel  one workgroup per output element: 256 strided sums over the workgroups' partials and a fixed
+//                             tree (stencil_grad_reduce_kernel's order); thread 0 writes the element, the offsets times -w_p.
+// Scratch: (row groups x strips) x Q x (1 + DMAX) doubles.  No atomics, nothing depends on the launch order of workgroups.
+// ======================================================================================================================
+constexpr int ST_WO_STRIP = 128;   // columns per workgroup: N = 4096 gives 64 x 32 workgroups
+
+// the sums of one column point y (weight wt = W_ij) into a / g: all q in order
+template <int DMAX>
+__device__ __forceinline__ void stencil_wo_sums(double& a, double (&g)[DMAX], const double (&xs)[DMAX], const double (&y)[DMAX],
+                                                double wt, const double* co, const double* cw, int qc, int kind,
+                                                double param) {
+  for (int q = 0; q < qc; ++q) {
+    double df[DMAX], d2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) {
+      df[d] = xs[d] - (y[d] - co[q * DMAX + d]);
+      d2 = fma(df[d], df[d], d2);
+    }
+    double k, kx;
+    kern_val_dd2(kind, d2, param, k, kx);
+    const double wv = wt * cw[q];
+    a = fma(wv, k, a);
+    const double wk = (2.0 * wv) * kx;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) g[d] = fma(wk, df[d], g[d]);
+  }
+}
+
+// the workgroup's 256 values of each of the 1 + DMAX sums -> dst[0 .. DMAX]: butterfly within a wave, then the four waves in
+// wave order.  red: two buffers, used in turn by consecutive calls (buf = the call's parity), so one barrier per call suffices
+template <int DMAX>
+__device__ __forceinline__ void stencil_wo_combine(double a, double (&g)[DMAX], double (*red)[ST_WAVES][1 + DMAX], int buf,
+                                                   int t, double* dst) {
+  const int lane = t & 63, wv = t >> 6;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    a = a + __shfl_xor(a, m, 64);
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) g[d] = g[d] + __shfl_xor(g[d], m, 64);
+  }
+  if (lane == 0) {
+    red[buf][wv][0] = a;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) red[buf][wv][1 + d] = g[d];
+  }
+  __syncthreads();
+  if (t < 1 + DMAX) dst[t] = ((red[buf][0][t] + red[buf][1][t]) + red[buf][2][t]) + red[buf][3][t];
+}
+
+// T: the term seen from the side whose stencil is differentiated (T.qr >= 1); G(i, j) of the launch's (row point i, column
+// point j) at Gm[(r0 + i) * sr + (c0 + j) * sc], as stencil_points_kernel.  blockIdx.x: the strip, blockIdx.y: the 64 rows;
+// partials[((blockIdx.y * gridDim.x + blockIdx.x) * T.qr + p) * (1 + DMAX) + e]
+template <int DMAX>
+__global__ __launch_bounds__(256) void stencil_wo_kernel(const double* __restrict__ Gm, long sr, long sc,
+                                                         const double* __restrict__ alpha, long r0, long nr, long c0, long nc,
+                                                         DevTerm T, double* __restrict__ partials) {
+  __shared__ StencilLds<DMAX> sm;
+  __shared__ double red[2][ST_WAVES][1 + DMAX];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  stage_stencil<DMAX>(sm.ro, sm.rw, T.str, T.qr, T.dim, t, 256);
+  stage_stencil<DMAX>(sm.co, sm.cw, T.stc, T.qc, T.dim, t, 256);
+  __syncthreads();
+  const int qc = T.qc > 0 ? T.qc : 1;
+  const long i = (long)blockIdx.y * ST_ROWS + lane;
+  const bool live = i < nr;
+  const long il = live ? i : nr - 1;     // (rows past the end read a valid point and add zeros)
+  const long j0 = (long)blockIdx.x * ST_WO_STRIP, j1 = std::min(nc, j0 + ST_WO_STRIP);
+  double x[DMAX];
+  load_pt<DMAX>(x, T.xr + il * T.ldr, T.dim);
+  const double wrow = T.coef * (T.rs ? T.rs[il] : 1.0);
+  double* dst = partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * T.qr * (1 + DMAX);
+  for (int p = 0; p < T.qr; ++p) {
+    double xs[DMAX], g[DMAX], a = 0.0;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) {
+      xs[d] = x[d] - sm.ro[p * DMAX + d];
+      g[d] = 0.0;
+    }
+    if (live) {
+      for (long j = j0 + wv; j < j1; j += ST_WAVES) {
+        double y[DMAX];
+        load_pt<DMAX>(y, T.xc + j * T.ldc, T.dim);
+        const double wt = (st_cotangent(Gm, sr, sc, alpha, r0 + i, c0 + j) * wrow) * (T.cs ? T.cs[j] : 1.0);
+        stencil_wo_sums<DMAX>(a, g, xs, y, wt, sm.co, sm.cw, qc, T.kind, T.param);
+      }
+    }
+    stencil_wo_combine<DMAX>(a, g, red, p & 1, t, dst + (long)p * (1 + DMAX));
+  }
+}
+
+// the diagonal form: entries (i, i) with W_i = w_i coef rs_i cs_i; partials[(blockIdx.x * T.qr + p) * (1 + DMAX) + e]
+template <int DMAX>
+__global__ __launch_bounds__(256) void stencil_wo_diag_kernel(const double* __restrict__ w, long n, DevTerm T,
+                                                              double* __restrict__ partials) {
+  __shared__ StencilLds<DMAX> sm;
+  __shared__ double red[2][ST_WAVES][1 + DMAX];
+  const int t = threadIdx.x;
+  stage_stencil<DMAX>(sm.ro, sm.rw, T.str, T.qr, T.dim, t, 256);
+  stage_stencil<DMAX>(sm.co, sm.cw, T.stc, T.qc, T.dim, t, 256);
+  __syncthreads();
+  const int qc = T.qc > 0 ? T.qc : 1;
+  const long i = (long)blockIdx.x * 256 + t;
+  const bool live = i < n;
+  const long il = live ? i : n - 1;
+  double x[DMAX], y[DMAX];
+  load_pt<DMAX>(x, T.xr + il * T.ldr, T.dim);
+  load_pt<DMAX>(y, T.xc + il * T.ldc, T.dim);
+  const double wt = live ? ((w[il] * T.coef) * (T.rs ? T.rs[il] : 1.0)) * (T.cs ? T.cs[il] : 1.0) : 0.0;
+  double* dst = partials + (long)blockIdx.x * T.qr * (1 + DMAX);
+  for (int p = 0; p < T.qr; ++p) {
+    double xs[DMAX], g[DMAX], a = 0.0;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) {
+      xs[d] = x[d] - sm.ro[p * DMAX + d];
+      g[d] = 0.0;
+    }
+    if (live) stencil_wo_sums<DMAX>(a, g, xs, y, wt, sm.co, sm.cw, qc, T.kind, T.param);
+    stencil_wo_combine<DMAX>(a, g, red, p & 1, t, dst + (long)p * (1 + DMAX));
+  }
+}
+
+// blockIdx.x = p * (1 + dim) + e: e == 0 the weight of point p, e >= 1 coordinate e - 1 of its offset; st: the differentiated
+// stencil (dim x q offsets, then the q weights); an output that is not asked for (NULL) is not formed
+__global__ __launch_bounds__(256) void stencil_wo_reduce_kernel(const double* __restrict__ partials, long nblocks, int q, int dim,
+                                                                int stride, const double* __restrict__ st, double* out_w,
+                                                                double* out_o) {
+  __shared__ double sh[256];
+  const int p = blockIdx.x / (1 + dim), e = blockIdx.x - p * (1 + dim);
+  if (e == 0 ? !out_w : !out_o) return;   // uniform
+  double s = 0.0;
+  for (long b = threadIdx.x; b < nblocks; b += 256) s += partials[(b * q + p) * stride + e];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  if (e == 0) out_w[p] = sh[0];
+  else out_o[(long)p * dim + (e - 1)] = -(st[(long)q * dim + p] * sh[0]);
+}
+
+static inline int st_dmax(int dim) { return dim <= 1 ? 1 : (dim <= 2 ? 2 : (dim <= 4 ? 4 : (dim <= 8 ? 8 : 16))); }
+
+long grad_stencil_wo_partials(long nr, long nc, const DevTerm& T, int transpose) {
+  const int q = transpose ? T.qc : T.qr;
+  if (nr <= 0 || nc <= 0 || q <= 0) return 0;
+  return ((nr + ST_ROWS - 1) / ST_ROWS) * ((nc + ST_WO_STRIP - 1) / ST_WO_STRIP) * q * (1 + st_dmax(T.dim));
+}
+
+long diag_grad_stencil_wo_partials(long n, const DevTerm& T, int transpose) {
+  const int q = transpose ? T.qc : T.qr;
+  if (n <= 0 || q <= 0) return 0;
+  return ((n + 255) / 256) * q * (1 + st_dmax(T.dim));
+}
+
+int launch_grad_stencil_wo(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                           const DevTerm& T, int transpose, double* partials, double* out_w, double* out_o, hipStream_t s) {
+  if (nr <= 0 || nc <= 0 || (!out_w && !out_o)) return 0;
+  if (stencil_term_check(T, "grad (weights and offsets)")) return -1;
+  const DevTerm U = transpose ? stencil_swapped(T) : T;
+  if (U.qr < 1) {
+    set_error("grad (weights and offsets): plain side: it has no stencil to differentiate");
+    return -1;
+  }
+  const long gx = (nc + ST_WO_STRIP - 1) / ST_WO_STRIP, gy = (nr + ST_ROWS - 1) / ST_ROWS;
+  if (gy > 65535) {
+    set_error("grad (weights and offsets): too many rows for one stencil launch");
+    return -1;
+  }
+#define SGP_STWO_CALL(DM)                                                                                                  \
+  hipLaunchKernelGGL((stencil_wo_kernel<DM>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, Gm, sr, sc, alpha, r0, nr, \
+                     c0, nc, U, partials)
+  SGP_STENCIL_DISPATCH(T.dim, SGP_STWO_CALL);
+#undef SGP_STWO_CALL
+  SGP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(stencil_wo_reduce_kernel, dim3((unsigned)(U.qr * (1 + U.dim))), dim3(256), 0, s, partials, gx * gy, U.qr,
+                     U.dim, 1 + st_dmax(U.dim), U.str, out_w, out_o);
+  SGP_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_diag_grad_stencil_wo(const double* w, long n, const DevTerm& T, int transpose, double* partials, double* out_w,
+                                double* out_o, hipStream_t s) {
+  if (n <= 0 || (!out_w && !out_o)) return 0;
+  if (stencil_term_check(T, "kernelmatrix_diag_grad (weights and offsets)")) return -1;
+  const DevTerm U = transpose ? stencil_swapped(T) : T;
+  if (U.qr < 1) {
+    set_error("kernelmatrix_diag_grad (weights and offsets): plain side: it has no stencil to differentiate");
+    return -1;
+  }
+  const long gx = (n + 255) / 256;
+#define SGP_STWOD_CALL(DM) \
+  hipLaunchKernelGGL((stencil_wo_diag_kernel<DM>), dim3((unsigned)gx), dim3(256), 0, s, w, n, U, partials)
+  SGP_STENCIL_DISPATCH(T.dim, SGP_STWOD_CALL);
+#undef SGP_STWOD_CALL
+  SGP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(stencil_wo_reduce_kernel, dim3((unsigned)(U.qr * (1 + U.dim))), dim3(256), 0, s, partials, gx, U.qr, U.dim,
+                     1 + st_dmax(U.dim), U.str, out_w, out_o);
   SGP_HIP(hipGetLastError());
   return 0;
 }

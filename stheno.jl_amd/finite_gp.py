@@ -13,7 +13,7 @@ import numpy as np
 
 from . import kernels as _kernels
 from . import lib as _lib
-from .flatten import build_spec, chain_input_gradients, zero_spec
+from .flatten import build_spec, chain_input_gradients, stencil_node_gradients, zero_spec
 from .gp import SthenoAbstractGP, mean_vector
 from .gppp import GPPP
 from .inputs import BlockData, eltype as _eltype
@@ -676,7 +676,34 @@ def _input_buffers(spec):
     return arrs, (C.POINTER(C.c_double) * max(1, len(arrs)))(*[_lib.dptr(a) for a in arrs])
 
 
-def logpdf_and_gradient_stencil(fx, y, inputs=False):
+def _stencil_tables(spec):
+    """the output tables of include/sthenomi_stencil_wo.h for `spec`: gw[t][side] (Q) and go[t][side] (Q x D in memory: the
+    layout of sgp_stencil.offsets), None on a plain side, and the two ctypes tables of 2 pointers per term"""
+    nt = spec.n_terms
+    gw = [[None if st is None else np.zeros(len(st[1])) for st in spec.term_stencils[t]] for t in range(nt)]
+    go = [[None if st is None else np.zeros(st[0].shape[::-1]) for st in spec.term_stencils[t]] for t in range(nt)]
+    tab = lambda g: (C.POINTER(C.c_double) * max(1, 2 * nt))(*[_lib.dptr(a) for row in g for a in row])    # noqa: E731
+    return gw, go, tab(gw), tab(go)
+
+
+def _attach_stencil_gradients(records, spec, gw, go, into):
+    """d_row_weights / d_row_offsets / d_col_weights / d_col_offsets on the records of stencil terms (None on a plain side;
+    offsets D x Q; the mirror term folded in with its sides swapped), and the chain back to the model's stencil nodes added
+    onto `into` (flatten.stencil_node_gradients)"""
+    go = [[None if a is None else a.T for a in row] for row in go]
+    for r in records:
+        t, mt = r["t"], r.get("mirror_t")
+        if spec.term_stencils[t] == (None, None):
+            continue
+        for side, name in enumerate(("row", "col")):
+            w, o = gw[t][side], go[t][side]
+            if w is not None and mt is not None:
+                w, o = w + gw[mt][1 - side], o + go[mt][1 - side]
+            r[f"d_{name}_weights"], r[f"d_{name}_offsets"] = w, (None if o is None else np.array(o))
+    return stencil_node_gradients(spec, gw, go, into)
+
+
+def logpdf_and_gradient_stencil(fx, y, inputs=False, stencils=False):
     """logpdf_and_gradient(fx, y, inputs=inputs) for every model it takes AND for models with stencil terms (`stencil`,
     `quadrature_convolve`) or patch_convolve terms, through sgp_logpdf_grad_stencil (include/sthenomi_stencil_grad.h): the
     same dict.  For a stencil term coef rs cs sum_pq w_p v_q k(x - a_p, x' - b_q) the record's d_coef is the derivative
@@ -684,8 +711,16 @@ def logpdf_and_gradient_stencil(fx, y, inputs=False):
     scale g of the points and the offsets (a lengthscale l = 1 / g gives d / dl = -g^2 d_inscale), exactly as for a plain
     term; the record also carries row_stencil / col_stencil.  inputs=True adds `inputs` and `x`: the stored points of a
     stencil side are the unshifted ones (shifting is a translation), so the chain back through Stretch / Shift / Select is
-    that of a plain term; the entry of an input that holds images is None.  Gradients with respect to a stencil's weights and
-    offsets are not formed.  Single-GPU contexts."""
+    that of a plain term; the entry of an input that holds images is None.  Single-GPU contexts.
+
+    stencils=True adds the gradients with respect to the stencils' own weights and offsets, through
+    sgp_logpdf_grad_stencil_wo (include/sthenomi_stencil_wo.h); everything else keeps its bits.  Each record of a stencil term
+    also carries d_row_weights (Q), d_row_offsets (D x Q), d_col_weights, d_col_offsets: the derivative with respect to the
+    stencil the library reads on that side (offsets in the kernel's scaled coordinates), None on a plain side, the mirror
+    term folded in with its sides swapped.  The result carries `stencils`: one entry per `stencil(...)` node of the model that
+    the observed processes reach, {"node", "d_offsets" (D x Q, the node's own shape), "d_weights" (Q)} -- the chain back
+    through the kernel's scalar input scale, the Stretch / Select maps below the node and nested stencils
+    (flatten.stencil_node_gradients); a scalar scale above or below the node belongs to the term's coefficient."""
     if not _is_prior(fx.f):
         raise NotImplementedError("gradients are implemented for prior Stheno processes")
     n = len(fx)
@@ -693,18 +728,32 @@ def logpdf_and_gradient_stencil(fx, y, inputs=False):
     spec = _prior_spec(fx.f, fx.x)
     _refuse_stencil_family("logpdf_and_gradient_stencil", spec)
     if spec.has_kprod:
-        return logpdf_and_gradient_param(fx, y, inputs=True) if inputs else logpdf_and_gradient(fx, y)
+        rec = logpdf_and_gradient_param(fx, y, inputs=True) if inputs else logpdf_and_gradient(fx, y)
+        if stencils:
+            rec["stencils"] = []       # (a model with a product of kernels has no stencil terms)
+        return rec
     m = _f64(mean_vector(fx.f, fx.x))
     kind, nbuf = _lib._noise_args(fx.noise, n)
     lp = np.zeros(1)
     gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
     gx, ptrs = _input_buffers(spec) if inputs else (None, None)
-    rc = _ctx().stencil_grad.sgp_logpdf_grad_stencil(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                                     _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm),
-                                                     _lib.dptr(gn), _lib.dptr(gc), _lib.dptr(gs), ptrs)
-    _lib.check(rc, "sgp_logpdf_grad_stencil")
+    if stencils:
+        gw, go, pw, po = _stencil_tables(spec)
+        rc = _ctx().stencil_wo.sgp_logpdf_grad_stencil_wo(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
+                                                          _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm),
+                                                          _lib.dptr(gn), _lib.dptr(gc), _lib.dptr(gs), ptrs, pw, po)
+        _lib.check(rc, "sgp_logpdf_grad_stencil_wo")
+    else:
+        rc = _ctx().stencil_grad.sgp_logpdf_grad_stencil(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
+                                                         _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm),
+                                                         _lib.dptr(gn), _lib.dptr(gc), _lib.dptr(gs), ptrs)
+        _lib.check(rc, "sgp_logpdf_grad_stencil")
     xb = chain_input_gradients(spec, gx)[0] if inputs else None
-    return _grad_record(spec, kind, lp[0], bufs, gx, xb)
+    rec = _grad_record(spec, kind, lp[0], bufs, gx, xb)
+    if stencils:
+        rec["stencils"] = list(_attach_stencil_gradients(rec["terms"], spec, gw, go, {}).values())
+        rec["_raw_stencils"] = (gw, go)
+    return rec
 
 
 def logpdf_and_gradient_batch(fxs, ys, return_infos=False):
@@ -1399,15 +1448,20 @@ def elbo_and_gradient_conv(vfe, fx, y=None, inputs=False):
                 _specs=dict(zz=zz, xz=xz, xx=xx))
 
 
-def elbo_and_gradient_stencil(vfe, fx, y=None, inputs=False):
+def elbo_and_gradient_stencil(vfe, fx, y=None, inputs=False, stencils=False):
     """elbo_and_gradient for every model it takes (without a product of kernels) AND for models with stencil terms (`stencil`,
     `quadrature_convolve`) or patch_convolve terms, through sgp_elbo_grad_stencil and sgp_kernelmatrix_diag_grad_stencil
     (include/sthenomi_stencil_grad.h): the same dict (see elbo_and_gradient; `scales` is None).  inputs=True adds zz_inputs /
     xz_inputs, `x` and `z` as elbo_and_gradient does -- a stencil side's stored points are the unshifted ones, so the chain back
     onto the blocks of fx.x and fz.x is that of a plain term; an entry that holds images (an input read by a patched side) is
-    None and contributes nothing.  Single-GPU contexts."""
+    None and contributes nothing.  Single-GPU contexts.
+
+    stencils=True adds the gradients with respect to the stencils' own weights and offsets, through sgp_elbo_grad_stencil_wo
+    and sgp_kernelmatrix_diag_grad_stencil_wo (include/sthenomi_stencil_wo.h), as logpdf_and_gradient_stencil does: the records
+    of zz_terms / xz_terms / xx_terms carry d_row_weights, d_row_offsets, d_col_weights, d_col_offsets, and `stencils` holds
+    one entry per stencil node, summed over the three places the bound reads it (K(z,z), K(x,z), diag K(x,x))."""
     if isinstance(vfe, SparseFiniteGP):
-        return elbo_and_gradient_stencil(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs)
+        return elbo_and_gradient_stencil(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, stencils=stencils)
     zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
     n, m = len(fx), len(vfe.fz)
     yv = _f64(np.asarray(y, dtype=np.float64).ravel())
@@ -1427,14 +1481,21 @@ def elbo_and_gradient_stencil(vfe, fx, y=None, inputs=False):
         gxz, pz = _input_buffers(zz)
         gxx, px = _input_buffers(xz)
         gdx, pd = _input_buffers(xx)     # var(f, x) depends on x wherever a diagonal term reads two different views of x
-    rc = lib.sgp_elbo_grad_stencil(_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(var_x), _lib.dptr(mean_x), nk, _lib.dptr(nbuf),
-                                   zk, _lib.dptr(zbuf), _lib.dptr(yv), _lib.dptr(out), _lib.dptr(gy), _lib.dptr(gm),
-                                   _lib.dptr(gn), _lib.dptr(gv), _lib.dptr(gzn), _lib.dptr(gcz), _lib.dptr(gsz), _lib.dptr(gcx),
-                                   _lib.dptr(gsx), pz, px)
-    _lib.check(rc, "sgp_elbo_grad_stencil")
+    e_args = (_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(var_x), _lib.dptr(mean_x), nk, _lib.dptr(nbuf), zk, _lib.dptr(zbuf),
+              _lib.dptr(yv), _lib.dptr(out), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn), _lib.dptr(gv), _lib.dptr(gzn),
+              _lib.dptr(gcz), _lib.dptr(gsz), _lib.dptr(gcx), _lib.dptr(gsx), pz, px)
     gcd, gsd = np.zeros(max(1, xx.n_terms)), np.zeros(max(1, xx.n_terms))
-    rc = lib.sgp_kernelmatrix_diag_grad_stencil(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd)
-    _lib.check(rc, "sgp_kernelmatrix_diag_grad_stencil")
+    if stencils:
+        wo = _ctx().stencil_wo
+        tz, tx, td = _stencil_tables(zz), _stencil_tables(xz), _stencil_tables(xx)
+        _lib.check(wo.sgp_elbo_grad_stencil_wo(*e_args, tz[2], tz[3], tx[2], tx[3]), "sgp_elbo_grad_stencil_wo")
+        rc = wo.sgp_kernelmatrix_diag_grad_stencil_wo(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd,
+                                                      td[2], td[3])
+        _lib.check(rc, "sgp_kernelmatrix_diag_grad_stencil_wo")
+    else:
+        _lib.check(lib.sgp_elbo_grad_stencil(*e_args), "sgp_elbo_grad_stencil")
+        rc = lib.sgp_kernelmatrix_diag_grad_stencil(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd)
+        _lib.check(rc, "sgp_kernelmatrix_diag_grad_stencil")
     nb = len(xx.row_len)
     xx_terms = [r for r in _term_records(xx, gcd, gsd, False) if r["I"] == r["J"]] if nb else []
     xb = zb = None
@@ -1443,12 +1504,19 @@ def elbo_and_gradient_stencil(vfe, fx, y=None, inputs=False):
         xr, zc = chain_input_gradients(xz, gxx)
         xd, _ = chain_input_gradients(xx, gdx)
         xb, zb = [a + b for a, b in zip(xr, xd)], [a + b for a, b in zip(zr, zc)]
-    return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
-                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
-                zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
-                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx, scales=None,
-                _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
-                _specs=dict(zz=zz, xz=xz, xx=xx))
+    rec = dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
+               z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
+               zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
+               xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx, scales=None,
+               _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
+               _specs=dict(zz=zz, xz=xz, xx=xx))
+    if stencils:
+        nodes = {}
+        for key, sp, tb in (("zz_terms", zz, tz), ("xz_terms", xz, tx), ("xx_terms", xx, td)):
+            _attach_stencil_gradients(rec[key], sp, tb[0], tb[1], nodes)
+        rec["stencils"] = list(nodes.values())
+        rec["_raw_stencils"] = dict(zz=tz[:2], xz=tx[:2], xx=td[:2])
+    return rec
 
 
 def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):

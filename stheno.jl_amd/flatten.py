@@ -34,13 +34,18 @@ from .inputs import BlockData, ColVecs, GPPPInput, as_matrix, blocks, is_pair_ve
 
 
 class _Path:
-    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom", "st")
+    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom", "st", "prov")
 
-    def __init__(self, key, atom, c, r, X, chain=(), geom=None, st=None):
+    def __init__(self, key, atom, c, r, X, chain=(), geom=None, st=None, prov=None):
         # chain: the input warps applied on the way down, outermost first, as (warp, inputs before it)
         # geom: (H, W, ph, pw) when the path passed a patch_convolve node -- X then holds the flattened images
         # st: (offsets D x Q, weights Q) when the path passed a stencil node -- the offsets in the coordinates of X
+        # prov: where st came from, for the chain rule of stencil_node_gradients: [(c_i, layers_i)], one entry per walk that
+        #       was merged into this path (sum c_i == c); layers = ((stencil node, M), ...) outermost first, M (dim of X x dim
+        #       of the node's offsets) the product of the Stretch / Select maps below the node.  Point (p_1, ..., p_K) of st
+        #       sits at the C-order index of its tuple: offsets sum_k M_k A_k[:, p_k], weight prod_k w_k[p_k]
         self.key, self.atom, self.c, self.r, self.X, self.chain, self.geom, self.st = key, atom, c, r, X, chain, geom, st
+        self.prov = prov
 
 
 class _ScaleVector(np.ndarray):
@@ -158,7 +163,8 @@ def _paths(f, x, c, r, key, mat, chain=(), geom=None):
     if op == "stencil":
         # sum_q w_q f(x - a_q): the paths of f read these points, shifted by the stencil in the library
         # (include/sthenomi_stencil.h)
-        return _stencil_paths(f.args[1], x, c, r, key, mat, chain, (f.args[2], f.args[3]))
+        return _stencil_paths(f.args[1], x, c, r, key, mat, chain, (f.args[2], f.args[3]),
+                              ((f, np.eye(f.args[2].shape[0])),))
     if op == "cross":
         raise ValueError("cross(...) can only appear at block level")
     raise ValueError(op)
@@ -207,10 +213,10 @@ def _map_offsets(g, A):
     return A[np.asarray(g.idx), :]
 
 
-def _stencil_paths(f, x, c, r, key, mat, chain, st):
+def _stencil_paths(f, x, c, r, key, mat, chain, st, layers):
     """the paths below a stencil node: what commutes with shifting the points -- sums, scalar scales, `+ known`, Shift
     (moves the points), Stretch and Select (map the points and the offsets alike), and stencils (which fold into one) --
-    and nothing else"""
+    and nothing else.  layers: the provenance of st (_Path.prov)"""
     A, w = st
     if isinstance(f, _gp.AtomicGP):
         if isinstance(f.gp, _gp.GP):
@@ -221,28 +227,30 @@ def _stencil_paths(f, x, c, r, key, mat, chain, st):
                 raise NotImplementedError(f"stencil: {len(w)} points of dimension {A.shape[0]} are beyond the library's "
                                           f"limits ({_lib.STENCIL_MAX_POINTS} points, dimension "
                                           f"{_lib.STENCIL_MAX_DIM})")
-            return [_Path(key + (id(f),), f, c, r, X, chain, None, st)]
+            return [_Path(key + (id(f),), f, c, r, X, chain, None, st, [(c, layers)])]
         raise NotImplementedError("stencil of a nested GPPP is not supported")
     if isinstance(f, GPPP) or not isinstance(f, _gp.DerivedGP):
         raise NotImplementedError(f"stencil over {type(f).__name__} is not supported")
     op = f.args[0]
     if op == "+":
-        return (_stencil_paths(f.args[1], x, c, r, key, mat, chain, st) +
-                _stencil_paths(f.args[2], x, c, r, key, mat, chain, st))
+        return (_stencil_paths(f.args[1], x, c, r, key, mat, chain, st, layers) +
+                _stencil_paths(f.args[2], x, c, r, key, mat, chain, st, layers))
     if op == "+known":
-        return _stencil_paths(f.args[2], x, c, r, key, mat, chain, st)
+        return _stencil_paths(f.args[2], x, c, r, key, mat, chain, st, layers)
     if op == "*":
         s = f.args[1]
         if not _gp._is_real(s):
             raise NotImplementedError("stencil: a function scale below a stencil does not commute with its shifts (only "
                                       "scalar scales do)")
-        return _stencil_paths(f.args[2], x, c * float(s), r, key, mat, chain, st)
+        return _stencil_paths(f.args[2], x, c * float(s), r, key, mat, chain, st, layers)
     if op == "o":
         g = f.args[2]
         if isinstance(g, _gp.Shift):
-            return _stencil_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), st)
+            return _stencil_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), st, layers)
         if isinstance(g, (_gp.Stretch, _gp.Select)):
-            return _stencil_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), (_map_offsets(g, A), w))
+            # (the maps are linear: the provenance matrices go through the same function as the offsets)
+            return _stencil_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), (_map_offsets(g, A), w),
+                                  tuple((n, _map_offsets(g, M)) for n, M in layers))
         raise NotImplementedError(f"stencil: the warp {_warp_name(g)} below a stencil does not commute with its shifts "
                                   "(only Shift, Stretch and Select do)")
     if op == "stencil":
@@ -251,7 +259,8 @@ def _stencil_paths(f, x, c, r, key, mat, chain, st):
         if B.shape[0] != A.shape[0]:
             raise ValueError(f"stencil: offsets of dimension {B.shape[0]} below offsets of dimension {A.shape[0]}")
         A2 = (A[:, :, None] + B[:, None, :]).reshape(A.shape[0], -1)
-        return _stencil_paths(f.args[1], x, c, r, key, mat, chain, (A2, np.outer(w, v).reshape(-1)))
+        return _stencil_paths(f.args[1], x, c, r, key, mat, chain, (A2, np.outer(w, v).reshape(-1)),
+                              layers + ((f, np.eye(B.shape[0])),))
     if op == "conv":
         raise NotImplementedError("stencil of a patch_convolve is not supported")
     raise NotImplementedError(f"stencil over `{op}` is not supported")
@@ -261,18 +270,24 @@ def _st_key(st):
     return None if st is None else (st[0].shape, st[0].tobytes(), st[1].tobytes())
 
 
-def _merge_paths(ps):
+def _merge_paths(ps, cancelled=None):
+    """cancelled (a list): gains the stencil paths that cancel exactly -- their term is gone, and with it the gradient with
+    respect to their stencils, which does not vanish (stencil_node_gradients refuses such a spec)"""
     out, index = [], {}
     for p in ps:
         k = (p.key, id(p.X), id(p.r) if p.r is not None else None, p.geom, _st_key(p.st))
         if k in index:
             index[k].c += p.c
+            if p.prov is not None:
+                index[k].prov = index[k].prov + p.prov
         else:
-            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom, p.st)
+            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom, p.st, None if p.prov is None else list(p.prov))
             index[k] = q
             out.append(q)
     # paths that cancel exactly (f - f, 2 f - f - f, ...) leave no term: the block is an exact zero, as in the
     # reference's recursion, which adds and subtracts identical matrices
+    if cancelled is not None:
+        cancelled.extend(q for q in out if q.c == 0.0 and q.st is not None)
     return [q for q in out if q.c != 0.0]
 
 
@@ -304,13 +319,14 @@ def build_spec(f, x, f2=None, x2=None):
     gpcs = {id(n.gpc) for n, _ in rows} | {id(n.gpc) for n, _ in cols}
     if len(gpcs) > 1:
         raise AssertionError("f.gpc === f'.gpc violated: processes come from different GPCs")
-    rpaths = [_merge_paths(_paths(n, v, 1.0, None, (), mat)) for n, v in rows]
-    cpaths = rpaths if symmetric else [_merge_paths(_paths(n, v, 1.0, None, (), mat)) for n, v in cols]
+    cancelled = []
+    rpaths = [_merge_paths(_paths(n, v, 1.0, None, (), mat), cancelled) for n, v in rows]
+    cpaths = rpaths if symmetric else [_merge_paths(_paths(n, v, 1.0, None, (), mat), cancelled) for n, v in cols]
     table = _InputTable()
-    pairs, geoms, stencils = {}, {}, {}
+    pairs, geoms, stencils, provs = {}, {}, {}, {}
     for I, pi in enumerate(rpaths):
         for J, pj in enumerate(cpaths):
-            merged, order = {}, []
+            merged, order, prov = {}, [], {}
             for p in pi:
                 for q in pj:
                     if p.key != q.key:
@@ -373,6 +389,13 @@ def build_spec(f, x, f2=None, x2=None):
                         else:
                             merged[k] = ([[kind, ri, ci, p.c * q.c * kc, param, p.r, q.r]], (p.geom, q.geom), sts)
                             order.append(k)
+                        if has_st:
+                            # the provenance of the term's two stencils: every walk's part of the coefficient, per side
+                            acc = prov.setdefault(k, (sc, [], []))
+                            if p.st is not None:
+                                acc[1].extend((ci_ * q.c * kc, layers) for ci_, layers in p.prov)
+                            if q.st is not None:
+                                acc[2].extend((p.c * cj_ * kc, layers) for cj_, layers in q.prov)
             if order:
                 # (a key holds one term, or the terms of one chain: a head and its continuations, which have plain sides)
                 pairs[(I, J)] = [tuple(t) for k in order for t in merged[k][0]]
@@ -381,9 +404,15 @@ def build_spec(f, x, f2=None, x2=None):
                     geoms[(I, J)] = [merged[k][1] if n == 0 else plain for k in order for n in range(len(merged[k][0]))]
                 if any(merged[k][2] != plain for k in order):
                     stencils[(I, J)] = [merged[k][2] if n == 0 else plain for k in order for n in range(len(merged[k][0]))]
+                    provs[(I, J)] = [prov.get(k) if n == 0 else None for k in order for n in range(len(merged[k][0]))]
     spec = _lib.Spec([len(v) for _, v in rows], [len(v) for _, v in cols], table.arrays, pairs, symmetric,
                      geoms=geoms or None, stencils=stencils or None)
     spec._mat_keep = mat  # keep the source arrays alive (ids are identity keys)
+    # per term (the order of spec.term_stencils): None, or (kernel input scale, row side, column side), a side being the
+    # list of (part of the term's coefficient, layers) of _Path.prov -- what stencil_node_gradients chains back through
+    spec.term_stencil_prov = [e for I in range(len(rows)) for J in range(len(cols))
+                              for e in provs.get((I, J), [None] * len(pairs.get((I, J), [])))]
+    spec.stencil_cancelled = bool(cancelled)
     spec.input_origin = table.origin   # per spec input: (side, block, warp chain, kernel input chain, raw points)
     spec.block_shapes = ([_leaf_shape(v) for _, v in rows], [_leaf_shape(v) for _, v in cols])
     return spec, rows, cols
@@ -398,6 +427,48 @@ def _leaf_shape(v):
     while isinstance(v, GPPPInput):   # nested programmes index a process of the inner GPPP
         v = v.x
     return as_matrix(v).shape
+
+
+def stencil_node_gradients(spec, gw, go, into=None):
+    """The chain from the library's stencils back to the `stencil(...)` nodes of the model.  gw[t][side] / go[t][side]: the
+    gradient with respect to the weights (Q) and offsets (D x Q) of the stencil that term t of `spec` reads on its row (0) or
+    column (1) side, None on a plain side (include/sthenomi_stencil_wo.h: every term's own copy, mirror pairs included).
+    The library's offsets are sc M_k A_k summed over the nested nodes k (sc: the kernel's scalar input scale, M_k: the
+    Stretch / Select maps below node k) and its weights their outer product, so
+        dA_k[:, p_k] = sc M_k' sum_others dA_lib,      dw_k[p_k] = sum_others dw_lib prod_{j != k} w_j[p_j];
+    a term merged from several walks gives each its part of the coefficient, c_walk / coef.  Returns (and adds onto) `into`:
+    id(node) -> {"node", "d_offsets" (D x Q, the node's own shape), "d_weights" (Q)}, in the order the nodes are met."""
+    into = {} if into is None else into
+    if getattr(spec, "stencil_cancelled", False):
+        raise NotImplementedError("gradients with respect to stencils: two stencil views of one process cancel exactly in this "
+                                  "model (their term is gone, their stencils' gradient is not)")
+    for t, prov in enumerate(getattr(spec, "term_stencil_prov", None) or []):
+        if prov is None:
+            continue
+        sc, coef = prov[0], float(spec._terms[t].coef)
+        for side in (0, 1):
+            walks = prov[1 + side]
+            if not walks:
+                continue
+            if coef == 0.0 and len(walks) > 1:
+                raise NotImplementedError("gradients with respect to stencils: a term merged from several stencil views whose "
+                                          "coefficients cancel exactly has no shares to hand out")
+            dA, dw = np.asarray(go[t][side], dtype=np.float64), np.asarray(gw[t][side], dtype=np.float64)
+            for part, layers in walks:
+                share = part / coef if coef != 0.0 else 1.0
+                ws = [np.asarray(n.args[3], dtype=np.float64) for n, _ in layers]
+                qs = tuple(len(w) for w in ws)
+                dAr, dwr = dA.reshape((dA.shape[0],) + qs), dw.reshape(qs)
+                for k, (node, M) in enumerate(layers):
+                    others = tuple(j for j in range(len(qs)) if j != k)
+                    wo = dwr
+                    for j in others:      # times the other nodes' weights, along their own axes
+                        wo = wo * ws[j].reshape([-1 if a == j else 1 for a in range(len(qs))])
+                    e = into.setdefault(id(node), {"node": node, "d_offsets": np.zeros(np.shape(node.args[2])),
+                                                   "d_weights": np.zeros(qs[k])})
+                    e["d_offsets"] += share * sc * (M.T @ dAr.sum(axis=tuple(1 + j for j in others)))
+                    e["d_weights"] += share * wo.sum(axis=others)
+    return into
 
 
 def zero_spec(n):

@@ -25,6 +25,7 @@ CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 CONV_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv_grad.so")
 STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
 STENCIL_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil_grad.so")
+STENCIL_WO_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil_wo.so")
 KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
 KPROD_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod_grad.so")
 
@@ -317,6 +318,22 @@ def stencil_grad_symbols():
     return sorted(_SIGS_STENCIL_GRAD)
 
 
+# include/sthenomi_stencil_wo.h: the same three plus the gradients with respect to the stencils' own weights and offsets (two
+# tables of 2 pointers per term; the ELBO: one pair for zz, one for xz), exported by libsthenomi_stencil_wo.so --
+# logpdf_and_gradient_stencil(..., stencils=True) and elbo_and_gradient_stencil(..., stencils=True) reach them through
+# stencil_wo_lib() / Context.stencil_wo
+_SIGS_STENCIL_WO = {
+    "sgp_logpdf_grad_stencil_wo": (C.c_int, _SIGS_STENCIL_GRAD["sgp_logpdf_grad_stencil"][1] + [_DD, _DD]),
+    "sgp_kernelmatrix_diag_grad_stencil_wo": (C.c_int, _SIGS_STENCIL_GRAD["sgp_kernelmatrix_diag_grad_stencil"][1] + [_DD, _DD]),
+    "sgp_elbo_grad_stencil_wo": (C.c_int, _SIGS_STENCIL_GRAD["sgp_elbo_grad_stencil"][1] + [_DD, _DD, _DD, _DD]),
+}
+
+
+def stencil_wo_symbols():
+    """Names include/sthenomi_stencil_wo.h declares: the entry points of libsthenomi_stencil_wo.so."""
+    return sorted(_SIGS_STENCIL_WO)
+
+
 def conv_grad_symbols():
     """Names include/sthenomi_conv_grad.h declares: the entry points of libsthenomi_conv_grad.so."""
     return sorted(_SIGS_CONV_GRAD)
@@ -589,6 +606,27 @@ def stencil_grad_lib():
         return lib
 
 
+_stencil_wo = None
+
+
+def stencil_wo_lib():
+    """dlopen libsthenomi_stencil_wo.so (include/sthenomi_stencil_wo.h) after the product library it links against."""
+    global _stencil_wo
+    load()
+    with _lib_lock:
+        if _stencil_wo is not None:
+            return _stencil_wo
+        if not os.path.exists(STENCIL_WO_LIB_PATH):
+            raise SthenoMIError(f"{STENCIL_WO_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(STENCIL_WO_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_STENCIL_WO.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _stencil_wo = lib
+        return lib
+
+
 _stencil = None
 
 
@@ -751,6 +789,11 @@ class Context:
     def stencil_grad(self):
         """libsthenomi_stencil_grad.so (sthenomi_stencil_grad.h): `ctx.stencil_grad.sgp_logpdf_grad_stencil(ctx.handle, ...)`"""
         return stencil_grad_lib()
+
+    @property
+    def stencil_wo(self):
+        """libsthenomi_stencil_wo.so (sthenomi_stencil_wo.h): `ctx.stencil_wo.sgp_logpdf_grad_stencil_wo(ctx.handle, ...)`"""
+        return stencil_wo_lib()
 
     @property
     def extend(self):
