@@ -22,6 +22,8 @@ const LIB_POOL = get(ENV, "STHENOMI_POOL_LIB", joinpath(dirname(LIB), "libstheno
 const LIB_EXTEND = get(ENV, "STHENOMI_EXTEND_LIB", joinpath(dirname(LIB), "libsthenomi_extend.so"))
 # include/sthenomi_postfx.h (sgp_posterior_rand / _logpdf and their sparse forms: rand / logpdf of f_post(x*, Σ*)): likewise
 const LIB_POSTFX = get(ENV, "STHENOMI_POSTFX_LIB", joinpath(dirname(LIB), "libsthenomi_postfx.so"))
+# include/sthenomi_predgrad.h (sgp_posterior_predict_grad_x and its sparse form: mean, var and their gradients in x*): likewise
+const LIB_PREDGRAD = get(ENV, "STHENOMI_PREDGRAD_LIB", joinpath(dirname(LIB), "libsthenomi_predgrad.so"))
 # include/sthenomi_vfe_update.h (sgp_sparse_posterior_update / _count: new data into a kept sparse posterior): likewise
 const LIB_VFE_UPDATE = get(ENV, "STHENOMI_VFE_UPDATE_LIB", joinpath(dirname(LIB), "libsthenomi_vfe_update.so"))
 # include/sthenomi_kprod.h (sgp_logpdf_grad_param: + d / d kernel parameters, through product chains and plain terms): likewise
@@ -690,6 +692,35 @@ function rand_with(fx::SparsePostFGP, Z::Matrix{Float64})
 end
 rand(rng::AbstractRNG, fx::Union{PostFGP,SparsePostFGP}, S::Int) = rand_with(fx, randn(rng, Float64, length(fx), S))
 rand(rng::AbstractRNG, fx::Union{PostFGP,SparsePostFGP}) = vec(rand(rng, fx, 1))
+
+# ---- mean_and_var of f_post(x*) with the gradients in x* (include/sthenomi_predgrad.h) --------------------------------
+# The "look" step of condition - look - add points: `mean_and_var_and_gradient(f_post(xp))` returns mean, var (Σ* added to var
+# only) and, per uploaded input array of the cross and prior specs, the per-point gradients the library writes (dim x n,
+# column i = d mean_i / d x*_i resp. d var_i / d x*_i; the prior arrays hold the k(x*, x*) part of the variance).  Mapping them
+# back through the model's warps is the pullback walk of the rrule below.  Refused by the library: products of kernels, patch and
+# stencil terms, a multi-GPU context.
+grad_arrays(sp::Spec) = [zeros(size(a)) for a in sp.keep[3]]     # one array per uploaded input of the spec
+grad_ptrs(gs) = Ptr{Float64}[pointer(g) for g in gs]
+function mean_and_var_and_gradient(fx::PostFGP)
+    cr, ss, ms = postfx_specs(fx.f, fx.x); n = length(fx); μ = zeros(n); v = zeros(n)
+    gm, gv, gp = grad_arrays(cr), grad_arrays(cr), grad_arrays(ss); pm, pv, pp = grad_ptrs(gm), grad_ptrs(gv), grad_ptrs(gp)
+    GC.@preserve cr ss ms μ v gm gv gp pm pv pp check(
+        @ccall LIB_PREDGRAD.sgp_posterior_predict_grad_x(fx.f.handle::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
+                                                         ms::Ptr{Float64}, μ::Ptr{Float64}, v::Ptr{Float64},
+                                                         pm::Ptr{Ptr{Float64}}, pv::Ptr{Ptr{Float64}},
+                                                         pp::Ptr{Ptr{Float64}})::Cint)
+    return (mean = μ, var = v .+ diag(fx.Σy), inputs_mean = gm, inputs_var = gv, inputs_var_prior = gp)
+end
+function mean_and_var_and_gradient(fx::SparsePostFGP)
+    cr, ss, ms = postfx_specs(fx.f, fx.x); n = length(fx); μ = zeros(n); v = zeros(n)
+    gm, gv, gp = grad_arrays(cr), grad_arrays(cr), grad_arrays(ss); pm, pv, pp = grad_ptrs(gm), grad_ptrs(gv), grad_ptrs(gp)
+    GC.@preserve cr ss ms μ v gm gv gp pm pv pp check(
+        @ccall LIB_PREDGRAD.sgp_sparse_posterior_predict_grad_x(handle!(fx.f)::Ptr{Cvoid}, cr.c::Ref{CSpec}, ss.c::Ref{CSpec},
+                                                                ms::Ptr{Float64}, μ::Ptr{Float64}, v::Ptr{Float64},
+                                                                pm::Ptr{Ptr{Float64}}, pv::Ptr{Ptr{Float64}},
+                                                                pp::Ptr{Ptr{Float64}})::Cint)
+    return (mean = μ, var = v .+ diag(fx.Σy), inputs_mean = gm, inputs_var = gv, inputs_var_prior = gp)
+end
 
 # ---- ChainRulesCore.rrule for logpdf(fx, y): what `Zygote.gradient(θ -> logpdf(build_gp(θ)(x, σ²), y), θ)`
 # needs (reference contract: test/gaussian_process_probabilistic_programme.jl:99-104 "does not error";

@@ -20,7 +20,7 @@ from .gp import (GP, GPC, AtomicGP, DerivedGP, Periodic, Select, Shift, Stretch,
                  periodic, quadrature_convolve, select, shift, stencil, stretch)
 from .gppp import GPPP, extract_components, gppp, gppp_sum_model  # noqa: F401
 from .finite_gp import (VFE, ApproxPosteriorGP, FiniteGP, PosteriorGP, SparseFiniteGP,  # noqa: F401
-                        cov, elbo, elbo_and_gradient, elbo_and_gradient_param, elbo_and_gradient_conv, elbo_and_gradient_stencil, logpdf, logpdf_and_gradient, logpdf_and_gradient_param, logpdf_and_gradient_conv, logpdf_and_gradient_stencil, logpdf_and_gradient_batch, logpdf_and_gradient_pool, logpdf_batch, logpdf_pool, logpdf_f32, marginals, mean, mean_and_cov, mean_and_var,
+                        cov, elbo, elbo_and_gradient, elbo_and_gradient_param, elbo_and_gradient_conv, elbo_and_gradient_stencil, logpdf, logpdf_and_gradient, logpdf_and_gradient_param, logpdf_and_gradient_conv, logpdf_and_gradient_stencil, logpdf_and_gradient_batch, logpdf_and_gradient_pool, logpdf_batch, logpdf_pool, logpdf_f32, marginals, mean, mean_and_cov, mean_and_var, mean_and_var_and_gradient,
                         posterior, posterior_mean_and_var_f32, prior_cov, prior_mean, prior_var, rand, sparse_cov, update_posterior, var)
 from .flatten import build_spec  # noqa: F401
 from .ordering import block_atoms, fill_reducing_order, permute_blocks, suggest_order_capi  # noqa: F401

@@ -58,6 +58,15 @@ int drv_sparse_posterior_rand(sgp_sparse_post* post, const sgp_cov_spec* cross, 
 int drv_sparse_posterior_logpdf(sgp_sparse_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss,
                                 const double* mean_s, int noise_kind, const double* noise, const double* Y, int64_t ldy,
                                 int64_t ncols, double* out);
+// posterior mean and variance with their gradients with respect to the test points (include/sthenomi_predgrad.h, forwarded
+// from libsthenomi_predgrad.so) -- predgrad.hip
+int drv_posterior_predict_grad_x(sgp_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss, const double* mean_s,
+                                 double* mean_out, double* var_out, double* const* grad_mean_inputs,
+                                 double* const* grad_var_inputs, double* const* grad_var_prior_inputs);
+int drv_sparse_posterior_predict_grad_x(sgp_sparse_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss,
+                                        const double* mean_s, double* mean_out, double* var_out,
+                                        double* const* grad_mean_inputs, double* const* grad_var_inputs,
+                                        double* const* grad_var_prior_inputs);
 // include/sthenomi_kprod.h: sgp_logpdf_grad_param, forwarded from libsthenomi_kprod.so; takes the context itself
 int drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
                           const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,

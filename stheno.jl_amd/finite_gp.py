@@ -195,6 +195,92 @@ def mean_and_var(fx):
     return m, (v.astype(np.float32) if _eltype(fx.x) == np.float32 else v)
 
 
+def _mean_varies(f, x):
+    """whether mean(f, .) is a function of the point somewhere under f (the walk of gp.mean_vector): a callable mean, a
+    callable offset, or a callable scale in front of anything -- a constant per block is not"""
+    from .gp import AtomicGP, GP, _is_real
+    from .gppp import extract_components
+    from .inputs import blocks, is_pair_vector, regroup_pairs
+    if isinstance(f, GPPP):
+        node, v = extract_components(f, x)
+        return _mean_varies(node, v)
+    if is_pair_vector(x):
+        x = regroup_pairs(x)
+    if isinstance(f, AtomicGP):
+        if isinstance(f.gp, GP):
+            return not (f.gp.mean_spec is None or _is_real(f.gp.mean_spec))
+        return _mean_varies(f.gp, x)
+    op = f.args[0]
+    if op == "cross":
+        return any(_mean_varies(g, b) for g, b in zip(f.args[1], blocks(x)))
+    if op == "+":
+        return _mean_varies(f.args[1], x) or _mean_varies(f.args[2], x)
+    if op in ("+known", "*"):
+        return not _is_real(f.args[1]) or _mean_varies(f.args[2], x)
+    if op == "o":
+        return _mean_varies(f.args[1], x)      # (a warp of the points leaves a constant a constant)
+    if op in ("conv", "stencil"):
+        return _mean_varies(f.args[1], x)
+    raise ValueError(op)
+
+
+def mean_and_var_and_gradient(fx):
+    """mean_and_var(fx) for fx = post(x*[, noise]) of an exact or VFE posterior together with the gradients of every
+    mean_i and var_i with respect to its own test point x*_i (include/sthenomi_predgrad.h): one call against the kept
+    factor, K(x*, x) assembled once, nothing factored -- what maximising an acquisition function over x* needs.
+
+    Returns a dict: `mean`, `var` (the noise added to var only; equal to mean_and_var(fx)); `d_mean`, `d_var`: one (D, n)
+    array per block of fx.x -- column i is d mean_i / d x*_i (d var_i / d x*_i), the spec-input gradients mapped back
+    through the model's Stretch / Select / Periodic / Shift warps and the kernels' input scales by
+    flatten.chain_input_gradients (blocks sharing one input object: its convention); `inputs_mean`, `inputs_var`,
+    `inputs_var_prior`: the raw per-spec-input arrays of the library; `_cross`, `_prior`: the two specs they belong to.
+
+    Not covered (NotImplementedError): a test-side term with a function-valued scale, a test-side prior mean that is a
+    function of the point, products of kernels / patch / stencil terms, a multi-GPU context, posteriors that answer
+    through explicit covariances.  A Float32 model is answered from the fp64 factor, as cov is."""
+    if isinstance(fx, SparseFiniteGP):
+        raise NotImplementedError("mean_and_var_and_gradient takes post(x*) of a posterior, not a SparseFiniteGP")
+    f = fx.f
+    if isinstance(f, ExplicitPosteriorGP):
+        raise NotImplementedError("mean_and_var_and_gradient: an ExplicitPosteriorGP answers through explicit covariances, "
+                                  "which carry no test points to differentiate")
+    if not isinstance(f, (PosteriorGP, ApproxPosteriorGP)):
+        raise NotImplementedError("mean_and_var_and_gradient takes post(x*) of an exact or VFE posterior")
+    ctx = _ctx()
+    if getattr(ctx, "is_multi", False):
+        raise NotImplementedError("mean_and_var_and_gradient is not supported on a multi-GPU context (the factor is sharded)")
+    cross, _, _ = build_spec(f.prior, fx.x, f.prior, f._train_inputs()[0])
+    pss = _prior_spec(f.prior, fx.x)
+    _refuse_patch_gradient(cross, pss)
+    _refuse_product_gradient("mean_and_var_and_gradient", cross, pss)
+    if (any(rs is not None for rs in cross.term_row_scale) or any(rs is not None for rs in pss.term_row_scale)
+            or any(cs is not None for cs in pss.term_col_scale)):
+        raise NotImplementedError("mean_and_var_and_gradient: a test-side term with a function-valued scale is not supported "
+                                  "(the library holds row scales fixed)")
+    if _mean_varies(f.prior, fx.x):
+        raise NotImplementedError("mean_and_var_and_gradient: a test-side prior mean that is a function of the point is not "
+                                  "supported (zero and constant means are)")
+    ns = cross.N
+    ms = _f64(mean_vector(f.prior, fx.x))
+    mo, vo = np.zeros(ns), np.zeros(ns)
+    gm = [np.zeros(np.asarray(a).shape, order="F") for a in cross.inputs]
+    gv = [np.zeros(np.asarray(a).shape, order="F") for a in cross.inputs]
+    gp = [np.zeros(np.asarray(a).shape, order="F") for a in pss.inputs]
+    stem = "sgp_posterior" if isinstance(f, PosteriorGP) else "sgp_sparse_posterior"
+    h = f._ensure()
+    rc = getattr(ctx.predgrad, stem + "_predict_grad_x")(h, cross.ref(), pss.ref(), _lib.dptr(ms), _lib.dptr(mo), _lib.dptr(vo),
+                                                        _dptrs(gm), _dptrs(gv), _dptrs(gp))
+    _lib.check(rc, stem + "_predict_grad_x")
+    d_mean = chain_input_gradients(cross, gm)[0]
+    d_var = [a + b for a, b in zip(chain_input_gradients(cross, gv)[0], chain_input_gradients(pss, gp)[0])]
+    m, v = _model_type((mo, vo), fx.x, *f._train_inputs())
+    v = v + _noise_diag(fx.noise, len(fx))
+    if _eltype(fx.x) == np.float32:
+        m, v = m.astype(np.float32), v.astype(np.float32)
+    return {"mean": m, "var": v, "d_mean": d_mean, "d_var": d_var, "inputs_mean": gm, "inputs_var": gv,
+            "inputs_var_prior": gp, "_cross": cross, "_prior": pss}
+
+
 class Normal:
     def __init__(self, mu, sigma):
         self.mu, self.sigma = mu, sigma

@@ -20,6 +20,7 @@ POOL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_pool.so")
 EXTEND_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend.so")
 EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so")
 POSTFX_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_postfx.so")
+PREDGRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_predgrad.so")
 VFE_UPDATE_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_vfe_update.so")
 CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
 CONV_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv_grad.so")
@@ -231,6 +232,17 @@ _SIGS_POSTFX = {
     "sgp_sparse_posterior_logpdf": _POSTFX_LOGPDF,
 }
 
+# include/sthenomi_predgrad.h: posterior mean and variance with their gradients with respect to the test points, exported by
+# libsthenomi_predgrad.so (it links against the product library and works on its posteriors) -- mean_and_var_and_gradient
+# reaches it through predgrad_lib() / Context.predgrad
+PREDGRAD_COL_CHUNK = 512                           # SGP_PREDGRAD_COL_CHUNK
+_PREDGRAD = (C.c_int, [_P, C.POINTER(sgp_cov_spec), C.POINTER(sgp_cov_spec), _D, _D, _D, C.POINTER(_D), C.POINTER(_D),
+                       C.POINTER(_D)])
+_SIGS_PREDGRAD = {
+    "sgp_posterior_predict_grad_x": _PREDGRAD,
+    "sgp_sparse_posterior_predict_grad_x": _PREDGRAD,
+}
+
 # include/sthenomi_vfe_update.h: new data into a kept sparse (VFE) posterior, exported by libsthenomi_vfe_update.so (it links
 # against the product library and works on its posteriors) -- update_posterior reaches it through vfe_update_lib() / Context.vfe_update
 _SIGS_VFE_UPDATE = {
@@ -367,6 +379,11 @@ def extend_symbols():
 def postfx_symbols():
     """Names include/sthenomi_postfx.h declares: the entry points of libsthenomi_postfx.so."""
     return sorted(_SIGS_POSTFX)
+
+
+def predgrad_symbols():
+    """Names include/sthenomi_predgrad.h declares: the entry points of libsthenomi_predgrad.so."""
+    return sorted(_SIGS_PREDGRAD)
 
 
 def vfe_update_symbols():
@@ -519,6 +536,27 @@ def postfx_lib():
             fn.restype = res
             fn.argtypes = args
         _postfx = lib
+        return lib
+
+
+_predgrad = None
+
+
+def predgrad_lib():
+    """dlopen libsthenomi_predgrad.so (include/sthenomi_predgrad.h) after the product library it links against."""
+    global _predgrad
+    load()
+    with _lib_lock:
+        if _predgrad is not None:
+            return _predgrad
+        if not os.path.exists(PREDGRAD_LIB_PATH):
+            raise SthenoMIError(f"{PREDGRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(PREDGRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, (res, args) in _SIGS_PREDGRAD.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _predgrad = lib
         return lib
 
 
@@ -804,6 +842,11 @@ class Context:
     def postfx(self):
         """libsthenomi_postfx.so (sthenomi_postfx.h): `ctx.postfx.sgp_posterior_logpdf(post_handle, ...)`"""
         return postfx_lib()
+
+    @property
+    def predgrad(self):
+        """libsthenomi_predgrad.so (sthenomi_predgrad.h): `ctx.predgrad.sgp_posterior_predict_grad_x(post_handle, ...)`"""
+        return predgrad_lib()
 
     @property
     def vfe_update(self):
