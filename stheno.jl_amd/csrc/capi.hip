@@ -1921,17 +1921,18 @@ struct StencilWo {
 // sum_ij G_ij dC_ij / d theta per flattened term of every block pair of `ds` (grad.hip):
 // G = (alpha alpha' - Kinv) / 2 when alpha != nullptr, else G = the matrix at `Gm` itself.
 // Product chains (ds->n_kprod; kprod.hip) are contracted one chain per launch, only where the caller says it carries them
-// (kprod_ok: sgp_logpdf_grad / sgp_logpdf_grad_param); dgp (optional): d / d param per term, which for the plain terms is
-// non-zero for SGP_CONST alone -- those run through the chain kernel once more, as chains of length one, for that entry.
-// Patch terms (ds->n_patch; conv.hip) are contracted one term per launch, only where the caller carries them (patch_ok: the
-// entry points of include/sthenomi_conv_grad.h), and stencil terms (ds->n_stencil; stencil.hip) likewise (stencil_ok: the entry
-// points of include/sthenomi_stencil_grad.h): they occupy [ts, tk) of their pair, behind the patch terms [tp, ts).
-static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr,
-                         long n_tc, DevBuf& dpart, double* dgc, double* dgs, hipStream_t s, bool kprod_ok = false,
-                         double* dgp = nullptr, bool patch_ok = false, bool stencil_ok = false) {
-  CHECK_ARG(stencil_ok || !ds->n_stencil, "gradient contraction: stencil terms are not supported");
-  CHECK_ARG(patch_ok || !ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
-  CHECK_ARG(kprod_ok || !ds->n_kprod, "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
+// (leave.kprod: sgp_logpdf_grad / sgp_logpdf_grad_param); dgp (NULL: not asked for): d / d param per term, which for the
+// plain terms is non-zero for SGP_CONST alone -- those run through the chain kernel once more, as chains of length one, for
+// that entry.
+// Patch terms (ds->n_patch; conv.hip) are contracted one term per launch, only where the caller carries them (leave.patch: the
+// entry points of include/sthenomi_conv_grad.h), and stencil terms (ds->n_stencil; stencil.hip) likewise (leave.stencil: the
+// entry points of include/sthenomi_stencil_grad.h): they occupy [ts, tk) of their pair, behind the patch terms [tp, ts).
+static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr, long n_tc,
+                         DevBuf& dpart, double* dgc, double* dgs, hipStream_t s, const GradLeave& leave, double* dgp) {
+  CHECK_ARG(leave.stencil || !ds->n_stencil, "gradient contraction: stencil terms are not supported");
+  CHECK_ARG(leave.patch || !ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
+  CHECK_ARG(leave.kprod || !ds->n_kprod,
+            "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
   long need = std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16);
   for (int p = 0; ds->n_patch && p < ds->nrb * ds->ncb; ++p)
     for (int t = ds->term_ptr[p] + ds->pair_nplain[p]; t < ds->term_ptr[p] + ds->pair_nplain[p] + ds->pair_npatch[p]; ++t)
@@ -1982,71 +1983,77 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
   return 0;
 }
 
+// The refusals the three gradient families share: a leave on a multi-GPU context, and stencil / patch terms without the leave.
+// stem: the family's name ("sgp_logpdf_grad", ...), which the texts are built on; b: the ELBO's second spec
+static int check_grad_leave(const sgp_ctx* ctx, const std::string& stem, const GradLeave& leave, const sgp_cov_spec* a,
+                            const sgp_cov_spec* b = nullptr) {
+  CHECK_ARG(!(leave.stencil && ctx->multi), stem + "_stencil: not supported on a multi-GPU context");
+  CHECK_ARG(!(leave.patch && ctx->multi), stem + "_conv: not supported on a multi-GPU context");
+  CHECK_ARG(leave.stencil || (!spec_has_stencil(ctx, a) && !spec_has_stencil(ctx, b)),
+            stem + (leave.patch ? "_conv" : "") + ": gradients through stencil terms are not supported");
+  CHECK_ARG(leave.patch || (!spec_has_patch(a) && !spec_has_patch(b)),
+            stem + ": gradients through patch (convolutional) terms are not supported");
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------
 // logpdf + reverse-mode gradient
 // ---------------------------------------------------------------------------------------
 // (every consumer of C^-1 -- the term contractions, the input-point and row-scale sums, the noise gradient -- walks the block
 // pairs WITH terms or the diagonal: none needs a tile outside K's own tile pattern)
-static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
-                            const double* noise, const double* y, double* logpdf_out, double* grad_y,
-                            double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
-                            double* const* grad_inputs, double* const* grad_rowscale = nullptr,
-                            double* grad_param = nullptr, bool with_param = false, bool patch_ok = false,
-                            bool stencil_ok = false, StencilWo* wo = nullptr) {
-  // (patch_ok: sgp_logpdf_grad_conv, include/sthenomi_conv_grad.h -- patch terms are contracted, conv.hip;
-  // stencil_ok: sgp_logpdf_grad_stencil, include/sthenomi_stencil_grad.h -- stencil terms too, stencil.hip; it sets patch_ok)
-  CHECK_ARG(ctx && spec && noise && y && logpdf_out, "sgp_logpdf_grad: NULL argument");
-  CHECK_ARG(spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
-  CHECK_ARG(noise_kind >= SGP_NOISE_SCALAR && noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
-  CHECK_ARG(!(stencil_ok && ctx->multi), "sgp_logpdf_grad_stencil: not supported on a multi-GPU context");
-  CHECK_ARG(!(patch_ok && ctx->multi), "sgp_logpdf_grad_conv: not supported on a multi-GPU context");
-  CHECK_ARG(stencil_ok || !spec_has_stencil(ctx, spec),
-            patch_ok ? "sgp_logpdf_grad_conv: gradients through stencil terms are not supported"
-                     : "sgp_logpdf_grad: gradients through stencil terms are not supported");
-  CHECK_ARG(patch_ok || !spec_has_patch(spec),
-            "sgp_logpdf_grad: gradients through patch (convolutional) terms are not supported");
-  CHECK_ARG(!(grad_inputs || grad_rowscale) || with_param || stencil_ok || !spec_has_kprod(spec),
+static int logpdf_grad_core(sgp_ctx* ctx, const LogpdfGradArgs& a) {
+  // (a.leave.kprod: sgp_logpdf_grad_param / _param_xs -- here it only lets grad_inputs / grad_rowscale through product chains,
+  // the term contraction carries chains for every caller; a.leave.patch: sgp_logpdf_grad_conv, include/sthenomi_conv_grad.h --
+  // patch terms are contracted, conv.hip; a.leave.stencil: sgp_logpdf_grad_stencil, include/sthenomi_stencil_grad.h -- stencil
+  // terms too, stencil.hip; it sets a.leave.patch)
+  CHECK_ARG(ctx && a.spec && a.noise && a.y && a.logpdf_out, "sgp_logpdf_grad: NULL argument");
+  CHECK_ARG(a.spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
+  CHECK_ARG(a.noise_kind >= SGP_NOISE_SCALAR && a.noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
+  CHECK_RC(check_grad_leave(ctx, "sgp_logpdf_grad", a.leave, a.spec));
+  CHECK_ARG(!(a.grad_inputs || a.grad_rowscale) || a.leave.kprod || a.leave.stencil || !spec_has_kprod(a.spec),
             "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
             "not supported: call sgp_logpdf_grad_param_xs (include/sthenomi_kprod_grad.h)");
-  CHECK_ARG(!(with_param && ctx->multi), "sgp_logpdf_grad_param: not supported on a multi-GPU context");
+  CHECK_ARG(!(a.leave.kprod && ctx->multi), "sgp_logpdf_grad_param: not supported on a multi-GPU context");
   CtxScope scope(ctx);
   // a multi-GPU context shards the gradient -- kernel terms, noise, y, the mean and (round 6) the input points and function
   // scales, a dense Sigma_y (multi.hip)
-  REFUSE_KPROD_MULTI(ctx, spec);
+  REFUSE_KPROD_MULTI(ctx, a.spec);
   if (ctx->multi)
-    return sgp_multi_logpdf_grad(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
-                                 grad_inscale, grad_inputs, grad_rowscale);
+    return sgp_multi_logpdf_grad(ctx, a.spec, a.mean, a.noise_kind, a.noise, a.y, a.logpdf_out, a.grad_y, a.grad_mean,
+                                 a.grad_noise, a.grad_coef, a.grad_inscale, a.grad_inputs, a.grad_rowscale);
   SpecGuard g;
-  CHECK_RC(dspec_create(ctx, spec, &g.ds));
+  CHECK_RC(dspec_create(ctx, a.spec, &g.ds));
   const sgp_dspec* ds = g.ds;
   long N = ds->N;
   CHECK_ARG(N >= 1, "sgp_logpdf_grad: empty data");
-  CHECK_ARG(images_unasked(ds, grad_inputs),
+  CHECK_ARG(images_unasked(ds, a.grad_inputs),
             "sgp_logpdf_grad_stencil: an input read by a patch (convolutional) side holds images, and gradients with respect to "
             "images are not supported: its grad_inputs entry must be NULL");
-  const bool dense_noise = noise_kind == SGP_NOISE_DENSE;   // grad_noise is then N x N (ld = N): the cotangent G itself
+  const bool dense_noise = a.noise_kind == SGP_NOISE_DENSE;   // grad_noise is then N x N (ld = N): the cotangent G itself
   long n_pad = rup(N, TILE);
   long nrows = TILE + n_pad;            // the (y - m)' row (+ zero padding), then the identity rows
   long m_tot = n_pad + nrows;
   hipStream_t s = ctx->stream;
-  if (wo) CHECK_RC(wo->prepare(ds, "sgp_logpdf_grad_stencil_wo", false, s));   // (wo: include/sthenomi_stencil_wo.h)
+  StencilWo wo;   // (include/sthenomi_stencil_wo.h; a no-op throughout when neither table is asked for)
+  wo.gw = a.grad_weights, wo.go = a.grad_offsets;
+  CHECK_RC(wo.prepare(ds, "sgp_logpdf_grad_stencil_wo", false, s));
   DevBuf dA, dKinv, dmean, dy, dalpha, dpart, dgc, dgs, dgn, dgp;
   NoiseDev nd;
   CHECK_RC(dA.alloc((size_t)m_tot * n_pad));
   CHECK_RC(dKinv.alloc((size_t)n_pad * n_pad));
-  if (mean) CHECK_RC(dmean.upload(mean, N));
-  CHECK_RC(dy.upload(y, N));
-  CHECK_RC(upload_noise(nd, noise_kind, noise, N));
+  if (a.mean) CHECK_RC(dmean.upload(a.mean, N));
+  CHECK_RC(dy.upload(a.y, N));
+  CHECK_RC(upload_noise(nd, a.noise_kind, a.noise, N));
   CHECK_RC(dalpha.alloc(n_pad));
   size_t nterms_total = ds->h_terms.size();
   CHECK_RC(dgc.alloc(std::max<size_t>(1, nterms_total)));
   CHECK_RC(dgs.alloc(std::max<size_t>(1, nterms_total)));
-  CHECK_RC(dgn.alloc(dense_noise && grad_noise ? (size_t)N * N : (size_t)n_pad));
+  CHECK_RC(dgn.alloc(dense_noise && a.grad_noise ? (size_t)N * N : (size_t)n_pad));
   SGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
   SGP_HIP(hipMemsetAsync(dalpha.p, 0, sizeof(double) * n_pad, s));
   SGP_HIP(hipMemsetAsync(dgc.p, 0, sizeof(double) * std::max<size_t>(1, nterms_total), s));
   SGP_HIP(hipMemsetAsync(dgs.p, 0, sizeof(double) * std::max<size_t>(1, nterms_total), s));
-  if (grad_param) {
+  if (a.grad_param) {
     CHECK_RC(dgp.alloc(std::max<size_t>(1, nterms_total)));
     SGP_HIP(hipMemsetAsync(dgp.p, 0, sizeof(double) * std::max<size_t>(1, nterms_total), s));
   }
@@ -2057,7 +2064,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
                     nd.diag.p, s));
   if (dense_noise) CHECK_RC(launch_add_dense(dA.p, m_tot, nd.dense.p, nd.ld_dense, N, 1, s));
   CHECK_RC(launch_fill_pad(dA.p, m_tot, N, n_pad, 0, n_pad, m_tot, 0, s));
-  CHECK_RC(launch_grad_border(dA.p, m_tot, n_pad, N, dy.p, mean ? dmean.p : nullptr, nrows, s));
+  CHECK_RC(launch_grad_border(dA.p, m_tot, n_pad, N, dy.p, a.mean ? dmean.p : nullptr, nrows, s));
   // Structural zeros (round 5): the factorisation of [K ; (y - m)' ; I] skips the tile products a programme with independent
   // components makes exact zeros -- in the factor AND in inv(L)', whose tile pattern is the closure of the factor's (the
   // identity rows run through the same symbolic elimination) -- C^-1 = inv(L)' inv(L) contracts only the k tiles both
@@ -2066,7 +2073,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   SzMask sz;
   {
     int words = 0;
-    CHECK_RC(sz_pattern(ctx, ds, noise_kind, n_pad, m_tot, &words, true));
+    CHECK_RC(sz_pattern(ctx, ds, a.noise_kind, n_pad, m_tot, &words, true));
     CHECK_RC(sz_upload(ctx, ctx->h_sz, words, s, &sz));
   }
   CHECK_RC(chol_bordered(ctx, dA.p, m_tot, n_pad, m_tot, nullptr, s, n_pad + TILE, sz.d_nz ? &sz : nullptr));
@@ -2096,21 +2103,23 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
     CHECK_RC(launch_gemm_nt_uut(Rinv, m_tot, dKinv.p, n_pad, n_pad, s, usk.nz ? &usk : nullptr));
   }
   CHECK_RC(launch_mirror_lower(dKinv.p, n_pad, n_pad, s));
-  if (grad_noise && dense_noise) CHECK_RC(launch_grad_noise_dense(dKinv.p, n_pad, dalpha.p, N, dgn.p, s));
-  else if (grad_noise) CHECK_RC(launch_grad_noise(dKinv.p, n_pad, dalpha.p, N, nd.kind == SGP_NOISE_DIAG, dgn.p, s));
-  if (grad_coef || grad_inscale || grad_param)
-    CHECK_RC(contract_spec(ds, dKinv.p, n_pad, dalpha.p, n_pad / TILE, n_pad / TILE, dpart, dgc.p, dgs.p, s, true,
-                           grad_param ? dgp.p : nullptr, patch_ok, stencil_ok));
+  if (a.grad_noise && dense_noise) CHECK_RC(launch_grad_noise_dense(dKinv.p, n_pad, dalpha.p, N, dgn.p, s));
+  else if (a.grad_noise) CHECK_RC(launch_grad_noise(dKinv.p, n_pad, dalpha.p, N, nd.kind == SGP_NOISE_DIAG, dgn.p, s));
+  GradLeave carried = a.leave;
+  carried.kprod = true;   // chains are contracted for every caller of this core
+  if (a.grad_coef || a.grad_inscale || a.grad_param)
+    CHECK_RC(contract_spec(ds, dKinv.p, n_pad, dalpha.p, n_pad / TILE, n_pad / TILE, dpart, dgc.p, dgs.p, s, carried,
+                           a.grad_param ? dgp.p : nullptr));
   // gradient w.r.t. the input points: row-side contraction over every block pair; the spec is
   // symmetric (block (J, I) mirrors (I, J)) and so is G, hence the column side equals the row side of
   // the mirror block and the total is twice the row-side sum
   // The row-scale vectors of function-scaled processes (K_ij = coef rs_i k_ij cs_j) ride along: the same
   // row-side sums with k in place of its derivative; the column scale of a term is the row scale of its mirror
   // term, so "row side x 2" covers both roles as it does for the points.
-  std::vector<DevBuf> dgx(grad_inputs ? spec->n_inputs : 0);
-  std::vector<DevBuf> dgr(grad_rowscale ? nterms_total : 0);
-  if (grad_inputs || grad_rowscale) {
-    for (int k = 0; grad_inputs && k < spec->n_inputs; ++k) {
+  std::vector<DevBuf> dgx(a.grad_inputs ? a.spec->n_inputs : 0);
+  std::vector<DevBuf> dgr(a.grad_rowscale ? nterms_total : 0);
+  if (a.grad_inputs || a.grad_rowscale) {
+    for (int k = 0; a.grad_inputs && k < a.spec->n_inputs; ++k) {
       size_t cnt = (size_t)std::max<long>(1, (long)ds->in_dim[k] * ds->in_n[k]);
       CHECK_RC(dgx[k].alloc(cnt));
       SGP_HIP(hipMemsetAsync(dgx[k].p, 0, sizeof(double) * cnt, s));
@@ -2121,35 +2130,35 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
         int p = I * ds->ncb + J;
         const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
         for (int t = ds->term_ptr[p]; t < t1;) {
-          int a = ds->term_row_input[t];
+          int ri = ds->term_row_input[t];
           double* gsv = nullptr;
           const DevTerm& T = ds->h_terms[t];
           if (T.ph) {   // a patch term (sgp_logpdf_grad_stencil alone asks here): the plain side of a one-sided one, once per
                         // pair -- the mirror pair gives the other role, which makes the "x 2"
-            if (grad_inputs && !(T.hr && T.hc))
+            if (a.grad_inputs && !(T.hr && T.hc))
               CHECK_RC(launch_grad_conv_points(dKinv.p, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                                ds->col_len[J], T, ds->d_terms + t, 1.0,
-                                               dgx[T.hr ? ds->term_col_input[t] : a].p, s));
+                                               dgx[T.hr ? ds->term_col_input[t] : ri].p, s));
             ++t;
             continue;
           }
           if (T.qr || T.qc) {   // a stencil term: the row side, twice (stencil.hip); its row scale is not formed
-            if (grad_inputs)
+            if (a.grad_inputs)
               CHECK_RC(launch_grad_stencil_points(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                                  ds->col_len[J], T, 0, 2.0, dgx[a].p, s));
+                                                  ds->col_len[J], T, 0, 2.0, dgx[ri].p, s));
             ++t;
             continue;
           }
-          if (grad_rowscale && grad_rowscale[term_src_of(ds, t)] && ds->h_terms[t].rs) {
+          if (a.grad_rowscale && a.grad_rowscale[term_src_of(ds, t)] && ds->h_terms[t].rs) {
             CHECK_RC(dgr[t].alloc((size_t)ds->row_len[I]));
             SGP_HIP(hipMemsetAsync(dgr[t].p, 0, sizeof(double) * ds->row_len[I], s));
             gsv = dgr[t].p;
           }
           if (t >= tk) {   // a chain: every factor's row input and the head's row scale in one pass (kprod.hip)
             const int e = chain_end(ds, t, t1);
-            if (grad_inputs || gsv) {
+            if (a.grad_inputs || gsv) {
               double* gxf[SGP_KPROD_MAX_FACTORS];
-              for (int f = t; f < e; ++f) gxf[f - t] = grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
+              for (int f = t; f < e; ++f) gxf[f - t] = a.grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
               CHECK_RC(launch_grad_kprod_inputs(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                                 ds->col_len[J], &ds->h_terms[t], e - t, chain_dmax(ds, t, e), 0, 2.0, gxf, gsv,
                                                 s));
@@ -2157,17 +2166,17 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
             t = e;
             continue;
           }
-          if (grad_inputs || gsv)
+          if (a.grad_inputs || gsv)
             CHECK_RC(launch_grad_inputs(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                         ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
-                                        grad_inputs ? dgx[a].p : nullptr, s, gsv));
+                                        a.grad_inputs ? dgx[ri].p : nullptr, s, gsv));
           ++t;
         }
       }
     }
   }
   // the stencils' own weights and offsets: both sides of every stencil term against the same cotangent (stencil.hip)
-  if (wo) CHECK_RC(wo->contract(ds, dKinv.p, n_pad, dalpha.p, true, s));
+  CHECK_RC(wo.contract(ds, dKinv.p, n_pad, dalpha.p, true, s));
   int info = fetch_info(ctx, s);
   if (info < 0) return -3;
   if (info > 0) {
@@ -2175,113 +2184,62 @@ static int logpdf_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
               std::to_string(info));
     return info;
   }
-  if (wo) CHECK_RC(wo->fetch());
-  SGP_HIP(hipMemcpy(logpdf_out, d_out, sizeof(double), hipMemcpyDeviceToHost));
+  CHECK_RC(wo.fetch());
+  SGP_HIP(hipMemcpy(a.logpdf_out, d_out, sizeof(double), hipMemcpyDeviceToHost));
   std::vector<double> ha(N);
   SGP_HIP(hipMemcpy(ha.data(), dalpha.p, sizeof(double) * N, hipMemcpyDeviceToHost));
-  if (grad_y)
-    for (long i = 0; i < N; ++i) grad_y[i] = -ha[i];
-  if (grad_mean)
-    for (long i = 0; i < N; ++i) grad_mean[i] = ha[i];
-  if (grad_noise)
-    SGP_HIP(hipMemcpy(grad_noise, dgn.p,
+  if (a.grad_y)
+    for (long i = 0; i < N; ++i) a.grad_y[i] = -ha[i];
+  if (a.grad_mean)
+    for (long i = 0; i < N; ++i) a.grad_mean[i] = ha[i];
+  if (a.grad_noise)
+    SGP_HIP(hipMemcpy(a.grad_noise, dgn.p,
                       sizeof(double) * (dense_noise ? (size_t)N * N : (nd.kind == SGP_NOISE_DIAG ? (size_t)N : (size_t)1)),
                       hipMemcpyDeviceToHost));
   // one entry per element of spec->terms, in the CALLER's order: a spec with product chains keeps its plain terms in front of
   // them on the device (dspec_create), so its entries go back through term_src
-  CHECK_RC(fetch_terms(ds, grad_coef, dgc.p));
-  CHECK_RC(fetch_terms(ds, grad_inscale, dgs.p));
-  if (grad_param) CHECK_RC(fetch_terms(ds, grad_param, dgp.p));
-  if (grad_inputs) {
-    for (int k = 0; k < spec->n_inputs; ++k) {
-      const sgp_input& in = spec->inputs[k];
-      if (!grad_inputs[k] || in.n == 0) continue;
-      SGP_HIP(hipMemcpy(grad_inputs[k], dgx[k].p, sizeof(double) * in.dim * in.n, hipMemcpyDeviceToHost));
+  CHECK_RC(fetch_terms(ds, a.grad_coef, dgc.p));
+  CHECK_RC(fetch_terms(ds, a.grad_inscale, dgs.p));
+  if (a.grad_param) CHECK_RC(fetch_terms(ds, a.grad_param, dgp.p));
+  if (a.grad_inputs) {
+    for (int k = 0; k < a.spec->n_inputs; ++k) {
+      const sgp_input& in = a.spec->inputs[k];
+      if (!a.grad_inputs[k] || in.n == 0) continue;
+      SGP_HIP(hipMemcpy(a.grad_inputs[k], dgx[k].p, sizeof(double) * in.dim * in.n, hipMemcpyDeviceToHost));
     }
   }
-  if (grad_rowscale) {
+  if (a.grad_rowscale) {
     for (int I = 0; I < ds->nrb; ++I)
       for (int J = 0; J < ds->ncb; ++J)
         for (int t = ds->term_ptr[I * ds->ncb + J]; t < ds->term_ptr[I * ds->ncb + J + 1]; ++t)
           if (dgr[t].p && ds->row_len[I] > 0)
-            SGP_HIP(hipMemcpy(grad_rowscale[term_src_of(ds, t)], dgr[t].p, sizeof(double) * ds->row_len[I],
+            SGP_HIP(hipMemcpy(a.grad_rowscale[term_src_of(ds, t)], dgr[t].p, sizeof(double) * ds->row_len[I],
                               hipMemcpyDeviceToHost));
   }
   return 0;
+}
+
+// the front door of the family (driver.h): the C entry points here and in the libraries beside this one fill a record, call it
+int sgp::drv_logpdf_grad(sgp_ctx* ctx, const LogpdfGradArgs& a) {
+  return with_df_fallback(ctx, [&]() { return logpdf_grad_core(ctx, a); });
 }
 
 extern "C" int sgp_logpdf_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
                                   const double* noise, const double* y, double* logpdf_out, double* grad_y,
                                   double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
                                   double* const* grad_inputs, double* const* grad_rowscale) {
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
-                            grad_coef, grad_inscale, grad_inputs, grad_rowscale);
-  });
+  LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                                      grad_inscale);
+  a.grad_inputs = grad_inputs, a.grad_rowscale = grad_rowscale;
+  return drv_logpdf_grad(ctx, a);
 }
 
 extern "C" int sgp_logpdf_grad(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
                                const double* noise, const double* y, double* logpdf_out, double* grad_y,
                                double* grad_mean, double* grad_noise, double* grad_coef,
                                double* grad_inscale) {
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
-                            grad_coef, grad_inscale, nullptr);
-  });
-}
-
-// include/sthenomi_kprod.h: sgp_logpdf_grad_param (its C entry point, in libsthenomi_kprod.so, forwards here)
-int sgp::drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
-                               const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
-                               double* grad_coef, double* grad_inscale, double* grad_param) {
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
-                            grad_inscale, nullptr, nullptr, grad_param, true);
-  });
-}
-
-// include/sthenomi_kprod_grad.h: sgp_logpdf_grad_param_xs -- the same with the input points and the row scales
-// include/sthenomi_conv_grad.h: sgp_logpdf_grad_conv (its C entry point, in libsthenomi_conv_grad.so, forwards here)
-int sgp::drv_logpdf_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
-                              const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
-                              double* grad_coef, double* grad_inscale) {
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
-                            grad_inscale, nullptr, nullptr, nullptr, false, true);
-  });
-}
-
-// include/sthenomi_stencil_grad.h: sgp_logpdf_grad_stencil (its C entry point, in libsthenomi_stencil_grad.so, forwards here)
-int sgp::drv_logpdf_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
-                                 const double* noise, const double* y, double* logpdf_out, double* grad_y, double* grad_mean,
-                                 double* grad_noise, double* grad_coef, double* grad_inscale, double* const* grad_inputs) {
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
-                            grad_inscale, grad_inputs, nullptr, nullptr, false, true, true);
-  });
-}
-
-// include/sthenomi_stencil_wo.h: sgp_logpdf_grad_stencil_wo (its C entry point, in libsthenomi_stencil_wo.so, forwards here)
-int sgp::drv_logpdf_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
-                                    const double* noise, const double* y, double* logpdf_out, double* grad_y,
-                                    double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
-                                    double* const* grad_inputs, double* const* grad_weights, double* const* grad_offsets) {
-  return with_df_fallback(ctx, [&]() {
-    StencilWo wo;
-    wo.gw = grad_weights, wo.go = grad_offsets;
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
-                            grad_inscale, grad_inputs, nullptr, nullptr, false, true, true, &wo);
-  });
-}
-
-int sgp::drv_logpdf_grad_param_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
-                                  const double* noise, const double* y, double* logpdf_out, double* grad_y, double* grad_mean,
-                                  double* grad_noise, double* grad_coef, double* grad_inscale, double* grad_param,
-                                  double* const* grad_inputs, double* const* grad_rowscale) {
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
-                            grad_inscale, grad_inputs, grad_rowscale, grad_param, true);
-  });
+  return drv_logpdf_grad(ctx, logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
+                                               grad_coef, grad_inscale));
 }
 
 extern "C" int sgp_logpdf_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
@@ -2289,10 +2247,10 @@ extern "C" int sgp_logpdf_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const d
                                  double* grad_mean, double* grad_noise, double* grad_coef,
                                  double* grad_inscale, double* const* grad_inputs) {
   CHECK_ARG(grad_inputs != nullptr, "sgp_logpdf_grad_x: grad_inputs is NULL");
-  return with_df_fallback(ctx, [&]() {
-    return logpdf_grad_core(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
-                            grad_coef, grad_inscale, grad_inputs);
-  });
+  LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                                      grad_inscale);
+  a.grad_inputs = grad_inputs;
+  return drv_logpdf_grad(ctx, a);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2536,7 +2494,7 @@ int pooled_chunk(sgp_ctx* ctx, PoolCall& call, const int* ids, int nb, std::vect
     if (PoolCall::at(call.grad_noise, gb))
       CHECK_RC(launch_grad_noise(M.Kinv.p, M.n_pad, alpha, M.N, M.nd.kind == SGP_NOISE_DIAG, gn, s));
     if (PoolCall::at(call.grad_coef, gb) || PoolCall::at(call.grad_inscale, gb))
-      CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, M.n_pad, alpha, M.T_c, M.T_c, M.part, gc, gs, s));
+      CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, M.n_pad, alpha, M.T_c, M.T_c, M.part, gc, gs, s, GradLeave(), nullptr));
   }
   std::vector<double> h_res((size_t)res_len);
   std::vector<int> h_info((size_t)nb);
@@ -3767,33 +3725,23 @@ extern "C" int sgp_elbo(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec
 //   G_xz = Lambda (R Z J' + delta (J u)')                      -> contraction over the xz spec
 //   G_zz = -1/2 J (B + B^-1 - 2 I + u u') J'                   -> contraction over the zz spec
 // ---------------------------------------------------------------------------------------
-static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz, const double* var_x,
-                          const double* mean_x, int noise_kind, const double* noise_x, int z_noise_kind,
-                          const double* z_noise, const double* y, double* elbo_out, double* grad_y,
-                          double* grad_mean, double* grad_noise, double* grad_var_x, double* grad_z_noise,
-                          double* grad_coef_zz, double* grad_inscale_zz, double* grad_coef_xz,
-                          double* grad_inscale_xz, double* const* grad_inputs_zz, double* const* grad_inputs_xz,
-                          double* const* grad_rowscale_zz = nullptr, double* const* grad_rowscale_xz = nullptr,
-                          double* const* grad_colscale_xz = nullptr, const sgp::ElboGradShard* shard = nullptr,
-                          double* grad_param_zz = nullptr, double* grad_param_xz = nullptr, bool kprod_ok = false,
-                          bool patch_ok = false, bool stencil_ok = false, StencilWo* wo_zz = nullptr,
-                          StencilWo* wo_xz = nullptr) {
+static int elbo_grad_core(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shard) {
   // shard (round 6, multi.hip: sgp_multi_elbo_grad): this call sees ONE rank's slice of the data points (xz, var_x, mean_x, a
   // diagonal noise_x, y and the per-point results are the slice's).  The sums over data points -- A A', A delta, the four
   // scalar sums -- are added up over the ranks by shard->reduce (every rank gets the total), the M x M stage runs replicated
   // on identical numbers, the data-point stage on the slice; the zz-side results are the primary rank's business only.
-  CHECK_ARG(ctx && zz && xz && var_x && noise_x && z_noise && y && elbo_out, "sgp_elbo_grad: NULL argument");
-  CHECK_ARG(zz->symmetric, "sgp_elbo_grad: zz spec must be symmetric");
-  CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG,
+  CHECK_ARG(ctx && a.zz && a.xz && a.var_x && a.noise_x && a.z_noise && a.y && a.elbo_out, "sgp_elbo_grad: NULL argument");
+  CHECK_ARG(a.zz->symmetric, "sgp_elbo_grad: zz spec must be symmetric");
+  CHECK_ARG(a.noise_kind == SGP_NOISE_SCALAR || a.noise_kind == SGP_NOISE_DIAG,
             "sgp_elbo_grad: Sigma_y must be isotropic or diagonal (as in AbstractGPs.elbo)");
-  CHECK_ARG(z_noise_kind >= SGP_NOISE_SCALAR && z_noise_kind <= SGP_NOISE_DENSE, "sgp_elbo_grad: bad Sigma_z kind");
+  CHECK_ARG(a.z_noise_kind >= SGP_NOISE_SCALAR && a.z_noise_kind <= SGP_NOISE_DENSE, "sgp_elbo_grad: bad Sigma_z kind");
   CtxScope scope(ctx);
   SpecGuard gz, gx;
-  CHECK_RC(dspec_create(ctx, zz, &gz.ds));
-  CHECK_RC(dspec_create(ctx, xz, &gx.ds));
+  CHECK_RC(dspec_create(ctx, a.zz, &gz.ds));
+  CHECK_RC(dspec_create(ctx, a.xz, &gx.ds));
   const long M = gz.ds->N, N = gx.ds->N;
   // a patched side reads images, and gradients with respect to those are not formed (include/sthenomi_conv_grad.h)
-  CHECK_ARG(images_unasked(gz.ds, grad_inputs_zz) && images_unasked(gx.ds, grad_inputs_xz),
+  CHECK_ARG(images_unasked(gz.ds, a.grad_inputs_zz) && images_unasked(gx.ds, a.grad_inputs_xz),
             "sgp_elbo_grad_conv: an input read by a patch (convolutional) side holds images, and gradients with respect to "
             "images are not supported: its grad_inputs entry must be NULL");
   CHECK_ARG(gx.ds->M == M, "sgp_elbo_grad: xz spec columns != number of inducing points");
@@ -3802,9 +3750,12 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   const long ld = m_pad + n_rows + m_pad;   // [Kzz + Sigma_z ; K(x,z) Lambda ; I]
   const long ldg = m_pad + TILE + m_pad;    // [A A' + I ; (A delta)' ; I]
   hipStream_t s = ctx->stream;
-  // (wo_zz / wo_xz: include/sthenomi_stencil_wo.h, never on a sharded call)
-  if (wo_zz) CHECK_RC(wo_zz->prepare(gz.ds, "sgp_elbo_grad_stencil_wo", false, s));
-  if (wo_xz) CHECK_RC(wo_xz->prepare(gx.ds, "sgp_elbo_grad_stencil_wo", false, s));
+  // (include/sthenomi_stencil_wo.h; no-ops throughout when no table is asked for, as on every sharded call -- the entry
+  // refuses the stencil leave on a multi-GPU context)
+  StencilWo wo_zz, wo_xz;
+  wo_zz.gw = a.grad_weights_zz, wo_zz.go = a.grad_offsets_zz, wo_xz.gw = a.grad_weights_xz, wo_xz.go = a.grad_offsets_xz;
+  CHECK_RC(wo_zz.prepare(gz.ds, "sgp_elbo_grad_stencil_wo", false, s));
+  CHECK_RC(wo_xz.prepare(gx.ds, "sgp_elbo_grad_stencil_wo", false, s));
   DevBuf dA, dG, dB, dBinv, dZ, dS, dRZ, dT1, dGzz, dy, dmean, dvar, ddelta, drsig, dots, sq, du, dut, dgy, dgsy,
       dpart, dgcz, dgsz, dgcx, dgsx, dgpz, dgpx;
   NoiseDev ndx, ndz;
@@ -3817,11 +3768,11 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   CHECK_RC(dT1.alloc((size_t)m_pad * m_pad));
   CHECK_RC(dGzz.alloc((size_t)m_pad * m_pad));
   CHECK_RC(dRZ.alloc((size_t)n_rows * m_pad));
-  CHECK_RC(dy.upload(y, N));
-  if (mean_x) CHECK_RC(dmean.upload(mean_x, N));
-  CHECK_RC(dvar.upload(var_x, N));
-  CHECK_RC(upload_noise(ndx, noise_kind, noise_x, N));
-  CHECK_RC(upload_noise(ndz, z_noise_kind, z_noise, M));
+  CHECK_RC(dy.upload(a.y, N));
+  if (a.mean_x) CHECK_RC(dmean.upload(a.mean_x, N));
+  CHECK_RC(dvar.upload(a.var_x, N));
+  CHECK_RC(upload_noise(ndx, a.noise_kind, a.noise_x, N));
+  CHECK_RC(upload_noise(ndz, a.z_noise_kind, a.z_noise, M));
   CHECK_RC(ddelta.alloc(n_rows));
   CHECK_RC(drsig.alloc(n_rows));
   CHECK_RC(dots.alloc(m_pad));
@@ -3839,11 +3790,11 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   SGP_HIP(hipMemsetAsync(dgsz.p, 0, sizeof(double) * ntz, s));
   SGP_HIP(hipMemsetAsync(dgcx.p, 0, sizeof(double) * ntx, s));
   SGP_HIP(hipMemsetAsync(dgsx.p, 0, sizeof(double) * ntx, s));
-  if (grad_param_zz) {
+  if (a.grad_param_zz) {
     CHECK_RC(dgpz.alloc(ntz));
     SGP_HIP(hipMemsetAsync(dgpz.p, 0, sizeof(double) * ntz, s));
   }
-  if (grad_param_xz) {
+  if (a.grad_param_xz) {
     CHECK_RC(dgpx.alloc(ntx));
     SGP_HIP(hipMemsetAsync(dgpx.p, 0, sizeof(double) * ntx, s));
   }
@@ -3851,7 +3802,7 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   SGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
   SGP_HIP(hipMemsetAsync(ddelta.p, 0, sizeof(double) * n_rows, s));
   SGP_HIP(hipMemsetAsync(drsig.p, 0, sizeof(double) * n_rows, s));
-  CHECK_RC(launch_elbo_scalars(ctx, dy.p, mean_x ? dmean.p : nullptr, dvar.p,
+  CHECK_RC(launch_elbo_scalars(ctx, dy.p, a.mean_x ? dmean.p : nullptr, dvar.p,
                      ndx.kind, ndx.sigma2, ndx.diag.p, N, ddelta.p, drsig.p, d_o, s));
   // ---- factor 1: [Kzz + Sigma_z ; K(x,z) Lambda ; I]  ->  Lz, R = A', J = Lz^-T
   double* Rw = dA.p + m_pad;
@@ -3939,7 +3890,7 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   {
     double tmp = h[0] + h[4] + h[1] - h[5];
     double dtc = -0.5 * ((double)(shard ? shard->n_total : N) * 1.8378770664093453 + tmp);
-    elbo_out[0] = dtc - 0.5 * (h[2] - h[3]);
+    a.elbo_out[0] = dtc - 0.5 * (h[2] - h[3]);
   }
   // ---- M x M stage
   CHECK_RC(launch_gemv_rows(Je, ldg, m_pad, m_pad, dG.p + m_pad, ldg, nullptr, du.p, s, 1));   // u = Le^-T b
@@ -3961,15 +3912,15 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
     CHECK_RC(launch_gemm_nt(dT1.p, m_pad, Jm, ld, dGzz.p, m_pad, m_pad, m_pad, m_pad, -0.5, 0.0, NOMASK, 0, 0, s));
   }
   // ---- contractions against the flattened terms
-  if (grad_coef_xz || grad_inscale_xz || grad_param_xz)
-    CHECK_RC(contract_spec(gx.ds, dE.p, n_rows, nullptr, n_rows / TILE, m_pad / TILE, dpart, dgcx.p, dgsx.p, s, kprod_ok,
-                           dgpx.p, patch_ok, stencil_ok));
-  if (grad_coef_zz || grad_inscale_zz || grad_param_zz)
-    CHECK_RC(contract_spec(gz.ds, dGzz.p, m_pad, nullptr, m_pad / TILE, m_pad / TILE, dpart, dgcz.p, dgsz.p, s, kprod_ok,
-                           dgpz.p, patch_ok, stencil_ok));
+  if (a.grad_coef_xz || a.grad_inscale_xz || a.grad_param_xz)
+    CHECK_RC(contract_spec(gx.ds, dE.p, n_rows, nullptr, n_rows / TILE, m_pad / TILE, dpart, dgcx.p, dgsx.p, s, a.leave,
+                           dgpx.p));
+  if (a.grad_coef_zz || a.grad_inscale_zz || a.grad_param_zz)
+    CHECK_RC(contract_spec(gz.ds, dGzz.p, m_pad, nullptr, m_pad / TILE, m_pad / TILE, dpart, dgcz.p, dgsz.p, s, a.leave,
+                           dgpz.p));
   // ---- input points: zz is symmetric (twice the row side, as in logpdf_grad_core); xz is
   // rectangular: row side for the x inputs, and the transposed contraction for the z inputs
-  std::vector<DevBuf> dgz(grad_inputs_zz ? zz->n_inputs : 0), dgxz(grad_inputs_xz ? xz->n_inputs : 0);
+  std::vector<DevBuf> dgz(a.grad_inputs_zz ? a.zz->n_inputs : 0), dgxz(a.grad_inputs_xz ? a.xz->n_inputs : 0);
   auto zero_inputs = [&](std::vector<DevBuf>& v, const sgp_dspec* ds) -> int {
     for (size_t k = 0; k < v.size(); ++k) {
       size_t cnt = (size_t)std::max<long>(1, (long)ds->in_dim[k] * ds->in_n[k]);
@@ -3982,7 +3933,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
   // the row-scale sums come out of the same passes (zz symmetric: "row side x 2" covers the column role through the
   // mirror term; xz: the row side gives d / d rs (scales at x), the transposed pass d / d cs (scales at z)).
   const size_t ntz_s = gz.ds->h_terms.size(), ntx_s = gx.ds->h_terms.size();
-  std::vector<DevBuf> drz(grad_rowscale_zz ? ntz_s : 0), drx(grad_rowscale_xz ? ntx_s : 0), dcx(grad_colscale_xz ? ntx_s : 0);
+  std::vector<DevBuf> drz(a.grad_rowscale_zz ? ntz_s : 0), drx(a.grad_rowscale_xz ? ntx_s : 0),
+      dcx(a.grad_colscale_xz ? ntx_s : 0);
   auto scale_buf = [&](std::vector<DevBuf>& v, double* const* want, const sgp_dspec* ds, size_t t, const double* vec, long len,
                        double** out) -> int {
     *out = nullptr;
@@ -4000,8 +3952,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
     return launch_grad_conv_points(Gm, ldgm, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J], ds->col_len[J], T,
                                    ds->d_terms + t, 1.0, into[k].p, s);
   };
-  if (grad_inputs_zz || grad_rowscale_zz) {
-    if (grad_inputs_zz) CHECK_RC(zero_inputs(dgz, gz.ds));
+  if (a.grad_inputs_zz || a.grad_rowscale_zz) {
+    if (a.grad_inputs_zz) CHECK_RC(zero_inputs(dgz, gz.ds));
     const sgp_dspec* ds = gz.ds;
     for (int I = 0; I < ds->nrb; ++I)
       for (int J = 0; J < ds->ncb; ++J) {
@@ -4016,18 +3968,18 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
             continue;
           }
           if (ds->h_terms[t].qr || ds->h_terms[t].qc) {   // a stencil term: the row side, twice (stencil.hip)
-            if (grad_inputs_zz)
+            if (a.grad_inputs_zz)
               CHECK_RC(launch_grad_stencil_points(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                                   ds->col_len[J], ds->h_terms[t], 0, 2.0, dgz[ds->term_row_input[t]].p, s));
             ++t;
             continue;
           }
-          CHECK_RC(scale_buf(drz, grad_rowscale_zz, ds, t, ds->h_terms[t].rs, ds->row_len[I], &gsv));
+          CHECK_RC(scale_buf(drz, a.grad_rowscale_zz, ds, t, ds->h_terms[t].rs, ds->row_len[I], &gsv));
           if (t >= tk) {   // a chain: one pass for every factor's row input and the head's row scale (kprod.hip)
             const int e = chain_end(ds, t, t1);
-            if (grad_inputs_zz || gsv) {
+            if (a.grad_inputs_zz || gsv) {
               double* gxf[SGP_KPROD_MAX_FACTORS];
-              for (int f = t; f < e; ++f) gxf[f - t] = grad_inputs_zz ? dgz[ds->term_row_input[f]].p : nullptr;
+              for (int f = t; f < e; ++f) gxf[f - t] = a.grad_inputs_zz ? dgz[ds->term_row_input[f]].p : nullptr;
               CHECK_RC(launch_grad_kprod_inputs(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                                 ds->col_len[J], &ds->h_terms[t], e - t, chain_dmax(ds, t, e), 0, 2.0, gxf, gsv,
                                                 s));
@@ -4035,16 +3987,16 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
             t = e;
             continue;
           }
-          if (grad_inputs_zz || gsv)
+          if (a.grad_inputs_zz || gsv)
             CHECK_RC(launch_grad_inputs(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                         ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
-                                        grad_inputs_zz ? dgz[ds->term_row_input[t]].p : nullptr, s, gsv));
+                                        a.grad_inputs_zz ? dgz[ds->term_row_input[t]].p : nullptr, s, gsv));
           ++t;
         }
       }
   }
-  if (grad_inputs_xz || grad_rowscale_xz || grad_colscale_xz) {
-    if (grad_inputs_xz) CHECK_RC(zero_inputs(dgxz, gx.ds));
+  if (a.grad_inputs_xz || a.grad_rowscale_xz || a.grad_colscale_xz) {
+    if (a.grad_inputs_xz) CHECK_RC(zero_inputs(dgxz, gx.ds));
     const sgp_dspec* ds = gx.ds;
     for (int I = 0; I < ds->nrb; ++I)
       for (int J = 0; J < ds->ncb; ++J) {
@@ -4060,7 +4012,7 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
           }
           if (T.qr || T.qc) {   // a stencil term: the row side for x, the transposed contraction (sides and stencils
                                 // swapped) for z (stencil.hip)
-            if (grad_inputs_xz) {
+            if (a.grad_inputs_xz) {
               CHECK_RC(launch_grad_stencil_points(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                                   ds->col_len[J], T, 0, 1.0, dgxz[ds->term_row_input[t]].p, s));
               CHECK_RC(launch_grad_stencil_points(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
@@ -4068,30 +4020,30 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
             }
             continue;
           }
-          CHECK_RC(scale_buf(drx, grad_rowscale_xz, ds, t, T.rs, ds->row_len[I], &gsr));
-          CHECK_RC(scale_buf(dcx, grad_colscale_xz, ds, t, T.cs, ds->col_len[J], &gsc));
+          CHECK_RC(scale_buf(drx, a.grad_rowscale_xz, ds, t, T.rs, ds->row_len[I], &gsr));
+          CHECK_RC(scale_buf(dcx, a.grad_colscale_xz, ds, t, T.cs, ds->col_len[J], &gsc));
           if (t >= tk) {   // a chain: the row pass for x, the transposed pass for z, every factor in each (kprod.hip)
             const int e = chain_end(ds, t, t1), cdm = chain_dmax(ds, t, e);
             double *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
             for (int f = t; f < e; ++f) {
-              gxr[f - t] = grad_inputs_xz ? dgxz[ds->term_row_input[f]].p : nullptr;
-              gxc[f - t] = grad_inputs_xz ? dgxz[ds->term_col_input[f]].p : nullptr;
+              gxr[f - t] = a.grad_inputs_xz ? dgxz[ds->term_row_input[f]].p : nullptr;
+              gxc[f - t] = a.grad_inputs_xz ? dgxz[ds->term_col_input[f]].p : nullptr;
             }
-            if (grad_inputs_xz || gsr)
+            if (a.grad_inputs_xz || gsr)
               CHECK_RC(launch_grad_kprod_inputs(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                                 ds->col_len[J], &ds->h_terms[t], e - t, cdm, 0, 1.0, gxr, gsr, s));
-            if (grad_inputs_xz || gsc)
+            if (a.grad_inputs_xz || gsc)
               CHECK_RC(launch_grad_kprod_inputs(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
                                                 ds->row_len[I], &ds->h_terms[t], e - t, cdm, 1, 1.0, gxc, gsc, s));
             t = e - 1;
             continue;
           }
-          if (grad_inputs_xz || gsr || gsc)
-            if (grad_inputs_xz || gsr)
+          if (a.grad_inputs_xz || gsr || gsc)
+            if (a.grad_inputs_xz || gsr)
             CHECK_RC(launch_grad_inputs(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
                                         ds->col_len[J], T, ds->pair_dmax[p], 1.0,
-                                        grad_inputs_xz ? dgxz[ds->term_row_input[t]].p : nullptr, s, gsr));
-          if (grad_inputs_xz || gsc) {
+                                        a.grad_inputs_xz ? dgxz[ds->term_row_input[t]].p : nullptr, s, gsr));
+          if (a.grad_inputs_xz || gsc) {
             DevTerm Tt = T;  // the same term seen from its column points
             Tt.xr = T.xc;
             Tt.ldr = T.ldc;
@@ -4101,69 +4053,69 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
             Tt.cs = T.rs;
             CHECK_RC(launch_grad_inputs(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
                                         ds->row_len[I], Tt, ds->pair_dmax[p], 1.0,
-                                        grad_inputs_xz ? dgxz[ds->term_col_input[t]].p : nullptr, s, gsc));
+                                        a.grad_inputs_xz ? dgxz[ds->term_col_input[t]].p : nullptr, s, gsc));
           }
         }
       }
   }
   // ---- the stencils' own weights and offsets: G_zz is symmetric, the xz cotangent is read transposed for its column side
-  if (wo_zz) CHECK_RC(wo_zz->contract(gz.ds, dGzz.p, m_pad, nullptr, true, s));
-  if (wo_xz) CHECK_RC(wo_xz->contract(gx.ds, dE.p, n_rows, nullptr, false, s));
+  CHECK_RC(wo_zz.contract(gz.ds, dGzz.p, m_pad, nullptr, true, s));
+  CHECK_RC(wo_xz.contract(gx.ds, dE.p, n_rows, nullptr, false, s));
   SGP_HIP(hipStreamSynchronize(s));
-  if (wo_zz) CHECK_RC(wo_zz->fetch());
-  if (wo_xz) CHECK_RC(wo_xz->fetch());
+  CHECK_RC(wo_zz.fetch());
+  CHECK_RC(wo_xz.fetch());
   // ---- results
   std::vector<double> hy(N), hs(N);
   SGP_HIP(hipMemcpy(hy.data(), dgy.p, sizeof(double) * N, hipMemcpyDeviceToHost));
   SGP_HIP(hipMemcpy(hs.data(), dgsy.p, sizeof(double) * N, hipMemcpyDeviceToHost));
-  if (grad_y)
-    for (long i = 0; i < N; ++i) grad_y[i] = hy[i];
-  if (grad_mean)
-    for (long i = 0; i < N; ++i) grad_mean[i] = -hy[i];
-  if (grad_noise) {
-    if (noise_kind == SGP_NOISE_DIAG) {
-      for (long i = 0; i < N; ++i) grad_noise[i] = hs[i];
+  if (a.grad_y)
+    for (long i = 0; i < N; ++i) a.grad_y[i] = hy[i];
+  if (a.grad_mean)
+    for (long i = 0; i < N; ++i) a.grad_mean[i] = -hy[i];
+  if (a.grad_noise) {
+    if (a.noise_kind == SGP_NOISE_DIAG) {
+      for (long i = 0; i < N; ++i) a.grad_noise[i] = hs[i];
     } else {
       double acc = 0.0;
       for (long i = 0; i < N; ++i) acc += hs[i];  // fixed order
-      grad_noise[0] = acc;
+      a.grad_noise[0] = acc;
     }
   }
-  if (grad_var_x) {
+  if (a.grad_var_x) {
     for (long i = 0; i < N; ++i) {
-      double s2 = noise_kind == SGP_NOISE_SCALAR ? noise_x[0] : noise_x[i];
-      grad_var_x[i] = -0.5 / s2;
+      double s2 = a.noise_kind == SGP_NOISE_SCALAR ? a.noise_x[0] : a.noise_x[i];
+      a.grad_var_x[i] = -0.5 / s2;
     }
   }
-  if (grad_z_noise && z_noise_kind == SGP_NOISE_DENSE) {
+  if (a.grad_z_noise && a.z_noise_kind == SGP_NOISE_DENSE) {
     // dense Sigma_z: the cotangent of Kzz + Sigma_z itself, M x M (ld M) -- as sgp_logpdf_grad returns G for a dense Sigma_y
-    SGP_HIP(hipMemcpy2D(grad_z_noise, sizeof(double) * M, dGzz.p, sizeof(double) * m_pad, sizeof(double) * M, (size_t)M,
+    SGP_HIP(hipMemcpy2D(a.grad_z_noise, sizeof(double) * M, dGzz.p, sizeof(double) * m_pad, sizeof(double) * M, (size_t)M,
                         hipMemcpyDeviceToHost));
-  } else if (grad_z_noise) {
+  } else if (a.grad_z_noise) {
     std::vector<double> dg(M);
     SGP_HIP(hipMemcpy2D(dg.data(), sizeof(double), dGzz.p, sizeof(double) * (m_pad + 1), sizeof(double), (size_t)M,
                         hipMemcpyDeviceToHost));
-    if (z_noise_kind == SGP_NOISE_DIAG) {
-      for (long i = 0; i < M; ++i) grad_z_noise[i] = dg[i];
+    if (a.z_noise_kind == SGP_NOISE_DIAG) {
+      for (long i = 0; i < M; ++i) a.grad_z_noise[i] = dg[i];
     } else {
       double acc = 0.0;
       for (long i = 0; i < M; ++i) acc += dg[i];
-      grad_z_noise[0] = acc;
+      a.grad_z_noise[0] = acc;
     }
   }
-  CHECK_RC(fetch_terms(gz.ds, grad_coef_zz, dgcz.p));
-  CHECK_RC(fetch_terms(gz.ds, grad_inscale_zz, dgsz.p));
-  CHECK_RC(fetch_terms(gz.ds, grad_param_zz, dgpz.p));
-  CHECK_RC(fetch_terms(gx.ds, grad_coef_xz, dgcx.p));
-  CHECK_RC(fetch_terms(gx.ds, grad_inscale_xz, dgsx.p));
-  CHECK_RC(fetch_terms(gx.ds, grad_param_xz, dgpx.p));
+  CHECK_RC(fetch_terms(gz.ds, a.grad_coef_zz, dgcz.p));
+  CHECK_RC(fetch_terms(gz.ds, a.grad_inscale_zz, dgsz.p));
+  CHECK_RC(fetch_terms(gz.ds, a.grad_param_zz, dgpz.p));
+  CHECK_RC(fetch_terms(gx.ds, a.grad_coef_xz, dgcx.p));
+  CHECK_RC(fetch_terms(gx.ds, a.grad_inscale_xz, dgsx.p));
+  CHECK_RC(fetch_terms(gx.ds, a.grad_param_xz, dgpx.p));
   for (size_t k = 0; k < dgz.size(); ++k)
-    if (grad_inputs_zz[k] && zz->inputs[k].n > 0)
-      SGP_HIP(hipMemcpy(grad_inputs_zz[k], dgz[k].p, sizeof(double) * zz->inputs[k].dim * zz->inputs[k].n,
+    if (a.grad_inputs_zz[k] && a.zz->inputs[k].n > 0)
+      SGP_HIP(hipMemcpy(a.grad_inputs_zz[k], dgz[k].p, sizeof(double) * a.zz->inputs[k].dim * a.zz->inputs[k].n,
                         hipMemcpyDeviceToHost));
   for (size_t k = 0; k < dgxz.size(); ++k)
-    if (grad_inputs_xz[k] && xz->inputs[k].n > 0)
-      SGP_HIP(hipMemcpy(grad_inputs_xz[k], dgxz[k].p, sizeof(double) * xz->inputs[k].dim * xz->inputs[k].n,
+    if (a.grad_inputs_xz[k] && a.xz->inputs[k].n > 0)
+      SGP_HIP(hipMemcpy(a.grad_inputs_xz[k], dgxz[k].p, sizeof(double) * a.xz->inputs[k].dim * a.xz->inputs[k].n,
                         hipMemcpyDeviceToHost));
   auto scale_out = [&](std::vector<DevBuf>& v, double* const* want, const sgp_dspec* ds, bool cols) -> int {
     if (!want) return 0;
@@ -4175,36 +4127,24 @@ static int elbo_grad_core(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_sp
                               hipMemcpyDeviceToHost));
     return 0;
   };
-  CHECK_RC(scale_out(drz, grad_rowscale_zz, gz.ds, false));
-  CHECK_RC(scale_out(drx, grad_rowscale_xz, gx.ds, false));
-  CHECK_RC(scale_out(dcx, grad_colscale_xz, gx.ds, true));
+  CHECK_RC(scale_out(drz, a.grad_rowscale_zz, gz.ds, false));
+  CHECK_RC(scale_out(drx, a.grad_rowscale_xz, gx.ds, false));
+  CHECK_RC(scale_out(dcx, a.grad_colscale_xz, gx.ds, true));
   return 0;
 }
 
-// the three entry points: one record of arguments; a multi-GPU context shards the data points over its ranks (round 6)
-static int elbo_grad_entry(sgp_ctx* ctx, const sgp::ElboGradArgs& a) {
+// the front door of the family (driver.h): the leave checks, then a multi-GPU context shards the data points over its ranks
+// (round 6).  The C entry points here and in the libraries beside this one fill a record and call it
+int sgp::elbo_grad_entry(sgp_ctx* ctx, const ElboGradArgs& a) {
   CHECK_ARG(ctx, "sgp_elbo_grad: NULL context");
-  CHECK_ARG(!(a.stencil_ok && ctx->multi), "sgp_elbo_grad_stencil: not supported on a multi-GPU context");
-  CHECK_ARG(!(a.patch_ok && ctx->multi), "sgp_elbo_grad_conv: not supported on a multi-GPU context");
-  CHECK_ARG(a.stencil_ok || (!spec_has_stencil(ctx, a.zz) && !spec_has_stencil(ctx, a.xz)),
-            a.patch_ok ? "sgp_elbo_grad_conv: gradients through stencil terms are not supported"
-                       : "sgp_elbo_grad: gradients through stencil terms are not supported");
-  CHECK_ARG(a.patch_ok || (!spec_has_patch(a.zz) && !spec_has_patch(a.xz)),
-            "sgp_elbo_grad: gradients through patch (convolutional) terms are not supported");
-  CHECK_ARG(a.kprod_ok || (!spec_has_kprod(a.zz) && !spec_has_kprod(a.xz)),
+  CHECK_RC(check_grad_leave(ctx, "sgp_elbo_grad", a.leave, a.zz, a.xz));
+  CHECK_ARG(a.leave.kprod || (!spec_has_kprod(a.zz) && !spec_has_kprod(a.xz)),
             "sgp_elbo_grad: gradients through product chains and the RQ / LINEAR kinds are not supported: call "
             "sgp_elbo_grad_param (include/sthenomi_kprod_grad.h)");
-  CHECK_ARG(!(a.kprod_ok && ctx->multi), "sgp_elbo_grad_param: not supported on a multi-GPU context");
+  CHECK_ARG(!(a.leave.kprod && ctx->multi), "sgp_elbo_grad_param: not supported on a multi-GPU context");
   if (ctx->multi && ctx->multi_nranks > 1) return sgp_multi_elbo_grad(ctx, a);
-  return sgp::drv_elbo_grad(ctx, a, nullptr);
+  return drv_elbo_grad(ctx, a, nullptr);
 }
-#define SGP_ELBO_GRAD_ARGS(a)                                                                                      \
-  sgp::ElboGradArgs a;                                                                                             \
-  a.zz = zz, a.xz = xz, a.var_x = var_x, a.mean_x = mean_x, a.noise_kind = noise_kind, a.noise_x = noise_x;       \
-  a.z_noise_kind = z_noise_kind, a.z_noise = z_noise, a.y = y, a.elbo_out = elbo_out, a.grad_y = grad_y;          \
-  a.grad_mean = grad_mean, a.grad_noise = grad_noise, a.grad_var_x = grad_var_x, a.grad_z_noise = grad_z_noise;   \
-  a.grad_coef_zz = grad_coef_zz, a.grad_inscale_zz = grad_inscale_zz, a.grad_coef_xz = grad_coef_xz;              \
-  a.grad_inscale_xz = grad_inscale_xz
 
 extern "C" int sgp_elbo_grad(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz, const double* var_x,
                              const double* mean_x, int noise_kind, const double* noise_x, int z_noise_kind,
@@ -4212,8 +4152,9 @@ extern "C" int sgp_elbo_grad(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov
                              double* grad_mean, double* grad_noise, double* grad_var_x, double* grad_z_noise,
                              double* grad_coef_zz, double* grad_inscale_zz, double* grad_coef_xz,
                              double* grad_inscale_xz) {
-  SGP_ELBO_GRAD_ARGS(a);
-  return elbo_grad_entry(ctx, a);
+  return elbo_grad_entry(ctx, elbo_grad_args(zz, xz, var_x, mean_x, noise_kind, noise_x, z_noise_kind, z_noise, y, elbo_out,
+                                             grad_y, grad_mean, grad_noise, grad_var_x, grad_z_noise, grad_coef_zz,
+                                             grad_inscale_zz, grad_coef_xz, grad_inscale_xz));
 }
 
 extern "C" int sgp_elbo_grad_x(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz, const double* var_x,
@@ -4224,7 +4165,9 @@ extern "C" int sgp_elbo_grad_x(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_c
                                double* grad_inscale_xz, double* const* grad_inputs_zz,
                                double* const* grad_inputs_xz) {
   CHECK_ARG(grad_inputs_zz && grad_inputs_xz, "sgp_elbo_grad_x: grad_inputs_* is NULL");
-  SGP_ELBO_GRAD_ARGS(a);
+  ElboGradArgs a = elbo_grad_args(zz, xz, var_x, mean_x, noise_kind, noise_x, z_noise_kind, z_noise, y, elbo_out, grad_y,
+                                  grad_mean, grad_noise, grad_var_x, grad_z_noise, grad_coef_zz, grad_inscale_zz, grad_coef_xz,
+                                  grad_inscale_xz);
   a.grad_inputs_zz = grad_inputs_zz, a.grad_inputs_xz = grad_inputs_xz;
   return elbo_grad_entry(ctx, a);
 }
@@ -4237,71 +4180,58 @@ extern "C" int sgp_elbo_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_
                                 double* grad_inscale_xz, double* const* grad_inputs_zz,
                                 double* const* grad_inputs_xz, double* const* grad_rowscale_zz,
                                 double* const* grad_rowscale_xz, double* const* grad_colscale_xz) {
-  SGP_ELBO_GRAD_ARGS(a);
+  ElboGradArgs a = elbo_grad_args(zz, xz, var_x, mean_x, noise_kind, noise_x, z_noise_kind, z_noise, y, elbo_out, grad_y,
+                                  grad_mean, grad_noise, grad_var_x, grad_z_noise, grad_coef_zz, grad_inscale_zz, grad_coef_xz,
+                                  grad_inscale_xz);
   a.grad_inputs_zz = grad_inputs_zz, a.grad_inputs_xz = grad_inputs_xz, a.grad_rowscale_zz = grad_rowscale_zz;
   a.grad_rowscale_xz = grad_rowscale_xz, a.grad_colscale_xz = grad_colscale_xz;
   return elbo_grad_entry(ctx, a);
 }
-#undef SGP_ELBO_GRAD_ARGS
-// include/sthenomi_kprod_grad.h: sgp_elbo_grad_param (its C entry point, in libsthenomi_kprod_grad.so, forwards here)
-int sgp::drv_elbo_grad_param(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
-// include/sthenomi_conv_grad.h: sgp_elbo_grad_conv (its C entry point, in libsthenomi_conv_grad.so, forwards here)
-int sgp::drv_elbo_grad_conv(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
-// include/sthenomi_stencil_grad.h: sgp_elbo_grad_stencil (its C entry point, in libsthenomi_stencil_grad.so, forwards here)
-int sgp::drv_elbo_grad_stencil(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
-// include/sthenomi_stencil_wo.h: sgp_elbo_grad_stencil_wo (its C entry point, in libsthenomi_stencil_wo.so, forwards here)
-int sgp::drv_elbo_grad_stencil_wo(sgp_ctx* ctx, const sgp::ElboGradArgs& a) { return elbo_grad_entry(ctx, a); }
 
 // sum_i w[i] d var_i / d theta over the diagonal of `spec` (the blocks (I, I) kernelmatrix_diag reads)
-static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
-                          double* grad_inscale, double* const* grad_inputs, double* const* grad_rowscale = nullptr,
-                          double* const* grad_colscale = nullptr, double* grad_param = nullptr, bool kprod_ok = false,
-                          bool patch_ok = false, bool stencil_ok = false, StencilWo* wo = nullptr) {
-  // (kprod_ok: sgp_kernelmatrix_diag_grad_param, include/sthenomi_kprod_grad.h -- every output may be NULL there;
-  // patch_ok: sgp_kernelmatrix_diag_grad_conv, include/sthenomi_conv_grad.h; stencil_ok: sgp_kernelmatrix_diag_grad_stencil,
-  // include/sthenomi_stencil_grad.h)
-  CHECK_ARG(ctx && spec && w && (kprod_ok || (grad_coef && grad_inscale)), "sgp_kernelmatrix_diag_grad: NULL argument");
-  CHECK_ARG(!(stencil_ok && ctx->multi), "sgp_kernelmatrix_diag_grad_stencil: not supported on a multi-GPU context");
-  CHECK_ARG(!(patch_ok && ctx->multi), "sgp_kernelmatrix_diag_grad_conv: not supported on a multi-GPU context");
-  CHECK_ARG(stencil_ok || !spec_has_stencil(ctx, spec),
-            patch_ok ? "sgp_kernelmatrix_diag_grad_conv: gradients through stencil terms are not supported"
-                     : "sgp_kernelmatrix_diag_grad: gradients through stencil terms are not supported");
-  CHECK_ARG(patch_ok || !spec_has_patch(spec),
-            "sgp_kernelmatrix_diag_grad: gradients through patch (convolutional) terms are not supported");
-  CHECK_ARG(kprod_ok || !spec_has_kprod(spec),
+static int diag_grad_core(sgp_ctx* ctx, const DiagGradArgs& a) {
+  // (a.leave.kprod: sgp_kernelmatrix_diag_grad_param, include/sthenomi_kprod_grad.h -- every output may be NULL there, and
+  // the conv / stencil families set it too; a.leave.patch: sgp_kernelmatrix_diag_grad_conv, include/sthenomi_conv_grad.h;
+  // a.leave.stencil: sgp_kernelmatrix_diag_grad_stencil, include/sthenomi_stencil_grad.h)
+  CHECK_ARG(ctx && a.spec && a.w && (a.leave.kprod || (a.grad_coef && a.grad_inscale)),
+            "sgp_kernelmatrix_diag_grad: NULL argument");
+  CHECK_RC(check_grad_leave(ctx, "sgp_kernelmatrix_diag_grad", a.leave, a.spec));
+  CHECK_ARG(a.leave.kprod || !spec_has_kprod(a.spec),
             "sgp_kernelmatrix_diag_grad: gradients through product chains and the RQ / LINEAR kinds are not supported: call "
             "sgp_kernelmatrix_diag_grad_param (include/sthenomi_kprod_grad.h)");
-  CHECK_ARG(!(kprod_ok && ctx->multi), "sgp_kernelmatrix_diag_grad_param: not supported on a multi-GPU context");
+  CHECK_ARG(!(a.leave.kprod && ctx->multi), "sgp_kernelmatrix_diag_grad_param: not supported on a multi-GPU context");
   CtxScope scope(ctx);
   SpecGuard g;
-  CHECK_RC(dspec_create(ctx, spec, &g.ds));
+  CHECK_RC(dspec_create(ctx, a.spec, &g.ds));
   const sgp_dspec* ds = g.ds;
   CHECK_ARG(ds->nrb == ds->ncb, "kernelmatrix_diag_grad: row / col block counts differ");
-  CHECK_ARG(images_unasked(ds, grad_inputs),
+  CHECK_ARG(images_unasked(ds, a.grad_inputs),
             "sgp_kernelmatrix_diag_grad_stencil: an input read by a patch (convolutional) side holds images, and gradients with "
             "respect to images are not supported: its grad_inputs entry must be NULL");
-  if (wo) CHECK_RC(wo->prepare(ds, "sgp_kernelmatrix_diag_grad_stencil_wo", true, ctx->stream));   // (sthenomi_stencil_wo.h)
+  StencilWo wo;   // (include/sthenomi_stencil_wo.h; a no-op throughout when neither table is asked for)
+  wo.gw = a.grad_weights, wo.go = a.grad_offsets;
+  CHECK_RC(wo.prepare(ds, "sgp_kernelmatrix_diag_grad_stencil_wo", true, ctx->stream));
   size_t nt = ds->h_terms.size();
   for (size_t t = 0; t < nt; ++t) {
-    if (grad_coef) grad_coef[t] = 0.0;
-    if (grad_inscale) grad_inscale[t] = 0.0;
-    if (grad_param) grad_param[t] = 0.0;
+    if (a.grad_coef) a.grad_coef[t] = 0.0;
+    if (a.grad_inscale) a.grad_inscale[t] = 0.0;
+    if (a.grad_param) a.grad_param[t] = 0.0;
   }
   if (ds->N == 0 || nt == 0) {
-    if (wo) {
+    if (wo.asked()) {
       SGP_HIP(hipStreamSynchronize(ctx->stream));
-      CHECK_RC(wo->fetch());
+      CHECK_RC(wo.fetch());
     }
     return 0;
   }
   DevBuf dw, dgc, dgs, dgp;
-  CHECK_RC(dw.upload(w, ds->N));
+  CHECK_RC(dw.upload(a.w, ds->N));
   CHECK_RC(dgc.alloc(nt));
   CHECK_RC(dgs.alloc(nt));
   hipStream_t s = ctx->stream;
   SGP_HIP(hipMemsetAsync(dgc.p, 0, sizeof(double) * nt, s));
   SGP_HIP(hipMemsetAsync(dgs.p, 0, sizeof(double) * nt, s));
-  if (grad_param) {
+  if (a.grad_param) {
     CHECK_RC(dgp.alloc(nt));
     SGP_HIP(hipMemsetAsync(dgp.p, 0, sizeof(double) * nt, s));
   }
@@ -4330,14 +4260,14 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
     if (ds->row_len[I] == 0 || t1 == t0) continue;
     CHECK_RC(launch_diag_grad(dw.p + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, t1 - t0, dgc.p + t0,
                               dgs.p + t0, s));
-    for (int t = t0; grad_param && t < t1; ++t)   // d / d param of a plain term: SGP_CONST alone, as a chain of length one
+    for (int t = t0; a.grad_param && t < t1; ++t)   // d / d param of a plain term: SGP_CONST alone, as a chain of length one
       if (ds->h_terms[t].kind == SGP_CONST)
         CHECK_RC(launch_diag_grad_kprod(dw.p + ds->row_off[I], ds->row_len[I], &ds->h_terms[t], 1, nullptr, nullptr,
                                         dgp.p + t, nullptr, nullptr, nullptr, nullptr, s));
   }
-  std::vector<DevBuf> dgx(grad_inputs ? spec->n_inputs : 0);
-  if (grad_inputs) {
-    for (int k = 0; k < spec->n_inputs; ++k) {
+  std::vector<DevBuf> dgx(a.grad_inputs ? a.spec->n_inputs : 0);
+  if (a.grad_inputs) {
+    for (int k = 0; k < a.spec->n_inputs; ++k) {
       size_t cnt = (size_t)std::max<long>(1, (long)ds->in_dim[k] * ds->in_n[k]);
       CHECK_RC(dgx[k].alloc(cnt));
       SGP_HIP(hipMemsetAsync(dgx[k].p, 0, sizeof(double) * cnt, s));
@@ -4350,7 +4280,7 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
                                          dgx[ds->term_row_input[t]].p, dgx[ds->term_col_input[t]].p, s));
       for (int t = diag_tk(p); t < diag_ts(p); ++t) {   // patch terms: the plain side of a one-sided one is not formed here
         const DevTerm& T = ds->h_terms[t];
-        CHECK_ARG((T.hr && T.hc) || !grad_inputs[T.hr ? ds->term_col_input[t] : ds->term_row_input[t]],
+        CHECK_ARG((T.hr && T.hc) || !a.grad_inputs[T.hr ? ds->term_col_input[t] : ds->term_row_input[t]],
                   "sgp_kernelmatrix_diag_grad_stencil: the input-point gradient of a one-sided patch (convolutional) term on "
                   "the diagonal is not supported: the grad_inputs entry of its plain side must be NULL");
       }
@@ -4359,23 +4289,23 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
                                                  dgx[ds->term_row_input[t]].p, dgx[ds->term_col_input[t]].p, s));
     }
   }
-  std::vector<DevBuf> drs(grad_rowscale ? nt : 0), dcs(grad_colscale ? nt : 0);
+  std::vector<DevBuf> drs(a.grad_rowscale ? nt : 0), dcs(a.grad_colscale ? nt : 0);
   auto scale_bufs = [&](int t, long len, double** o_r, double** o_c) -> int {
     const DevTerm& T = ds->h_terms[t];
     *o_r = *o_c = nullptr;
-    if (grad_rowscale && grad_rowscale[term_src_of(ds, t)] && T.rs) {
+    if (a.grad_rowscale && a.grad_rowscale[term_src_of(ds, t)] && T.rs) {
       CHECK_RC(drs[t].alloc((size_t)len));
       SGP_HIP(hipMemsetAsync(drs[t].p, 0, sizeof(double) * len, s));
       *o_r = drs[t].p;
     }
-    if (grad_colscale && grad_colscale[term_src_of(ds, t)] && T.cs) {
+    if (a.grad_colscale && a.grad_colscale[term_src_of(ds, t)] && T.cs) {
       CHECK_RC(dcs[t].alloc((size_t)len));
       SGP_HIP(hipMemsetAsync(dcs[t].p, 0, sizeof(double) * len, s));
       *o_c = dcs[t].p;
     }
     return 0;
   };
-  if (grad_rowscale || grad_colscale)
+  if (a.grad_rowscale || a.grad_colscale)
     for (int I = 0; I < ds->nrb; ++I) {
       const long len = ds->row_len[I];
       if (len == 0) continue;
@@ -4397,82 +4327,62 @@ static int diag_grad_core(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* 
       CHECK_RC(scale_bufs(t, len, &o_r, &o_c));
       double *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
       for (int f = t; f < e; ++f) {
-        gxr[f - t] = grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
-        gxc[f - t] = grad_inputs ? dgx[ds->term_col_input[f]].p : nullptr;
+        gxr[f - t] = a.grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
+        gxc[f - t] = a.grad_inputs ? dgx[ds->term_col_input[f]].p : nullptr;
       }
       CHECK_RC(launch_diag_grad_kprod(dw.p + ds->row_off[I], len, &ds->h_terms[t], e - t, dgc.p + t, dgs.p + t,
-                                      grad_param ? dgp.p + t : nullptr, gxr, gxc, o_r, o_c, s));
+                                      a.grad_param ? dgp.p + t : nullptr, gxr, gxc, o_r, o_c, s));
       t = e;
     }
   }
-  if (wo) CHECK_RC(wo->contract_diag(ds, dw.p, s));   // the stencils' own weights and offsets (stencil.hip)
+  CHECK_RC(wo.contract_diag(ds, dw.p, s));   // the stencils' own weights and offsets (stencil.hip)
   SGP_HIP(hipStreamSynchronize(s));
-  if (wo) CHECK_RC(wo->fetch());
-  CHECK_RC(fetch_terms(ds, grad_coef, dgc.p));
-  CHECK_RC(fetch_terms(ds, grad_inscale, dgs.p));
-  CHECK_RC(fetch_terms(ds, grad_param, dgp.p));
-  for (int I = 0; I < ds->nrb && (grad_rowscale || grad_colscale); ++I)
+  CHECK_RC(wo.fetch());
+  CHECK_RC(fetch_terms(ds, a.grad_coef, dgc.p));
+  CHECK_RC(fetch_terms(ds, a.grad_inscale, dgs.p));
+  CHECK_RC(fetch_terms(ds, a.grad_param, dgp.p));
+  for (int I = 0; I < ds->nrb && (a.grad_rowscale || a.grad_colscale); ++I)
     for (int t = ds->term_ptr[I * ds->ncb + I]; t < ds->term_ptr[I * ds->ncb + I + 1]; ++t) {
-      if (grad_rowscale && drs[t].p)
-        SGP_HIP(hipMemcpy(grad_rowscale[term_src_of(ds, t)], drs[t].p, sizeof(double) * ds->row_len[I], hipMemcpyDeviceToHost));
-      if (grad_colscale && dcs[t].p)
-        SGP_HIP(hipMemcpy(grad_colscale[term_src_of(ds, t)], dcs[t].p, sizeof(double) * ds->row_len[I], hipMemcpyDeviceToHost));
+      if (a.grad_rowscale && drs[t].p)
+        SGP_HIP(hipMemcpy(a.grad_rowscale[term_src_of(ds, t)], drs[t].p, sizeof(double) * ds->row_len[I],
+                          hipMemcpyDeviceToHost));
+      if (a.grad_colscale && dcs[t].p)
+        SGP_HIP(hipMemcpy(a.grad_colscale[term_src_of(ds, t)], dcs[t].p, sizeof(double) * ds->row_len[I],
+                          hipMemcpyDeviceToHost));
     }
   for (size_t k = 0; k < dgx.size(); ++k)
-    if (grad_inputs[k] && spec->inputs[k].n > 0)
-      SGP_HIP(hipMemcpy(grad_inputs[k], dgx[k].p, sizeof(double) * spec->inputs[k].dim * spec->inputs[k].n,
+    if (a.grad_inputs[k] && a.spec->inputs[k].n > 0)
+      SGP_HIP(hipMemcpy(a.grad_inputs[k], dgx[k].p, sizeof(double) * a.spec->inputs[k].dim * a.spec->inputs[k].n,
                         hipMemcpyDeviceToHost));
   return 0;
 }
 
+// the front door of the family (driver.h): the C entry points here and in the libraries beside this one fill a record, call it
+int sgp::drv_diag_grad(sgp_ctx* ctx, const DiagGradArgs& a) { return diag_grad_core(ctx, a); }
+
 extern "C" int sgp_kernelmatrix_diag_grad(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w,
                                           double* grad_coef, double* grad_inscale) {
-  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, nullptr);
+  DiagGradArgs a;
+  a.spec = spec, a.w = w, a.grad_coef = grad_coef, a.grad_inscale = grad_inscale;
+  return drv_diag_grad(ctx, a);
 }
 
 extern "C" int sgp_kernelmatrix_diag_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w,
                                             double* grad_coef, double* grad_inscale,
                                             double* const* grad_inputs) {
   CHECK_ARG(grad_inputs != nullptr, "sgp_kernelmatrix_diag_grad_x: grad_inputs is NULL");
-  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs);
+  DiagGradArgs a;
+  a.spec = spec, a.w = w, a.grad_coef = grad_coef, a.grad_inscale = grad_inscale, a.grad_inputs = grad_inputs;
+  return drv_diag_grad(ctx, a);
 }
 
 extern "C" int sgp_kernelmatrix_diag_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w,
                                              double* grad_coef, double* grad_inscale, double* const* grad_inputs,
                                              double* const* grad_rowscale, double* const* grad_colscale) {
-  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, grad_rowscale, grad_colscale);
-}
-
-// include/sthenomi_kprod_grad.h: sgp_kernelmatrix_diag_grad_param (its C entry point, in libsthenomi_kprod_grad.so, forwards here)
-// include/sthenomi_conv_grad.h: sgp_kernelmatrix_diag_grad_conv (its C entry point, in libsthenomi_conv_grad.so, forwards here)
-int sgp::drv_diag_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale) {
-  CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_conv: NULL argument");
-  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, nullptr, nullptr, nullptr, nullptr, true, true);
-}
-
-// include/sthenomi_stencil_grad.h: sgp_kernelmatrix_diag_grad_stencil (its C entry point, in libsthenomi_stencil_grad.so,
-// forwards here)
-int sgp::drv_diag_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
-                               double* const* grad_inputs) {
-  CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_stencil: NULL argument");
-  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, nullptr, nullptr, nullptr, true, true, true);
-}
-
-// include/sthenomi_stencil_wo.h: sgp_kernelmatrix_diag_grad_stencil_wo (its C entry point, in libsthenomi_stencil_wo.so,
-// forwards here)
-int sgp::drv_diag_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
-                                  double* grad_inscale, double* const* grad_inputs, double* const* grad_weights,
-                                  double* const* grad_offsets) {
-  CHECK_ARG(grad_coef && grad_inscale, "sgp_kernelmatrix_diag_grad_stencil_wo: NULL argument");
-  StencilWo wo;
-  wo.gw = grad_weights, wo.go = grad_offsets;
-  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, nullptr, nullptr, nullptr, true, true, true, &wo);
-}
-
-int sgp::drv_diag_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
-                             double* grad_param, double* const* grad_inputs, double* const* grad_rowscale,
-                             double* const* grad_colscale) {
-  return diag_grad_core(ctx, spec, w, grad_coef, grad_inscale, grad_inputs, grad_rowscale, grad_colscale, grad_param, true);
+  DiagGradArgs a;
+  a.spec = spec, a.w = w, a.grad_coef = grad_coef, a.grad_inscale = grad_inscale, a.grad_inputs = grad_inputs;
+  a.grad_rowscale = grad_rowscale, a.grad_colscale = grad_colscale;
+  return drv_diag_grad(ctx, a);
 }
 
 static int sgp_sparse_posterior_create_impl(sgp_ctx* ctx, const sgp_cov_spec* zz,
@@ -4873,15 +4783,7 @@ int drv_vfe_partial(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz
                            part_len);
 }
 int drv_elbo_grad(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradShard* shard) {
-  auto run = [&]() {
-    StencilWo wz, wx;
-    wz.gw = a.grad_weights_zz, wz.go = a.grad_offsets_zz, wx.gw = a.grad_weights_xz, wx.go = a.grad_offsets_xz;
-    return elbo_grad_core(ctx, a.zz, a.xz, a.var_x, a.mean_x, a.noise_kind, a.noise_x, a.z_noise_kind, a.z_noise, a.y,
-                          a.elbo_out, a.grad_y, a.grad_mean, a.grad_noise, a.grad_var_x, a.grad_z_noise, a.grad_coef_zz,
-                          a.grad_inscale_zz, a.grad_coef_xz, a.grad_inscale_xz, a.grad_inputs_zz, a.grad_inputs_xz,
-                          a.grad_rowscale_zz, a.grad_rowscale_xz, a.grad_colscale_xz, shard, a.grad_param_zz, a.grad_param_xz,
-                          a.kprod_ok, a.patch_ok, a.stencil_ok, wz.asked() ? &wz : nullptr, wx.asked() ? &wx : nullptr);
-  };
+  auto run = [&]() { return elbo_grad_core(ctx, a, shard); };
   // (a rank of a sharded call cannot rerun on its own -- the reduction is collective: multi.hip reruns all of them)
   return shard ? run() : with_df_fallback(ctx, run);
 }

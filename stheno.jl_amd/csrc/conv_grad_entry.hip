@@ -1,6 +1,7 @@
 // libsthenomi_conv_grad.so -- the entry points of include/sthenomi_conv_grad.h.  Links against libsthenomi.so, whose driver
 // carries patch terms through the gradient cores (capi.hip: logpdf_grad_core, diag_grad_core, elbo_grad_core; kernels in
-// conv.hip); this file only gives the three their C names.
+// conv.hip); this file only gives the three their C names: each fills its core's record (ctx.h), sets the leave the family
+// carries and calls the core's door (driver.h).
 #include "ctx.h"
 #include "driver.h"
 #include "../../include/sthenomi_conv_grad.h"
@@ -8,13 +9,22 @@
 extern "C" int sgp_logpdf_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
                                     const double* noise, const double* y, double* logpdf_out, double* grad_y,
                                     double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale) {
-  return sgp::drv_logpdf_grad_conv(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
-                                   grad_inscale);
+  sgp::LogpdfGradArgs a = sgp::logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
+                                                grad_coef, grad_inscale);
+  a.leave.patch = true;
+  return sgp::drv_logpdf_grad(ctx, a);
 }
 
 extern "C" int sgp_kernelmatrix_diag_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
                                                double* grad_inscale) {
-  return sgp::drv_diag_grad_conv(ctx, spec, w, grad_coef, grad_inscale);
+  if (!(grad_coef && grad_inscale)) {
+    sgp::set_error("sgp_kernelmatrix_diag_grad_conv: NULL argument");
+    return -1;
+  }
+  sgp::DiagGradArgs a;
+  a.spec = spec, a.w = w, a.grad_coef = grad_coef, a.grad_inscale = grad_inscale;
+  a.leave.kprod = a.leave.patch = true;
+  return sgp::drv_diag_grad(ctx, a);
 }
 
 extern "C" int sgp_elbo_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz, const double* var_x,
@@ -24,12 +34,9 @@ extern "C" int sgp_elbo_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* zz, const sg
                                   double* grad_coef_zz, double* grad_inscale_zz, double* grad_coef_xz,
                                   double* grad_inscale_xz, double* const* grad_inputs_zz,
                                   double* const* grad_inputs_xz) {
-  sgp::ElboGradArgs a;
-  a.zz = zz, a.xz = xz, a.var_x = var_x, a.mean_x = mean_x, a.noise_kind = noise_kind, a.noise_x = noise_x;
-  a.z_noise_kind = z_noise_kind, a.z_noise = z_noise, a.y = y, a.elbo_out = elbo_out, a.grad_y = grad_y;
-  a.grad_mean = grad_mean, a.grad_noise = grad_noise, a.grad_var_x = grad_var_x, a.grad_z_noise = grad_z_noise;
-  a.grad_coef_zz = grad_coef_zz, a.grad_inscale_zz = grad_inscale_zz, a.grad_coef_xz = grad_coef_xz;
-  a.grad_inscale_xz = grad_inscale_xz, a.grad_inputs_zz = grad_inputs_zz, a.grad_inputs_xz = grad_inputs_xz;
-  a.patch_ok = true;
-  return sgp::drv_elbo_grad_conv(ctx, a);
+  sgp::ElboGradArgs a = sgp::elbo_grad_args(zz, xz, var_x, mean_x, noise_kind, noise_x, z_noise_kind, z_noise, y, elbo_out,
+                                            grad_y, grad_mean, grad_noise, grad_var_x, grad_z_noise, grad_coef_zz,
+                                            grad_inscale_zz, grad_coef_xz, grad_inscale_xz);
+  a.grad_inputs_zz = grad_inputs_zz, a.grad_inputs_xz = grad_inputs_xz, a.leave.patch = true;
+  return sgp::elbo_grad_entry(ctx, a);
 }

@@ -47,9 +47,52 @@ int sgp_multi_logpdf_grad(struct sgp_ctx* ctx, const sgp_cov_spec* spec, const d
                           const double* noise, const double* y, double* logpdf_out, double* grad_y, double* grad_mean,
                           double* grad_noise, double* grad_coef, double* grad_inscale, double* const* grad_inputs = nullptr,
                           double* const* grad_rowscale = nullptr);
-// sgp_elbo_grad / _x / _xs: the arguments of the three entry points as one record (NULL = not asked for), and one rank's
-// view of a data-sharded call (round 6)
+// The gradient cores of capi.hip (logpdf_grad_core, diag_grad_core, elbo_grad_core) take one record each: what every entry
+// point of a family passes, NULL = not asked for.  One rank's view of a data-sharded ELBO call (round 6) sits beside them.
 namespace sgp {
+// the leave an entry point gives its core to carry terms beyond the plain ones; each core's own comment says what it means
+struct GradLeave {
+  bool kprod = false;     // product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h, sthenomi_kprod_grad.h)
+  bool patch = false;     // patch (convolutional) terms (include/sthenomi_conv_grad.h)
+  bool stencil = false;   // stencil terms (include/sthenomi_stencil_grad.h, sthenomi_stencil_wo.h); set together with patch
+};
+// sgp_logpdf_grad / _x / _xs / _param / _param_xs / _conv / _stencil / _stencil_wo
+struct LogpdfGradArgs {
+  const sgp_cov_spec* spec = nullptr;
+  const double* mean = nullptr;
+  int noise_kind = 0;
+  const double *noise = nullptr, *y = nullptr;
+  double *logpdf_out = nullptr, *grad_y = nullptr, *grad_mean = nullptr, *grad_noise = nullptr, *grad_coef = nullptr,
+         *grad_inscale = nullptr, *grad_param = nullptr;
+  double* const* grad_inputs = nullptr;
+  double* const* grad_rowscale = nullptr;
+  // the stencils' own weights and offsets, two pointers per term (include/sthenomi_stencil_wo.h)
+  double* const* grad_weights = nullptr;
+  double* const* grad_offsets = nullptr;
+  GradLeave leave;
+};
+// the eleven arguments every sgp_logpdf_grad* entry point has, as a record; the caller adds its family's own
+inline LogpdfGradArgs logpdf_grad_args(const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
+                                       const double* y, double* logpdf_out, double* grad_y, double* grad_mean,
+                                       double* grad_noise, double* grad_coef, double* grad_inscale) {
+  LogpdfGradArgs a;
+  a.spec = spec, a.mean = mean, a.noise_kind = noise_kind, a.noise = noise, a.y = y, a.logpdf_out = logpdf_out;
+  a.grad_y = grad_y, a.grad_mean = grad_mean, a.grad_noise = grad_noise, a.grad_coef = grad_coef, a.grad_inscale = grad_inscale;
+  return a;
+}
+// sgp_kernelmatrix_diag_grad / _x / _xs / _param / _conv / _stencil / _stencil_wo
+struct DiagGradArgs {
+  const sgp_cov_spec* spec = nullptr;
+  const double* w = nullptr;
+  double *grad_coef = nullptr, *grad_inscale = nullptr, *grad_param = nullptr;
+  double* const* grad_inputs = nullptr;
+  double* const* grad_rowscale = nullptr;
+  double* const* grad_colscale = nullptr;
+  double* const* grad_weights = nullptr;
+  double* const* grad_offsets = nullptr;
+  GradLeave leave;
+};
+// sgp_elbo_grad / _x / _xs / _param / _conv / _stencil / _stencil_wo
 struct ElboGradArgs {
   const sgp_cov_spec *zz = nullptr, *xz = nullptr;
   const double *var_x = nullptr, *mean_x = nullptr;
@@ -65,19 +108,29 @@ struct ElboGradArgs {
   double* const* grad_rowscale_zz = nullptr;
   double* const* grad_rowscale_xz = nullptr;
   double* const* grad_colscale_xz = nullptr;
-  // sgp_elbo_grad_param (include/sthenomi_kprod_grad.h): d / d param per term, and the leave to carry product chains
+  // sgp_elbo_grad_param (include/sthenomi_kprod_grad.h): d / d param per term
   double *grad_param_zz = nullptr, *grad_param_xz = nullptr;
-  bool kprod_ok = false;
-  // sgp_elbo_grad_conv (include/sthenomi_conv_grad.h): the leave to carry patch terms
-  bool patch_ok = false;
-  // sgp_elbo_grad_stencil (include/sthenomi_stencil_grad.h): the leave to carry stencil terms (it sets patch_ok as well)
-  bool stencil_ok = false;
   // sgp_elbo_grad_stencil_wo (include/sthenomi_stencil_wo.h): the stencils' own weights and offsets, two pointers per term
   double* const* grad_weights_zz = nullptr;
   double* const* grad_offsets_zz = nullptr;
   double* const* grad_weights_xz = nullptr;
   double* const* grad_offsets_xz = nullptr;
+  GradLeave leave;
 };
+// the nineteen arguments every sgp_elbo_grad* entry point has, as a record; the caller adds its family's own
+inline ElboGradArgs elbo_grad_args(const sgp_cov_spec* zz, const sgp_cov_spec* xz, const double* var_x, const double* mean_x,
+                                   int noise_kind, const double* noise_x, int z_noise_kind, const double* z_noise,
+                                   const double* y, double* elbo_out, double* grad_y, double* grad_mean, double* grad_noise,
+                                   double* grad_var_x, double* grad_z_noise, double* grad_coef_zz, double* grad_inscale_zz,
+                                   double* grad_coef_xz, double* grad_inscale_xz) {
+  ElboGradArgs a;
+  a.zz = zz, a.xz = xz, a.var_x = var_x, a.mean_x = mean_x, a.noise_kind = noise_kind, a.noise_x = noise_x;
+  a.z_noise_kind = z_noise_kind, a.z_noise = z_noise, a.y = y, a.elbo_out = elbo_out, a.grad_y = grad_y;
+  a.grad_mean = grad_mean, a.grad_noise = grad_noise, a.grad_var_x = grad_var_x, a.grad_z_noise = grad_z_noise;
+  a.grad_coef_zz = grad_coef_zz, a.grad_inscale_zz = grad_inscale_zz, a.grad_coef_xz = grad_coef_xz;
+  a.grad_inscale_xz = grad_inscale_xz;
+  return a;
+}
 struct ElboGradShard {
   bool primary = false;   // the rank that also produces the zz-side results (G_zz and its contractions)
   long n_total = 0;       // data points of the whole call (the bound's N log 2 pi)

@@ -67,43 +67,13 @@ int drv_sparse_posterior_predict_grad_x(sgp_sparse_post* post, const sgp_cov_spe
                                         const double* mean_s, double* mean_out, double* var_out,
                                         double* const* grad_mean_inputs, double* const* grad_var_inputs,
                                         double* const* grad_var_prior_inputs);
-// include/sthenomi_kprod.h: sgp_logpdf_grad_param, forwarded from libsthenomi_kprod.so; takes the context itself
-int drv_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
-                          const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
-                          double* grad_coef, double* grad_inscale, double* grad_param);
-// ... sgp_logpdf_grad_param_xs, sgp_kernelmatrix_diag_grad_param, sgp_elbo_grad_param: the supersets that carry product chains (include/sthenomi_kprod_grad.h)
-int drv_logpdf_grad_param_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
-                             const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
-                             double* grad_coef, double* grad_inscale, double* grad_param, double* const* grad_inputs,
-                             double* const* grad_rowscale);
-int drv_diag_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
-                        double* grad_param, double* const* grad_inputs, double* const* grad_rowscale,
-                        double* const* grad_colscale);
-int drv_elbo_grad_param(sgp_ctx* ctx, const ElboGradArgs& a);   // a.kprod_ok set by the caller
-// sgp_logpdf_grad_conv, sgp_kernelmatrix_diag_grad_conv, sgp_elbo_grad_conv: the gradients that carry patch terms
-// (include/sthenomi_conv_grad.h, forwarded from libsthenomi_conv_grad.so)
-int drv_logpdf_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
-                         const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
-                         double* grad_coef, double* grad_inscale);
-int drv_diag_grad_conv(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale);
-int drv_elbo_grad_conv(sgp_ctx* ctx, const ElboGradArgs& a);   // a.patch_ok set by the caller
-// sgp_logpdf_grad_stencil, sgp_kernelmatrix_diag_grad_stencil, sgp_elbo_grad_stencil: the gradients that carry stencil terms,
-// input points included (include/sthenomi_stencil_grad.h, forwarded from libsthenomi_stencil_grad.so)
-int drv_logpdf_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
-                            const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
-                            double* grad_coef, double* grad_inscale, double* const* grad_inputs);
-int drv_diag_grad_stencil(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
-                          double* const* grad_inputs);
-int drv_elbo_grad_stencil(sgp_ctx* ctx, const ElboGradArgs& a);   // a.patch_ok and a.stencil_ok set by the caller
-// sgp_logpdf_grad_stencil_wo, sgp_kernelmatrix_diag_grad_stencil_wo, sgp_elbo_grad_stencil_wo: the same with the gradients with
-// respect to the stencils' own weights and offsets (include/sthenomi_stencil_wo.h, forwarded from libsthenomi_stencil_wo.so)
-int drv_logpdf_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,
-                               const double* y, double* logpdf_out, double* grad_y, double* grad_mean, double* grad_noise,
-                               double* grad_coef, double* grad_inscale, double* const* grad_inputs,
-                               double* const* grad_weights, double* const* grad_offsets);
-int drv_diag_grad_stencil_wo(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef, double* grad_inscale,
-                             double* const* grad_inputs, double* const* grad_weights, double* const* grad_offsets);
-int drv_elbo_grad_stencil_wo(sgp_ctx* ctx, const ElboGradArgs& a);   // a.grad_weights_* / a.grad_offsets_* as well
+// The gradient front doors: one per core of capi.hip, taking the core's argument record (ctx.h).  The C entry points of every
+// family -- capi.hip's own and those of libsthenomi_kprod / _kprod_grad / _conv_grad / _stencil_grad / _stencil_wo.so -- fill
+// a record, set the leave their family carries and call the door; each takes the context itself.
+int drv_logpdf_grad(sgp_ctx* ctx, const LogpdfGradArgs& a);   // logpdf_grad_core, with the dataflow time-out fallback
+int drv_diag_grad(sgp_ctx* ctx, const DiagGradArgs& a);       // diag_grad_core
+// the leave checks, then the data-sharded call on a multi-GPU context (multi.hip) or drv_elbo_grad below on one GPU
+int elbo_grad_entry(sgp_ctx* ctx, const ElboGradArgs& a);
 int drv_diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStream_t s);
 int drv_dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out);   // caller holds the context
 // register a patch geometry on ctx (include/sthenomi_conv.h: sgp_conv_geom, whose C entry point in libsthenomi_conv.so

@@ -1,6 +1,7 @@
 // libsthenomi_kprod_grad.so -- the entry points of include/sthenomi_kprod_grad.h.  Links against libsthenomi.so, whose driver
 // carries product chains through the gradient cores (capi.hip: logpdf_grad_core, diag_grad_core, elbo_grad_core; kernels in
-// kprod.hip); this file only gives the superset family its C names.
+// kprod.hip); this file only gives the superset family its C names: each fills its core's record (ctx.h), sets the chain
+// leave and calls the core's door (driver.h).
 #include "ctx.h"
 #include "driver.h"
 #include "../../include/sthenomi_kprod_grad.h"
@@ -9,15 +10,19 @@ extern "C" int sgp_logpdf_grad_param_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, 
                                         const double* noise, const double* y, double* logpdf_out, double* grad_y,
                                         double* grad_mean, double* grad_noise, double* grad_coef, double* grad_inscale,
                                         double* grad_param, double* const* grad_inputs, double* const* grad_rowscale) {
-  return sgp::drv_logpdf_grad_param_xs(ctx, spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
-                                       grad_coef, grad_inscale, grad_param, grad_inputs, grad_rowscale);
+  sgp::LogpdfGradArgs a = sgp::logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
+                                                grad_coef, grad_inscale);
+  a.grad_param = grad_param, a.grad_inputs = grad_inputs, a.grad_rowscale = grad_rowscale, a.leave.kprod = true;
+  return sgp::drv_logpdf_grad(ctx, a);
 }
 
 extern "C" int sgp_kernelmatrix_diag_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* w, double* grad_coef,
                                                 double* grad_inscale, double* grad_param, double* const* grad_inputs,
                                                 double* const* grad_rowscale, double* const* grad_colscale) {
-  return sgp::drv_diag_grad_param(ctx, spec, w, grad_coef, grad_inscale, grad_param, grad_inputs, grad_rowscale,
-                                  grad_colscale);
+  sgp::DiagGradArgs a;
+  a.spec = spec, a.w = w, a.grad_coef = grad_coef, a.grad_inscale = grad_inscale, a.grad_param = grad_param;
+  a.grad_inputs = grad_inputs, a.grad_rowscale = grad_rowscale, a.grad_colscale = grad_colscale, a.leave.kprod = true;
+  return sgp::drv_diag_grad(ctx, a);
 }
 
 extern "C" int sgp_elbo_grad_param(sgp_ctx* ctx, const sgp_cov_spec* zz, const sgp_cov_spec* xz, const double* var_x,
@@ -29,13 +34,11 @@ extern "C" int sgp_elbo_grad_param(sgp_ctx* ctx, const sgp_cov_spec* zz, const s
                                    double* const* grad_inputs_zz, double* const* grad_inputs_xz,
                                    double* const* grad_rowscale_zz, double* const* grad_rowscale_xz,
                                    double* const* grad_colscale_xz) {
-  sgp::ElboGradArgs a;
-  a.zz = zz, a.xz = xz, a.var_x = var_x, a.mean_x = mean_x, a.noise_kind = noise_kind, a.noise_x = noise_x;
-  a.z_noise_kind = z_noise_kind, a.z_noise = z_noise, a.y = y, a.elbo_out = elbo_out, a.grad_y = grad_y;
-  a.grad_mean = grad_mean, a.grad_noise = grad_noise, a.grad_var_x = grad_var_x, a.grad_z_noise = grad_z_noise;
-  a.grad_coef_zz = grad_coef_zz, a.grad_inscale_zz = grad_inscale_zz, a.grad_coef_xz = grad_coef_xz;
-  a.grad_inscale_xz = grad_inscale_xz, a.grad_param_zz = grad_param_zz, a.grad_param_xz = grad_param_xz;
+  sgp::ElboGradArgs a = sgp::elbo_grad_args(zz, xz, var_x, mean_x, noise_kind, noise_x, z_noise_kind, z_noise, y, elbo_out,
+                                            grad_y, grad_mean, grad_noise, grad_var_x, grad_z_noise, grad_coef_zz,
+                                            grad_inscale_zz, grad_coef_xz, grad_inscale_xz);
+  a.grad_param_zz = grad_param_zz, a.grad_param_xz = grad_param_xz;
   a.grad_inputs_zz = grad_inputs_zz, a.grad_inputs_xz = grad_inputs_xz, a.grad_rowscale_zz = grad_rowscale_zz;
-  a.grad_rowscale_xz = grad_rowscale_xz, a.grad_colscale_xz = grad_colscale_xz, a.kprod_ok = true;
-  return sgp::drv_elbo_grad_param(ctx, a);
+  a.grad_rowscale_xz = grad_rowscale_xz, a.grad_colscale_xz = grad_colscale_xz, a.leave.kprod = true;
+  return sgp::elbo_grad_entry(ctx, a);
 }
