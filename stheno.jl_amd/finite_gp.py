@@ -440,6 +440,25 @@ def _grad_record(spec, kind, lp, bufs, inputs=None, x=None, scales=None, rowscal
                 _raw=(gc, gs) if gp is None else (gc, gs, gp), _rowscale=rowscale, _spec=spec)
 
 
+def _logpdf_grad_spec(fx, y):
+    """What every logpdf gradient does before its family's refusals: the prior check, y as a float64 vector, the spec."""
+    if not _is_prior(fx.f):
+        raise NotImplementedError("gradients are implemented for prior Stheno processes")
+    return _f64(np.asarray(y, dtype=np.float64).ravel()), _prior_spec(fx.f, fx.x)
+
+
+def _logpdf_grad_frame(fx, yv, spec):
+    """... and after them: the mean, the noise, the output buffers and the 12 leading arguments every sgp_logpdf_grad* entry
+    point takes (context through grad_inscale) -> (noise kind, lp, buffers, arguments).  A caller adds its tail pointers,
+    names its entry point and finishes through _grad_record."""
+    m = _f64(mean_vector(fx.f, fx.x))
+    kind, nbuf = _lib._noise_args(fx.noise, len(fx))
+    lp = np.zeros(1)
+    bufs = _grad_buffers(spec, kind, len(fx))
+    d = _lib.dptr
+    return kind, lp, bufs, (_ctx().handle, spec.ref(), d(m), kind, d(nbuf), d(yv), d(lp)) + tuple(d(b) for b in bufs)
+
+
 def _grad_failed(spec, info):
     return dict(logpdf=float("nan"), info=int(info), y=None, mean=None, noise=None, terms=None, inputs=None, x=None,
                 scales=None, _raw=None, _rowscale=None, _spec=spec)
@@ -571,60 +590,28 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, gamma of GammaExponential, c of Linear / Constant; 0 for nu
     of GeneralMaternKernel, which is held fixed).  inputs / scales of such
     models come from logpdf_and_gradient_param."""
-    if not _is_prior(fx.f):
-        raise NotImplementedError("gradients are implemented for prior Stheno processes")
-    n = len(fx)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    spec = _prior_spec(fx.f, fx.x)
+    yv, spec = _logpdf_grad_spec(fx, y)
     _refuse_patch_gradient(spec)
     if inputs or scales:
         _refuse_product_gradient("logpdf_and_gradient: inputs=True / scales=True", spec)
-    m = _f64(mean_vector(fx.f, fx.x))
-    kind, nbuf = _lib._noise_args(fx.noise, n)
-    lp = np.zeros(1)
-    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
-    nt = max(1, spec.n_terms)
-    gx = None
-    grs = None
+    kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
     if spec.has_kprod:
         if _ctx().is_multi:
             raise NotImplementedError("a product of kernels is not supported on a multi-GPU context")
-        gp = np.zeros(nt)
-        rc = _ctx().kprod.sgp_logpdf_grad_param(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                                _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
-                                                _lib.dptr(gc), _lib.dptr(gs), _lib.dptr(gp))
-        _lib.check(rc, "sgp_logpdf_grad_param")
+        gp = np.zeros(max(1, spec.n_terms))
+        _lib.check(_ctx().kprod.sgp_logpdf_grad_param(*args, _lib.dptr(gp)), "sgp_logpdf_grad_param")
         return _grad_record(spec, kind, lp[0], bufs, gp=gp)
+    gx = ptrs = grs = None
+    if inputs:
+        gx = _input_buffers(spec)[0]
+        ptrs = _dptrs(gx)       # (len(gx) slots: a spec without inputs hands these two entry points an empty table, not one NULL)
     if scales:
-        if inputs:
-            gx = [np.zeros(np.asarray(a).shape, order="F") for a in spec.inputs]
-            ptrs = (C.POINTER(C.c_double) * len(gx))(*[_lib.dptr(a) for a in gx])
-        else:
-            ptrs = None
-        rl = np.asarray(spec.row_len)
-        ncb = len(spec.col_len)
-        grs = [None] * nt
-        for p in range(len(rl) * ncb):
-            for t in range(spec._term_ptr[p], spec._term_ptr[p + 1]):
-                if spec.term_row_scale[t] is not None:
-                    grs[t] = np.zeros(int(rl[p // ncb]))
-        sptrs = (C.POINTER(C.c_double) * nt)(*[_lib.dptr(a) if a is not None else None for a in grs])
-        rc = _ctx().lib.sgp_logpdf_grad_xs(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                           _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
-                                           _lib.dptr(gc), _lib.dptr(gs), ptrs, sptrs)
-        _lib.check(rc, "sgp_logpdf_grad_xs")
+        grs, sptrs = _scale_arrays(spec, "row")
+        _lib.check(_ctx().lib.sgp_logpdf_grad_xs(*args, ptrs, sptrs), "sgp_logpdf_grad_xs")
     elif inputs:
-        gx = [np.zeros(np.asarray(a).shape, order="F") for a in spec.inputs]
-        ptrs = (C.POINTER(C.c_double) * len(gx))(*[_lib.dptr(a) for a in gx])
-        rc = _ctx().lib.sgp_logpdf_grad_x(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                          _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
-                                          _lib.dptr(gc), _lib.dptr(gs), ptrs)
-        _lib.check(rc, "sgp_logpdf_grad_x")
+        _lib.check(_ctx().lib.sgp_logpdf_grad_x(*args, ptrs), "sgp_logpdf_grad_x")
     else:
-        rc = _ctx().lib.sgp_logpdf_grad(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                        _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
-                                        _lib.dptr(gc), _lib.dptr(gs))
-        _lib.check(rc, "sgp_logpdf_grad")
+        _lib.check(_ctx().lib.sgp_logpdf_grad(*args), "sgp_logpdf_grad")
     # x: the same gradient mapped back through the model's input transformations onto the blocks of
     # fx.x (one (D, n) array per block; blocks sharing one input object get their joint gradient in
     # the first of them)
@@ -676,27 +663,13 @@ def logpdf_and_gradient_param(fx, y, inputs=False, scales=False):
     through a LinearTransform or an ARDTransform also carries `d_transform`, the derivative with respect to that transform's
     matrix or vector (_attach_d_transform): the frequencies and bandwidths of a spectral mixture.  Single-GPU contexts; no
     patch / stencil terms."""
-    if not _is_prior(fx.f):
-        raise NotImplementedError("gradients are implemented for prior Stheno processes")
-    n = len(fx)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    spec = _prior_spec(fx.f, fx.x)
+    yv, spec = _logpdf_grad_spec(fx, y)
     _refuse_param_family("logpdf_and_gradient_param", spec)
-    m = _f64(mean_vector(fx.f, fx.x))
-    kind, nbuf = _lib._noise_args(fx.noise, n)
-    lp = np.zeros(1)
-    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
+    kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
     gp = np.zeros(max(1, spec.n_terms))
-    gx = ptrs = grs = sptrs = None
-    if inputs:
-        gx = [np.zeros(np.asarray(a).shape, order="F") for a in spec.inputs]
-        ptrs = (C.POINTER(C.c_double) * max(1, len(gx)))(*[_lib.dptr(a) for a in gx])
-    if scales:
-        grs, sptrs = _scale_arrays(spec, "row")
-    rc = _ctx().kprod_grad.sgp_logpdf_grad_param_xs(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                                    _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
-                                                    _lib.dptr(gc), _lib.dptr(gs), _lib.dptr(gp), ptrs, sptrs)
-    _lib.check(rc, "sgp_logpdf_grad_param_xs")
+    gx, ptrs = _input_buffers(spec) if inputs else (None, None)
+    grs, sptrs = _scale_arrays(spec, "row") if scales else (None, None)
+    _lib.check(_ctx().kprod_grad.sgp_logpdf_grad_param_xs(*args, _lib.dptr(gp), ptrs, sptrs), "sgp_logpdf_grad_param_xs")
     xb = chain_input_gradients(spec, gx)[0] if inputs else None
     rec = _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs, gp=gp)
     if inputs:
@@ -725,22 +698,12 @@ def logpdf_and_gradient_conv(fx, y):
     under patch_convolve; a lengthscale l = 1 / g gives d / dl = -g^2 d_inscale), exactly as for a plain term; the record also
     carries row_geom / col_geom.  No inputs / scales: gradients with respect to images are not formed.  Single-GPU contexts,
     no stencil terms."""
-    if not _is_prior(fx.f):
-        raise NotImplementedError("gradients are implemented for prior Stheno processes")
-    n = len(fx)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    spec = _prior_spec(fx.f, fx.x)
+    yv, spec = _logpdf_grad_spec(fx, y)
     _refuse_conv_family("logpdf_and_gradient_conv", spec)
     if spec.has_kprod:
         return logpdf_and_gradient(fx, y)
-    m = _f64(mean_vector(fx.f, fx.x))
-    kind, nbuf = _lib._noise_args(fx.noise, n)
-    lp = np.zeros(1)
-    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
-    rc = _ctx().conv_grad.sgp_logpdf_grad_conv(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf), _lib.dptr(yv),
-                                               _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn), _lib.dptr(gc),
-                                               _lib.dptr(gs))
-    _lib.check(rc, "sgp_logpdf_grad_conv")
+    kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
+    _lib.check(_ctx().conv_grad.sgp_logpdf_grad_conv(*args), "sgp_logpdf_grad_conv")
     return _grad_record(spec, kind, lp[0], bufs)
 
 
@@ -807,33 +770,20 @@ def logpdf_and_gradient_stencil(fx, y, inputs=False, stencils=False):
     the observed processes reach, {"node", "d_offsets" (D x Q, the node's own shape), "d_weights" (Q)} -- the chain back
     through the kernel's scalar input scale, the Stretch / Select maps below the node and nested stencils
     (flatten.stencil_node_gradients); a scalar scale above or below the node belongs to the term's coefficient."""
-    if not _is_prior(fx.f):
-        raise NotImplementedError("gradients are implemented for prior Stheno processes")
-    n = len(fx)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    spec = _prior_spec(fx.f, fx.x)
+    yv, spec = _logpdf_grad_spec(fx, y)
     _refuse_stencil_family("logpdf_and_gradient_stencil", spec)
     if spec.has_kprod:
         rec = logpdf_and_gradient_param(fx, y, inputs=True) if inputs else logpdf_and_gradient(fx, y)
         if stencils:
             rec["stencils"] = []       # (a model with a product of kernels has no stencil terms)
         return rec
-    m = _f64(mean_vector(fx.f, fx.x))
-    kind, nbuf = _lib._noise_args(fx.noise, n)
-    lp = np.zeros(1)
-    gy, gm, gn, gc, gs = bufs = _grad_buffers(spec, kind, n)
+    kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
     gx, ptrs = _input_buffers(spec) if inputs else (None, None)
     if stencils:
         gw, go, pw, po = _stencil_tables(spec)
-        rc = _ctx().stencil_wo.sgp_logpdf_grad_stencil_wo(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                                          _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm),
-                                                          _lib.dptr(gn), _lib.dptr(gc), _lib.dptr(gs), ptrs, pw, po)
-        _lib.check(rc, "sgp_logpdf_grad_stencil_wo")
+        _lib.check(_ctx().stencil_wo.sgp_logpdf_grad_stencil_wo(*args, ptrs, pw, po), "sgp_logpdf_grad_stencil_wo")
     else:
-        rc = _ctx().stencil_grad.sgp_logpdf_grad_stencil(_ctx().handle, spec.ref(), _lib.dptr(m), kind, _lib.dptr(nbuf),
-                                                         _lib.dptr(yv), _lib.dptr(lp), _lib.dptr(gy), _lib.dptr(gm),
-                                                         _lib.dptr(gn), _lib.dptr(gc), _lib.dptr(gs), ptrs)
-        _lib.check(rc, "sgp_logpdf_grad_stencil")
+        _lib.check(_ctx().stencil_grad.sgp_logpdf_grad_stencil(*args, ptrs), "sgp_logpdf_grad_stencil")
     xb = chain_input_gradients(spec, gx)[0] if inputs else None
     rec = _grad_record(spec, kind, lp[0], bufs, gx, xb)
     if stencils:
@@ -1387,6 +1337,68 @@ def _scale_arrays(spec, side):
     return arrs, (C.POINTER(C.c_double) * nt)(*[_lib.dptr(a) if a is not None else None for a in arrs])
 
 
+def _elbo_grad_specs(vfe, fx, y):
+    """What every ELBO gradient does before its family's refusals: _vfe_args, y as a float64 vector and the spec of
+    diag K(x,x) -> the specs (zz, xz, xx) the refusals look at, and what _elbo_grad_frame goes on from."""
+    zz, xz, *rest = _vfe_args(vfe, fx)
+    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
+    return (zz, xz, _prior_spec(fx.f, fx.x)), (len(fx), len(vfe.fz), yv, *rest)
+
+
+def _elbo_grad_frame(specs, head, per_term=2):
+    """... and after them: var(f, x) (a library call: sgp_kernelmatrix_diag), the output buffers, per spec the per-term arrays
+    (gc, gs), with per_term=3 (gc, gs, gp), and the leading arguments of the two calls every family makes:
+    `args`, those of its sgp_elbo_grad* entry point (context through grad_z_noise, then the per-term arrays of zz and of xz),
+    and `dargs`, those of its sgp_kernelmatrix_diag_grad* entry point (context, xx, the weights d elbo / d var, the per-term
+    arrays of xx).  A caller adds its tail pointers and names its entry points."""
+    (zz, xz, xx), (n, m, yv, mean_x, nk, nbuf, zk, zbuf) = specs, head
+    var_x = _f64(_kernelmatrix_diag(xx))
+    out = np.zeros(1)
+    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
+    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
+    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
+    raw = {k: tuple(np.zeros(max(1, sp.n_terms)) for _ in range(per_term)) for k, sp in zip(("zz", "xz", "xx"), specs)}
+    d = _lib.dptr
+    args = (_ctx().handle, zz.ref(), xz.ref(), d(var_x), d(mean_x), nk, d(nbuf), zk, d(zbuf), d(yv), d(out), d(gy), d(gm),
+            d(gn), d(gv), d(gzn)) + tuple(d(a) for a in raw["zz"] + raw["xz"])
+    dargs = (_ctx().handle, xx.ref(), d(gv)) + tuple(d(a) for a in raw["xx"])
+    return dict(specs=specs, args=args, dargs=dargs, out=out, bufs=(gy, gm, gn, gv, gzn), raw=raw, kinds=(nk, zk))
+
+
+def _elbo_scale_arrays(specs):
+    """the five places the bound reads a function-valued scale -- zz rows, xz rows, xz columns, xx rows, xx columns: their
+    _scale_arrays -> (the five lists of arrays, the five pointer tables)"""
+    zz, xz, xx = specs
+    both = [_scale_arrays(sp, side) for sp, side in ((zz, "row"), (xz, "row"), (xz, "col"), (xx, "row"), (xx, "col"))]
+    return [a for a, _ in both], [p for _, p in both]
+
+
+def _elbo_grad_result(F, gin=(None, None, None), scale_arrs=None):
+    """The dict every ELBO gradient returns, from its frame after the two calls.  gin: the input-gradient arrays of
+    (zz, xz, xx) where they were asked for: their chain rule back onto the blocks of fx.x and fz.x gives `x` and `z` (no
+    xx arrays -- the _conv family forms none -- no `x`).  scale_arrs: the arrays of _elbo_scale_arrays."""
+    (zz, xz, xx), (gy, gm, gn, gv, gzn), raw, (nk, zk) = F["specs"], F["bufs"], F["raw"], F["kinds"]
+    records = _term_records if len(raw["zz"]) == 2 else _term_records_kprod
+    xx_terms = [r for r in records(xx, *raw["xx"], False) if r["I"] == r["J"]] if len(xx.row_len) else []
+    gxz, gxx, gdx = gin
+    xb = zb = None
+    if gxz is not None:   # chain rule back onto the blocks of fx.x and fz.x (through every factor's own view)
+        zr, _ = chain_input_gradients(zz, gxz)
+        xr, zc = chain_input_gradients(xz, gxx)
+        zb = [a + b for a, b in zip(zr, zc)]
+        if gdx is not None:
+            xd, _ = chain_input_gradients(xx, gdx)
+            xb = [a + b for a, b in zip(xr, xd)]
+    S = scale_arrs
+    return dict(elbo=float(F["out"][0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
+                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
+                zz_terms=records(zz, *raw["zz"], True), xz_terms=records(xz, *raw["xz"], False),
+                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx,
+                scales=(_scale_records(zz, S[0], more=((xz, S[1], "row"), (xz, S[2], "col"), (xx, S[3], "row"), (xx, S[4], "col")))
+                        if S else None),
+                _raw=raw, _specs=dict(zz=zz, xz=xz, xx=xx))
+
+
 def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
     """elbo(VFE(fz), fx, y) and its reverse-mode gradient (what Zygote derives through
     AbstractGPs.elbo on the reference path; sgp_elbo_grad).
@@ -1402,72 +1414,26 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
     places the bound reads sigma: K(z,z), K(x,z) (row side at x, column side at z) and diag K(x,x)."""
     if isinstance(vfe, SparseFiniteGP):
         return elbo_and_gradient(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, scales=scales)
-    zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
-    n, m = len(fx), len(vfe.fz)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    xx = _prior_spec(fx.f, fx.x)
-    _refuse_patch_gradient(zz, xz, xx)
-    _refuse_product_gradient("elbo_and_gradient", zz, xz, xx)
-    var_x = _f64(_kernelmatrix_diag(xx))
-    out = np.zeros(1)
-    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
-    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
-    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
-    gcz, gsz = np.zeros(max(1, zz.n_terms)), np.zeros(max(1, zz.n_terms))
-    gcx, gsx = np.zeros(max(1, xz.n_terms)), np.zeros(max(1, xz.n_terms))
-    lib = _ctx().lib
-    gxz = gxx = None
-    args = (_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(var_x), _lib.dptr(mean_x), nk, _lib.dptr(nbuf), zk,
-            _lib.dptr(zbuf), _lib.dptr(yv), _lib.dptr(out), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn), _lib.dptr(gv),
-            _lib.dptr(gzn), _lib.dptr(gcz), _lib.dptr(gsz), _lib.dptr(gcx), _lib.dptr(gsx))
-    pz = px = None
-    if inputs:
-        gxz = [np.zeros(a.shape, order="F") for a in zz.inputs]
-        gxx = [np.zeros(a.shape, order="F") for a in xz.inputs]
-        pz = (C.POINTER(C.c_double) * max(1, len(gxz)))(*[_lib.dptr(a) for a in gxz])
-        px = (C.POINTER(C.c_double) * max(1, len(gxx)))(*[_lib.dptr(a) for a in gxx])
-    srz = srx = scx = None
+    specs, head = _elbo_grad_specs(vfe, fx, y)
+    _refuse_patch_gradient(*specs)
+    _refuse_product_gradient("elbo_and_gradient", *specs)
+    F = _elbo_grad_frame(specs, head)
+    lib, args, dargs = _ctx().lib, F["args"], F["dargs"]
+    # (inputs: var(f, x) depends on x wherever a diagonal term reads two different views of x; scales: and on sigma(x):
+    # var_i = sum_t coef rs_i cs_i k_t)
+    (gxz, pz), (gxx, px), (gdx, pd) = [_input_buffers(sp) if inputs else (None, None) for sp in specs]
+    S, (prz, prx, pcx, pdr, pdc) = _elbo_scale_arrays(specs) if scales else (None, [None] * 5)
     if scales:
-        srz, prz = _scale_arrays(zz, "row")
-        srx, prx = _scale_arrays(xz, "row")
-        scx, pcx = _scale_arrays(xz, "col")
         _lib.check(lib.sgp_elbo_grad_xs(*args, pz, px, prz, prx, pcx), "sgp_elbo_grad_xs")
+        rc = lib.sgp_kernelmatrix_diag_grad_xs(*dargs, pd, pdr, pdc)
     elif inputs:
         _lib.check(lib.sgp_elbo_grad_x(*args, pz, px), "sgp_elbo_grad_x")
+        rc = lib.sgp_kernelmatrix_diag_grad_x(*dargs, pd)
     else:
         _lib.check(lib.sgp_elbo_grad(*args), "sgp_elbo_grad")
-    gcd, gsd = np.zeros(max(1, xx.n_terms)), np.zeros(max(1, xx.n_terms))
-    gdx = pd = None
-    if inputs:      # var(f, x) depends on x wherever a diagonal term reads two different views of x
-        gdx = [np.zeros(a.shape, order="F") for a in xx.inputs]
-        pd = (C.POINTER(C.c_double) * max(1, len(gdx)))(*[_lib.dptr(a) for a in gdx])
-    sdr = sdc = None
-    if scales:      # ... and on sigma(x): var_i = sum_t coef rs_i cs_i k_t
-        sdr, pdr = _scale_arrays(xx, "row")
-        sdc, pdc = _scale_arrays(xx, "col")
-        rc = lib.sgp_kernelmatrix_diag_grad_xs(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd,
-                                               pdr, pdc)
-    elif inputs:
-        rc = lib.sgp_kernelmatrix_diag_grad_x(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd)
-    else:
-        rc = lib.sgp_kernelmatrix_diag_grad(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd))
+        rc = lib.sgp_kernelmatrix_diag_grad(*dargs)
     _lib.check(rc, "sgp_kernelmatrix_diag_grad")
-    nb = len(xx.row_len)
-    xx_terms = [r for r in _term_records(xx, gcd, gsd, False) if r["I"] == r["J"]] if nb else []
-    xb = zb = None
-    if inputs:   # chain rule back onto the blocks of fx.x and fz.x
-        zr, _ = chain_input_gradients(zz, gxz)
-        xr, zc = chain_input_gradients(xz, gxx)
-        xd, _ = chain_input_gradients(xx, gdx)
-        xb, zb = [a + b for a, b in zip(xr, xd)], [a + b for a, b in zip(zr, zc)]
-    return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
-                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
-                zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
-                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx,
-                scales=(_scale_records(zz, srz, more=((xz, srx, "row"), (xz, scx, "col"), (xx, sdr, "row"), (xx, sdc, "col")))
-                        if scales else None),
-                _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
-                _specs=dict(zz=zz, xz=xz, xx=xx))
+    return _elbo_grad_result(F, (gxz, gxx, gdx), S)
 
 
 def _patched_inputs(spec):
@@ -1491,47 +1457,15 @@ def elbo_and_gradient_conv(vfe, fx, y=None, inputs=False):
     contexts, no stencil terms."""
     if isinstance(vfe, SparseFiniteGP):
         return elbo_and_gradient_conv(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs)
-    zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
-    n, m = len(fx), len(vfe.fz)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    xx = _prior_spec(fx.f, fx.x)
-    _refuse_conv_family("elbo_and_gradient_conv", zz, xz, xx)
-    _refuse_product_gradient("elbo_and_gradient_conv", zz, xz, xx)
-    var_x = _f64(_kernelmatrix_diag(xx))
-    out = np.zeros(1)
-    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
-    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
-    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
-    gcz, gsz = np.zeros(max(1, zz.n_terms)), np.zeros(max(1, zz.n_terms))
-    gcx, gsx = np.zeros(max(1, xz.n_terms)), np.zeros(max(1, xz.n_terms))
+    specs, head = _elbo_grad_specs(vfe, fx, y)
+    _refuse_conv_family("elbo_and_gradient_conv", *specs)
+    _refuse_product_gradient("elbo_and_gradient_conv", *specs)
+    F = _elbo_grad_frame(specs, head)
     lib = _ctx().conv_grad
-    gxz = gxx = pz = px = None
-    if inputs:
-        gxz = [None if k in _patched_inputs(zz) else np.zeros(a.shape, order="F") for k, a in enumerate(zz.inputs)]
-        gxx = [None if k in _patched_inputs(xz) else np.zeros(a.shape, order="F") for k, a in enumerate(xz.inputs)]
-        pz = (C.POINTER(C.c_double) * max(1, len(gxz)))(*[_lib.dptr(a) for a in gxz])
-        px = (C.POINTER(C.c_double) * max(1, len(gxx)))(*[_lib.dptr(a) for a in gxx])
-    rc = lib.sgp_elbo_grad_conv(_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(var_x), _lib.dptr(mean_x), nk, _lib.dptr(nbuf), zk,
-                                _lib.dptr(zbuf), _lib.dptr(yv), _lib.dptr(out), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn),
-                                _lib.dptr(gv), _lib.dptr(gzn), _lib.dptr(gcz), _lib.dptr(gsz), _lib.dptr(gcx), _lib.dptr(gsx),
-                                pz, px)
-    _lib.check(rc, "sgp_elbo_grad_conv")
-    gcd, gsd = np.zeros(max(1, xx.n_terms)), np.zeros(max(1, xx.n_terms))
-    rc = lib.sgp_kernelmatrix_diag_grad_conv(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd))
-    _lib.check(rc, "sgp_kernelmatrix_diag_grad_conv")
-    nb = len(xx.row_len)
-    xx_terms = [r for r in _term_records(xx, gcd, gsd, False) if r["I"] == r["J"]] if nb else []
-    zb = None
-    if inputs:   # chain rule back onto the blocks of fz.x
-        zr, _ = chain_input_gradients(zz, gxz)
-        _, zc = chain_input_gradients(xz, gxx)
-        zb = [a + b for a, b in zip(zr, zc)]
-    return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=None, z=zb,
-                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
-                zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
-                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx, scales=None,
-                _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
-                _specs=dict(zz=zz, xz=xz, xx=xx))
+    (gxz, pz), (gxx, px) = [_input_buffers(sp) if inputs else (None, None) for sp in specs[:2]]
+    _lib.check(lib.sgp_elbo_grad_conv(*F["args"], pz, px), "sgp_elbo_grad_conv")
+    _lib.check(lib.sgp_kernelmatrix_diag_grad_conv(*F["dargs"]), "sgp_kernelmatrix_diag_grad_conv")
+    return _elbo_grad_result(F, (gxz, gxx, None))
 
 
 def elbo_and_gradient_stencil(vfe, fx, y=None, inputs=False, stencils=False):
@@ -1548,54 +1482,24 @@ def elbo_and_gradient_stencil(vfe, fx, y=None, inputs=False, stencils=False):
     one entry per stencil node, summed over the three places the bound reads it (K(z,z), K(x,z), diag K(x,x))."""
     if isinstance(vfe, SparseFiniteGP):
         return elbo_and_gradient_stencil(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, stencils=stencils)
-    zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
-    n, m = len(fx), len(vfe.fz)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    xx = _prior_spec(fx.f, fx.x)
-    _refuse_stencil_family("elbo_and_gradient_stencil", zz, xz, xx)
-    _refuse_product_gradient("elbo_and_gradient_stencil", zz, xz, xx)
-    var_x = _f64(_kernelmatrix_diag(xx))
-    out = np.zeros(1)
-    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
-    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
-    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
-    gcz, gsz = np.zeros(max(1, zz.n_terms)), np.zeros(max(1, zz.n_terms))
-    gcx, gsx = np.zeros(max(1, xz.n_terms)), np.zeros(max(1, xz.n_terms))
-    lib = _ctx().stencil_grad
-    gxz = gxx = gdx = pz = px = pd = None
-    if inputs:
-        gxz, pz = _input_buffers(zz)
-        gxx, px = _input_buffers(xz)
-        gdx, pd = _input_buffers(xx)     # var(f, x) depends on x wherever a diagonal term reads two different views of x
-    e_args = (_ctx().handle, zz.ref(), xz.ref(), _lib.dptr(var_x), _lib.dptr(mean_x), nk, _lib.dptr(nbuf), zk, _lib.dptr(zbuf),
-              _lib.dptr(yv), _lib.dptr(out), _lib.dptr(gy), _lib.dptr(gm), _lib.dptr(gn), _lib.dptr(gv), _lib.dptr(gzn),
-              _lib.dptr(gcz), _lib.dptr(gsz), _lib.dptr(gcx), _lib.dptr(gsx), pz, px)
-    gcd, gsd = np.zeros(max(1, xx.n_terms)), np.zeros(max(1, xx.n_terms))
+    specs, head = _elbo_grad_specs(vfe, fx, y)
+    _refuse_stencil_family("elbo_and_gradient_stencil", *specs)
+    _refuse_product_gradient("elbo_and_gradient_stencil", *specs)
+    F = _elbo_grad_frame(specs, head)
+    zz, xz, xx = specs
+    # (var(f, x) depends on x wherever a diagonal term reads two different views of x)
+    (gxz, pz), (gxx, px), (gdx, pd) = [_input_buffers(sp) if inputs else (None, None) for sp in specs]
     if stencils:
         wo = _ctx().stencil_wo
         tz, tx, td = _stencil_tables(zz), _stencil_tables(xz), _stencil_tables(xx)
-        _lib.check(wo.sgp_elbo_grad_stencil_wo(*e_args, tz[2], tz[3], tx[2], tx[3]), "sgp_elbo_grad_stencil_wo")
-        rc = wo.sgp_kernelmatrix_diag_grad_stencil_wo(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd,
-                                                      td[2], td[3])
-        _lib.check(rc, "sgp_kernelmatrix_diag_grad_stencil_wo")
+        _lib.check(wo.sgp_elbo_grad_stencil_wo(*F["args"], pz, px, tz[2], tz[3], tx[2], tx[3]), "sgp_elbo_grad_stencil_wo")
+        _lib.check(wo.sgp_kernelmatrix_diag_grad_stencil_wo(*F["dargs"], pd, td[2], td[3]),
+                   "sgp_kernelmatrix_diag_grad_stencil_wo")
     else:
-        _lib.check(lib.sgp_elbo_grad_stencil(*e_args), "sgp_elbo_grad_stencil")
-        rc = lib.sgp_kernelmatrix_diag_grad_stencil(_ctx().handle, xx.ref(), _lib.dptr(gv), _lib.dptr(gcd), _lib.dptr(gsd), pd)
-        _lib.check(rc, "sgp_kernelmatrix_diag_grad_stencil")
-    nb = len(xx.row_len)
-    xx_terms = [r for r in _term_records(xx, gcd, gsd, False) if r["I"] == r["J"]] if nb else []
-    xb = zb = None
-    if inputs:   # chain rule back onto the blocks of fx.x and fz.x
-        zr, _ = chain_input_gradients(zz, gxz)
-        xr, zc = chain_input_gradients(xz, gxx)
-        xd, _ = chain_input_gradients(xx, gdx)
-        xb, zb = [a + b for a, b in zip(xr, xd)], [a + b for a, b in zip(zr, zc)]
-    rec = dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
-               z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
-               zz_terms=_term_records(zz, gcz, gsz, True), xz_terms=_term_records(xz, gcx, gsx, False),
-               xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx, scales=None,
-               _raw=dict(zz=(gcz, gsz), xz=(gcx, gsx), xx=(gcd, gsd)),
-               _specs=dict(zz=zz, xz=xz, xx=xx))
+        lib = _ctx().stencil_grad
+        _lib.check(lib.sgp_elbo_grad_stencil(*F["args"], pz, px), "sgp_elbo_grad_stencil")
+        _lib.check(lib.sgp_kernelmatrix_diag_grad_stencil(*F["dargs"], pd), "sgp_kernelmatrix_diag_grad_stencil")
+    rec = _elbo_grad_result(F, (gxz, gxx, gdx))
     if stencils:
         nodes = {}
         for key, sp, tb in (("zz_terms", zz, tz), ("xz_terms", xz, tx), ("xx_terms", xx, td)):
@@ -1614,64 +1518,20 @@ def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):
     Single-GPU contexts; no patch / stencil terms."""
     if isinstance(vfe, SparseFiniteGP):
         return elbo_and_gradient_param(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, scales=scales)
-    zz, xz, mean_x, nk, nbuf, zk, zbuf = _vfe_args(vfe, fx)
-    n, m = len(fx), len(vfe.fz)
-    yv = _f64(np.asarray(y, dtype=np.float64).ravel())
-    xx = _prior_spec(fx.f, fx.x)
-    _refuse_param_family("elbo_and_gradient_param", zz, xz, xx)
-    var_x = _f64(_kernelmatrix_diag(xx))
-    out = np.zeros(1)
-    gy, gm, gv = np.zeros(n), np.zeros(n), np.zeros(n)
-    gn = np.zeros(n if nk == _lib.NOISE_DIAG else 1)
-    gzn = np.zeros((m, m), order="F") if zk == _lib.NOISE_DENSE else np.zeros(m if zk == _lib.NOISE_DIAG else 1)
-    gcz, gsz, gpz = (np.zeros(max(1, zz.n_terms)) for _ in range(3))
-    gcx, gsx, gpx = (np.zeros(max(1, xz.n_terms)) for _ in range(3))
-    gcd, gsd, gpd = (np.zeros(max(1, xx.n_terms)) for _ in range(3))
+    specs, head = _elbo_grad_specs(vfe, fx, y)
+    _refuse_param_family("elbo_and_gradient_param", *specs)
+    F = _elbo_grad_frame(specs, head, per_term=3)
     lib = _ctx().kprod_grad
-    gxz = gxx = gdx = pz = px = pd = None
+    # (var(f, x) depends on x where a factor reads two views)
+    (gxz, pz), (gxx, px), (gdx, pd) = gin = [_input_buffers(sp) if inputs else (None, None) for sp in specs]
+    S, (prz, prx, pcx, pdr, pdc) = _elbo_scale_arrays(specs) if scales else (None, [None] * 5)
+    _lib.check(lib.sgp_elbo_grad_param(*F["args"], pz, px, prz, prx, pcx), "sgp_elbo_grad_param")
+    _lib.check(lib.sgp_kernelmatrix_diag_grad_param(*F["dargs"], pd, pdr, pdc), "sgp_kernelmatrix_diag_grad_param")
+    rec = _elbo_grad_result(F, (gxz, gxx, gdx), S)
     if inputs:
-        gxz = [np.zeros(a.shape, order="F") for a in zz.inputs]
-        gxx = [np.zeros(a.shape, order="F") for a in xz.inputs]
-        gdx = [np.zeros(a.shape, order="F") for a in xx.inputs]     # var(f, x) depends on x where a factor reads two views
-        pz = (C.POINTER(C.c_double) * max(1, len(gxz)))(*[_lib.dptr(a) for a in gxz])
-        px = (C.POINTER(C.c_double) * max(1, len(gxx)))(*[_lib.dptr(a) for a in gxx])
-        pd = (C.POINTER(C.c_double) * max(1, len(gdx)))(*[_lib.dptr(a) for a in gdx])
-    srz = srx = scx = sdr = sdc = prz = prx = pcx = pdr = pdc = None
-    if scales:
-        srz, prz = _scale_arrays(zz, "row")
-        srx, prx = _scale_arrays(xz, "row")
-        scx, pcx = _scale_arrays(xz, "col")
-        sdr, pdr = _scale_arrays(xx, "row")
-        sdc, pdc = _scale_arrays(xx, "col")
-    d = _lib.dptr
-    rc = lib.sgp_elbo_grad_param(_ctx().handle, zz.ref(), xz.ref(), d(var_x), d(mean_x), nk, d(nbuf), zk, d(zbuf), d(yv),
-                                 d(out), d(gy), d(gm), d(gn), d(gv), d(gzn), d(gcz), d(gsz), d(gpz), d(gcx), d(gsx), d(gpx),
-                                 pz, px, prz, prx, pcx)
-    _lib.check(rc, "sgp_elbo_grad_param")
-    rc = lib.sgp_kernelmatrix_diag_grad_param(_ctx().handle, xx.ref(), d(gv), d(gcd), d(gsd), d(gpd), pd, pdr, pdc)
-    _lib.check(rc, "sgp_kernelmatrix_diag_grad_param")
-    nb = len(xx.row_len)
-    xx_all = _term_records_kprod(xx, gcd, gsd, gpd, False) if nb else []
-    zz_terms, xz_terms = _term_records_kprod(zz, gcz, gsz, gpz, True), _term_records_kprod(xz, gcx, gsx, gpx, False)
-    if inputs:
-        _attach_d_transform(zz_terms, zz, gxz)
-        _attach_d_transform(xz_terms, xz, gxx)
-        _attach_d_transform(xx_all, xx, gdx)
-    xx_terms = [r for r in xx_all if r["I"] == r["J"]]
-    xb = zb = None
-    if inputs:   # chain rule back onto the blocks of fx.x and fz.x, through every factor's own view
-        zr, _ = chain_input_gradients(zz, gxz)
-        xr, zc = chain_input_gradients(xz, gxx)
-        xd, _ = chain_input_gradients(xx, gdx)
-        xb, zb = [a + b for a, b in zip(xr, xd)], [a + b for a, b in zip(zr, zc)]
-    return dict(elbo=float(out[0]), y=gy, mean=gm, noise=(gn if nk == _lib.NOISE_DIAG else float(gn[0])), x=xb, z=zb,
-                z_noise=(gzn if zk != _lib.NOISE_SCALAR else float(gzn[0])), var=gv,
-                zz_terms=zz_terms, xz_terms=xz_terms,
-                xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx,
-                scales=(_scale_records(zz, srz, more=((xz, srx, "row"), (xz, scx, "col"), (xx, sdr, "row"), (xx, sdc, "col")))
-                        if scales else None),
-                _raw=dict(zz=(gcz, gsz, gpz), xz=(gcx, gsx, gpx), xx=(gcd, gsd, gpd)),
-                _specs=dict(zz=zz, xz=xz, xx=xx))
+        for key, sp, (g, _) in zip(("zz_terms", "xz_terms", "xx_terms"), specs, gin):
+            _attach_d_transform(rec[key], sp, g)
+    return rec
 
 
 class ApproxPosteriorGP:

@@ -9,26 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from functools import partial
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi.so")
-BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_bench.so")
-BATCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_batch.so")
-POOL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_pool.so")
-EXTEND_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend.so")
-EXTEND_BENCH_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_extend_bench.so")
-POSTFX_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_postfx.so")
-PREDGRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_predgrad.so")
-VFE_UPDATE_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_vfe_update.so")
-CONV_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv.so")
-CONV_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_conv_grad.so")
-STENCIL_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil.so")
-STENCIL_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil_grad.so")
-STENCIL_WO_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_stencil_wo.so")
-KPROD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod.so")
-KPROD_GRAD_LIB_PATH = os.path.join(_HERE, "csrc", "libsthenomi_kprod_grad.so")
 
 # kernel kinds / noise kinds (sthenomi.h enums)
 SE, MATERN12, MATERN32, MATERN52, WHITE, CONST = range(6)
@@ -173,8 +159,7 @@ _SIGS = {
     "sgp_dev_rows_dot": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "sgp_dev_rows_gram": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
 }
-# include/sthenomi_bench.h: micro-benchmark / diagnosis / test hooks, exported by libsthenomi_bench.so (round 6), NOT by the product
-# library -- bench.py, tools/ and the GPU tests reach them through bench_lib() / Context.bench
+
 _SIGS_BENCH = {
     "sgp_bench_df_fallbacks": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "sgp_bench_multi_fault": (C.c_int, [_P, C.c_int, C.c_int64]),
@@ -190,17 +175,13 @@ _SIGS_BENCH = {
     "sgp_bench_gemm": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _D, _D]),
 }
 
-# include/sthenomi_batch.h: the batched gradient, exported by libsthenomi_batch.so (it links against the product library and
-# works on its contexts) -- the host mirror reaches it through batch_lib() / Context.batch
 _SIGS_BATCH = {
     "sgp_logpdf_grad_batch": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(sgp_cov_spec)), C.POINTER(_D), C.c_int,
                                         C.POINTER(_D), C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D),
                                         C.POINTER(_D), C.POINTER(_D), C.POINTER(C.c_int)]),
 }
 
-# include/sthenomi_pool.h: independent models of DIFFERENT sizes and noise kinds in one call, exported by libsthenomi_pool.so
-# (it links against the product library and works on its contexts) -- the host mirror reaches it through pool_lib() /
-# Context.pool
+
 class sgp_pool_report(C.Structure):
     _fields_ = [("pool_launches", C.c_int32), ("pooled_members", C.c_int32), ("single_members", C.c_int32),
                 ("distinct_sizes", C.c_int32)]
@@ -214,14 +195,10 @@ _SIGS_POOL = {
                                        C.POINTER(_D), C.POINTER(_D), C.POINTER(C.c_int), C.POINTER(sgp_pool_report)]),
 }
 
-# include/sthenomi_extend.h: extending a kept factor with new data, exported by libsthenomi_extend.so (it links against the
-# product library and works on its posteriors) -- update_posterior reaches it through extend_lib() / Context.extend
 _SIGS_EXTEND = {
     "sgp_posterior_extend": (C.c_int, [_P, C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, C.c_int64, C.c_int64, _D, _D]),
 }
 
-# include/sthenomi_postfx.h: rand / logpdf of a posterior FiniteGP against the kept factor, exported by libsthenomi_postfx.so (it
-# links against the product library and works on its posteriors) -- rand / logpdf reach it through postfx_lib() / Context.postfx
 _POSTFX_RAND = (C.c_int, [_P, C.POINTER(sgp_cov_spec), C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, C.c_int64, C.c_int64, _D,
                           C.c_int64])
 _POSTFX_LOGPDF = (C.c_int, [_P, C.POINTER(sgp_cov_spec), C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, C.c_int64, C.c_int64, _D])
@@ -232,10 +209,7 @@ _SIGS_POSTFX = {
     "sgp_sparse_posterior_logpdf": _POSTFX_LOGPDF,
 }
 
-# include/sthenomi_predgrad.h: posterior mean and variance with their gradients with respect to the test points, exported by
-# libsthenomi_predgrad.so (it links against the product library and works on its posteriors) -- mean_and_var_and_gradient
-# reaches it through predgrad_lib() / Context.predgrad
-PREDGRAD_COL_CHUNK = 512                           # SGP_PREDGRAD_COL_CHUNK
+PREDGRAD_COL_CHUNK = 512                           # SGP_PREDGRAD_COL_CHUNK (include/sthenomi_predgrad.h)
 _PREDGRAD = (C.c_int, [_P, C.POINTER(sgp_cov_spec), C.POINTER(sgp_cov_spec), _D, _D, _D, C.POINTER(_D), C.POINTER(_D),
                        C.POINTER(_D)])
 _SIGS_PREDGRAD = {
@@ -243,21 +217,16 @@ _SIGS_PREDGRAD = {
     "sgp_sparse_posterior_predict_grad_x": _PREDGRAD,
 }
 
-# include/sthenomi_vfe_update.h: new data into a kept sparse (VFE) posterior, exported by libsthenomi_vfe_update.so (it links
-# against the product library and works on its posteriors) -- update_posterior reaches it through vfe_update_lib() / Context.vfe_update
 _SIGS_VFE_UPDATE = {
     "sgp_sparse_posterior_update": (C.c_int, [_P, C.POINTER(sgp_cov_spec), _D, _D, C.c_int, _D, _D, _D]),
     "sgp_sparse_posterior_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
 }
 
-# include/sthenomi_extend_bench.h: the measurement hook of the extension (libsthenomi_extend_bench.so; tools and tests only)
 _SIGS_EXTEND_BENCH = {
     "sgp_bench_extend_row_solve": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D]),
 }
 
 
-# include/sthenomi_conv.h: patch-geometry registration, exported by libsthenomi_conv.so (it links against the product library
-# and works on its contexts) -- Spec.bind reaches it through conv_lib()
 class sgp_patch_geom(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("patch_h", C.c_int32), ("patch_w", C.c_int32)]
 
@@ -270,8 +239,6 @@ _SIGS_CONV = {
 STENCIL_MAX_POINTS, STENCIL_MAX_DIM = 64, 16      # include/sthenomi_stencil.h: the limits of a stencil
 
 
-# include/sthenomi_stencil.h: stencil registration, exported by libsthenomi_stencil.so (links against the product library and
-# works on its contexts) -- Spec.bind reaches it through stencil_lib()
 class sgp_stencil(C.Structure):
     _fields_ = [("dim", C.c_int32), ("npoints", C.c_int32), ("offsets", C.POINTER(C.c_double)),
                 ("weights", C.POINTER(C.c_double))]
@@ -282,17 +249,11 @@ _SIGS_STENCIL = {
 }
 
 
-# include/sthenomi_kprod.h: the parameter gradient through product chains and plain terms alike, exported by
-# libsthenomi_kprod.so (links against the product library and works on its contexts) -- logpdf_and_gradient reaches it through
-# kprod_lib()
 _SIGS_KPROD = {
     "sgp_logpdf_grad_param": (C.c_int, [_P, C.POINTER(sgp_cov_spec), _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
 }
 
 
-# include/sthenomi_kprod_grad.h: the supersets of sgp_logpdf_grad_xs / sgp_kernelmatrix_diag_grad_xs / sgp_elbo_grad_xs that carry
-# product chains and return d / d param, exported by libsthenomi_kprod_grad.so -- logpdf_and_gradient_param and
-# elbo_and_gradient_param reach them through kprod_grad_lib() / Context.kprod_grad
 _SPEC = C.POINTER(sgp_cov_spec)
 _DD = C.POINTER(_D)
 _SIGS_KPROD_GRAD = {
@@ -303,9 +264,6 @@ _SIGS_KPROD_GRAD = {
 }
 
 
-# include/sthenomi_conv_grad.h: sgp_logpdf_grad / sgp_kernelmatrix_diag_grad / sgp_elbo_grad_x with patch terms carried through,
-# exported by libsthenomi_conv_grad.so -- logpdf_and_gradient_conv and elbo_and_gradient_conv reach them through
-# conv_grad_lib() / Context.conv_grad
 _SIGS_CONV_GRAD = {
     "sgp_logpdf_grad_conv": (C.c_int, [_P, _SPEC, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D]),
     "sgp_kernelmatrix_diag_grad_conv": (C.c_int, [_P, _SPEC, _D, _D, _D]),
@@ -314,9 +272,6 @@ _SIGS_CONV_GRAD = {
 }
 
 
-# include/sthenomi_stencil_grad.h: the same three with stencil terms carried through and the input points on both sides, exported
-# by libsthenomi_stencil_grad.so -- logpdf_and_gradient_stencil and elbo_and_gradient_stencil reach them through
-# stencil_grad_lib() / Context.stencil_grad
 _SIGS_STENCIL_GRAD = {
     "sgp_logpdf_grad_stencil": (C.c_int, [_P, _SPEC, _D, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _DD]),
     "sgp_kernelmatrix_diag_grad_stencil": (C.c_int, [_P, _SPEC, _D, _D, _D, _DD]),
@@ -325,15 +280,6 @@ _SIGS_STENCIL_GRAD = {
 }
 
 
-def stencil_grad_symbols():
-    """Names include/sthenomi_stencil_grad.h declares: the entry points of libsthenomi_stencil_grad.so."""
-    return sorted(_SIGS_STENCIL_GRAD)
-
-
-# include/sthenomi_stencil_wo.h: the same three plus the gradients with respect to the stencils' own weights and offsets (two
-# tables of 2 pointers per term; the ELBO: one pair for zz, one for xz), exported by libsthenomi_stencil_wo.so --
-# logpdf_and_gradient_stencil(..., stencils=True) and elbo_and_gradient_stencil(..., stencils=True) reach them through
-# stencil_wo_lib() / Context.stencil_wo
 _SIGS_STENCIL_WO = {
     "sgp_logpdf_grad_stencil_wo": (C.c_int, _SIGS_STENCIL_GRAD["sgp_logpdf_grad_stencil"][1] + [_DD, _DD]),
     "sgp_kernelmatrix_diag_grad_stencil_wo": (C.c_int, _SIGS_STENCIL_GRAD["sgp_kernelmatrix_diag_grad_stencil"][1] + [_DD, _DD]),
@@ -341,64 +287,75 @@ _SIGS_STENCIL_WO = {
 }
 
 
-def stencil_wo_symbols():
-    """Names include/sthenomi_stencil_wo.h declares: the entry points of libsthenomi_stencil_wo.so."""
-    return sorted(_SIGS_STENCIL_WO)
+# The sibling libraries, one row each: family name -> the signatures of libsthenomi_<name>.so, which exports exactly
+# include/sthenomi_<name>.h, links against the product library and works on its contexts and posteriors.  family_lib(name)
+# loads one; the host mirror reaches it through Context.<name> (or <name>_lib()).
+FAMILIES = {
+    # micro-benchmark / diagnosis / test hooks, NOT product: only bench.py, tools/ and the GPU tests load it
+    "bench": _SIGS_BENCH,
+    # the batched gradient: logpdf_and_gradient_batch
+    "batch": _SIGS_BATCH,
+    # independent models of DIFFERENT sizes and noise kinds in one call: logpdf_pool / logpdf_and_gradient_pool
+    "pool": _SIGS_POOL,
+    # patch-geometry registration: Spec.bind, through conv_lib()
+    "conv": _SIGS_CONV,
+    # sgp_logpdf_grad / sgp_kernelmatrix_diag_grad / sgp_elbo_grad_x with patch terms carried through:
+    # logpdf_and_gradient_conv / elbo_and_gradient_conv
+    "conv_grad": _SIGS_CONV_GRAD,
+    # stencil registration: Spec.bind, through stencil_lib()
+    "stencil": _SIGS_STENCIL,
+    # the same three with stencil terms carried through and the input points on both sides:
+    # logpdf_and_gradient_stencil / elbo_and_gradient_stencil
+    "stencil_grad": _SIGS_STENCIL_GRAD,
+    # ... plus the gradients with respect to the stencils' own weights and offsets (two tables of 2 pointers per term; the
+    # ELBO: one pair for zz, one for xz): the same two functions with stencils=True
+    "stencil_wo": _SIGS_STENCIL_WO,
+    # the parameter gradient through product chains and plain terms alike: logpdf_and_gradient
+    "kprod": _SIGS_KPROD,
+    # the supersets of sgp_logpdf_grad_xs / sgp_kernelmatrix_diag_grad_xs / sgp_elbo_grad_xs that carry product chains and
+    # return d / d param: logpdf_and_gradient_param / elbo_and_gradient_param
+    "kprod_grad": _SIGS_KPROD_GRAD,
+    # extending a kept factor with new data: update_posterior
+    "extend": _SIGS_EXTEND,
+    # the measurement hook of the extension, NOT product: tools and tests only
+    "extend_bench": _SIGS_EXTEND_BENCH,
+    # rand / logpdf of a posterior FiniteGP against the kept factor
+    "postfx": _SIGS_POSTFX,
+    # posterior mean and variance with their gradients with respect to the test points: mean_and_var_and_gradient
+    "predgrad": _SIGS_PREDGRAD,
+    # new data into a kept sparse (VFE) posterior: update_posterior
+    "vfe_update": _SIGS_VFE_UPDATE,
+}
+_family_libs = {}
 
 
-def conv_grad_symbols():
-    """Names include/sthenomi_conv_grad.h declares: the entry points of libsthenomi_conv_grad.so."""
-    return sorted(_SIGS_CONV_GRAD)
+def family_path(name):
+    """Where libsthenomi_<name>.so is built: beside the product library."""
+    return os.path.join(_HERE, "csrc", f"libsthenomi_{name}.so")
 
 
-def kprod_grad_symbols():
-    """Names include/sthenomi_kprod_grad.h declares: the entry points of libsthenomi_kprod_grad.so."""
-    return sorted(_SIGS_KPROD_GRAD)
+def family_symbols(name):
+    """Names include/sthenomi_<name>.h declares: the entry points of libsthenomi_<name>.so."""
+    return sorted(FAMILIES[name])
 
 
-def kprod_symbols():
-    """Names include/sthenomi_kprod.h declares: the entry points of libsthenomi_kprod.so."""
-    return sorted(_SIGS_KPROD)
-
-
-def stencil_symbols():
-    """Names include/sthenomi_stencil.h declares: the entry points of libsthenomi_stencil.so."""
-    return sorted(_SIGS_STENCIL)
-
-
-def conv_symbols():
-    """Names include/sthenomi_conv.h declares: the entry points of libsthenomi_conv.so."""
-    return sorted(_SIGS_CONV)
-
-
-def extend_symbols():
-    """Names include/sthenomi_extend.h declares: the entry points of libsthenomi_extend.so."""
-    return sorted(_SIGS_EXTEND)
-
-
-def postfx_symbols():
-    """Names include/sthenomi_postfx.h declares: the entry points of libsthenomi_postfx.so."""
-    return sorted(_SIGS_POSTFX)
-
-
-def predgrad_symbols():
-    """Names include/sthenomi_predgrad.h declares: the entry points of libsthenomi_predgrad.so."""
-    return sorted(_SIGS_PREDGRAD)
-
-
-def vfe_update_symbols():
-    """Names include/sthenomi_vfe_update.h declares: the entry points of libsthenomi_vfe_update.so."""
-    return sorted(_SIGS_VFE_UPDATE)
-
-
-def batch_symbols():
-    """Names include/sthenomi_batch.h declares: the entry points of libsthenomi_batch.so."""
-    return sorted(_SIGS_BATCH)
-
-
-def pool_symbols():
-    """Names include/sthenomi_pool.h declares: the entry points of libsthenomi_pool.so."""
-    return sorted(_SIGS_POOL)
+def family_lib(name):
+    """dlopen libsthenomi_<name>.so (include/sthenomi_<name>.h) after the product library it links against, and type its
+    symbols; one handle per family."""
+    sigs = FAMILIES[name]
+    load()
+    with _lib_lock:
+        if name not in _family_libs:
+            path = family_path(name)
+            if not os.path.exists(path):
+                raise SthenoMIError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
+            for sym, (res, args) in sigs.items():
+                fn = getattr(lib, sym)
+                fn.restype = res
+                fn.argtypes = args
+            _family_libs[name] = lib
+        return _family_libs[name]
 
 
 def exported_symbols():
@@ -406,326 +363,27 @@ def exported_symbols():
     return sorted(_SIGS)
 
 
-def bench_symbols():
-    """Names include/sthenomi_bench.h declares: the entry points of libsthenomi_bench.so."""
-    return sorted(_SIGS_BENCH)
+def _names(name):
+    return family_path(name), partial(family_lib, name), partial(family_symbols, name)
 
 
-_bench = None
-
-
-def bench_lib():
-    """dlopen libsthenomi_bench.so (micro-benchmarks, diagnosis and test hooks: include/sthenomi_bench.h).  It links against
-    the product library and works on contexts created there; nothing on a product path loads it."""
-    global _bench
-    load()
-    with _lib_lock:
-        if _bench is not None:
-            return _bench
-        if not os.path.exists(BENCH_LIB_PATH):
-            raise SthenoMIError(f"{BENCH_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(BENCH_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_BENCH.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bench = lib
-        return lib
-
-
-_batch = None
-
-
-def batch_lib():
-    """dlopen libsthenomi_batch.so (include/sthenomi_batch.h) after the product library it links against."""
-    global _batch
-    load()
-    with _lib_lock:
-        if _batch is not None:
-            return _batch
-        if not os.path.exists(BATCH_LIB_PATH):
-            raise SthenoMIError(f"{BATCH_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(BATCH_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_BATCH.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _batch = lib
-        return lib
-
-
-_pool = None
-
-
-def pool_lib():
-    """dlopen libsthenomi_pool.so (include/sthenomi_pool.h) after the product library it links against."""
-    global _pool
-    load()
-    with _lib_lock:
-        if _pool is not None:
-            return _pool
-        if not os.path.exists(POOL_LIB_PATH):
-            raise SthenoMIError(f"{POOL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(POOL_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_POOL.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _pool = lib
-        return lib
-
-
-_extend = None
-
-
-def extend_lib():
-    """dlopen libsthenomi_extend.so (include/sthenomi_extend.h) after the product library it links against."""
-    global _extend
-    load()
-    with _lib_lock:
-        if _extend is not None:
-            return _extend
-        if not os.path.exists(EXTEND_LIB_PATH):
-            raise SthenoMIError(f"{EXTEND_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(EXTEND_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_EXTEND.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _extend = lib
-        return lib
-
-
-_vfe_update = None
-
-
-def vfe_update_lib():
-    """dlopen libsthenomi_vfe_update.so (include/sthenomi_vfe_update.h) after the product library it links against."""
-    global _vfe_update
-    load()
-    with _lib_lock:
-        if _vfe_update is not None:
-            return _vfe_update
-        if not os.path.exists(VFE_UPDATE_LIB_PATH):
-            raise SthenoMIError(
-                f"{VFE_UPDATE_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(VFE_UPDATE_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_VFE_UPDATE.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _vfe_update = lib
-        return lib
-
-
-_postfx = None
-
-
-def postfx_lib():
-    """dlopen libsthenomi_postfx.so (include/sthenomi_postfx.h) after the product library it links against."""
-    global _postfx
-    load()
-    with _lib_lock:
-        if _postfx is not None:
-            return _postfx
-        if not os.path.exists(POSTFX_LIB_PATH):
-            raise SthenoMIError(f"{POSTFX_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(POSTFX_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_POSTFX.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _postfx = lib
-        return lib
-
-
-_predgrad = None
-
-
-def predgrad_lib():
-    """dlopen libsthenomi_predgrad.so (include/sthenomi_predgrad.h) after the product library it links against."""
-    global _predgrad
-    load()
-    with _lib_lock:
-        if _predgrad is not None:
-            return _predgrad
-        if not os.path.exists(PREDGRAD_LIB_PATH):
-            raise SthenoMIError(f"{PREDGRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(PREDGRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_PREDGRAD.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _predgrad = lib
-        return lib
-
-
-_extend_bench = None
-
-
-def extend_bench_lib():
-    """dlopen libsthenomi_extend_bench.so (include/sthenomi_extend_bench.h); nothing on a product path loads it."""
-    global _extend_bench
-    load()
-    with _lib_lock:
-        if _extend_bench is not None:
-            return _extend_bench
-        if not os.path.exists(EXTEND_BENCH_LIB_PATH):
-            raise SthenoMIError(f"{EXTEND_BENCH_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(EXTEND_BENCH_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_EXTEND_BENCH.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _extend_bench = lib
-        return lib
-
-
-_conv = None
-
-
-def conv_lib():
-    """dlopen libsthenomi_conv.so (include/sthenomi_conv.h) after the product library it links against."""
-    global _conv
-    load()
-    with _lib_lock:
-        if _conv is not None:
-            return _conv
-        if not os.path.exists(CONV_LIB_PATH):
-            raise SthenoMIError(f"{CONV_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(CONV_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_CONV.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _conv = lib
-        return lib
-
-
-_conv_grad = None
-
-
-def conv_grad_lib():
-    """dlopen libsthenomi_conv_grad.so (include/sthenomi_conv_grad.h) after the product library it links against."""
-    global _conv_grad
-    load()
-    with _lib_lock:
-        if _conv_grad is not None:
-            return _conv_grad
-        if not os.path.exists(CONV_GRAD_LIB_PATH):
-            raise SthenoMIError(f"{CONV_GRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(CONV_GRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_CONV_GRAD.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _conv_grad = lib
-        return lib
-
-
-_stencil_grad = None
-
-
-def stencil_grad_lib():
-    """dlopen libsthenomi_stencil_grad.so (include/sthenomi_stencil_grad.h) after the product library it links against."""
-    global _stencil_grad
-    load()
-    with _lib_lock:
-        if _stencil_grad is not None:
-            return _stencil_grad
-        if not os.path.exists(STENCIL_GRAD_LIB_PATH):
-            raise SthenoMIError(f"{STENCIL_GRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(STENCIL_GRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_STENCIL_GRAD.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _stencil_grad = lib
-        return lib
-
-
-_stencil_wo = None
-
-
-def stencil_wo_lib():
-    """dlopen libsthenomi_stencil_wo.so (include/sthenomi_stencil_wo.h) after the product library it links against."""
-    global _stencil_wo
-    load()
-    with _lib_lock:
-        if _stencil_wo is not None:
-            return _stencil_wo
-        if not os.path.exists(STENCIL_WO_LIB_PATH):
-            raise SthenoMIError(f"{STENCIL_WO_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(STENCIL_WO_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_STENCIL_WO.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _stencil_wo = lib
-        return lib
-
-
-_stencil = None
-
-
-def stencil_lib():
-    """dlopen libsthenomi_stencil.so (include/sthenomi_stencil.h) after the product library it links against."""
-    global _stencil
-    load()
-    with _lib_lock:
-        if _stencil is not None:
-            return _stencil
-        if not os.path.exists(STENCIL_LIB_PATH):
-            raise SthenoMIError(f"{STENCIL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(STENCIL_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_STENCIL.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _stencil = lib
-        return lib
-
-
-_kprod = None
-
-
-def kprod_lib():
-    """dlopen libsthenomi_kprod.so (include/sthenomi_kprod.h) after the product library it links against."""
-    global _kprod
-    load()
-    with _lib_lock:
-        if _kprod is not None:
-            return _kprod
-        if not os.path.exists(KPROD_LIB_PATH):
-            raise SthenoMIError(f"{KPROD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(KPROD_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_KPROD.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _kprod = lib
-        return lib
-
-
-_kprod_grad = None
-
-
-def kprod_grad_lib():
-    """dlopen libsthenomi_kprod_grad.so (include/sthenomi_kprod_grad.h) after the product library it links against."""
-    global _kprod_grad
-    load()
-    with _lib_lock:
-        if _kprod_grad is not None:
-            return _kprod_grad
-        if not os.path.exists(KPROD_GRAD_LIB_PATH):
-            raise SthenoMIError(f"{KPROD_GRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(KPROD_GRAD_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS_KPROD_GRAD.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _kprod_grad = lib
-        return lib
+# the names the families had before the table: aliases of the three routines above (Spec.bind reaches conv_lib /
+# stencil_lib through these module globals at call time, so a test double can stand in for them)
+BENCH_LIB_PATH, bench_lib, bench_symbols = _names("bench")
+BATCH_LIB_PATH, batch_lib, batch_symbols = _names("batch")
+POOL_LIB_PATH, pool_lib, pool_symbols = _names("pool")
+CONV_LIB_PATH, conv_lib, conv_symbols = _names("conv")
+CONV_GRAD_LIB_PATH, conv_grad_lib, conv_grad_symbols = _names("conv_grad")
+STENCIL_LIB_PATH, stencil_lib, stencil_symbols = _names("stencil")
+STENCIL_GRAD_LIB_PATH, stencil_grad_lib, stencil_grad_symbols = _names("stencil_grad")
+STENCIL_WO_LIB_PATH, stencil_wo_lib, stencil_wo_symbols = _names("stencil_wo")
+KPROD_LIB_PATH, kprod_lib, kprod_symbols = _names("kprod")
+KPROD_GRAD_LIB_PATH, kprod_grad_lib, kprod_grad_symbols = _names("kprod_grad")
+EXTEND_LIB_PATH, extend_lib, extend_symbols = _names("extend")
+EXTEND_BENCH_LIB_PATH, extend_bench_lib, extend_bench_symbols = _names("extend_bench")
+POSTFX_LIB_PATH, postfx_lib, postfx_symbols = _names("postfx")
+PREDGRAD_LIB_PATH, predgrad_lib, predgrad_symbols = _names("predgrad")
+VFE_UPDATE_LIB_PATH, vfe_update_lib, vfe_update_symbols = _names("vfe_update")
 
 
 def load():
@@ -794,66 +452,6 @@ class Context:
         self.lib = lib
 
     @property
-    def bench(self):
-        """libsthenomi_bench.so (sthenomi_bench.h): `ctx.bench.sgp_bench_*(ctx.handle, ...)`"""
-        return bench_lib()
-
-    @property
-    def batch(self):
-        """libsthenomi_batch.so (sthenomi_batch.h): `ctx.batch.sgp_logpdf_grad_batch(ctx.handle, ...)`"""
-        return batch_lib()
-
-    @property
-    def pool(self):
-        """libsthenomi_pool.so (sthenomi_pool.h): `ctx.pool.sgp_logpdf_pool(ctx.handle, ...)`"""
-        return pool_lib()
-
-    @property
-    def kprod(self):
-        """libsthenomi_kprod.so (sthenomi_kprod.h): `ctx.kprod.sgp_logpdf_grad_param(ctx.handle, ...)`"""
-        return kprod_lib()
-
-    @property
-    def kprod_grad(self):
-        """libsthenomi_kprod_grad.so (sthenomi_kprod_grad.h): `ctx.kprod_grad.sgp_elbo_grad_param(ctx.handle, ...)`"""
-        return kprod_grad_lib()
-
-    @property
-    def conv_grad(self):
-        """libsthenomi_conv_grad.so (sthenomi_conv_grad.h): `ctx.conv_grad.sgp_logpdf_grad_conv(ctx.handle, ...)`"""
-        return conv_grad_lib()
-
-    @property
-    def stencil_grad(self):
-        """libsthenomi_stencil_grad.so (sthenomi_stencil_grad.h): `ctx.stencil_grad.sgp_logpdf_grad_stencil(ctx.handle, ...)`"""
-        return stencil_grad_lib()
-
-    @property
-    def stencil_wo(self):
-        """libsthenomi_stencil_wo.so (sthenomi_stencil_wo.h): `ctx.stencil_wo.sgp_logpdf_grad_stencil_wo(ctx.handle, ...)`"""
-        return stencil_wo_lib()
-
-    @property
-    def extend(self):
-        """libsthenomi_extend.so (sthenomi_extend.h): `ctx.extend.sgp_posterior_extend(post_handle, ...)`"""
-        return extend_lib()
-
-    @property
-    def postfx(self):
-        """libsthenomi_postfx.so (sthenomi_postfx.h): `ctx.postfx.sgp_posterior_logpdf(post_handle, ...)`"""
-        return postfx_lib()
-
-    @property
-    def predgrad(self):
-        """libsthenomi_predgrad.so (sthenomi_predgrad.h): `ctx.predgrad.sgp_posterior_predict_grad_x(post_handle, ...)`"""
-        return predgrad_lib()
-
-    @property
-    def vfe_update(self):
-        """libsthenomi_vfe_update.so (sthenomi_vfe_update.h): `ctx.vfe_update.sgp_sparse_posterior_update(post_handle, ...)`"""
-        return vfe_update_lib()
-
-    @property
     def ndev(self):
         return int(self.lib.sgp_ctx_ndev(self.handle))
 
@@ -883,6 +481,14 @@ class Context:
         except Exception:
             pass
 
+
+def _family_property(name):
+    return property(lambda self: family_lib(name),
+                    doc=f"libsthenomi_{name}.so (sthenomi_{name}.h): `ctx.{name}.sgp_...(ctx.handle or a posterior's, ...)`")
+
+
+for _name in FAMILIES:
+    setattr(Context, _name, _family_property(_name))
 
 _default_ctx = None
 
