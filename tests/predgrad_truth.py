@@ -14,6 +14,7 @@ arithmetic delivers on the same problem.  No LAPACK solve and no numpy.linalg be
   gv[k][:, i] = the same with alpha_j -> -2 B_ij
   gp[k]       = grad_truth.diag_grad(prior_ss, w = 1): the k**_ii part
 Q with B = K* Q (C^-1, or Lz^-T (I - Le^-T Le^-1) Lz^-1) rides along for the tests that bound third derivatives.
+exact_core / sparse_core hold the factorisations, alpha and u: the one computation tests/forward_truth.py shares.
 
 Every sum comes with the sum of the absolute values of its addends (Sn_* = that sum / the number of columns, entry by
 entry, as grad_truth.contract); the error unit is eps = 2^-53 times grad_truth.scale_entries of both.
@@ -87,22 +88,21 @@ def _finish(out, S_cross, S_prior, mean_s, alpha, Bm, Ks, dt):
     return out
 
 
-def predict_grad(S_train, noise_kind, noise, mean, y, S_cross, S_prior, mean_s, dt, cholesky=None):
-    """sgp_posterior_predict_grad_x as documented, in dtype dt"""
+def exact_core(S_train, noise_kind, noise, mean, y, dt, cholesky=None):
+    """C = K + Sigma_y = L L', L^-1, delta = y - m and alpha = L^-T L^-1 delta in dtype dt: the one computation behind
+    predict_grad and tests/forward_truth.py"""
     cholesky = cholesky or T.cholesky
     n = int(sum(S_train["row_len"]))
     C = _sym(T.dense(S_train, dt)) + T.noise_matrix(noise_kind, noise, n, dt)
-    Li = tri_inverse(cholesky(C))
+    Lm = cholesky(C)
+    Li = tri_inverse(Lm)
     delta = np.asarray(y, np.float64).astype(dt) - np.asarray(mean, np.float64).astype(dt)
-    Ci = Li.T @ Li
-    alpha = Li.T @ (Li @ delta)
-    Ks = T.dense(S_cross, dt)
-    return _finish(dict(n=n, Q=Ci), S_cross, S_prior, mean_s, alpha, Ks @ Ci, Ks, dt)
+    z = Li @ delta
+    return dict(n=n, L=Lm, Li=Li, delta=delta, z=z, alpha=Li.T @ z)
 
 
-def sparse_predict_grad(S_zz, z_noise_kind, z_noise, S_xz, noise_kind, noise, mean, y, S_cross, S_prior, mean_s, dt,
-                        cholesky=None):
-    """sgp_sparse_posterior_predict_grad_x as documented, in dtype dt (noise: scalar or diagonal)"""
+def sparse_core(S_zz, z_noise_kind, z_noise, S_xz, noise_kind, noise, mean, y, dt, cholesky=None):
+    """Lz^-1, A, Le, Le^-1, delta, u and alpha of the header's sparse statement in dtype dt (noise: scalar or diagonal)"""
     cholesky = cholesky or T.cholesky
     n, m = int(sum(S_xz["row_len"])), int(sum(S_xz["col_len"]))
     Kzz = _sym(T.dense(S_zz, dt)) + T.noise_matrix(z_noise_kind, z_noise, m, dt)
@@ -111,16 +111,32 @@ def sparse_predict_grad(S_zz, z_noise_kind, z_noise, S_xz, noise_kind, noise, me
     rsig = dt(1) / np.sqrt(sy)
     Lzi = tri_inverse(cholesky(Kzz))
     A = (Lzi @ Kxz.T) * rsig[None, :]
-    Lei = tri_inverse(cholesky(A @ A.T + np.eye(m, dtype=dt)))
+    Le = cholesky(A @ A.T + np.eye(m, dtype=dt))
+    Lei = tri_inverse(Le)
     delta = (np.asarray(y, np.float64).astype(dt) - np.asarray(mean, np.float64).astype(dt)) * rsig
     u = Lei @ (A @ delta)
-    alpha = Lzi.T @ (Lei.T @ u)
+    return dict(n=n, m=m, sy=sy, Lzi=Lzi, A=A, Le=Le, Lei=Lei, delta=delta, u=u, alpha=Lzi.T @ (Lei.T @ u))
+
+
+def predict_grad(S_train, noise_kind, noise, mean, y, S_cross, S_prior, mean_s, dt, cholesky=None):
+    """sgp_posterior_predict_grad_x as documented, in dtype dt"""
+    c = exact_core(S_train, noise_kind, noise, mean, y, dt, cholesky)
+    Ci = c["Li"].T @ c["Li"]
+    Ks = T.dense(S_cross, dt)
+    return _finish(dict(n=c["n"], Q=Ci), S_cross, S_prior, mean_s, c["alpha"], Ks @ Ci, Ks, dt)
+
+
+def sparse_predict_grad(S_zz, z_noise_kind, z_noise, S_xz, noise_kind, noise, mean, y, S_cross, S_prior, mean_s, dt,
+                        cholesky=None):
+    """sgp_sparse_posterior_predict_grad_x as documented, in dtype dt (noise: scalar or diagonal)"""
+    c = sparse_core(S_zz, z_noise_kind, z_noise, S_xz, noise_kind, noise, mean, y, dt, cholesky)
+    Lzi, Lei = c["Lzi"], c["Lei"]
     Ks = T.dense(S_cross, dt)
     Bp = Ks @ Lzi.T
     Cp = Bp @ Lei.T
     Bm = Bp @ Lzi - (Cp @ Lei) @ Lzi
     Q = Lzi.T @ Lzi - (Lzi.T @ Lei.T) @ (Lei @ Lzi)            # B = K* Q
-    return _finish(dict(n=m, Q=Q), S_cross, S_prior, mean_s, alpha, Bm, Ks, dt)
+    return _finish(dict(n=c["m"], Q=Q), S_cross, S_prior, mean_s, c["alpha"], Bm, Ks, dt)
 
 
 def family_units(prefix, out, R):

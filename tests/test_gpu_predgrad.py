@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import forward_truth as FT
 import grad_truth as T
 import predgrad_truth as PT
 import stheno_jl_amd as P
@@ -142,13 +143,25 @@ def prior_part_check(case, g, R):
     assert fig <= 1.0, (case.id, fig)
 
 
-def values_check(s, g, R):
-    """mean and var themselves against the truth, loosely (their bits are pinned to the predict call below): 1e-9 of the
-    absolute sum of their addends"""
-    v_truth = np.asarray(R["var"], dtype=np.float64) + np.asarray(s["fxs"].noise)
-    m_truth = np.asarray(R["mean"], dtype=np.float64)
-    assert np.max(np.abs(g["mean"] - m_truth) / np.asarray(R["S_mean"] + 1, dtype=np.float64)) < 1e-9
-    assert np.max(np.abs(g["var"] - v_truth) / np.asarray(R["S_var"] + 1, dtype=np.float64)) < 1e-9
+def values_check(case, s, g, R, R64):
+    """mean and var themselves against the truth (their bits are pinned to the predict call below) under the post.mean /
+    post.var (spost.*) bound of tests/forward_truth.py: MARGIN * max(the reference's float64 figure on this case, that
+    family's floor), in eps of the scale of the truth; var is the latent variance plus the test noise on both sides"""
+    pre = "spost" if case.sparse else "post"
+    noise = np.asarray(s["fxs"].noise, dtype=np.float64)
+    v_truth = R["var"] + noise.astype(R["var"].dtype)
+    scales = {"mean": T.scale_entries(R["mean"], R["S_mean"] / R["n"]),
+              "var": T.scale_entries(v_truth, (R["S_var"] + np.abs(noise).astype(R["var"].dtype)) / R["n"])}
+
+    def figures(m, v):
+        return {"mean": T.units(m, R["mean"], scales["mean"]), "var": T.units(v, v_truth, scales["var"])}
+
+    dev = figures(g["mean"], g["var"])
+    f64 = GT.yardstick(figures(r["mean"], r["var"] + noise) for r in R64)
+    for key in ("mean", "var"):
+        floor = FT.FLOORS[f"{pre}.{key}"]
+        print(f"{case.id:18s} {pre + '.' + key:15s} device {dev[key]:10.1f}  float64 {f64[key]:10.1f}  floor {floor:8.1f}")
+        assert dev[key] <= FT.MARGIN * max(f64[key], floor), (case.id, key, dev[key], f64[key])
 
 
 @pytest.mark.parametrize("case", ALL_CASES, ids=repr)
@@ -156,7 +169,7 @@ def test_prediction_gradient_against_truth(case):
     s, g, (R, *R64) = run_case(case)
     for v in list(g["inputs_mean"]) + list(g["inputs_var"]) + list(g["inputs_var_prior"]) + [g["mean"], g["var"]]:
         assert not np.any(np.isnan(v))
-    values_check(s, g, R)
+    values_check(case, s, g, R, R64)
     hold(case, device_units(case, g, R), yardstick(case, R, R64))
     prior_part_check(case, g, R)
     if "views" in case.id:

@@ -128,7 +128,7 @@ def test_the_doubles_gradients_are_inside_the_device_bound(case):
     """the GPU file's body on the NumPy double (LAPACK solves): the same verdict function, so that a mistake in the case list,
     the marshalling or the unit bookkeeping shows here and not first on the device"""
     s, g, (R, *R64) = GP.run_case(case)
-    GP.values_check(s, g, R)
+    GP.values_check(case, s, g, R, R64)
     GP.hold(case, GP.device_units(case, g, R), GP.yardstick(case, R, R64))
     GP.prior_part_check(case, g, R)
 
