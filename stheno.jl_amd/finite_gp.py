@@ -1396,7 +1396,10 @@ def _elbo_grad_result(F, gin=(None, None, None), scale_arrs=None):
                 xx_terms=xx_terms, zz_inputs=gxz, xz_inputs=gxx,
                 scales=(_scale_records(zz, S[0], more=((xz, S[1], "row"), (xz, S[2], "col"), (xx, S[3], "row"), (xx, S[4], "col")))
                         if S else None),
-                _raw=raw, _specs=dict(zz=zz, xz=xz, xx=xx))
+                _raw=raw, _specs=dict(zz=zz, xz=xz, xx=xx),
+                # the library's per-term scale arrays (zz rows, xz rows, xz columns, xx rows, xx columns; None without
+                # scales=True) and the diagonal's input arrays, as they came back: what `scales`, `x` and `z` are built from
+                _scale_arrays=S, _xx_inputs=gdx)
 
 
 def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):

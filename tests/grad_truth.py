@@ -277,10 +277,12 @@ def noise_matrix(kind, noise, n, dt):
     return np.asarray(noise, dtype=np.float64).astype(dt)
 
 
-def logpdf_grad(S, noise_kind, noise, mean, y, dt, inputs=False, scales=False, cholesky=None):
+def logpdf_grad(S, noise_kind, noise, mean, y, dt, inputs=False, scales=False, cholesky=None, ops=None):
     """sgp_logpdf_grad_xs as documented, in dtype dt: alpha = C^-1 (y - m), G = (alpha alpha' - C^-1) / 2.
-    `cholesky`: the factorisation to use (default: the column recurrence above)."""
+    `cholesky`: the factorisation to use (default: the column recurrence above).  `ops`: a module whose `dense` and
+    `contract` read another kind of spec (tests/kprod_grad_truth.py: product chains); default: this one."""
     cholesky = cholesky or globals()["cholesky"]
+    dense, contract = (globals()["dense"], globals()["contract"]) if ops is None else (ops.dense, ops.contract)
     n = int(sum(S["row_len"]))
     K = dense(S, dt)
     K = np.tril(K) + np.tril(K, -1).T                   # the lower triangle is the matrix (exactly symmetric)
@@ -310,12 +312,15 @@ def logpdf_grad(S, noise_kind, noise, mean, y, dt, inputs=False, scales=False, c
 
 
 # ---- elbo and its gradient (oracle/abstractgps.py: elbo_gradient_wrt_cov, restated from its docstring) -----------------------
-def elbo_grad(Szz, Sxz, Sxx, noise_kind, noise, z_noise_kind, z_noise, mean, y, dt, inputs=False, cholesky=None):
+def elbo_grad(Szz, Sxz, Sxx, noise_kind, noise, z_noise_kind, z_noise, mean, y, dt, inputs=False, cholesky=None, ops=None):
     """With Lambda = diag(sy)^-1/2, A = Lz^-1 Kzx Lambda, B = A A' + I, delta = Lambda (y - m), u = B^-1 A delta,
     J = Lz^-T:  dA = (I - B^-1 - u u') A + u delta';  dKxz = Lambda dA' Lz^-1;  dKzz = -1/2 J (B + B^-1 - 2 I + u u') J';
     ddelta = -delta + A' u;  dy = Lambda ddelta;  dvar = -1 / (2 sy);
-    dsy = -1/(2 sy) + var/(2 sy^2) - (ddelta delta + diag(A' dA)) / (2 sy)."""
+    dsy = -1/(2 sy) + var/(2 sy^2) - (ddelta delta + diag(A' dA)) / (2 sy).
+    `ops`: as for logpdf_grad, with `diag_of`."""
     cholesky = cholesky or globals()["cholesky"]
+    dense, diag_of, contract = ((globals()["dense"], globals()["diag_of"], globals()["contract"]) if ops is None else
+                                (ops.dense, ops.diag_of, ops.contract))
     n, m = int(sum(Sxz["row_len"])), int(sum(Sxz["col_len"]))
     half, one, two = dt(1) / dt(2), dt(1), dt(2)
     Kzz = dense(Szz, dt)

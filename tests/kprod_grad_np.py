@@ -76,8 +76,12 @@ def np_input_grads(spec, G, pairs=None):
                 continue
             d2 = ((xr[:, :, None] - xc[:, None, :]) ** 2).sum(0)
             Cm = 2.0 * A * kappa_prime(t.kind, d2, t.param)
-            row[t.row_input] += xr * Cm.sum(1)[None, :] - xc @ Cm.T
-            col[t.col_input] += xc * Cm.sum(0)[None, :] - xr @ Cm
+            # (direct differences, coordinate by coordinate, as the library forms them: x_i sum_j C_ij - sum_j C_ij x'_j cancels
+            # where close pairs carry a large kappa' -- general-nu Matern below nu = 1, points on a line)
+            for d in range(xr.shape[0]):
+                E = Cm * (xr[d][:, None] - xc[d][None, :])
+                row[t.row_input][d] += E.sum(1)
+                col[t.col_input][d] -= E.sum(0)
     return dict(row=row, col=col, rs=rs, cs=cs)
 
 

@@ -16,7 +16,7 @@ import kprod_np as kn
 import stheno_jl_amd as P
 from stheno_jl_amd import lib as L
 from test_gpu_kernel_formulas import _pair_at_offsets
-from test_gpu_kprod import _G, _atom, _call, _kernelmatrix_rc, _model, _two_blocks, rel
+from test_gpu_kprod import _G, _atom, _call, _kernelmatrix_rc, _model, _two_blocks, analytic_inscale, rel
 from test_gpu_kprod_grad import _check_against_evaluator, _check_diag, _close, _lp_param_xs, _without_pairs
 from test_gpu_parity import REL
 from test_kprod_grad_on_numpy import titsias
@@ -209,11 +209,12 @@ def _check_terms(g, noise, y):
     G, Cm = _G(spec, noise, y)
     assert abs(g["logpdf"] - np_logpdf(Cm, y)) <= REL * abs(g["logpdf"])
     gc, gs, gp = g["_raw"]
-    ec, es, ep = kn.np_contract(spec, G)
+    ec, _, ep = kn.np_contract(spec, G)
+    es = analytic_inscale(spec, G)
     for t in range(spec.n_terms):
         assert abs(gc[t] - ec[t]) <= 1e-8 * max(1.0, abs(ec[t])), (t, gc[t], ec[t])
         assert abs(gp[t] - ep[t]) <= 1e-8 * max(1.0, abs(ep[t])), (t, gp[t], ep[t])
-        assert abs(gs[t] - es[t]) <= 2e-6 * max(1.0, abs(es[t])), (t, gs[t], es[t])
+        assert abs(gs[t] - es[t]) <= 1e-8 * max(1.0, abs(es[t])), (t, gs[t], es[t])
     kinds = np.array([spec._terms[t].kind & L.KIND_MASK for t in range(spec.n_terms)])
     return kinds, gp[:spec.n_terms]
 

@@ -17,7 +17,7 @@ import matern_nu_truth as mt
 import stheno_jl_amd as P
 from stheno_jl_amd import lib as L
 from test_gpu_kernel_formulas import _pair_at_offsets
-from test_gpu_kprod import _G, _atom, _call, _kernelmatrix_rc, _model, _two_blocks, rel
+from test_gpu_kprod import _G, _atom, _call, _kernelmatrix_rc, _model, _two_blocks, analytic_inscale, rel
 from test_gpu_kprod_grad import _check_against_evaluator, _close
 from test_gpu_parity import REL
 from test_kprod_grad_on_numpy import titsias
@@ -132,7 +132,7 @@ def _grad_case(nu, chained):
 @pytest.mark.parametrize("nu", [0.3, 1.25, 3.7])
 def test_logpdf_gradients_match_the_contractions_of_the_restatement(nu, chained):
     """logpdf_and_gradient_param, N = 150, D = 3: coefficient, input-scale and parameter outputs against kprod_np.np_contract
-    (1e-8, 2e-6, the rule of tests/test_gpu_kprod.py), the point gradients against kprod_grad_np.np_input_grads (the rule of
+    (1e-8; the input scale against the analytic dk / dg of tests/kprod_grad_truth.py, at 1e-8 too), the point gradients against kprod_grad_np.np_input_grads (the rule of
     tests/test_gpu_kprod_grad.py: _check_against_evaluator); grad_param of the kind is exactly 0"""
     F, x, _, y = _grad_case(nu, chained)
     g = P.logpdf_and_gradient_param(F(x, 0.1), y, inputs=True)
@@ -140,11 +140,12 @@ def test_logpdf_gradients_match_the_contractions_of_the_restatement(nu, chained)
     G, Cm = _G(spec, 0.1, y)
     assert abs(g["logpdf"] - np_logpdf(Cm, y)) <= REL * abs(g["logpdf"])
     gc, gs, gp = g["_raw"]
-    ec, es, ep = kn.np_contract(spec, G)
+    ec, _, ep = kn.np_contract(spec, G)
+    es = analytic_inscale(spec, G)
     for t in range(spec.n_terms):
         assert abs(gc[t] - ec[t]) <= 1e-8 * max(1.0, abs(ec[t])), (t, gc[t], ec[t])
         assert abs(gp[t] - ep[t]) <= 1e-8 * max(1.0, abs(ep[t])), (t, gp[t], ep[t])
-        assert abs(gs[t] - es[t]) <= 2e-6 * max(1.0, abs(es[t])), (t, gs[t], es[t])
+        assert abs(gs[t] - es[t]) <= 1e-8 * max(1.0, abs(es[t])), (t, gs[t], es[t])
     kinds = np.array([spec._terms[t].kind & L.KIND_MASK for t in range(spec.n_terms)])
     assert np.sum(kinds == L.MATERN_NU) == 1 and np.all(gp[:spec.n_terms][kinds == L.MATERN_NU] == 0.0)
     assert all(r["d_param"] == 0.0 for r in g["terms"] if r["kind"] == L.MATERN_NU)

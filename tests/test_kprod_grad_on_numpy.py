@@ -3,6 +3,7 @@
 (plain C, exactly what libsthenomi_kprod_grad.so exports and lib.py types), the host functions logpdf_and_gradient_param /
 elbo_and_gradient_param over a NumPy double of the three entry points, and the refusals."""
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -272,8 +273,9 @@ class FakeKprodGrad:
         assert kind == L.NOISE_SCALAR
         Cm = kn.np_spec_matrix(s) + noise[0] * np.eye(n)
         delta = _vec(y, n) - (_vec(mean, n) if mean else 0.0)
-        Ci = np.linalg.inv(Cm)
-        al = Ci @ delta
+        Li = sla.solve_triangular(np.linalg.cholesky(Cm), np.eye(n), lower=True)      # (the library's route: C^-1 = L^-T L^-1)
+        Ci = Li.T @ Li
+        al = Li.T @ (Li @ delta)
         G = 0.5 * (np.outer(al, al) - Ci)
         lp[0] = np_logpdf(Cm, delta)
         _vec(gy, n)[:] = -al
@@ -303,9 +305,9 @@ class FakeKprodGrad:
         assert nk == L.NOISE_SCALAR and zk == L.NOISE_SCALAR
         s2 = noise_x[0]
         v = _vec(var_x, N)
-        delta = (_vec(y, N) - (_vec(mean_x, N) if mean_x else 0.0)) / np.sqrt(s2)
+        resid = _vec(y, N) - (_vec(mean_x, N) if mean_x else 0.0)
         elbo_out[0], (dKzz, dKxz, dy, dsy) = titsias(kn.np_spec_matrix(sz) + z_noise[0] * np.eye(M), kn.np_spec_matrix(sx), v,
-                                                    delta * np.sqrt(s2), s2, cotangents=True)
+                                                    resid, s2, cotangents=True)
         _vec(gy, N)[:] = dy
         _vec(gm, N)[:] = -dy
         gn[0] = dsy
@@ -327,24 +329,27 @@ def titsias(Kzz, Kxz, var_x, y, s2, cotangents=False):
     """the Titsias bound from NumPy matrices (Kzz with its jitter), and its cotangents (oracle/abstractgps.py's derivation)"""
     M, N = Kzz.shape[0], Kxz.shape[0]
     Lz = np.linalg.cholesky(Kzz)
-    A = sla.solve_triangular(Lz, Kxz.T, lower=True) / np.sqrt(s2)
+    Lzi = sla.solve_triangular(Lz, np.eye(M), lower=True)
+    rsig = 1.0 / np.sqrt(s2)                                   # (Lambda = diag(s2)^-1/2, applied as a product)
+    A = (Lzi @ Kxz.T) * rsig                                   # (through Lz^-1, the library's route)
     Bm = A @ A.T + np.eye(M)
     Le = np.linalg.cholesky(Bm)
-    delta = y / np.sqrt(s2)
+    delta = y * rsig
     b = sla.solve_triangular(Le, A @ delta, lower=True)
     val = -0.5 * (N * np.log(2.0 * np.pi) + N * np.log(s2) + 2.0 * np.log(np.diag(Le)).sum() + delta @ delta - b @ b) \
         - 0.5 * (np.sum(var_x) / s2 - np.sum(A * A))
     if not cotangents:
         return float(val)
-    u = sla.cho_solve((Le, True), A @ delta)
-    Binv = sla.cho_solve((Le, True), np.eye(M))
+    Lei = sla.solve_triangular(Le, np.eye(M), lower=True)      # (B^-1 = Le^-T Le^-1, the library's route)
+    u = Lei.T @ b
+    Binv = Lei.T @ Lei
     Z = np.eye(M) - Binv - np.outer(u, u)
     S = Bm + Binv - 2.0 * np.eye(M) + np.outer(u, u)
-    J = sla.solve_triangular(Lz, np.eye(M), lower=True).T
+    J = Lzi.T
     dA_T = A.T @ Z + np.outer(delta, u)
     ddelta = -delta + A.T @ u
     dsy = -0.5 / s2 + 0.5 * var_x / s2 ** 2 - 0.5 * (ddelta * delta + (A.T * dA_T).sum(1)) / s2
-    return float(val), ((-0.5 * J @ S @ J.T), (dA_T @ J.T) / np.sqrt(s2), ddelta / np.sqrt(s2), float(dsy.sum()))
+    return float(val), ((-0.5 * J @ S @ J.T), (dA_T @ J.T) * rsig, ddelta * rsig, float(dsy.sum()))
 
 
 def install_fake(monkeypatch):
