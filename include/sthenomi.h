@@ -52,7 +52,11 @@ enum {
   SGP_COSINE = 16,  /* CosineKernel: cos(pi d), param ignored                            */
   SGP_GAMMAEXP = 17, /* GammaExponentialKernel(gamma): exp(-d^gamma), param = gamma in (0, 2] */
   /* 18 and 19 are no kinds either */
-  SGP_MATERN_NU = 20 /* MaternKernel(nu): 2^(1-nu) / Gamma(nu) x^nu K_nu(x), x = sqrt(2 nu) d, param = nu in (0, 32] */
+  SGP_MATERN_NU = 20, /* MaternKernel(nu): 2^(1-nu) / Gamma(nu) x^nu K_nu(x), x = sqrt(2 nu) d, param = nu in (0, 32] */
+  /* 21 .. 23 are no kinds.  The kinds below are functions of x'y, x'x and y'y, not of the distance alone */
+  SGP_NEURALNET = 24, /* NeuralNetworkKernel: asin(x'y / sqrt((1 + x'x)(1 + y'y))), param ignored */
+  SGP_FBM = 25,       /* FBMKernel(h): (|x|^2h + |y|^2h - |x - y|^2h) / 2, param = h in (0, 1] */
+  SGP_EXPONENTIATED = 26 /* ExponentiatedKernel: exp(x'y), param ignored; 27 and above are no kinds */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -83,7 +87,8 @@ typedef struct {
                          Stencil terms: the same encoding, ids of the same table registered by
                          sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
-  double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu */
+  double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu;
+                         SGP_FBM: h; ignored by the other kinds */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

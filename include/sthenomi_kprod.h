@@ -15,9 +15,10 @@
  *   - every factor names its own row_input / col_input (the factors of one product read differently scaled or transformed
  *     views of the points); the two inputs of a factor have one dimension;
  *   - a continuation has coef == 1.0, NULL row_scale / col_scale and reserved == 0, and is never the first term of a pair;
- *   - the head of a chain, and any term of the kinds SGP_RQ / SGP_LINEAR / SGP_COSINE / SGP_GAMMAEXP / SGP_MATERN_NU (a chain
- *     of length one), has reserved == 0: there are no products with patch or stencil sides.
- * Kinds that exist on this path only (codes 6, 7, 16, 17, 20; 8 .. 15, 18, 19 and everything above 20 are refused as unknown):
+ *   - the head of a chain, and any term of the kinds SGP_RQ / SGP_LINEAR / SGP_COSINE / SGP_GAMMAEXP / SGP_MATERN_NU / SGP_NEURALNET /
+ *     SGP_FBM / SGP_EXPONENTIATED (a chain of length one), has reserved == 0: there are no products with patch or stencil sides.
+ * Kinds that exist on this path only (codes 6, 7, 16, 17, 20, 24, 25, 26; 8 .. 15, 18, 19, 21 .. 23 and everything above 26 are refused as
+ * unknown):
  *   SGP_RQ        param = alpha > 0:  (1 + d^2 / (2 alpha))^-alpha       (RationalQuadraticKernel)
  *   SGP_LINEAR    param = c >= 0:     x'y + c                            (LinearKernel; PolynomialKernel(n, c) is a chain of
  *                                                                         n such factors)
@@ -31,6 +32,25 @@
  *                                                                        (MaternKernel(nu): Euclidean d, as in KernelFunctions and
  *                                                                         scikit-learn; nu = 1/2, 3/2, 5/2 are SGP_MATERN12 / 32 /
  *                                                                         52, which stay the faster closed forms)
+ *   SGP_NEURALNET param ignored:     asin(x'y / sqrt((1 + x'x)(1 + y'y)))       (NeuralNetworkKernel, Williams' arcsine kernel)
+ *   SGP_FBM       param = h, finite and in (0, 1]:  (|x|^2h + |y|^2h - |x - y|^2h) / 2
+ *                                                                        (FBMKernel: fractional Brownian motion; h = 1/2 is the
+ *                                                                         Wiener process on the half line, h = 1 is x'y)
+ *   SGP_EXPONENTIATED param ignored: exp(x'y)                            (ExponentiatedKernel)
+ * The last three are not functions of the distance: they are functions of s = x'y, a = x'x, b = y'y, formed by one fma chain
+ * each in the same order (s == a == b bit for bit where x == y), and of d^2 = |x - y|^2 formed from direct differences, never
+ * as a + b - 2 s.  SGP_NEURALNET is evaluated as atan2(s, R) with R^2 = (1 + a)(1 + b) - s^2 = 1 + a + b + sum_{i<j} (x_i y_j -
+ * x_j y_i)^2 (Lagrange's identity: a sum of squares, D (D - 1) / 2 products, empty and exact at D = 1): asin of a ratio near 1,
+ * and a b - s^2 as a difference, lose several 1e5 units of 2^-53 on nearly parallel points at large norms.  SGP_FBM: a power term
+ * whose base (a, b or d^2) is exactly 0 contributes exactly 0 to the value and to every derivative -- d / dh included
+ * (0^h log 0 := 0), and h < 1/2, where the true point derivative diverges: the subgradient rule GammaExponential and Matern-1/2
+ * have at coincident points.  So FBM is exactly a^h on the diagonal and exactly 0 against the origin.
+ * Range: finite results for |x|^2, |y|^2 <= 1e300 (SGP_NEURALNET, SGP_FBM) and x'y <= 709 (SGP_EXPONENTIATED); SGP_NEURALNET is
+ * ACCURATE only while (1 + x'x)(1 + y'y) is representable (norms up to about 1e77): beyond it the squares of Lagrange's sum
+ * overflow, R is +inf and the kernel and its derivatives come out as 0 -- finite, and wrong (parallel points at norm 1e150 give 0
+ * where the kernel is pi / 2).  Scale such inputs first.  An overflowed
+ * exp is +inf, and the factorisation then reports "not positive definite" like any other such matrix.  Beyond the range the
+ * results are inf or NaN; nothing faults.  Error models: tests/dotkinds_truth.py.
  * General-nu Matern has no library call to lean on: K_nu is evaluated in fp64 by Temme's series (x <= 2) or Steed's second
  * continued fraction (x > 2) at the order mu = nu - n in [-1/2, 1/2), followed by n - 1 steps of the upward recurrence, on
  * quantities scaled by the power of x and by e^x so that nothing overflows or underflows before the last product; what depends
@@ -60,9 +80,14 @@
  *     grad_coef[h]       = sum_ij G_ij rs_i cs_j prod_f k_f        grad_coef[continuation] = 0
  *     grad_inscale[f]    = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != f} k_f') d k_f(g x, g x') / dg at g = 1
  * (LINEAR: 2 x'y;  RQ: -d^2 (1 + d^2 / (2 alpha))^(-alpha - 1);  COSINE: -pi d sin(pi d);  GAMMAEXP: -gamma d^gamma k;
- * MATERN_NU: -C x^(nu+1) K_(nu-1)(x), C = 2^(1-nu) / Gamma(nu)).  With
+ * MATERN_NU: -C x^(nu+1) K_(nu-1)(x), C = 2^(1-nu) / Gamma(nu);  NEURALNET: s (1 / (1 + a) + 1 / (1 + b)) / R;  FBM: 2 h k;
+ * EXPONENTIATED: 2 s k).  With
  * respect to the points a distance kind contributes 2 kappa' (x - x'), kappa' = d k / d (d^2): COSINE -pi sin(pi d) / (2 d),
- * GAMMAEXP -(gamma / 2) d^gamma k / d^2, MATERN_NU -(nu / x) C x^nu K_(nu-1)(x).  The gradients with respect to the points the factors read,
+ * GAMMAEXP -(gamma / 2) d^gamma k / d^2, MATERN_NU -(nu / x) C x^nu K_(nu-1)(x).  The kinds of x'y contribute
+ * d k / d x (row point; the column point's is the same with x and y exchanged):  LINEAR y;  NEURALNET (y - s x / (1 + a)) / R;
+ * FBM h a^(h-1) x - h (d^2)^(h-1) (x - y);  EXPONENTIATED k y.  On the diagonal (sgp_kernelmatrix_diag_grad_param) they follow
+ * LINEAR's convention: the row input receives d k / d x, the column input d k / d y, both added when the two are one array.
+ * The gradients with respect to the points the factors read,
  * to function-valued scales and everything behind the ELBO come from the superset family of include/sthenomi_kprod_grad.h
  * (sgp_logpdf_grad_param_xs, sgp_kernelmatrix_diag_grad_param, sgp_elbo_grad_param; libsthenomi_kprod_grad.so).  The entry points of include/sthenomi.h
  * for those gradients keep refusing chains with rc < 0 and a message naming "product" and the function to call instead:
@@ -86,7 +111,7 @@ extern "C" {
  * one entry per element of spec->terms,
  *     grad_param[t] = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != t} k_f') d k_t / d param
  * with d k / d param = k (u / (1 + u) - log1p(u)), u = d^2 / (2 alpha), for SGP_RQ; d k / d gamma = -k d^gamma log(d^2) / 2 for
- * SGP_GAMMAEXP; 1 for SGP_LINEAR and SGP_CONST; 0 for the kinds without a parameter (SGP_COSINE among them) and for
+ * SGP_GAMMAEXP; d k / d h = (a^h log a + b^h log b - (d^2)^h log d^2) / 2 for SGP_FBM; 1 for SGP_LINEAR and SGP_CONST; 0 for the kinds without a parameter (SGP_COSINE, SGP_NEURALNET and SGP_EXPONENTIATED among them) and for
  * SGP_MATERN_NU, whose nu is held fixed.  Plain terms (outside any chain) get their entries too.  Every other output is bit for bit what
  * sgp_logpdf_grad returns for the same arguments.  Any spec sgp_logpdf_grad takes, on a single-GPU context: a multi-GPU
  * context refuses this entry point (rc < 0) whatever the spec holds, product chains or not. */

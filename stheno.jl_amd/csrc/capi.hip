@@ -308,9 +308,10 @@ extern "C" int sgp_ctx_destroy(sgp_ctx* c) {
 // ---------------------------------------------------------------------------------------
 // device-resident specs
 // ---------------------------------------------------------------------------------------
-// the kinds of include/sthenomi.h: 0 .. 7, 16 / 17 and 20 (8 .. 15, 18, 19 and everything above stay unknown)
+// the kinds of include/sthenomi.h: 0 .. 7, 16 / 17, 20 and 24 .. 26 (8 .. 15, 18, 19, 21 .. 23 and everything above stay unknown)
 static bool kind_known(int k) {
-  return (k >= SGP_SE && k <= SGP_LINEAR) || k == SGP_COSINE || k == SGP_GAMMAEXP || k == SGP_MATERN_NU;
+  return (k >= SGP_SE && k <= SGP_LINEAR) || k == SGP_COSINE || k == SGP_GAMMAEXP || k == SGP_MATERN_NU ||
+         (k >= SGP_NEURALNET && k <= SGP_EXPONENTIATED);
 }
 
 static int pow2ceil(int d) {
@@ -374,7 +375,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   const int nterms = sp->term_ptr[npairs];
   std::vector<size_t> rs_off(nterms, (size_t)-1), cs_off(nterms, (size_t)-1);
   std::vector<long> rs_len(nterms, 0), cs_len(nterms, 0);
-  // product chains and terms of the RQ / LINEAR / COSINE / GAMMAEXP kinds (include/sthenomi_kprod.h): a class of their own
+  // product chains and terms of the kinds above SGP_CONST (include/sthenomi_kprod.h): a class of their own
   // (kprod.hip)
   std::vector<char> is_kp(std::max(1, nterms), 0);
   std::vector<size_t> nuc_off(std::max(1, nterms), (size_t)-1);   // SGP_MATERN_NU: the term's constants of nu (kprod.hip)
@@ -404,6 +405,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
             return fail("spec: SGP_GAMMAEXP (product path): param = gamma must be in (0, 2]");
           if ((T.kind & 0xff) == SGP_MATERN_NU && !(T.param > 0.0 && T.param <= SGP_MATERN_NU_MAX))
             return fail("spec: SGP_MATERN_NU (product path): param = nu must be finite and in (0, 32]");
+          if ((T.kind & 0xff) == SGP_FBM && !(T.param > 0.0 && T.param <= 1.0))
+            return fail("spec: SGP_FBM (product path): param = h must be finite and in (0, 1]");
           if ((T.kind & 0xff) == SGP_LINEAR && !(T.param >= 0.0 && T.param < 1e300))
             return fail("spec: SGP_LINEAR (product path): param = c must be >= 0 and finite");
           if (T.row_input >= 0 && T.row_input < sp->n_inputs) {
@@ -665,7 +668,7 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
         int kdmax = 1;
         const int cnt = kprod_group(ds->h_terms.data(), t, t1, &kdmax);
         CHECK_RC(launch_assemble_kprod(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, kdmax,
-                                       kprod_has_matern_nu(ds->h_terms.data() + t, cnt), lower_only, t > t0 ? 1 : 0,
+                                       kprod_mode(ds->h_terms.data() + t, cnt), lower_only, t > t0 ? 1 : 0,
                                        t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
         t += cnt;
       }
@@ -1643,7 +1646,7 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
       int kdmax = 1;
       const int cnt = kprod_group(ds->h_terms.data(), t, t1k, &kdmax);
       CHECK_RC(launch_diag_kprod(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t, cnt,
-                                 kprod_has_matern_nu(ds->h_terms.data() + t, cnt), 1, s));
+                                 kprod_mode(ds->h_terms.data() + t, cnt), 1, s));
       t += cnt;
     }
   }
@@ -1974,7 +1977,7 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       for (int t = tk; t < t1;) {
         const int e = chain_end(ds, t, t1), cdmax = chain_dmax(ds, t, e);
         CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, e - t, cdmax,
-                                   kprod_has_matern_nu(ds->h_terms.data() + t, e - t), trf, tcf, trl - trf,
+                                   kprod_mode(ds->h_terms.data() + t, e - t), trf, tcf, trl - trf,
                                    tcl - tcf, dpart.p, dgc + t, dgs + t, dgp ? dgp + t : nullptr, s));
         t = e;
       }

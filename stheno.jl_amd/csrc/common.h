@@ -190,10 +190,11 @@ int launch_diag_grad_stencil_wo(const double* w, long n, const DevTerm& T, int t
 // kprod.hip: product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h).  The terms of one launch are whole chains;
 // kprod_group cuts a pair's chain terms [t, t1) into launches (returns how many terms the launch at t carries, *dmax_out = its
 // DMAX) for the matrix and the diagonal alike.  Arguments of launch_assemble_kprod as launch_assemble_block.
-// mn: whether those terms hold a SGP_MATERN_NU factor (kprod_has_matern_nu of their host copies): the kernels are instantiated
-// with and without the Bessel routine
+// mn: kprod_mode of those terms' host copies -- 0: none of SGP_MATERN_NU and the kinds of x'y (SGP_NEURALNET, SGP_FBM,
+// SGP_EXPONENTIATED), 1: SGP_MATERN_NU and none of those three, 2: one of the three.  The kernels are instantiated per mode, so
+// that chains without the Bessel routine or without those kinds run what they ran before either existed
 int kprod_group(const DevTerm* h_terms, int t, int t1, int* dmax_out);
-bool kprod_has_matern_nu(const DevTerm* h_terms, int n);
+int kprod_mode(const DevTerm* h_terms, int n);
 int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* d_terms, int nterms,
                           int dmax, int mn, int lower_only, int accumulate, int noise_kind, double sigma2,
                           const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,

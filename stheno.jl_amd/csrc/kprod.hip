@@ -1,5 +1,6 @@
 // Product chains (include/sthenomi_kprod.h): covariance terms that multiply several leaf kernels, each on its own view of
-// the points, and the kinds that exist only here: RationalQuadratic, Linear, Cosine, GammaExponential and general-nu Matern.
+// the points, and the kinds that exist only here: RationalQuadratic, Linear, Cosine, GammaExponential, general-nu Matern and
+// the kinds of x'y: NeuralNetwork, FBM, Exponentiated.
 //     chain value (i, j) = coef_head rs_i cs_j  prod_f k_f(x^f_i, x'^f_j)
 // KernelFunctions' KernelProduct [EXT] (`k1 * k2`, reached through src/Stheno.jl:4-6); the locally periodic kernel of the
 // Mauna-Loa models and the sums of products of the neural-kernel-network example are such chains.
@@ -25,7 +26,8 @@
 
 namespace sgp {
 
-enum { K_RQ = 6, K_LINEAR = 7, K_COSINE = 16, K_GAMMAEXP = 17, K_MATERN_NU = 20 };
+enum { K_RQ = 6, K_LINEAR = 7, K_COSINE = 16, K_GAMMAEXP = 17, K_MATERN_NU = 20, K_NEURALNET = 24, K_FBM = 25,
+       K_EXPONENTIATED = 26 };
 constexpr int KP_KIND_MASK = 0xff, KP_TIMES_PREV = 0x100;   // sthenomi.h: SGP_KIND_TIMES_PREV
 constexpr int KP_MAXF = 8;                                  // sthenomi_kprod.h: SGP_KPROD_MAX_FACTORS
 constexpr int KP_CHUNK = 8;                                 // columns per accumulator chunk
@@ -238,18 +240,14 @@ void matern_nu_constants(double nu, double* out) {
 __device__ __noinline__ KpDerivs newkind_derivs(int kind, double d2, double param) {
   return kind == K_COSINE ? cosine_derivs(d2) : gexp_derivs(d2, param);
 }
-// MN: whether the chains of a launch hold a MATERN_NU factor.  The Bessel routine's registers count against every kernel that
+// MN: the launch mode (kprod_mode below: 0, 1 with a MATERN_NU factor, 2 with a NEURALNET / FBM / EXPONENTIATED factor); this
+// paragraph is about modes 0 and 1.  The Bessel routine's registers count against every kernel that
 // can call it (the assembly: 3 waves per SIMD become 2; the contractions go to scratch), so every kernel below is instantiated
 // with and without it, and chains without the kind run what they ran before it existed (docs/03_kernels.md section 3.2e).
 // With MN the three kinds sit behind one call site (nuc: MATERN_NU only)
 __device__ __noinline__ KpDerivs newkind_derivs_mn(int kind, double d2, double param, const double* nuc) {
   if (kind == K_MATERN_NU) return matern_nu_derivs(d2, param, nuc);
   return kind == K_COSINE ? cosine_derivs(d2) : gexp_derivs(d2, param);
-}
-bool kprod_has_matern_nu(const DevTerm* h_terms, int n) {
-  for (int t = 0; t < n; ++t)
-    if ((h_terms[t].kind & KP_KIND_MASK) == K_MATERN_NU) return true;
-  return false;
 }
 
 template <int DMAX>
@@ -270,6 +268,144 @@ __device__ __forceinline__ double kp_dot(const double (&xi)[DMAX], const double*
   return s;
 }
 
+// ---- NEURALNET, FBM, EXPONENTIATED: kinds of the scalars s = x'y, a = x'x, b = y'y (and e, below) ----------------------------
+// s, a and b share kp_dot's fma order, so s == a == b bit for bit where x == y; every sum is symmetric in (x, y) bit for bit.
+//   e = d2 (FBM): |x - y|^2 from direct differences, kp_d2's chain -- never a + b - 2 s
+//   e = L  (NEURALNET): Lagrange's sum  sum_{i<j} (x_i y_j - x_j y_i)^2 = a b - s^2, i outer, j inner.  A sum of squares: no
+//       cancellation against a b (nearly parallel points at large norms lose everything in a b - s^2).  The two products are
+//       rounded separately (no contraction), so exchanging x and y negates every term exactly; L = 0 exactly where x == y
+//       and at D = 1.  R^2 = (1 + a)(1 + b) - s^2 = ((a + b) + 1) + L.
+//   NEURALNET      k = asin(s / sqrt((1 + a)(1 + b))) = atan2(s, R): |k| < pi / 2 always, no argument near 1 to lose
+//   FBM            k = ((a^h + b^h) - d2^h) / 2.  pow(0, h) = 0: a power term whose base is exactly 0 contributes exactly 0 to
+//                  the value and to every derivative (0^h log 0 := 0 and, for h < 1, 0^(h - 1) := 0: the subgradient rule of
+//                  GAMMAEXP and Matern-1/2 at coincident points).  So k = a^h exactly where x == y, 0 exactly against the origin
+//   EXPONENTIATED  k = exp(s); beyond s = 709.78 it is +inf (the factorisation then reports "not positive definite")
+// Derivatives (KpDotDerivs): dk = d k / d g (both inputs scaled by g, at g = 1), dp = d k / d param, and the point derivatives
+//     d k / d x = c1 x + c2 (x - y) + c3 y,      d k / d y = c1y y + c2 (y - x) + c3 x
+//   NEURALNET      dk = s (1 / (1 + a) + 1 / (1 + b)) / R,  c1 = -s / ((1 + a) R),  c1y = -s / ((1 + b) R),  c3 = 1 / R
+//   FBM            dk = 2 h k,  dp = ((a^h log a + b^h log b) - d2^h log d2) / 2,  c1 = h a^h / a,  c1y = h b^h / b,
+//                  c2 = -h d2^h / d2  (kept on x - y: folded into the coefficients of x and y it would cancel at close points)
+//   EXPONENTIATED  dk = 2 s k,  c3 = k
+// Range: finite for a, b <= 1e300 (NEURALNET, FBM) and s <= 709 (EXPONENTIATED); beyond it inf or NaN, never a fault.  NEURALNET
+// is accurate only while (1 + a)(1 + b) is representable: beyond it L overflows, R = inf and k and its derivatives are 0.
+// Out of line, one body each: the matrix and the diagonal get the same bits from the same scalars.
+struct KpDot {
+  double s, a, b, e;
+};
+struct KpDotDerivs {
+  double k, dk, dp, c1, c1y, c2, c3;
+};
+__device__ __forceinline__ double kp_cross(double xi, double yj, double xj, double yi) {
+#pragma clang fp contract(off)
+  const double p = xi * yj, q = xj * yi;
+  return p - q;
+}
+// dim <= DMAX coordinates are read (the assembly pads its points with zeros up to DMAX: they add exact zeros)
+template <int DMAX>
+__device__ __forceinline__ KpDot kp_dot_scalars(int kind, const double* x, const double* y) {
+  KpDot r = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int d = 0; d < DMAX; ++d) {
+    r.s = fma(x[d], y[d], r.s);
+    r.a = fma(x[d], x[d], r.a);
+    r.b = fma(y[d], y[d], r.b);
+  }
+  if (kind == K_FBM) {
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) {
+      const double df = x[d] - y[d];
+      r.e = fma(df, df, r.e);
+    }
+  } else if (kind == K_NEURALNET) {
+#pragma unroll
+    for (int i = 0; i < DMAX; ++i)
+#pragma unroll
+      for (int j = i + 1; j < DMAX; ++j) {
+        const double c = kp_cross(x[i], y[j], x[j], y[i]);
+        r.e = fma(c, c, r.e);
+      }
+  }
+  return r;
+}
+__device__ __forceinline__ KpDot kp_dot_scalars_n(int kind, const double* x, const double* y, int dim) {
+  KpDot r = {0.0, 0.0, 0.0, 0.0};
+  for (int d = 0; d < dim; ++d) {
+    r.s = fma(x[d], y[d], r.s);
+    r.a = fma(x[d], x[d], r.a);
+    r.b = fma(y[d], y[d], r.b);
+  }
+  if (kind == K_FBM) {
+    for (int d = 0; d < dim; ++d) {
+      const double df = x[d] - y[d];
+      r.e = fma(df, df, r.e);
+    }
+  } else if (kind == K_NEURALNET) {
+    for (int i = 0; i < dim; ++i)
+      for (int j = i + 1; j < dim; ++j) {
+        const double c = kp_cross(x[i], y[j], x[j], y[i]);
+        r.e = fma(c, c, r.e);
+      }
+  }
+  return r;
+}
+__device__ __noinline__ double dotkind_eval(int kind, double h, double s, double a, double b, double e) {
+  if (kind == K_EXPONENTIATED) return exp(s);
+  if (kind == K_FBM) return 0.5 * ((pow(a, h) + pow(b, h)) - pow(e, h));
+  return atan2(s, sqrt(((a + b) + 1.0) + e));
+}
+__device__ __noinline__ KpDotDerivs dotkind_derivs(int kind, double h, double s, double a, double b, double e) {
+  KpDotDerivs r = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (kind == K_EXPONENTIATED) {
+    r.k = exp(s);
+    r.dk = 2.0 * s * r.k;
+    r.c3 = r.k;
+    return r;
+  }
+  if (kind == K_FBM) {
+    const double pa = pow(a, h), pb = pow(b, h), pd = pow(e, h);
+    r.k = 0.5 * ((pa + pb) - pd);
+    r.dk = 2.0 * h * r.k;
+    const double la = a > 0.0 ? pa * log(a) : 0.0, lb = b > 0.0 ? pb * log(b) : 0.0, ld = e > 0.0 ? pd * log(e) : 0.0;
+    r.dp = 0.5 * ((la + lb) - ld);
+    r.c1 = a > 0.0 ? h * pa / a : 0.0;
+    r.c1y = b > 0.0 ? h * pb / b : 0.0;
+    r.c2 = e > 0.0 ? -(h * pd / e) : 0.0;
+    return r;
+  }
+  const double R = sqrt(((a + b) + 1.0) + e), ia = 1.0 / (1.0 + a), ib = 1.0 / (1.0 + b);
+  r.k = atan2(s, R);
+  r.dk = s * (ia + ib) / R;
+  r.c1 = -(s * ia) / R;
+  r.c1y = -(s * ib) / R;
+  r.c3 = 1.0 / R;
+  return r;
+}
+// The launch mode of every kernel below (the template argument MN): 0 the chains hold none of MATERN_NU and the three kinds
+// above, 1 they hold MATERN_NU and none of the three, 2 they hold one of the three (and possibly MATERN_NU).  Modes 0 and 1
+// are what ran before the three kinds existed: the compiler reports the registers, scratch and LDS they had
+// (tools/kprod_resources.py; docs/03_kernels.md section 3.2e)
+int kprod_mode(const DevTerm* h_terms, int n) {
+  int mode = 0;
+  for (int t = 0; t < n; ++t) {
+    const int kind = h_terms[t].kind & KP_KIND_MASK;
+    if (kind >= K_NEURALNET) return 2;
+    if (kind == K_MATERN_NU) mode = 1;
+  }
+  return mode;
+}
+
+// one factor of one of the three kinds over a chunk of columns
+template <int DMAX>
+__device__ __forceinline__ void factor_chunk_dot(int kind, double (&prod)[KP_CHUNK], const double (&xi)[DMAX], const double* sp,
+                                                 double param, bool head) {
+#pragma unroll
+  for (int q = 0; q < KP_CHUNK; ++q) {
+    const KpDot r = kp_dot_scalars<DMAX>(kind, xi, sp + q * DMAX);
+    const double k = dotkind_eval(kind, param, r.s, r.a, r.b, r.e);
+    prod[q] = head ? k : prod[q] * k;
+  }
+}
+
 // one factor over a chunk of columns: prod = k (the head) or prod * k (a continuation).  KIND is a template argument so that
 // each case is straight-line code over the KP_CHUNK independent entries, as in the plain assembly
 template <int DMAX, int KIND>
@@ -288,9 +424,13 @@ __device__ __forceinline__ void factor_chunk(double (&prod)[KP_CHUNK], const dou
   }
 }
 
-template <int DMAX, bool MN>
+template <int DMAX, int MN>
 __device__ __forceinline__ void factor_chunk_any(int kind, double (&prod)[KP_CHUNK], const double (&xi)[DMAX],
                                                  const double* sp, double param, bool head, const double* nuc) {
+  if (MN == 2 && kind >= K_NEURALNET) {
+    factor_chunk_dot<DMAX>(kind, prod, xi, sp, param, head);
+    return;
+  }
   if (MN && kind == K_MATERN_NU) {
     factor_chunk<DMAX, K_MATERN_NU>(prod, xi, sp, param, head, nuc);
     return;
@@ -310,7 +450,7 @@ __device__ __forceinline__ void factor_chunk_any(int kind, double (&prod)[KP_CHU
 }
 
 // terms [0, nterms): whole chains (a term with KP_TIMES_PREV continues the chain of the nearest term before it without)
-template <int DMAX, bool MN>
+template <int DMAX, int MN>
 __global__ __launch_bounds__(256) void assemble_kprod_kernel(
     double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* terms, int nterms, int lower_only,
     int accumulate, int noise_kind, double sigma2, const double* noise_diag, long tile_r_first, long tile_c_first) {
@@ -432,11 +572,14 @@ int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc
 #define SGP_KP(DM)                                                                                                     \
   do {                                                                                                                 \
     const size_t lds = (size_t)nterms * TILE * DM * sizeof(double);                                                    \
-    if (mn)                                                                                                            \
-      hipLaunchKernelGGL((assemble_kprod_kernel<DM, true>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms, \
+    if (mn == 2)                                                                                                       \
+      hipLaunchKernelGGL((assemble_kprod_kernel<DM, 2>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms,  \
+                         lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first);        \
+    else if (mn)                                                                                                       \
+      hipLaunchKernelGGL((assemble_kprod_kernel<DM, 1>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms,  \
                          lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first);        \
     else                                                                                                               \
-      hipLaunchKernelGGL((assemble_kprod_kernel<DM, false>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms,      \
+      hipLaunchKernelGGL((assemble_kprod_kernel<DM, 0>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms,          \
                          nterms, lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first); \
   } while (0)
   if (dmax <= 1) SGP_KP(1);
@@ -450,11 +593,15 @@ int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc
 }
 
 // ---- the diagonal: out[i] (+)= the sum of the chains of one launch group, in the assembly's operation order ------------
-template <bool MN>
+template <int MN>
 __device__ __forceinline__ double kp_factor_diag(const DevTerm& T, long i) {
   const int kind = T.kind & KP_KIND_MASK;
   const double* a = T.xr + i * T.ldr;
   const double* b = T.xc + i * T.ldc;
+  if (MN == 2 && kind >= K_NEURALNET) {
+    const KpDot r = kp_dot_scalars_n(kind, a, b, T.dim);
+    return dotkind_eval(kind, T.param, r.s, r.a, r.b, r.e);
+  }
   if (kind == K_LINEAR) {
     double s = 0.0;
     for (int d = 0; d < T.dim; ++d) s = fma(a[d], b[d], s);
@@ -472,7 +619,7 @@ __device__ __forceinline__ double kp_factor_diag(const DevTerm& T, long i) {
   return kern_eval(kind, d2, T.param);
 }
 
-template <bool MN>
+template <int MN>
 __global__ void diag_kprod_kernel(double* out, long n, const DevTerm* terms, int nterms, int accumulate) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -497,11 +644,14 @@ __global__ void diag_kprod_kernel(double* out, long n, const DevTerm* terms, int
 
 int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int mn, int accumulate, hipStream_t s) {
   if (n <= 0 || nterms <= 0) return 0;
-  if (mn)
-    hipLaunchKernelGGL(diag_kprod_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
+  if (mn == 2)
+    hipLaunchKernelGGL(diag_kprod_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
+                       accumulate);
+  else if (mn)
+    hipLaunchKernelGGL(diag_kprod_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
                        accumulate);
   else
-    hipLaunchKernelGGL(diag_kprod_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
+    hipLaunchKernelGGL(diag_kprod_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
                        accumulate);
   SGP_HIP(hipGetLastError());
   return 0;
@@ -509,9 +659,17 @@ int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, i
 
 // ---- gradient contraction of ONE chain --------------------------------------------------------------------------------
 // k, d k / d g (both inputs scaled by g, at g = 1) and d k / d param of one factor
-template <int DMAX, bool MN>
+template <int DMAX, int MN>
 __device__ __forceinline__ void kp_factor_grad(int kind, double param, const double* xr, const double* sp, double& k,
                                                double& dk, double& dp, const DevTerm* term) {
+  if (MN == 2 && kind >= K_NEURALNET) {
+    const KpDot q = kp_dot_scalars<DMAX>(kind, xr, sp);
+    const KpDotDerivs r = dotkind_derivs(kind, param, q.s, q.a, q.b, q.e);
+    k = r.k;
+    dk = r.dk;
+    dp = r.dp;
+    return;
+  }
   if (kind == K_LINEAR) {
     double s = 0.0;
 #pragma unroll
@@ -550,7 +708,7 @@ __device__ __forceinline__ void kp_factor_grad(int kind, double param, const dou
   dp = kind == G_CONST ? 1.0 : 0.0;
 }
 
-template <int DMAX, bool MN>
+template <int DMAX, int MN>
 __global__ __launch_bounds__(256) void grad_kprod_kernel(const double* Kinv, long ldk, const double* alpha, long r0, long nr,
                                                          long c0, long nc, const DevTerm* terms, int nf,
                                                          long tile_r_first, long tile_c_first,
@@ -695,7 +853,7 @@ __global__ __launch_bounds__(256) void grad_kprod_reduce_kernel(const double* pa
   }
 }
 
-template <int DMAX, bool MN>
+template <int DMAX, int MN>
 static int launch_grad_kprod_t(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
                                const DevTerm* d_terms, int nf, long trf, long tcf, long trc, long tcc, double* partials,
                                hipStream_t s) {
@@ -723,8 +881,9 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
   }
   int rc;
 #define SGP_KG(DM)                                                                                                     \
-  rc = mn ? launch_grad_kprod_t<DM, true>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s)  \
-          : launch_grad_kprod_t<DM, false>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s)
+  rc = mn == 2 ? launch_grad_kprod_t<DM, 2>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s) \
+       : mn    ? launch_grad_kprod_t<DM, 1>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s) \
+               : launch_grad_kprod_t<DM, 0>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s)
   if (dmax <= 1) SGP_KG(1);
   else if (dmax <= 2) SGP_KG(2);
   else if (dmax <= 4) SGP_KG(4);
@@ -747,9 +906,20 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
 // NK: 1 if the chain holds a COSINE / GAMMAEXP factor, 2 if it holds a MATERN_NU factor (and possibly those), else 0.  The call of their out-of-line routine costs the row-side kernel
 // below registers at every factor (DMAX = 1: 2 waves per SIMD become 1), so chains of the older kinds run an instantiation
 // without it
+// NK == 3: the chain holds a NEURALNET / FBM / EXPONENTIATED factor (and possibly any other kind).  Such a factor has
+// d k / d x = c1 x + c2 (x - x') + c3 x' (KpDotDerivs), c2 = 2 kx; c1 and c3 exist in that instantiation only.
 template <int DMAX, int NK>
 __device__ __forceinline__ void kp_factor_dx(int kind, double param, const double* xr, const double* sp, double& k,
-                                             double& kx, const double* nuc) {
+                                             double& kx, const double* nuc, double& c1, double& c3) {
+  if (NK == 3 && kind >= K_NEURALNET) {
+    const KpDot q = kp_dot_scalars<DMAX>(kind, xr, sp);
+    const KpDotDerivs r = dotkind_derivs(kind, param, q.s, q.a, q.b, q.e);
+    k = r.k;
+    kx = 0.5 * r.c2;
+    c1 = r.c1;
+    c3 = r.c3;
+    return;
+  }
   if (kind == K_LINEAR) {
     double s = 0.0;
 #pragma unroll
@@ -771,8 +941,8 @@ __device__ __forceinline__ void kp_factor_dx(int kind, double param, const doubl
     kx = -0.5 * exp(-(param + 1.0) * l);
     return;
   }
-  if (NK && (kind == K_COSINE || kind == K_GAMMAEXP || (NK == 2 && kind == K_MATERN_NU))) {
-    const KpDerivs r = NK == 2 ? newkind_derivs_mn(kind, d2, param, nuc) : newkind_derivs(kind, d2, param);
+  if (NK && (kind == K_COSINE || kind == K_GAMMAEXP || (NK >= 2 && kind == K_MATERN_NU))) {
+    const KpDerivs r = NK >= 2 ? newkind_derivs_mn(kind, d2, param, nuc) : newkind_derivs(kind, d2, param);
     k = r.k;
     kx = r.kx;
     return;
@@ -851,13 +1021,15 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
         const double gm = Gm[grow * sr + gc * sc];
         const double g = alpha ? 0.5 * (ai * alpha[gc] - gm) : gm;
         double k[TMAX], kx[TMAX], pre[TMAX + 1];
+        double c1[NK == 3 ? TMAX : 1], c3[NK == 3 ? TMAX : 1];   // NEURALNET / FBM / EXPONENTIATED: kp_factor_dx
         pre[0] = 1.0;
 #pragma unroll
         for (int f = 0; f < TMAX; ++f) {
           k[f] = 1.0;
           kx[f] = 0.0;
+          if (NK == 3) c1[NK == 3 ? f : 0] = c3[NK == 3 ? f : 0] = 0.0;
           if (f < nf) kp_factor_dx<DMAX, NK>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], kx[f],
-                                              NK == 2 ? C.t[f].nuc : nullptr);
+                                              NK >= 2 ? C.t[f].nuc : nullptr, c1[NK == 3 ? f : 0], c3[NK == 3 ? f : 0]);
           pre[f + 1] = pre[f] * k[f];
         }
         const double gcs = g * scs[p];
@@ -869,7 +1041,14 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
           if (f < nf) {
             const double excl = w * (pre[f] * suf);
             const double* sp = &sx[(f * TILE + p) * DMAX];
-            if (kind[f] == K_LINEAR) {
+            if (NK == 3 && kind[f] >= K_NEURALNET) {
+              const double e1 = excl * c1[NK == 3 ? f : 0], e2 = 2.0 * excl * kx[f], e3 = excl * c3[NK == 3 ? f : 0];
+#pragma unroll
+              for (int d = 0; d < DMAX; ++d) {
+                const double xv = xr[f * DMAX + d];
+                acc[f * DMAX + d] = fma(e3, sp[d], fma(e2, xv - sp[d], fma(e1, xv, acc[f * DMAX + d])));
+              }
+            } else if (kind[f] == K_LINEAR) {
 #pragma unroll
               for (int d = 0; d < DMAX; ++d) acc[f * DMAX + d] = fma(excl, sp[d], acc[f * DMAX + d]);
             } else {
@@ -946,10 +1125,11 @@ int launch_grad_kprod_inputs(const double* Gm, long sr, long sc, const double* a
   int nk = 0;
   for (int f = 0; f < nf; ++f) {
     const int kind = h_terms[f].kind & KP_KIND_MASK;
-    nk = std::max(nk, kind == K_MATERN_NU ? 2 : (kind == K_COSINE || kind == K_GAMMAEXP) ? 1 : 0);
+    nk = std::max(nk, kind >= K_NEURALNET ? 3 : kind == K_MATERN_NU ? 2 : (kind == K_COSINE || kind == K_GAMMAEXP) ? 1 : 0);
   }
 #define SGP_KI(DM)                                                                                                     \
-  rc = nk == 2 ? launch_grad_kprod_inputs_t<DM, 2>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
+  rc = nk == 3 ? launch_grad_kprod_inputs_t<DM, 3>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
+       : nk == 2 ? launch_grad_kprod_inputs_t<DM, 2>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)          \
        : nk    ? launch_grad_kprod_inputs_t<DM, 1>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
                : launch_grad_kprod_inputs_t<DM, 0>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)
   if (dmax <= 1) SGP_KI(1);
@@ -973,7 +1153,7 @@ struct KpDiagArgs {
   double* gxc[KP_MAXF];
 };
 
-template <bool MN>
+template <int MN>
 __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, long n, KpDiagArgs C, int nf, double* out_coef,
                                                               double* out_scale, double* out_param, double* out_rs,
                                                               double* out_cs) {
@@ -983,17 +1163,30 @@ __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, l
   for (int f = 0; f < KP_MAXF; ++f) gs_acc[f] = gp_acc[f] = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) {
     double k[KP_MAXF], dk[KP_MAXF], dp[KP_MAXF], kx[KP_MAXF], pre[KP_MAXF + 1];
+    constexpr int NDOT = MN == 2 ? KP_MAXF : 1;   // NEURALNET / FBM / EXPONENTIATED: the coefficients of KpDotDerivs
+    double c1[NDOT], c1y[NDOT], c3[NDOT];
     pre[0] = 1.0;
 #pragma unroll
     for (int f = 0; f < KP_MAXF; ++f) {
       k[f] = 1.0;
       dk[f] = dp[f] = kx[f] = 0.0;
+      if (MN == 2) c1[f % NDOT] = c1y[f % NDOT] = c3[f % NDOT] = 0.0;
       if (f < nf) {
         const DevTerm& T = C.t[f];
         const int kind = T.kind & KP_KIND_MASK;
         const double* a = T.xr + i * T.ldr;
         const double* b = T.xc + i * T.ldc;
-        if (kind == K_LINEAR) {
+        if (MN == 2 && kind >= K_NEURALNET) {
+          const KpDot q = kp_dot_scalars_n(kind, a, b, T.dim);
+          const KpDotDerivs r = dotkind_derivs(kind, T.param, q.s, q.a, q.b, q.e);
+          k[f] = r.k;
+          dk[f] = r.dk;
+          dp[f] = r.dp;
+          kx[f] = 0.5 * r.c2;
+          c1[f % NDOT] = r.c1;
+          c1y[f % NDOT] = r.c1y;
+          c3[f % NDOT] = r.c3;
+        } else if (kind == K_LINEAR) {
           double s = 0.0;
           for (int d = 0; d < T.dim; ++d) s = fma(a[d], b[d], s);
           k[f] = s + T.param;
@@ -1056,7 +1249,16 @@ __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, l
       const double* b = T.xc + i * T.ldc;
       double* orow = C.gxr[f] + i * T.dim;
       double* ocol = C.gxc[f] + i * T.dim;
-      if ((T.kind & KP_KIND_MASK) == K_LINEAR) {
+      if (MN == 2 && (T.kind & KP_KIND_MASK) >= K_NEURALNET) {
+        // LINEAR's convention: the row input receives d k / d x, the column input d k / d y, both added when they are one array
+        const double e1 = excl[f] * c1[f % NDOT], e1y = excl[f] * c1y[f % NDOT], e2 = 2.0 * excl[f] * kx[f],
+                     e3 = excl[f] * c3[f % NDOT];
+        for (int d = 0; d < T.dim; ++d) {
+          const double av = a[d], bv = b[d];
+          orow[d] += fma(e3, bv, fma(e2, av - bv, e1 * av));
+          ocol[d] += fma(e3, av, fma(e2, bv - av, e1y * bv));
+        }
+      } else if ((T.kind & KP_KIND_MASK) == K_LINEAR) {
         for (int d = 0; d < T.dim; ++d) {
           const double av = a[d], bv = b[d];
           orow[d] += excl[f] * bv;
@@ -1120,11 +1322,15 @@ int launch_diag_grad_kprod(const double* w, long n, const DevTerm* h_terms, int 
     C.gxr[f] = (f < nf && gxr) ? gxr[f] : nullptr;
     C.gxc[f] = (f < nf && gxc) ? gxc[f] : nullptr;
   }
-  if (kprod_has_matern_nu(h_terms, nf))
-    hipLaunchKernelGGL(diag_grad_kprod_kernel<true>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
+  const int mode = kprod_mode(h_terms, nf);
+  if (mode == 2)
+    hipLaunchKernelGGL(diag_grad_kprod_kernel<2>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
+                       out_rs, out_cs);
+  else if (mode)
+    hipLaunchKernelGGL(diag_grad_kprod_kernel<1>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
                        out_rs, out_cs);
   else
-    hipLaunchKernelGGL(diag_grad_kprod_kernel<false>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
+    hipLaunchKernelGGL(diag_grad_kprod_kernel<0>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
                        out_rs, out_cs);
   SGP_HIP(hipGetLastError());
   return 0;

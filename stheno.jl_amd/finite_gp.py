@@ -587,7 +587,7 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
     sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
     index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
-    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, gamma of GammaExponential, c of Linear / Constant; 0 for nu
+    d_param, the derivative w.r.t. the kernel's parameter (alpha of RQ, gamma of GammaExponential, h of FBM, c of Linear / Constant; 0 for nu
     of GeneralMaternKernel, which is held fixed).  inputs / scales of such
     models come from logpdf_and_gradient_param."""
     yv, spec = _logpdf_grad_spec(fx, y)

@@ -355,6 +355,14 @@ def build_spec(f, x, f2=None, x2=None):
                                 ri = table.get(p.X, s, ("row", I, p.chain))
                                 ci = table.get(q.X, s, ("row" if symmetric else "col", J, q.chain))
                                 chain.append((kind, param, ri, ci))
+                            # the library's limits (include/sthenomi_kprod.h), named here as it names them
+                            dims = [int(np.asarray(table.arrays[c[2]]).shape[0]) for c in chain]
+                            dmax = 1 << max(0, max(dims) - 1).bit_length()
+                            if max(dims) > _lib.KPROD_MAX_DIM or len(chain) * dmax > 64:
+                                raise NotImplementedError(f"a product of {len(chain)} kernels (or a kernel of the product path) on "
+                                                          f"inputs of dimension {max(dims)} is beyond the library's limits: factor "
+                                                          f"dimension <= {_lib.KPROD_MAX_DIM}, factors x dimension (rounded up to a "
+                                                          "power of two) <= 64")
                             k = ("product", tuple(chain), id(p.r) if p.r is not None else None,
                                  id(q.r) if q.r is not None else None)
                             if k in merged:

@@ -312,6 +312,30 @@ class LinearKernel(Kernel):
         return [(_lib.LINEAR, 1.0, self.c, ())]
 
 
+class NeuralNetworkKernel(_Simple):
+    """asin(x'y / sqrt((1 + x'x)(1 + y'y))) (KernelFunctions NeuralNetworkKernel, Williams' arcsine kernel); evaluated on the
+    product path (include/sthenomi_kprod.h: SGP_NEURALNET)"""
+    kind = _lib.NEURALNET
+
+
+class FBMKernel(Kernel):
+    """(|x|^2h + |y|^2h - |x - y|^2h) / 2, h in (0, 1] (KernelFunctions FBMKernel): fractional Brownian motion, the Wiener
+    process at h = 1/2 and x'y at h = 1; evaluated on the product path (SGP_FBM, param = h)"""
+
+    def __init__(self, h=0.5):
+        self.h = float(h)
+        if not 0.0 < self.h <= 1.0:
+            raise ValueError("FBMKernel: h must be in (0, 1]")
+
+    def leaf_terms(self):
+        return [(_lib.FBM, 1.0, self.h, ())]
+
+
+class ExponentiatedKernel(_Simple):
+    """exp(x'y) (KernelFunctions ExponentiatedKernel); evaluated on the product path (SGP_EXPONENTIATED)"""
+    kind = _lib.EXPONENTIATED
+
+
 class PolynomialKernel(Kernel):
     """(x'y + c)^degree: a chain of `degree` LINEAR factors"""
 

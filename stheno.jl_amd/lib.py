@@ -22,6 +22,7 @@ RQ, LINEAR = 6, 7                  # evaluated by the product-chain path only (i
 COSINE, GAMMAEXP = 16, 17          # the same path (8 .. 15 are no kinds)
 MATERN_NU = 20                     # general-nu Matern, the same path (18, 19 are no kinds); nu in (0, MATERN_NU_MAX]
 MATERN_NU_MAX = 32.0
+NEURALNET, FBM, EXPONENTIATED = 24, 25, 26   # kinds of x'y, x'x and y'y, the same path (21 .. 23 and 27+ are no kinds)
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
 KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain
