@@ -48,7 +48,8 @@ enum {
   /* the kinds below are evaluated by the product-chain path only (include/sthenomi_kprod.h) */
   SGP_RQ = 6,       /* RationalQuadraticKernel(alpha): (1 + d^2 / (2 alpha))^-alpha, param = alpha > 0 */
   SGP_LINEAR = 7,   /* LinearKernel(c): x'y + c, param = c >= 0                          */
-  /* 8 .. 15 are no kinds: a spec that names one is refused ("unknown kernel kind") */
+  /* 8, 9 and 15 are no kinds: a spec that names one is refused ("unknown kernel kind").  10 .. 14 are SGP_WIENER and
+     SGP_PIECEWISE0 .. SGP_PIECEWISE3, kinds of the product path declared with it in include/sthenomi_kprod.h */
   SGP_COSINE = 16,  /* CosineKernel: cos(pi d), param ignored                            */
   SGP_GAMMAEXP = 17, /* GammaExponentialKernel(gamma): exp(-d^gamma), param = gamma in (0, 2] */
   /* 18 and 19 are no kinds either */
@@ -88,7 +89,7 @@ typedef struct {
                          sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
   double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu;
-                         SGP_FBM: h; ignored by the other kinds */
+                         SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; ignored by the other kinds */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

@@ -16,9 +16,9 @@
  *     views of the points); the two inputs of a factor have one dimension;
  *   - a continuation has coef == 1.0, NULL row_scale / col_scale and reserved == 0, and is never the first term of a pair;
  *   - the head of a chain, and any term of the kinds SGP_RQ / SGP_LINEAR / SGP_COSINE / SGP_GAMMAEXP / SGP_MATERN_NU / SGP_NEURALNET /
- *     SGP_FBM / SGP_EXPONENTIATED (a chain of length one), has reserved == 0: there are no products with patch or stencil sides.
- * Kinds that exist on this path only (codes 6, 7, 16, 17, 20, 24, 25, 26; 8 .. 15, 18, 19, 21 .. 23 and everything above 26 are refused as
- * unknown):
+ *     SGP_FBM / SGP_EXPONENTIATED / SGP_WIENER / SGP_PIECEWISE0 .. 3 (a chain of length one), has reserved == 0: there are no products with patch or stencil sides.
+ * Kinds that exist on this path only (codes 6, 7, 10 .. 14, 16, 17, 20, 24, 25, 26; 8, 9, 15, 18, 19, 21 .. 23 and 27 and above
+ * are refused as unknown):
  *   SGP_RQ        param = alpha > 0:  (1 + d^2 / (2 alpha))^-alpha       (RationalQuadraticKernel)
  *   SGP_LINEAR    param = c >= 0:     x'y + c                            (LinearKernel; PolynomialKernel(n, c) is a chain of
  *                                                                         n such factors)
@@ -51,6 +51,31 @@
  * where the kernel is pi / 2).  Scale such inputs first.  An overflowed
  * exp is +inf, and the factorisation then reports "not positive definite" like any other such matrix.  Beyond the range the
  * results are inf or NaN; nothing faults.  Error models: tests/dotkinds_truth.py.
+ *   SGP_WIENER    param = i, exactly 0, 1, 2 or 3:  the i-times integrated Wiener process (WienerKernel{i}); with X = |x|,
+ *                 Y = |y|, m = min(X, Y), M = max(X, Y), d = |x - y|:
+ *                     i = 0  m          i = 1  m^3 / 3 + m^2 d / 2          i = 2  m^5 / 20 + m^3 d (X + Y - m / 2) / 12
+ *                     i = 3  m^7 / 252 + m^4 d (5 M^2 + 2 X Y + 3 m^2) / 720
+ *   SGP_PIECEWISE0 .. SGP_PIECEWISE3 (the code carries the degree q)  param = j, an integer in [1, SGP_PIECEWISE_J_MAX]:
+ *                 max(1 - r, 0)^(j + q) p_q(r), r = d   (PiecewisePolynomialKernel{q}(dim), Rasmussen & Williams eq. 4.21; the
+ *                 host passes j = floor(dim / 2) + q + 1, the library knows nothing of dim)
+ *                     p_0 = 1    p_1 = 1 + (j + 1) r    p_2 = 1 + (j + 2) r + (j^2 + 4 j + 3) / 3 r^2
+ *                     p_3 = 1 + (j + 3) r + (6 j^2 + 36 j + 45) / 15 r^2 + (j^3 + 9 j^2 + 23 j + 15) / 15 r^3
+ * SGP_WIENER is a kind of the scalars above: X^2 = a, Y^2 = b and d^2 from direct differences (never a + b - 2 s), the three
+ * square roots correctly rounded; only +, x, / by constants, min and max follow, every term is positive.  Rules at the ends:
+ * the kernel is symmetric bit for bit (min / max and the commutative X + Y and X Y); exactly 0 against the origin; on the
+ * diagonal d = 0 exactly and k is the single first term.  Point derivatives in the coefficient form of the kinds of x'y,
+ * d k / d x = c1 x + c2 (x - y) (c3 = 0): dX / dx = x / X and 0 at X = 0, dd / dx = (x - y) / d and 0 at d = 0; at a tie X == Y,
+ * which includes every diagonal entry, dm (and dM) goes half to each side, x / (2 X) and y / (2 Y): with LINEAR's diagonal
+ * convention this gives the true d k(x, x) / dx, the rule SGP_FBM follows at h = 1/2.  d k / d g = (2 i + 1) k (homogeneous),
+ * d k / d param = 0 (i is discrete).  Finite while m^(2 i + 1) and the products with d and M^2 are representable.  i >= 1 is
+ * not known to be positive definite beyond the half line.
+ * SGP_PIECEWISE: exactly 1 at d^2 == 0; exactly 0 with every derivative exactly 0 for r >= 1 and for an overflowed d^2 (the
+ * only kind whose exact zeros come from the data).  The power is taken by square-and-multiply on 1 - r (exact for r >= 1/2),
+ * not pow.  d k / d (d^2) = k'(r) / (2 r) with k'(r) = -r (1 - r)^(j+q-1) pt_q(r) for q >= 1 (pt_1 = (j + 1)(j + 2),
+ * pt_2 = (j + 3)(j + 4) / 3 (1 + (j + 1) r), pt_3 a quadratic: stheno.jl_amd/csrc/kprod.hip), a power times a polynomial and
+ * never a quotient by r; q = 0: -j (1 - r)^(j-1) / (2 r), and 0 at r = 0, the subgradient Matern-1/2 has there.
+ * d k / d g = 2 d^2 d k / d (d^2), d k / d param = 0.  A param outside these sets, not integer-valued, NaN or inf is refused
+ * at upload by name, as SGP_FBM's.  Error models: tests/wienerpp_truth.py.
  * General-nu Matern has no library call to lean on: K_nu is evaluated in fp64 by Temme's series (x <= 2) or Steed's second
  * continued fraction (x > 2) at the order mu = nu - n in [-1/2, 1/2), followed by n - 1 steps of the upward recurrence, on
  * quantities scaled by the power of x and by e^x so that nothing overflows or underflows before the last product; what depends
@@ -81,7 +106,7 @@
  *     grad_inscale[f]    = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != f} k_f') d k_f(g x, g x') / dg at g = 1
  * (LINEAR: 2 x'y;  RQ: -d^2 (1 + d^2 / (2 alpha))^(-alpha - 1);  COSINE: -pi d sin(pi d);  GAMMAEXP: -gamma d^gamma k;
  * MATERN_NU: -C x^(nu+1) K_(nu-1)(x), C = 2^(1-nu) / Gamma(nu);  NEURALNET: s (1 / (1 + a) + 1 / (1 + b)) / R;  FBM: 2 h k;
- * EXPONENTIATED: 2 s k).  With
+ * EXPONENTIATED: 2 s k;  WIENER: (2 i + 1) k;  PIECEWISE: 2 d^2 d k / d (d^2)).  With
  * respect to the points a distance kind contributes 2 kappa' (x - x'), kappa' = d k / d (d^2): COSINE -pi sin(pi d) / (2 d),
  * GAMMAEXP -(gamma / 2) d^gamma k / d^2, MATERN_NU -(nu / x) C x^nu K_(nu-1)(x).  The kinds of x'y contribute
  * d k / d x (row point; the column point's is the same with x and y exchanged):  LINEAR y;  NEURALNET (y - s x / (1 + a)) / R;
@@ -106,13 +131,23 @@ extern "C" {
 #define SGP_KPROD_MAX_FACTORS 8
 #define SGP_KPROD_MAX_DIM 16
 #define SGP_MATERN_NU_MAX 32.0
+#define SGP_PIECEWISE_J_MAX 64
+
+/* Values of sgp_term.kind that exist on this path only and are declared here (the others: the enum of include/sthenomi.h) */
+enum {
+  SGP_WIENER = 10,     /* WienerKernel{i}: the i-times integrated Wiener process of |x|, |y|, |x - y|; param = i in {0, 1, 2, 3} */
+  SGP_PIECEWISE0 = 11, /* PiecewisePolynomialKernel{q}(dim): max(1 - d, 0)^(j + q) p_q(d), q = code - 11; param = j, an integer */
+  SGP_PIECEWISE1 = 12, /*   in [1, SGP_PIECEWISE_J_MAX]; the host passes j = floor(dim / 2) + q + 1                              */
+  SGP_PIECEWISE2 = 13,
+  SGP_PIECEWISE3 = 14
+};
 
 /* sgp_logpdf_grad plus the gradient with respect to the kernel parameters: grad_param (may be NULL, like every output) has
  * one entry per element of spec->terms,
  *     grad_param[t] = sum_ij G_ij coef_h rs_i cs_j (prod_{f' != t} k_f') d k_t / d param
  * with d k / d param = k (u / (1 + u) - log1p(u)), u = d^2 / (2 alpha), for SGP_RQ; d k / d gamma = -k d^gamma log(d^2) / 2 for
- * SGP_GAMMAEXP; d k / d h = (a^h log a + b^h log b - (d^2)^h log d^2) / 2 for SGP_FBM; 1 for SGP_LINEAR and SGP_CONST; 0 for the kinds without a parameter (SGP_COSINE, SGP_NEURALNET and SGP_EXPONENTIATED among them) and for
- * SGP_MATERN_NU, whose nu is held fixed.  Plain terms (outside any chain) get their entries too.  Every other output is bit for bit what
+ * SGP_GAMMAEXP; d k / d h = (a^h log a + b^h log b - (d^2)^h log d^2) / 2 for SGP_FBM; 1 for SGP_LINEAR and SGP_CONST; 0 for the kinds without a parameter (SGP_COSINE, SGP_NEURALNET and SGP_EXPONENTIATED among them), for
+ * SGP_MATERN_NU, whose nu is held fixed, and for SGP_WIENER and SGP_PIECEWISE0 .. 3, whose i and j are discrete.  Plain terms (outside any chain) get their entries too.  Every other output is bit for bit what
  * sgp_logpdf_grad returns for the same arguments.  Any spec sgp_logpdf_grad takes, on a single-GPU context: a multi-GPU
  * context refuses this entry point (rc < 0) whatever the spec holds, product chains or not. */
 int sgp_logpdf_grad_param(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind, const double* noise,

@@ -106,6 +106,12 @@ leaf(k::MaternKernel) = [(20, 1.0, Float64(only(k.ν)), Chain())]
 leaf(::NeuralNetworkKernel) = [(24, 1.0, 0.0, Chain())]
 leaf(k::FBMKernel) = [(25, 1.0, Float64(only(k.h)), Chain())]
 leaf(::ExponentiatedKernel) = [(26, 1.0, 0.0, Chain())]
+# SGP_WIENER = 10 (param = i in 0 .. 3; WienerKernel(i = -1) is a WhiteKernel already) and SGP_PIECEWISE0 .. 3 = 11 .. 14 (the code
+# carries the degree, param = j = floor(dim / 2) + degree + 1; KernelFunctions keeps alpha = j + degree in the kernel)
+leaf(::WienerKernel{I}) where {I} = [(10, 1.0, Float64(I), Chain())]
+leaf(k::PiecewisePolynomialKernel{D}) where {D} = [(11 + D, 1.0, Float64(k.alpha - D), Chain())]
+# (1 + d^2 / alpha)^-alpha = RationalQuadratic(alpha) (SGP_RQ = 6, param = alpha) on points scaled by sqrt 2
+leaf(k::RationalKernel) = [(6, 1.0, Float64(only(k.α)), Chain([(:scale, sqrt(2.0))]))]
 leaf(k::ScaledKernel) = [(a, c * only(k.σ²), p, ch) for (a, c, p, ch) in leaf(k.kernel)]
 leaf(k::KernelSum) = reduce(vcat, leaf.(k.kernels))
 # k o t evaluates k(t(x), t(y)): t is applied to the raw points first, the inner kernel's own chain after it

@@ -10,6 +10,7 @@ from .lib import PosDefException, SthenoMIError  # noqa: F401
 from .inputs import BlockData, ColVecs, GPPPInput, ImageVector, blocks, split, vcat  # noqa: F401
 from .kernels import (ARDTransform, CosineKernel, ExponentiatedKernel, FBMKernel, GammaExponentialKernel, NeuralNetworkKernel, GeneralMaternKernel, LinearTransform, MaternKernel,  # noqa: F401
                       SelectTransform, gaborkernel, spectral_mixture_kernel, spectral_mixture_product_kernel)
+from .kernels import PiecewisePolynomialKernel, RationalKernel, WienerKernel  # noqa: F401
 from .kernels import (ConstantKernel, ExponentialKernel, KernelProduct, KernelSum, LinearKernel, Matern12Kernel,  # noqa: F401
                       Matern32Kernel, Matern52Kernel, PeriodicKernel, PeriodicTransform, PolynomialKernel,
                       RationalQuadraticKernel, ScaledKernel, ScaleTransform,

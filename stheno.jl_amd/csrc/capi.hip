@@ -308,10 +308,11 @@ extern "C" int sgp_ctx_destroy(sgp_ctx* c) {
 // ---------------------------------------------------------------------------------------
 // device-resident specs
 // ---------------------------------------------------------------------------------------
-// the kinds of include/sthenomi.h: 0 .. 7, 16 / 17, 20 and 24 .. 26 (8 .. 15, 18, 19, 21 .. 23 and everything above stay unknown)
+// the kinds of include/sthenomi.h: 0 .. 7, 10 .. 14, 16 / 17, 20 and 24 .. 26 (8, 9, 15, 18, 19, 21 .. 23 and everything above stay
+// unknown)
 static bool kind_known(int k) {
   return (k >= SGP_SE && k <= SGP_LINEAR) || k == SGP_COSINE || k == SGP_GAMMAEXP || k == SGP_MATERN_NU ||
-         (k >= SGP_NEURALNET && k <= SGP_EXPONENTIATED);
+         (k >= SGP_NEURALNET && k <= SGP_EXPONENTIATED) || (k >= SGP_WIENER && k <= SGP_PIECEWISE3);
 }
 
 static int pow2ceil(int d) {
@@ -407,6 +408,11 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
             return fail("spec: SGP_MATERN_NU (product path): param = nu must be finite and in (0, 32]");
           if ((T.kind & 0xff) == SGP_FBM && !(T.param > 0.0 && T.param <= 1.0))
             return fail("spec: SGP_FBM (product path): param = h must be finite and in (0, 1]");
+          if ((T.kind & 0xff) == SGP_WIENER && !(T.param == 0.0 || T.param == 1.0 || T.param == 2.0 || T.param == 3.0))
+            return fail("spec: SGP_WIENER (product path): param = i must be exactly 0, 1, 2 or 3");
+          if ((T.kind & 0xff) >= SGP_PIECEWISE0 && (T.kind & 0xff) <= SGP_PIECEWISE3 &&
+              !(T.param >= 1.0 && T.param <= (double)SGP_PIECEWISE_J_MAX && T.param == (double)(int)T.param))
+            return fail("spec: SGP_PIECEWISE (product path): param = j must be an integer in [1, 64]");
           if ((T.kind & 0xff) == SGP_LINEAR && !(T.param >= 0.0 && T.param < 1e300))
             return fail("spec: SGP_LINEAR (product path): param = c must be >= 0 and finite");
           if (T.row_input >= 0 && T.row_input < sp->n_inputs) {

@@ -191,8 +191,9 @@ int launch_diag_grad_stencil_wo(const double* w, long n, const DevTerm& T, int t
 // kprod_group cuts a pair's chain terms [t, t1) into launches (returns how many terms the launch at t carries, *dmax_out = its
 // DMAX) for the matrix and the diagonal alike.  Arguments of launch_assemble_kprod as launch_assemble_block.
 // mn: kprod_mode of those terms' host copies -- 0: none of SGP_MATERN_NU and the kinds of x'y (SGP_NEURALNET, SGP_FBM,
-// SGP_EXPONENTIATED), 1: SGP_MATERN_NU and none of those three, 2: one of the three.  The kernels are instantiated per mode, so
-// that chains without the Bessel routine or without those kinds run what they ran before either existed
+// SGP_EXPONENTIATED), 1: SGP_MATERN_NU and none of those three, 2: one of the three and neither SGP_WIENER nor a
+// SGP_PIECEWISE kind, 3: SGP_WIENER or a SGP_PIECEWISE kind.  The kernels are instantiated per mode, so that chains without
+// the Bessel routine or without those kinds run what they ran before any of them existed
 int kprod_group(const DevTerm* h_terms, int t, int t1, int* dmax_out);
 int kprod_mode(const DevTerm* h_terms, int n);
 int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* d_terms, int nterms,

@@ -1,6 +1,7 @@
 // Product chains (include/sthenomi_kprod.h): covariance terms that multiply several leaf kernels, each on its own view of
 // the points, and the kinds that exist only here: RationalQuadratic, Linear, Cosine, GammaExponential, general-nu Matern and
-// the kinds of x'y: NeuralNetwork, FBM, Exponentiated.
+// the kinds of x'y: NeuralNetwork, FBM, Exponentiated, and Wiener (|x|, |y|, |x - y|) and the compactly supported
+// PiecewisePolynomial kinds.
 //     chain value (i, j) = coef_head rs_i cs_j  prod_f k_f(x^f_i, x'^f_j)
 // KernelFunctions' KernelProduct [EXT] (`k1 * k2`, reached through src/Stheno.jl:4-6); the locally periodic kernel of the
 // Mauna-Loa models and the sums of products of the neural-kernel-network example are such chains.
@@ -26,7 +27,7 @@
 
 namespace sgp {
 
-enum { K_RQ = 6, K_LINEAR = 7, K_COSINE = 16, K_GAMMAEXP = 17, K_MATERN_NU = 20, K_NEURALNET = 24, K_FBM = 25,
+enum { K_RQ = 6, K_LINEAR = 7, K_WIENER = 10, K_PP0 = 11, K_PP3 = 14, K_COSINE = 16, K_GAMMAEXP = 17, K_MATERN_NU = 20, K_NEURALNET = 24, K_FBM = 25,
        K_EXPONENTIATED = 26 };
 constexpr int KP_KIND_MASK = 0xff, KP_TIMES_PREV = 0x100;   // sthenomi.h: SGP_KIND_TIMES_PREV
 constexpr int KP_MAXF = 8;                                  // sthenomi_kprod.h: SGP_KPROD_MAX_FACTORS
@@ -236,6 +237,54 @@ void matern_nu_constants(double nu, double* out) {
   out[MN_KX0] = nu > 1.0 ? (double)(-(long double)nu / (2.0L * ((long double)nu - 1.0L))) : 0.0;
 }
 
+// PiecewisePolynomial (codes 11 .. 14, q = code - 11; param = j, an integer in [1, 64]: the host passes floor(dim / 2) + q + 1):
+//     k = max(1 - r, 0)^(j + q) p_q(r),  r = sqrt(d2)      (Rasmussen & Williams eq. 4.21)
+//   p_0 = 1,  p_1 = 1 + (j + 1) r,  p_2 = 1 + (j + 2) r + (j + 1)(j + 3) / 3 r^2,
+//   p_3 = 1 + (j + 3) r + (6 j^2 + 36 j + 45) / 15 r^2 + (j + 1)(j + 3)(j + 5) / 15 r^3
+// The power is taken by square-and-multiply on t = 1 - r (exact for r >= 1/2), never pow.  k' = -r t^(j+q-1) pt_q(r) for q >= 1:
+//   pt_1 = (j + 1)(j + 2),  pt_2 = (j + 3)(j + 4) / 3 (1 + (j + 1) r),
+//   pt_3 = A0 + A1 r + A2 r^2,  n = j + 3, c2 and c3 the coefficients of r^2 and r^3 in p_3:
+//          A0 = n^2 + n - 2 c2,  A1 = (n + 2) c2 - 3 c3,  A2 = (n + 3) c3   (integer numerators over 15: exact before one division)
+// so kx = d k / d (d2) = k' / (2 r) = -t^(j+q-1) pt_q / 2 is a power times a polynomial, never a quotient by r; q = 0 has
+// kx = -j t^(j-1) / (2 r), and 0 at r == 0 (the subgradient Matern-1/2 has there).  dk = d k / d g = 2 d2 kx, dp = 0.
+// Ends: exactly 1 at d2 == 0 (t = 1, p = 1); exactly 0 with every derivative exactly 0 for r >= 1, an overflowed or NaN d2.
+__device__ __forceinline__ double pp_pow(double t, int e) {
+  double pw = 1.0;
+  for (; e > 0; e >>= 1) {
+    if (e & 1) pw *= t;
+    t *= t;
+  }
+  return pw;
+}
+__device__ __noinline__ KpDerivs pp_derivs(int q, double d2, double j) {
+#pragma clang fp contract(off)
+  KpDerivs o = {0.0, 0.0, 0.0, 0.0};
+  const double r = sqrt(d2);
+  if (!(r < 1.0)) return o;
+  const double t = 1.0 - r;
+  const double pw = pp_pow(t, (int)j + q - 1);   // t^(j+q-1); j + q - 1 >= 0
+  double p = 1.0, pt = 0.0;
+  if (q == 1) {
+    p = 1.0 + (j + 1.0) * r;
+    pt = (j + 1.0) * (j + 2.0);
+  } else if (q == 2) {
+    p = 1.0 + r * ((j + 2.0) + ((j + 1.0) * (j + 3.0) / 3.0) * r);
+    pt = ((j + 3.0) * (j + 4.0) / 3.0) * (1.0 + (j + 1.0) * r);
+  } else if (q == 3) {
+    const double n = j + 3.0, n2 = 6.0 * j * j + 36.0 * j + 45.0, n3 = (j + 1.0) * (j + 3.0) * (j + 5.0);
+    p = 1.0 + r * (n + r * (n2 / 15.0 + (n3 / 15.0) * r));
+    const double a0 = (15.0 * (n * n + n) - 2.0 * n2) / 15.0, a1 = ((n + 2.0) * n2 - 3.0 * n3) / 15.0,
+                 a2 = (n + 3.0) * n3 / 15.0;
+    pt = a0 + r * (a1 + a2 * r);
+  }
+  o.k = (pw * t) * p;
+  if (q == 0) o.kx = r > 0.0 ? -(j * pw) / (2.0 * r) : 0.0;
+  else o.kx = -0.5 * (pw * pt);
+  o.dk = 2.0 * d2 * o.kx;
+  return o;
+}
+__device__ __noinline__ double pp_eval(int q, double d2, double j) { return pp_derivs(q, d2, j).k; }
+
 // one call site per factor in the contractions: the two kinds behind one out-of-line routine
 __device__ __noinline__ KpDerivs newkind_derivs(int kind, double d2, double param) {
   return kind == K_COSINE ? cosine_derivs(d2) : gexp_derivs(d2, param);
@@ -301,7 +350,8 @@ __device__ __forceinline__ double kp_cross(double xi, double yj, double xj, doub
   return p - q;
 }
 // dim <= DMAX coordinates are read (the assembly pads its points with zeros up to DMAX: they add exact zeros)
-template <int DMAX>
+// W: the caller is a mode-3 instantiation (WIENER, PIECEWISE: e = d2 as FBM's)
+template <int DMAX, bool W = false>
 __device__ __forceinline__ KpDot kp_dot_scalars(int kind, const double* x, const double* y) {
   KpDot r = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -310,7 +360,7 @@ __device__ __forceinline__ KpDot kp_dot_scalars(int kind, const double* x, const
     r.a = fma(x[d], x[d], r.a);
     r.b = fma(y[d], y[d], r.b);
   }
-  if (kind == K_FBM) {
+  if (kind == K_FBM || (W && kind < K_COSINE)) {
 #pragma unroll
     for (int d = 0; d < DMAX; ++d) {
       const double df = x[d] - y[d];
@@ -327,6 +377,7 @@ __device__ __forceinline__ KpDot kp_dot_scalars(int kind, const double* x, const
   }
   return r;
 }
+template <bool W = false>
 __device__ __forceinline__ KpDot kp_dot_scalars_n(int kind, const double* x, const double* y, int dim) {
   KpDot r = {0.0, 0.0, 0.0, 0.0};
   for (int d = 0; d < dim; ++d) {
@@ -334,7 +385,7 @@ __device__ __forceinline__ KpDot kp_dot_scalars_n(int kind, const double* x, con
     r.a = fma(x[d], x[d], r.a);
     r.b = fma(y[d], y[d], r.b);
   }
-  if (kind == K_FBM) {
+  if (kind == K_FBM || (W && kind < K_COSINE)) {
     for (int d = 0; d < dim; ++d) {
       const double df = x[d] - y[d];
       r.e = fma(df, df, r.e);
@@ -380,28 +431,110 @@ __device__ __noinline__ KpDotDerivs dotkind_derivs(int kind, double h, double s,
   r.c3 = 1.0 / R;
   return r;
 }
-// The launch mode of every kernel below (the template argument MN): 0 the chains hold none of MATERN_NU and the three kinds
-// above, 1 they hold MATERN_NU and none of the three, 2 they hold one of the three (and possibly MATERN_NU).  Modes 0 and 1
-// are what ran before the three kinds existed: the compiler reports the registers, scratch and LDS they had
+// WIENER (code 10, param = i in {0, 1, 2, 3}): the i-times integrated Wiener process on X = |x| = sqrt(a), Y = |y| = sqrt(b),
+// d = |x - y| = sqrt(e) (e from direct differences, as FBM's), m = min(X, Y), M = max(X, Y):
+//     i = 0  m        i = 1  m^3 / 3 + m^2 d / 2        i = 2  m^5 / 20 + m^3 d (X + Y - m / 2) / 12
+//     i = 3  m^7 / 252 + m^4 d (5 M^2 + 2 X Y + 3 m^2) / 720
+// Every term is positive, the square roots are correctly rounded, min / max, X + Y and X Y are symmetric bit for bit: so is k.
+// m = 0 against the origin gives exactly 0; d = 0 exactly on the diagonal leaves the single first term.
+// Derivatives: k is a function of (m, M, S = X + Y, P = X Y, d); with wx = d m / d X = 1, 0 or -- at a tie X == Y, which
+// includes the diagonal -- 1/2 (the rule FBM follows at h = 1/2), wy = 1 - wx, d M / d X = wy:
+//     kX = wx km + wy kM + kS + kP Y,   kY = wy km + wx kM + kS + kP X
+//     d k / d x = c1 x + c2 (x - y),  c1 = kX / X (0 at X == 0),  c2 = kd / d (0 at d == 0),  c3 = 0;  c1y = kY / Y
+//     dk = d k / d g = (2 i + 1) k (homogeneous),  dp = 0 (i is discrete)
+struct KpWiener {
+  double k, km, kM, kS, kP, kd;
+};
+__device__ __forceinline__ KpWiener wiener_parts(int i, double X, double Y, double d) {
+#pragma clang fp contract(off)
+  KpWiener o = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const double m = fmin(X, Y), M = fmax(X, Y), m2 = m * m;
+  if (i == 0) {
+    o.k = m;
+    o.km = 1.0;
+  } else if (i == 1) {
+    o.k = m2 * m / 3.0 + m2 * d * 0.5;
+    o.km = m2 + m * d;
+    o.kd = 0.5 * m2;
+  } else if (i == 2) {
+    const double m3 = m2 * m, S = X + Y, T = S - 0.5 * m;
+    o.k = m3 * m2 / 20.0 + m3 * d * T / 12.0;
+    o.km = m2 * m2 / 4.0 + m2 * d * (3.0 * S - 2.0 * m) / 12.0;
+    o.kS = m3 * d / 12.0;
+    o.kd = m3 * T / 12.0;
+  } else {
+    const double m3 = m2 * m, m4 = m2 * m2, Q = (5.0 * (M * M) + 2.0 * (X * Y)) + 3.0 * m2;
+    o.k = m4 * m3 / 252.0 + m4 * d * Q / 720.0;
+    o.km = (m4 * m2 / 36.0 + m3 * d * Q / 180.0) + m4 * m * d / 120.0;
+    o.kM = m4 * d * M / 72.0;
+    o.kP = m4 * d / 360.0;
+    o.kd = m4 * Q / 720.0;
+  }
+  return o;
+}
+__device__ __noinline__ double wiener_eval(double p, double a, double b, double e) {
+  return wiener_parts((int)p, sqrt(a), sqrt(b), sqrt(e)).k;
+}
+__device__ __noinline__ KpDotDerivs wiener_derivs(double p, double a, double b, double e) {
+#pragma clang fp contract(off)
+  KpDotDerivs r = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const double X = sqrt(a), Y = sqrt(b), d = sqrt(e);
+  const KpWiener w = wiener_parts((int)p, X, Y, d);
+  const double wx = X < Y ? 1.0 : (X > Y ? 0.0 : 0.5), wy = 1.0 - wx;
+  const double kX = ((wx * w.km + wy * w.kM) + w.kS) + w.kP * Y, kY = ((wy * w.km + wx * w.kM) + w.kS) + w.kP * X;
+  r.k = w.k;
+  r.dk = (2.0 * p + 1.0) * w.k;
+  r.c1 = X > 0.0 ? kX / X : 0.0;
+  r.c1y = Y > 0.0 ? kY / Y : 0.0;
+  r.c2 = d > 0.0 ? w.kd / d : 0.0;
+  return r;
+}
+// mode 3 (below): WIENER, PIECEWISE and the three kinds above behind one call site each.  A PIECEWISE kind goes the same way
+// with e = d2, c2 = 2 kx and c1 = c3 = 0
+__device__ __noinline__ double dotkind_eval_w(int kind, double h, double s, double a, double b, double e) {
+  if (kind >= K_NEURALNET) return dotkind_eval(kind, h, s, a, b, e);
+  if (kind == K_WIENER) return wiener_eval(h, a, b, e);
+  return pp_eval(kind - K_PP0, e, h);
+}
+__device__ __noinline__ KpDotDerivs dotkind_derivs_w(int kind, double h, double s, double a, double b, double e) {
+  if (kind >= K_NEURALNET) return dotkind_derivs(kind, h, s, a, b, e);
+  if (kind == K_WIENER) return wiener_derivs(h, a, b, e);
+  const KpDerivs q = pp_derivs(kind - K_PP0, e, h);
+  KpDotDerivs r = {q.k, q.dk, 0.0, 0.0, 0.0, 2.0 * q.kx, 0.0};
+  return r;
+}
+// The launch mode of every kernel below (the template argument MN): 0 the chains hold none of MATERN_NU and the kinds
+// above, 1 they hold MATERN_NU and none of those, 2 they hold one of NEURALNET / FBM / EXPONENTIATED (and possibly MATERN_NU)
+// and none of WIENER / PIECEWISE, 3 they hold a WIENER or PIECEWISE factor (and possibly any other kind).  Modes 0 to 2
+// are what ran before WIENER and PIECEWISE existed: the compiler reports the registers, scratch and LDS they had
 // (tools/kprod_resources.py; docs/03_kernels.md section 3.2e)
+__host__ __device__ __forceinline__ bool kp_is_wpp(int kind) { return kind >= K_WIENER && kind <= K_PP3; }
 int kprod_mode(const DevTerm* h_terms, int n) {
   int mode = 0;
   for (int t = 0; t < n; ++t) {
     const int kind = h_terms[t].kind & KP_KIND_MASK;
-    if (kind >= K_NEURALNET) return 2;
-    if (kind == K_MATERN_NU) mode = 1;
+    if (kp_is_wpp(kind)) return 3;
+    if (kind >= K_NEURALNET) mode = 2;
+    else if (kind == K_MATERN_NU && mode < 2) mode = 1;
   }
   return mode;
 }
+// Whether `kind` takes the route of the scalars (s, a, b, e) in launch mode MN, and that route's two calls.  Written so that a
+// mode-2 instantiation is, once the constant conditions are folded, the very code it was before mode 3 existed
+#define KP_DOT_ROUTE(MN, kind) ((MN) == 3 ? ((kind) >= K_NEURALNET || kp_is_wpp(kind)) : ((MN) == 2 && (kind) >= K_NEURALNET))
+#define KP_DOT_EVAL(MN, kind, h, r) \
+  ((MN) == 3 ? dotkind_eval_w(kind, h, (r).s, (r).a, (r).b, (r).e) : dotkind_eval(kind, h, (r).s, (r).a, (r).b, (r).e))
+#define KP_DOT_DERIVS(MN, kind, h, r) \
+  ((MN) == 3 ? dotkind_derivs_w(kind, h, (r).s, (r).a, (r).b, (r).e) : dotkind_derivs(kind, h, (r).s, (r).a, (r).b, (r).e))
 
 // one factor of one of the three kinds over a chunk of columns
-template <int DMAX>
+template <int DMAX, int MN>
 __device__ __forceinline__ void factor_chunk_dot(int kind, double (&prod)[KP_CHUNK], const double (&xi)[DMAX], const double* sp,
                                                  double param, bool head) {
 #pragma unroll
   for (int q = 0; q < KP_CHUNK; ++q) {
-    const KpDot r = kp_dot_scalars<DMAX>(kind, xi, sp + q * DMAX);
-    const double k = dotkind_eval(kind, param, r.s, r.a, r.b, r.e);
+    const KpDot r = kp_dot_scalars<DMAX, MN == 3>(kind, xi, sp + q * DMAX);
+    const double k = KP_DOT_EVAL(MN, kind, param, r);
     prod[q] = head ? k : prod[q] * k;
   }
 }
@@ -427,8 +560,8 @@ __device__ __forceinline__ void factor_chunk(double (&prod)[KP_CHUNK], const dou
 template <int DMAX, int MN>
 __device__ __forceinline__ void factor_chunk_any(int kind, double (&prod)[KP_CHUNK], const double (&xi)[DMAX],
                                                  const double* sp, double param, bool head, const double* nuc) {
-  if (MN == 2 && kind >= K_NEURALNET) {
-    factor_chunk_dot<DMAX>(kind, prod, xi, sp, param, head);
+  if (KP_DOT_ROUTE(MN, kind)) {
+    factor_chunk_dot<DMAX, MN>(kind, prod, xi, sp, param, head);
     return;
   }
   if (MN && kind == K_MATERN_NU) {
@@ -572,7 +705,10 @@ int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc
 #define SGP_KP(DM)                                                                                                     \
   do {                                                                                                                 \
     const size_t lds = (size_t)nterms * TILE * DM * sizeof(double);                                                    \
-    if (mn == 2)                                                                                                       \
+    if (mn == 3)                                                                                                       \
+      hipLaunchKernelGGL((assemble_kprod_kernel<DM, 3>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms,  \
+                         lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first);        \
+    else if (mn == 2)                                                                                                  \
       hipLaunchKernelGGL((assemble_kprod_kernel<DM, 2>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms,  \
                          lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first);        \
     else if (mn)                                                                                                       \
@@ -598,9 +734,9 @@ __device__ __forceinline__ double kp_factor_diag(const DevTerm& T, long i) {
   const int kind = T.kind & KP_KIND_MASK;
   const double* a = T.xr + i * T.ldr;
   const double* b = T.xc + i * T.ldc;
-  if (MN == 2 && kind >= K_NEURALNET) {
-    const KpDot r = kp_dot_scalars_n(kind, a, b, T.dim);
-    return dotkind_eval(kind, T.param, r.s, r.a, r.b, r.e);
+  if (KP_DOT_ROUTE(MN, kind)) {
+    const KpDot r = kp_dot_scalars_n<MN == 3>(kind, a, b, T.dim);
+    return KP_DOT_EVAL(MN, kind, T.param, r);
   }
   if (kind == K_LINEAR) {
     double s = 0.0;
@@ -644,7 +780,10 @@ __global__ void diag_kprod_kernel(double* out, long n, const DevTerm* terms, int
 
 int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int mn, int accumulate, hipStream_t s) {
   if (n <= 0 || nterms <= 0) return 0;
-  if (mn == 2)
+  if (mn == 3)
+    hipLaunchKernelGGL(diag_kprod_kernel<3>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
+                       accumulate);
+  else if (mn == 2)
     hipLaunchKernelGGL(diag_kprod_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d_terms, nterms,
                        accumulate);
   else if (mn)
@@ -662,9 +801,9 @@ int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, i
 template <int DMAX, int MN>
 __device__ __forceinline__ void kp_factor_grad(int kind, double param, const double* xr, const double* sp, double& k,
                                                double& dk, double& dp, const DevTerm* term) {
-  if (MN == 2 && kind >= K_NEURALNET) {
-    const KpDot q = kp_dot_scalars<DMAX>(kind, xr, sp);
-    const KpDotDerivs r = dotkind_derivs(kind, param, q.s, q.a, q.b, q.e);
+  if (KP_DOT_ROUTE(MN, kind)) {
+    const KpDot q = kp_dot_scalars<DMAX, MN == 3>(kind, xr, sp);
+    const KpDotDerivs r = KP_DOT_DERIVS(MN, kind, param, q);
     k = r.k;
     dk = r.dk;
     dp = r.dp;
@@ -881,7 +1020,8 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
   }
   int rc;
 #define SGP_KG(DM)                                                                                                     \
-  rc = mn == 2 ? launch_grad_kprod_t<DM, 2>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s) \
+  rc = mn == 3 ? launch_grad_kprod_t<DM, 3>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s) \
+       : mn == 2 ? launch_grad_kprod_t<DM, 2>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s) \
        : mn    ? launch_grad_kprod_t<DM, 1>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s) \
                : launch_grad_kprod_t<DM, 0>(Kinv, ldk, alpha, r0, nr, c0, nc, d_terms, nf, trf, tcf, trc, tcc, partials, s)
   if (dmax <= 1) SGP_KG(1);
@@ -908,12 +1048,13 @@ int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0
 // without it
 // NK == 3: the chain holds a NEURALNET / FBM / EXPONENTIATED factor (and possibly any other kind).  Such a factor has
 // d k / d x = c1 x + c2 (x - x') + c3 x' (KpDotDerivs), c2 = 2 kx; c1 and c3 exist in that instantiation only.
+// NK == 4: the chain holds a WIENER / PIECEWISE factor (and possibly any other kind): launch mode 3 of the kernels above.
 template <int DMAX, int NK>
 __device__ __forceinline__ void kp_factor_dx(int kind, double param, const double* xr, const double* sp, double& k,
                                              double& kx, const double* nuc, double& c1, double& c3) {
-  if (NK == 3 && kind >= K_NEURALNET) {
-    const KpDot q = kp_dot_scalars<DMAX>(kind, xr, sp);
-    const KpDotDerivs r = dotkind_derivs(kind, param, q.s, q.a, q.b, q.e);
+  if (KP_DOT_ROUTE(NK - 1, kind)) {
+    const KpDot q = kp_dot_scalars<DMAX, NK == 4>(kind, xr, sp);
+    const KpDotDerivs r = KP_DOT_DERIVS(NK - 1, kind, param, q);
     k = r.k;
     kx = 0.5 * r.c2;
     c1 = r.c1;
@@ -1021,15 +1162,15 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
         const double gm = Gm[grow * sr + gc * sc];
         const double g = alpha ? 0.5 * (ai * alpha[gc] - gm) : gm;
         double k[TMAX], kx[TMAX], pre[TMAX + 1];
-        double c1[NK == 3 ? TMAX : 1], c3[NK == 3 ? TMAX : 1];   // NEURALNET / FBM / EXPONENTIATED: kp_factor_dx
+        double c1[NK >= 3 ? TMAX : 1], c3[NK >= 3 ? TMAX : 1];   // NEURALNET / FBM / EXPONENTIATED / WIENER: kp_factor_dx
         pre[0] = 1.0;
 #pragma unroll
         for (int f = 0; f < TMAX; ++f) {
           k[f] = 1.0;
           kx[f] = 0.0;
-          if (NK == 3) c1[NK == 3 ? f : 0] = c3[NK == 3 ? f : 0] = 0.0;
+          if (NK >= 3) c1[NK >= 3 ? f : 0] = c3[NK >= 3 ? f : 0] = 0.0;
           if (f < nf) kp_factor_dx<DMAX, NK>(kind[f], param[f], &xr[f * DMAX], &sx[(f * TILE + p) * DMAX], k[f], kx[f],
-                                              NK >= 2 ? C.t[f].nuc : nullptr, c1[NK == 3 ? f : 0], c3[NK == 3 ? f : 0]);
+                                              NK >= 2 ? C.t[f].nuc : nullptr, c1[NK >= 3 ? f : 0], c3[NK >= 3 ? f : 0]);
           pre[f + 1] = pre[f] * k[f];
         }
         const double gcs = g * scs[p];
@@ -1041,8 +1182,8 @@ __global__ __launch_bounds__(256) void grad_kprod_inputs_kernel(const double* Gm
           if (f < nf) {
             const double excl = w * (pre[f] * suf);
             const double* sp = &sx[(f * TILE + p) * DMAX];
-            if (NK == 3 && kind[f] >= K_NEURALNET) {
-              const double e1 = excl * c1[NK == 3 ? f : 0], e2 = 2.0 * excl * kx[f], e3 = excl * c3[NK == 3 ? f : 0];
+            if (KP_DOT_ROUTE(NK - 1, kind[f])) {
+              const double e1 = excl * c1[NK >= 3 ? f : 0], e2 = 2.0 * excl * kx[f], e3 = excl * c3[NK >= 3 ? f : 0];
 #pragma unroll
               for (int d = 0; d < DMAX; ++d) {
                 const double xv = xr[f * DMAX + d];
@@ -1125,10 +1266,11 @@ int launch_grad_kprod_inputs(const double* Gm, long sr, long sc, const double* a
   int nk = 0;
   for (int f = 0; f < nf; ++f) {
     const int kind = h_terms[f].kind & KP_KIND_MASK;
-    nk = std::max(nk, kind >= K_NEURALNET ? 3 : kind == K_MATERN_NU ? 2 : (kind == K_COSINE || kind == K_GAMMAEXP) ? 1 : 0);
+    nk = std::max(nk, kp_is_wpp(kind) ? 4 : kind >= K_NEURALNET ? 3 : kind == K_MATERN_NU ? 2 : (kind == K_COSINE || kind == K_GAMMAEXP) ? 1 : 0);
   }
 #define SGP_KI(DM)                                                                                                     \
-  rc = nk == 3 ? launch_grad_kprod_inputs_t<DM, 3>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
+  rc = nk == 4 ? launch_grad_kprod_inputs_t<DM, 4>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
+       : nk == 3 ? launch_grad_kprod_inputs_t<DM, 3>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)          \
        : nk == 2 ? launch_grad_kprod_inputs_t<DM, 2>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)          \
        : nk    ? launch_grad_kprod_inputs_t<DM, 1>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)            \
                : launch_grad_kprod_inputs_t<DM, 0>(Gm, sr, sc, alpha, r0, nr, c0, nc, C, nf, scale, gsv, s)
@@ -1163,22 +1305,22 @@ __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, l
   for (int f = 0; f < KP_MAXF; ++f) gs_acc[f] = gp_acc[f] = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) {
     double k[KP_MAXF], dk[KP_MAXF], dp[KP_MAXF], kx[KP_MAXF], pre[KP_MAXF + 1];
-    constexpr int NDOT = MN == 2 ? KP_MAXF : 1;   // NEURALNET / FBM / EXPONENTIATED: the coefficients of KpDotDerivs
+    constexpr int NDOT = MN >= 2 ? KP_MAXF : 1;   // NEURALNET / FBM / EXPONENTIATED: the coefficients of KpDotDerivs
     double c1[NDOT], c1y[NDOT], c3[NDOT];
     pre[0] = 1.0;
 #pragma unroll
     for (int f = 0; f < KP_MAXF; ++f) {
       k[f] = 1.0;
       dk[f] = dp[f] = kx[f] = 0.0;
-      if (MN == 2) c1[f % NDOT] = c1y[f % NDOT] = c3[f % NDOT] = 0.0;
+      if (MN >= 2) c1[f % NDOT] = c1y[f % NDOT] = c3[f % NDOT] = 0.0;
       if (f < nf) {
         const DevTerm& T = C.t[f];
         const int kind = T.kind & KP_KIND_MASK;
         const double* a = T.xr + i * T.ldr;
         const double* b = T.xc + i * T.ldc;
-        if (MN == 2 && kind >= K_NEURALNET) {
-          const KpDot q = kp_dot_scalars_n(kind, a, b, T.dim);
-          const KpDotDerivs r = dotkind_derivs(kind, T.param, q.s, q.a, q.b, q.e);
+        if (KP_DOT_ROUTE(MN, kind)) {
+          const KpDot q = kp_dot_scalars_n<MN == 3>(kind, a, b, T.dim);
+          const KpDotDerivs r = KP_DOT_DERIVS(MN, kind, T.param, q);
           k[f] = r.k;
           dk[f] = r.dk;
           dp[f] = r.dp;
@@ -1249,7 +1391,7 @@ __global__ __launch_bounds__(256) void diag_grad_kprod_kernel(const double* w, l
       const double* b = T.xc + i * T.ldc;
       double* orow = C.gxr[f] + i * T.dim;
       double* ocol = C.gxc[f] + i * T.dim;
-      if (MN == 2 && (T.kind & KP_KIND_MASK) >= K_NEURALNET) {
+      if (KP_DOT_ROUTE(MN, T.kind & KP_KIND_MASK)) {
         // LINEAR's convention: the row input receives d k / d x, the column input d k / d y, both added when they are one array
         const double e1 = excl[f] * c1[f % NDOT], e1y = excl[f] * c1y[f % NDOT], e2 = 2.0 * excl[f] * kx[f],
                      e3 = excl[f] * c3[f % NDOT];
@@ -1323,7 +1465,10 @@ int launch_diag_grad_kprod(const double* w, long n, const DevTerm* h_terms, int 
     C.gxc[f] = (f < nf && gxc) ? gxc[f] : nullptr;
   }
   const int mode = kprod_mode(h_terms, nf);
-  if (mode == 2)
+  if (mode == 3)
+    hipLaunchKernelGGL(diag_grad_kprod_kernel<3>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
+                       out_rs, out_cs);
+  else if (mode == 2)
     hipLaunchKernelGGL(diag_grad_kprod_kernel<2>, dim3(1), dim3(256), 0, s, w, n, C, nf, out_coef, out_scale, out_param,
                        out_rs, out_cs);
   else if (mode)

@@ -357,6 +357,11 @@ def build_spec(f, x, f2=None, x2=None):
                                 chain.append((kind, param, ri, ci))
                             # the library's limits (include/sthenomi_kprod.h), named here as it names them
                             dims = [int(np.asarray(table.arrays[c[2]]).shape[0]) for c in chain]
+                            for (kind, param, _, _), dm in zip(chain, dims):
+                                if _lib.PIECEWISE0 <= kind <= _lib.PIECEWISE3 and dm > _kernels.piecewise_max_dim(kind, param):
+                                    raise ValueError(f"PiecewisePolynomialKernel (degree {kind - _lib.PIECEWISE0}, j = {int(param)}) is "
+                                                     f"positive definite up to dimension {_kernels.piecewise_max_dim(kind, param)} "
+                                                     f"and reads points of dimension {dm} after its transforms: pass dim >= {dm}")
                             dmax = 1 << max(0, max(dims) - 1).bit_length()
                             if max(dims) > _lib.KPROD_MAX_DIM or len(chain) * dmax > 64:
                                 raise NotImplementedError(f"a product of {len(chain)} kernels (or a kernel of the product path) on "

@@ -336,6 +336,59 @@ class ExponentiatedKernel(_Simple):
     kind = _lib.EXPONENTIATED
 
 
+def WienerKernel(i=0):
+    """KernelFunctions' WienerKernel{i}: the i-times integrated Wiener process, i = 0 .. 3, a function of |x|, |y| and
+    |x - y| (include/sthenomi_kprod.h: SGP_WIENER, param = i).  i = -1 is WhiteKernel(), as in KernelFunctions.  i >= 1 is not
+    known to be positive definite beyond the half line."""
+    if i == -1:
+        return WhiteKernel()
+    if isinstance(i, bool) or i not in (0, 1, 2, 3):
+        raise ValueError(f"WienerKernel: i must be -1, 0, 1, 2 or 3, not {i!r}")
+    return _WienerKernel(int(i))
+
+
+class _WienerKernel(Kernel):
+    def __init__(self, i):
+        self.i = i
+
+    def leaf_terms(self):
+        return [(_lib.WIENER, 1.0, float(self.i), ())]
+
+
+class PiecewisePolynomialKernel(Kernel):
+    """max(1 - d, 0)^(j + q) p_q(d), j = floor(dim / 2) + q + 1, q = degree in 0 .. 3 (KernelFunctions
+    PiecewisePolynomialKernel{q}(dim), Rasmussen & Williams eq. 4.21): compactly supported, exactly 0 beyond distance 1.
+    Positive definite on inputs of dimension <= dim only: build_spec raises ValueError where the kernel reads more.
+    Evaluated on the product path (SGP_PIECEWISE0 .. 3: the code carries q, param = j)."""
+
+    def __init__(self, degree=0, *, dim):
+        if isinstance(degree, bool) or degree not in (0, 1, 2, 3):
+            raise ValueError(f"PiecewisePolynomialKernel: degree must be 0, 1, 2 or 3, not {degree!r}")
+        if isinstance(dim, bool) or dim != int(dim) or dim < 1:
+            raise ValueError(f"PiecewisePolynomialKernel: dim must be a positive integer, not {dim!r}")
+        self.degree, self.dim = int(degree), int(dim)
+        self.j = self.dim // 2 + self.degree + 1
+        if self.j > _lib.PIECEWISE_J_MAX:
+            raise ValueError(f"PiecewisePolynomialKernel: j = dim // 2 + degree + 1 = {self.j} is beyond {_lib.PIECEWISE_J_MAX}")
+
+    def leaf_terms(self):
+        return [(_lib.PIECEWISE0 + self.degree, 1.0, float(self.j), ())]
+
+
+def piecewise_max_dim(kind, j):
+    """the largest input dimension at which a SGP_PIECEWISE term (kind, param = j) is positive definite: j = floor(dim / 2) +
+    q + 1 gives dim <= 2 (j - q - 1) + 1"""
+    return 2 * (int(j) - (kind - _lib.PIECEWISE0) - 1) + 1
+
+
+def RationalKernel(alpha=2.0):
+    """(1 + d^2 / alpha)^-alpha (KernelFunctions RationalKernel): RationalQuadraticKernel(alpha) o ScaleTransform(sqrt 2), a
+    name on the host; d / d alpha comes back in d_param"""
+    if not float(alpha) > 0.0:
+        raise ValueError("RationalKernel: alpha must be > 0")
+    return TransformedKernel(RationalQuadraticKernel(alpha), ScaleTransform(np.sqrt(2.0)))
+
+
 class PolynomialKernel(Kernel):
     """(x'y + c)^degree: a chain of `degree` LINEAR factors"""
 

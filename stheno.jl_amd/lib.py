@@ -22,6 +22,9 @@ RQ, LINEAR = 6, 7                  # evaluated by the product-chain path only (i
 COSINE, GAMMAEXP = 16, 17          # the same path (8 .. 15 are no kinds)
 MATERN_NU = 20                     # general-nu Matern, the same path (18, 19 are no kinds); nu in (0, MATERN_NU_MAX]
 MATERN_NU_MAX = 32.0
+WIENER = 10                        # WienerKernel{i}, param = i in {0, 1, 2, 3}; the same path (8, 9 and 15 are no kinds)
+PIECEWISE0, PIECEWISE1, PIECEWISE2, PIECEWISE3 = 11, 12, 13, 14   # PiecewisePolynomialKernel{q}: the code carries q, param = j
+PIECEWISE_J_MAX = 64
 NEURALNET, FBM, EXPONENTIATED = 24, 25, 26   # kinds of x'y, x'x and y'y, the same path (21 .. 23 and 27+ are no kinds)
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
