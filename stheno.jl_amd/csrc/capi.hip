@@ -7,6 +7,7 @@
 #include "df_tasks.h"
 #include "df_pool.h"
 #include "../../include/sthenomi_kprod.h"
+#include "kprod_kinds_table.h"
 #include <limits>
 
 #include <algorithm>
@@ -308,19 +309,6 @@ extern "C" int sgp_ctx_destroy(sgp_ctx* c) {
 // ---------------------------------------------------------------------------------------
 // device-resident specs
 // ---------------------------------------------------------------------------------------
-// the kinds of include/sthenomi.h: 0 .. 7, 10 .. 14, 16 / 17, 20 and 24 .. 26 (8, 9, 15, 18, 19, 21 .. 23 and everything above stay
-// unknown)
-static bool kind_known(int k) {
-  return (k >= SGP_SE && k <= SGP_LINEAR) || k == SGP_COSINE || k == SGP_GAMMAEXP || k == SGP_MATERN_NU ||
-         (k >= SGP_NEURALNET && k <= SGP_EXPONENTIATED) || (k >= SGP_WIENER && k <= SGP_PIECEWISE3);
-}
-
-static int pow2ceil(int d) {
-  int p = 1;
-  while (p < d) p <<= 1;
-  return p;
-}
-
 // Uploads a spec with ONE host -> device copy: inputs (packed to ld == dim), row / column scale
 // vectors and the term table are laid out in a pinned staging buffer of the context and moved in
 // one piece into one cached device block.  Caller holds the context (CtxScope / ctx->mu).
@@ -386,7 +374,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
       int chain_len = 0, chain_dmax = 1;
       for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t) {
         const sgp_term& T = sp->terms[t];
-        if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) || !kind_known(T.kind & 0xff))
+        if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) || !kp_kind_known(T.kind & 0xff))
           return fail("spec: unknown kernel kind");
         const bool cont = (T.kind & SGP_KIND_TIMES_PREV) != 0;
         const bool next_cont = t + 1 < sp->term_ptr[p + 1] && sp->terms[t + 1].kind >= 0 &&
@@ -400,21 +388,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
                         "LINEAR kinds)");
           if (cont && (T.coef != 1.0 || T.row_scale || T.col_scale))
             return fail("spec: product chain: a continuation must have coef == 1.0 and NULL scales (the head carries them)");
-          if ((T.kind & 0xff) == SGP_RQ && !(T.param > 0.0 && T.param < 1e300))
-            return fail("spec: SGP_RQ (product path): param = alpha must be > 0 and finite");
-          if ((T.kind & 0xff) == SGP_GAMMAEXP && !(T.param > 0.0 && T.param <= 2.0))
-            return fail("spec: SGP_GAMMAEXP (product path): param = gamma must be in (0, 2]");
-          if ((T.kind & 0xff) == SGP_MATERN_NU && !(T.param > 0.0 && T.param <= SGP_MATERN_NU_MAX))
-            return fail("spec: SGP_MATERN_NU (product path): param = nu must be finite and in (0, 32]");
-          if ((T.kind & 0xff) == SGP_FBM && !(T.param > 0.0 && T.param <= 1.0))
-            return fail("spec: SGP_FBM (product path): param = h must be finite and in (0, 1]");
-          if ((T.kind & 0xff) == SGP_WIENER && !(T.param == 0.0 || T.param == 1.0 || T.param == 2.0 || T.param == 3.0))
-            return fail("spec: SGP_WIENER (product path): param = i must be exactly 0, 1, 2 or 3");
-          if ((T.kind & 0xff) >= SGP_PIECEWISE0 && (T.kind & 0xff) <= SGP_PIECEWISE3 &&
-              !(T.param >= 1.0 && T.param <= (double)SGP_PIECEWISE_J_MAX && T.param == (double)(int)T.param))
-            return fail("spec: SGP_PIECEWISE (product path): param = j must be an integer in [1, 64]");
-          if ((T.kind & 0xff) == SGP_LINEAR && !(T.param >= 0.0 && T.param < 1e300))
-            return fail("spec: SGP_LINEAR (product path): param = c must be >= 0 and finite");
+          if (const char* refusal = kp_param_refusal(T.kind & 0xff, T.param)) return fail(refusal);   // kprod_kinds_table.h
           if (T.row_input >= 0 && T.row_input < sp->n_inputs) {
             const int64_t dim = sp->inputs[T.row_input].dim;
             if (dim > SGP_KPROD_MAX_DIM)
@@ -673,9 +647,8 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       for (int t = tk; t < t1;) {   // whole chains per launch, as many as fit its LDS (kprod.hip: kprod_group)
         int kdmax = 1;
         const int cnt = kprod_group(ds->h_terms.data(), t, t1, &kdmax);
-        CHECK_RC(launch_assemble_kprod(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, kdmax,
-                                       kprod_mode(ds->h_terms.data() + t, cnt), lower_only, t > t0 ? 1 : 0,
-                                       t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+        CHECK_RC(launch_assemble_kprod(Kv, ld, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, kdmax, lower_only,
+                                       t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
         t += cnt;
       }
     }
@@ -1651,8 +1624,7 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
     for (int t = t1; t < t1k;) {   // product chains, in the launch groups of the matrix assembly: the same sums
       int kdmax = 1;
       const int cnt = kprod_group(ds->h_terms.data(), t, t1k, &kdmax);
-      CHECK_RC(launch_diag_kprod(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t, cnt,
-                                 kprod_mode(ds->h_terms.data() + t, cnt), 1, s));
+      CHECK_RC(launch_diag_kprod(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
       t += cnt;
     }
   }
@@ -1978,13 +1950,12 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
                                      s));
       for (int t = t0; dgp && t < tp; ++t)
         if (ds->h_terms[t].kind == SGP_CONST)
-          CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, 1, 1, 0, trf, tcf, trl - trf, tcl - tcf,
-                                     dpart.p, nullptr, nullptr, dgp + t, s));
+          CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, 1, 1, trf, tcf,
+                                     trl - trf, tcl - tcf, dpart.p, nullptr, nullptr, dgp + t, s));
       for (int t = tk; t < t1;) {
         const int e = chain_end(ds, t, t1), cdmax = chain_dmax(ds, t, e);
-        CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, e - t, cdmax,
-                                   kprod_mode(ds->h_terms.data() + t, e - t), trf, tcf, trl - trf,
-                                   tcl - tcf, dpart.p, dgc + t, dgs + t, dgp ? dgp + t : nullptr, s));
+        CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, e - t, cdmax, trf,
+                                   tcf, trl - trf, tcl - tcf, dpart.p, dgc + t, dgs + t, dgp ? dgp + t : nullptr, s));
         t = e;
       }
     }

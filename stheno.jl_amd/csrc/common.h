@@ -190,23 +190,21 @@ int launch_diag_grad_stencil_wo(const double* w, long n, const DevTerm& T, int t
 // kprod.hip: product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h).  The terms of one launch are whole chains;
 // kprod_group cuts a pair's chain terms [t, t1) into launches (returns how many terms the launch at t carries, *dmax_out = its
 // DMAX) for the matrix and the diagonal alike.  Arguments of launch_assemble_kprod as launch_assemble_block.
-// mn: kprod_mode of those terms' host copies -- 0: none of SGP_MATERN_NU and the kinds of x'y (SGP_NEURALNET, SGP_FBM,
-// SGP_EXPONENTIATED), 1: SGP_MATERN_NU and none of those three, 2: one of the three and neither SGP_WIENER nor a
-// SGP_PIECEWISE kind, 3: SGP_WIENER or a SGP_PIECEWISE kind.  The kernels are instantiated per mode, so that chains without
-// the Bessel routine or without those kinds run what they ran before any of them existed
+// Every launcher takes the host copies of its terms (h_terms; where the kernel reads them from device memory, d_terms too,
+// as launch_grad_conv does) and picks the kernel instantiation from their kinds: kprod_kinds_table.h
 int kprod_group(const DevTerm* h_terms, int t, int t1, int* dmax_out);
-int kprod_mode(const DevTerm* h_terms, int n);
-int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* d_terms, int nterms,
-                          int dmax, int mn, int lower_only, int accumulate, int noise_kind, double sigma2,
+int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* h_terms,
+                          const DevTerm* d_terms, int nterms, int dmax, int lower_only, int accumulate, int noise_kind, double sigma2,
                           const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
                           long tile_c_cnt, hipStream_t s);
 // out[i] (i < n) = (accumulate ? out[i] : 0) + the chains of one launch group, summed as launch_assemble_kprod sums entry (i, i)
-int launch_diag_kprod(double* out, long n, const DevTerm* d_terms, int nterms, int mn, int accumulate, hipStream_t s);
+int launch_diag_kprod(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
+                      hipStream_t s);
 // gradient contraction of ONE chain (nf factors at d_terms): out_coef / out_scale / out_param point at the chain's first entry
 // (nf each; any may be NULL); partials: tile rows x tile columns x 24 doubles
 int launch_grad_kprod(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
-                      const DevTerm* d_terms, int nf, int dmax, int mn, long trf, long tcf, long trc, long tcc,
-                      double* partials, double* out_coef, double* out_scale, double* out_param, hipStream_t s);
+                      const DevTerm* h_terms, const DevTerm* d_terms, int nf, int dmax, long trf, long tcf, long trc,
+                      long tcc, double* partials, double* out_coef, double* out_scale, double* out_param, hipStream_t s);
 
 // input-point gradients and the head's row-scale sums of ONE chain over one block pair (kprod.hip: grad_kprod_inputs_kernel):
 // h_terms the chain's nf factors (host copies), gx[f] the gradient of factor f's row input (NULL: not asked for), G addressed
