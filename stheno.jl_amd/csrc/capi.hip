@@ -8,6 +8,7 @@
 #include "df_pool.h"
 #include "../../include/sthenomi_kprod.h"
 #include "kprod_kinds_table.h"
+#include "spec_segments.h"
 #include <limits>
 
 #include <algorithm>
@@ -602,6 +603,14 @@ extern "C" int sgp_dspec_destroy(sgp_dspec* ds) {
   return 0;
 }
 
+// which terms of pair p are what (spec_segments.h), from the counts dspec_create fills for every spec
+static inline PairSegs pair_segments(const sgp_dspec* ds, int p) {
+  return pair_segments(ds->term_ptr.data(), ds->pair_nplain.data(), ds->pair_npatch.data(), ds->pair_nkprod.data(), p);
+}
+// the chain whose head sits at device position t: one past its last factor, and its DMAX
+static inline int chain_end(const sgp_dspec* ds, int t, int t1) { return chain_end(ds->h_terms.data(), t, t1); }
+static inline int chain_dmax(const sgp_dspec* ds, int t, int e) { return chain_dmax(ds->h_terms.data(), t, e); }
+
 // Assemble the block pairs of `ds` into the matrix whose element (r, c) (global indices,
 // optionally shifted by row_shift) lives at Kv[r + row_shift + c*ld], restricted to the
 // global tile window [tile_r_lo, tile_r_hi) x [tile_c_lo, tile_c_hi).
@@ -618,7 +627,7 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       long tcf = std::max(c0 / TILE, tile_c_lo), tcl = std::min((c0 + nc - 1) / TILE + 1, tile_c_hi);
       if (trf >= trl || tcf >= tcl) continue;
       int p = I * ds->ncb + J;
-      int t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
+      const auto [t0, tp, ts, tk, t1] = pair_segments(ds, p);   // plain | patch (conv.hip) | stencil (stencil.hip) | chains (kprod.hip)
       int dmax = ds->pair_dmax[p];
       int per = assemble_terms_per_launch(dmax);  // terms per launch: <= 64 KiB of LDS
       int nk = (ds->symmetric && I == J) ? noise_kind : -1;
@@ -627,10 +636,6 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
                                        sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
         continue;
       }
-      const bool structured = ds->n_patch || ds->n_stencil || ds->n_kprod;
-      const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;             // product chains: [tk, t1), kprod.hip
-      const int tp = structured ? t0 + ds->pair_nplain[p] : t1;              // patch terms: [tp, ts), conv.hip
-      const int ts = (ds->n_stencil || ds->n_kprod) ? tp + ds->pair_npatch[p] : t1;   // stencil terms: [ts, tk), stencil.hip
       for (int t = t0; t < tp; t += per) {
         int cnt = std::min(per, tp - t);
         CHECK_RC(launch_assemble_block(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax,
@@ -1599,31 +1604,28 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag: block lengths differ");
     int p = I * ds->ncb + I;
-    int t0 = ds->term_ptr[p], t1k = ds->term_ptr[p + 1];
-    const int t1 = ds->n_kprod ? t1k - ds->pair_nkprod[p] : t1k;        // product chains: [t1, t1k), kprod.hip
-    const int np = (ds->n_patch || ds->n_stencil || ds->n_kprod) ? ds->pair_nplain[p] : t1 - t0;
-    const int te = (ds->n_stencil || ds->n_kprod) ? t0 + np + ds->pair_npatch[p] : t1;   // plain + patch terms: [t0, te)
-    if (np < te - t0) {   // patch terms (conv.hip)
+    const auto [t0, tp, ts, tk, t1] = pair_segments(ds, p);
+    if (tp < ts) {   // patch terms (conv.hip), in one launch with the plain terms in front of them
       int max_d = 1, d_all = -1, max_px = 1;
-      for (int t = t0 + np; t < te; ++t) {
+      for (int t = tp; t < ts; ++t) {
         const DevTerm& T = ds->h_terms[t];
         max_d = std::max(max_d, T.dim);
         d_all = (d_all < 0 || d_all == T.dim) ? T.dim : 0;
         max_px = std::max(max_px, T.hr * T.wr + T.hc * T.wc);
       }
-      CHECK_RC(launch_diag_conv(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, np, te - t0, max_d, d_all, max_px,
+      CHECK_RC(launch_diag_conv(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, tp - t0, ts - t0, max_d, d_all, max_px,
                                 s));
     } else {
-      CHECK_RC(launch_diag_terms(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, te - t0, s));
+      CHECK_RC(launch_diag_terms(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, ts - t0, s));
     }
-    if (te < t1) {        // stencil terms (stencil.hip), added onto the plain and patch diagonal
+    if (ts < tk) {        // stencil terms (stencil.hip), added onto the plain and patch diagonal
       int max_dim = 1;
-      for (int t = te; t < t1; ++t) max_dim = std::max(max_dim, ds->h_terms[t].dim);
-      CHECK_RC(launch_diag_stencil(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + te, t1 - te, max_dim, s));
+      for (int t = ts; t < tk; ++t) max_dim = std::max(max_dim, ds->h_terms[t].dim);
+      CHECK_RC(launch_diag_stencil(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + ts, tk - ts, max_dim, s));
     }
-    for (int t = t1; t < t1k;) {   // product chains, in the launch groups of the matrix assembly: the same sums
+    for (int t = tk; t < t1;) {   // product chains, in the launch groups of the matrix assembly: the same sums
       int kdmax = 1;
-      const int cnt = kprod_group(ds->h_terms.data(), t, t1k, &kdmax);
+      const int cnt = kprod_group(ds->h_terms.data(), t, t1, &kdmax);
       CHECK_RC(launch_diag_kprod(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
       t += cnt;
     }
@@ -1743,22 +1745,6 @@ extern "C" int sgp_rand(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* me
   return with_df_fallback(ctx, [&]() { return sgp_rand_impl(ctx, spec, mean, noise_kind, noise, Z, ldz, S, out, ldo); });
 }
 
-// the caller's index of the term at device position t (a spec with product chains keeps its plain terms in front: dspec_create)
-static inline int term_src_of(const sgp_dspec* ds, int t) {
-  return (ds->n_kprod || ds->n_patch || ds->n_stencil) ? ds->term_src[t] : t;
-}
-// the chain whose head sits at device position t: one past its last factor, and its DMAX
-static inline int chain_end(const sgp_dspec* ds, int t, int t1) {
-  int e = t + 1;
-  while (e < t1 && (ds->h_terms[e].kind & SGP_KIND_TIMES_PREV)) ++e;
-  return e;
-}
-static inline int chain_dmax(const sgp_dspec* ds, int t, int e) {
-  int dm = 1;
-  for (int f = t; f < e; ++f) dm = std::max(dm, pow2ceil(ds->h_terms[f].dim));
-  return dm;
-}
-
 // whether no entry of `want` (NULL: none) asks for the gradient of an input that a patched side reads: those hold images
 static bool images_unasked(const sgp_dspec* ds, double* const* want) {
   for (size_t t = 0; want && t < ds->h_terms.size(); ++t) {
@@ -1772,8 +1758,7 @@ static bool images_unasked(const sgp_dspec* ds, double* const* want) {
 static int fetch_terms(const sgp_dspec* ds, double* dst, const double* d_src) {
   const size_t nt = ds->h_terms.size();
   if (!dst || !nt) return 0;
-  if (!ds->n_kprod && !ds->n_patch && !ds->n_stencil) {   // (patch and stencil terms sit behind the pair's plain terms on the
-                                                          //  device, as chains do)
+  if (!ds->n_kprod && !ds->n_patch && !ds->n_stencil) {   // every term plain: the device order is the caller's (term_src[t] == t)
     SGP_HIP(hipMemcpy(dst, d_src, sizeof(double) * nt, hipMemcpyDeviceToHost));
     return 0;
   }
@@ -1793,8 +1778,8 @@ struct StencilWo {
   DevBuf out, part;
   std::vector<Job> jobs;
   bool asked() const { return gw || go; }
-  double* want_w(const sgp_dspec* ds, int t, int side) const { return gw ? gw[2 * term_src_of(ds, t) + side] : nullptr; }
-  double* want_o(const sgp_dspec* ds, int t, int side) const { return go ? go[2 * term_src_of(ds, t) + side] : nullptr; }
+  double* want_w(const sgp_dspec* ds, int t, int side) const { return gw ? gw[2 * ds->term_src[t] + side] : nullptr; }
+  double* want_o(const sgp_dspec* ds, int t, int side) const { return go ? go[2 * ds->term_src[t] + side] : nullptr; }
 
   // refuse what has no stencil of its own, and size the output and the scratch.  diag: the diagonal pairs alone are contracted
   int prepare(const sgp_dspec* ds, const char* who, bool diag, hipStream_t s) {
@@ -1803,14 +1788,13 @@ struct StencilWo {
     long need = 1;
     for (int I = 0; I < ds->nrb; ++I)
       for (int J = 0; J < ds->ncb; ++J) {
-        const int p = I * ds->ncb + J, t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
-        const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
-        for (int t = t0; t < t1; ++t) {
+        const PairSegs g = pair_segments(ds, I * ds->ncb + J);
+        for (int t = g.t0; t < g.t1; ++t) {
           const DevTerm& T = ds->h_terms[t];
           for (int side = 0; side < 2; ++side) {
             double *hw = want_w(ds, t, side), *ho = want_o(ds, t, side);
             if (!hw && !ho) continue;
-            if (t >= tk) {
+            if (t >= g.tk) {
               set_error(std::string(who) + ": a grad_weights / grad_offsets entry of a product chain term must be NULL");
               return -1;
             }
@@ -1901,13 +1885,13 @@ struct StencilWo {
 
 // sum_ij G_ij dC_ij / d theta per flattened term of every block pair of `ds` (grad.hip):
 // G = (alpha alpha' - Kinv) / 2 when alpha != nullptr, else G = the matrix at `Gm` itself.
-// Product chains (ds->n_kprod; kprod.hip) are contracted one chain per launch, only where the caller says it carries them
-// (leave.kprod: sgp_logpdf_grad / sgp_logpdf_grad_param); dgp (NULL: not asked for): d / d param per term, which for the
-// plain terms is non-zero for SGP_CONST alone -- those run through the chain kernel once more, as chains of length one, for
-// that entry.
-// Patch terms (ds->n_patch; conv.hip) are contracted one term per launch, only where the caller carries them (leave.patch: the
-// entry points of include/sthenomi_conv_grad.h), and stencil terms (ds->n_stencil; stencil.hip) likewise (leave.stencil: the
-// entry points of include/sthenomi_stencil_grad.h): they occupy [ts, tk) of their pair, behind the patch terms [tp, ts).
+// The terms of a pair are contracted class by class, in the order of its PairSegs (spec_segments.h): the plain terms [t0, tp)
+// several per launch; the patch terms [tp, ts) one per launch (conv.hip), only where the caller carries them (leave.patch: the
+// entry points of include/sthenomi_conv_grad.h); the stencil terms [ts, tk) likewise (stencil.hip; leave.stencil: the entry
+// points of include/sthenomi_stencil_grad.h); the product chains [tk, t1) one chain per launch (kprod.hip), only where the
+// caller says it carries them (leave.kprod: the cores set it where their entry points take chains).
+// dgp (NULL: not asked for): d / d param per term, which for the plain terms is non-zero for SGP_CONST alone -- those run
+// through the chain kernel once more, as chains of length one, for that entry, between the stencil terms and the chains.
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr, long n_tc,
                          DevBuf& dpart, double* dgc, double* dgs, hipStream_t s, const GradLeave& leave, double* dgp) {
   CHECK_ARG(leave.stencil || !ds->n_stencil, "gradient contraction: stencil terms are not supported");
@@ -1915,13 +1899,11 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
   CHECK_ARG(leave.kprod || !ds->n_kprod,
             "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
   long need = std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16);
-  for (int p = 0; ds->n_patch && p < ds->nrb * ds->ncb; ++p)
-    for (int t = ds->term_ptr[p] + ds->pair_nplain[p]; t < ds->term_ptr[p] + ds->pair_nplain[p] + ds->pair_npatch[p]; ++t)
-      need = std::max(need, grad_conv_partials(ds->row_len[p / ds->ncb], ds->col_len[p % ds->ncb], ds->h_terms[t]));
-  for (int p = 0; ds->n_stencil && p < ds->nrb * ds->ncb; ++p) {
+  for (int p = 0; p < ds->nrb * ds->ncb; ++p) {   // the partial sums of the largest patch or stencil term
     const int I = p / ds->ncb, J = p % ds->ncb;
-    const int ts = ds->term_ptr[p] + ds->pair_nplain[p] + ds->pair_npatch[p], tk = ds->term_ptr[p + 1] - ds->pair_nkprod[p];
-    for (int t = ts; t < tk; ++t)
+    const PairSegs g = pair_segments(ds, p);
+    for (int t = g.tp; t < g.ts; ++t) need = std::max(need, grad_conv_partials(ds->row_len[I], ds->col_len[J], ds->h_terms[t]));
+    for (int t = g.ts; t < g.tk; ++t)
       need = std::max(need, grad_stencil_partials(ds->row_off[I], ds->row_len[I], ds->col_off[J], ds->col_len[J], ds->h_terms[t]));
   }
   CHECK_RC(dpart.alloc((size_t)need));
@@ -1932,12 +1914,9 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       long r0 = ds->row_off[I], nr = ds->row_len[I], c0 = ds->col_off[J], nc = ds->col_len[J];
       long trf = r0 / TILE, trl = (r0 + nr - 1) / TILE + 1, tcf = c0 / TILE, tcl = (c0 + nc - 1) / TILE + 1;
       int p = I * ds->ncb + J;
-      int t0 = ds->term_ptr[p], t1 = ds->term_ptr[p + 1];
+      const auto [t0, tp, ts, tk, t1] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = std::min(8, std::max(1, 64 / dmax));
-      const int tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
-      const int tp = (ds->n_patch || ds->n_stencil) ? t0 + ds->pair_nplain[p] : tk;   // patch terms: [tp, ts)
-      const int ts = ds->n_stencil ? tp + ds->pair_npatch[p] : tk;                    // stencil terms: [ts, tk)
       for (int t = t0; t < tp; t += per) {
         int cnt = std::min(per, tp - t);
         CHECK_RC(launch_grad_block(Gm, ldg, alpha, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax, trf, tcf,
@@ -1973,6 +1952,133 @@ static int check_grad_leave(const sgp_ctx* ctx, const std::string& stem, const G
             stem + (leave.patch ? "_conv" : "") + ": gradients through stencil terms are not supported");
   CHECK_ARG(leave.patch || (!spec_has_patch(a) && !spec_has_patch(b)),
             stem + ": gradients through patch (convolutional) terms are not supported");
+  return 0;
+}
+
+// The buffers of the input-point / function-scale gradients of one spec: a point-sum buffer per input (want_x) and a row /
+// column scale-sum buffer per term (want[0] / want[1], one entry per element of spec->terms); a NULL table: not asked for.
+// Allocated and zeroed on the stream, copied back into the caller's tables after the stream has run.
+struct TermGradBufs {
+  struct Scale { DevBuf buf; long len = 0; };
+  const sgp_dspec* ds = nullptr;
+  double* const* want_x = nullptr;
+  double* const* want[2] = {nullptr, nullptr};   // [0] row scales, [1] column scales
+  hipStream_t s = nullptr;
+  std::vector<DevBuf> gx;
+  std::vector<Scale> gs[2];
+
+  int init(const sgp_dspec* ds_, double* const* x, double* const* r, double* const* c, hipStream_t s_) {
+    ds = ds_, want_x = x, want[0] = r, want[1] = c, s = s_;
+    gx = std::vector<DevBuf>(x ? ds->in_dim.size() : 0);
+    for (int side = 0; side < 2; ++side) gs[side] = std::vector<Scale>(want[side] ? ds->h_terms.size() : 0);
+    for (size_t k = 0; k < gx.size(); ++k) {
+      const size_t cnt = (size_t)std::max<long>(1, (long)ds->in_dim[k] * ds->in_n[k]);
+      CHECK_RC(gx[k].alloc(cnt));
+      SGP_HIP(hipMemsetAsync(gx[k].p, 0, sizeof(double) * cnt, s));
+    }
+    return 0;
+  }
+  bool asked() const { return want_x || want[0] || want[1]; }
+  double* input(int k) const { return want_x ? gx[k].p : nullptr; }
+  // *out: the zeroed sums of the row (side 0) or column (side 1) scale vector `vec` (len entries) of the term at device
+  // position t.  NULL unless the caller's table has an entry for the term, the term has that vector and len > 0
+  int scale(int t, int side, const double* vec, long len, double** out) {
+    *out = nullptr;
+    if (!want[side] || !want[side][ds->term_src[t]] || !vec || len <= 0) return 0;
+    Scale& b = gs[side][t];
+    CHECK_RC(b.buf.alloc((size_t)len));
+    SGP_HIP(hipMemsetAsync(b.buf.p, 0, sizeof(double) * len, s));
+    b.len = len;
+    *out = b.buf.p;
+    return 0;
+  }
+  // after the stream has run: the inputs with points and a non-NULL entry, and every scale buffer handed out
+  int fetch() {
+    for (size_t k = 0; k < gx.size(); ++k)
+      if (want_x[k] && ds->in_n[k] > 0)
+        SGP_HIP(hipMemcpy(want_x[k], gx[k].p, sizeof(double) * ds->in_dim[k] * ds->in_n[k], hipMemcpyDeviceToHost));
+    for (int side = 0; side < 2; ++side)
+      for (size_t t = 0; t < gs[side].size(); ++t)
+        if (gs[side][t].buf.p)
+          SGP_HIP(hipMemcpy(want[side][ds->term_src[t]], gs[side][t].buf.p, sizeof(double) * gs[side][t].len,
+                            hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
+
+// the same plain term seen from its column points
+static DevTerm transposed(const DevTerm& T) {
+  DevTerm Tt = T;
+  Tt.xr = T.xc, Tt.ldr = T.ldc, Tt.rs = T.cs;
+  Tt.xc = T.xr, Tt.ldc = T.ldr, Tt.cs = T.rs;
+  return Tt;
+}
+
+// The input-point / function-scale pass: what it reads and where its sums go (device pointers).
+struct InputPass {
+  const double* Gm;      // cotangent as in contract_spec: G(i, j) at Gm[i + j * ldg], or (alpha alpha' - Gm) / 2 with alpha
+  long ldg;
+  const double* alpha;
+  bool symmetric;        // true: G and the spec are symmetric -- block (J, I) mirrors (I, J), so the column side of a pair is the
+                         // row side of its mirror pair: the row side alone, weight 2 (patch terms 1: the mirror pair supplies
+                         // the other role).  false: the row side, then the transposed pass for the column side, weight 1 each
+  TermGradBufs* bufs;
+};
+// Every term of every pair, pair-major and in device order (PairSegs): a launch adds into its input's buffer without
+// atomics, so this order is what fixes the bits.  A function-scaled term (K_ij = coef rs_i k_ij cs_j) has the sums of its
+// scale vectors ride along, with k in place of its derivative; a side is launched when points or that side's scale are asked
+// for.  Stencil terms form no scale sums, patch terms neither, and only the plain side of a one-sided patch term has points.
+static int input_pass(const sgp_dspec* ds, const InputPass& q, hipStream_t s) {
+  TermGradBufs& b = *q.bufs;
+  if (!b.asked()) return 0;
+  const bool points = b.want_x != nullptr;
+  const double w = q.symmetric ? 2.0 : 1.0;
+  for (int I = 0; I < ds->nrb; ++I)
+    for (int J = 0; J < ds->ncb; ++J) {
+      const long r0 = ds->row_off[I], nr = ds->row_len[I], c0 = ds->col_off[J], nc = ds->col_len[J];
+      if (nr == 0 || nc == 0) continue;
+      const int p = I * ds->ncb + J;
+      const PairSegs g = pair_segments(ds, p);
+      for (int t = g.t0; t < g.tp; ++t) {
+        const DevTerm& T = ds->h_terms[t];
+        double *gsr, *gsc;
+        CHECK_RC(b.scale(t, 0, T.rs, nr, &gsr));
+        CHECK_RC(b.scale(t, 1, T.cs, nc, &gsc));
+        if (points || gsr)
+          CHECK_RC(launch_grad_inputs(q.Gm, 1, q.ldg, q.alpha, r0, nr, c0, nc, T, ds->pair_dmax[p], w,
+                                      b.input(ds->term_row_input[t]), s, gsr));
+        if (!q.symmetric && (points || gsc))
+          CHECK_RC(launch_grad_inputs(q.Gm, q.ldg, 1, q.alpha, c0, nc, r0, nr, transposed(T), ds->pair_dmax[p], 1.0,
+                                      b.input(ds->term_col_input[t]), s, gsc));
+      }
+      for (int t = g.tp; points && t < g.ts; ++t) {   // (conv.hip)
+        const DevTerm& T = ds->h_terms[t];
+        if (T.hr && T.hc) continue;
+        CHECK_RC(launch_grad_conv_points(q.Gm, q.ldg, q.alpha, r0, nr, c0, nc, T, ds->d_terms + t, 1.0,
+                                         b.input(T.hr ? ds->term_col_input[t] : ds->term_row_input[t]), s));
+      }
+      for (int t = g.ts; points && t < g.tk; ++t) {   // (stencil.hip; transposed: sides and stencils swapped)
+        const DevTerm& T = ds->h_terms[t];
+        CHECK_RC(launch_grad_stencil_points(q.Gm, 1, q.ldg, q.alpha, r0, nr, c0, nc, T, 0, w, b.input(ds->term_row_input[t]), s));
+        if (!q.symmetric)
+          CHECK_RC(launch_grad_stencil_points(q.Gm, q.ldg, 1, q.alpha, c0, nc, r0, nr, T, 1, 1.0,
+                                              b.input(ds->term_col_input[t]), s));
+      }
+      for (int t = g.tk; t < g.t1;) {   // a chain: every factor's input and the head's scale in one launch per side (kprod.hip)
+        const int e = chain_end(ds, t, g.t1), cdmax = chain_dmax(ds, t, e);
+        double *gsr, *gsc, *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
+        CHECK_RC(b.scale(t, 0, ds->h_terms[t].rs, nr, &gsr));
+        CHECK_RC(b.scale(t, 1, ds->h_terms[t].cs, nc, &gsc));
+        for (int f = t; f < e; ++f) gxr[f - t] = b.input(ds->term_row_input[f]), gxc[f - t] = b.input(ds->term_col_input[f]);
+        if (points || gsr)
+          CHECK_RC(launch_grad_kprod_inputs(q.Gm, 1, q.ldg, q.alpha, r0, nr, c0, nc, &ds->h_terms[t], e - t, cdmax, 0, w, gxr, gsr,
+                                            s));
+        if (!q.symmetric && (points || gsc))
+          CHECK_RC(launch_grad_kprod_inputs(q.Gm, q.ldg, 1, q.alpha, c0, nc, r0, nr, &ds->h_terms[t], e - t, cdmax, 1, 1.0, gxc,
+                                            gsc, s));
+        t = e;
+      }
+    }
   return 0;
 }
 
@@ -2090,71 +2196,11 @@ static int logpdf_grad_core(sgp_ctx* ctx, const LogpdfGradArgs& a) {
   if (a.grad_coef || a.grad_inscale || a.grad_param)
     CHECK_RC(contract_spec(ds, dKinv.p, n_pad, dalpha.p, n_pad / TILE, n_pad / TILE, dpart, dgc.p, dgs.p, s, carried,
                            a.grad_param ? dgp.p : nullptr));
-  // gradient w.r.t. the input points: row-side contraction over every block pair; the spec is
-  // symmetric (block (J, I) mirrors (I, J)) and so is G, hence the column side equals the row side of
-  // the mirror block and the total is twice the row-side sum
-  // The row-scale vectors of function-scaled processes (K_ij = coef rs_i k_ij cs_j) ride along: the same
-  // row-side sums with k in place of its derivative; the column scale of a term is the row scale of its mirror
-  // term, so "row side x 2" covers both roles as it does for the points.
-  std::vector<DevBuf> dgx(a.grad_inputs ? a.spec->n_inputs : 0);
-  std::vector<DevBuf> dgr(a.grad_rowscale ? nterms_total : 0);
-  if (a.grad_inputs || a.grad_rowscale) {
-    for (int k = 0; a.grad_inputs && k < a.spec->n_inputs; ++k) {
-      size_t cnt = (size_t)std::max<long>(1, (long)ds->in_dim[k] * ds->in_n[k]);
-      CHECK_RC(dgx[k].alloc(cnt));
-      SGP_HIP(hipMemsetAsync(dgx[k].p, 0, sizeof(double) * cnt, s));
-    }
-    for (int I = 0; I < ds->nrb; ++I) {
-      for (int J = 0; J < ds->ncb; ++J) {
-        if (ds->row_len[I] == 0 || ds->col_len[J] == 0) continue;
-        int p = I * ds->ncb + J;
-        const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
-        for (int t = ds->term_ptr[p]; t < t1;) {
-          int ri = ds->term_row_input[t];
-          double* gsv = nullptr;
-          const DevTerm& T = ds->h_terms[t];
-          if (T.ph) {   // a patch term (sgp_logpdf_grad_stencil alone asks here): the plain side of a one-sided one, once per
-                        // pair -- the mirror pair gives the other role, which makes the "x 2"
-            if (a.grad_inputs && !(T.hr && T.hc))
-              CHECK_RC(launch_grad_conv_points(dKinv.p, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                               ds->col_len[J], T, ds->d_terms + t, 1.0,
-                                               dgx[T.hr ? ds->term_col_input[t] : ri].p, s));
-            ++t;
-            continue;
-          }
-          if (T.qr || T.qc) {   // a stencil term: the row side, twice (stencil.hip); its row scale is not formed
-            if (a.grad_inputs)
-              CHECK_RC(launch_grad_stencil_points(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                                  ds->col_len[J], T, 0, 2.0, dgx[ri].p, s));
-            ++t;
-            continue;
-          }
-          if (a.grad_rowscale && a.grad_rowscale[term_src_of(ds, t)] && ds->h_terms[t].rs) {
-            CHECK_RC(dgr[t].alloc((size_t)ds->row_len[I]));
-            SGP_HIP(hipMemsetAsync(dgr[t].p, 0, sizeof(double) * ds->row_len[I], s));
-            gsv = dgr[t].p;
-          }
-          if (t >= tk) {   // a chain: every factor's row input and the head's row scale in one pass (kprod.hip)
-            const int e = chain_end(ds, t, t1);
-            if (a.grad_inputs || gsv) {
-              double* gxf[SGP_KPROD_MAX_FACTORS];
-              for (int f = t; f < e; ++f) gxf[f - t] = a.grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
-              CHECK_RC(launch_grad_kprod_inputs(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                                ds->col_len[J], &ds->h_terms[t], e - t, chain_dmax(ds, t, e), 0, 2.0, gxf, gsv,
-                                                s));
-            }
-            t = e;
-            continue;
-          }
-          if (a.grad_inputs || gsv)
-            CHECK_RC(launch_grad_inputs(dKinv.p, 1, n_pad, dalpha.p, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                        ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
-                                        a.grad_inputs ? dgx[ri].p : nullptr, s, gsv));
-          ++t;
-        }
-      }
-    }
-  }
+  // gradient w.r.t. the input points and the row-scale vectors of function-scaled processes: the spec and G are symmetric,
+  // so the row side, twice, covers the column role too -- the column scale of a term is the row scale of its mirror term
+  TermGradBufs bufs;
+  CHECK_RC(bufs.init(ds, a.grad_inputs, a.grad_rowscale, nullptr, s));
+  CHECK_RC(input_pass(ds, {dKinv.p, n_pad, dalpha.p, true, &bufs}, s));
   // the stencils' own weights and offsets: both sides of every stencil term against the same cotangent (stencil.hip)
   CHECK_RC(wo.contract(ds, dKinv.p, n_pad, dalpha.p, true, s));
   int info = fetch_info(ctx, s);
@@ -2181,21 +2227,7 @@ static int logpdf_grad_core(sgp_ctx* ctx, const LogpdfGradArgs& a) {
   CHECK_RC(fetch_terms(ds, a.grad_coef, dgc.p));
   CHECK_RC(fetch_terms(ds, a.grad_inscale, dgs.p));
   if (a.grad_param) CHECK_RC(fetch_terms(ds, a.grad_param, dgp.p));
-  if (a.grad_inputs) {
-    for (int k = 0; k < a.spec->n_inputs; ++k) {
-      const sgp_input& in = a.spec->inputs[k];
-      if (!a.grad_inputs[k] || in.n == 0) continue;
-      SGP_HIP(hipMemcpy(a.grad_inputs[k], dgx[k].p, sizeof(double) * in.dim * in.n, hipMemcpyDeviceToHost));
-    }
-  }
-  if (a.grad_rowscale) {
-    for (int I = 0; I < ds->nrb; ++I)
-      for (int J = 0; J < ds->ncb; ++J)
-        for (int t = ds->term_ptr[I * ds->ncb + J]; t < ds->term_ptr[I * ds->ncb + J + 1]; ++t)
-          if (dgr[t].p && ds->row_len[I] > 0)
-            SGP_HIP(hipMemcpy(a.grad_rowscale[term_src_of(ds, t)], dgr[t].p, sizeof(double) * ds->row_len[I],
-                              hipMemcpyDeviceToHost));
-  }
+  CHECK_RC(bufs.fetch());
   return 0;
 }
 
@@ -3899,145 +3931,13 @@ static int elbo_grad_core(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradSha
     CHECK_RC(contract_spec(gz.ds, dGzz.p, m_pad, nullptr, m_pad / TILE, m_pad / TILE, dpart, dgcz.p, dgsz.p, s, a.leave,
                            dgpz.p));
   // ---- input points: zz is symmetric (twice the row side, as in logpdf_grad_core); xz is
-  // rectangular: row side for the x inputs, and the transposed contraction for the z inputs
-  std::vector<DevBuf> dgz(a.grad_inputs_zz ? a.zz->n_inputs : 0), dgxz(a.grad_inputs_xz ? a.xz->n_inputs : 0);
-  auto zero_inputs = [&](std::vector<DevBuf>& v, const sgp_dspec* ds) -> int {
-    for (size_t k = 0; k < v.size(); ++k) {
-      size_t cnt = (size_t)std::max<long>(1, (long)ds->in_dim[k] * ds->in_n[k]);
-      CHECK_RC(v[k].alloc(cnt));
-      SGP_HIP(hipMemsetAsync(v[k].p, 0, sizeof(double) * cnt, s));
-    }
-    return 0;
-  };
-  // Function-valued scales sigma(x) * f (product.jl:25-48) ride along as in logpdf_grad_core: K_ij = coef rs_i k_ij cs_j,
-  // the row-scale sums come out of the same passes (zz symmetric: "row side x 2" covers the column role through the
-  // mirror term; xz: the row side gives d / d rs (scales at x), the transposed pass d / d cs (scales at z)).
-  const size_t ntz_s = gz.ds->h_terms.size(), ntx_s = gx.ds->h_terms.size();
-  std::vector<DevBuf> drz(a.grad_rowscale_zz ? ntz_s : 0), drx(a.grad_rowscale_xz ? ntx_s : 0),
-      dcx(a.grad_colscale_xz ? ntx_s : 0);
-  auto scale_buf = [&](std::vector<DevBuf>& v, double* const* want, const sgp_dspec* ds, size_t t, const double* vec, long len,
-                       double** out) -> int {
-    *out = nullptr;
-    if (!want || !want[term_src_of(ds, (int)t)] || !vec || len <= 0) return 0;
-    CHECK_RC(v[t].alloc((size_t)len));
-    SGP_HIP(hipMemsetAsync(v[t].p, 0, sizeof(double) * len, s));
-    *out = v[t].p;
-    return 0;
-  };
-  // d / d (plain side's points) of the one-sided patch term t of pair (I, J), into that side's input (conv.hip)
-  auto patch_points = [&](const sgp_dspec* ds, const double* Gm, long ldgm, int I, int J, int t, std::vector<DevBuf>& into) -> int {
-    const DevTerm& T = ds->h_terms[t];
-    if (into.empty() || (T.hr && T.hc)) return 0;
-    const int k = T.hr ? ds->term_col_input[t] : ds->term_row_input[t];
-    return launch_grad_conv_points(Gm, ldgm, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J], ds->col_len[J], T,
-                                   ds->d_terms + t, 1.0, into[k].p, s);
-  };
-  if (a.grad_inputs_zz || a.grad_rowscale_zz) {
-    if (a.grad_inputs_zz) CHECK_RC(zero_inputs(dgz, gz.ds));
-    const sgp_dspec* ds = gz.ds;
-    for (int I = 0; I < ds->nrb; ++I)
-      for (int J = 0; J < ds->ncb; ++J) {
-        if (ds->row_len[I] == 0 || ds->col_len[J] == 0) continue;
-        int p = I * ds->ncb + J;
-        const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
-        for (int t = ds->term_ptr[p]; t < t1;) {
-          double* gsv = nullptr;
-          if (ds->h_terms[t].ph) {   // a patch term: the plain side of a one-sided one (its mirror pair gives the other role)
-            CHECK_RC(patch_points(ds, dGzz.p, m_pad, I, J, t, dgz));
-            ++t;
-            continue;
-          }
-          if (ds->h_terms[t].qr || ds->h_terms[t].qc) {   // a stencil term: the row side, twice (stencil.hip)
-            if (a.grad_inputs_zz)
-              CHECK_RC(launch_grad_stencil_points(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                                  ds->col_len[J], ds->h_terms[t], 0, 2.0, dgz[ds->term_row_input[t]].p, s));
-            ++t;
-            continue;
-          }
-          CHECK_RC(scale_buf(drz, a.grad_rowscale_zz, ds, t, ds->h_terms[t].rs, ds->row_len[I], &gsv));
-          if (t >= tk) {   // a chain: one pass for every factor's row input and the head's row scale (kprod.hip)
-            const int e = chain_end(ds, t, t1);
-            if (a.grad_inputs_zz || gsv) {
-              double* gxf[SGP_KPROD_MAX_FACTORS];
-              for (int f = t; f < e; ++f) gxf[f - t] = a.grad_inputs_zz ? dgz[ds->term_row_input[f]].p : nullptr;
-              CHECK_RC(launch_grad_kprod_inputs(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                                ds->col_len[J], &ds->h_terms[t], e - t, chain_dmax(ds, t, e), 0, 2.0, gxf, gsv,
-                                                s));
-            }
-            t = e;
-            continue;
-          }
-          if (a.grad_inputs_zz || gsv)
-            CHECK_RC(launch_grad_inputs(dGzz.p, 1, m_pad, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                        ds->col_len[J], ds->h_terms[t], ds->pair_dmax[p], 2.0,
-                                        a.grad_inputs_zz ? dgz[ds->term_row_input[t]].p : nullptr, s, gsv));
-          ++t;
-        }
-      }
-  }
-  if (a.grad_inputs_xz || a.grad_rowscale_xz || a.grad_colscale_xz) {
-    if (a.grad_inputs_xz) CHECK_RC(zero_inputs(dgxz, gx.ds));
-    const sgp_dspec* ds = gx.ds;
-    for (int I = 0; I < ds->nrb; ++I)
-      for (int J = 0; J < ds->ncb; ++J) {
-        if (ds->row_len[I] == 0 || ds->col_len[J] == 0) continue;
-        int p = I * ds->ncb + J;
-        const int t1 = ds->term_ptr[p + 1], tk = ds->n_kprod ? t1 - ds->pair_nkprod[p] : t1;   // product chains: [tk, t1)
-        for (int t = ds->term_ptr[p]; t < t1; ++t) {
-          const DevTerm& T = ds->h_terms[t];
-          double *gsr = nullptr, *gsc = nullptr;
-          if (T.ph) {   // a patch term: the plain side of a one-sided one
-            CHECK_RC(patch_points(ds, dE.p, n_rows, I, J, t, dgxz));
-            continue;
-          }
-          if (T.qr || T.qc) {   // a stencil term: the row side for x, the transposed contraction (sides and stencils
-                                // swapped) for z (stencil.hip)
-            if (a.grad_inputs_xz) {
-              CHECK_RC(launch_grad_stencil_points(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                                  ds->col_len[J], T, 0, 1.0, dgxz[ds->term_row_input[t]].p, s));
-              CHECK_RC(launch_grad_stencil_points(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
-                                                  ds->row_len[I], T, 1, 1.0, dgxz[ds->term_col_input[t]].p, s));
-            }
-            continue;
-          }
-          CHECK_RC(scale_buf(drx, a.grad_rowscale_xz, ds, t, T.rs, ds->row_len[I], &gsr));
-          CHECK_RC(scale_buf(dcx, a.grad_colscale_xz, ds, t, T.cs, ds->col_len[J], &gsc));
-          if (t >= tk) {   // a chain: the row pass for x, the transposed pass for z, every factor in each (kprod.hip)
-            const int e = chain_end(ds, t, t1), cdm = chain_dmax(ds, t, e);
-            double *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
-            for (int f = t; f < e; ++f) {
-              gxr[f - t] = a.grad_inputs_xz ? dgxz[ds->term_row_input[f]].p : nullptr;
-              gxc[f - t] = a.grad_inputs_xz ? dgxz[ds->term_col_input[f]].p : nullptr;
-            }
-            if (a.grad_inputs_xz || gsr)
-              CHECK_RC(launch_grad_kprod_inputs(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                                ds->col_len[J], &ds->h_terms[t], e - t, cdm, 0, 1.0, gxr, gsr, s));
-            if (a.grad_inputs_xz || gsc)
-              CHECK_RC(launch_grad_kprod_inputs(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
-                                                ds->row_len[I], &ds->h_terms[t], e - t, cdm, 1, 1.0, gxc, gsc, s));
-            t = e - 1;
-            continue;
-          }
-          if (a.grad_inputs_xz || gsr || gsc)
-            if (a.grad_inputs_xz || gsr)
-            CHECK_RC(launch_grad_inputs(dE.p, 1, n_rows, nullptr, ds->row_off[I], ds->row_len[I], ds->col_off[J],
-                                        ds->col_len[J], T, ds->pair_dmax[p], 1.0,
-                                        a.grad_inputs_xz ? dgxz[ds->term_row_input[t]].p : nullptr, s, gsr));
-          if (a.grad_inputs_xz || gsc) {
-            DevTerm Tt = T;  // the same term seen from its column points
-            Tt.xr = T.xc;
-            Tt.ldr = T.ldc;
-            Tt.xc = T.xr;
-            Tt.ldc = T.ldr;
-            Tt.rs = T.cs;
-            Tt.cs = T.rs;
-            CHECK_RC(launch_grad_inputs(dE.p, n_rows, 1, nullptr, ds->col_off[J], ds->col_len[J], ds->row_off[I],
-                                        ds->row_len[I], Tt, ds->pair_dmax[p], 1.0,
-                                        a.grad_inputs_xz ? dgxz[ds->term_col_input[t]].p : nullptr, s, gsc));
-          }
-        }
-      }
-  }
+  // rectangular: row side for the x inputs, and the transposed contraction for the z inputs.  Function-valued scales
+  // sigma(x) * f (product.jl:25-48) ride along: the row side gives d / d rs (scales at x), the transposed pass d / d cs (at z)
+  TermGradBufs bufs_zz, bufs_xz;
+  CHECK_RC(bufs_zz.init(gz.ds, a.grad_inputs_zz, a.grad_rowscale_zz, nullptr, s));
+  CHECK_RC(input_pass(gz.ds, {dGzz.p, m_pad, nullptr, true, &bufs_zz}, s));
+  CHECK_RC(bufs_xz.init(gx.ds, a.grad_inputs_xz, a.grad_rowscale_xz, a.grad_colscale_xz, s));
+  CHECK_RC(input_pass(gx.ds, {dE.p, n_rows, nullptr, false, &bufs_xz}, s));
   // ---- the stencils' own weights and offsets: G_zz is symmetric, the xz cotangent is read transposed for its column side
   CHECK_RC(wo_zz.contract(gz.ds, dGzz.p, m_pad, nullptr, true, s));
   CHECK_RC(wo_xz.contract(gx.ds, dE.p, n_rows, nullptr, false, s));
@@ -4089,27 +3989,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradSha
   CHECK_RC(fetch_terms(gx.ds, a.grad_coef_xz, dgcx.p));
   CHECK_RC(fetch_terms(gx.ds, a.grad_inscale_xz, dgsx.p));
   CHECK_RC(fetch_terms(gx.ds, a.grad_param_xz, dgpx.p));
-  for (size_t k = 0; k < dgz.size(); ++k)
-    if (a.grad_inputs_zz[k] && a.zz->inputs[k].n > 0)
-      SGP_HIP(hipMemcpy(a.grad_inputs_zz[k], dgz[k].p, sizeof(double) * a.zz->inputs[k].dim * a.zz->inputs[k].n,
-                        hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < dgxz.size(); ++k)
-    if (a.grad_inputs_xz[k] && a.xz->inputs[k].n > 0)
-      SGP_HIP(hipMemcpy(a.grad_inputs_xz[k], dgxz[k].p, sizeof(double) * a.xz->inputs[k].dim * a.xz->inputs[k].n,
-                        hipMemcpyDeviceToHost));
-  auto scale_out = [&](std::vector<DevBuf>& v, double* const* want, const sgp_dspec* ds, bool cols) -> int {
-    if (!want) return 0;
-    for (int I = 0; I < ds->nrb; ++I)
-      for (int J = 0; J < ds->ncb; ++J)
-        for (int t = ds->term_ptr[I * ds->ncb + J]; t < ds->term_ptr[I * ds->ncb + J + 1]; ++t)
-          if (v[t].p)
-            SGP_HIP(hipMemcpy(want[term_src_of(ds, t)], v[t].p, sizeof(double) * (cols ? ds->col_len[J] : ds->row_len[I]),
-                              hipMemcpyDeviceToHost));
-    return 0;
-  };
-  CHECK_RC(scale_out(drz, a.grad_rowscale_zz, gz.ds, false));
-  CHECK_RC(scale_out(drx, a.grad_rowscale_xz, gx.ds, false));
-  CHECK_RC(scale_out(dcx, a.grad_colscale_xz, gx.ds, true));
+  CHECK_RC(bufs_zz.fetch());
+  CHECK_RC(bufs_xz.fetch());
   return 0;
 }
 
@@ -4215,101 +4096,72 @@ static int diag_grad_core(sgp_ctx* ctx, const DiagGradArgs& a) {
     CHECK_RC(dgp.alloc(nt));
     SGP_HIP(hipMemsetAsync(dgp.p, 0, sizeof(double) * nt, s));
   }
-  // the plain terms of a diagonal pair: [term_ptr, diag_tk); its product chains behind them (kprod.hip)
-  // (and, where the caller carries them, its patch terms between the two: [diag_tk, diag_tp), conv.hip)
-  // (and, where the caller carries them, its stencil terms behind the patch terms: [diag_ts, diag_tp), stencil.hip)
-  auto diag_tp = [&](int p) { return ds->n_kprod ? ds->term_ptr[p + 1] - ds->pair_nkprod[p] : ds->term_ptr[p + 1]; };
-  auto diag_tk = [&](int p) { return (ds->n_patch || ds->n_stencil) ? ds->term_ptr[p] + ds->pair_nplain[p] : diag_tp(p); };
-  auto diag_ts = [&](int p) { return ds->n_stencil ? diag_tk(p) + ds->pair_npatch[p] : diag_tp(p); };
+  // Only the diagonal pairs are read, class by class over all of them (PairSegs, spec_segments.h): the patch and stencil
+  // terms' coefficients and scales, the plain terms', the input points, the plain terms' function scales, then the chains.
+  auto diag_segs = [&](int I) { return pair_segments(ds, I * ds->ncb + I); };
   DevBuf dpart;
   if (ds->n_patch || ds->n_stencil) CHECK_RC(dpart.alloc((size_t)2 * ds->N));
   for (int I = 0; (ds->n_patch || ds->n_stencil) && I < ds->nrb; ++I) {
-    const int p = I * ds->ncb + I;
+    const PairSegs g = diag_segs(I);
     if (ds->row_len[I] == 0 || ds->row_len[I] != ds->col_len[I]) continue;
-    for (int t = diag_tk(p); t < diag_ts(p); ++t)
+    for (int t = g.tp; t < g.ts; ++t)   // (conv.hip)
       CHECK_RC(launch_diag_grad_conv(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t], ds->d_terms + t, dpart.p,
                                      dgc.p + t, dgs.p + t, s));
-    for (int t = diag_ts(p); t < diag_tp(p); ++t)
+    for (int t = g.ts; t < g.tk; ++t)   // (stencil.hip)
       CHECK_RC(launch_diag_grad_stencil(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t], ds->d_terms + t, dpart.p,
                                         dgc.p + t, dgs.p + t, s));
   }
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag_grad: block lengths differ");
-    int p = I * ds->ncb + I;
-    int t0 = ds->term_ptr[p], t1 = diag_tk(p);
-    if (ds->row_len[I] == 0 || t1 == t0) continue;
-    CHECK_RC(launch_diag_grad(dw.p + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, t1 - t0, dgc.p + t0,
-                              dgs.p + t0, s));
-    for (int t = t0; a.grad_param && t < t1; ++t)   // d / d param of a plain term: SGP_CONST alone, as a chain of length one
+    const PairSegs g = diag_segs(I);
+    if (ds->row_len[I] == 0 || g.tp == g.t0) continue;
+    CHECK_RC(launch_diag_grad(dw.p + ds->row_off[I], ds->row_len[I], ds->d_terms + g.t0, g.tp - g.t0, dgc.p + g.t0,
+                              dgs.p + g.t0, s));
+    for (int t = g.t0; a.grad_param && t < g.tp; ++t)   // d / d param of a plain term: SGP_CONST alone, as a chain of length one
       if (ds->h_terms[t].kind == SGP_CONST)
         CHECK_RC(launch_diag_grad_kprod(dw.p + ds->row_off[I], ds->row_len[I], &ds->h_terms[t], 1, nullptr, nullptr,
                                         dgp.p + t, nullptr, nullptr, nullptr, nullptr, s));
   }
-  std::vector<DevBuf> dgx(a.grad_inputs ? a.spec->n_inputs : 0);
-  if (a.grad_inputs) {
-    for (int k = 0; k < a.spec->n_inputs; ++k) {
-      size_t cnt = (size_t)std::max<long>(1, (long)ds->in_dim[k] * ds->in_n[k]);
-      CHECK_RC(dgx[k].alloc(cnt));
-      SGP_HIP(hipMemsetAsync(dgx[k].p, 0, sizeof(double) * cnt, s));
+  TermGradBufs bufs;
+  CHECK_RC(bufs.init(ds, a.grad_inputs, a.grad_rowscale, a.grad_colscale, s));
+  for (int I = 0; a.grad_inputs && I < ds->nrb; ++I) {
+    const PairSegs g = diag_segs(I);
+    if (ds->row_len[I] == 0) continue;
+    for (int t = g.t0; t < g.tp; ++t)
+      CHECK_RC(launch_diag_grad_inputs(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t],
+                                       bufs.input(ds->term_row_input[t]), bufs.input(ds->term_col_input[t]), s));
+    for (int t = g.tp; t < g.ts; ++t) {   // patch terms: the plain side of a one-sided one is not formed here
+      const DevTerm& T = ds->h_terms[t];
+      CHECK_ARG((T.hr && T.hc) || !a.grad_inputs[T.hr ? ds->term_col_input[t] : ds->term_row_input[t]],
+                "sgp_kernelmatrix_diag_grad_stencil: the input-point gradient of a one-sided patch (convolutional) term on "
+                "the diagonal is not supported: the grad_inputs entry of its plain side must be NULL");
     }
-    for (int I = 0; I < ds->nrb; ++I) {
-      int p = I * ds->ncb + I;
-      if (ds->row_len[I] == 0) continue;
-      for (int t = ds->term_ptr[p]; t < diag_tk(p); ++t)
-        CHECK_RC(launch_diag_grad_inputs(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t],
-                                         dgx[ds->term_row_input[t]].p, dgx[ds->term_col_input[t]].p, s));
-      for (int t = diag_tk(p); t < diag_ts(p); ++t) {   // patch terms: the plain side of a one-sided one is not formed here
-        const DevTerm& T = ds->h_terms[t];
-        CHECK_ARG((T.hr && T.hc) || !a.grad_inputs[T.hr ? ds->term_col_input[t] : ds->term_row_input[t]],
-                  "sgp_kernelmatrix_diag_grad_stencil: the input-point gradient of a one-sided patch (convolutional) term on "
-                  "the diagonal is not supported: the grad_inputs entry of its plain side must be NULL");
-      }
-      for (int t = diag_ts(p); t < diag_tp(p); ++t)   // stencil terms: + on the row input, - on the column input (stencil.hip)
-        CHECK_RC(launch_diag_grad_stencil_points(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t],
-                                                 dgx[ds->term_row_input[t]].p, dgx[ds->term_col_input[t]].p, s));
+    for (int t = g.ts; t < g.tk; ++t)   // stencil terms: + on the row input, - on the column input (stencil.hip)
+      CHECK_RC(launch_diag_grad_stencil_points(dw.p + ds->row_off[I], ds->row_len[I], ds->h_terms[t],
+                                               bufs.input(ds->term_row_input[t]), bufs.input(ds->term_col_input[t]), s));
+  }
+  for (int I = 0; (a.grad_rowscale || a.grad_colscale) && I < ds->nrb; ++I) {
+    const PairSegs g = diag_segs(I);
+    const long len = ds->row_len[I];
+    for (int t = g.t0; t < g.tp; ++t) {
+      double *o_r, *o_c;
+      CHECK_RC(bufs.scale(t, 0, ds->h_terms[t].rs, len, &o_r));
+      CHECK_RC(bufs.scale(t, 1, ds->h_terms[t].cs, len, &o_c));
+      if (!o_r && !o_c) continue;
+      CHECK_RC(launch_diag_scale_grad(dw.p + ds->row_off[I], len, ds->h_terms[t], o_r, o_c, s));
     }
   }
-  std::vector<DevBuf> drs(a.grad_rowscale ? nt : 0), dcs(a.grad_colscale ? nt : 0);
-  auto scale_bufs = [&](int t, long len, double** o_r, double** o_c) -> int {
-    const DevTerm& T = ds->h_terms[t];
-    *o_r = *o_c = nullptr;
-    if (a.grad_rowscale && a.grad_rowscale[term_src_of(ds, t)] && T.rs) {
-      CHECK_RC(drs[t].alloc((size_t)len));
-      SGP_HIP(hipMemsetAsync(drs[t].p, 0, sizeof(double) * len, s));
-      *o_r = drs[t].p;
-    }
-    if (a.grad_colscale && a.grad_colscale[term_src_of(ds, t)] && T.cs) {
-      CHECK_RC(dcs[t].alloc((size_t)len));
-      SGP_HIP(hipMemsetAsync(dcs[t].p, 0, sizeof(double) * len, s));
-      *o_c = dcs[t].p;
-    }
-    return 0;
-  };
-  if (a.grad_rowscale || a.grad_colscale)
-    for (int I = 0; I < ds->nrb; ++I) {
-      const long len = ds->row_len[I];
-      if (len == 0) continue;
-      for (int t = ds->term_ptr[I * ds->ncb + I]; t < diag_tk(I * ds->ncb + I); ++t) {
-        double *o_r = nullptr, *o_c = nullptr;
-        CHECK_RC(scale_bufs(t, len, &o_r, &o_c));
-        if (!o_r && !o_c) continue;
-        CHECK_RC(launch_diag_scale_grad(dw.p + ds->row_off[I], len, ds->h_terms[t], o_r, o_c, s));
-      }
-    }
-  // product chains: every gradient of a chain in one launch
-  for (int I = 0; ds->n_kprod && I < ds->nrb; ++I) {
+  // product chains: every gradient of a chain in one launch (kprod.hip)
+  for (int I = 0; I < ds->nrb; ++I) {
+    const PairSegs g = diag_segs(I);
     const long len = ds->row_len[I];
-    const int p = I * ds->ncb + I, t1 = ds->term_ptr[p + 1];
     if (len == 0) continue;
-    for (int t = diag_tp(p); t < t1;) {
-      const int e = chain_end(ds, t, t1);
-      double *o_r = nullptr, *o_c = nullptr;
-      CHECK_RC(scale_bufs(t, len, &o_r, &o_c));
-      double *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
-      for (int f = t; f < e; ++f) {
-        gxr[f - t] = a.grad_inputs ? dgx[ds->term_row_input[f]].p : nullptr;
-        gxc[f - t] = a.grad_inputs ? dgx[ds->term_col_input[f]].p : nullptr;
-      }
+    for (int t = g.tk; t < g.t1;) {
+      const int e = chain_end(ds, t, g.t1);
+      double *o_r, *o_c, *gxr[SGP_KPROD_MAX_FACTORS], *gxc[SGP_KPROD_MAX_FACTORS];
+      CHECK_RC(bufs.scale(t, 0, ds->h_terms[t].rs, len, &o_r));
+      CHECK_RC(bufs.scale(t, 1, ds->h_terms[t].cs, len, &o_c));
+      for (int f = t; f < e; ++f) gxr[f - t] = bufs.input(ds->term_row_input[f]), gxc[f - t] = bufs.input(ds->term_col_input[f]);
       CHECK_RC(launch_diag_grad_kprod(dw.p + ds->row_off[I], len, &ds->h_terms[t], e - t, dgc.p + t, dgs.p + t,
                                       a.grad_param ? dgp.p + t : nullptr, gxr, gxc, o_r, o_c, s));
       t = e;
@@ -4321,19 +4173,7 @@ static int diag_grad_core(sgp_ctx* ctx, const DiagGradArgs& a) {
   CHECK_RC(fetch_terms(ds, a.grad_coef, dgc.p));
   CHECK_RC(fetch_terms(ds, a.grad_inscale, dgs.p));
   CHECK_RC(fetch_terms(ds, a.grad_param, dgp.p));
-  for (int I = 0; I < ds->nrb && (a.grad_rowscale || a.grad_colscale); ++I)
-    for (int t = ds->term_ptr[I * ds->ncb + I]; t < ds->term_ptr[I * ds->ncb + I + 1]; ++t) {
-      if (a.grad_rowscale && drs[t].p)
-        SGP_HIP(hipMemcpy(a.grad_rowscale[term_src_of(ds, t)], drs[t].p, sizeof(double) * ds->row_len[I],
-                          hipMemcpyDeviceToHost));
-      if (a.grad_colscale && dcs[t].p)
-        SGP_HIP(hipMemcpy(a.grad_colscale[term_src_of(ds, t)], dcs[t].p, sizeof(double) * ds->row_len[I],
-                          hipMemcpyDeviceToHost));
-    }
-  for (size_t k = 0; k < dgx.size(); ++k)
-    if (a.grad_inputs[k] && a.spec->inputs[k].n > 0)
-      SGP_HIP(hipMemcpy(a.grad_inputs[k], dgx[k].p, sizeof(double) * a.spec->inputs[k].dim * a.spec->inputs[k].n,
-                        hipMemcpyDeviceToHost));
+  CHECK_RC(bufs.fetch());
   return 0;
 }
 
