@@ -57,7 +57,48 @@ enum {
   /* 21 .. 23 are no kinds.  The kinds below are functions of x'y, x'x and y'y, not of the distance alone */
   SGP_NEURALNET = 24, /* NeuralNetworkKernel: asin(x'y / sqrt((1 + x'x)(1 + y'y))), param ignored */
   SGP_FBM = 25,       /* FBMKernel(h): (|x|^2h + |y|^2h - |x - y|^2h) / 2, param = h in (0, 1] */
-  SGP_EXPONENTIATED = 26 /* ExponentiatedKernel: exp(x'y), param ignored; 27 and above are no kinds */
+  SGP_EXPONENTIATED = 26, /* ExponentiatedKernel: exp(x'y), param ignored; 27 .. 31 are no kinds */
+  /* Derivative kinds: 32 + the base kind.  A term of one of them is the covariance between partial derivatives of a process
+   * with the stationary base kernel k = kappa(s), s = |u|^2, u = x_i - y_j (the derivative process of
+   * examples/differentiation/script.jl, in closed form).  Matern-1/2 is not mean-square differentiable: 33 is no kind, and
+   * neither is anything above 35.
+   *
+   * param = 17 a + b with integers a, b in 0 .. 16: a = 0: the row side is not differentiated, a = c + 1: it is
+   * differentiated along coordinate c of the points the term reads; b likewise for the column side.  (a, b) = (0, 0) is the
+   * plain kind and refused.  The value of the term, times coef rs_i cs_j:
+   *     (p+1, 0)     2 kappa'(s) u_p
+   *     (0, q+1)    -2 kappa'(s) u_q
+   *     (p+1, q+1)  -4 kappa''(s) u_p u_q - 2 kappa'(s) delta_pq
+   * At a coincident pair (u = 0 exactly) the one-sided kinds are exactly 0 and the two-sided kind is exactly
+   * -2 kappa'(0) delta_pq: SE 1, Matern-3/2 3, Matern-5/2 5/3.  An overflowed s gives exact zeros.  A one-sided kind is not
+   * symmetric in (x, y); a symmetric spec's diagonal block pair may hold the terms (p+1, q+1) and (q+1, p+1), whose sum is.
+   * sgp_kernelmatrix_diag of these terms equals the diagonal of sgp_kernelmatrix bit for bit, as for every class.
+   *
+   * grad_coef / grad_inscale of sgp_logpdf_grad (and _batch, _pool) keep their meaning: for grad_inscale both inputs are
+   * scaled by g and the differentiation is with respect to the scaled points, which gives coef rs_i cs_j (u . grad_u T) at
+   * g = 1:
+   *     (p+1, 0)     (4 s kappa'' + 2 kappa') u_p          (0, q+1): its negative in u_q
+   *     (p+1, q+1)  -8 s kappa''' u_p u_q - 8 kappa'' u_p u_q - 4 s kappa'' delta_pq
+   * all finite, and 0 at u = 0, for the three kinds.
+   *
+   * Refused by dspec creation, with these texts:
+   *   "spec: SGP_DERIV: param must be an integer 17 a + b with a and b in 0 .. 16, not both 0 (a - 1, b - 1: the
+   *    differentiated coordinate of the row, column side; 0: that side is not differentiated)"   (NaN, non-integer, range)
+   *   "spec: SGP_DERIV: a differentiated coordinate must be < the input dimension"
+   *   "spec: SGP_DERIV: the input dimension of a derivative term must be <= 16"
+   *   "spec: a derivative term takes no SGP_KIND_TIMES_PREV, on it or on its successor (no products of differentiated
+   *    kernels)"
+   *   "spec: a derivative term must have reserved == 0 (no patch or stencil sides)"
+   *   "spec: derivative terms are not supported on a multi-GPU context"
+   * Taken by every fp64 operator of a single-GPU context that goes through the common assembly (kernelmatrix and its
+   * diagonal, logpdf and its batch and pool forms, rand, the posterior and sparse-posterior families with predict, elbo, and
+   * the extend, postfx and vfe_update families) and by sgp_logpdf_grad / _batch / _pool for grad_coef and grad_inscale.
+   * Refused, with a message that names "derivative": sgp_logpdf_grad_x / _xs, sgp_kernelmatrix_diag_grad*, sgp_elbo_grad*,
+   * the *_param, *_conv, *_stencil and *_stencil_wo families, sgp_posterior_predict_grad_x and its sparse form, every *_f32
+   * entry point, every multi-GPU context. */
+  SGP_DERIV_SE = SGP_SE + 32,             /* 32 */
+  SGP_DERIV_MATERN32 = SGP_MATERN32 + 32, /* 34 */
+  SGP_DERIV_MATERN52 = SGP_MATERN52 + 32  /* 35 */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -89,7 +130,8 @@ typedef struct {
                          sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
   double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu;
-                         SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; ignored by the other kinds */
+                         SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; SGP_DERIV_*: 17 a + b; ignored by the
+                         other kinds */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

@@ -102,6 +102,7 @@ leaf(::CosineKernel) = [(16, 1.0, 0.0, Chain())]
 leaf(k::GammaExponentialKernel) = [(17, 1.0, Float64(only(k.γ)), Chain())]
 # SGP_MATERN_NU = 20: any order in (0, 32] (a Bessel function per entry); 1/2, 3/2, 5/2 are Matern12Kernel .. Matern52Kernel
 leaf(k::MaternKernel) = [(20, 1.0, Float64(only(k.ν)), Chain())]
+# derivative kinds (SGP_DERIV_SE = 32, SGP_DERIV_MATERN32 = 34, SGP_DERIV_MATERN52 = 35: 32 + the base kind, param = 17 a + b)
 # kinds of x'y, x'x and y'y (SGP_NEURALNET = 24, SGP_FBM = 25 with param = h in (0, 1], SGP_EXPONENTIATED = 26)
 leaf(::NeuralNetworkKernel) = [(24, 1.0, 0.0, Chain())]
 leaf(k::FBMKernel) = [(25, 1.0, Float64(only(k.h)), Chain())]

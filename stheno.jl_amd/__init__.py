@@ -17,7 +17,7 @@ from .kernels import (ConstantKernel, ExponentialKernel, KernelProduct, KernelSu
                       ScaleTransformedKernel, TransformedKernel,
                       SEKernel, SqExponentialKernel, WhiteKernel, with_lengthscale)
 from .gp import (GP, GPC, AtomicGP, DerivedGP, Periodic, Select, Shift, Stretch,  # noqa: F401
-                 additive_gp, atomic, compose, conv_geometry, cross, extract_patches, mean_vector, patch_convolve,
+                 additive_gp, atomic, compose, conv_geometry, cross, derivative, extract_patches, mean_vector, patch_convolve,
                  periodic, quadrature_convolve, select, shift, stencil, stretch)
 from .gppp import GPPP, extract_components, gppp, gppp_sum_model  # noqa: F401
 from .finite_gp import (VFE, ApproxPosteriorGP, FiniteGP, PosteriorGP, SparseFiniteGP,  # noqa: F401

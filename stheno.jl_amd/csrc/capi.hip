@@ -40,9 +40,12 @@ constexpr long WOUT_LARGE = 1024;  // ... for n_pad >= 32768 (halves the C-tile 
 using namespace sgp;
 
 // product chains (include/sthenomi_kprod.h) have no sharded instantiation: refused before a multi-GPU context's ranks see them
-#define REFUSE_KPROD_MULTI(ctx, sp)                        \
-  CHECK_ARG(!((ctx)->multi && spec_has_kprod(sp)), \
-            "spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context")
+#define REFUSE_KPROD_MULTI(ctx, sp)                                                                          \
+  do {                                                                                                       \
+    CHECK_ARG(!((ctx)->multi && spec_has_deriv(sp)), sgp::DERIV_REFUSAL_MULTI); /* (deriv.hip: likewise) */  \
+    CHECK_ARG(!((ctx)->multi && spec_has_kprod(sp)),                                                         \
+              "spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context");    \
+  } while (0)
 
 #define CHECK_ARG(cond, msg)       \
   do {                             \
@@ -368,6 +371,9 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   // product chains and terms of the kinds above SGP_CONST (include/sthenomi_kprod.h): a class of their own
   // (kprod.hip)
   std::vector<char> is_kp(std::max(1, nterms), 0);
+  // terms of the derivative kinds (include/sthenomi.h: SGP_DERIV_*): a class of their own (deriv.hip), validated against a table
+  // of its own (deriv_kinds.h) -- the product path's table does not know them
+  std::vector<char> is_dv(std::max(1, nterms), 0);
   std::vector<size_t> nuc_off(std::max(1, nterms), (size_t)-1);   // SGP_MATERN_NU: the term's constants of nu (kprod.hip)
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
@@ -375,12 +381,21 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
       int chain_len = 0, chain_dmax = 1;
       for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t) {
         const sgp_term& T = sp->terms[t];
-        if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) || !kp_kind_known(T.kind & 0xff))
+        if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) ||
+            !(kp_kind_known(T.kind & 0xff) || deriv_kind_known(T.kind & 0xff)))
           return fail("spec: unknown kernel kind");
         const bool cont = (T.kind & SGP_KIND_TIMES_PREV) != 0;
         const bool next_cont = t + 1 < sp->term_ptr[p + 1] && sp->terms[t + 1].kind >= 0 &&
                                (sp->terms[t + 1].kind & SGP_KIND_TIMES_PREV);
-        is_kp[t] = cont || next_cont || (T.kind & 0xff) > SGP_CONST;
+        is_dv[t] = deriv_kind_known(T.kind & 0xff);
+        if (is_dv[t]) {
+          if (cont || next_cont) return fail(DERIV_REFUSAL_CHAIN);
+          if (T.reserved) return fail(DERIV_REFUSAL_RESERVED);
+          if (T.row_input >= 0 && T.row_input < sp->n_inputs)
+            if (const char* refusal = deriv_param_refusal(T.param, (long)sp->inputs[T.row_input].dim)) return fail(refusal);
+          ++ds->n_deriv;
+        }
+        is_kp[t] = !is_dv[t] && (cont || next_cont || (T.kind & 0xff) > SGP_CONST);
         if (is_kp[t]) {
           if (cont && t == sp->term_ptr[p])
             return fail("spec: product chain: a continuation (SGP_KIND_TIMES_PREV) cannot be the first term of a block pair");
@@ -453,11 +468,12 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           cs_len[t] = ds->col_len[J];
           cs_off[t] = place(sizeof(double) * (size_t)cs_len[t]);
         }
-        if (!T.reserved && !is_kp[t]) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
+        if (!T.reserved && !is_kp[t] && !is_dv[t]) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
       }
     }
   if (ds->n_kprod && (ctx->multi || ctx->multi_rank))
     return fail("spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context");
+  if (ds->n_deriv && (ctx->multi || ctx->multi_rank)) return fail(DERIV_REFUSAL_MULTI);
   const size_t terms_off = place(sizeof(DevTerm) * (size_t)std::max(1, nterms));
   // ---- one cached device block, one pinned staging buffer
   char* d_base = (char*)pool_alloc(ctx, total);
@@ -492,23 +508,26 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
-      // plain | patch | stencil | product chains within every pair (the caller's order when the spec has none of the last three;
-      // chains stay contiguous and in the caller's order: the passes below are stable)
+      // plain | patch | stencil | derivative | product chains within every pair (the caller's order when the spec has none of
+      // the last four; chains and the groups of derivative terms stay contiguous and in the caller's order: the passes below
+      // are stable)
       auto cls = [&](int t) {
-        if (is_kp[t]) return 3;
+        if (is_kp[t]) return 4;
+        if (is_dv[t]) return 3;
         const uint32_t code = (uint32_t)sp->terms[t].reserved;
         if (!code) return 0;
         const uint32_t id = (code & 0xffffu) ? (code & 0xffffu) : (code >> 16);
         return ctx->conv_geoms[id - 1].st > 0 ? 2 : 1;
       };
       std::vector<int> order;
-      int ncls[4] = {0, 0, 0, 0};
-      for (int pass = 0; pass < 4; ++pass)
+      int ncls[5] = {0, 0, 0, 0, 0};
+      for (int pass = 0; pass < 5; ++pass)
         for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t)
           if (cls(t) == pass) order.push_back(t), ++ncls[pass];
       ds->pair_nplain.push_back(ncls[0]);
       ds->pair_npatch.push_back(ncls[1]);
-      ds->pair_nkprod.push_back(ncls[3]);
+      ds->pair_nderiv.push_back(ncls[3]);
+      ds->pair_nkprod.push_back(ncls[4]);
       for (size_t k = 0; k < order.size(); ++k) {
         const int t = order[k], pos = sp->term_ptr[p] + (int)k;
         const sgp_term& T = sp->terms[t];
@@ -605,7 +624,8 @@ extern "C" int sgp_dspec_destroy(sgp_dspec* ds) {
 
 // which terms of pair p are what (spec_segments.h), from the counts dspec_create fills for every spec
 static inline PairSegs pair_segments(const sgp_dspec* ds, int p) {
-  return pair_segments(ds->term_ptr.data(), ds->pair_nplain.data(), ds->pair_npatch.data(), ds->pair_nkprod.data(), p);
+  return pair_segments(ds->term_ptr.data(), ds->pair_nplain.data(), ds->pair_npatch.data(), ds->pair_nderiv.data(),
+                       ds->pair_nkprod.data(), p);
 }
 // the chain whose head sits at device position t: one past its last factor, and its DMAX
 static inline int chain_end(const sgp_dspec* ds, int t, int t1) { return chain_end(ds->h_terms.data(), t, t1); }
@@ -627,7 +647,8 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       long tcf = std::max(c0 / TILE, tile_c_lo), tcl = std::min((c0 + nc - 1) / TILE + 1, tile_c_hi);
       if (trf >= trl || tcf >= tcl) continue;
       int p = I * ds->ncb + J;
-      const auto [t0, tp, ts, tk, t1] = pair_segments(ds, p);   // plain | patch (conv.hip) | stencil (stencil.hip) | chains (kprod.hip)
+      // plain | patch (conv.hip) | stencil (stencil.hip) | derivative (deriv.hip) | chains (kprod.hip)
+      const auto [t0, tp, ts, tk, t1, td] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = assemble_terms_per_launch(dmax);  // terms per launch: <= 64 KiB of LDS
       int nk = (ds->symmetric && I == J) ? noise_kind : -1;
@@ -645,10 +666,16 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       for (int t = tp; t < ts; ++t)
         CHECK_RC(launch_assemble_conv(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only, t > t0 ? 1 : 0,
                                       t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
-      for (int t = ts; t < tk; ++t)
+      for (int t = ts; t < td; ++t)
         CHECK_RC(launch_assemble_stencil(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only,
                                          t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf,
                                          tcl - tcf, s));
+      for (int t = td; t < tk;) {   // one group per launch: one exponential per point pair for all its terms (deriv.hip)
+        const int cnt = deriv_group(ds->h_terms.data(), t, tk);
+        CHECK_RC(launch_assemble_deriv(Kv, ld, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, lower_only,
+                                       t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+        t += cnt;
+      }
       for (int t = tk; t < t1;) {   // whole chains per launch, as many as fit its LDS (kprod.hip: kprod_group)
         int kdmax = 1;
         const int cnt = kprod_group(ds->h_terms.data(), t, t1, &kdmax);
@@ -1604,7 +1631,7 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag: block lengths differ");
     int p = I * ds->ncb + I;
-    const auto [t0, tp, ts, tk, t1] = pair_segments(ds, p);
+    const auto [t0, tp, ts, tk, t1, td] = pair_segments(ds, p);
     if (tp < ts) {   // patch terms (conv.hip), in one launch with the plain terms in front of them
       int max_d = 1, d_all = -1, max_px = 1;
       for (int t = tp; t < ts; ++t) {
@@ -1618,10 +1645,15 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
     } else {
       CHECK_RC(launch_diag_terms(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + t0, ts - t0, s));
     }
-    if (ts < tk) {        // stencil terms (stencil.hip), added onto the plain and patch diagonal
+    if (ts < td) {        // stencil terms (stencil.hip), added onto the plain and patch diagonal
       int max_dim = 1;
-      for (int t = ts; t < tk; ++t) max_dim = std::max(max_dim, ds->h_terms[t].dim);
-      CHECK_RC(launch_diag_stencil(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + ts, tk - ts, max_dim, s));
+      for (int t = ts; t < td; ++t) max_dim = std::max(max_dim, ds->h_terms[t].dim);
+      CHECK_RC(launch_diag_stencil(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + ts, td - ts, max_dim, s));
+    }
+    for (int t = td; t < tk;) {   // derivative terms, in the groups of the matrix assembly: the same sums
+      const int cnt = deriv_group(ds->h_terms.data(), t, tk);
+      CHECK_RC(launch_diag_deriv(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
+      t += cnt;
     }
     for (int t = tk; t < t1;) {   // product chains, in the launch groups of the matrix assembly: the same sums
       int kdmax = 1;
@@ -1892,18 +1924,25 @@ struct StencilWo {
 // caller says it carries them (leave.kprod: the cores set it where their entry points take chains).
 // dgp (NULL: not asked for): d / d param per term, which for the plain terms is non-zero for SGP_CONST alone -- those run
 // through the chain kernel once more, as chains of length one, for that entry, between the stencil terms and the chains.
+static GradLeave pool_leave() {   // what sgp_logpdf_grad_batch / _pool carry beyond the plain terms: derivative terms
+  GradLeave l;
+  l.deriv = true;
+  return l;
+}
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr, long n_tc,
                          DevBuf& dpart, double* dgc, double* dgs, hipStream_t s, const GradLeave& leave, double* dgp) {
   CHECK_ARG(leave.stencil || !ds->n_stencil, "gradient contraction: stencil terms are not supported");
   CHECK_ARG(leave.patch || !ds->n_patch, "gradient contraction: patch (convolutional) terms are not supported");
   CHECK_ARG(leave.kprod || !ds->n_kprod,
             "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
+  CHECK_ARG(leave.deriv || !ds->n_deriv, "gradient contraction: derivative terms are not supported here");
   long need = std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16);
+  if (ds->n_deriv) need = std::max(need, grad_deriv_partials(n_tr, n_tc));
   for (int p = 0; p < ds->nrb * ds->ncb; ++p) {   // the partial sums of the largest patch or stencil term
     const int I = p / ds->ncb, J = p % ds->ncb;
     const PairSegs g = pair_segments(ds, p);
     for (int t = g.tp; t < g.ts; ++t) need = std::max(need, grad_conv_partials(ds->row_len[I], ds->col_len[J], ds->h_terms[t]));
-    for (int t = g.ts; t < g.tk; ++t)
+    for (int t = g.ts; t < g.td; ++t)
       need = std::max(need, grad_stencil_partials(ds->row_off[I], ds->row_len[I], ds->col_off[J], ds->col_len[J], ds->h_terms[t]));
   }
   CHECK_RC(dpart.alloc((size_t)need));
@@ -1914,7 +1953,7 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       long r0 = ds->row_off[I], nr = ds->row_len[I], c0 = ds->col_off[J], nc = ds->col_len[J];
       long trf = r0 / TILE, trl = (r0 + nr - 1) / TILE + 1, tcf = c0 / TILE, tcl = (c0 + nc - 1) / TILE + 1;
       int p = I * ds->ncb + J;
-      const auto [t0, tp, ts, tk, t1] = pair_segments(ds, p);
+      const auto [t0, tp, ts, tk, t1, td] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = std::min(8, std::max(1, 64 / dmax));
       for (int t = t0; t < tp; t += per) {
@@ -1924,9 +1963,15 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       }
       for (int t = tp; t < ts; ++t)
         CHECK_RC(launch_grad_conv(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, dpart.p, dgc + t, dgs + t, s));
-      for (int t = ts; t < tk; ++t)
+      for (int t = ts; t < td; ++t)
         CHECK_RC(launch_grad_stencil(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, dpart.p, dgc + t, dgs + t,
                                      s));
+      for (int t = td; t < tk;) {   // derivative terms, one group per launch (deriv.hip)
+        const int cnt = deriv_group(ds->h_terms.data(), t, tk);
+        CHECK_RC(launch_grad_deriv(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, trf, tcf, trl - trf,
+                                   tcl - tcf, dpart.p, dgc + t, dgs + t, s));
+        t += cnt;
+      }
       for (int t = t0; dgp && t < tp; ++t)
         if (ds->h_terms[t].kind == SGP_CONST)
           CHECK_RC(launch_grad_kprod(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, 1, 1, trf, tcf,
@@ -2031,6 +2076,7 @@ struct InputPass {
 static int input_pass(const sgp_dspec* ds, const InputPass& q, hipStream_t s) {
   TermGradBufs& b = *q.bufs;
   if (!b.asked()) return 0;
+  CHECK_ARG(!ds->n_deriv, "input-point and scale gradients through derivative terms are not supported");
   const bool points = b.want_x != nullptr;
   const double w = q.symmetric ? 2.0 : 1.0;
   for (int I = 0; I < ds->nrb; ++I)
@@ -2057,7 +2103,7 @@ static int input_pass(const sgp_dspec* ds, const InputPass& q, hipStream_t s) {
         CHECK_RC(launch_grad_conv_points(q.Gm, q.ldg, q.alpha, r0, nr, c0, nc, T, ds->d_terms + t, 1.0,
                                          b.input(T.hr ? ds->term_col_input[t] : ds->term_row_input[t]), s));
       }
-      for (int t = g.ts; points && t < g.tk; ++t) {   // (stencil.hip; transposed: sides and stencils swapped)
+      for (int t = g.ts; points && t < g.td; ++t) {   // (stencil.hip; transposed: sides and stencils swapped)
         const DevTerm& T = ds->h_terms[t];
         CHECK_RC(launch_grad_stencil_points(q.Gm, 1, q.ldg, q.alpha, r0, nr, c0, nc, T, 0, w, b.input(ds->term_row_input[t]), s));
         if (!q.symmetric)
@@ -2095,6 +2141,12 @@ static int logpdf_grad_core(sgp_ctx* ctx, const LogpdfGradArgs& a) {
   CHECK_ARG(ctx && a.spec && a.noise && a.y && a.logpdf_out, "sgp_logpdf_grad: NULL argument");
   CHECK_ARG(a.spec->symmetric, "sgp_logpdf_grad: spec must be symmetric");
   CHECK_ARG(a.noise_kind >= SGP_NOISE_SCALAR && a.noise_kind <= SGP_NOISE_DENSE, "sgp_logpdf_grad: bad noise kind");
+  // derivative terms (deriv.hip) are contracted for sgp_logpdf_grad itself -- grad_coef and grad_inscale -- and for no other
+  // member of the family
+  CHECK_ARG(a.leave.deriv || !spec_has_deriv(a.spec),
+            "sgp_logpdf_grad_x / _xs / _param / _conv / _stencil / _stencil_wo: input-point, scale, parameter, patch and stencil "
+            "gradients through derivative terms are not supported: sgp_logpdf_grad returns grad_coef and grad_inscale");
+  CHECK_ARG(!(ctx->multi && spec_has_deriv(a.spec)), DERIV_REFUSAL_MULTI);
   CHECK_RC(check_grad_leave(ctx, "sgp_logpdf_grad", a.leave, a.spec));
   CHECK_ARG(!(a.grad_inputs || a.grad_rowscale) || a.leave.kprod || a.leave.stencil || !spec_has_kprod(a.spec),
             "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
@@ -2250,8 +2302,10 @@ extern "C" int sgp_logpdf_grad(sgp_ctx* ctx, const sgp_cov_spec* spec, const dou
                                const double* noise, const double* y, double* logpdf_out, double* grad_y,
                                double* grad_mean, double* grad_noise, double* grad_coef,
                                double* grad_inscale) {
-  return drv_logpdf_grad(ctx, logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise,
-                                               grad_coef, grad_inscale));
+  LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
+                                      grad_inscale);
+  a.leave.deriv = true;   // (this entry point alone carries derivative terms)
+  return drv_logpdf_grad(ctx, a);
 }
 
 extern "C" int sgp_logpdf_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const double* mean, int noise_kind,
@@ -2506,7 +2560,7 @@ int pooled_chunk(sgp_ctx* ctx, PoolCall& call, const int* ids, int nb, std::vect
     if (PoolCall::at(call.grad_noise, gb))
       CHECK_RC(launch_grad_noise(M.Kinv.p, M.n_pad, alpha, M.N, M.nd.kind == SGP_NOISE_DIAG, gn, s));
     if (PoolCall::at(call.grad_coef, gb) || PoolCall::at(call.grad_inscale, gb))
-      CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, M.n_pad, alpha, M.T_c, M.T_c, M.part, gc, gs, s, GradLeave(), nullptr));
+      CHECK_RC(contract_spec(M.g.ds, M.Kinv.p, M.n_pad, alpha, M.T_c, M.T_c, M.part, gc, gs, s, pool_leave(), nullptr));
   }
   std::vector<double> h_res((size_t)res_len);
   std::vector<int> h_info((size_t)nb);
@@ -3747,6 +3801,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradSha
   CHECK_ARG(a.noise_kind == SGP_NOISE_SCALAR || a.noise_kind == SGP_NOISE_DIAG,
             "sgp_elbo_grad: Sigma_y must be isotropic or diagonal (as in AbstractGPs.elbo)");
   CHECK_ARG(a.z_noise_kind >= SGP_NOISE_SCALAR && a.z_noise_kind <= SGP_NOISE_DENSE, "sgp_elbo_grad: bad Sigma_z kind");
+  CHECK_ARG(!spec_has_deriv(a.zz) && !spec_has_deriv(a.xz),
+            "sgp_elbo_grad: gradients of the ELBO through derivative terms are not supported");
   CtxScope scope(ctx);
   SpecGuard gz, gx;
   CHECK_RC(dspec_create(ctx, a.zz, &gz.ds));
@@ -4056,6 +4112,8 @@ static int diag_grad_core(sgp_ctx* ctx, const DiagGradArgs& a) {
   // a.leave.stencil: sgp_kernelmatrix_diag_grad_stencil, include/sthenomi_stencil_grad.h)
   CHECK_ARG(ctx && a.spec && a.w && (a.leave.kprod || (a.grad_coef && a.grad_inscale)),
             "sgp_kernelmatrix_diag_grad: NULL argument");
+  CHECK_ARG(!spec_has_deriv(a.spec),
+            "sgp_kernelmatrix_diag_grad: gradients of the diagonal through derivative terms are not supported");
   CHECK_RC(check_grad_leave(ctx, "sgp_kernelmatrix_diag_grad", a.leave, a.spec));
   CHECK_ARG(a.leave.kprod || !spec_has_kprod(a.spec),
             "sgp_kernelmatrix_diag_grad: gradients through product chains and the RQ / LINEAR kinds are not supported: call "

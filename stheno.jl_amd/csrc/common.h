@@ -217,6 +217,23 @@ int launch_diag_grad_kprod(const double* w, long n, const DevTerm* h_terms, int 
                            double* out_param, double* const* gxr, double* const* gxc, double* out_rs, double* out_cs,
                            hipStream_t s);
 
+// deriv.hip: the derivative kinds (include/sthenomi.h: SGP_DERIV_*), a term class of its own.  A launch carries ONE group of a
+// pair's derivative terms (deriv_kinds.h: deriv_group -- the same base kind, points and scale vectors), host copies at h_terms,
+// device copies at d_terms.  Arguments of launch_assemble_deriv as launch_assemble_block.
+int launch_assemble_deriv(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* h_terms,
+                          const DevTerm* d_terms, int nterms, int lower_only, int accumulate, int noise_kind, double sigma2,
+                          const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
+                          long tile_c_cnt, hipStream_t s);
+// out[i] (i < n) = (accumulate ? out[i] : 0) + the group, summed as launch_assemble_deriv sums entry (i, i)
+int launch_diag_deriv(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
+                      hipStream_t s);
+// gradient contraction of one group: out_coef / out_scale point at the group's first entry (nterms each); partials:
+// grad_deriv_partials(trc, tcc) doubles, reduced in a fixed order.  G as in launch_grad_block
+long grad_deriv_partials(long trc, long tcc);
+int launch_grad_deriv(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
+                      const DevTerm* h_terms, const DevTerm* d_terms, int nterms, long trf, long tcf, long trc, long tcc,
+                      double* partials, double* out_coef, double* out_scale, hipStream_t s);
+
 void set_error(const std::string& s);
 
 #define SGP_HIP(expr)                                                                     \

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "../../include/sthenomi.h"
 #include "../../include/sthenomi_bench.h"
+#include "deriv_kinds.h"
 
 #include <mutex>
 #include <vector>
@@ -55,6 +56,7 @@ struct GradLeave {
   bool kprod = false;     // product chains and the RQ / LINEAR kinds (include/sthenomi_kprod.h, sthenomi_kprod_grad.h)
   bool patch = false;     // patch (convolutional) terms (include/sthenomi_conv_grad.h)
   bool stencil = false;   // stencil terms (include/sthenomi_stencil_grad.h, sthenomi_stencil_wo.h); set together with patch
+  bool deriv = false;     // derivative terms (include/sthenomi.h: SGP_DERIV_*): sgp_logpdf_grad and its batch / pool forms alone
 };
 // sgp_logpdf_grad / _x / _xs / _param / _param_xs / _conv / _stencil / _stencil_wo
 struct LogpdfGradArgs {
@@ -421,12 +423,25 @@ inline bool spec_has_stencil(const sgp_ctx* ctx, const sgp_cov_spec* sp) {
   return false;
 }
 
-// a term of a product chain (include/sthenomi_kprod.h) or of a kind only kprod.hip evaluates
+// a term of a derivative kind (include/sthenomi.h: SGP_DERIV_*; deriv.hip): every path without a derivative kernel refuses
+// such a spec by name, before any other class's refusal reads its terms
+inline bool term_is_deriv(const sgp_term& T) { return T.kind >= 0 && sgp::deriv_kind_known(T.kind & 0xff); }
+inline bool spec_has_deriv(const sgp_cov_spec* sp) {
+  if (!sp || !sp->term_ptr || !sp->terms) return false;
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t)
+    if (term_is_deriv(sp->terms[t])) return true;
+  return false;
+}
+
+// a term of a product chain (include/sthenomi_kprod.h) or of a kind only kprod.hip evaluates (the derivative kinds are
+// deriv.hip's)
 inline bool spec_has_kprod(const sgp_cov_spec* sp) {
   if (!sp || !sp->term_ptr || !sp->terms) return false;
   const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
   for (int t = 0; t < n; ++t)
-    if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || (sp->terms[t].kind & 0xff) > SGP_CONST) return true;
+    if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || ((sp->terms[t].kind & 0xff) > SGP_CONST && !term_is_deriv(sp->terms[t])))
+      return true;
   return false;
 }
 
@@ -455,5 +470,9 @@ struct sgp_dspec {
   // and in the caller's order; n_kprod == 0: none
   std::vector<int> pair_nkprod;
   int n_kprod = 0;
+  // derivative terms (deriv.hip): between the stencil terms and the chains of their pair (pair_nderiv of them), in the caller's
+  // order, which keeps the terms of a group next to each other; n_deriv == 0: none
+  std::vector<int> pair_nderiv;
+  int n_deriv = 0;
   std::vector<int> term_src;           // index in the caller's spec->terms of the term at each device position
 };

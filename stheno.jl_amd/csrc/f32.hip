@@ -516,6 +516,7 @@ extern "C" int sgp_logpdf_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const doub
   F_CHECK_ARG(spec->symmetric, "sgp_logpdf_f32: spec must be symmetric");
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG,
               "sgp_logpdf_f32: noise kind must be SCALAR or DIAG");
+  F_CHECK_ARG(!spec_has_deriv(spec), "sgp_logpdf_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_logpdf_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_kprod(spec), "sgp_logpdf_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");
@@ -592,6 +593,7 @@ extern "C" int sgp_logpdf_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const doub
 
 extern "C" int sgp_kernelmatrix_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, float* K, int64_t ldk) {
   F_CHECK_ARG(ctx && spec && K, "sgp_kernelmatrix_f32: NULL argument");
+  F_CHECK_ARG(!spec_has_deriv(spec), "sgp_kernelmatrix_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_kernelmatrix_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_kprod(spec), "sgp_kernelmatrix_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");
@@ -700,6 +702,7 @@ extern "C" int sgp_rand_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   F_CHECK_ARG(ctx && spec && noise && Z && out, "sgp_rand_f32: NULL argument");
   F_CHECK_ARG(spec->symmetric, "sgp_rand_f32: spec must be symmetric");
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG, "sgp_rand_f32: noise kind must be SCALAR or DIAG");
+  F_CHECK_ARG(!spec_has_deriv(spec), "sgp_rand_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_rand_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec), "sgp_rand_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_kprod(spec), "sgp_rand_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");
@@ -756,6 +759,7 @@ extern "C" int sgp_posterior_mean_var_f32(sgp_ctx* ctx, const sgp_cov_spec* spec
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG,
               "sgp_posterior_mean_var_f32: noise kind must be SCALAR or DIAG");
   F_CHECK_ARG(!var_out || prior_ss, "sgp_posterior_mean_var_f32: prior_ss spec required for var");
+  F_CHECK_ARG(!spec_has_deriv(spec) && !spec_has_deriv(cross) && !spec_has_deriv(prior_ss), "sgp_posterior_mean_var_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec) && !spec_has_stencil(ctx, cross) && !spec_has_stencil(ctx, prior_ss), "sgp_posterior_mean_var_f32: stencil terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_patch(spec) && !spec_has_patch(cross) && !spec_has_patch(prior_ss), "sgp_posterior_mean_var_f32: patch (convolutional) terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_kprod(spec) && !spec_has_kprod(cross) && !spec_has_kprod(prior_ss), "sgp_posterior_mean_var_f32: product chains and the RQ / LINEAR kinds have no fp32 path: use the fp64 entry point");

@@ -575,6 +575,7 @@ int predgrad_impl(sgp_ctx* ctx, const Kept& k, const PgArgs& a) {
 int check_specs(const sgp_ctx* ctx, const PgArgs& a) {
   for (const sgp_cov_spec* sp : {a.cross, a.prior_ss}) {
     if (!sp) continue;
+    REFUSE_UNLESS(!spec_has_deriv(sp), a.who, "gradients through derivative terms are not supported");
     REFUSE_UNLESS(!spec_has_stencil(ctx, sp), a.who, "gradients through stencil terms are not supported");
     REFUSE_UNLESS(!spec_has_patch(sp), a.who, "gradients through patch (convolutional) terms are not supported");
     REFUSE_UNLESS(!spec_has_kprod(sp), a.who,

@@ -57,6 +57,14 @@ def _refuse_product_gradient(what, *specs):
                                   "logpdf_and_gradient_param / elbo_and_gradient_param carry inputs, scales and the ELBO")
 
 
+def _refuse_deriv(what, *specs):
+    """`what` through derivative terms (`derivative`; include/sthenomi.h: SGP_DERIV_*) is not implemented (the library refuses
+    it too): logpdf_and_gradient(fx, y) and its batch / pool forms return d_coef and d_inscale"""
+    if any(sp.has_deriv for sp in specs):
+        raise NotImplementedError(f"{what} through derivative covariance terms is not supported: logpdf_and_gradient(fx, y) "
+                                  "returns d_coef and d_inscale of a model with derivative(f)")
+
+
 def _is_prior(f):
     return isinstance(f, (GPPP, SthenoAbstractGP))
 
@@ -251,6 +259,7 @@ def mean_and_var_and_gradient(fx):
         raise NotImplementedError("mean_and_var_and_gradient is not supported on a multi-GPU context (the factor is sharded)")
     cross, _, _ = build_spec(f.prior, fx.x, f.prior, f._train_inputs()[0])
     pss = _prior_spec(f.prior, fx.x)
+    _refuse_deriv("mean_and_var_and_gradient", cross, pss)
     _refuse_patch_gradient(cross, pss)
     _refuse_product_gradient("mean_and_var_and_gradient", cross, pss)
     if (any(rs is not None for rs in cross.term_row_scale) or any(rs is not None for rs in pss.term_row_scale)
@@ -519,6 +528,7 @@ def logpdf_f32(fx, y):
     if yv.shape[0] != n:
         raise ValueError("length(y) != length(fx)")
     spec = _prior_spec(fx.f, fx.x)
+    _refuse_deriv("logpdf_f32: the fp32 path", spec)
     if spec.has_stencil:
         raise NotImplementedError("stencil terms have no fp32 path: call logpdf, which runs them in fp64")
     if spec.has_kprod:
@@ -584,6 +594,13 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     include the mirror-image pair (J, I).  d_inscale is the derivative w.r.t. a common scale g of the
     term's inputs (stretch(f, g)); a lengthscale l = 1/g gives d/dl = -g^2 d_inscale.
 
+    A model with derivative(f) (include/sthenomi.h: SGP_DERIV_*) is taken with inputs=False, scales=False: the records of its
+    derivative terms carry "deriv": (p or None, q or None), the differentiated coordinate of the row / column side.  Their
+    d_inscale keeps its meaning -- both inputs scaled by g, the differentiation taken with respect to the scaled points -- so
+    the chain to a scalar stretch a below the node (stretch(f, a), or with_lengthscale(k, 1 / a)), whose Jacobian factor a
+    sits in the coefficient once per differentiated side, is, with m the number of differentiated sides of the term,
+        d / da = (m * coef * d_coef + d_inscale) / a.
+
     A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
     sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
     index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
@@ -593,6 +610,7 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     yv, spec = _logpdf_grad_spec(fx, y)
     _refuse_patch_gradient(spec)
     if inputs or scales:
+        _refuse_deriv("logpdf_and_gradient: inputs=True / scales=True", spec)
         _refuse_product_gradient("logpdf_and_gradient: inputs=True / scales=True", spec)
     kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
     if spec.has_kprod:
@@ -647,6 +665,7 @@ def _attach_d_transform(records, spec, gx):
 
 def _refuse_param_family(what, *specs):
     """what the superset family of include/sthenomi_kprod_grad.h does not carry: patch / stencil sides, a multi-GPU context"""
+    _refuse_deriv(what, *specs)
     _refuse_patch_gradient(*specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what}: a product of kernels (the gradients of include/sthenomi_kprod_grad.h) is not "
@@ -679,6 +698,7 @@ def logpdf_and_gradient_param(fx, y, inputs=False, scales=False):
 
 def _refuse_conv_family(what, *specs):
     """what the entry points of include/sthenomi_conv_grad.h refuse: a multi-GPU context, stencil terms"""
+    _refuse_deriv(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_stencil for sp in specs):
@@ -710,6 +730,7 @@ def logpdf_and_gradient_conv(fx, y):
 def _refuse_stencil_family(what, *specs):
     """what the entry points of include/sthenomi_stencil_grad.h refuse: a multi-GPU context; and what their records cannot
     carry"""
+    _refuse_deriv(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_patch or sp.has_stencil for sp in specs) and any(sp.has_kprod for sp in specs):
@@ -1159,6 +1180,7 @@ def posterior_mean_and_var_f32(fx, y, xs):
     spec = _prior_spec(fx.f, fx.x)
     cross, _, _ = build_spec(fx.f, xs, fx.f, fx.x)
     pss = _prior_spec(fx.f, xs)
+    _refuse_deriv("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
     kind, nbuf = _lib._noise_args(fx.noise, len(y))
     if kind == _lib.NOISE_DENSE or not spec.f32_supported() or not cross.f32_supported():
         raise NotImplementedError("beyond the fp32 kernels' limits (dense noise, input dimension > 16, too many terms)")
@@ -1277,6 +1299,23 @@ def _term_records_kprod(spec, gc, gs, gp, symmetric=True):
     return out
 
 
+def _deriv_sides(kind, param):
+    """(p or None, q or None): the differentiated coordinate of the row / column side of a term of a derivative kind; None
+    for every other kind"""
+    if (int(kind) & _lib.KIND_MASK) not in _lib.DERIV_OF.values():
+        return None
+    a, b = divmod(int(param), _lib.DERIV_PARAM_BASE)
+    return (a - 1 if a else None, b - 1 if b else None)
+
+
+def _mirror_param(kind, param):
+    """the param of a term's mirror image in pair (J, I): a derivative term's sides swap, every other param stays"""
+    if _deriv_sides(kind, param) is None:
+        return param
+    a, b = divmod(int(param), _lib.DERIV_PARAM_BASE)
+    return float(_lib.DERIV_PARAM_BASE * b + a)
+
+
 def _swap_sides(key):
     """(row, col[, row stencil, col stencil]) of a term's geometry key seen from the mirror pair"""
     return key[1::-1] + key[:1:-1]
@@ -1307,6 +1346,8 @@ def _term_records(spec, gc, gs, symmetric, gp=None):
                 out.append(dict(I=I, J=J, kind=T.kind, coef=T.coef, row_input=T.row_input, col_input=T.col_input,
                                 row_scaled=sid[t][0] is not None, col_scaled=sid[t][1] is not None,
                                 t=t, mirror_t=None, d_coef=float(gc[t]), d_inscale=float(gs[t])))
+                if _deriv_sides(T.kind, T.param) is not None:
+                    out[-1]["deriv"] = _deriv_sides(T.kind, T.param)
                 if spec.has_patch:
                     out[-1].update(row_geom=geo[t][0], col_geom=geo[t][1])
                 if spec.has_stencil:
@@ -1316,7 +1357,8 @@ def _term_records(spec, gc, gs, symmetric, gp=None):
             for J in range(I + 1, ncb):
                 for t in range(tp[I * ncb + J], tp[I * ncb + J + 1]):
                     T = spec._terms[t]
-                    k = index.get((J, I, T.kind, T.col_input, T.row_input, T.param, sid[t][1], sid[t][0]) + _swap_sides(geo[t]))
+                    k = index.get((J, I, T.kind, T.col_input, T.row_input, _mirror_param(T.kind, T.param), sid[t][1], sid[t][0]) +
+                                  _swap_sides(geo[t]))
                     if k is None:
                         raise AssertionError("symmetric spec without a mirror term: flattener invariant broken")
                     out[k]["mirror_t"] = t
@@ -1418,6 +1460,7 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
     if isinstance(vfe, SparseFiniteGP):
         return elbo_and_gradient(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, scales=scales)
     specs, head = _elbo_grad_specs(vfe, fx, y)
+    _refuse_deriv("elbo_and_gradient", *specs)
     _refuse_patch_gradient(*specs)
     _refuse_product_gradient("elbo_and_gradient", *specs)
     F = _elbo_grad_frame(specs, head)

@@ -17,6 +17,8 @@ with  +            -> union of paths                 (addition.jl:20-47; known-f
       cross / GPPP -> one process per block           (cross.jl:54-93, gppp.jl:25-43)
       stencil      -> the path carries (offsets, weights): ONE term per pair of paths, the library sums the
                       shifted evaluations (include/sthenomi_stencil.h)
+      derivative   -> the path carries a direction; a pair of paths gives one term of a derivative kind per pair of
+                      non-zero direction components (include/sthenomi.h: SGP_DERIV_*)
 and the leaf kernel expanded into SimpleKernel terms (ScaledKernel -> coefficient, KernelSum ->
 several terms, ScaleTransform -> input scale, KernelProduct -> a chain of terms the library multiplies entry by
 entry: include/sthenomi_kprod.h).  Block pairs without a common atom get no
@@ -34,9 +36,9 @@ from .inputs import BlockData, ColVecs, GPPPInput, as_matrix, blocks, is_pair_ve
 
 
 class _Path:
-    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom", "st", "prov")
+    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom", "st", "prov", "dv")
 
-    def __init__(self, key, atom, c, r, X, chain=(), geom=None, st=None, prov=None):
+    def __init__(self, key, atom, c, r, X, chain=(), geom=None, st=None, prov=None, dv=None):
         # chain: the input warps applied on the way down, outermost first, as (warp, inputs before it)
         # geom: (H, W, ph, pw) when the path passed a patch_convolve node -- X then holds the flattened images
         # st: (offsets D x Q, weights Q) when the path passed a stencil node -- the offsets in the coordinates of X
@@ -44,8 +46,9 @@ class _Path:
         #       was merged into this path (sum c_i == c); layers = ((stencil node, M), ...) outermost first, M (dim of X x dim
         #       of the node's offsets) the product of the Stretch / Select maps below the node.  Point (p_1, ..., p_K) of st
         #       sits at the C-order index of its tuple: offsets sum_k M_k A_k[:, p_k], weight prod_k w_k[p_k]
+        # dv: the direction (length dim of X) along which the process is differentiated when the path passed a derivative node
         self.key, self.atom, self.c, self.r, self.X, self.chain, self.geom, self.st = key, atom, c, r, X, chain, geom, st
-        self.prov = prov
+        self.prov, self.dv = prov, dv
 
 
 class _ScaleVector(np.ndarray):
@@ -165,9 +168,64 @@ def _paths(f, x, c, r, key, mat, chain=(), geom=None):
         # (include/sthenomi_stencil.h)
         return _stencil_paths(f.args[1], x, c, r, key, mat, chain, (f.args[2], f.args[3]),
                               ((f, np.eye(f.args[2].shape[0])),))
+    if op == "deriv":
+        # d f / d x[dim]: the paths of f read these points and carry the direction e_dim (include/sthenomi.h: SGP_DERIV_*)
+        D = as_matrix(x).shape[0] if isinstance(x, ColVecs) else 1
+        if f.args[2] >= D:
+            raise ValueError(f"derivative: dim = {f.args[2]} for inputs of dimension {D}")
+        v = np.zeros(D)
+        v[f.args[2]] = 1.0
+        return _deriv_paths(f.args[1], x, c, r, key, mat, chain, v)
     if op == "cross":
         raise ValueError("cross(...) can only appear at block level")
     raise ValueError(op)
+
+
+def _deriv_paths(f, x, c, r, key, mat, chain, v):
+    """the paths below a derivative node: what commutes with differentiation along the direction v (in the coordinates of
+    x) -- sums, scalar scales, `+ known`, Shift, and Stretch / Select, which map the direction as _map_offsets maps offsets
+    (the chain rule: f(g(x)) differentiated along v is f differentiated along Dg v) -- and nothing else"""
+    if isinstance(f, _gp.AtomicGP):
+        if not isinstance(f.gp, _gp.GP):
+            raise NotImplementedError("derivative of a nested GPPP is not supported")
+        m = f.gp.mean_spec
+        if m is not None and not _gp._is_real(m):
+            raise NotImplementedError("derivative: a callable prior mean below the node cannot be differentiated (a constant "
+                                      "mean differentiates to 0)")
+        X = mat(x)
+        if X.shape[0] != v.shape[0]:
+            raise ValueError(f"derivative: a direction of dimension {v.shape[0]} for inputs of dimension {X.shape[0]}")
+        return [_Path(key + (id(f),), f, c, r, X, chain, dv=v)]
+    if isinstance(f, GPPP) or not isinstance(f, _gp.DerivedGP):
+        raise NotImplementedError("derivative of a nested GPPP is not supported" if isinstance(f, GPPP) else
+                                  f"derivative over {type(f).__name__} is not supported")
+    op = f.args[0]
+    if op == "+":
+        return _deriv_paths(f.args[1], x, c, r, key, mat, chain, v) + _deriv_paths(f.args[2], x, c, r, key, mat, chain, v)
+    if op == "+known":
+        return _deriv_paths(f.args[2], x, c, r, key, mat, chain, v)
+    if op == "*":
+        s = f.args[1]
+        if not _gp._is_real(s):
+            raise NotImplementedError("derivative: a function-valued scale below the node is not supported (the product rule "
+                                      "needs the scale's own derivative; only scalar scales commute)")
+        return _deriv_paths(f.args[2], x, c * float(s), r, key, mat, chain, v)
+    if op == "o":
+        g = f.args[2]
+        if isinstance(g, _gp.Shift):
+            return _deriv_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), v)
+        if isinstance(g, (_gp.Stretch, _gp.Select)):
+            return _deriv_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),),
+                                _map_offsets(g, v[:, None])[:, 0])
+        raise NotImplementedError(f"derivative: the warp {_warp_name(g)} below the node is not supported (only Shift, Stretch "
+                                  "and Select are)")
+    if op == "deriv":
+        raise NotImplementedError("derivative of a derivative on one side (a second derivative) is not supported")
+    if op == "conv":
+        raise NotImplementedError("derivative of a patch_convolve is not supported")
+    if op == "stencil":
+        raise NotImplementedError("derivative of a stencil is not supported")
+    raise NotImplementedError(f"derivative over `{op}` is not supported")
 
 
 def _conv_paths(f, x, c, r, key, mat, chain, geom):
@@ -201,6 +259,8 @@ def _conv_paths(f, x, c, r, key, mat, chain, geom):
         raise NotImplementedError("patch_convolve of a patch_convolve is not supported")
     if op == "stencil":
         raise NotImplementedError("patch_convolve of a stencil is not supported")
+    if op == "deriv":
+        raise NotImplementedError("patch_convolve of a derivative is not supported")
     raise NotImplementedError(f"patch_convolve over `{op}` is not supported")
 
 
@@ -263,6 +323,8 @@ def _stencil_paths(f, x, c, r, key, mat, chain, st, layers):
                               layers + ((f, np.eye(B.shape[0])),))
     if op == "conv":
         raise NotImplementedError("stencil of a patch_convolve is not supported")
+    if op == "deriv":
+        raise NotImplementedError("stencil of a derivative is not supported")
     raise NotImplementedError(f"stencil over `{op}` is not supported")
 
 
@@ -275,13 +337,14 @@ def _merge_paths(ps, cancelled=None):
     respect to their stencils, which does not vanish (stencil_node_gradients refuses such a spec)"""
     out, index = [], {}
     for p in ps:
-        k = (p.key, id(p.X), id(p.r) if p.r is not None else None, p.geom, _st_key(p.st))
+        k = (p.key, id(p.X), id(p.r) if p.r is not None else None, p.geom, _st_key(p.st),
+             None if p.dv is None else p.dv.tobytes())
         if k in index:
             index[k].c += p.c
             if p.prov is not None:
                 index[k].prov = index[k].prov + p.prov
         else:
-            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom, p.st, None if p.prov is None else list(p.prov))
+            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom, p.st, None if p.prov is None else list(p.prov), p.dv)
             index[k] = q
             out.append(q)
     # paths that cancel exactly (f - f, 2 f - f - f, ...) leave no term: the block is an exact zero, as in the
@@ -339,7 +402,14 @@ def build_spec(f, x, f2=None, x2=None):
                     if has_st and (p.geom is not None or q.geom is not None):
                         raise NotImplementedError("a covariance between a patch_convolve view and a stencil view of one "
                                                   "process is not supported")
+                    has_dv = p.dv is not None or q.dv is not None
+                    if has_dv and (has_st or p.geom is not None or q.geom is not None):
+                        raise NotImplementedError("a covariance between a derivative view and a patch_convolve or stencil "
+                                                  "view of one process is not supported")
                     for (kc, factors) in p.atom.gp.kernel.leaf_products():
+                        if has_dv:
+                            _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order)
+                            continue
                         if len(factors) > 1 or factors[0][0] > _lib.CONST:
                             # a product of kernels, or a kind that exists on the product path only: a chain of terms
                             # (include/sthenomi_kprod.h), each factor reading its own view of the points
@@ -429,6 +499,42 @@ def build_spec(f, x, f2=None, x2=None):
     spec.input_origin = table.origin   # per spec input: (side, block, warp chain, kernel input chain, raw points)
     spec.block_shapes = ([_leaf_shape(v) for _, v in rows], [_leaf_shape(v) for _, v in cols])
     return spec, rows, cols
+
+
+def _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order):
+    """the terms of one leaf of the kernel between the paths p and q, at least one of which carries a direction: one term of
+    the leaf's derivative kind per pair of non-zero components of the two directions, seen through the kernel's own input
+    transform (kernels.chain_direction), the components -- the Jacobian factors -- in its coefficient"""
+    if len(factors) > 1 or factors[0][0] not in _lib.DERIV_OF:
+        raise NotImplementedError("derivative: the kernel below the node must be SE, Matern-3/2 or Matern-5/2, or a sum or "
+                                  "scaling of these (no products of kernels, no Matern-1/2, no kernel of the product path)")
+    (kind, _, s), = factors
+    sides = []
+    for path in (p, q):
+        if path.dv is None:
+            sides.append([(0, 1.0)])
+            continue
+        v = _kernels.chain_direction(s, path.dv)
+        if v is None:
+            raise NotImplementedError("derivative: the kernel's input transform (PeriodicTransform) is not linear: only "
+                                      "ScaleTransform / ARDTransform / LinearTransform / SelectTransform / with_lengthscale are "
+                                      "supported below the node")
+        sides.append([(d + 1, float(v[d])) for d in range(v.shape[0]) if v[d] != 0.0])
+    ri = table.get(p.X, s, ("row", I, p.chain))
+    ci = table.get(q.X, s, ("row" if symmetric else "col", J, q.chain))
+    if np.asarray(table.arrays[ri]).shape[0] > _lib.DERIV_MAX_DIM:
+        raise NotImplementedError(f"derivative: inputs of dimension {np.asarray(table.arrays[ri]).shape[0]} are beyond the "
+                                  f"library's limit of {_lib.DERIV_MAX_DIM}")
+    for a, va in sides[0]:
+        for b, vb in sides[1]:
+            param = float(_lib.DERIV_PARAM_BASE * a + b)
+            k = (_lib.DERIV_OF[kind], param, ri, ci, id(p.r) if p.r is not None else None,
+                 id(q.r) if q.r is not None else None, None, None, None, None)
+            if k in merged:
+                merged[k][0][0][3] += p.c * q.c * kc * va * vb
+            else:
+                merged[k] = ([[_lib.DERIV_OF[kind], ri, ci, p.c * q.c * kc * va * vb, param, p.r, q.r]], (None, None), (None, None))
+                order.append(k)
 
 
 def _point_dim(p):

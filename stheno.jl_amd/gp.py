@@ -289,6 +289,57 @@ def quadrature_convolve(f, num_points=15):
     return stencil(f, t, w)
 
 
+# ---- derivative processes -------------------------------------------------------------------------------------------
+def derivative(f, dim=0):
+    """g = derivative(f, dim): the process g(x) = d f(x) / d x[dim], exactly -- the covariances of f and g are kappa' and
+    kappa'' of f's kernel times coordinate differences, one closed-form evaluation per entry (include/sthenomi.h: the
+    SGP_DERIV kinds), where the reference's examples/differentiation/script.jl takes a finite difference.  `dim` counts
+    the coordinates of the inputs g is evaluated at (0 for scalar inputs).
+
+    Below g, f may carry sums, scalar scales, `+ constant`, Shift, Stretch and Select warps (a direction that is no longer
+    axis-aligned in the kernel's coordinates expands into one term per coordinate; a coordinate a Select drops removes
+    the term), and kernels that are SE, Matern-3/2 or Matern-5/2, sums and scalings of these, under ScaleTransform /
+    ARDTransform / LinearTransform / SelectTransform / with_lengthscale.  Everything else raises NotImplementedError that
+    names the derivative: a function-valued scale, Periodic, a second derivative on one side, patch_convolve or stencil
+    above or below, a nested GPPP, products of kernels and every other kernel, and a callable prior mean (a constant mean
+    differentiates to 0)."""
+    if not isinstance(dim, (int, np.integer)) or dim < 0:
+        raise ValueError("derivative: dim must be a non-negative integer")
+    return DerivedGP(("deriv", f, int(dim)), f.gpc)
+
+
+def _deriv_mean(f, x):
+    """mean(derivative(f), x): 0 where every mean below the node is a constant; a callable one is refused"""
+    from .gppp import GPPP
+    if isinstance(f, GPPP):
+        raise NotImplementedError("derivative of a nested GPPP is not supported")
+    if isinstance(f, AtomicGP):
+        if not isinstance(f.gp, GP):
+            raise NotImplementedError("derivative of a nested GPPP is not supported")
+        m = f.gp.mean_spec
+        if m is not None and not _is_real(m):
+            raise NotImplementedError("derivative: a callable prior mean below the node cannot be differentiated (a constant "
+                                      "mean differentiates to 0)")
+        return np.zeros(len(x))
+    op = f.args[0]
+    if op == "+":
+        return _deriv_mean(f.args[1], x) + _deriv_mean(f.args[2], x)
+    if op == "+known":
+        if not _is_real(f.args[1]):
+            raise NotImplementedError("derivative: a known function added below the node cannot be differentiated (a "
+                                      "constant differentiates to 0)")
+        return _deriv_mean(f.args[2], x)
+    if op == "*":
+        if not _is_real(f.args[1]):
+            raise NotImplementedError("derivative: a function-valued scale below the node is not supported")
+        return _deriv_mean(f.args[2], x)
+    if op == "o":
+        if not isinstance(f.args[2], (Stretch, Select, Shift)):
+            raise NotImplementedError("derivative: only Shift, Stretch and Select warps are supported below the node")
+        return _deriv_mean(f.args[1], x)
+    raise NotImplementedError(f"derivative over `{op}` is not supported")
+
+
 # ---- prior mean (host, O(N) per node) ----------------------------------------------------------
 def mean_vector(f, x):
     """mean(f, x) by the reference's recursion (addition.jl:26,73-74; product.jl:25,54;
@@ -329,6 +380,8 @@ def mean_vector(f, x):
         for q in range(len(w)):
             out = out + w[q] * mean_vector(g, warp(Shift(A[:, q] if isinstance(x, ColVecs) else A[0, q]), x))
         return out
+    if op == "deriv":
+        return _deriv_mean(f.args[1], x)
     if op == "cross":
         return np.concatenate([mean_vector(g, b) for g, b in zip(f.args[1], blocks(x))])
     raise ValueError(op)

@@ -121,6 +121,25 @@ def _sincos_r(v, D):
     return r
 
 
+def chain_direction(chain, v):
+    """a direction v (length D) in the raw points' coordinates seen through the chain's Jacobian -- the direction, in the
+    coordinates of apply_chain(chain, X), along which the kernel is differentiated when the process is differentiated along
+    v; None if a step is not linear (periodic, sincos)"""
+    v = np.asarray(v, dtype=np.float64)
+    for kind, p in chain:
+        if kind == "scale":
+            v = p * v
+        elif kind == "linear":
+            v = _linear_A(p, v.shape[0]) @ v
+        elif kind == "ard":
+            v = _ard_v(p, v.shape[0]) * v
+        elif kind == "select":
+            v = v[list(p)]
+        else:
+            return None
+    return v
+
+
 def chain_scale(chain):
     """the scale of a pure-scaling chain (1.0 for the empty chain); None if the chain is not a scaling"""
     if not chain:

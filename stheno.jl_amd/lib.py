@@ -26,6 +26,11 @@ WIENER = 10                        # WienerKernel{i}, param = i in {0, 1, 2, 3};
 PIECEWISE0, PIECEWISE1, PIECEWISE2, PIECEWISE3 = 11, 12, 13, 14   # PiecewisePolynomialKernel{q}: the code carries q, param = j
 PIECEWISE_J_MAX = 64
 NEURALNET, FBM, EXPONENTIATED = 24, 25, 26   # kinds of x'y, x'x and y'y, the same path (21 .. 23 and 27+ are no kinds)
+# the derivative kinds (include/sthenomi.h: 32 + the base kind; deriv.hip): param = DERIV_PARAM_BASE * a + b, a - 1 / b - 1 the
+# differentiated coordinate of the row / column side, 0 = that side is not differentiated; input dimension <= DERIV_MAX_DIM
+DERIV_SE, DERIV_MATERN32, DERIV_MATERN52 = 32, 34, 35
+DERIV_OF = {SE: DERIV_SE, MATERN32: DERIV_MATERN32, MATERN52: DERIV_MATERN52}
+DERIV_MAX_DIM, DERIV_PARAM_BASE = 16, 17
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
 KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain
@@ -573,7 +578,9 @@ class Spec:
         self.has_stencil = any(st != (None, None) for st in self.term_stencils)
         # product chains / the RQ, LINEAR, COSINE and GAMMAEXP kinds (include/sthenomi_kprod.h): a term whose kind carries KIND_TIMES_PREV
         # continues the chain of the term before it
-        self.has_kprod = any((int(t[0]) & KIND_TIMES_PREV) or (int(t[0]) & KIND_MASK) > CONST for t in terms)
+        self.has_deriv = any(int(t[0]) in DERIV_OF.values() for t in terms)     # derivative terms: a class of their own
+        self.has_kprod = any((int(t[0]) & KIND_TIMES_PREV) or
+                             ((int(t[0]) & KIND_MASK) > CONST and int(t[0]) not in DERIV_OF.values()) for t in terms)
         self._bound = None
         self.n_terms = len(terms)
         self._term_ptr = np.asarray(term_ptr, dtype=np.int32)
@@ -650,7 +657,7 @@ class Spec:
     def f32_supported(self):
         """The fp32 device kernels (csrc/f32.hip: assemble_f32) take input dimension <= 16 and, per block pair,
         (number of terms) x (dimension rounded up to a power of two) <= 64; anything else runs on the fp64 path."""
-        if self.has_patch or self.has_stencil or self.has_kprod:
+        if self.has_patch or self.has_stencil or self.has_kprod or self.has_deriv:
             return False                 # patch / stencil / product terms: fp64 only (a Float32 model runs there and is rounded back)
         tp = self._term_ptr
         for p in range(len(tp) - 1):
