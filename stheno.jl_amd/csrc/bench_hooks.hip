@@ -20,19 +20,6 @@ constexpr long NOMASK = -(1L << 40);
 
 using namespace sgp;
 
-#define CHECK_ARG(cond, msg)       \
-  do {                             \
-    if (!(cond)) {                 \
-      sgp::set_error(msg);         \
-      return -1;                   \
-    }                              \
-  } while (0)
-#define CHECK_RC(expr)        \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-
 static double update_flops(long m, long nc, long k) {
   // algorithmic flops of C[lower, m x nc] -= P P': triangle of the square part + rows below
   return (double)k * (double)nc * (double)(nc + 1) + 2.0 * (double)k * (double)(m - nc) * (double)nc;

@@ -2,6 +2,7 @@
 // every numerical result is produced by the HIP kernels in this directory.
 #include "ctx.h"
 #include "driver.h"
+#include "kept.h"
 #include "tilemap.h"
 #include "sz_pattern.h"
 #include "df_tasks.h"
@@ -45,19 +46,6 @@ using namespace sgp;
     CHECK_ARG(!((ctx)->multi && spec_has_deriv(sp)), sgp::DERIV_REFUSAL_MULTI); /* (deriv.hip: likewise) */  \
     CHECK_ARG(!((ctx)->multi && spec_has_kprod(sp)),                                                         \
               "spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context");    \
-  } while (0)
-
-#define CHECK_ARG(cond, msg)       \
-  do {                             \
-    if (!(cond)) {                 \
-      sgp::set_error(msg);         \
-      return -1;                   \
-    }                              \
-  } while (0)
-#define CHECK_RC(expr)        \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
   } while (0)
 
 extern "C" int sgp_abi_version(void) { return SGP_ABI_VERSION; }
@@ -1569,11 +1557,6 @@ extern "C" int sgp_dev_logpdf(sgp_ctx* ctx, const sgp_dspec* ds, double* d_A, co
 // ---------------------------------------------------------------------------------------
 // host-buffer helpers
 // ---------------------------------------------------------------------------------------
-struct SpecGuard {
-  sgp_dspec* ds = nullptr;
-  ~SpecGuard() { dspec_free(ds); }
-};
-
 static int upload_matrix(DevBuf& b, const double* h, long ldh, long nr, long nc) {
   CHECK_RC(b.alloc((size_t)nr * nc));
   if (nr && nc &&
@@ -3053,42 +3036,40 @@ extern "C" int sgp_posterior_create(sgp_ctx* ctx, const sgp_cov_spec* spec, cons
   return with_df_fallback(ctx, [&]() { return sgp_posterior_create_impl(ctx, spec, mean, noise_kind, noise, y, alpha_out, out); });
 }
 
-// shared by dense and sparse prediction: V rows (x* bordered rows, ns_pad x n_pad)
-static int predict_common(sgp_ctx* ctx, const sgp_dspec* cross, const sgp_dspec* prior,
-                          const double* d_means, long Ns, long ns_pad, double* dV, long n_pad,
-                          const double* d_z, long ldz, long N_cols, double* mean_out,
-                          double* var_out, double* cov_out, int64_t ldcov, double var_sign_second,
-                          const double* dV2, hipStream_t s) {
-  DevBuf dmu, dprior, dvar, dcov;
-  if (mean_out) {
-    CHECK_RC(dmu.alloc(Ns));
-    CHECK_RC(launch_gemv_rows(dV, ns_pad, Ns, N_cols, d_z, ldz, d_means, dmu.p, s));
+// What the three predict entry points do past the solved cross rows (kept.h): mean and variance off them, the covariance
+// K** - V V' (+ V2 V2') from the prior spec or the caller's prior_cov (leading dimension ldp), one drain, the copies back
+struct PredictOut {
+  double *mean, *var, *cov;
+  int64_t ldcov;
+};
+static int predict_read(sgp_ctx* ctx, const Kept& k, CrossRows& R, const sgp_dspec* prior, const double* prior_var,
+                        const double* prior_cov, long ldp, const PredictOut& o, hipStream_t s) {
+  const long Ns = R.Ns, ns_pad = R.ns_pad;
+  DevBuf dcov;
+  if (o.mean) CHECK_RC(R.mean(k, s));
+  if (o.var) {
+    CHECK_ARG(prior || prior_var, "predict: prior_ss spec required for var");
+    CHECK_RC(R.variance(ctx, k, prior, prior_var, s));
   }
-  if (var_out) {
-    CHECK_ARG(prior != nullptr, "predict: prior_ss spec required for var");
-    CHECK_RC(dprior.alloc(Ns));
-    CHECK_RC(dvar.alloc(Ns));
-    CHECK_RC(diag_of_spec(ctx, prior, dprior.p, s));
-    CHECK_RC(launch_colsumsq_sub(dV, ns_pad, Ns, N_cols, dprior.p, dvar.p, -1.0, s));
-    if (dV2) CHECK_RC(launch_colsumsq_sub(dV2, ns_pad, Ns, N_cols, dvar.p, dvar.p, var_sign_second, s));
-  }
-  if (cov_out) {
-    CHECK_ARG(prior != nullptr, "predict: prior_ss spec required for cov");
+  if (o.cov) {
+    CHECK_ARG(prior || prior_cov, "predict: prior_ss spec required for cov");
     CHECK_RC(dcov.alloc((size_t)ns_pad * ns_pad));
     SGP_HIP(hipMemsetAsync(dcov.p, 0, sizeof(double) * ns_pad * ns_pad, s));
-    CHECK_RC(assemble(prior, dcov.p, ns_pad, 0, ns_pad / TILE, 0, ns_pad / TILE, 0, -1, 0.0, nullptr, s));
-    CHECK_RC(launch_gemm_nt(dV, ns_pad, dV, ns_pad, dcov.p, ns_pad, ns_pad, ns_pad, n_pad, -1.0, 1.0,
-                            NOMASK, 0, 0, s));
-    if (dV2)
-      CHECK_RC(launch_gemm_nt(dV2, ns_pad, dV2, ns_pad, dcov.p, ns_pad, ns_pad, ns_pad, n_pad,
-                              var_sign_second, 1.0, NOMASK, 0, 0, s));
+    if (prior)
+      CHECK_RC(assemble(prior, dcov.p, ns_pad, 0, ns_pad / TILE, 0, ns_pad / TILE, 0, -1, 0.0, nullptr, s));
+    else
+      SGP_HIP(hipMemcpy2DAsync(dcov.p, sizeof(double) * ns_pad, prior_cov, sizeof(double) * ldp, sizeof(double) * Ns, (size_t)Ns,
+                               hipMemcpyHostToDevice, s));
+    CHECK_RC(launch_gemm_nt(R.V.p, ns_pad, R.V.p, ns_pad, dcov.p, ns_pad, ns_pad, ns_pad, k.n_pad, -1.0, 1.0, NOMASK, 0, 0, s));
+    if (k.L2)
+      CHECK_RC(launch_gemm_nt(R.V2.p, ns_pad, R.V2.p, ns_pad, dcov.p, ns_pad, ns_pad, ns_pad, k.n_pad, +1.0, 1.0, NOMASK, 0, 0, s));
   }
   SGP_HIP(hipStreamSynchronize(s));
-  if (mean_out) SGP_HIP(hipMemcpy(mean_out, dmu.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
-  if (var_out) SGP_HIP(hipMemcpy(var_out, dvar.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
-  if (cov_out)
-    SGP_HIP(hipMemcpy2D(cov_out, sizeof(double) * ldcov, dcov.p, sizeof(double) * ns_pad,
-                        sizeof(double) * Ns, (size_t)Ns, hipMemcpyDeviceToHost));
+  if (o.mean) SGP_HIP(hipMemcpy(o.mean, R.mu.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
+  if (o.var) SGP_HIP(hipMemcpy(o.var, R.var.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
+  if (o.cov)
+    SGP_HIP(hipMemcpy2D(o.cov, sizeof(double) * o.ldcov, dcov.p, sizeof(double) * ns_pad, sizeof(double) * Ns, (size_t)Ns,
+                        hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -3096,10 +3077,8 @@ extern "C" int sgp_posterior_predict(sgp_post* post, const sgp_cov_spec* cross,
                                      const sgp_cov_spec* prior_ss, const double* mean_s,
                                      double* mean_out, double* var_out, double* cov_out,
                                      int64_t ldcov) {
-  CHECK_ARG(post && cross, "sgp_posterior_predict: NULL argument");
+  CHECK_RC(kept_door(post, cross, "sgp_posterior_predict"));
   sgp_ctx* ctx = post->ctx;
-  CHECK_ARG(ctx_is_live(ctx, post->ctx_serial),
-            "sgp_posterior_predict: the context this posterior was created on has been destroyed");
   CtxScope scope(ctx);
   if (post->mp) return sgp_multi_posterior_predict(post->mp, cross, prior_ss, mean_s, mean_out, var_out, cov_out, ldcov);
   SpecGuard gc, gp;
@@ -3110,17 +3089,10 @@ extern "C" int sgp_posterior_predict(sgp_post* post, const sgp_cov_spec* cross,
   CHECK_ARG(!gp.ds || gp.ds->N == Ns, "sgp_posterior_predict: prior_ss size != number of x*");
   CHECK_ARG(!cov_out || ldcov >= Ns, "sgp_posterior_predict: ldcov < Ns");
   if (Ns == 0) return 0;
-  long ns_pad = rup(Ns, TILE), n_pad = post->n_pad;
-  hipStream_t s = ctx->stream;
-  DevBuf dV, dms;
-  CHECK_RC(dV.alloc((size_t)ns_pad * n_pad));
-  if (mean_s) CHECK_RC(dms.upload(mean_s, Ns));
-  SGP_HIP(hipMemsetAsync(dV.p, 0, sizeof(double) * ns_pad * n_pad, s));
-  CHECK_RC(assemble(gc.ds, dV.p, ns_pad, 0, ns_pad / TILE, 0, n_pad / TILE, 0, -1, 0.0, nullptr, s));
-  CHECK_RC(row_trsm(ctx, dV.p, ns_pad, ns_pad, post->dA, post->ld, post->d_wall, n_pad, s));
-  return predict_common(ctx, gc.ds, gp.ds, mean_s ? dms.p : nullptr, Ns, ns_pad, dV.p, n_pad,
-                        post->dA + n_pad, post->ld, post->N, mean_out, var_out, cov_out, ldcov,
-                        0.0, nullptr, s);
+  const Kept k = PostRef(post).kept();
+  CrossRows R;
+  CHECK_RC(R.solve(ctx, k, CrossSource{gc.ds, nullptr, 0, Ns, mean_s}, rup(Ns, TILE), ctx->stream));
+  return predict_read(ctx, k, R, gp.ds, nullptr, nullptr, 0, PredictOut{mean_out, var_out, cov_out, ldcov}, ctx->stream);
 }
 
 // Predictions against a kept factor with the cross-covariance GIVEN as a matrix (round 5): what conditioning on top of a process
@@ -3133,49 +3105,18 @@ extern "C" int sgp_posterior_predict_explicit(sgp_post* post, const double* cros
                                               const double* prior_var, const double* prior_cov, int64_t ldp,
                                               const double* mean_s, double* mean_out, double* var_out, double* cov_out,
                                               int64_t ldcov) {
-  CHECK_ARG(post && cross, "sgp_posterior_predict_explicit: NULL argument");
+  CHECK_RC(kept_door(post, cross, "sgp_posterior_predict_explicit", "not available on a multi-GPU context's sharded factor", false));
   sgp_ctx* ctx = post->ctx;
-  CHECK_ARG(ctx_is_live(ctx, post->ctx_serial),
-            "sgp_posterior_predict_explicit: the context this posterior was created on has been destroyed");
-  CHECK_ARG(!post->mp, "sgp_posterior_predict_explicit: not available on a multi-GPU context's sharded factor");
-  const long Ns = ns, N = post->N;
+  const long Ns = ns;
   CHECK_ARG(Ns >= 0 && ldc >= std::max<long>(Ns, 1), "sgp_posterior_predict_explicit: bad sizes");
   CHECK_ARG(!var_out || prior_var, "sgp_posterior_predict_explicit: prior_var required for var");
   CHECK_ARG(!cov_out || (prior_cov && ldp >= Ns && ldcov >= Ns), "sgp_posterior_predict_explicit: prior_cov required for cov");
   if (Ns == 0) return 0;
   CtxScope scope(ctx);
-  const long ns_pad = rup(Ns, TILE), n_pad = post->n_pad;
-  hipStream_t s = ctx->stream;
-  DevBuf dV, dms, dmu, dprior, dvar, dcov;
-  CHECK_RC(dV.alloc((size_t)ns_pad * n_pad));
-  if (mean_s) CHECK_RC(dms.upload(mean_s, Ns));
-  SGP_HIP(hipMemsetAsync(dV.p, 0, sizeof(double) * ns_pad * n_pad, s));
-  SGP_HIP(hipMemcpy2DAsync(dV.p, sizeof(double) * ns_pad, cross, sizeof(double) * ldc, sizeof(double) * Ns, (size_t)N,
-                           hipMemcpyHostToDevice, s));
-  CHECK_RC(row_trsm(ctx, dV.p, ns_pad, ns_pad, post->dA, post->ld, post->d_wall, n_pad, s));
-  if (mean_out) {
-    CHECK_RC(dmu.alloc(Ns));
-    CHECK_RC(launch_gemv_rows(dV.p, ns_pad, Ns, N, post->dA + n_pad, post->ld, mean_s ? dms.p : nullptr, dmu.p, s));
-  }
-  if (var_out) {
-    CHECK_RC(dprior.upload(prior_var, Ns));
-    CHECK_RC(dvar.alloc(Ns));
-    CHECK_RC(launch_colsumsq_sub(dV.p, ns_pad, Ns, N, dprior.p, dvar.p, -1.0, s));
-  }
-  if (cov_out) {
-    CHECK_RC(dcov.alloc((size_t)ns_pad * ns_pad));
-    SGP_HIP(hipMemsetAsync(dcov.p, 0, sizeof(double) * ns_pad * ns_pad, s));
-    SGP_HIP(hipMemcpy2DAsync(dcov.p, sizeof(double) * ns_pad, prior_cov, sizeof(double) * ldp, sizeof(double) * Ns, (size_t)Ns,
-                             hipMemcpyHostToDevice, s));
-    CHECK_RC(launch_gemm_nt(dV.p, ns_pad, dV.p, ns_pad, dcov.p, ns_pad, ns_pad, ns_pad, n_pad, -1.0, 1.0, NOMASK, 0, 0, s));
-  }
-  SGP_HIP(hipStreamSynchronize(s));
-  if (mean_out) SGP_HIP(hipMemcpy(mean_out, dmu.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
-  if (var_out) SGP_HIP(hipMemcpy(var_out, dvar.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
-  if (cov_out)
-    SGP_HIP(hipMemcpy2D(cov_out, sizeof(double) * ldcov, dcov.p, sizeof(double) * ns_pad, sizeof(double) * Ns, (size_t)Ns,
-                        hipMemcpyDeviceToHost));
-  return 0;
+  const Kept k = PostRef(post).kept();
+  CrossRows R;
+  CHECK_RC(R.solve(ctx, k, CrossSource{nullptr, cross, (long)ldc, Ns, mean_s}, rup(Ns, TILE), ctx->stream));
+  return predict_read(ctx, k, R, nullptr, prior_var, prior_cov, ldp, PredictOut{mean_out, var_out, cov_out, ldcov}, ctx->stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -4318,14 +4259,14 @@ extern "C" int sgp_sparse_posterior_create(sgp_ctx* ctx, const sgp_cov_spec* zz,
   return with_df_fallback(ctx, [&]() { return sgp_sparse_posterior_create_impl(ctx, zz, xz, mean_x, noise_kind, noise_x, z_noise_kind, z_noise, y, out); });
 }
 
+// B' = K(x*, z) Lz^-T, C' = B' Le^-T (always solved);  mean* = m* + K*z alpha, alpha = Lz^-T Le^-T (Le^-1 A delta)
+// =>  mean* = m* + C' (Le^-1 A delta);  var* = k** - |B|^2 + |C|^2
 extern "C" int sgp_sparse_posterior_predict(sgp_sparse_post* post, const sgp_cov_spec* cross,
                                             const sgp_cov_spec* prior_ss, const double* mean_s,
                                             double* mean_out, double* var_out, double* cov_out,
                                             int64_t ldcov) {
-  CHECK_ARG(post && cross, "sgp_sparse_posterior_predict: NULL argument");
+  CHECK_RC(kept_door(post, cross, "sgp_sparse_posterior_predict"));
   sgp_ctx* ctx = post->ctx;
-  CHECK_ARG(ctx_is_live(ctx, post->ctx_serial),
-            "sgp_sparse_posterior_predict: the context this posterior was created on has been destroyed");
   CtxScope scope(ctx);
   SpecGuard gc, gp;
   CHECK_RC(dspec_create(ctx, cross, &gc.ds));
@@ -4335,28 +4276,10 @@ extern "C" int sgp_sparse_posterior_predict(sgp_sparse_post* post, const sgp_cov
   CHECK_ARG(!gp.ds || gp.ds->N == Ns, "sparse predict: prior_ss size != number of x*");
   CHECK_ARG(!cov_out || ldcov >= Ns, "sparse predict: ldcov < Ns");
   if (Ns == 0) return 0;
-  long ns_pad = rup(Ns, TILE), m_pad = post->m_pad;
-  hipStream_t s = ctx->stream;
-  DevBuf dB, dB2, dms;
-  CHECK_RC(dB.alloc((size_t)ns_pad * m_pad));
-  CHECK_RC(dB2.alloc((size_t)ns_pad * m_pad));
-  if (mean_s) CHECK_RC(dms.upload(mean_s, Ns));
-  SGP_HIP(hipMemsetAsync(dB.p, 0, sizeof(double) * ns_pad * m_pad, s));
-  CHECK_RC(assemble(gc.ds, dB.p, ns_pad, 0, ns_pad / TILE, 0, m_pad / TILE, 0, -1, 0.0, nullptr, s));
-  // B' = K(x*, z) Lz^-T ; then C' = B' Le^-T
-  CHECK_RC(row_trsm(ctx, dB.p, ns_pad, ns_pad, post->dLz, m_pad, post->d_wz, m_pad, s));
-  SGP_HIP(hipMemcpyAsync(dB2.p, dB.p, sizeof(double) * ns_pad * m_pad, hipMemcpyDeviceToDevice, s));
-  CHECK_RC(row_trsm(ctx, dB2.p, ns_pad, ns_pad, post->dG, post->ldg, post->d_wg, m_pad, s));
-  // mean* = m* + K*z alpha, alpha = Lz^-T Le^-T (Le^-1 A delta)  =>  mean* = m* + C' (Le^-1 A delta)
-  // var*  = k** - |B|^2 + |C|^2
-  if (mean_out)
-    CHECK_RC(predict_common(ctx, gc.ds, gp.ds, mean_s ? dms.p : nullptr, Ns, ns_pad, dB2.p, m_pad,
-                            post->dG + m_pad, post->ldg, post->M, mean_out, nullptr, nullptr, 0,
-                            0.0, nullptr, s));
-  if (var_out || cov_out)
-    CHECK_RC(predict_common(ctx, gc.ds, gp.ds, nullptr, Ns, ns_pad, dB.p, m_pad, post->dG + m_pad,
-                            post->ldg, post->M, nullptr, var_out, cov_out, ldcov, +1.0, dB2.p, s));
-  return 0;
+  const Kept k = PostRef(post).kept();
+  CrossRows R;
+  CHECK_RC(R.solve(ctx, k, CrossSource{gc.ds, nullptr, 0, Ns, mean_s}, rup(Ns, TILE), ctx->stream));
+  return predict_read(ctx, k, R, gp.ds, nullptr, nullptr, 0, PredictOut{mean_out, var_out, cov_out, ldcov}, ctx->stream);
 }
 
 // ---------------------------------------------------------------------------------------

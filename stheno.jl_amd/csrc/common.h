@@ -246,6 +246,28 @@ void set_error(const std::string& s);
     }                                                                                     \
   } while (0)
 
+// the host-side early returns of every unit: a refused argument (-1, error text set) and a failed step (its code)
+#define CHECK_ARG(cond, msg)       \
+  do {                             \
+    if (!(cond)) {                 \
+      sgp::set_error(msg);         \
+      return -1;                   \
+    }                              \
+  } while (0)
+#define CHECK_RC(expr)        \
+  do {                        \
+    int _rc = (expr);         \
+    if (_rc != 0) return _rc; \
+  } while (0)
+// a refusal that names the entry point it came through
+#define REFUSE_UNLESS(cond, who, msg)                     \
+  do {                                                    \
+    if (!(cond)) {                                        \
+      sgp::set_error(std::string(who) + ": " + (msg));    \
+      return -1;                                          \
+    }                                                     \
+  } while (0)
+
 // Raise a kernel's dynamic-LDS limit once per device (function attributes are per device; a process
 // may hold contexts on several GPUs).
 #define SGP_LDS_ATTR_ONCE(func, bytes)                                                              \

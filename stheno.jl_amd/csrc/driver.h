@@ -83,6 +83,13 @@ int drv_conv_geom(sgp_ctx* ctx, int h, int w, int ph, int pw, int32_t* id_out);
 // share the table of sgp_conv_geom; a bitwise-equal stencil registered before keeps its id
 int drv_stencil_register(sgp_ctx* ctx, int dim, int npoints, const double* offsets, const double* weights, int32_t* id_out);
 void drv_dspec_free(sgp_dspec* ds);
+// a device spec that lives as long as the call that created it
+struct SpecGuard {
+  sgp_dspec* ds = nullptr;
+  ~SpecGuard() {
+    if (ds) drv_dspec_free(ds);
+  }
+};
 long drv_invd_stride();
 // structural zeros (common.h; capi.hip: sz_pattern / sz_upload): rank 0's context computes the tile pattern of the factor
 // (host), every rank uploads it; *words = 0 / *d_nz = nullptr: dense

@@ -18,19 +18,6 @@
 
 using namespace sgp;
 
-#define CHECK_ARG(cond, msg)       \
-  do {                             \
-    if (!(cond)) {                 \
-      sgp::set_error(msg);         \
-      return -1;                   \
-    }                              \
-  } while (0)
-#define CHECK_RC(expr)        \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-
 namespace {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -77,13 +64,6 @@ __global__ __launch_bounds__(128) void logdet_blocks_kernel(const double* __rest
   __syncthreads();
   if (threadIdx.x == 0) out[b] = 2.0 * (sh[0] + sh[1]);
 }
-
-struct SpecGuard {
-  sgp_dspec* ds = nullptr;
-  ~SpecGuard() {
-    if (ds) drv_dspec_free(ds);
-  }
-};
 
 constexpr long WB = 4 * TILE;   // column block of the row solve (capi.hip: row_trsm)
 // The deep products of the extension have few C tiles (2 - 4 tile rows for a few to a few hundred new points): one launch

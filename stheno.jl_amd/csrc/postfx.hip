@@ -4,8 +4,7 @@
 // add S* to the covariance itself and hand the sum back as dense noise on a zero-term spec to sgp_logpdf / sgp_rand -- two
 // N*^2 transfers around the factorisation.  Here the same launches run in the same order with the N*^2 buffers left where
 // they are, so the result keeps the bits of that route:
-//   V   <- K(x*, x) L^-T                       (row_trsm against the kept factor; the sparse posterior: B against Lz, C = B Le^-T)
-//   m*  <- mean_s + V z                        (launch_gemv_rows; stays on the device)
+//   V (and C), m*                              the solved cross rows and the mean off them: kept.h, shared with predict
 //   C*  <- K(x*, x*) - V V' (+ C C')           straight into the bordered buffer of sgp_geometry(N*, ncols or 0), lower tiles
 //   C*  += S*                                  ONE add per entry of the tiles the factorisation reads, as the host's C + S*
 //   identity padding, border rows (Y - m*)'    (launch_fill_pad, launch_border_rows: what build_bordered runs)
@@ -13,26 +12,11 @@
 // The product K** - V V' runs on the lower tiles only (mask_off == 0): launch_gemm_nt enumerates fewer tiles of the same
 // kernel, every tile it computes contracts k in the same order as the full product -- the factorisation never reads the others.
 // Every launch is ordered on the context's stream; no kernel here waits on another workgroup.
-#include "ctx.h"
-#include "driver.h"
+#include "kept.h"
 
 #include <string>
 
 using namespace sgp;
-
-#define CHECK_RC(expr)        \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-// a refusal names the entry point it came through
-#define REFUSE_UNLESS(cond, who, msg)                     \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      sgp::set_error(std::string(who) + ": " + (msg));    \
-      return -1;                                          \
-    }                                                     \
-  } while (0)
 
 namespace {
 
@@ -57,25 +41,11 @@ int launch_add_noise_sd(double* K, long ld, long N, int noise_kind, double sigma
   return 0;
 }
 
-struct SpecGuard {
-  sgp_dspec* ds = nullptr;
-  ~SpecGuard() {
-    if (ds) drv_dspec_free(ds);
-  }
-};
-
 int upload_cols(DevBuf& b, const double* h, long ldh, long nr, long nc) {
   CHECK_RC(b.alloc((size_t)nr * nc));
   SGP_HIP(hipMemcpy2D(b.p, sizeof(double) * nr, h, sizeof(double) * ldh, sizeof(double) * nr, (size_t)nc, hipMemcpyHostToDevice));
   return 0;
 }
-
-// the kept factor(s) a posterior answers from: V = K(x*, .) L1^-T over n_pad columns of which n are points; the sparse
-// posterior solves V once more against L2 (C = B Le^-T), takes its mean from C and adds C C' back; z: the solved border row
-struct Kept {
-  const double *L1 = nullptr, *w1 = nullptr, *L2 = nullptr, *w2 = nullptr, *z = nullptr;
-  long ld1 = 0, ld2 = 0, ldz = 0, n = 0, n_pad = 0;
-};
 
 struct FxArgs {
   const char* who;
@@ -88,8 +58,9 @@ struct FxArgs {
   bool rand;
 };
 
-int postfx_impl(sgp_ctx* ctx, const Kept& k, const FxArgs& a) {
+int postfx_impl(sgp_ctx* ctx, PostRef post, const FxArgs& a) {
   CtxScope scope(ctx);
+  const Kept k = post.kept();
   SpecGuard gc, gp;
   CHECK_RC(drv_dspec_create(ctx, a.cross, &gc.ds));
   CHECK_RC(drv_dspec_create(ctx, a.prior_ss, &gp.ds));
@@ -106,25 +77,16 @@ int postfx_impl(sgp_ctx* ctx, const Kept& k, const FxArgs& a) {
   REFUSE_UNLESS(n_pad / TILE <= ctx->n_slots, a.who, "too many test points for the logdet slot buffer");
   hipStream_t s = ctx->stream;
 
-  DevBuf dV, dV2, dms, dmu, dA, dX, dnoise;
-  CHECK_RC(dV.alloc((size_t)n_pad * k.n_pad));
-  if (a.mean_s) CHECK_RC(dms.upload(a.mean_s, Ns));
+  DevBuf dA, dX, dnoise;
   if (a.noise_kind == SGP_NOISE_DIAG) CHECK_RC(dnoise.upload(a.noise, Ns));
   if (a.noise_kind == SGP_NOISE_DENSE) CHECK_RC(dnoise.upload(a.noise, (size_t)Ns * Ns));
   const double sigma2 = a.noise_kind == SGP_NOISE_SCALAR ? a.noise[0] : 0.0;
   CHECK_RC(upload_cols(dX, a.X, a.ldx, Ns, cols));
 
-  // ---- V (and C), the posterior mean: the launches of sgp_posterior_predict / sgp_sparse_posterior_predict
-  SGP_HIP(hipMemsetAsync(dV.p, 0, sizeof(double) * n_pad * k.n_pad, s));
-  CHECK_RC(drv_assemble(gc.ds, dV.p, n_pad, 0, n_pad / TILE, 0, k.n_pad / TILE, 0, -1, 0.0, nullptr, s));
-  CHECK_RC(drv_row_trsm(ctx, dV.p, n_pad, n_pad, k.L1, k.ld1, k.w1, k.n_pad, s));
-  if (k.L2) {
-    CHECK_RC(dV2.alloc((size_t)n_pad * k.n_pad));
-    SGP_HIP(hipMemcpyAsync(dV2.p, dV.p, sizeof(double) * n_pad * k.n_pad, hipMemcpyDeviceToDevice, s));
-    CHECK_RC(drv_row_trsm(ctx, dV2.p, n_pad, n_pad, k.L2, k.ld2, k.w2, k.n_pad, s));
-  }
-  CHECK_RC(dmu.alloc(Ns));
-  CHECK_RC(launch_gemv_rows(k.L2 ? dV2.p : dV.p, n_pad, Ns, k.n, k.z, k.ldz, a.mean_s ? dms.p : nullptr, dmu.p, s));
+  // ---- V (and C), the posterior mean
+  CrossRows R;
+  CHECK_RC(R.solve(ctx, k, CrossSource{gc.ds, nullptr, 0, Ns, a.mean_s}, n_pad, s));
+  CHECK_RC(R.mean(k, s));
 
   // ---- C* + S* in the bordered buffer
   CHECK_RC(dA.alloc((size_t)m_tot * n_pad));
@@ -132,14 +94,14 @@ int postfx_impl(sgp_ctx* ctx, const Kept& k, const FxArgs& a) {
   SGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
   CHECK_RC(drv_assemble(gp.ds, dA.p, m_tot, 0, n_pad / TILE, 0, n_pad / TILE, 0, -1, 0.0, nullptr, s));
   constexpr long LOWER = 0;   // launch_gemm_nt's mask_off: the tiles with tile row >= tile column
-  CHECK_RC(launch_gemm_nt(dV.p, n_pad, dV.p, n_pad, dA.p, m_tot, n_pad, n_pad, k.n_pad, -1.0, 1.0, LOWER, 0, 0, s));
-  if (k.L2) CHECK_RC(launch_gemm_nt(dV2.p, n_pad, dV2.p, n_pad, dA.p, m_tot, n_pad, n_pad, k.n_pad, 1.0, 1.0, LOWER, 0, 0, s));
+  CHECK_RC(launch_gemm_nt(R.V.p, n_pad, R.V.p, n_pad, dA.p, m_tot, n_pad, n_pad, k.n_pad, -1.0, 1.0, LOWER, 0, 0, s));
+  if (k.L2) CHECK_RC(launch_gemm_nt(R.V2.p, n_pad, R.V2.p, n_pad, dA.p, m_tot, n_pad, n_pad, k.n_pad, 1.0, 1.0, LOWER, 0, 0, s));
   if (a.noise_kind == SGP_NOISE_DENSE)
     CHECK_RC(launch_add_dense(dA.p, m_tot, dnoise.p, Ns, Ns, 1, s));
   else
     CHECK_RC(launch_add_noise_sd(dA.p, m_tot, Ns, a.noise_kind, sigma2, dnoise.p, s));
   CHECK_RC(launch_fill_pad(dA.p, m_tot, Ns, n_pad, 0, n_pad, m_tot, 0, s));
-  if (!a.rand) CHECK_RC(launch_border_rows(dA.p, m_tot, n_pad, Ns, 0, n_pad, dX.p, Ns, cols, dmu.p, s));
+  if (!a.rand) CHECK_RC(launch_border_rows(dA.p, m_tot, n_pad, Ns, 0, n_pad, dX.p, Ns, cols, R.mu.p, s));
   CHECK_RC(drv_chol_sub(ctx, dA.p, m_tot, n_pad, m_tot, nullptr, s));
 
   DevBuf dZt, dOut;
@@ -150,7 +112,7 @@ int postfx_impl(sgp_ctx* ctx, const Kept& k, const FxArgs& a) {
     CHECK_RC(dOut.alloc((size_t)n_pad * s_pad));
     SGP_HIP(hipMemsetAsync(dZt.p, 0, sizeof(double) * s_pad * n_pad, s));
     CHECK_RC(launch_transpose_add(dX.p, Ns, Ns, cols, dZt.p, s_pad, nullptr, s));
-    CHECK_RC(drv_fill_mean_cols(dOut.p, n_pad, n_pad, s_pad, Ns, dmu.p, s));
+    CHECK_RC(drv_fill_mean_cols(dOut.p, n_pad, n_pad, s_pad, Ns, R.mu.p, s));
     CHECK_RC(launch_gemm_nt_lz(dA.p, m_tot, dZt.p, s_pad, dOut.p, n_pad, n_pad, s_pad, 1.0, s));
   } else {        // the tail of sgp_logpdf
     CHECK_RC(launch_rowsumsq(dA.p + n_pad, m_tot, Ns, cols, ctx->d_scal + 16, 0, s));
@@ -171,48 +133,22 @@ int postfx_impl(sgp_ctx* ctx, const Kept& k, const FxArgs& a) {
   return 0;
 }
 
-// what every entry point checks before it looks at the posterior's context
-int check_args(const FxArgs& a, const void* post) {
+// what every entry point checks of its arguments, then the door (kept.h) for the posterior's context
+int enter(PostRef post, const FxArgs& a, const char* multi_refusal) {
   REFUSE_UNLESS(post && a.cross && a.prior_ss && a.noise && a.X && a.out, a.who, "NULL argument");
   REFUSE_UNLESS(a.noise_kind >= SGP_NOISE_SCALAR && a.noise_kind <= SGP_NOISE_DENSE, a.who, "bad noise kind");
   REFUSE_UNLESS(a.cols >= 1, a.who, a.rand ? "S must be at least 1" : "ncols must be at least 1");
-  return 0;
+  CHECK_RC(kept_door(post, true, a.who, multi_refusal));
+  sgp_ctx* ctx = post.ctx();
+  return drv_with_df_fallback(ctx, [&]() { return postfx_impl(ctx, post, a); });
 }
 
 int dense_entry(sgp_post* post, const FxArgs& a) {
-  CHECK_RC(check_args(a, post));
-  sgp_ctx* ctx = post->ctx;
-  REFUSE_UNLESS(drv_ctx_is_live(ctx, post->ctx_serial), a.who, "the context this posterior was created on has been destroyed");
-  REFUSE_UNLESS(!post->mp && !ctx->multi, a.who,
-                "a posterior of a multi-GPU context (sharded factor) is not sampled or scored on the device");
-  Kept k;
-  k.L1 = post->dA;
-  k.ld1 = post->ld;
-  k.w1 = post->d_wall;
-  k.z = post->dA + post->n_pad;
-  k.ldz = post->ld;
-  k.n = post->N;
-  k.n_pad = post->n_pad;
-  return drv_with_df_fallback(ctx, [&]() { return postfx_impl(ctx, k, a); });
+  return enter(post, a, "a posterior of a multi-GPU context (sharded factor) is not sampled or scored on the device");
 }
 
 int sparse_entry(sgp_sparse_post* post, const FxArgs& a) {
-  CHECK_RC(check_args(a, post));
-  sgp_ctx* ctx = post->ctx;
-  REFUSE_UNLESS(drv_ctx_is_live(ctx, post->ctx_serial), a.who, "the context this posterior was created on has been destroyed");
-  REFUSE_UNLESS(!ctx->multi, a.who, "a posterior of a multi-GPU context is not sampled or scored on the device");
-  Kept k;
-  k.L1 = post->dLz;
-  k.ld1 = post->m_pad;
-  k.w1 = post->d_wz;
-  k.L2 = post->dG;
-  k.ld2 = post->ldg;
-  k.w2 = post->d_wg;
-  k.z = post->dG + post->m_pad;
-  k.ldz = post->ldg;
-  k.n = post->M;
-  k.n_pad = post->m_pad;
-  return drv_with_df_fallback(ctx, [&]() { return postfx_impl(ctx, k, a); });
+  return enter(post, a, "a posterior of a multi-GPU context is not sampled or scored on the device");
 }
 
 }  // namespace

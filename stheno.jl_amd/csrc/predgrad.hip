@@ -1,8 +1,8 @@
 // Posterior mean and variance at test points with their gradients with respect to those points
 // (include/sthenomi_predgrad.h), against the kept factor.
 //
-//   V     <- K(x*, x) L^-T                 the launches of sgp_posterior_predict (the sparse posterior: B' against Lz, C' = B' Le^-T)
-//   mean, var                              launch_gemv_rows / diag_of_spec + launch_colsumsq_sub, as predict: the same bits
+//   V (and C'), mean, var                  the solved cross rows and what is read off them: kept.h, shared with predict --
+//                                          the same bits (the sparse posterior: V = B' against Lz, C' = B' Le^-T)
 //   alpha <- L^-T z                        the single-vector back substitution (sparse: against Le, then Lz)
 //   B     <- V L^-1                        row_backsolve below (sparse: B = (B' - C' Le^-1) Lz^-1)
 //   d mean_i / d x*_i = sum_j alpha_j coef rs_i cs_j kappa'(d2_ij) 2 (xr_i - xc_j),  d var_i / d x*_i: alpha_j -> -2 B_ij
@@ -10,8 +10,7 @@
 //   the k**_ii part of d var_i / d x*_i    launch_diag_grad_inputs with w = 1
 // Nothing is factored; every launch is ordered on the context's stream; no kernel waits on another workgroup and none uses
 // atomics: every output element has one writer and sums its addends in an order the shapes alone decide.
-#include "ctx.h"
-#include "driver.h"
+#include "kept.h"
 #include "kern_grad.h"
 #include "potrf_diag.h"
 #include "../../include/sthenomi_predgrad.h"
@@ -21,20 +20,6 @@
 #include <vector>
 
 using namespace sgp;
-
-#define CHECK_RC(expr)        \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-// a refusal names the entry point it came through
-#define REFUSE_UNLESS(cond, who, msg)                     \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      sgp::set_error(std::string(who) + ": " + (msg));    \
-      return -1;                                          \
-    }                                                     \
-  } while (0)
 
 namespace {
 
@@ -400,19 +385,6 @@ __global__ void fill_ones_kernel(double* p, long n) {
   if (i < n) p[i] = 1.0;
 }
 
-struct SpecGuard {
-  sgp_dspec* ds = nullptr;
-  ~SpecGuard() {
-    if (ds) drv_dspec_free(ds);
-  }
-};
-
-// the kept factor(s) a posterior answers from (as postfx.hip: Kept)
-struct Kept {
-  const double *L1 = nullptr, *w1 = nullptr, *L2 = nullptr, *w2 = nullptr, *z = nullptr;
-  long ld1 = 0, ld2 = 0, ldz = 0, n = 0, n_pad = 0;
-};
-
 struct PgArgs {
   const char* who;
   const sgp_cov_spec *cross, *prior_ss;
@@ -438,8 +410,9 @@ int fetch_inputs(const sgp_cov_spec* sp, const std::vector<DevBuf>& d, const std
   return 0;
 }
 
-int predgrad_impl(sgp_ctx* ctx, const Kept& k, const PgArgs& a) {
+int predgrad_impl(sgp_ctx* ctx, PostRef post, const PgArgs& a) {
   CtxScope scope(ctx);
+  const Kept k = post.kept();
   SpecGuard gc, gp;
   CHECK_RC(drv_dspec_create(ctx, a.cross, &gc.ds));
   if (a.prior_ss) CHECK_RC(drv_dspec_create(ctx, a.prior_ss, &gp.ds));
@@ -454,29 +427,11 @@ int predgrad_impl(sgp_ctx* ctx, const Kept& k, const PgArgs& a) {
   const long ns_pad = (Ns + TILE - 1) / TILE * TILE, n_pad = k.n_pad;
   hipStream_t s = ctx->stream;
 
-  // ---- V (and C'), mean and variance: the launches of sgp_posterior_predict / sgp_sparse_posterior_predict
-  DevBuf dV, dV2, dms, dmu, dprior, dvar;
-  CHECK_RC(dV.alloc((size_t)ns_pad * n_pad));
-  if (a.mean_s) CHECK_RC(dms.upload(a.mean_s, Ns));
-  SGP_HIP(hipMemsetAsync(dV.p, 0, sizeof(double) * ns_pad * n_pad, s));
-  CHECK_RC(drv_assemble(dc, dV.p, ns_pad, 0, ns_pad / TILE, 0, n_pad / TILE, 0, -1, 0.0, nullptr, s));
-  CHECK_RC(drv_row_trsm(ctx, dV.p, ns_pad, ns_pad, k.L1, k.ld1, k.w1, n_pad, s));
-  if (k.L2) {
-    CHECK_RC(dV2.alloc((size_t)ns_pad * n_pad));
-    SGP_HIP(hipMemcpyAsync(dV2.p, dV.p, sizeof(double) * ns_pad * n_pad, hipMemcpyDeviceToDevice, s));
-    CHECK_RC(drv_row_trsm(ctx, dV2.p, ns_pad, ns_pad, k.L2, k.ld2, k.w2, n_pad, s));
-  }
-  if (a.mean_out) {
-    CHECK_RC(dmu.alloc(Ns));
-    CHECK_RC(launch_gemv_rows(k.L2 ? dV2.p : dV.p, ns_pad, Ns, k.n, k.z, k.ldz, a.mean_s ? dms.p : nullptr, dmu.p, s));
-  }
-  if (a.var_out) {
-    CHECK_RC(dprior.alloc(Ns));
-    CHECK_RC(dvar.alloc(Ns));
-    CHECK_RC(drv_diag_of_spec(ctx, dp, dprior.p, s));
-    CHECK_RC(launch_colsumsq_sub(dV.p, ns_pad, Ns, k.n, dprior.p, dvar.p, -1.0, s));
-    if (k.L2) CHECK_RC(launch_colsumsq_sub(dV2.p, ns_pad, Ns, k.n, dvar.p, dvar.p, +1.0, s));
-  }
+  // ---- V (and C'), mean and variance
+  CrossRows R;
+  CHECK_RC(R.solve(ctx, k, CrossSource{dc, nullptr, 0, Ns, a.mean_s}, ns_pad, s));
+  if (a.mean_out) CHECK_RC(R.mean(k, s));
+  if (a.var_out) CHECK_RC(R.variance(ctx, k, dp, nullptr, s));
 
   // ---- alpha and B
   DevBuf dz, dal, dscr, dpart;
@@ -500,10 +455,10 @@ int predgrad_impl(sgp_ctx* ctx, const Kept& k, const PgArgs& a) {
   if (want_gv) {
     CHECK_RC(dscr.alloc((size_t)std::min<long>(4 * TILE, n_pad) * n_pad));
     if (k.L2) {   // B = (B' - C' Le^-1) Lz^-1
-      CHECK_RC(row_backsolve(dV2.p, ns_pad, ns_pad, k.L2, k.ld2, k.w2, n_pad, dscr.p, s));
-      CHECK_RC(drv_axpy_block(dV.p, ns_pad, dV2.p, ns_pad, ns_pad, n_pad, -1.0, s));
+      CHECK_RC(row_backsolve(R.V2.p, ns_pad, ns_pad, k.L2, k.ld2, k.w2, n_pad, dscr.p, s));
+      CHECK_RC(drv_axpy_block(R.V.p, ns_pad, R.V2.p, ns_pad, ns_pad, n_pad, -1.0, s));
     }
-    CHECK_RC(row_backsolve(dV.p, ns_pad, ns_pad, k.L1, k.ld1, k.w1, n_pad, dscr.p, s));
+    CHECK_RC(row_backsolve(R.V.p, ns_pad, ns_pad, k.L1, k.ld1, k.w1, n_pad, dscr.p, s));
   }
 
   // ---- the contraction, term by term
@@ -534,7 +489,7 @@ int predgrad_impl(sgp_ctx* ctx, const Kept& k, const PgArgs& a) {
         const int p = I * dc->ncb + J;
         for (int t = dc->term_ptr[p]; t < dc->term_ptr[p + 1]; ++t) {
           const int kin = dc->term_row_input[t];
-          CHECK_RC(launch_predgrad(want_gv ? dV.p : nullptr, ns_pad, d_alpha, dc->row_off[I], dc->row_len[I],
+          CHECK_RC(launch_predgrad(want_gv ? R.V.p : nullptr, ns_pad, d_alpha, dc->row_off[I], dc->row_len[I],
                                    dc->col_off[J], dc->col_len[J], dc->h_terms[t], dpart.p, want_gm ? dgm[kin].p : nullptr,
                                    want_gv ? dgv[kin].p : nullptr, s));
         }
@@ -563,16 +518,18 @@ int predgrad_impl(sgp_ctx* ctx, const Kept& k, const PgArgs& a) {
   }
 
   SGP_HIP(hipStreamSynchronize(s));
-  if (a.mean_out) SGP_HIP(hipMemcpy(a.mean_out, dmu.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
-  if (a.var_out) SGP_HIP(hipMemcpy(a.var_out, dvar.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
+  if (a.mean_out) SGP_HIP(hipMemcpy(a.mean_out, R.mu.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
+  if (a.var_out) SGP_HIP(hipMemcpy(a.var_out, R.var.p, sizeof(double) * Ns, hipMemcpyDeviceToHost));
   if (want_gm) CHECK_RC(fetch_inputs(a.cross, dgm, row_read, a.g_mean));
   if (want_gv) CHECK_RC(fetch_inputs(a.cross, dgv, row_read, a.g_var));
   if (want_gp) CHECK_RC(fetch_inputs(a.prior_ss, dgp, prior_all, a.g_prior));
   return 0;
 }
 
-// what every entry point checks before it looks at the posterior's context
-int check_specs(const sgp_ctx* ctx, const PgArgs& a) {
+// the door of every entry point (kept.h), then what it refuses of its own
+int enter(PostRef post, const PgArgs& a, const char* multi_refusal) {
+  CHECK_RC(kept_door(post, a.cross, a.who, multi_refusal));
+  sgp_ctx* ctx = post.ctx();
   for (const sgp_cov_spec* sp : {a.cross, a.prior_ss}) {
     if (!sp) continue;
     REFUSE_UNLESS(!spec_has_deriv(sp), a.who, "gradients through derivative terms are not supported");
@@ -582,7 +539,7 @@ int check_specs(const sgp_ctx* ctx, const PgArgs& a) {
                   "gradients through product chains and the kinds beyond the six plain ones are not supported");
   }
   REFUSE_UNLESS(a.prior_ss || (!a.var_out && !a.g_var && !a.g_prior), a.who, "prior_ss is required for the variance and its gradients");
-  return 0;
+  return predgrad_impl(ctx, post, a);
 }
 
 }  // namespace
@@ -594,21 +551,7 @@ int drv_posterior_predict_grad_x(sgp_post* post, const sgp_cov_spec* cross, cons
                                  double* const* grad_var_inputs, double* const* grad_var_prior_inputs) {
   const PgArgs a{"sgp_posterior_predict_grad_x", cross, prior_ss, mean_s, mean_out, var_out, grad_mean_inputs, grad_var_inputs,
                  grad_var_prior_inputs};
-  REFUSE_UNLESS(post && cross, a.who, "NULL argument");
-  sgp_ctx* ctx = post->ctx;
-  REFUSE_UNLESS(drv_ctx_is_live(ctx, post->ctx_serial), a.who, "the context this posterior was created on has been destroyed");
-  REFUSE_UNLESS(!post->mp && !ctx->multi, a.who,
-                "a posterior of a multi-GPU context (sharded factor) has no prediction gradient on the device");
-  CHECK_RC(check_specs(ctx, a));
-  Kept k;
-  k.L1 = post->dA;
-  k.ld1 = post->ld;
-  k.w1 = post->d_wall;
-  k.z = post->dA + post->n_pad;
-  k.ldz = post->ld;
-  k.n = post->N;
-  k.n_pad = post->n_pad;
-  return predgrad_impl(ctx, k, a);
+  return enter(post, a, "a posterior of a multi-GPU context (sharded factor) has no prediction gradient on the device");
 }
 
 int drv_sparse_posterior_predict_grad_x(sgp_sparse_post* post, const sgp_cov_spec* cross, const sgp_cov_spec* prior_ss,
@@ -617,23 +560,7 @@ int drv_sparse_posterior_predict_grad_x(sgp_sparse_post* post, const sgp_cov_spe
                                         double* const* grad_var_prior_inputs) {
   const PgArgs a{"sgp_sparse_posterior_predict_grad_x", cross, prior_ss, mean_s, mean_out, var_out, grad_mean_inputs,
                  grad_var_inputs, grad_var_prior_inputs};
-  REFUSE_UNLESS(post && cross, a.who, "NULL argument");
-  sgp_ctx* ctx = post->ctx;
-  REFUSE_UNLESS(drv_ctx_is_live(ctx, post->ctx_serial), a.who, "the context this posterior was created on has been destroyed");
-  REFUSE_UNLESS(!ctx->multi, a.who, "a posterior of a multi-GPU context has no prediction gradient on the device");
-  CHECK_RC(check_specs(ctx, a));
-  Kept k;
-  k.L1 = post->dLz;
-  k.ld1 = post->m_pad;
-  k.w1 = post->d_wz;
-  k.L2 = post->dG;
-  k.ld2 = post->ldg;
-  k.w2 = post->d_wg;
-  k.z = post->dG + post->m_pad;
-  k.ldz = post->ldg;
-  k.n = post->M;
-  k.n_pad = post->m_pad;
-  return predgrad_impl(ctx, k, a);
+  return enter(post, a, "a posterior of a multi-GPU context has no prediction gradient on the device");
 }
 
 }  // namespace sgp

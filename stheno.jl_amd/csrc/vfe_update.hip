@@ -21,20 +21,6 @@
 
 using namespace sgp;
 
-#define CHECK_RC(expr)        \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-// a refusal names the entry point it came through
-#define REFUSE_UNLESS(cond, who, msg)                     \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      sgp::set_error(std::string(who) + ": " + (msg));    \
-      return -1;                                          \
-    }                                                     \
-  } while (0)
-
 namespace {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -74,13 +60,6 @@ __global__ __launch_bounds__(256) void vfe_prepare_factor_kernel(const double* _
     *(d2*)(F + off + col * ld) = v;
   }
 }
-
-struct SpecGuard {
-  sgp_dspec* ds = nullptr;
-  ~SpecGuard() {
-    if (ds) drv_dspec_free(ds);
-  }
-};
 
 const char* const WHO = "sgp_sparse_posterior_update";
 

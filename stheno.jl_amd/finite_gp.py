@@ -257,8 +257,7 @@ def mean_and_var_and_gradient(fx):
     ctx = _ctx()
     if getattr(ctx, "is_multi", False):
         raise NotImplementedError("mean_and_var_and_gradient is not supported on a multi-GPU context (the factor is sharded)")
-    cross, _, _ = build_spec(f.prior, fx.x, f.prior, f._train_inputs()[0])
-    pss = _prior_spec(f.prior, fx.x)
+    cross, pss, ms = _cross_side(f, fx.x)
     _refuse_deriv("mean_and_var_and_gradient", cross, pss)
     _refuse_patch_gradient(cross, pss)
     _refuse_product_gradient("mean_and_var_and_gradient", cross, pss)
@@ -270,13 +269,11 @@ def mean_and_var_and_gradient(fx):
         raise NotImplementedError("mean_and_var_and_gradient: a test-side prior mean that is a function of the point is not "
                                   "supported (zero and constant means are)")
     ns = cross.N
-    ms = _f64(mean_vector(f.prior, fx.x))
     mo, vo = np.zeros(ns), np.zeros(ns)
     gm = [np.zeros(np.asarray(a).shape, order="F") for a in cross.inputs]
     gv = [np.zeros(np.asarray(a).shape, order="F") for a in cross.inputs]
     gp = [np.zeros(np.asarray(a).shape, order="F") for a in pss.inputs]
-    stem = "sgp_posterior" if isinstance(f, PosteriorGP) else "sgp_sparse_posterior"
-    h = f._ensure()
+    stem, h = f._stem, f._ensure()
     rc = getattr(ctx.predgrad, stem + "_predict_grad_x")(h, cross.ref(), pss.ref(), _lib.dptr(ms), _lib.dptr(mo), _lib.dptr(vo),
                                                         _dptrs(gm), _dptrs(gv), _dptrs(gp))
     _lib.check(rc, stem + "_predict_grad_x")
@@ -339,12 +336,8 @@ def _postfx_route(fx):
     if all(_eltype(x) == np.float32 for x in (fx.x, *f._train_inputs())):
         return None
     kind, nbuf = _lib._noise_args(fx.noise, len(fx))
-    cross, _, _ = build_spec(f.prior, fx.x, f.prior, f._train_inputs()[0])
-    pss = _prior_spec(f.prior, fx.x)
-    ms = _f64(mean_vector(f.prior, fx.x))
-    if isinstance(f, PosteriorGP):
-        return lib, "sgp_posterior", f._ensure(), cross, pss, ms, kind, nbuf
-    return lib, "sgp_sparse_posterior", f._ensure(), cross, pss, ms, kind, nbuf
+    cross, pss, ms = _cross_side(f, fx.x)
+    return lib, f._stem, f._ensure(), cross, pss, ms, kind, nbuf
 
 
 def logpdf(fx, y):
@@ -985,8 +978,90 @@ def rand(rng, fx, S=None, Z=None):
     return out[:, 0].copy() if S is None else out
 
 
+# ---- posteriors --------------------------------------------------------------------------------
+def _cross_side(post, xs, want_prior=True):
+    """(cross, prior_ss or None, mean_s) of a kept posterior at the test points xs: the spec of K(x*, x) against the points
+    the factor was made from, the symmetric spec of K(x*, x*) and the prior mean at x* -- what every entry point that reads
+    the kept factor takes (predict, rand / logpdf of post(x*), the prediction gradients)."""
+    cross, _, _ = build_spec(post.prior, xs, post.prior, post._train_inputs()[0])
+    pss = _prior_spec(post.prior, xs) if want_prior else None
+    return cross, pss, _f64(mean_vector(post.prior, xs))
+
+
+class _KeptPosterior:
+    """What the posteriors share: a handle `_h` on factors kept in HBM and the moments read off them.  A subclass gives
+    `_stem` (its entry points are <stem>_predict, _destroy, and for rand / logpdf / the prediction gradients _rand, _logpdf,
+    _predict_grad_x), `_train_inputs()`, `_ensure()` where its handle can be rebuilt, and -- where the cross side is not a
+    pair of specs -- `_reader` and `_typed`."""
+
+    _stem = "sgp_posterior"
+
+    def _ensure(self):
+        return self._h
+
+    def __del__(self):  # pragma: no cover
+        try:
+            if self._h:
+                getattr(_lib.load(), self._stem + "_destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __call__(self, xs, noise=1e-18):
+        return FiniteGP(self, xs, noise)
+
+    def _reader(self, xs, want_var, want_cov):
+        """(N*, call): call(handle, mean_out, var_out, cov_out, ldcov) -> (entry point, rc)"""
+        cross, pss, ms = _cross_side(self, xs, want_var or want_cov)
+        name = self._stem + "_predict"
+
+        def call(h, *outs):
+            return name, getattr(_ctx().lib, name)(h, cross.ref(), pss.ref() if pss is not None else None, _lib.dptr(ms), *outs)
+        return cross.N, call
+
+    def _typed(self, out, *xs):
+        return _model_type(out, *xs, *self._train_inputs())
+
+    def _predict(self, xs, want_mean, want_var, want_cov):
+        ns, call = self._reader(xs, want_var, want_cov)
+        mo = np.zeros(ns) if want_mean else None
+        vo = np.zeros(ns) if want_var else None
+        co = np.zeros((ns, ns), order="F") if want_cov else None
+        name, rc = call(self._ensure(), _lib.dptr(mo), _lib.dptr(vo), _lib.dptr(co), max(ns, 1))
+        _lib.check(rc, name)
+        return mo, vo, co
+
+    def mean(self, xs):
+        return self._typed(self._predict(xs, True, False, False)[0], xs)
+
+    def var(self, xs):
+        return self._typed(self._predict(xs, False, True, False)[1], xs)
+
+    def cov(self, xs, zs=None):
+        if zs is None:
+            return self._typed(self._predict(xs, False, False, True)[2], xs)
+        # cov(post, x*, z*) = K(x*, z*) - V_x*' V_z*: the off-diagonal block of the joint covariance over [x*; z*]
+        joint = self._predict(BlockData([xs, zs]) if not isinstance(xs, BlockData) else _concat(xs, zs),
+                              False, False, True)[2]
+        nx = len(xs)
+        return self._typed(joint[:nx, nx:], xs, zs)
+
+    def mean_and_var(self, xs):
+        m, v, _ = self._predict(xs, True, True, False)
+        return self._typed((m, v), xs)
+
+    def mean_and_cov(self, xs):
+        m, _, c = self._predict(xs, True, False, True)
+        return self._typed((m, c), xs)
+
+
+def _concat(xs, zs):
+    zb = zs.X if isinstance(zs, BlockData) else [zs]
+    return BlockData(list(xs.X) + list(zb))
+
+
 # ---- exact posterior ---------------------------------------------------------------------------
-class PosteriorGP:
+class PosteriorGP(_KeptPosterior):
     """posterior(fx, y): keeps L and L^-1 (y - m) in HBM (sgp_post); data = (alpha, x, delta)."""
 
     def __init__(self, prior, x, handle, alpha, delta, noise=None, y=None, mean_x=None):
@@ -1014,61 +1089,8 @@ class PosteriorGP:
         self._ensure()
         return self._alpha
 
-    def __del__(self):  # pragma: no cover
-        try:
-            if self._h:
-                _lib.load().sgp_posterior_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def __call__(self, xs, noise=1e-18):
-        return FiniteGP(self, xs, noise)
-
     def _train_inputs(self):
         return (self.x,)
-
-    def _predict(self, xs, want_mean, want_var, want_cov):
-        cross, _, _ = build_spec(self.prior, xs, self.prior, self.x)
-        pss = _prior_spec(self.prior, xs) if (want_var or want_cov) else None
-        ns = cross.N
-        ms = _f64(mean_vector(self.prior, xs))
-        self._ensure()
-        mo = np.zeros(ns) if want_mean else None
-        vo = np.zeros(ns) if want_var else None
-        co = np.zeros((ns, ns), order="F") if want_cov else None
-        rc = _ctx().lib.sgp_posterior_predict(self._h, cross.ref(), pss.ref() if pss is not None else None,
-                                              _lib.dptr(ms), _lib.dptr(mo), _lib.dptr(vo), _lib.dptr(co), max(ns, 1))
-        _lib.check(rc, "sgp_posterior_predict")
-        return mo, vo, co
-
-    def mean(self, xs):
-        return _model_type(self._predict(xs, True, False, False)[0], xs, *self._train_inputs())
-
-    def var(self, xs):
-        return _model_type(self._predict(xs, False, True, False)[1], xs, *self._train_inputs())
-
-    def cov(self, xs, zs=None):
-        if zs is None:
-            return _model_type(self._predict(xs, False, False, True)[2], xs, *self._train_inputs())
-        # cov(post, x*, z*) = K(x*, z*) - V_x*' V_z*: the off-diagonal block of the joint covariance
-        joint = self._predict(BlockData([xs, zs]) if not isinstance(xs, BlockData) else _concat(xs, zs),
-                              False, False, True)[2]
-        nx = len(xs)
-        return _model_type(joint[:nx, nx:], xs, zs, *self._train_inputs())
-
-    def mean_and_var(self, xs):
-        m, v, _ = self._predict(xs, True, True, False)
-        return _model_type((m, v), xs, *self._train_inputs())
-
-    def mean_and_cov(self, xs):
-        m, _, c = self._predict(xs, True, False, True)
-        return _model_type((m, c), xs, *self._train_inputs())
-
-
-def _concat(xs, zs):
-    zb = zs.X if isinstance(zs, BlockData) else [zs]
-    return BlockData(list(xs.X) + list(zb))
 
 
 def _stack_observations(p1, fx2, y2):
@@ -1580,10 +1602,12 @@ def elbo_and_gradient_param(vfe, fx, y=None, inputs=False, scales=False):
     return rec
 
 
-class ApproxPosteriorGP:
+class ApproxPosteriorGP(_KeptPosterior):
     """posterior(VFE(fz), fx, y): keeps Lz, the factor of A A' + I and the sums over the data points in HBM (sgp_sparse_post).
     vfe / batches: the VFE object and the observation batches (x, Sigma_y, y) it was conditioned on, by reference -- what
     update_posterior needs to rebuild a posterior whose handle moved on, or to re-condition on other inducing points."""
+
+    _stem = "sgp_sparse_posterior"
 
     def __init__(self, prior, z, handle, vfe=None, batches=None, created=None):
         self.prior, self.z, self._h = prior, z, handle
@@ -1612,59 +1636,11 @@ class ApproxPosteriorGP:
             self._trace0 = t
         return self._trace0
 
-    def __del__(self):  # pragma: no cover
-        try:
-            if self._h:
-                _lib.load().sgp_sparse_posterior_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def __call__(self, xs, noise=1e-18):
-        return FiniteGP(self, xs, noise)
-
     def _train_inputs(self):
         return (self.z,)
 
-    def _predict(self, xs, want_mean, want_var, want_cov):
-        cross, _, _ = build_spec(self.prior, xs, self.prior, self.z)
-        pss = _prior_spec(self.prior, xs) if (want_var or want_cov) else None
-        ns = cross.N
-        ms = _f64(mean_vector(self.prior, xs))
-        mo = np.zeros(ns) if want_mean else None
-        vo = np.zeros(ns) if want_var else None
-        co = np.zeros((ns, ns), order="F") if want_cov else None
-        rc = _ctx().lib.sgp_sparse_posterior_predict(self._ensure(), cross.ref(), pss.ref() if pss is not None else None,
-                                                     _lib.dptr(ms), _lib.dptr(mo), _lib.dptr(vo), _lib.dptr(co),
-                                                     max(ns, 1))
-        _lib.check(rc, "sgp_sparse_posterior_predict")
-        return mo, vo, co
 
-    def mean(self, xs):
-        return _model_type(self._predict(xs, True, False, False)[0], xs, *self._train_inputs())
-
-    def var(self, xs):
-        return _model_type(self._predict(xs, False, True, False)[1], xs, *self._train_inputs())
-
-    def cov(self, xs, zs=None):
-        if zs is None:
-            return _model_type(self._predict(xs, False, False, True)[2], xs, *self._train_inputs())
-        # cov(post, x*, z*): the off-diagonal block of the joint covariance over [x*; z*] (as PosteriorGP.cov)
-        joint = self._predict(BlockData([xs, zs]) if not isinstance(xs, BlockData) else _concat(xs, zs),
-                              False, False, True)[2]
-        nx = len(xs)
-        return _model_type(joint[:nx, nx:], xs, zs, *self._train_inputs())
-
-    def mean_and_var(self, xs):
-        m, v, _ = self._predict(xs, True, True, False)
-        return _model_type((m, v), xs, *self._train_inputs())
-
-    def mean_and_cov(self, xs):
-        m, _, c = self._predict(xs, True, False, True)
-        return _model_type((m, c), xs, *self._train_inputs())
-
-
-class ExplicitPosteriorGP:
+class ExplicitPosteriorGP(_KeptPosterior):
     """posterior(g(x2, S2), y2) for a process g whose covariance is not a sum of kernel terms (round 5): g answers
     mean / var / cov itself (the approximate posterior does, on the device); the factor of cov(g, x2) + S2 is built by
     sgp_posterior_create on the zero-term spec with dense noise, predictions go through sgp_posterior_predict_explicit with
@@ -1688,55 +1664,24 @@ class ExplicitPosteriorGP:
         _lib.check(rc, "sgp_posterior_create")
         self._h, self.alpha, self.delta = h, alpha, y - self._mean_x
 
-    def __del__(self):  # pragma: no cover
-        try:
-            if self._h:
-                _lib.load().sgp_posterior_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def __call__(self, xs, noise=1e-18):
-        return FiniteGP(self, xs, noise)
-
     def _train_inputs(self):
         return (self.x,)
 
-    def _predict(self, xs, want_mean, want_var, want_cov):
+    def _reader(self, xs, want_var, want_cov):
         ns = len(xs)
         cross = np.asfortranarray(np.asarray(self.base.cov(xs, self.x), dtype=np.float64))       # ns x N
         ms = _f64(np.asarray(self.base.mean(xs), dtype=np.float64))
         pv = _f64(np.asarray(self.base.var(xs), dtype=np.float64)) if want_var else None
         pc = np.asfortranarray(np.asarray(self.base.cov(xs), dtype=np.float64)) if want_cov else None
-        mo = np.zeros(ns) if want_mean else None
-        vo = np.zeros(ns) if want_var else None
-        co = np.zeros((ns, ns), order="F") if want_cov else None
-        rc = _ctx().lib.sgp_posterior_predict_explicit(self._h, _lib.dptr(cross), max(ns, 1), ns, _lib.dptr(pv), _lib.dptr(pc),
-                                                       max(ns, 1), _lib.dptr(ms), _lib.dptr(mo), _lib.dptr(vo), _lib.dptr(co),
-                                                       max(ns, 1))
-        _lib.check(rc, "sgp_posterior_predict_explicit")
-        return mo, vo, co
 
-    def mean(self, xs):
-        return self._predict(xs, True, False, False)[0]
+        def call(h, *outs):
+            rc = _ctx().lib.sgp_posterior_predict_explicit(h, _lib.dptr(cross), max(ns, 1), ns, _lib.dptr(pv), _lib.dptr(pc),
+                                                           max(ns, 1), _lib.dptr(ms), *outs)
+            return "sgp_posterior_predict_explicit", rc
+        return ns, call
 
-    def var(self, xs):
-        return self._predict(xs, False, True, False)[1]
-
-    def cov(self, xs, zs=None):
-        if zs is None:
-            return self._predict(xs, False, False, True)[2]
-        joint = self._predict(BlockData([xs, zs]) if not isinstance(xs, BlockData) else _concat(xs, zs), False, False, True)[2]
-        nx = len(xs)
-        return joint[:nx, nx:]
-
-    def mean_and_var(self, xs):
-        m, v, _ = self._predict(xs, True, True, False)
-        return m, v
-
-    def mean_and_cov(self, xs):
-        m, _, c = self._predict(xs, True, False, True)
-        return m, c
+    def _typed(self, out, *xs):       # base answered in its own type
+        return out
 
 
 def _vfe_create(vfe, fx, y):
