@@ -3,6 +3,7 @@
 #include "ctx.h"
 #include "driver.h"
 #include "kept.h"
+#include "asm_frame.h"
 #include "tilemap.h"
 #include "sz_pattern.h"
 #include "df_tasks.h"
@@ -625,6 +626,7 @@ static inline int chain_dmax(const sgp_dspec* ds, int t, int e) { return chain_d
 static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, long tile_r_hi,
                     long tile_c_lo, long tile_c_hi, int lower_only, int noise_kind, double sigma2,
                     const double* d_noise_diag, hipStream_t s) {
+  AsmLaunch L{Kv, ld, lower_only, noise_kind, sigma2, d_noise_diag};   // the target: once per call
   for (int I = 0; I < ds->nrb; ++I) {
     if (ds->row_len[I] == 0) continue;
     for (int J = 0; J < ds->ncb; ++J) {
@@ -634,41 +636,43 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       long trf = std::max(r0 / TILE, tile_r_lo), trl = std::min((r0 + nr - 1) / TILE + 1, tile_r_hi);
       long tcf = std::max(c0 / TILE, tile_c_lo), tcl = std::min((c0 + nc - 1) / TILE + 1, tile_c_hi);
       if (trf >= trl || tcf >= tcl) continue;
+      // the pair's rectangle and tile window: once per pair.  Sigma_y lands in the diagonal blocks of a symmetric matrix
+      L.r0 = r0, L.nr = nr, L.c0 = c0, L.nc = nc, L.diag = ds->symmetric && I == J;
+      L.r_first = trf, L.c_first = tcf, L.r_cnt = trl - trf, L.c_cnt = tcl - tcf;
       int p = I * ds->ncb + J;
       // plain | patch (conv.hip) | stencil (stencil.hip) | derivative (deriv.hip) | chains (kprod.hip)
       const auto [t0, tp, ts, tk, t1, td] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = assemble_terms_per_launch(dmax);  // terms per launch: <= 64 KiB of LDS
-      int nk = (ds->symmetric && I == J) ? noise_kind : -1;
-      if (t0 == t1) {
-        CHECK_RC(launch_assemble_block(Kv, ld, r0, nr, c0, nc, ds->d_terms, 0, 1, lower_only, 0, nk,
-                                       sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+      L.first = true;
+      if (t0 == t1) {   // a pair without terms: zeros (+ Sigma_y)
+        CHECK_RC(launch_assemble_block(L, ds->d_terms, 0, 1, s));
         continue;
       }
       for (int t = t0; t < tp; t += per) {
         int cnt = std::min(per, tp - t);
-        CHECK_RC(launch_assemble_block(Kv, ld, r0, nr, c0, nc, ds->d_terms + t, cnt, dmax,
-                                       lower_only, t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2,
-                                       d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+        L.first = t == t0;
+        CHECK_RC(launch_assemble_block(L, ds->d_terms + t, cnt, dmax, s));
       }
-      for (int t = tp; t < ts; ++t)
-        CHECK_RC(launch_assemble_conv(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only, t > t0 ? 1 : 0,
-                                      t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
-      for (int t = ts; t < td; ++t)
-        CHECK_RC(launch_assemble_stencil(Kv, ld, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, lower_only,
-                                         t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf,
-                                         tcl - tcf, s));
+      for (int t = tp; t < ts; ++t) {
+        L.first = t == t0;
+        CHECK_RC(launch_assemble_conv(L, ds->h_terms[t], ds->d_terms + t, s));
+      }
+      for (int t = ts; t < td; ++t) {
+        L.first = t == t0;
+        CHECK_RC(launch_assemble_stencil(L, ds->h_terms[t], ds->d_terms + t, s));
+      }
       for (int t = td; t < tk;) {   // one group per launch: one exponential per point pair for all its terms (deriv.hip)
         const int cnt = deriv_group(ds->h_terms.data(), t, tk);
-        CHECK_RC(launch_assemble_deriv(Kv, ld, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, lower_only,
-                                       t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+        L.first = t == t0;
+        CHECK_RC(launch_assemble_deriv(L, ds->h_terms.data() + t, ds->d_terms + t, cnt, s));
         t += cnt;
       }
       for (int t = tk; t < t1;) {   // whole chains per launch, as many as fit its LDS (kprod.hip: kprod_group)
         int kdmax = 1;
         const int cnt = kprod_group(ds->h_terms.data(), t, t1, &kdmax);
-        CHECK_RC(launch_assemble_kprod(Kv, ld, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, kdmax, lower_only,
-                                       t > t0 ? 1 : 0, t == t0 ? nk : -1, sigma2, d_noise_diag, trf, tcf, trl - trf, tcl - tcf, s));
+        L.first = t == t0;
+        CHECK_RC(launch_assemble_kprod(L, ds->h_terms.data() + t, ds->d_terms + t, cnt, kdmax, s));
         t += cnt;
       }
     }

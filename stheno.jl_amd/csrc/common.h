@@ -123,11 +123,13 @@ constexpr int STENCIL_MAX_DIM = 16;
 constexpr int CONV_MAX_PIXELS = 3072;   // images of at most this many pixels: five of them are staged in LDS at once
 constexpr int CONV_MAX_PATCH = 64;      // ph * pw
 
-// conv.hip: patch terms of one block pair, one launch per term, onto what the plain terms wrote (accumulate != 0) or
-// written afresh with the pair's noise; `dterm` is the device copy of `T`
-int launch_assemble_conv(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm& T, const DevTerm* dterm,
-                         int lower_only, int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,
-                         long tile_r_first, long tile_c_first, long tile_r_cnt, long tile_c_cnt, hipStream_t s);
+// what an assembly launch writes into: the target matrix, the pair's rectangle, the tile window, and whether it is the pair's
+// first launch (asm_frame.h)
+struct AsmLaunch;
+
+// conv.hip: patch terms of one block pair, one launch per term, onto what the pair's earlier launches wrote or, as its first
+// launch, written afresh with the pair's noise; `dterm` is the device copy of `T`
+int launch_assemble_conv(const AsmLaunch& L, const DevTerm& T, const DevTerm* dterm, hipStream_t s);
 // out[i] (i < n) = the plain terms' diagonal (nplain of them, diag_terms_kernel's sum) followed by the patch terms
 // terms[nplain, nterms), each summed as launch_assemble_conv sums entry (i, i).  max_d: the widest patch of those terms,
 // d_all: their common patch dimension (0: they differ), max_pixels: the most image pixels (row + column side) of one term
@@ -150,9 +152,7 @@ int launch_grad_conv_points(const double* Gm, long ldg, const double* alpha, lon
                             const DevTerm& T, const DevTerm* dterm, double scale, double* gz, hipStream_t s);
 
 // stencil.hip: stencil terms of one block pair, one launch per term, arguments as launch_assemble_conv
-int launch_assemble_stencil(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm& T, const DevTerm* dterm,
-                            int lower_only, int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,
-                            long tile_r_first, long tile_c_first, long tile_r_cnt, long tile_c_cnt, hipStream_t s);
+int launch_assemble_stencil(const AsmLaunch& L, const DevTerm& T, const DevTerm* dterm, hipStream_t s);
 // out[i] (i < n) = fma(s_t(i), w_t(i), out[i]) for the stencil terms t in order, s_t(i) summed as launch_assemble_stencil
 // sums entry (i, i); out holds the pair's plain and patch diagonal.  max_dim: the largest input dimension of those terms
 int launch_diag_stencil(double* out, long n, const DevTerm* d_terms, int nterms, int max_dim, hipStream_t s);
@@ -193,10 +193,8 @@ int launch_diag_grad_stencil_wo(const double* w, long n, const DevTerm& T, int t
 // Every launcher takes the host copies of its terms (h_terms; where the kernel reads them from device memory, d_terms too,
 // as launch_grad_conv does) and picks the kernel instantiation from their kinds: kprod_kinds_table.h
 int kprod_group(const DevTerm* h_terms, int t, int t1, int* dmax_out);
-int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* h_terms,
-                          const DevTerm* d_terms, int nterms, int dmax, int lower_only, int accumulate, int noise_kind, double sigma2,
-                          const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
-                          long tile_c_cnt, hipStream_t s);
+int launch_assemble_kprod(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int dmax,
+                          hipStream_t s);
 // out[i] (i < n) = (accumulate ? out[i] : 0) + the chains of one launch group, summed as launch_assemble_kprod sums entry (i, i)
 int launch_diag_kprod(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
                       hipStream_t s);
@@ -220,10 +218,7 @@ int launch_diag_grad_kprod(const double* w, long n, const DevTerm* h_terms, int 
 // deriv.hip: the derivative kinds (include/sthenomi.h: SGP_DERIV_*), a term class of its own.  A launch carries ONE group of a
 // pair's derivative terms (deriv_kinds.h: deriv_group -- the same base kind, points and scale vectors), host copies at h_terms,
 // device copies at d_terms.  Arguments of launch_assemble_deriv as launch_assemble_block.
-int launch_assemble_deriv(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* h_terms,
-                          const DevTerm* d_terms, int nterms, int lower_only, int accumulate, int noise_kind, double sigma2,
-                          const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
-                          long tile_c_cnt, hipStream_t s);
+int launch_assemble_deriv(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, hipStream_t s);
 // out[i] (i < n) = (accumulate ? out[i] : 0) + the group, summed as launch_assemble_deriv sums entry (i, i)
 int launch_diag_deriv(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
                       hipStream_t s);
@@ -284,11 +279,7 @@ void set_error(const std::string& s);
 
 // ---- launchers implemented in the .hip files -------------------------------------------
 // kernelmatrix.hip
-int launch_assemble_block(double* K, long ld, long r0, long nr, long c0, long nc,
-                          const DevTerm* d_terms, int nterms, int lds_dim_sum, int lower_only,
-                          int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,
-                          long tile_r_first, long tile_c_first, long tile_r_cnt, long tile_c_cnt,
-                          hipStream_t s);
+int launch_assemble_block(const AsmLaunch& L, const DevTerm* d_terms, int nterms, int dmax, hipStream_t s);
 int assemble_terms_per_launch(int dmax);  // how many terms one launch_assemble_block may carry (LDS)
 int launch_rows_dot(const double* rows, long ld, long nrows, long nc, const double* zrow, double* sumsq,
                     double* dot, hipStream_t s);

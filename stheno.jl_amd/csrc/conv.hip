@@ -17,7 +17,7 @@
 //                 by the same functions as above, so var == diag(cov) bit for bit.
 // Accumulation onto the plain terms of the pair: v = fma(s, w, K) with w = (coef rs_i) cs_j; a pair without plain terms
 // is written afresh, fma(s, w, 0) (+ the noise on the diagonal) by its first patch term.
-#include "common.h"
+#include "asm_frame.h"
 #include "kern_eval.h"
 #include "kern_grad.h"
 #include <algorithm>
@@ -125,14 +125,6 @@ __device__ __forceinline__ bool entry_live(long r, long c, int lower_only) { ret
 
 __device__ __forceinline__ double entry_weight(const DevTerm& T, long lr, long lc) {
   return (T.coef * (T.rs ? T.rs[lr] : 1.0)) * (T.cs ? T.cs[lc] : 1.0);
-}
-
-__device__ __forceinline__ void write_entry(double* K, long ld, long r, long c, double s, double w, int accumulate,
-                                            int noise_kind, double sigma2, const double* noise_diag) {
-  double* p = K + r + c * ld;
-  double v = fma(s, w, accumulate ? *p : 0.0);
-  if (noise_kind >= 0 && r == c) v += (noise_kind == 0) ? sigma2 : noise_diag[r];
-  *p = v;
 }
 
 // ---- one side patched -----------------------------------------------------------------------------------------------
@@ -261,36 +253,32 @@ __global__ __launch_bounds__(64) void diag_conv_kernel(double* out, long n, cons
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
 template <int DMAX, bool EXACT, int KIND>
-static int launch_conv_t(double* K, long ld, long r0, long c0, long rlo, long rhi, long clo, long chi, const DevTerm& T,
-                         const DevTerm* dterm, int lower_only, int accumulate, int noise_kind, double sigma2,
-                         const double* d_noise_diag, hipStream_t s) {
+static int launch_conv_t(const AsmLaunch& L, long rlo, long rhi, long clo, long chi, const DevTerm& T, const DevTerm* dterm,
+                         hipStream_t s) {
   if (T.hr && T.hc) {
     const size_t lds = sizeof(double) * ((size_t)T.hr * T.wr + (size_t)CONV2_WAVES * T.hc * T.wc);
     SGP_LDS_ATTR_ONCE((conv2_kernel<DMAX, EXACT, KIND>), 160 * 1024);
     dim3 grid((unsigned)(rhi - rlo), (unsigned)((chi - clo + CONV2_WAVES - 1) / CONV2_WAVES));
-    hipLaunchKernelGGL((conv2_kernel<DMAX, EXACT, KIND>), grid, dim3(256), lds, s, K, ld, r0, c0, rlo, rhi, clo, chi, dterm,
-                       lower_only, accumulate, noise_kind, sigma2, d_noise_diag);
+    hipLaunchKernelGGL((conv2_kernel<DMAX, EXACT, KIND>), grid, dim3(256), lds, s, L.K, L.ld, L.r0, L.c0, rlo, rhi, clo, chi,
+                       dterm, ASM_TAIL(L));
   } else {
     const bool row_img = T.hr > 0;
     const long na = row_img ? rhi - rlo : chi - clo, nb = row_img ? chi - clo : rhi - rlo;
     const size_t lds = sizeof(double) * (size_t)CONV1_IMG * (row_img ? T.hr * T.wr : T.hc * T.wc);
     SGP_LDS_ATTR_ONCE((conv1_kernel<DMAX, EXACT, KIND>), 160 * 1024);
     dim3 grid((unsigned)((na + CONV1_IMG - 1) / CONV1_IMG), (unsigned)((nb + 256 * CONV1_CC - 1) / (256 * CONV1_CC)));
-    hipLaunchKernelGGL((conv1_kernel<DMAX, EXACT, KIND>), grid, dim3(256), lds, s, K, ld, r0, c0, rlo, rhi, clo, chi, dterm,
-                       lower_only, accumulate, noise_kind, sigma2, d_noise_diag);
+    hipLaunchKernelGGL((conv1_kernel<DMAX, EXACT, KIND>), grid, dim3(256), lds, s, L.K, L.ld, L.r0, L.c0, rlo, rhi, clo, chi,
+                       dterm, ASM_TAIL(L));
   }
   SGP_HIP(hipGetLastError());
   return 0;
 }
 
 template <int DMAX, bool EXACT>
-static int launch_conv_kind(int kind, double* K, long ld, long r0, long c0, long rlo, long rhi, long clo, long chi,
-                            const DevTerm& T, const DevTerm* dterm, int lower_only, int accumulate, int noise_kind,
-                            double sigma2, const double* d_noise_diag, hipStream_t s) {
-#define SGP_CONVK(KD) \
-  return launch_conv_t<DMAX, EXACT, KD>(K, ld, r0, c0, rlo, rhi, clo, chi, T, dterm, lower_only, accumulate, noise_kind, \
-                                        sigma2, d_noise_diag, s)
-  switch (kind) {
+static int launch_conv_kind(const AsmLaunch& L, long rlo, long rhi, long clo, long chi, const DevTerm& T, const DevTerm* dterm,
+                            hipStream_t s) {
+#define SGP_CONVK(KD) return launch_conv_t<DMAX, EXACT, KD>(L, rlo, rhi, clo, chi, T, dterm, s)
+  switch (T.kind) {
     case K_SE: SGP_CONVK(K_SE);
     case K_M12: SGP_CONVK(K_M12);
     case K_M32: SGP_CONVK(K_M32);
@@ -314,21 +302,15 @@ static int launch_conv_kind(int kind, double* K, long ld, long r0, long c0, long
     else CALL(64, false);                       \
   } while (0)
 
-int launch_assemble_conv(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm& T, const DevTerm* dterm,
-                         int lower_only, int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,
-                         long tile_r_first, long tile_c_first, long tile_r_cnt, long tile_c_cnt, hipStream_t s) {
-  if (tile_r_cnt <= 0 || tile_c_cnt <= 0) return 0;
-  const long rlo = std::max(r0, tile_r_first * TILE), rhi = std::min(r0 + nr, (tile_r_first + tile_r_cnt) * TILE);
-  const long clo = std::max(c0, tile_c_first * TILE), chi = std::min(c0 + nc, (tile_c_first + tile_c_cnt) * TILE);
-  if (rlo >= rhi || clo >= chi) return 0;
+int launch_assemble_conv(const AsmLaunch& L, const DevTerm& T, const DevTerm* dterm, hipStream_t s) {
+  long rlo, rhi, clo, chi;
+  if (!L.entries(rlo, rhi, clo, chi)) return 0;
   const int D = T.ph * T.pw;
   if (!(T.hr || T.hc) || D < 1 || D > CONV_MAX_PATCH) {
     set_error("assemble: not a patch term");
     return -1;
   }
-#define SGP_CONV_CALL(DM, EX) \
-  return launch_conv_kind<DM, EX>(T.kind, K, ld, r0, c0, rlo, rhi, clo, chi, T, dterm, lower_only, accumulate, noise_kind, \
-                                  sigma2, d_noise_diag, s)
+#define SGP_CONV_CALL(DM, EX) return launch_conv_kind<DM, EX>(L, rlo, rhi, clo, chi, T, dterm, s)
   SGP_CONV_DISPATCH(D, SGP_CONV_CALL);
 #undef SGP_CONV_CALL
   return 0;

@@ -13,7 +13,7 @@
 // column points [point][DMAX], row points [d][row], row and column scales staged in LDS once per tile; 16-byte stores on
 // interior tiles.  The coordinate differences u_p of a term are re-formed from the staged points (an LDS address, not a
 // register index: no scratch), by the very subtraction the distance used.
-#include "common.h"
+#include "asm_frame.h"
 #include "deriv_eval.h"
 #include "deriv_kinds.h"
 #include <algorithm>
@@ -57,48 +57,18 @@ __global__ __launch_bounds__(256) void assemble_deriv_kernel(
   const int t = threadIdx.x;
   const int lane = t & 63, wv = t >> 6;
 
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  if (cbeg >= cend || rbeg >= rend) return;   // uniform over the workgroup
+  TileClip cl;
+  if (!tile_clip(gtr, gtc, r0, nr, c0, nc, cl)) return;   // uniform over the workgroup
 
-  double* sc = smem;
-  double* sr = sc + TILE * DMAX;
-  double* srw = sr + TILE * DMAX;
-  double* scw = srw + TILE;
-  {
-    const DevTerm T = terms[0];   // the group's points and scales
-    const int D = T.dim;
-    for (int idx = t; idx < TILE * DMAX; idx += 256) {
-      const int p = idx / DMAX, d = idx % DMAX;
-      const long gc = gtc * TILE + p, gr = gtr * TILE + p;
-      sc[idx] = (d < D && gc >= cbeg && gc < cend) ? T.xc[(gc - c0) * T.ldc + d] : 0.0;
-      sr[d * TILE + p] = (d < D && gr >= rbeg && gr < rend) ? T.xr[(gr - r0) * T.ldr + d] : 0.0;
-    }
-    if (t < TILE) {
-      const long gr = gtr * TILE + t;
-      srw[t] = (gr >= rbeg && gr < rend) ? (T.rs ? T.rs[gr - r0] : 1.0) : 0.0;
-    } else {
-      const int p = t - TILE;
-      const long gc = gtc * TILE + p;
-      scw[p] = (gc >= cbeg && gc < cend) ? (T.cs ? T.cs[gc - c0] : 1.0) : 0.0;
-    }
-  }
+  const double* sc = smem;
+  const double* sr = sc + TILE * DMAX;
+  const double* srw = sr + TILE * DMAX;
+  const double* scw = srw + TILE;
+  // the group's points and scales; the row weight is the row scale alone (every term brings its own coefficient)
+  stage_pair_points<DMAX>(smem, terms[0], 1.0, gtr, gtc, r0, c0, cl, t);
   __syncthreads();
 
-  const long g0 = gtr * TILE + 2 * lane, g1 = g0 + 1;
-  const bool ok0 = g0 >= rbeg && g0 < rend, ok1 = g1 >= rbeg && g1 < rend;
-  const bool diag_noise = noise_kind >= 0 && gtr == gtc;
-  double nv0 = 0.0, nv1 = 0.0;
-  if (diag_noise) {
-    nv0 = (noise_kind == 0) ? sigma2 : (ok0 ? noise_diag[g0] : 0.0);
-    nv1 = (noise_kind == 0) ? sigma2 : (ok1 ? noise_diag[g1] : 0.0);
-  }
-  const bool full = (cend - cbeg == TILE) && (rend - rbeg == TILE) && !accumulate &&
-                    ((((unsigned long long)(K + g0)) & 15ull) == 0) && ((ld & 1) == 0);
+  const PairRows R = pair_rows(K, ld, gtr, gtc, lane, cl, accumulate, noise_kind, sigma2, noise_diag);
 
   double xi0[DMAX], xi1[DMAX];
 #pragma unroll
@@ -145,43 +115,17 @@ __global__ __launch_bounds__(256) void assemble_deriv_kernel(
         acc1[q] = fma(v1, w1 * cq, acc1[q]);
       }
     }
-    if (full && !diag_noise) {
-      double* kp = K + g0 + (gtc * TILE + pbase) * ld;
-#pragma unroll
-      for (int q = 0; q < DCC; ++q) *reinterpret_cast<double2*>(kp + q * ld) = make_double2(acc0[q], acc1[q]);
-    } else if (full) {
-#pragma unroll
-      for (int q = 0; q < DCC; ++q) {
-        const long gc = gtc * TILE + pbase + q;
-        double v0 = acc0[q], v1 = acc1[q];
-        if (gc == g0) v0 += nv0;
-        if (gc == g1) v1 += nv1;
-        *reinterpret_cast<double2*>(K + g0 + gc * ld) = make_double2(v0, v1);
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < DCC; ++q) {
-        const long gc = gtc * TILE + pbase + q;
-        if (gc >= cbeg && gc < cend) {
-          double v0 = acc0[q], v1 = acc1[q];
-          if (diag_noise && gc == g0) v0 += nv0;
-          if (diag_noise && gc == g1) v1 += nv1;
-          double* p = K + g0 + gc * ld;
-          if (ok0) p[0] = accumulate ? p[0] + v0 : v0;
-          if (ok1) p[1] = accumulate ? p[1] + v1 : v1;
-        }
-      }
-    }
+    store_pair_tail<DCC>(K, ld, gtc * TILE + pbase, cl, R, acc0, acc1, accumulate);
   }
 }
 
 template <int BASE>
-static int launch_assemble_deriv_b(int dmax, dim3 grid, size_t lds, hipStream_t s, double* K, long ld, long r0, long nr,
-                                   long c0, long nc, const DevTerm* d_terms, int nterms, int lower_only, int accumulate,
-                                   int noise_kind, double sigma2, const double* d_noise_diag, long trf, long tcf) {
-#define SGP_DV(DM)                                                                                                          \
-  hipLaunchKernelGGL((assemble_deriv_kernel<DM, BASE>), grid, dim3(256), lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms, \
-                     lower_only, accumulate, noise_kind, sigma2, d_noise_diag, trf, tcf)
+static int launch_assemble_deriv_b(const AsmLaunch& L, int dmax, const DevTerm* d_terms, int nterms, hipStream_t s) {
+  const size_t lds = sizeof(double) * deriv_lds_doubles(dmax);
+  const dim3 grid((unsigned)L.r_cnt, (unsigned)L.c_cnt);
+#define SGP_DV(DM)                                                                                                      \
+  hipLaunchKernelGGL((assemble_deriv_kernel<DM, BASE>), grid, dim3(256), lds, s, L.K, L.ld, L.r0, L.nr, L.c0, L.nc, d_terms, \
+                     nterms, ASM_TAIL(L), L.r_first, L.c_first)
   if (dmax <= 1) SGP_DV(1);
   else if (dmax <= 2) SGP_DV(2);
   else if (dmax <= 4) SGP_DV(4);
@@ -192,23 +136,16 @@ static int launch_assemble_deriv_b(int dmax, dim3 grid, size_t lds, hipStream_t 
   return 0;
 }
 
-// One group of one block pair (h_terms: host copies, d_terms: the same on the device); arguments as launch_assemble_block
-int launch_assemble_deriv(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* h_terms,
-                          const DevTerm* d_terms, int nterms, int lower_only, int accumulate, int noise_kind, double sigma2,
-                          const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
-                          long tile_c_cnt, hipStream_t s) {
-  if (nterms <= 0 || tile_r_cnt <= 0 || tile_c_cnt <= 0) return 0;
+// One group of one block pair (h_terms: host copies, d_terms: the same on the device)
+int launch_assemble_deriv(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, hipStream_t s) {
+  if (nterms <= 0 || L.empty()) return 0;
   const int code = h_terms[0].kind & 0xff, dim = h_terms[0].dim;
   if (!deriv_kind_known(code) || dim < 1 || dim > DERIV_MAX_DIM) {
     set_error("assemble: not a derivative term");
     return -1;
   }
   const int dmax = deriv_dmax_class(dim);
-  const size_t lds = sizeof(double) * deriv_lds_doubles(dmax);
-  const dim3 grid((unsigned)tile_r_cnt, (unsigned)tile_c_cnt);
-#define SGP_DVB(B)                                                                                                      \
-  return launch_assemble_deriv_b<B>(dmax, grid, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms, lower_only, accumulate, \
-                                    noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first)
+#define SGP_DVB(B) return launch_assemble_deriv_b<B>(L, dmax, d_terms, nterms, s)
   switch (deriv_base(code)) {
     case K_SE: SGP_DVB(K_SE);
     case K_M32: SGP_DVB(K_M32);
@@ -299,13 +236,9 @@ __global__ __launch_bounds__(256) void grad_deriv_kernel(const double* Kinv, lon
   int* sab = reinterpret_cast<int*>(scoef + DERIV_GRAD_MAXT);           // [DERIV_GRAD_MAXT][2] their (a, b)
   const int t = threadIdx.x;
   const int trow = t & 127, th = t >> 7;
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  const bool live_tile = cbeg < cend && rbeg < rend;
+  TileClip cl;
+  const bool live_tile = tile_clip(gtr, gtc, r0, nr, c0, nc, cl);
+  const auto [cbeg, cend, rbeg, rend] = cl;
   const DevTerm T = terms[0];
   for (int idx = t; idx < TILE * DMAX; idx += 256) {
     const int p = idx / DMAX, d = idx % DMAX;

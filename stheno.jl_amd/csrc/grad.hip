@@ -10,7 +10,7 @@
 // with the same tiling as the assembly kernel (kernelmatrix.hip): 128x128 tiles, thread = one row
 // x 64 columns, column points broadcast from LDS.  Partials per workgroup are reduced in fixed
 // order by a second kernel (deterministic).
-#include "common.h"
+#include "asm_frame.h"
 #include "kern_grad.h"
 #include <algorithm>
 
@@ -36,15 +36,9 @@ __global__ __launch_bounds__(256) void grad_block_kernel(const double* Kinv, lon
   double* scs = smem + TMAX * TILE * DMAX;     // [nterms][128] column scales
   const int t = threadIdx.x;
   const int trow = t & 127, th = t >> 7;
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  if (cbeg < clo) cbeg = clo;   // (a rank of the sharded gradient contracts the columns of ITS panels only: multi.hip)
-  if (cend > chi) cend = chi;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  const bool live_tile = cbeg < cend && rbeg < rend;
+  TileClip cl;   // (a rank of the sharded gradient contracts the columns of ITS panels only: multi.hip)
+  const bool live_tile = tile_clip(gtr, gtc, r0, nr, c0, nc, cl, clo, chi);
+  const auto [cbeg, cend, rbeg, rend] = cl;
 
   for (int tm = 0; tm < nterms; ++tm) {
     const DevTerm T = terms[tm];
@@ -175,15 +169,9 @@ __global__ __launch_bounds__(256) void grad_block_bigd_kernel(const double* Kinv
   const long gtc = tile_c_first + blockIdx.y;
   const int t = threadIdx.x;
   const int trow = t & 127, th = t >> 7;
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  if (cbeg < clo) cbeg = clo;
-  if (cend > chi) cend = chi;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  const bool live_tile = cbeg < cend && rbeg < rend;
+  TileClip cl;
+  const bool live_tile = tile_clip(gtr, gtc, r0, nr, c0, nc, cl, clo, chi);
+  const auto [cbeg, cend, rbeg, rend] = cl;
   const long grow = gtr * TILE + trow;
   const bool live = live_tile && grow >= rbeg && grow < rend;
   const long lrow = grow - r0;

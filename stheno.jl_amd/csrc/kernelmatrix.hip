@@ -15,7 +15,7 @@
 // copy of the ColVecs segment) and read as wave-uniform broadcasts; the row point lives in
 // registers.  Distances are the direct sum_d (a_d - b_d)^2 (exactly 0 on coincident points, so
 // SE diagonals are exactly 1: test/gp/atomic_gp.jl:34), not the GEMM trick.
-#include "common.h"
+#include "asm_frame.h"
 #include "kern_eval.h"
 #include <algorithm>
 
@@ -50,27 +50,10 @@ __global__ __launch_bounds__(256) void assemble_block_kernel(
   const int t = threadIdx.x;
   const int trow = t & 127, th = t >> 7;
 
-  // column range of this tile inside the block-pair rectangle
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  if (cbeg >= cend || rbeg >= rend) return;
-
-  // stage column points of every term: smem[(tm*128 + p)*DMAX + d], p relative to gtc*128
-  for (int tm = 0; tm < nterms; ++tm) {
-    const DevTerm T = terms[tm];
-    const int D = T.dim;
-    for (int idx = t; idx < TILE * DMAX; idx += 256) {
-      int p = idx / DMAX, d = idx % DMAX;
-      long gc = gtc * TILE + p;
-      double v = 0.0;
-      if (d < D && gc >= cbeg && gc < cend) v = T.xc[(gc - c0) * T.ldc + d];
-      smem[(tm * TILE + p) * DMAX + d] = v;
-    }
-  }
+  TileClip cl;
+  if (!tile_clip(gtr, gtc, r0, nr, c0, nc, cl)) return;   // uniform over the workgroup
+  const auto [cbeg, cend, rbeg, rend] = cl;
+  stage_col_points<DMAX>(smem, terms, nterms, gtc, c0, cl, t);
   __syncthreads();
 
   const long grow = gtr * TILE + trow;
@@ -78,8 +61,7 @@ __global__ __launch_bounds__(256) void assemble_block_kernel(
   if (!row_ok) return;  // no further barriers below
   const long lrow = grow - r0;
   const bool diag_noise = noise_kind >= 0;
-  double nval = 0.0;
-  if (diag_noise) nval = (noise_kind == 0) ? sigma2 : noise_diag[grow];
+  const double nval = row_noise(noise_kind, sigma2, noise_diag, grow);
 
   for (int jc = 0; jc < 64; jc += CCHUNK) {
     const int pbase = th * 64 + jc;  // point index within the tile
@@ -115,17 +97,7 @@ __global__ __launch_bounds__(256) void assemble_block_kernel(
         default: term_chunk<DMAX, K_CONST>(acc, xi, sp, cw, T.param); break;
       }
     }
-#pragma unroll
-    for (int q = 0; q < CCHUNK; ++q) {
-      long gc = gtc * TILE + pbase + q;
-      if (gc >= cbeg && gc < cend) {
-        double v = acc[q];
-        if (diag_noise && gc == grow) v += nval;
-        double* p = K + grow + gc * ld;
-        if (accumulate) v += *p;
-        *p = v;
-      }
-    }
+    store_row_tail<CCHUNK>(K, ld, grow, gtc * TILE + pbase, cl, acc, diag_noise, nval, accumulate);
   }
 }
 
@@ -148,13 +120,9 @@ __global__ __launch_bounds__(256) void assemble_bigd_kernel(double* K, long ld, 
   __shared__ __attribute__((aligned(16))) double sx[TILE * BIGD_CHUNK];
   const int t = threadIdx.x;
   const int trow = t & 127, th = t >> 7;
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  if (cbeg >= cend || rbeg >= rend) return;   // uniform over the workgroup
+  TileClip cl;
+  if (!tile_clip(gtr, gtc, r0, nr, c0, nc, cl)) return;   // uniform over the workgroup
+  const auto [cbeg, cend, rbeg, rend] = cl;
   const DevTerm T = terms[0];
   const int D = T.dim;
   const long grow = gtr * TILE + trow;
@@ -191,17 +159,13 @@ __global__ __launch_bounds__(256) void assemble_bigd_kernel(double* K, long ld, 
   }
   if (!row_ok) return;
   const double rsv = T.coef * (T.rs ? T.rs[lrow] : 1.0);
-  double nval = 0.0;
-  if (noise_kind >= 0) nval = (noise_kind == 0) ? sigma2 : noise_diag[grow];
+  const double nval = row_noise(noise_kind, sigma2, noise_diag, grow);
 #pragma unroll
-  for (int q = 0; q < 64; ++q) {
+  for (int q = 0; q < 64; ++q) {   // (the kernel is evaluated here, entry by entry: store_row_tail's loop written out)
     const long gc = gtc * TILE + th * 64 + q;
     if (gc < cbeg || gc >= cend) continue;
-    double v = kern_eval(T.kind, acc[q], T.param) * rsv * (T.cs ? T.cs[gc - c0] : 1.0);
-    if (noise_kind >= 0 && gc == grow) v += nval;
-    double* p = K + grow + gc * ld;
-    if (accumulate) v += *p;
-    *p = v;
+    const double v = kern_eval(T.kind, acc[q], T.param) * rsv * (T.cs ? T.cs[gc - c0] : 1.0);
+    store_row_entry(K, ld, grow, gc, v, noise_kind >= 0, nval, accumulate);
   }
 }
 
@@ -272,36 +236,18 @@ __global__ __launch_bounds__(256) void assemble_block2_kernel(
   const int t = threadIdx.x;
   const int lane = t & 63, wv = t >> 6;
 
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  if (cbeg >= cend || rbeg >= rend) return;
+  TileClip cl;
+  if (!tile_clip(gtr, gtc, r0, nr, c0, nc, cl)) return;   // uniform over the workgroup
 
-  for (int tm = 0; tm < nterms; ++tm) {
+  for (int tm = 0; tm < nterms; ++tm) {   // the row weight carries the term's coefficient
     const DevTerm T = terms[tm];
-    const int D = T.dim;
-    double* sc = smem + tm * TD;
-    double* sr = sc + TILE * DMAX;
-    for (int idx = t; idx < TILE * DMAX; idx += 256) {
-      const int p = idx / DMAX, d = idx % DMAX;
-      const long gc = gtc * TILE + p, gr = gtr * TILE + p;
-      sc[idx] = (d < D && gc >= cbeg && gc < cend) ? T.xc[(gc - c0) * T.ldc + d] : 0.0;
-      sr[d * TILE + p] = (d < D && gr >= rbeg && gr < rend) ? T.xr[(gr - r0) * T.ldr + d] : 0.0;  // [d][row]
-    }
-    if (t < TILE) {
-      const long gr = gtr * TILE + t;
-      sr[TILE * DMAX + t] = (gr >= rbeg && gr < rend) ? T.coef * (T.rs ? T.rs[gr - r0] : 1.0) : 0.0;
-    } else {
-      const int p = t - TILE;
-      const long gc = gtc * TILE + p;
-      sr[TILE * DMAX + TILE + p] = (gc >= cbeg && gc < cend) ? (T.cs ? T.cs[gc - c0] : 1.0) : 0.0;
-    }
+    stage_pair_points<DMAX>(smem + tm * TD, T, T.coef, gtr, gtc, r0, c0, cl, t);
   }
   __syncthreads();
 
+  // asm_frame.h's pair_rows and, below, store_pair_tail, written out: through either helper every instantiation of this
+  // kernel takes two more SGPRs (92 for 90), and the refactor that introduced them was to leave every kernel's figures alone
+  const auto [cbeg, cend, rbeg, rend] = cl;
   const long g0 = gtr * TILE + 2 * lane, g1 = g0 + 1;
   const bool ok0 = g0 >= rbeg && g0 < rend, ok1 = g1 >= rbeg && g1 < rend;
   const bool diag_noise = noise_kind >= 0 && gtr == gtc;  // only tiles on the diagonal carry Sigma_y entries
@@ -373,41 +319,28 @@ __global__ __launch_bounds__(256) void assemble_block2_kernel(
 }
 
 template <int DMAX>
-static int launch_assemble_t(double* K, long ld, long r0, long nr, long c0, long nc,
-                             const DevTerm* d_terms, int nterms, int lower_only, int accumulate,
-                             int noise_kind, double sigma2, const double* d_noise_diag,
-                             long tile_r_first, long tile_c_first, long tile_r_cnt,
-                             long tile_c_cnt, hipStream_t s) {
+static int launch_assemble_t(const AsmLaunch& L, const DevTerm* d_terms, int nterms, hipStream_t s) {
   size_t lds = (size_t)nterms * TILE * DMAX * sizeof(double);
   if (DMAX <= 16) lds = (size_t)nterms * asm2_term_doubles(DMAX <= 16 ? DMAX : 16) * sizeof(double);
   if (lds == 0) lds = 16;
-  dim3 grid((unsigned)tile_r_cnt, (unsigned)tile_c_cnt), block(256);
+  dim3 grid((unsigned)L.r_cnt, (unsigned)L.c_cnt), block(256);
   if (DMAX <= 16) {
     // square window on the diagonal in lower mode: launch the live tiles only
-    const int tri = lower_only && tile_r_first == tile_c_first && tile_r_cnt == tile_c_cnt;
-    if (tri) grid = dim3((unsigned)(tile_r_cnt * (tile_r_cnt + 1) / 2));
-    hipLaunchKernelGGL(assemble_block2_kernel<(DMAX <= 16 ? DMAX : 16)>, grid, block, lds, s, K, ld, r0, nr, c0, nc,
-                       d_terms, nterms, lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first,
-                       tile_c_first, tri);
+    const int tri = L.lower_only && L.r_first == L.c_first && L.r_cnt == L.c_cnt;
+    if (tri) grid = dim3((unsigned)(L.r_cnt * (L.r_cnt + 1) / 2));
+    hipLaunchKernelGGL(assemble_block2_kernel<(DMAX <= 16 ? DMAX : 16)>, grid, block, lds, s, L.K, L.ld, L.r0, L.nr, L.c0,
+                       L.nc, d_terms, nterms, ASM_TAIL(L), L.r_first, L.c_first, tri);
   } else {
-    hipLaunchKernelGGL(assemble_block_kernel<DMAX>, grid, block, lds, s, K, ld, r0, nr, c0, nc,
-                       d_terms, nterms, lower_only, accumulate, noise_kind, sigma2, d_noise_diag,
-                       tile_r_first, tile_c_first);
+    hipLaunchKernelGGL(assemble_block_kernel<DMAX>, grid, block, lds, s, L.K, L.ld, L.r0, L.nr, L.c0, L.nc, d_terms, nterms,
+                       ASM_TAIL(L), L.r_first, L.c_first);
   }
   SGP_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_assemble_block(double* K, long ld, long r0, long nr, long c0, long nc,
-                          const DevTerm* d_terms, int nterms, int dmax, int lower_only,
-                          int accumulate, int noise_kind, double sigma2,
-                          const double* d_noise_diag, long tile_r_first, long tile_c_first,
-                          long tile_r_cnt, long tile_c_cnt, hipStream_t s) {
-  if (tile_r_cnt <= 0 || tile_c_cnt <= 0) return 0;
-#define SGP_ASM(DM)                                                                            \
-  return launch_assemble_t<DM>(K, ld, r0, nr, c0, nc, d_terms, nterms, lower_only, accumulate, \
-                               noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first,   \
-                               tile_r_cnt, tile_c_cnt, s)
+int launch_assemble_block(const AsmLaunch& L, const DevTerm* d_terms, int nterms, int dmax, hipStream_t s) {
+  if (L.empty()) return 0;
+#define SGP_ASM(DM) return launch_assemble_t<DM>(L, d_terms, nterms, s)
   if (dmax <= 1) SGP_ASM(1);
   if (dmax <= 2) SGP_ASM(2);
   if (dmax <= 4) SGP_ASM(4);
@@ -420,9 +353,8 @@ int launch_assemble_block(double* K, long ld, long r0, long nr, long c0, long nc
     set_error("assemble: input dimension > 64 takes one term per launch");
     return -1;
   }
-  hipLaunchKernelGGL(assemble_bigd_kernel, dim3((unsigned)tile_r_cnt, (unsigned)tile_c_cnt), dim3(256), 0, s, K, ld, r0,
-                     nr, c0, nc, d_terms, lower_only, accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first,
-                     tile_c_first);
+  hipLaunchKernelGGL(assemble_bigd_kernel, dim3((unsigned)L.r_cnt, (unsigned)L.c_cnt), dim3(256), 0, s, L.K, L.ld, L.r0, L.nr,
+                     L.c0, L.nc, d_terms, ASM_TAIL(L), L.r_first, L.c_first);
   SGP_HIP(hipGetLastError());
   return 0;
 }

@@ -20,7 +20,7 @@
 // launch: d / d coef of the head, d / d input scale and d / d param of every factor, the products with one factor left out
 // formed from prefix and suffix products (never a division: a factor that is exactly 0 -- WHITE off the diagonal, an
 // underflowed SE -- gives exact zeros for itself and finite values for the others).
-#include "common.h"
+#include "asm_frame.h"
 #include "kern_eval.h"
 #include "kern_grad.h"
 #include "kprod_kinds_table.h"
@@ -116,33 +116,17 @@ __global__ __launch_bounds__(256) void assemble_kprod_kernel(
   const int t = threadIdx.x;
   const int trow = t & 127, th = t >> 7;
 
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  if (cbeg >= cend || rbeg >= rend) return;   // uniform over the workgroup
-
-  for (int tm = 0; tm < nterms; ++tm) {
-    const DevTerm T = terms[tm];
-    const int D = T.dim;
-    for (int idx = t; idx < TILE * DMAX; idx += 256) {
-      const int p = idx / DMAX, d = idx % DMAX;
-      const long gc = gtc * TILE + p;
-      double v = 0.0;
-      if (d < D && gc >= cbeg && gc < cend) v = T.xc[(gc - c0) * T.ldc + d];
-      smem[(tm * TILE + p) * DMAX + d] = v;
-    }
-  }
+  TileClip cl;
+  if (!tile_clip(gtr, gtc, r0, nr, c0, nc, cl)) return;   // uniform over the workgroup
+  const auto [cbeg, cend, rbeg, rend] = cl;
+  stage_col_points<DMAX>(smem, terms, nterms, gtc, c0, cl, t);
   __syncthreads();
 
   const long grow = gtr * TILE + trow;
   if (grow < rbeg || grow >= rend) return;  // no further barriers below
   const long lrow = grow - r0;
   const bool diag_noise = noise_kind >= 0;
-  double nval = 0.0;
-  if (diag_noise) nval = (noise_kind == 0) ? sigma2 : noise_diag[grow];
+  const double nval = row_noise(noise_kind, sigma2, noise_diag, grow);
 
   for (int jc = 0; jc < 64; jc += KP_CHUNK) {
     const int pbase = th * 64 + jc;  // point index within the tile
@@ -179,17 +163,7 @@ __global__ __launch_bounds__(256) void assemble_kprod_kernel(
       for (int q = 0; q < KP_CHUNK; ++q) acc[q] = fma(prod[q], cw[q], acc[q]);
       tm = f;
     }
-#pragma unroll
-    for (int q = 0; q < KP_CHUNK; ++q) {
-      const long gc = gtc * TILE + pbase + q;
-      if (gc >= cbeg && gc < cend) {
-        double v = acc[q];
-        if (diag_noise && gc == grow) v += nval;
-        double* p = K + grow + gc * ld;
-        if (accumulate) v += *p;
-        *p = v;
-      }
-    }
+    store_row_tail<KP_CHUNK>(K, ld, grow, gtc * TILE + pbase, cl, acc, diag_noise, nval, accumulate);
   }
 }
 
@@ -228,21 +202,19 @@ static int kp_dispatch(int dmax, int mode, F f) {
   return -1;
 }
 
-int launch_assemble_kprod(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm* h_terms,
-                          const DevTerm* d_terms, int nterms, int dmax, int lower_only, int accumulate, int noise_kind,
-                          double sigma2, const double* d_noise_diag, long tile_r_first, long tile_c_first, long tile_r_cnt,
-                          long tile_c_cnt, hipStream_t s) {
-  if (tile_r_cnt <= 0 || tile_c_cnt <= 0 || nterms <= 0) return 0;
+int launch_assemble_kprod(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int dmax,
+                          hipStream_t s) {
+  if (L.empty() || nterms <= 0) return 0;
   if (dmax > 16 || nterms * dmax > 64) {
     set_error("assemble: a product launch beyond terms x dimension <= 64");
     return -1;
   }
-  const dim3 grid((unsigned)tile_r_cnt, (unsigned)tile_c_cnt), block(256);
+  const dim3 grid((unsigned)L.r_cnt, (unsigned)L.c_cnt), block(256);
   return kp_dispatch<KP_MN_MODES>(dmax, kp_mn_of_tier(kp_chain_tier(h_terms, nterms)), [&](auto dm, auto mn) {
     constexpr int DM = decltype(dm)::value, MN = decltype(mn)::value;
     const size_t lds = (size_t)nterms * TILE * DM * sizeof(double);
-    hipLaunchKernelGGL((assemble_kprod_kernel<DM, MN>), grid, block, lds, s, K, ld, r0, nr, c0, nc, d_terms, nterms, lower_only,
-                       accumulate, noise_kind, sigma2, d_noise_diag, tile_r_first, tile_c_first);
+    hipLaunchKernelGGL((assemble_kprod_kernel<DM, MN>), grid, block, lds, s, L.K, L.ld, L.r0, L.nr, L.c0, L.nc, d_terms, nterms,
+                       ASM_TAIL(L), L.r_first, L.c_first);
     SGP_HIP(hipGetLastError());
     return 0;
   });
@@ -373,13 +345,9 @@ __global__ __launch_bounds__(256) void grad_kprod_kernel(const double* Kinv, lon
   double* scs = smem + TMAX * TILE * DMAX;   // [128] column scale of the head
   const int t = threadIdx.x;
   const int trow = t & 127, th = t >> 7;
-  long cbeg = gtc * TILE, cend = cbeg + TILE;
-  if (cbeg < c0) cbeg = c0;
-  if (cend > c0 + nc) cend = c0 + nc;
-  long rbeg = gtr * TILE, rend = rbeg + TILE;
-  if (rbeg < r0) rbeg = r0;
-  if (rend > r0 + nr) rend = r0 + nr;
-  const bool live_tile = cbeg < cend && rbeg < rend;
+  TileClip cl;
+  const bool live_tile = tile_clip(gtr, gtc, r0, nr, c0, nc, cl);
+  const auto [cbeg, cend, rbeg, rend] = cl;
 
   for (int f = 0; f < nf; ++f) {
     const DevTerm T = terms[f];

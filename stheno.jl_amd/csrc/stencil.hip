@@ -14,7 +14,7 @@
 //                        diagonal already in `out` through the same summation function, so var == diag(cov) bit for bit.
 // Accumulation onto the pair's plain and patch terms: v = fma(s, w, K) with w = (coef rs_i) cs_j; a pair with nothing
 // before its first stencil term is written afresh, fma(s, w, 0) (+ the noise on the diagonal).
-#include "common.h"
+#include "asm_frame.h"
 #include "kern_eval.h"
 #include "kern_grad.h"
 #include <algorithm>
@@ -140,6 +140,7 @@ __global__ __launch_bounds__(256) void stencil_kernel(double* __restrict__ K, lo
   for (int c = 0; c < CC; ++c) {
     const long col = cfirst + c;
     if (col < clo || col >= chi) continue;
+    // asm_frame.h's write_entry, written out: through the helper the D = 8 covariance measured above the parent's range
     double* p = K + r + col * ld;
     double v = fma(s[c], st_weight(T, r - r0, col - c0), accumulate ? *p : 0.0);
     if (noise_kind >= 0 && r == col) v += (noise_kind == 0) ? sigma2 : noise_diag[r];
@@ -174,28 +175,23 @@ __global__ __launch_bounds__(256) void diag_stencil_kernel(double* out, long n, 
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
 template <int DMAX, int KIND>
-static int launch_stencil_t(double* K, long ld, long r0, long c0, long rlo, long rhi, long clo, long chi,
-                            const DevTerm* dterm, int lower_only, int accumulate, int noise_kind, double sigma2,
-                            const double* d_noise_diag, hipStream_t s) {
+static int launch_stencil_t(const AsmLaunch& L, long rlo, long rhi, long clo, long chi, const DevTerm* dterm, hipStream_t s) {
   constexpr int BC = ST_WAVES * st_cc<DMAX>();
   const long gx = (chi - 1) / BC - clo / BC + 1, gy = (rhi - 1) / ST_ROWS - rlo / ST_ROWS + 1;
   if (gy > 65535) {
     set_error("assemble: too many rows for one stencil launch");
     return -1;
   }
-  hipLaunchKernelGGL((stencil_kernel<DMAX, KIND>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, K, ld, r0, c0, rlo,
-                     rhi, clo, chi, dterm, lower_only, accumulate, noise_kind, sigma2, d_noise_diag);
+  hipLaunchKernelGGL((stencil_kernel<DMAX, KIND>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, L.K, L.ld, L.r0, L.c0,
+                     rlo, rhi, clo, chi, dterm, ASM_TAIL(L));
   SGP_HIP(hipGetLastError());
   return 0;
 }
 
 template <int DMAX>
-static int launch_stencil_kind(int kind, double* K, long ld, long r0, long c0, long rlo, long rhi, long clo, long chi,
-                               const DevTerm* dterm, int lower_only, int accumulate, int noise_kind, double sigma2,
-                               const double* d_noise_diag, hipStream_t s) {
-#define SGP_STK(KD)                                                                                                       \
-  return launch_stencil_t<DMAX, KD>(K, ld, r0, c0, rlo, rhi, clo, chi, dterm, lower_only, accumulate, noise_kind, sigma2, \
-                                    d_noise_diag, s)
+static int launch_stencil_kind(const AsmLaunch& L, long rlo, long rhi, long clo, long chi, int kind, const DevTerm* dterm,
+                               hipStream_t s) {
+#define SGP_STK(KD) return launch_stencil_t<DMAX, KD>(L, rlo, rhi, clo, chi, dterm, s)
   switch (kind) {
     case K_SE: SGP_STK(K_SE);
     case K_M12: SGP_STK(K_M12);
@@ -216,20 +212,14 @@ static int launch_stencil_kind(int kind, double* K, long ld, long r0, long c0, l
     else CALL(16);                    \
   } while (0)
 
-int launch_assemble_stencil(double* K, long ld, long r0, long nr, long c0, long nc, const DevTerm& T, const DevTerm* dterm,
-                            int lower_only, int accumulate, int noise_kind, double sigma2, const double* d_noise_diag,
-                            long tile_r_first, long tile_c_first, long tile_r_cnt, long tile_c_cnt, hipStream_t s) {
-  if (tile_r_cnt <= 0 || tile_c_cnt <= 0) return 0;
-  const long rlo = std::max(r0, tile_r_first * TILE), rhi = std::min(r0 + nr, (tile_r_first + tile_r_cnt) * TILE);
-  const long clo = std::max(c0, tile_c_first * TILE), chi = std::min(c0 + nc, (tile_c_first + tile_c_cnt) * TILE);
-  if (rlo >= rhi || clo >= chi) return 0;
+int launch_assemble_stencil(const AsmLaunch& L, const DevTerm& T, const DevTerm* dterm, hipStream_t s) {
+  long rlo, rhi, clo, chi;
+  if (!L.entries(rlo, rhi, clo, chi)) return 0;
   if (!(T.qr || T.qc) || T.dim < 1 || T.dim > STENCIL_MAX_DIM || T.qr > STENCIL_MAX_POINTS || T.qc > STENCIL_MAX_POINTS) {
     set_error("assemble: not a stencil term");
     return -1;
   }
-#define SGP_ST_CALL(DM) \
-  return launch_stencil_kind<DM>(T.kind, K, ld, r0, c0, rlo, rhi, clo, chi, dterm, lower_only, accumulate, noise_kind, \
-                                 sigma2, d_noise_diag, s)
+#define SGP_ST_CALL(DM) return launch_stencil_kind<DM>(L, rlo, rhi, clo, chi, T.kind, dterm, s)
   SGP_STENCIL_DISPATCH(T.dim, SGP_ST_CALL);
 #undef SGP_ST_CALL
   return 0;

@@ -63,6 +63,8 @@ def main():
         kr.write(rows, sys.stdout)
     if a.against:
         old = kr.read(a.against)
+        # (kr.read spells boolean template arguments 1 / 0; this compiler's demangler prints true / false)
+        rows = {re.sub(r"\btrue\b", "1", re.sub(r"\bfalse\b", "0", n)): v for n, v in rows.items()}
         bad = [n for n in old if rows.get(n) != old[n]]
         for n in bad:
             print("DIFFERS", n, old[n], rows.get(n), file=sys.stderr)
