@@ -270,8 +270,8 @@ class FakeKprodGrad:
     def sgp_logpdf_grad_param_xs(self, ctx, spec, mean, kind, noise, y, lp, gy, gm, gn, gc, gs, gp, gin, grs):
         s = self._spec(spec)
         n = s.N
-        assert kind == L.NOISE_SCALAR
-        Cm = kn.np_spec_matrix(s) + noise[0] * np.eye(n)
+        assert kind in (L.NOISE_SCALAR, L.NOISE_DIAG)
+        Cm = kn.np_spec_matrix(s) + (np.diag(_vec(noise, n)) if kind == L.NOISE_DIAG else noise[0] * np.eye(n))
         delta = _vec(y, n) - (_vec(mean, n) if mean else 0.0)
         Li = sla.solve_triangular(np.linalg.cholesky(Cm), np.eye(n), lower=True)      # (the library's route: C^-1 = L^-T L^-1)
         Ci = Li.T @ Li
@@ -280,7 +280,10 @@ class FakeKprodGrad:
         lp[0] = np_logpdf(Cm, delta)
         _vec(gy, n)[:] = -al
         _vec(gm, n)[:] = al
-        gn[0] = np.trace(G)
+        if kind == L.NOISE_DIAG:
+            _vec(gn, n)[:] = np.diag(G)
+        else:
+            gn[0] = np.trace(G)
         for dst, src in zip((gc, gs, gp), kn.np_contract(s, G)):
             self._put_terms(dst, src, s.n_terms)
         ev = kg.np_input_grads(s, G)
@@ -302,17 +305,21 @@ class FakeKprodGrad:
                             gcz, gsz, gpz, gcx, gsx, gpx, gin_zz, gin_xz, grs_zz, grs_xz, gcs_xz):
         sz, sx = self._spec(zz), self._spec(xz)
         M, N = sz.N, sx.N
-        assert nk == L.NOISE_SCALAR and zk == L.NOISE_SCALAR
+        assert nk == L.NOISE_SCALAR and zk in (L.NOISE_SCALAR, L.NOISE_DENSE)
+        Sz = _mat(z_noise, M, M, M) if zk == L.NOISE_DENSE else z_noise[0] * np.eye(M)
         s2 = noise_x[0]
         v = _vec(var_x, N)
         resid = _vec(y, N) - (_vec(mean_x, N) if mean_x else 0.0)
-        elbo_out[0], (dKzz, dKxz, dy, dsy) = titsias(kn.np_spec_matrix(sz) + z_noise[0] * np.eye(M), kn.np_spec_matrix(sx), v,
+        elbo_out[0], (dKzz, dKxz, dy, dsy) = titsias(kn.np_spec_matrix(sz) + Sz, kn.np_spec_matrix(sx), v,
                                                     resid, s2, cotangents=True)
         _vec(gy, N)[:] = dy
         _vec(gm, N)[:] = -dy
         gn[0] = dsy
         _vec(gv, N)[:] = -0.5 / s2
-        gzn[0] = np.trace(dKzz)
+        if zk == L.NOISE_DENSE:
+            _mat(gzn, M, M, M)[:, :] = dKzz
+        else:
+            gzn[0] = np.trace(dKzz)
         for dsts, s, G in (((gcz, gsz, gpz), sz, dKzz), ((gcx, gsx, gpx), sx, dKxz)):
             for dst, src in zip(dsts, kn.np_contract(s, G)):
                 self._put_terms(dst, src, s.n_terms)

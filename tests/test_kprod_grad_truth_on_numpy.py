@@ -352,7 +352,7 @@ def test_recorded_float64_figures_are_reproduced_to_a_factor_two():
 
 
 # ---- the GPU file's bodies on the NumPy double, under SELF_MARGIN ----------------------------------------------------------------
-# FakeKprodGrad takes a scalar Sigma_y and a scalar Sigma_z and writes every output: the two cases with a dense Sigma_z and
+# the bodies run here with a scalar Sigma_z, and FakeKprodGrad writes every output: the two cases with a dense Sigma_z and
 # the NULL-output calls are not covered
 DOUBLE_ELBO_CASES = [c for c in GK.ELBO_CASES if c.z_noise == "scalar"]
 
