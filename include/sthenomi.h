@@ -98,7 +98,38 @@ enum {
    * entry point, every multi-GPU context. */
   SGP_DERIV_SE = SGP_SE + 32,             /* 32 */
   SGP_DERIV_MATERN32 = SGP_MATERN32 + 32, /* 34 */
-  SGP_DERIV_MATERN52 = SGP_MATERN52 + 32  /* 35 */
+  SGP_DERIV_MATERN52 = SGP_MATERN52 + 32, /* 35 */
+  /* The Gibbs kind: a squared-exponential whose lengthscale depends on the point.  A class of its own (gibbs.hip): neither a
+   * product-path kind nor a derivative kind; 36 .. 39 stay no kinds.
+   *
+   * A term of this kind reads points of dimension D + 1, D in 1 .. 15: coordinates 0 .. D - 1 are the location, coordinate D is
+   * the lengthscale l > 0 at that point, evaluated by the caller.  With s = |x - y|^2 over the D location coordinates,
+   * q = lx^2 + ly^2, c = 2 lx ly / q in (0, 1] and p = param, an integer in 1 .. 16:
+   *     K_ij = coef rs_i cs_j c^(p/2) exp(-s / q)
+   * p = 1 is KernelFunctions' GibbsKernel, (sqrt(lx ly) / l) SqExponentialKernel with lengthscale l = hypot(lx, ly) / sqrt(2).
+   * p = D is the form of Paciorek and Schervish: it is the one that is positive definite in D dimensions; a p below D is not
+   * in general.  c^(p/2) is sqrt(c) multiplied p times: no pow and no log on the device.
+   *
+   * Exact values: a pair that coincides in all D + 1 coordinates gives exactly coef rs_i cs_j (as (coef rs_i) cs_j); an
+   * exponential that underflowed gives an exact 0, whatever q holds; sgp_kernelmatrix_diag equals the diagonal of
+   * sgp_kernelmatrix bit for bit.  The error model (docs/03_kernels.md, 3.2g) holds for l in [2^-500, 2^500], where l^2 and
+   * q neither overflow nor lose bits to underflow: l^2 is formed once per point, and one reciprocal of q serves c and the
+   * exponent.  An l that is not positive and finite gives NaN or 0 entries; the host evaluates and checks l.
+   *
+   * Gradients: grad_coef as for every kind.  grad_inscale: the D location coordinates of both sides scaled by g with l held
+   * as uploaded, -2 (s / q) K_ij at g = 1.  grad_inputs of sgp_logpdf_grad_x (D + 1 rows per point, G the cotangent):
+   *     rows 0 .. D - 1 of the row input, column i:  sum_j G_ij K_ij (-2 (x_i - y_j) / q)
+   *     row D:                                         sum_j G_ij K_ij (p / 2 (1 / lx - 2 lx / q) + 2 s lx / q^2)
+   * and the mirror image for the column side.  Row D is what the parameters of l(.) are trained with.
+   *
+   * Refused by dspec creation, every text naming "Gibbs": a param that is no integer in 1 .. 16 (NaN included); points of
+   * dimension < 2 or > 16; SGP_KIND_TIMES_PREV on the term or on its successor; reserved != 0; a multi-GPU context.
+   * Taken by every fp64 operator of a single-GPU context that goes through the common assembly (as the derivative kinds),
+   * by sgp_logpdf_grad / _batch / _pool for grad_coef and grad_inscale, and by sgp_logpdf_grad_x.  Refused, with a message
+   * that names "Gibbs": sgp_logpdf_grad_xs with scale outputs, sgp_kernelmatrix_diag_grad*, sgp_elbo_grad*, the *_param,
+   * *_conv, *_stencil and *_stencil_wo families, the predict-gradient entry points, every *_f32 entry point, every multi-GPU
+   * context. */
+  SGP_GIBBS = SGP_SE + 40                 /* 40 */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -130,8 +161,8 @@ typedef struct {
                          sgp_stencil_register (include/sthenomi_stencil.h, libsthenomi_stencil.so)      */
   double coef;        /* product of scalar scales (may be negative)                      */
   double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu;
-                         SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; SGP_DERIV_*: 17 a + b; ignored by the
-                         other kinds */
+                         SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; SGP_DERIV_*: 17 a + b; SGP_GIBBS: p;
+                         ignored by the other kinds */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

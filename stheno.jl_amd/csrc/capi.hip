@@ -45,6 +45,7 @@ using namespace sgp;
 #define REFUSE_KPROD_MULTI(ctx, sp)                                                                          \
   do {                                                                                                       \
     CHECK_ARG(!((ctx)->multi && spec_has_deriv(sp)), sgp::DERIV_REFUSAL_MULTI); /* (deriv.hip: likewise) */  \
+    CHECK_ARG(!((ctx)->multi && spec_has_gibbs(sp)), sgp::GIBBS_REFUSAL_MULTI); /* (gibbs.hip: likewise) */  \
     CHECK_ARG(!((ctx)->multi && spec_has_kprod(sp)),                                                         \
               "spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context");    \
   } while (0)
@@ -363,6 +364,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   // terms of the derivative kinds (include/sthenomi.h: SGP_DERIV_*): a class of their own (deriv.hip), validated against a table
   // of its own (deriv_kinds.h) -- the product path's table does not know them
   std::vector<char> is_dv(std::max(1, nterms), 0);
+  // terms of the Gibbs kind (include/sthenomi.h: SGP_GIBBS): likewise (gibbs.hip, gibbs_kinds.h)
+  std::vector<char> is_gb(std::max(1, nterms), 0);
   std::vector<size_t> nuc_off(std::max(1, nterms), (size_t)-1);   // SGP_MATERN_NU: the term's constants of nu (kprod.hip)
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
@@ -371,7 +374,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
       for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t) {
         const sgp_term& T = sp->terms[t];
         if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) ||
-            !(kp_kind_known(T.kind & 0xff) || deriv_kind_known(T.kind & 0xff)))
+            !(kp_kind_known(T.kind & 0xff) || deriv_kind_known(T.kind & 0xff) || gibbs_kind_known(T.kind & 0xff)))
           return fail("spec: unknown kernel kind");
         const bool cont = (T.kind & SGP_KIND_TIMES_PREV) != 0;
         const bool next_cont = t + 1 < sp->term_ptr[p + 1] && sp->terms[t + 1].kind >= 0 &&
@@ -384,7 +387,15 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
             if (const char* refusal = deriv_param_refusal(T.param, (long)sp->inputs[T.row_input].dim)) return fail(refusal);
           ++ds->n_deriv;
         }
-        is_kp[t] = !is_dv[t] && (cont || next_cont || (T.kind & 0xff) > SGP_CONST);
+        is_gb[t] = gibbs_kind_known(T.kind & 0xff);
+        if (is_gb[t]) {
+          if (cont || next_cont) return fail(GIBBS_REFUSAL_CHAIN);
+          if (T.reserved) return fail(GIBBS_REFUSAL_RESERVED);
+          if (T.row_input >= 0 && T.row_input < sp->n_inputs)
+            if (const char* refusal = gibbs_param_refusal(T.param, (long)sp->inputs[T.row_input].dim)) return fail(refusal);
+          ++ds->n_gibbs;
+        }
+        is_kp[t] = !is_dv[t] && !is_gb[t] && (cont || next_cont || (T.kind & 0xff) > SGP_CONST);
         if (is_kp[t]) {
           if (cont && t == sp->term_ptr[p])
             return fail("spec: product chain: a continuation (SGP_KIND_TIMES_PREV) cannot be the first term of a block pair");
@@ -457,12 +468,13 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           cs_len[t] = ds->col_len[J];
           cs_off[t] = place(sizeof(double) * (size_t)cs_len[t]);
         }
-        if (!T.reserved && !is_kp[t] && !is_dv[t]) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
+        if (!T.reserved && !is_kp[t] && !is_dv[t] && !is_gb[t]) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
       }
     }
   if (ds->n_kprod && (ctx->multi || ctx->multi_rank))
     return fail("spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context");
   if (ds->n_deriv && (ctx->multi || ctx->multi_rank)) return fail(DERIV_REFUSAL_MULTI);
+  if (ds->n_gibbs && (ctx->multi || ctx->multi_rank)) return fail(GIBBS_REFUSAL_MULTI);
   const size_t terms_off = place(sizeof(DevTerm) * (size_t)std::max(1, nterms));
   // ---- one cached device block, one pinned staging buffer
   char* d_base = (char*)pool_alloc(ctx, total);
@@ -497,11 +509,12 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
-      // plain | patch | stencil | derivative | product chains within every pair (the caller's order when the spec has none of
-      // the last four; chains and the groups of derivative terms stay contiguous and in the caller's order: the passes below
-      // are stable)
+      // plain | patch | stencil | derivative | Gibbs | product chains within every pair (the caller's order when the spec has
+      // none of the last five; chains and the groups of derivative and Gibbs terms stay contiguous and in the caller's order:
+      // the passes below are stable)
       auto cls = [&](int t) {
-        if (is_kp[t]) return 4;
+        if (is_kp[t]) return 5;
+        if (is_gb[t]) return 4;
         if (is_dv[t]) return 3;
         const uint32_t code = (uint32_t)sp->terms[t].reserved;
         if (!code) return 0;
@@ -509,14 +522,15 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
         return ctx->conv_geoms[id - 1].st > 0 ? 2 : 1;
       };
       std::vector<int> order;
-      int ncls[5] = {0, 0, 0, 0, 0};
-      for (int pass = 0; pass < 5; ++pass)
+      int ncls[6] = {0, 0, 0, 0, 0, 0};
+      for (int pass = 0; pass < 6; ++pass)
         for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t)
           if (cls(t) == pass) order.push_back(t), ++ncls[pass];
       ds->pair_nplain.push_back(ncls[0]);
       ds->pair_npatch.push_back(ncls[1]);
       ds->pair_nderiv.push_back(ncls[3]);
-      ds->pair_nkprod.push_back(ncls[4]);
+      ds->pair_ngibbs.push_back(ncls[4]);
+      ds->pair_nkprod.push_back(ncls[5]);
       for (size_t k = 0; k < order.size(); ++k) {
         const int t = order[k], pos = sp->term_ptr[p] + (int)k;
         const sgp_term& T = sp->terms[t];
@@ -614,7 +628,7 @@ extern "C" int sgp_dspec_destroy(sgp_dspec* ds) {
 // which terms of pair p are what (spec_segments.h), from the counts dspec_create fills for every spec
 static inline PairSegs pair_segments(const sgp_dspec* ds, int p) {
   return pair_segments(ds->term_ptr.data(), ds->pair_nplain.data(), ds->pair_npatch.data(), ds->pair_nderiv.data(),
-                       ds->pair_nkprod.data(), p);
+                       ds->pair_ngibbs.data(), ds->pair_nkprod.data(), p);
 }
 // the chain whose head sits at device position t: one past its last factor, and its DMAX
 static inline int chain_end(const sgp_dspec* ds, int t, int t1) { return chain_end(ds->h_terms.data(), t, t1); }
@@ -640,8 +654,8 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       L.r0 = r0, L.nr = nr, L.c0 = c0, L.nc = nc, L.diag = ds->symmetric && I == J;
       L.r_first = trf, L.c_first = tcf, L.r_cnt = trl - trf, L.c_cnt = tcl - tcf;
       int p = I * ds->ncb + J;
-      // plain | patch (conv.hip) | stencil (stencil.hip) | derivative (deriv.hip) | chains (kprod.hip)
-      const auto [t0, tp, ts, tk, t1, td] = pair_segments(ds, p);
+      // plain | patch (conv.hip) | stencil (stencil.hip) | derivative (deriv.hip) | Gibbs (gibbs.hip) | chains (kprod.hip)
+      const auto [t0, tp, ts, tk, t1, td, tg] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = assemble_terms_per_launch(dmax);  // terms per launch: <= 64 KiB of LDS
       L.first = true;
@@ -662,10 +676,16 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
         L.first = t == t0;
         CHECK_RC(launch_assemble_stencil(L, ds->h_terms[t], ds->d_terms + t, s));
       }
-      for (int t = td; t < tk;) {   // one group per launch: one exponential per point pair for all its terms (deriv.hip)
-        const int cnt = deriv_group(ds->h_terms.data(), t, tk);
+      for (int t = td; t < tg;) {   // one group per launch: one exponential per point pair for all its terms (deriv.hip)
+        const int cnt = deriv_group(ds->h_terms.data(), t, tg);
         L.first = t == t0;
         CHECK_RC(launch_assemble_deriv(L, ds->h_terms.data() + t, ds->d_terms + t, cnt, s));
+        t += cnt;
+      }
+      for (int t = tg; t < tk;) {   // likewise (gibbs.hip)
+        const int cnt = gibbs_group(ds->h_terms.data(), t, tk);
+        L.first = t == t0;
+        CHECK_RC(launch_assemble_gibbs(L, ds->h_terms.data() + t, ds->d_terms + t, cnt, s));
         t += cnt;
       }
       for (int t = tk; t < t1;) {   // whole chains per launch, as many as fit its LDS (kprod.hip: kprod_group)
@@ -1618,7 +1638,7 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag: block lengths differ");
     int p = I * ds->ncb + I;
-    const auto [t0, tp, ts, tk, t1, td] = pair_segments(ds, p);
+    const auto [t0, tp, ts, tk, t1, td, tg] = pair_segments(ds, p);
     if (tp < ts) {   // patch terms (conv.hip), in one launch with the plain terms in front of them
       int max_d = 1, d_all = -1, max_px = 1;
       for (int t = tp; t < ts; ++t) {
@@ -1637,9 +1657,14 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
       for (int t = ts; t < td; ++t) max_dim = std::max(max_dim, ds->h_terms[t].dim);
       CHECK_RC(launch_diag_stencil(d_out + ds->row_off[I], ds->row_len[I], ds->d_terms + ts, td - ts, max_dim, s));
     }
-    for (int t = td; t < tk;) {   // derivative terms, in the groups of the matrix assembly: the same sums
-      const int cnt = deriv_group(ds->h_terms.data(), t, tk);
+    for (int t = td; t < tg;) {   // derivative terms, in the groups of the matrix assembly: the same sums
+      const int cnt = deriv_group(ds->h_terms.data(), t, tg);
       CHECK_RC(launch_diag_deriv(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
+      t += cnt;
+    }
+    for (int t = tg; t < tk;) {   // Gibbs terms, likewise
+      const int cnt = gibbs_group(ds->h_terms.data(), t, tk);
+      CHECK_RC(launch_diag_gibbs(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
       t += cnt;
     }
     for (int t = tk; t < t1;) {   // product chains, in the launch groups of the matrix assembly: the same sums
@@ -1911,9 +1936,9 @@ struct StencilWo {
 // caller says it carries them (leave.kprod: the cores set it where their entry points take chains).
 // dgp (NULL: not asked for): d / d param per term, which for the plain terms is non-zero for SGP_CONST alone -- those run
 // through the chain kernel once more, as chains of length one, for that entry, between the stencil terms and the chains.
-static GradLeave pool_leave() {   // what sgp_logpdf_grad_batch / _pool carry beyond the plain terms: derivative terms
+static GradLeave pool_leave() {   // what sgp_logpdf_grad_batch / _pool carry beyond the plain terms: derivative and Gibbs terms
   GradLeave l;
-  l.deriv = true;
+  l.deriv = l.gibbs = true;
   return l;
 }
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr, long n_tc,
@@ -1924,7 +1949,9 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
             "gradient contraction: product chains and the RQ / LINEAR kinds are not supported here");
   CHECK_ARG(leave.deriv || !ds->n_deriv, "gradient contraction: derivative terms are not supported here");
   long need = std::max<long>(1, n_tr * n_tc) * ((ds->n_kprod || dgp) ? 24 : 16);
+  CHECK_ARG(leave.gibbs || !ds->n_gibbs, "gradient contraction: Gibbs terms are not supported here");
   if (ds->n_deriv) need = std::max(need, grad_deriv_partials(n_tr, n_tc));
+  if (ds->n_gibbs) need = std::max(need, grad_gibbs_partials(n_tr, n_tc));
   for (int p = 0; p < ds->nrb * ds->ncb; ++p) {   // the partial sums of the largest patch or stencil term
     const int I = p / ds->ncb, J = p % ds->ncb;
     const PairSegs g = pair_segments(ds, p);
@@ -1940,7 +1967,7 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       long r0 = ds->row_off[I], nr = ds->row_len[I], c0 = ds->col_off[J], nc = ds->col_len[J];
       long trf = r0 / TILE, trl = (r0 + nr - 1) / TILE + 1, tcf = c0 / TILE, tcl = (c0 + nc - 1) / TILE + 1;
       int p = I * ds->ncb + J;
-      const auto [t0, tp, ts, tk, t1, td] = pair_segments(ds, p);
+      const auto [t0, tp, ts, tk, t1, td, tg] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = std::min(8, std::max(1, 64 / dmax));
       for (int t = t0; t < tp; t += per) {
@@ -1953,9 +1980,15 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       for (int t = ts; t < td; ++t)
         CHECK_RC(launch_grad_stencil(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, dpart.p, dgc + t, dgs + t,
                                      s));
-      for (int t = td; t < tk;) {   // derivative terms, one group per launch (deriv.hip)
-        const int cnt = deriv_group(ds->h_terms.data(), t, tk);
+      for (int t = td; t < tg;) {   // derivative terms, one group per launch (deriv.hip)
+        const int cnt = deriv_group(ds->h_terms.data(), t, tg);
         CHECK_RC(launch_grad_deriv(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, trf, tcf, trl - trf,
+                                   tcl - tcf, dpart.p, dgc + t, dgs + t, s));
+        t += cnt;
+      }
+      for (int t = tg; t < tk;) {   // Gibbs terms, likewise (gibbs.hip)
+        const int cnt = gibbs_group(ds->h_terms.data(), t, tk);
+        CHECK_RC(launch_grad_gibbs(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, trf, tcf, trl - trf,
                                    tcl - tcf, dpart.p, dgc + t, dgs + t, s));
         t += cnt;
       }
@@ -2064,6 +2097,7 @@ static int input_pass(const sgp_dspec* ds, const InputPass& q, hipStream_t s) {
   TermGradBufs& b = *q.bufs;
   if (!b.asked()) return 0;
   CHECK_ARG(!ds->n_deriv, "input-point and scale gradients through derivative terms are not supported");
+  CHECK_ARG(!ds->n_gibbs || !(b.want[0] || b.want[1]), "scale gradients through Gibbs terms are not supported");
   const bool points = b.want_x != nullptr;
   const double w = q.symmetric ? 2.0 : 1.0;
   for (int I = 0; I < ds->nrb; ++I)
@@ -2096,6 +2130,15 @@ static int input_pass(const sgp_dspec* ds, const InputPass& q, hipStream_t s) {
         if (!q.symmetric)
           CHECK_RC(launch_grad_stencil_points(q.Gm, q.ldg, 1, q.alpha, c0, nc, r0, nr, T, 1, 1.0,
                                               b.input(ds->term_col_input[t]), s));
+      }
+      // a group of Gibbs terms: one launch, lengthscale row included (gibbs.hip).  Only symmetric cotangents arrive here
+      // (sgp_logpdf_grad_x; the ELBO gradients refuse the kind), where the row side of a pair and of its mirror cover both roles
+      for (int t = g.tg; points && t < g.tk;) {
+        const int cnt = gibbs_group(ds->h_terms.data(), t, g.tk);
+        CHECK_ARG(q.symmetric, "input-point gradients through Gibbs terms take a symmetric cotangent only");
+        CHECK_RC(launch_grad_gibbs_inputs(q.Gm, 1, q.ldg, q.alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, cnt, w,
+                                          b.input(ds->term_row_input[t]), s));
+        t += cnt;
       }
       for (int t = g.tk; t < g.t1;) {   // a chain: every factor's input and the head's scale in one launch per side (kprod.hip)
         const int e = chain_end(ds, t, g.t1), cdmax = chain_dmax(ds, t, e);
@@ -2134,6 +2177,11 @@ static int logpdf_grad_core(sgp_ctx* ctx, const LogpdfGradArgs& a) {
             "sgp_logpdf_grad_x / _xs / _param / _conv / _stencil / _stencil_wo: input-point, scale, parameter, patch and stencil "
             "gradients through derivative terms are not supported: sgp_logpdf_grad returns grad_coef and grad_inscale");
   CHECK_ARG(!(ctx->multi && spec_has_deriv(a.spec)), DERIV_REFUSAL_MULTI);
+  // Gibbs terms (gibbs.hip): sgp_logpdf_grad and sgp_logpdf_grad_x (and _xs without scale outputs)
+  CHECK_ARG(a.leave.gibbs || !spec_has_gibbs(a.spec),
+            "sgp_logpdf_grad_xs with scale outputs / _param / _conv / _stencil / _stencil_wo: scale, parameter, patch and stencil "
+            "gradients through Gibbs terms are not supported: sgp_logpdf_grad_x returns grad_coef, grad_inscale and grad_inputs");
+  CHECK_ARG(!(ctx->multi && spec_has_gibbs(a.spec)), GIBBS_REFUSAL_MULTI);
   CHECK_RC(check_grad_leave(ctx, "sgp_logpdf_grad", a.leave, a.spec));
   CHECK_ARG(!(a.grad_inputs || a.grad_rowscale) || a.leave.kprod || a.leave.stencil || !spec_has_kprod(a.spec),
             "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
@@ -2282,6 +2330,7 @@ extern "C" int sgp_logpdf_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const 
   LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                                       grad_inscale);
   a.grad_inputs = grad_inputs, a.grad_rowscale = grad_rowscale;
+  a.leave.gibbs = grad_rowscale == nullptr;   // (Gibbs terms: the input points, no scale outputs)
   return drv_logpdf_grad(ctx, a);
 }
 
@@ -2292,6 +2341,7 @@ extern "C" int sgp_logpdf_grad(sgp_ctx* ctx, const sgp_cov_spec* spec, const dou
   LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                                       grad_inscale);
   a.leave.deriv = true;   // (this entry point alone carries derivative terms)
+  a.leave.gibbs = true;
   return drv_logpdf_grad(ctx, a);
 }
 
@@ -2303,6 +2353,7 @@ extern "C" int sgp_logpdf_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const d
   LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                                       grad_inscale);
   a.grad_inputs = grad_inputs;
+  a.leave.gibbs = true;   // (Gibbs terms: D + 1 rows per point, the last the lengthscale's)
   return drv_logpdf_grad(ctx, a);
 }
 
@@ -3746,6 +3797,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradSha
   CHECK_ARG(a.noise_kind == SGP_NOISE_SCALAR || a.noise_kind == SGP_NOISE_DIAG,
             "sgp_elbo_grad: Sigma_y must be isotropic or diagonal (as in AbstractGPs.elbo)");
   CHECK_ARG(a.z_noise_kind >= SGP_NOISE_SCALAR && a.z_noise_kind <= SGP_NOISE_DENSE, "sgp_elbo_grad: bad Sigma_z kind");
+  CHECK_ARG(!spec_has_gibbs(a.zz) && !spec_has_gibbs(a.xz),
+            "sgp_elbo_grad: gradients of the ELBO through Gibbs terms are not supported");
   CHECK_ARG(!spec_has_deriv(a.zz) && !spec_has_deriv(a.xz),
             "sgp_elbo_grad: gradients of the ELBO through derivative terms are not supported");
   CtxScope scope(ctx);
@@ -4057,6 +4110,8 @@ static int diag_grad_core(sgp_ctx* ctx, const DiagGradArgs& a) {
   // a.leave.stencil: sgp_kernelmatrix_diag_grad_stencil, include/sthenomi_stencil_grad.h)
   CHECK_ARG(ctx && a.spec && a.w && (a.leave.kprod || (a.grad_coef && a.grad_inscale)),
             "sgp_kernelmatrix_diag_grad: NULL argument");
+  CHECK_ARG(!spec_has_gibbs(a.spec),
+            "sgp_kernelmatrix_diag_grad: gradients of the diagonal through Gibbs terms are not supported");
   CHECK_ARG(!spec_has_deriv(a.spec),
             "sgp_kernelmatrix_diag_grad: gradients of the diagonal through derivative terms are not supported");
   CHECK_RC(check_grad_leave(ctx, "sgp_kernelmatrix_diag_grad", a.leave, a.spec));

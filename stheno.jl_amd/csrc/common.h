@@ -229,6 +229,21 @@ int launch_grad_deriv(const double* Kinv, long ldk, const double* alpha, long r0
                       const DevTerm* h_terms, const DevTerm* d_terms, int nterms, long trf, long tcf, long trc, long tcc,
                       double* partials, double* out_coef, double* out_scale, hipStream_t s);
 
+// gibbs.hip: the Gibbs kind (include/sthenomi.h: SGP_GIBBS), a term class of its own.  A launch carries ONE group of a pair's
+// Gibbs terms (gibbs_kinds.h: gibbs_group -- the same points and scale vectors; the terms differ in (coef, param)).  The first
+// four as their derivative counterparts above
+int launch_assemble_gibbs(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, hipStream_t s);
+int launch_diag_gibbs(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
+                      hipStream_t s);
+long grad_gibbs_partials(long trc, long tcc);
+int launch_grad_gibbs(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
+                      const DevTerm* h_terms, const DevTerm* d_terms, int nterms, long trf, long tcf, long trc, long tcc,
+                      double* partials, double* out_coef, double* out_scale, hipStream_t s);
+// gx (T.dim x nr, packed) += scale * d / d(points of T's row side) of sum_ij G_ij (the group)_ij, the lengthscale row included;
+// G and its strides as launch_grad_inputs.  T: the group's first term, sides swapped for the column side; d_terms: the group
+int launch_grad_gibbs_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                             const DevTerm& T, const DevTerm* d_terms, int nterms, double scale, double* gx, hipStream_t s);
+
 void set_error(const std::string& s);
 
 #define SGP_HIP(expr)                                                                     \

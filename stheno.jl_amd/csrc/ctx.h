@@ -6,6 +6,7 @@
 #include "../../include/sthenomi.h"
 #include "../../include/sthenomi_bench.h"
 #include "deriv_kinds.h"
+#include "gibbs_kinds.h"
 
 #include <mutex>
 #include <vector>
@@ -57,6 +58,7 @@ struct GradLeave {
   bool patch = false;     // patch (convolutional) terms (include/sthenomi_conv_grad.h)
   bool stencil = false;   // stencil terms (include/sthenomi_stencil_grad.h, sthenomi_stencil_wo.h); set together with patch
   bool deriv = false;     // derivative terms (include/sthenomi.h: SGP_DERIV_*): sgp_logpdf_grad and its batch / pool forms alone
+  bool gibbs = false;     // Gibbs terms (include/sthenomi.h: SGP_GIBBS): those, and sgp_logpdf_grad_x / _xs without scale outputs
 };
 // sgp_logpdf_grad / _x / _xs / _param / _param_xs / _conv / _stencil / _stencil_wo
 struct LogpdfGradArgs {
@@ -434,13 +436,23 @@ inline bool spec_has_deriv(const sgp_cov_spec* sp) {
   return false;
 }
 
+// a term of the Gibbs kind (include/sthenomi.h: SGP_GIBBS; gibbs.hip): likewise
+inline bool term_is_gibbs(const sgp_term& T) { return T.kind >= 0 && sgp::gibbs_kind_known(T.kind & 0xff); }
+inline bool spec_has_gibbs(const sgp_cov_spec* sp) {
+  if (!sp || !sp->term_ptr || !sp->terms) return false;
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t)
+    if (term_is_gibbs(sp->terms[t])) return true;
+  return false;
+}
+
 // a term of a product chain (include/sthenomi_kprod.h) or of a kind only kprod.hip evaluates (the derivative kinds are
-// deriv.hip's)
+// deriv.hip's, the Gibbs kind gibbs.hip's)
 inline bool spec_has_kprod(const sgp_cov_spec* sp) {
   if (!sp || !sp->term_ptr || !sp->terms) return false;
   const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
   for (int t = 0; t < n; ++t)
-    if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || ((sp->terms[t].kind & 0xff) > SGP_CONST && !term_is_deriv(sp->terms[t])))
+    if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || ((sp->terms[t].kind & 0xff) > SGP_CONST && !term_is_deriv(sp->terms[t]) && !term_is_gibbs(sp->terms[t])))
       return true;
   return false;
 }
@@ -474,5 +486,8 @@ struct sgp_dspec {
   // order, which keeps the terms of a group next to each other; n_deriv == 0: none
   std::vector<int> pair_nderiv;
   int n_deriv = 0;
+  // Gibbs terms (gibbs.hip): between the derivative terms and the chains of their pair, likewise; n_gibbs == 0: none
+  std::vector<int> pair_ngibbs;
+  int n_gibbs = 0;
   std::vector<int> term_src;           // index in the caller's spec->terms of the term at each device position
 };

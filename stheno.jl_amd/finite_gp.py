@@ -65,6 +65,14 @@ def _refuse_deriv(what, *specs):
                                   "returns d_coef and d_inscale of a model with derivative(f)")
 
 
+def _refuse_gibbs(what, *specs):
+    """`what` through Gibbs terms (GibbsKernel; include/sthenomi.h: SGP_GIBBS) is not implemented (the library refuses it
+    too): logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, the input gradients and d_lengthscale"""
+    if any(sp.has_gibbs for sp in specs):
+        raise NotImplementedError(f"{what} through Gibbs covariance terms (GibbsKernel) is not supported: "
+                                  "logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, inputs and d_lengthscale")
+
+
 def _is_prior(f):
     return isinstance(f, (GPPP, SthenoAbstractGP))
 
@@ -259,6 +267,7 @@ def mean_and_var_and_gradient(fx):
         raise NotImplementedError("mean_and_var_and_gradient is not supported on a multi-GPU context (the factor is sharded)")
     cross, pss, ms = _cross_side(f, fx.x)
     _refuse_deriv("mean_and_var_and_gradient", cross, pss)
+    _refuse_gibbs("mean_and_var_and_gradient", cross, pss)
     _refuse_patch_gradient(cross, pss)
     _refuse_product_gradient("mean_and_var_and_gradient", cross, pss)
     if (any(rs is not None for rs in cross.term_row_scale) or any(rs is not None for rs in pss.term_row_scale)
@@ -522,6 +531,7 @@ def logpdf_f32(fx, y):
         raise ValueError("length(y) != length(fx)")
     spec = _prior_spec(fx.f, fx.x)
     _refuse_deriv("logpdf_f32: the fp32 path", spec)
+    _refuse_gibbs("logpdf_f32: the fp32 path", spec)
     if spec.has_stencil:
         raise NotImplementedError("stencil terms have no fp32 path: call logpdf, which runs them in fp64")
     if spec.has_kprod:
@@ -594,6 +604,14 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     sits in the coefficient once per differentiated side, is, with m the number of differentiated sides of the term,
         d / da = (m * coef * d_coef + d_inscale) / a.
 
+    A model with a GibbsKernel (include/sthenomi.h: SGP_GIBBS) is taken with scales=False.  The points its terms read carry the
+    lengthscale l(x) as their last row, so with inputs=True the last row of such an entry of `inputs` is d logpdf / d l(x_i),
+    and the records of Gibbs terms carry it as "d_lengthscale": (row side, column side), length n each -- the cotangent of
+    the view the term reads, summed over every term that reads it (records on one view carry one and the same array: do not
+    add them up); the gradient of a parameter theta of l is sum_i d_lengthscale[i] * d l(x_i) / d theta.  `x` (and the location
+    rows of `inputs`) is then the PARTIAL derivative with l held fixed: the total derivative with respect to a point adds
+    d_lengthscale[i] * grad l(x_i).  Their d_inscale scales the location coordinates alone.
+
     A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
     sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
     index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
@@ -604,7 +622,11 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     _refuse_patch_gradient(spec)
     if inputs or scales:
         _refuse_deriv("logpdf_and_gradient: inputs=True / scales=True", spec)
+        if scales:
+            _refuse_gibbs("logpdf_and_gradient: scales=True", spec)
         _refuse_product_gradient("logpdf_and_gradient: inputs=True / scales=True", spec)
+    if spec.has_kprod:      # (sgp_logpdf_grad_param refuses the kind)
+        _refuse_gibbs("logpdf_and_gradient of a model that also holds a product-path kernel", spec)
     kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
     if spec.has_kprod:
         if _ctx().is_multi:
@@ -627,7 +649,12 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     # fx.x (one (D, n) array per block; blocks sharing one input object get their joint gradient in
     # the first of them)
     xb = chain_input_gradients(spec, gx)[0] if inputs else None
-    return _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs)
+    rec = _grad_record(spec, kind, lp[0], bufs, gx, xb, _scale_records(spec, grs) if scales else None, grs)
+    if inputs and spec.has_gibbs:
+        for r in rec["terms"]:
+            if (int(r["kind"]) & _lib.KIND_MASK) == _lib.GIBBS:
+                r["d_lengthscale"] = (gx[r["row_input"]][-1, :], gx[r["col_input"]][-1, :])
+    return rec
 
 
 def _attach_d_transform(records, spec, gx):
@@ -659,6 +686,7 @@ def _attach_d_transform(records, spec, gx):
 def _refuse_param_family(what, *specs):
     """what the superset family of include/sthenomi_kprod_grad.h does not carry: patch / stencil sides, a multi-GPU context"""
     _refuse_deriv(what, *specs)
+    _refuse_gibbs(what, *specs)
     _refuse_patch_gradient(*specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what}: a product of kernels (the gradients of include/sthenomi_kprod_grad.h) is not "
@@ -692,6 +720,7 @@ def logpdf_and_gradient_param(fx, y, inputs=False, scales=False):
 def _refuse_conv_family(what, *specs):
     """what the entry points of include/sthenomi_conv_grad.h refuse: a multi-GPU context, stencil terms"""
     _refuse_deriv(what, *specs)
+    _refuse_gibbs(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_stencil for sp in specs):
@@ -724,6 +753,7 @@ def _refuse_stencil_family(what, *specs):
     """what the entry points of include/sthenomi_stencil_grad.h refuse: a multi-GPU context; and what their records cannot
     carry"""
     _refuse_deriv(what, *specs)
+    _refuse_gibbs(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_patch or sp.has_stencil for sp in specs) and any(sp.has_kprod for sp in specs):
@@ -1203,6 +1233,7 @@ def posterior_mean_and_var_f32(fx, y, xs):
     cross, _, _ = build_spec(fx.f, xs, fx.f, fx.x)
     pss = _prior_spec(fx.f, xs)
     _refuse_deriv("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
+    _refuse_gibbs("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
     kind, nbuf = _lib._noise_args(fx.noise, len(y))
     if kind == _lib.NOISE_DENSE or not spec.f32_supported() or not cross.f32_supported():
         raise NotImplementedError("beyond the fp32 kernels' limits (dense noise, input dimension > 16, too many terms)")
@@ -1483,6 +1514,7 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
         return elbo_and_gradient(VFE(vfe.finducing), vfe.fobs, fx, inputs=inputs, scales=scales)
     specs, head = _elbo_grad_specs(vfe, fx, y)
     _refuse_deriv("elbo_and_gradient", *specs)
+    _refuse_gibbs("elbo_and_gradient", *specs)
     _refuse_patch_gradient(*specs)
     _refuse_product_gradient("elbo_and_gradient", *specs)
     F = _elbo_grad_frame(specs, head)

@@ -410,7 +410,7 @@ def build_spec(f, x, f2=None, x2=None):
                         if has_dv:
                             _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order)
                             continue
-                        if len(factors) > 1 or factors[0][0] > _lib.CONST:
+                        if len(factors) > 1 or (factors[0][0] > _lib.CONST and factors[0][0] != _lib.GIBBS):
                             # a product of kernels, or a kind that exists on the product path only: a chain of terms
                             # (include/sthenomi_kprod.h), each factor reading its own view of the points
                             if has_st or p.geom is not None or q.geom is not None:
@@ -505,6 +505,8 @@ def _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order):
     """the terms of one leaf of the kernel between the paths p and q, at least one of which carries a direction: one term of
     the leaf's derivative kind per pair of non-zero components of the two directions, seen through the kernel's own input
     transform (kernels.chain_direction), the components -- the Jacobian factors -- in its coefficient"""
+    if any(f[0] == _lib.GIBBS for f in factors):
+        raise NotImplementedError("derivative: a GibbsKernel below the node is not supported (its lengthscale step is not linear)")
     if len(factors) > 1 or factors[0][0] not in _lib.DERIV_OF:
         raise NotImplementedError("derivative: the kernel below the node must be SE, Matern-3/2 or Matern-5/2, or a sum or "
                                   "scaling of these (no products of kernels, no Matern-1/2, no kernel of the product path)")

@@ -6,8 +6,10 @@ transformation (KernelFunctions `TransformedKernel`): a tuple of steps applied t
 order -- ("scale", s) for ScaleTransform(s) / with_lengthscale, ("periodic", f) for
 PeriodicTransform(f) (/root/reference/examples/extended_mauna_loa/script.jl:129), ("sincos", r) for the
 embedding behind PeriodicKernel(r), ("linear", A) / ("ard", v) / ("select", idx) for KernelFunctions' LinearTransform,
-ARDTransform and SelectTransform -- evaluated on the host (O(N D)) when the spec is built.  Matrices, vectors and index
-lists are stored as tuples of floats / ints: equal maps give equal (hashable) chains, so equal views are uploaded once.
+ARDTransform and SelectTransform, ("lengthscale", fn) for the row l(X) that GibbsKernel appends below the location rows
+(always the last step) -- evaluated on the host (O(N D)) when the spec is built.  Matrices, vectors and index
+lists are stored as tuples of floats / ints: equal maps give equal (hashable) chains, so equal views are uploaded once
+(a lengthscale step compares by its callable).
 
 Products of kernels (`k1 * k2`, KernelFunctions KernelProduct) expand into chains of such leaves:
 `leaf_products()` returns [(coef, [(kind, param, input_chain), ...])], one entry per product of primitives,
@@ -51,6 +53,8 @@ def apply_chain(chain, X):
             X = _ard_v(v, X.shape[0])[:, None] * X
         elif kind == "select":
             X = X[list(v), :]
+        elif kind == "lengthscale":
+            X = np.vstack([X, _lengthscale_row(v, X)])     # the Gibbs kind's points: the location, then l(x)
         elif kind == "sincos":
             # x_d -> [sin 2 pi x_d, cos 2 pi x_d] / (2 r_d): squared distances become sum_d sin^2(pi (x_d - y_d)) / r_d^2,
             # so SE over these points is KernelFunctions' PeriodicKernel(r); rows: the D sines, then the D cosines
@@ -60,6 +64,14 @@ def apply_chain(chain, X):
         else:
             raise ValueError(kind)
     return np.asfortranarray(X)
+
+
+def _lengthscale_row(fn, X):
+    """l(X) of a ("lengthscale", fn) step: n positive finite values for the D x n points X"""
+    l = np.asarray(fn(X), dtype=np.float64).reshape(-1)
+    if l.shape[0] != X.shape[1] or not np.all(np.isfinite(l)) or not np.all(l > 0.0):
+        raise ValueError(f"GibbsKernel: lengthscale must return {X.shape[1]} positive finite values for {X.shape[1]} points")
+    return l
 
 
 def _linear_A(v, D):
@@ -81,7 +93,8 @@ def _ard_v(v, D):
 def chain_vjp(chain, X, gout, transforms=None):
     """cotangent of the raw points given the cotangent of apply_chain(chain, X).  transforms: a list that receives, in
     chain order, the cotangent of every ("linear", A) step's matrix (g X_in') and every ("ard", v) step's vector
-    (the row sums of g * X_in), X_in the points that step reads and g the cotangent of what it returns"""
+    (the row sums of g * X_in), X_in the points that step reads and g the cotangent of what it returns, and of every
+    ("lengthscale", fn) step's appended row l(X_in) (length n): that step's location rows pass through with l held fixed"""
     stack = [np.asarray(X, dtype=np.float64)]
     for kind, v in chain[:-1]:
         stack.append(apply_chain(((kind, v),), stack[-1]))
@@ -100,6 +113,9 @@ def chain_vjp(chain, X, gout, transforms=None):
             gin = np.zeros(xin.shape)
             np.add.at(gin, list(v), g)
             g = gin
+        elif kind == "lengthscale":
+            found.append(g[-1, :].copy())
+            g = g[:-1, :]
         elif kind == "sincos":
             D = xin.shape[0]
             h = (np.pi / _sincos_r(v, D))[:, None]          # 2 pi / (2 r_d)
@@ -124,7 +140,7 @@ def _sincos_r(v, D):
 def chain_direction(chain, v):
     """a direction v (length D) in the raw points' coordinates seen through the chain's Jacobian -- the direction, in the
     coordinates of apply_chain(chain, X), along which the kernel is differentiated when the process is differentiated along
-    v; None if a step is not linear (periodic, sincos)"""
+    v; None if a step is not linear (periodic, sincos, lengthscale)"""
     v = np.asarray(v, dtype=np.float64)
     for kind, p in chain:
         if kind == "scale":
@@ -304,7 +320,29 @@ class KernelProduct(Kernel):
         out = [(1.0, [])]
         for k in self.kernels:
             out = [(c * kc, fs + kfs) for (c, fs) in out for (kc, kfs) in k.leaf_products()]
+        if len(self.kernels) > 1 and any(f[0] == _lib.GIBBS for _, fs in out for f in fs):
+            raise NotImplementedError("a product of kernels with a GibbsKernel factor is not supported (the Gibbs kind is "
+                                      "no factor of the library's product chains)")
         return out
+
+
+class GibbsKernel(Kernel):
+    """KernelFunctions' GibbsKernel(; lengthscale): a squared-exponential whose lengthscale depends on the point,
+        k(x, y) = (2 lx ly / (lx^2 + ly^2))^(power / 2) exp(-|x - y|^2 / (lx^2 + ly^2)),   lx = lengthscale(x).
+    `lengthscale`: a callable that takes the D x n points the kernel sees (after the transforms around it) and returns n
+    positive finite values (ValueError otherwise).  power = 1 is KernelFunctions' kernel; power = D is the form of Paciorek and
+    Schervish, the one that is positive definite in D dimensions (a power below D is not in general).  Evaluated on the
+    device (include/sthenomi.h: SGP_GIBBS): the host appends the row l(X) to the points, O(n)."""
+
+    def __init__(self, lengthscale, power=1):
+        if not callable(lengthscale):
+            raise TypeError("GibbsKernel: lengthscale must be a callable of the D x n points")
+        if power != int(power) or not 1 <= int(power) <= _lib.GIBBS_MAX_POWER:
+            raise ValueError(f"GibbsKernel: power must be an integer in 1 .. {_lib.GIBBS_MAX_POWER}")
+        self.lengthscale, self.power = lengthscale, int(power)
+
+    def leaf_terms(self):
+        return [(_lib.GIBBS, 1.0, float(self.power), (("lengthscale", self.lengthscale),))]
 
 
 class RationalQuadraticKernel(Kernel):

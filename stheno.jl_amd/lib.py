@@ -31,6 +31,10 @@ NEURALNET, FBM, EXPONENTIATED = 24, 25, 26   # kinds of x'y, x'x and y'y, the sa
 DERIV_SE, DERIV_MATERN32, DERIV_MATERN52 = 32, 34, 35
 DERIV_OF = {SE: DERIV_SE, MATERN32: DERIV_MATERN32, MATERN52: DERIV_MATERN52}
 DERIV_MAX_DIM, DERIV_PARAM_BASE = 16, 17
+# the Gibbs kind (include/sthenomi.h: SGP_GIBBS; gibbs.hip): points of dimension D + 1 <= GIBBS_MAX_DIM, the last coordinate the
+# lengthscale at the point; param = the power p of the normaliser, an integer in 1 .. GIBBS_MAX_POWER
+GIBBS = 40
+GIBBS_MAX_DIM, GIBBS_MAX_POWER = 16, 16
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
 KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain
@@ -579,8 +583,10 @@ class Spec:
         # product chains / the RQ, LINEAR, COSINE and GAMMAEXP kinds (include/sthenomi_kprod.h): a term whose kind carries KIND_TIMES_PREV
         # continues the chain of the term before it
         self.has_deriv = any(int(t[0]) in DERIV_OF.values() for t in terms)     # derivative terms: a class of their own
+        self.has_gibbs = any(int(t[0]) == GIBBS for t in terms)                 # Gibbs terms: likewise
         self.has_kprod = any((int(t[0]) & KIND_TIMES_PREV) or
-                             ((int(t[0]) & KIND_MASK) > CONST and int(t[0]) not in DERIV_OF.values()) for t in terms)
+                             ((int(t[0]) & KIND_MASK) > CONST and int(t[0]) not in DERIV_OF.values() and int(t[0]) != GIBBS)
+                             for t in terms)
         self._bound = None
         self.n_terms = len(terms)
         self._term_ptr = np.asarray(term_ptr, dtype=np.int32)
@@ -657,7 +663,7 @@ class Spec:
     def f32_supported(self):
         """The fp32 device kernels (csrc/f32.hip: assemble_f32) take input dimension <= 16 and, per block pair,
         (number of terms) x (dimension rounded up to a power of two) <= 64; anything else runs on the fp64 path."""
-        if self.has_patch or self.has_stencil or self.has_kprod or self.has_deriv:
+        if self.has_patch or self.has_stencil or self.has_kprod or self.has_deriv or self.has_gibbs:
             return False                 # patch / stencil / product terms: fp64 only (a Float32 model runs there and is rounded back)
         tp = self._term_ptr
         for p in range(len(tp) - 1):
