@@ -129,7 +129,35 @@ enum {
    * that names "Gibbs": sgp_logpdf_grad_xs with scale outputs, sgp_kernelmatrix_diag_grad*, sgp_elbo_grad*, the *_param,
    * *_conv, *_stencil and *_stencil_wo families, the predict-gradient entry points, every *_f32 entry point, every multi-GPU
    * context. */
-  SGP_GIBBS = SGP_SE + 40                 /* 40 */
+  SGP_GIBBS = SGP_SE + 40,                /* 40 */
+  /* Additive kinds: 48 + the base kind (SE, Matern-1/2, -3/2, -5/2).  The additive kernel of Duvenaud, Nickisch and Rasmussen:
+   * the elementary symmetric polynomial of order r = param of the D one-dimensional base kernels.  A class of its own
+   * (additive.hip); 41 .. 47 stay no kinds, and neither is anything above 51.
+   *
+   * A term reads points of dimension D in 1 .. 16 (after the caller's transforms: ARD lengthscales are applied already);
+   * param = r, an integer in 1 .. min(D, 8).  With u_d = x_d - y_d and z_d = kappa_base(u_d^2):
+   *     K_ij = coef rs_i cs_j e_r(z_0 .. z_{D-1})
+   * e_0 .. e_R come from ONE recurrence in one fixed order: e = (1, 0, .., 0); for d = 0 .. D - 1, for k = min(d + 1, R) down
+   * to 1: e_k = fma(z_d, e_{k-1}, e_k).  The terms of a block pair that share kind, points, scale vectors and dimension form
+   * one launch group: the recurrence runs once per point pair to the group's largest order, and the entry is the sum over the
+   * group's terms, in their order, of fma(e_{r_t}, (coef_t rs_i) cs_j, acc).
+   *
+   * Exact values: a pair that coincides in every coordinate gives exactly C(D, r) (coef rs_i) cs_j; a coordinate whose
+   * exponential underflowed contributes an exact z_d = 0; a pair with fewer than r live coordinates gives an exact 0;
+   * sgp_kernelmatrix_diag equals the diagonal of sgp_kernelmatrix bit for bit.  Error model: docs/03_kernels.md, 3.2h.
+   *
+   * Gradients: grad_coef as for every kind.  grad_inscale: both inputs scaled by g; with s_d = u_d^2 and
+   * v_d = 2 s_d kappa'(s_d) it is coef rs_i cs_j sum_d v_d e_{r-1}(z without d).  grad_inputs of sgp_logpdf_grad_x, row d of
+   * the row input, column i:  sum_j G_ij rs_i cs_j A_d 2 kappa'(s_d) u_d,  A_d = sum_t coef_t e_{r_t - 1}(z without d), and
+   * the mirror image for the column side.  Matern-1/2 contributes 0 from a coordinate with u_d = 0.
+   *
+   * Refused by dspec creation, every text naming "additive": a param that is no integer in 1 .. min(D, 8) (NaN included);
+   * points of dimension > 16; SGP_KIND_TIMES_PREV on the term or on its successor; reserved != 0; a multi-GPU context.
+   * Taken and refused by the operators exactly as SGP_GIBBS is, the refusals naming "additive". */
+  SGP_ADDITIVE_SE = SGP_SE + 48,             /* 48 */
+  SGP_ADDITIVE_MATERN12 = SGP_MATERN12 + 48, /* 49 */
+  SGP_ADDITIVE_MATERN32 = SGP_MATERN32 + 48, /* 50 */
+  SGP_ADDITIVE_MATERN52 = SGP_MATERN52 + 48  /* 51 */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -162,7 +190,7 @@ typedef struct {
   double coef;        /* product of scalar scales (may be negative)                      */
   double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu;
                          SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; SGP_DERIV_*: 17 a + b; SGP_GIBBS: p;
-                         ignored by the other kinds */
+                         SGP_ADDITIVE_*: the order r; ignored by the other kinds */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

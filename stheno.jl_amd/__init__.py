@@ -11,6 +11,7 @@ from .inputs import BlockData, ColVecs, GPPPInput, ImageVector, blocks, split, v
 from .kernels import (ARDTransform, CosineKernel, ExponentiatedKernel, FBMKernel, GammaExponentialKernel, NeuralNetworkKernel, GeneralMaternKernel, LinearTransform, MaternKernel,  # noqa: F401
                       SelectTransform, gaborkernel, spectral_mixture_kernel, spectral_mixture_product_kernel)
 from .kernels import PiecewisePolynomialKernel, RationalKernel, WienerKernel  # noqa: F401
+from .kernels import AdditiveKernel, additive_kernel  # noqa: F401
 from .kernels import (GibbsKernel, ConstantKernel, ExponentialKernel, KernelProduct, KernelSum, LinearKernel, Matern12Kernel,  # noqa: F401
                       Matern32Kernel, Matern52Kernel, PeriodicKernel, PeriodicTransform, PolynomialKernel,
                       RationalQuadraticKernel, ScaledKernel, ScaleTransform,

@@ -244,9 +244,24 @@ int launch_grad_gibbs(const double* Kinv, long ldk, const double* alpha, long r0
 int launch_grad_gibbs_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
                              const DevTerm& T, const DevTerm* d_terms, int nterms, double scale, double* gx, hipStream_t s);
 
+// additive.hip: the additive kinds (include/sthenomi.h: SGP_ADDITIVE_*), a term class of its own.  A launch carries ONE group
+// of a pair's additive terms (additive_kinds.h: additive_group -- the same kind, points and scale vectors; the terms differ
+// in (coef, param)).  As their Gibbs counterparts above; the input-point launcher takes the group's host copies too (the
+// order class is the group's largest order)
+int launch_assemble_additive(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, hipStream_t s);
+int launch_diag_additive(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
+                         hipStream_t s);
+long grad_additive_partials(long trc, long tcc);
+int launch_grad_additive(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
+                         const DevTerm* h_terms, const DevTerm* d_terms, int nterms, long trf, long tcf, long trc, long tcc,
+                         double* partials, double* out_coef, double* out_scale, hipStream_t s);
+int launch_grad_additive_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                                const DevTerm& T, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, double scale,
+                                double* gx, hipStream_t s);
+
 void set_error(const std::string& s);
 
-#define SGP_HIP(expr)                                                                     \
+#define SGP_HIP(expr)                                                                    \
   do {                                                                                    \
     hipError_t _e = (expr);                                                               \
     if (_e != hipSuccess) {                                                               \

@@ -6,6 +6,7 @@
 #include "../../include/sthenomi.h"
 #include "../../include/sthenomi_bench.h"
 #include "deriv_kinds.h"
+#include "additive_kinds.h"
 #include "gibbs_kinds.h"
 
 #include <mutex>
@@ -58,6 +59,7 @@ struct GradLeave {
   bool patch = false;     // patch (convolutional) terms (include/sthenomi_conv_grad.h)
   bool stencil = false;   // stencil terms (include/sthenomi_stencil_grad.h, sthenomi_stencil_wo.h); set together with patch
   bool deriv = false;     // derivative terms (include/sthenomi.h: SGP_DERIV_*): sgp_logpdf_grad and its batch / pool forms alone
+  bool additive = false;  // additive terms (include/sthenomi.h: SGP_ADDITIVE_*): the entry points that carry Gibbs terms
   bool gibbs = false;     // Gibbs terms (include/sthenomi.h: SGP_GIBBS): those, and sgp_logpdf_grad_x / _xs without scale outputs
 };
 // sgp_logpdf_grad / _x / _xs / _param / _param_xs / _conv / _stencil / _stencil_wo
@@ -446,13 +448,24 @@ inline bool spec_has_gibbs(const sgp_cov_spec* sp) {
   return false;
 }
 
+// a term of the additive kinds (include/sthenomi.h: SGP_ADDITIVE_*; additive.hip): likewise
+inline bool term_is_additive(const sgp_term& T) { return T.kind >= 0 && sgp::additive_kind_known(T.kind & 0xff); }
+inline bool spec_has_additive(const sgp_cov_spec* sp) {
+  if (!sp || !sp->term_ptr || !sp->terms) return false;
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t)
+    if (term_is_additive(sp->terms[t])) return true;
+  return false;
+}
+
 // a term of a product chain (include/sthenomi_kprod.h) or of a kind only kprod.hip evaluates (the derivative kinds are
-// deriv.hip's, the Gibbs kind gibbs.hip's)
+// deriv.hip's, the Gibbs kind gibbs.hip's, the additive kinds additive.hip's)
 inline bool spec_has_kprod(const sgp_cov_spec* sp) {
   if (!sp || !sp->term_ptr || !sp->terms) return false;
   const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
   for (int t = 0; t < n; ++t)
-    if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || ((sp->terms[t].kind & 0xff) > SGP_CONST && !term_is_deriv(sp->terms[t]) && !term_is_gibbs(sp->terms[t])))
+    if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || ((sp->terms[t].kind & 0xff) > SGP_CONST && !term_is_deriv(sp->terms[t]) &&
+                                                   !term_is_gibbs(sp->terms[t]) && !term_is_additive(sp->terms[t])))
       return true;
   return false;
 }
@@ -489,5 +502,8 @@ struct sgp_dspec {
   // Gibbs terms (gibbs.hip): between the derivative terms and the chains of their pair, likewise; n_gibbs == 0: none
   std::vector<int> pair_ngibbs;
   int n_gibbs = 0;
+  // additive terms (additive.hip): between the Gibbs terms and the chains of their pair, likewise; n_additive == 0: none
+  std::vector<int> pair_nadditive;
+  int n_additive = 0;
   std::vector<int> term_src;           // index in the caller's spec->terms of the term at each device position
 };

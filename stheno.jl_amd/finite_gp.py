@@ -73,6 +73,14 @@ def _refuse_gibbs(what, *specs):
                                   "logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, inputs and d_lengthscale")
 
 
+def _refuse_additive(what, *specs):
+    """`what` through additive terms (AdditiveKernel; include/sthenomi.h: SGP_ADDITIVE_*) is not implemented (the library
+    refuses it too): logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, the input gradients and d_transform"""
+    if any(sp.has_additive for sp in specs):
+        raise NotImplementedError(f"{what} through additive covariance terms (AdditiveKernel) is not supported: "
+                                  "logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, inputs and d_transform")
+
+
 def _is_prior(f):
     return isinstance(f, (GPPP, SthenoAbstractGP))
 
@@ -268,6 +276,7 @@ def mean_and_var_and_gradient(fx):
     cross, pss, ms = _cross_side(f, fx.x)
     _refuse_deriv("mean_and_var_and_gradient", cross, pss)
     _refuse_gibbs("mean_and_var_and_gradient", cross, pss)
+    _refuse_additive("mean_and_var_and_gradient", cross, pss)
     _refuse_patch_gradient(cross, pss)
     _refuse_product_gradient("mean_and_var_and_gradient", cross, pss)
     if (any(rs is not None for rs in cross.term_row_scale) or any(rs is not None for rs in pss.term_row_scale)
@@ -532,6 +541,7 @@ def logpdf_f32(fx, y):
     spec = _prior_spec(fx.f, fx.x)
     _refuse_deriv("logpdf_f32: the fp32 path", spec)
     _refuse_gibbs("logpdf_f32: the fp32 path", spec)
+    _refuse_additive("logpdf_f32: the fp32 path", spec)
     if spec.has_stencil:
         raise NotImplementedError("stencil terms have no fp32 path: call logpdf, which runs them in fp64")
     if spec.has_kprod:
@@ -624,9 +634,11 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
         _refuse_deriv("logpdf_and_gradient: inputs=True / scales=True", spec)
         if scales:
             _refuse_gibbs("logpdf_and_gradient: scales=True", spec)
+            _refuse_additive("logpdf_and_gradient: scales=True", spec)
         _refuse_product_gradient("logpdf_and_gradient: inputs=True / scales=True", spec)
     if spec.has_kprod:      # (sgp_logpdf_grad_param refuses the kind)
         _refuse_gibbs("logpdf_and_gradient of a model that also holds a product-path kernel", spec)
+        _refuse_additive("logpdf_and_gradient of a model that also holds a product-path kernel", spec)
     kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
     if spec.has_kprod:
         if _ctx().is_multi:
@@ -654,6 +666,8 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
         for r in rec["terms"]:
             if (int(r["kind"]) & _lib.KIND_MASK) == _lib.GIBBS:
                 r["d_lengthscale"] = (gx[r["row_input"]][-1, :], gx[r["col_input"]][-1, :])
+    if inputs and spec.has_additive:      # the per-dimension lengthscales of an additive model: the ARDTransform's vector
+        _attach_d_transform(rec["terms"], spec, gx)
     return rec
 
 
@@ -687,6 +701,7 @@ def _refuse_param_family(what, *specs):
     """what the superset family of include/sthenomi_kprod_grad.h does not carry: patch / stencil sides, a multi-GPU context"""
     _refuse_deriv(what, *specs)
     _refuse_gibbs(what, *specs)
+    _refuse_additive(what, *specs)
     _refuse_patch_gradient(*specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what}: a product of kernels (the gradients of include/sthenomi_kprod_grad.h) is not "
@@ -721,6 +736,7 @@ def _refuse_conv_family(what, *specs):
     """what the entry points of include/sthenomi_conv_grad.h refuse: a multi-GPU context, stencil terms"""
     _refuse_deriv(what, *specs)
     _refuse_gibbs(what, *specs)
+    _refuse_additive(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_stencil for sp in specs):
@@ -754,6 +770,7 @@ def _refuse_stencil_family(what, *specs):
     carry"""
     _refuse_deriv(what, *specs)
     _refuse_gibbs(what, *specs)
+    _refuse_additive(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_patch or sp.has_stencil for sp in specs) and any(sp.has_kprod for sp in specs):
@@ -1234,6 +1251,7 @@ def posterior_mean_and_var_f32(fx, y, xs):
     pss = _prior_spec(fx.f, xs)
     _refuse_deriv("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
     _refuse_gibbs("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
+    _refuse_additive("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
     kind, nbuf = _lib._noise_args(fx.noise, len(y))
     if kind == _lib.NOISE_DENSE or not spec.f32_supported() or not cross.f32_supported():
         raise NotImplementedError("beyond the fp32 kernels' limits (dense noise, input dimension > 16, too many terms)")
@@ -1515,6 +1533,7 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
     specs, head = _elbo_grad_specs(vfe, fx, y)
     _refuse_deriv("elbo_and_gradient", *specs)
     _refuse_gibbs("elbo_and_gradient", *specs)
+    _refuse_additive("elbo_and_gradient", *specs)
     _refuse_patch_gradient(*specs)
     _refuse_product_gradient("elbo_and_gradient", *specs)
     F = _elbo_grad_frame(specs, head)

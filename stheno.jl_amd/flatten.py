@@ -410,7 +410,8 @@ def build_spec(f, x, f2=None, x2=None):
                         if has_dv:
                             _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order)
                             continue
-                        if len(factors) > 1 or (factors[0][0] > _lib.CONST and factors[0][0] != _lib.GIBBS):
+                        if len(factors) > 1 or (factors[0][0] > _lib.CONST and factors[0][0] != _lib.GIBBS
+                                                and factors[0][0] not in _lib.ADDITIVE_OF.values()):
                             # a product of kernels, or a kind that exists on the product path only: a chain of terms
                             # (include/sthenomi_kprod.h), each factor reading its own view of the points
                             if has_st or p.geom is not None or q.geom is not None:
@@ -450,6 +451,10 @@ def build_spec(f, x, f2=None, x2=None):
                                 order.append(k)
                             continue
                         (kind, param, s), = factors
+                        if kind in _lib.ADDITIVE_OF.values():
+                            if has_st or p.geom is not None or q.geom is not None:
+                                raise NotImplementedError("an additive kernel (AdditiveKernel) below patch_convolve or a "
+                                                          "stencil is not supported")
                         if (p.geom is not None or q.geom is not None) and _kernels.chain_scale(s) is None:
                             raise NotImplementedError("patch_convolve: the kernel's input transform does not commute with "
                                                       "patch extraction (only a scalar ScaleTransform / with_lengthscale "
@@ -505,6 +510,8 @@ def _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order):
     """the terms of one leaf of the kernel between the paths p and q, at least one of which carries a direction: one term of
     the leaf's derivative kind per pair of non-zero components of the two directions, seen through the kernel's own input
     transform (kernels.chain_direction), the components -- the Jacobian factors -- in its coefficient"""
+    if any(f[0] in _lib.ADDITIVE_OF.values() for f in factors):
+        raise NotImplementedError("derivative: an additive kernel (AdditiveKernel) below the node is not supported")
     if any(f[0] == _lib.GIBBS for f in factors):
         raise NotImplementedError("derivative: a GibbsKernel below the node is not supported (its lengthscale step is not linear)")
     if len(factors) > 1 or factors[0][0] not in _lib.DERIV_OF:

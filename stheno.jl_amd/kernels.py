@@ -320,6 +320,9 @@ class KernelProduct(Kernel):
         out = [(1.0, [])]
         for k in self.kernels:
             out = [(c * kc, fs + kfs) for (c, fs) in out for (kc, kfs) in k.leaf_products()]
+        if len(self.kernels) > 1 and any(f[0] in _lib.ADDITIVE_OF.values() for _, fs in out for f in fs):
+            raise NotImplementedError("a product of kernels with an additive factor (AdditiveKernel) is not supported (the "
+                                      "additive kinds are no factors of the library's product chains)")
         if len(self.kernels) > 1 and any(f[0] == _lib.GIBBS for _, fs in out for f in fs):
             raise NotImplementedError("a product of kernels with a GibbsKernel factor is not supported (the Gibbs kind is "
                                       "no factor of the library's product chains)")
@@ -343,6 +346,35 @@ class GibbsKernel(Kernel):
 
     def leaf_terms(self):
         return [(_lib.GIBBS, 1.0, float(self.power), (("lengthscale", self.lengthscale),))]
+
+
+class AdditiveKernel(Kernel):
+    """The additive kernel of Duvenaud, Nickisch and Rasmussen of one order: the elementary symmetric polynomial e_order of the
+    D one-dimensional base kernels, k(x, y) = sum over d_1 < .. < d_order of prod_i base(x_{d_i}, y_{d_i}).  `base`: SEKernel,
+    Matern12Kernel / ExponentialKernel, Matern32Kernel or Matern52Kernel, as constructed (no transform inside: lengthscales
+    come from an ARDTransform / ScaleTransform / with_lengthscale around the AdditiveKernel).  `order`: an integer in
+    1 .. min(D, 8), D the dimension of the points the kernel sees (the library checks it against D).  Evaluated on the device
+    by one recurrence per point pair (include/sthenomi.h: SGP_ADDITIVE_*)."""
+
+    def __init__(self, base, order):
+        if type(base) not in (SEKernel, Matern12Kernel, Matern32Kernel, Matern52Kernel):
+            raise TypeError("AdditiveKernel: the additive base must be SEKernel, Matern12Kernel (ExponentialKernel), "
+                            "Matern32Kernel or Matern52Kernel; put transforms around the AdditiveKernel")
+        if order != int(order) or not 1 <= int(order) <= _lib.ADDITIVE_MAX_ORDER:
+            raise ValueError(f"AdditiveKernel: the additive order must be an integer in 1 .. {_lib.ADDITIVE_MAX_ORDER}")
+        self.base, self.order = base, int(order)
+
+    def leaf_terms(self):
+        return [(_lib.ADDITIVE_OF[self.base.kind], 1.0, float(self.order), ())]
+
+
+def additive_kernel(base, variances):
+    """sum_r variances[r - 1] * AdditiveKernel(base, r), r = 1 .. len(variances): the full additive model up to that order.  All
+    its terms read one view of the points, so they flatten to one launch group: one recurrence per point pair for all orders"""
+    variances = [float(v) for v in variances]
+    if not variances:
+        raise ValueError("additive_kernel: at least one variance (the additive model's first order)")
+    return KernelSum([ScaledKernel(AdditiveKernel(base, r + 1), v) for r, v in enumerate(variances)])
 
 
 class RationalQuadraticKernel(Kernel):

@@ -35,6 +35,11 @@ DERIV_MAX_DIM, DERIV_PARAM_BASE = 16, 17
 # lengthscale at the point; param = the power p of the normaliser, an integer in 1 .. GIBBS_MAX_POWER
 GIBBS = 40
 GIBBS_MAX_DIM, GIBBS_MAX_POWER = 16, 16
+# the additive kinds (include/sthenomi.h: SGP_ADDITIVE_*; additive.hip): 48 + the base kind; points of dimension <=
+# ADDITIVE_MAX_DIM, param = the order r of the elementary symmetric polynomial, an integer in 1 .. min(D, ADDITIVE_MAX_ORDER)
+ADDITIVE_SE, ADDITIVE_MATERN12, ADDITIVE_MATERN32, ADDITIVE_MATERN52 = 48, 49, 50, 51
+ADDITIVE_OF = {SE: ADDITIVE_SE, MATERN12: ADDITIVE_MATERN12, MATERN32: ADDITIVE_MATERN32, MATERN52: ADDITIVE_MATERN52}
+ADDITIVE_MAX_DIM, ADDITIVE_MAX_ORDER = 16, 8
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
 KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain
@@ -584,8 +589,10 @@ class Spec:
         # continues the chain of the term before it
         self.has_deriv = any(int(t[0]) in DERIV_OF.values() for t in terms)     # derivative terms: a class of their own
         self.has_gibbs = any(int(t[0]) == GIBBS for t in terms)                 # Gibbs terms: likewise
+        self.has_additive = any(int(t[0]) in ADDITIVE_OF.values() for t in terms)   # additive terms: likewise
         self.has_kprod = any((int(t[0]) & KIND_TIMES_PREV) or
-                             ((int(t[0]) & KIND_MASK) > CONST and int(t[0]) not in DERIV_OF.values() and int(t[0]) != GIBBS)
+                             ((int(t[0]) & KIND_MASK) > CONST and int(t[0]) not in DERIV_OF.values() and int(t[0]) != GIBBS
+                              and int(t[0]) not in ADDITIVE_OF.values())
                              for t in terms)
         self._bound = None
         self.n_terms = len(terms)
@@ -663,7 +670,7 @@ class Spec:
     def f32_supported(self):
         """The fp32 device kernels (csrc/f32.hip: assemble_f32) take input dimension <= 16 and, per block pair,
         (number of terms) x (dimension rounded up to a power of two) <= 64; anything else runs on the fp64 path."""
-        if self.has_patch or self.has_stencil or self.has_kprod or self.has_deriv or self.has_gibbs:
+        if self.has_patch or self.has_stencil or self.has_kprod or self.has_deriv or self.has_gibbs or self.has_additive:
             return False                 # patch / stencil / product terms: fp64 only (a Float32 model runs there and is rounded back)
         tp = self._term_ptr
         for p in range(len(tp) - 1):
