@@ -157,7 +157,41 @@ enum {
   SGP_ADDITIVE_SE = SGP_SE + 48,             /* 48 */
   SGP_ADDITIVE_MATERN12 = SGP_MATERN12 + 48, /* 49 */
   SGP_ADDITIVE_MATERN32 = SGP_MATERN32 + 48, /* 50 */
-  SGP_ADDITIVE_MATERN52 = SGP_MATERN52 + 48  /* 51 */
+  SGP_ADDITIVE_MATERN52 = SGP_MATERN52 + 48, /* 51 */
+  /* The blur kind: the squared-exponential integrated against a Gaussian footprint on either side.  A class of its own
+   * (blur.hip): neither a product-path kind nor one of the classes above; 52 .. 55 stay no kinds.
+   *
+   * A term of this kind reads points of dimension 2 D, D in 1 .. 8: rows 0 .. D - 1 are the location mu, rows D .. 2 D - 1 the
+   * variances s_d >= 0 of the footprint N(mu, diag s) at that point, after the caller's transforms.  With u_d = mu_d - mu'_d
+   * and q_d = 1 + (s_d + s'_d):
+   *     K_ij = coef rs_i cs_j  prod_d q_d^(-1/2)  exp(-1/2 sum_d u_d^2 / q_d)
+   * the SE kernel integrated against N(mu, diag s) on one side and N(mu', diag s') on the other.  A point with s = 0 is a
+   * plain evaluation: one formula gives cov(g, g'), cov(g, f) and cov(f, f).  param is ignored.
+   *
+   * Evaluation order: w_d = 1 / q_d; the exponent is t = fma(u_d w_d, u_d, t) with d ascending, E = exp(-t / 2) by the SE
+   * kernel's exponential; the normaliser is ONE reciprocal square root of the product of the q_d, d ascending; the entry is
+   * fma(rsqrt E, (coef rs_i) cs_j, acc).  Padding coordinates contribute q = 1 and u = 0 exactly.  A group whose one side has
+   * variances that are all exactly 0 takes w_d and the normaliser from the other side's point alone (staged once per tile);
+   * the bits are those of the two-sided evaluation of the same pair.
+   *
+   * Exact values: with every variance on both sides exactly 0 an entry is bit-equal to the SGP_SE term on the location rows;
+   * a pair that coincides in location with zero variances gives exactly (coef rs_i) cs_j; an exponential that underflowed
+   * gives an exact 0; sgp_kernelmatrix_diag (coef rs cs prod_d (1 + 2 s_d)^(-1/2)) equals the diagonal of sgp_kernelmatrix
+   * bit for bit; q_d is symmetric in the two sides, so a symmetric spec is exactly symmetric.  The error model
+   * (docs/03_kernels.md, 3.2i) holds for s in [0, 2^500].
+   *
+   * Gradients: grad_coef as for every kind.  grad_inscale: both sides' locations scaled by g and both sides' variances by
+   * g^2, K_ij sum_d -(S_d q_d + u_d^2) / q_d^2 at g = 1, S_d = s_d + s'_d.  grad_inputs of sgp_logpdf_grad_x (2 D rows per
+   * point, G the cotangent):
+   *     row d < D of the row input, column i:  sum_j G_ij K_ij (-u_d / q_d)
+   *     row D + d:                             sum_j G_ij K_ij 1/2 (u_d^2 / q_d^2 - 1 / q_d)
+   * and the mirror image for the column side.  The variance rows are what a footprint width is trained with.
+   *
+   * Refused by dspec creation, every text naming "blur": points of odd dimension or of dimension > 16; SGP_KIND_TIMES_PREV on
+   * the term or on its successor; reserved != 0; a multi-GPU context; a variance that is negative, NaN or infinite (the
+   * variance rows of every input a blur term reads are scanned on the host, O(D n)).
+   * Taken and refused by the operators exactly as SGP_GIBBS is, the refusals naming "blur". */
+  SGP_BLUR_SE = SGP_SE + 56                  /* 56 */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -190,7 +224,7 @@ typedef struct {
   double coef;        /* product of scalar scales (may be negative)                      */
   double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu;
                          SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; SGP_DERIV_*: 17 a + b; SGP_GIBBS: p;
-                         SGP_ADDITIVE_*: the order r; ignored by the other kinds */
+                         SGP_ADDITIVE_*: the order r; ignored by the other kinds (SGP_BLUR_SE among them) */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

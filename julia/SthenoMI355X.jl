@@ -106,6 +106,8 @@ leaf(k::MaternKernel) = [(20, 1.0, Float64(only(k.ν)), Chain())]
 const SGP_GIBBS = 40
 # the additive kinds (include/sthenomi.h: 48 + the base kind SE, Matern-1/2, -3/2, -5/2; param = the order r)
 const SGP_ADDITIVE = 48
+# the blur kind (include/sthenomi.h: points of dimension 2 D, the locations and below them the footprint's variances)
+const SGP_BLUR_SE = 56
 # derivative kinds (SGP_DERIV_SE = 32, SGP_DERIV_MATERN32 = 34, SGP_DERIV_MATERN52 = 35: 32 + the base kind, param = 17 a + b)
 # kinds of x'y, x'x and y'y (SGP_NEURALNET = 24, SGP_FBM = 25 with param = h in (0, 1], SGP_EXPONENTIATED = 26)
 leaf(::NeuralNetworkKernel) = [(24, 1.0, 0.0, Chain())]

@@ -87,6 +87,7 @@ struct DevTerm {
   const double* cs;  // col scale or nullptr
   // patch term (conv.hip): ph x pw patches, stride 1, of the images of a side with hr / hc > 0 -- that side's points are
   // column-major hr x wr (hc x wc) images, dim = ph * pw counts the patch; ph == 0: a plain term
+  // (a blur term, blur.hip: ph == 0, and wr / wc != 0 says that side's variance rows are all exactly 0)
   int ph, pw, hr, wr, hc, wc;
   // stencil term (stencil.hip): a side with qr / qc > 0 reads its points shifted by a registered stencil -- str (stc)
   // holds its offsets (dim x qr, column-major) followed by its qr weights on the device; qr == 0: that side is plain
@@ -258,6 +259,19 @@ int launch_grad_additive(const double* Kinv, long ldk, const double* alpha, long
 int launch_grad_additive_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
                                 const DevTerm& T, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, double scale,
                                 double* gx, hipStream_t s);
+
+// blur.hip: the blur kind (include/sthenomi.h: SGP_BLUR_SE), a term class of its own.  A launch carries ONE group of a pair's
+// blur terms (blur_kinds.h: blur_group -- the same points and scale vectors; the terms differ in coef).  As their Gibbs
+// counterparts above; gx of the input-point launcher has 2 D rows per point, the last D the variances'
+int launch_assemble_blur(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, hipStream_t s);
+int launch_diag_blur(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
+                     hipStream_t s);
+long grad_blur_partials(long trc, long tcc);
+int launch_grad_blur(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
+                     const DevTerm* h_terms, const DevTerm* d_terms, int nterms, long trf, long tcf, long trc, long tcc,
+                     double* partials, double* out_coef, double* out_scale, hipStream_t s);
+int launch_grad_blur_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                            const DevTerm& T, const DevTerm* d_terms, int nterms, double scale, double* gx, hipStream_t s);
 
 void set_error(const std::string& s);
 

@@ -7,6 +7,7 @@
 #include "../../include/sthenomi_bench.h"
 #include "deriv_kinds.h"
 #include "additive_kinds.h"
+#include "blur_kinds.h"
 #include "gibbs_kinds.h"
 
 #include <mutex>
@@ -60,6 +61,7 @@ struct GradLeave {
   bool stencil = false;   // stencil terms (include/sthenomi_stencil_grad.h, sthenomi_stencil_wo.h); set together with patch
   bool deriv = false;     // derivative terms (include/sthenomi.h: SGP_DERIV_*): sgp_logpdf_grad and its batch / pool forms alone
   bool additive = false;  // additive terms (include/sthenomi.h: SGP_ADDITIVE_*): the entry points that carry Gibbs terms
+  bool blur = false;      // blur terms (include/sthenomi.h: SGP_BLUR_SE): likewise
   bool gibbs = false;     // Gibbs terms (include/sthenomi.h: SGP_GIBBS): those, and sgp_logpdf_grad_x / _xs without scale outputs
 };
 // sgp_logpdf_grad / _x / _xs / _param / _param_xs / _conv / _stencil / _stencil_wo
@@ -458,14 +460,25 @@ inline bool spec_has_additive(const sgp_cov_spec* sp) {
   return false;
 }
 
+// a term of the blur kind (include/sthenomi.h: SGP_BLUR_SE; blur.hip): likewise
+inline bool term_is_blur(const sgp_term& T) { return T.kind >= 0 && sgp::blur_kind_known(T.kind & 0xff); }
+inline bool spec_has_blur(const sgp_cov_spec* sp) {
+  if (!sp || !sp->term_ptr || !sp->terms) return false;
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t)
+    if (term_is_blur(sp->terms[t])) return true;
+  return false;
+}
+
 // a term of a product chain (include/sthenomi_kprod.h) or of a kind only kprod.hip evaluates (the derivative kinds are
-// deriv.hip's, the Gibbs kind gibbs.hip's, the additive kinds additive.hip's)
+// deriv.hip's, the Gibbs kind gibbs.hip's, the additive kinds additive.hip's, the blur kind blur.hip's)
 inline bool spec_has_kprod(const sgp_cov_spec* sp) {
   if (!sp || !sp->term_ptr || !sp->terms) return false;
   const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
   for (int t = 0; t < n; ++t)
     if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || ((sp->terms[t].kind & 0xff) > SGP_CONST && !term_is_deriv(sp->terms[t]) &&
-                                                   !term_is_gibbs(sp->terms[t]) && !term_is_additive(sp->terms[t])))
+                                                   !term_is_gibbs(sp->terms[t]) && !term_is_additive(sp->terms[t]) &&
+                                                   !term_is_blur(sp->terms[t])))
       return true;
   return false;
 }
@@ -505,5 +518,8 @@ struct sgp_dspec {
   // additive terms (additive.hip): between the Gibbs terms and the chains of their pair, likewise; n_additive == 0: none
   std::vector<int> pair_nadditive;
   int n_additive = 0;
+  // blur terms (blur.hip): between the additive terms and the chains of their pair, likewise; n_blur == 0: none
+  std::vector<int> pair_nblur;
+  int n_blur = 0;
   std::vector<int> term_src;           // index in the caller's spec->terms of the term at each device position
 };

@@ -533,6 +533,7 @@ int enter(PostRef post, const PgArgs& a, const char* multi_refusal) {
   for (const sgp_cov_spec* sp : {a.cross, a.prior_ss}) {
     if (!sp) continue;
     REFUSE_UNLESS(!spec_has_gibbs(sp), a.who, "gradients through Gibbs terms are not supported");
+    REFUSE_UNLESS(!spec_has_blur(sp), a.who, "gradients through blur terms are not supported");
     REFUSE_UNLESS(!spec_has_additive(sp), a.who, "gradients through additive terms are not supported");
     REFUSE_UNLESS(!spec_has_deriv(sp), a.who, "gradients through derivative terms are not supported");
     REFUSE_UNLESS(!spec_has_stencil(ctx, sp), a.who, "gradients through stencil terms are not supported");

@@ -19,6 +19,8 @@ with  +            -> union of paths                 (addition.jl:20-47; known-f
                       shifted evaluations (include/sthenomi_stencil.h)
       derivative   -> the path carries a direction; a pair of paths gives one term of a derivative kind per pair of
                       non-zero direction components (include/sthenomi.h: SGP_DERIV_*)
+      blur         -> the path carries the variances of a Gaussian footprint; a pair of paths either of which does gives
+                      one SGP_BLUR_SE term on points with variance rows (include/sthenomi.h), SGP_SE otherwise
 and the leaf kernel expanded into SimpleKernel terms (ScaledKernel -> coefficient, KernelSum ->
 several terms, ScaleTransform -> input scale, KernelProduct -> a chain of terms the library multiplies entry by
 entry: include/sthenomi_kprod.h).  Block pairs without a common atom get no
@@ -36,9 +38,9 @@ from .inputs import BlockData, ColVecs, GPPPInput, as_matrix, blocks, is_pair_ve
 
 
 class _Path:
-    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom", "st", "prov", "dv")
+    __slots__ = ("key", "atom", "c", "r", "X", "chain", "geom", "st", "prov", "dv", "bl")
 
-    def __init__(self, key, atom, c, r, X, chain=(), geom=None, st=None, prov=None, dv=None):
+    def __init__(self, key, atom, c, r, X, chain=(), geom=None, st=None, prov=None, dv=None, bl=None):
         # chain: the input warps applied on the way down, outermost first, as (warp, inputs before it)
         # geom: (H, W, ph, pw) when the path passed a patch_convolve node -- X then holds the flattened images
         # st: (offsets D x Q, weights Q) when the path passed a stencil node -- the offsets in the coordinates of X
@@ -48,7 +50,8 @@ class _Path:
         #       sits at the C-order index of its tuple: offsets sum_k M_k A_k[:, p_k], weight prod_k w_k[p_k]
         # dv: the direction (length dim of X) along which the process is differentiated when the path passed a derivative node
         self.key, self.atom, self.c, self.r, self.X, self.chain, self.geom, self.st = key, atom, c, r, X, chain, geom, st
-        self.prov, self.dv = prov, dv
+        # bl: kernels.BlurRows when the path passed a blur node -- the variances of its footprint in the coordinates of X
+        self.prov, self.dv, self.bl = prov, dv, bl
 
 
 class _ScaleVector(np.ndarray):
@@ -78,6 +81,7 @@ class _MatCache:
         self.keep = []
         self.warped = {}
         self.scaled = {}
+        self.blurred = {}
 
     def warp(self, f, g, x):
         k = (id(f), id(x))
@@ -94,6 +98,16 @@ class _MatCache:
             self.scaled[k] = _ScaleVector(sx if r is None else np.asarray(r) * sx, fac)
             self.keep.append((f, x, r))
         return self.scaled[k]
+
+    def blur_rows(self, bl, s):
+        """the variance rows of a path (bl: its kernels.BlurRows, None: it passed no blur node) behind the kernel chain s"""
+        if bl is None:
+            return _kernels.BLUR_ZERO_ROWS
+        k = (id(bl), s)
+        if k not in self.blurred:
+            self.blurred[k] = bl.through(s)
+            self.keep.append(bl)
+        return self.blurred[k]
 
     def __call__(self, x):
         k = id(x)
@@ -176,9 +190,62 @@ def _paths(f, x, c, r, key, mat, chain=(), geom=None):
         v = np.zeros(D)
         v[f.args[2]] = 1.0
         return _deriv_paths(f.args[1], x, c, r, key, mat, chain, v)
+    if op == "blur":
+        # int f(x + e) N(e; 0, diag s(x)) de: the paths of f read these points and carry s (include/sthenomi.h: SGP_BLUR_SE)
+        X = mat(x)
+        bl = _kernels.BlurRows(_gp.blur_variance(f.args[2], X), np.arange(X.shape[0]), np.ones(X.shape[0]), X.shape[0])
+        return _blur_paths(f.args[1], x, c, r, key, mat, chain, bl)
     if op == "cross":
         raise ValueError("cross(...) can only appear at block level")
     raise ValueError(op)
+
+
+def _blur_paths(f, x, c, r, key, mat, chain, bl):
+    """the paths below a blur node: what keeps a Gaussian footprint Gaussian and axis-aligned -- sums, scalar scales,
+    `+ constant`, Shift (leaves the variances), a diagonal Stretch (multiplies them by its squares), Select (selects them),
+    further blur nodes (variances add) -- and nothing else"""
+    if isinstance(f, _gp.AtomicGP):
+        if not isinstance(f.gp, _gp.GP):
+            raise NotImplementedError("blur of a nested GPPP is not supported")
+        m = f.gp.mean_spec
+        if m is not None and not _gp._is_real(m):
+            raise NotImplementedError("blur: a non-constant prior mean below the node is not supported (its smoothed form is "
+                                      "the caller's; a constant mean stays)")
+        return [_Path(key + (id(f),), f, c, r, mat(x), chain, bl=bl)]
+    if isinstance(f, GPPP) or not isinstance(f, _gp.DerivedGP):
+        raise NotImplementedError("blur of a nested GPPP is not supported" if isinstance(f, GPPP) else
+                                  f"blur over {type(f).__name__} is not supported")
+    op = f.args[0]
+    if op == "+":
+        return _blur_paths(f.args[1], x, c, r, key, mat, chain, bl) + _blur_paths(f.args[2], x, c, r, key, mat, chain, bl)
+    if op == "+known":
+        if not _gp._is_real(f.args[1]):
+            raise NotImplementedError("blur: a known function added below the node is not supported (a constant stays)")
+        return _blur_paths(f.args[2], x, c, r, key, mat, chain, bl)
+    if op == "*":
+        s = f.args[1]
+        if not _gp._is_real(s):
+            raise NotImplementedError("blur: a function-valued scale below the node is not supported (only scalar scales "
+                                      "commute with the integral)")
+        return _blur_paths(f.args[2], x, c * float(s), r, key, mat, chain, bl)
+    if op == "o":
+        g = f.args[2]
+        if isinstance(g, _gp.Shift):
+            below = bl
+        elif isinstance(g, _gp.Stretch):
+            below = bl.through((("scale", float(g.l)),) if np.ndim(g.l) == 0 else (("linear", np.asarray(g.l, dtype=np.float64)),))
+        elif isinstance(g, _gp.Select):
+            below = bl.through((("select", (int(g.idx),) if isinstance(g.idx, (int, np.integer)) else tuple(g.idx)),))
+        else:
+            raise NotImplementedError(f"blur: the warp {_warp_name(g)} below the node is not supported (only Shift, a diagonal "
+                                      "Stretch and Select are)")
+        return _blur_paths(f.args[1], mat.warp(f, g, x), c, r, key, mat, chain + ((g, x),), below)
+    if op == "blur":
+        X = mat(x)
+        return _blur_paths(f.args[1], x, c, r, key, mat, chain,
+                           _kernels.BlurRows(bl.S + _gp.blur_variance(f.args[2], X), bl.sel, bl.fac, bl.nrows))
+    raise NotImplementedError(f"blur over `{op}` is not supported" if op not in ("deriv", "conv", "stencil") else
+                              f"blur of a {dict(deriv='derivative', conv='patch_convolve', stencil='stencil')[op]} is not supported")
 
 
 def _deriv_paths(f, x, c, r, key, mat, chain, v):
@@ -338,13 +405,13 @@ def _merge_paths(ps, cancelled=None):
     out, index = [], {}
     for p in ps:
         k = (p.key, id(p.X), id(p.r) if p.r is not None else None, p.geom, _st_key(p.st),
-             None if p.dv is None else p.dv.tobytes())
+             None if p.dv is None else p.dv.tobytes(), None if p.bl is None else (p.bl.S.tobytes(), p.bl.sel.tobytes(), p.bl.fac.tobytes()))
         if k in index:
             index[k].c += p.c
             if p.prov is not None:
                 index[k].prov = index[k].prov + p.prov
         else:
-            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom, p.st, None if p.prov is None else list(p.prov), p.dv)
+            q = _Path(p.key, p.atom, p.c, p.r, p.X, p.chain, p.geom, p.st, None if p.prov is None else list(p.prov), p.dv, p.bl)
             index[k] = q
             out.append(q)
     # paths that cancel exactly (f - f, 2 f - f - f, ...) leave no term: the block is an exact zero, as in the
@@ -406,7 +473,14 @@ def build_spec(f, x, f2=None, x2=None):
                     if has_dv and (has_st or p.geom is not None or q.geom is not None):
                         raise NotImplementedError("a covariance between a derivative view and a patch_convolve or stencil "
                                                   "view of one process is not supported")
+                    has_bl = p.bl is not None or q.bl is not None
+                    if has_bl and (has_dv or has_st or p.geom is not None or q.geom is not None):
+                        raise NotImplementedError("a covariance between a blur view and a derivative, patch_convolve or "
+                                                  "stencil view of one process is not supported")
                     for (kc, factors) in p.atom.gp.kernel.leaf_products():
+                        if has_bl:
+                            _blur_terms(p, q, kc, factors, table, symmetric, I, J, merged, order, mat)
+                            continue
                         if has_dv:
                             _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order)
                             continue
@@ -544,6 +618,31 @@ def _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order):
             else:
                 merged[k] = ([[_lib.DERIV_OF[kind], ri, ci, p.c * q.c * kc * va * vb, param, p.r, q.r]], (None, None), (None, None))
                 order.append(k)
+
+
+def _blur_terms(p, q, kc, factors, table, symmetric, I, J, merged, order, mat):
+    """the term of one leaf of the kernel between the paths p and q, at least one of which passed a blur node: SGP_BLUR_SE on
+    points that carry their variance rows below the location rows (a ("blur", rows) step behind the kernel's own input chain,
+    which has acted on the variances too: kernels.BlurRows.through); a path without a node carries zeros"""
+    if len(factors) > 1:
+        raise NotImplementedError("blur: a product of kernels below the node is not supported (no closed form is built)")
+    (kind, _, s), = factors
+    if kind != _lib.SE:
+        raise NotImplementedError("blur: the kernel below the node must be the squared-exponential (SEKernel), or a sum or "
+                                  "scaling of such (Matern and every other kernel have no closed form here)")
+    rows = [mat.blur_rows(path.bl, s) for path in (p, q)]
+    ri = table.get(p.X, s + (("blur", rows[0]),), ("row", I, p.chain))
+    ci = table.get(q.X, s + (("blur", rows[1]),), ("row" if symmetric else "col", J, q.chain))
+    if np.asarray(table.arrays[ri]).shape[0] > _lib.BLUR_MAX_DIM:
+        raise NotImplementedError(f"blur: inputs of dimension {np.asarray(table.arrays[ri]).shape[0] // 2} are beyond the "
+                                  f"library's limit of {_lib.BLUR_MAX_DIM // 2}")
+    k = (_lib.BLUR_SE, 0.0, ri, ci, id(p.r) if p.r is not None else None, id(q.r) if q.r is not None else None,
+         None, None, None, None)
+    if k in merged:
+        merged[k][0][0][3] += p.c * q.c * kc
+    else:
+        merged[k] = ([[_lib.BLUR_SE, ri, ci, p.c * q.c * kc, 0.0, p.r, q.r]], (None, None), (None, None))
+        order.append(k)
 
 
 def _point_dim(p):

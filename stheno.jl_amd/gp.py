@@ -340,6 +340,58 @@ def _deriv_mean(f, x):
     raise NotImplementedError(f"derivative over `{op}` is not supported")
 
 
+# ---- Gaussian-smoothed processes ------------------------------------------------------------------------------------
+def blur(f, variance):
+    """g = blur(f, variance): the process g(x) = int f(x + e) N(e; 0, diag s(x)) de, exactly, for a squared-exponential f --
+    one closed-form evaluation per covariance entry (include/sthenomi.h: SGP_BLUR_SE) where quadrature_convolve takes a
+    Gauss-Hermite sum.  `variance`: a scalar, a length-D vector, or a callable of the D x n points g is evaluated at that
+    returns D x n non-negative values.  blur(f, 1.0) at 0 is the reference's commented-out `∫(StandardNormal(), f)`; cov(g, f)
+    and cov(g, g') come from the same formula, so conditioning on f predicts the integral and the other way round.
+
+    Below g, f may carry sums, scalar scales, `+ constant`, Shift, diagonal Stretch and Select warps (a stretch by a multiplies
+    the variance by a^2, in the kernel's coordinates), further blur nodes (variances add) and SE kernels under ScaleTransform /
+    ARDTransform / SelectTransform / with_lengthscale.  Everything else raises NotImplementedError that names blur: any other
+    kernel, products of kernels, a non-diagonal linear map, Periodic, a GibbsKernel, a function-valued scale, a callable prior
+    mean, derivative on either side of the node, patch_convolve or stencil sides, a nested GPPP."""
+    if not callable(variance):
+        v = np.asarray(variance, dtype=np.float64)
+        if v.ndim > 1 or not np.all(np.isfinite(v)) or not np.all(v >= 0.0):
+            raise ValueError("blur: variance must be a finite scalar or vector >= 0, or a callable of the points")
+    return DerivedGP(("blur", f, variance), f.gpc)
+
+
+def blur_variance(variance, X):
+    """the D x n variances of a blur node at the D x n points X"""
+    if callable(variance):
+        S = np.asarray(variance(X), dtype=np.float64)
+    else:
+        v = np.asarray(variance, dtype=np.float64)
+        S = v
+        if v.ndim == 0 or v.shape == (X.shape[0],):        # a scalar, or one variance per coordinate: the same at every point
+            S = np.broadcast_to(v.reshape(-1, 1) if v.ndim == 1 else v, X.shape)
+    if S.shape != X.shape or not np.all(np.isfinite(S)) or not np.all(S >= 0.0):
+        raise ValueError(f"blur: variance must give {X.shape[0]} x {X.shape[1]} finite values >= 0 for points of that shape")
+    return np.array(S, dtype=np.float64)
+
+
+def _blur_mean_check(f):
+    """mean(blur(f), x) == mean(f, x) where every mean below the node is a constant; anything else is refused"""
+    from .gppp import GPPP
+    if isinstance(f, GPPP) or (isinstance(f, AtomicGP) and not isinstance(f.gp, GP)):
+        raise NotImplementedError("blur of a nested GPPP is not supported")
+    if isinstance(f, AtomicGP):
+        if f.gp.mean_spec is not None and not _is_real(f.gp.mean_spec):
+            raise NotImplementedError("blur: a non-constant prior mean below the node is not supported (its smoothed form is "
+                                      "the caller's; a constant mean stays)")
+        return
+    op = f.args[0]
+    if op in ("+known", "*") and not _is_real(f.args[1]):
+        raise NotImplementedError("blur: a function-valued scale or known function below the node is not supported")
+    if op in ("+", "+known", "*", "o", "blur"):   # (everything else is refused where the paths are walked: flatten.py)
+        for g in (f.args[1:3] if op == "+" else (f.args[2],) if op in ("+known", "*") else (f.args[1],)):
+            _blur_mean_check(g)
+
+
 # ---- prior mean (host, O(N) per node) ----------------------------------------------------------
 def mean_vector(f, x):
     """mean(f, x) by the reference's recursion (addition.jl:26,73-74; product.jl:25,54;
@@ -382,6 +434,9 @@ def mean_vector(f, x):
         return out
     if op == "deriv":
         return _deriv_mean(f.args[1], x)
+    if op == "blur":
+        _blur_mean_check(f.args[1])
+        return mean_vector(f.args[1], x)
     if op == "cross":
         return np.concatenate([mean_vector(g, b) for g, b in zip(f.args[1], blocks(x))])
     raise ValueError(op)

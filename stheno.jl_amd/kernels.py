@@ -55,6 +55,12 @@ def apply_chain(chain, X):
             X = X[list(v), :]
         elif kind == "lengthscale":
             X = np.vstack([X, _lengthscale_row(v, X)])     # the Gibbs kind's points: the location, then l(x)
+        elif kind == "blur":
+            # the blur kind's points: the location, then the variances of the footprint (zeros for a view without a node)
+            S = np.zeros(X.shape) if v.S is None else v.S
+            if S.shape != X.shape:
+                raise ValueError(f"blur: variance rows of shape {S.shape} for points of shape {X.shape}")
+            X = np.vstack([X, S])
         elif kind == "sincos":
             # x_d -> [sin 2 pi x_d, cos 2 pi x_d] / (2 r_d): squared distances become sum_d sin^2(pi (x_d - y_d)) / r_d^2,
             # so SE over these points is KernelFunctions' PeriodicKernel(r); rows: the D sines, then the D cosines
@@ -64,6 +70,47 @@ def apply_chain(chain, X):
         else:
             raise ValueError(kind)
     return np.asfortranarray(X)
+
+
+class BlurRows:
+    """what a ("blur", rows) step appends below the location rows (always the last step of its chain): S, the D x n variances
+    in the kernel's coordinates (None: zeros, a view that passed no blur node), and how they came from the outermost node's
+    variances s: S[i] = fac[i] * s[sel[i]] (+ the nested nodes' shares).  Compares by identity: flatten.py hands one object to
+    every path that reads the same view"""
+
+    def __init__(self, S=None, sel=None, fac=None, nrows=0):
+        self.S, self.sel, self.fac, self.nrows = S, sel, fac, nrows
+
+    def through(self, chain):
+        """these rows seen through a kernel's input chain: a diagonal factor a multiplies a variance by a^2, a select selects"""
+        if self.S is None:
+            return self
+        S, sel, fac = self.S, self.sel, self.fac
+        for kind, v in chain:
+            if kind == "select":
+                S, sel, fac = S[list(v), :], sel[list(v)], fac[list(v)]
+                continue
+            if kind == "scale" and np.ndim(v) == 0:
+                a = np.full(S.shape[0], float(v))
+            elif kind == "ard":
+                a = _ard_v(v, S.shape[0])
+            elif kind == "linear" and np.array_equal(_linear_A(v, S.shape[0]), np.diag(np.diag(_linear_A(v, S.shape[0])))):
+                a = np.diag(_linear_A(v, S.shape[0])).copy()   # (a square diagonal matrix)
+            else:
+                raise NotImplementedError(f"blur: the kernel's input transform `{kind}` below the node is not supported (only "
+                                          "ScaleTransform / ARDTransform / SelectTransform / with_lengthscale and diagonal "
+                                          "linear maps keep a Gaussian footprint axis-aligned)")
+            S, fac = (a * a)[:, None] * S, fac * a * a
+        return BlurRows(S, sel, fac, self.nrows)
+
+    def node_cotangent(self, gS):
+        """the cotangent of the outermost node's D x n variances given that of S"""
+        out = np.zeros((self.nrows, gS.shape[1]))
+        np.add.at(out, self.sel, self.fac[:, None] * gS)
+        return out
+
+
+BLUR_ZERO_ROWS = BlurRows()
 
 
 def _lengthscale_row(fn, X):
@@ -116,6 +163,9 @@ def chain_vjp(chain, X, gout, transforms=None):
         elif kind == "lengthscale":
             found.append(g[-1, :].copy())
             g = g[:-1, :]
+        elif kind == "blur":
+            found.append(g[g.shape[0] // 2:, :].copy())
+            g = g[:g.shape[0] // 2, :]
         elif kind == "sincos":
             D = xin.shape[0]
             h = (np.pi / _sincos_r(v, D))[:, None]          # 2 pi / (2 r_d)
