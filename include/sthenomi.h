@@ -191,7 +191,47 @@ enum {
    * the term or on its successor; reserved != 0; a multi-GPU context; a variance that is negative, NaN or infinite (the
    * variance rows of every input a blur term reads are scanned on the host, O(D n)).
    * Taken and refused by the operators exactly as SGP_GIBBS is, the refusals naming "blur". */
-  SGP_BLUR_SE = SGP_SE + 56                  /* 56 */
+  SGP_BLUR_SE = SGP_SE + 56,                 /* 56 */
+  /* The arc-cosine kinds: the covariance of a depth-L fully connected ReLU network in its infinite-width limit (Cho & Saul;
+   * Lee et al.: the NNGP kernel) and that network's neural tangent kernel (Jacot et al.).  A class of their own (arccos.hip):
+   * neither product-path kinds nor one of the classes above; 57 .. 63 and 66 .. 71 stay no kinds.
+   *
+   * A term reads points of dimension D in 1 .. 16, after the caller's transforms; param = L, an integer in 1 .. 16, the
+   * number of hidden layers.  With n_x = sqrt(x'x), n_y = sqrt(y'y), c_0 the cosine of the angle between x and y,
+   *     kappa_0(c) = 1 - acos(c) / pi,     kappa_1(c) = (sqrt(1 - c^2) + (pi - acos c) c) / pi,
+   *     c_{l+1} = kappa_1(c_l),            t_0 = c_0,  t_{l+1} = c_{l+1} + t_l kappa_0(c_l)          l = 0 .. L - 1,
+   *     K_ij = coef rs_i cs_j n_x n_y c_L  (SGP_NNGP)         K_ij = coef rs_i cs_j n_x n_y t_L  (SGP_NTK)
+   * the weight-variance-2 normalisation, under which norms pass through the layers unchanged: a coincident pair has c_l = 1
+   * at every layer and t_L = L + 1.  There are no bias terms inside the network; a first-layer bias variance b is a constant
+   * coordinate sqrt(b) appended to every point (the host's kernels do that).
+   *
+   * Evaluation order: the recursion is carried in the half angle h = theta / 2, not in c (near-parallel points have 1 - c_0
+   * below 2^-53, and the NTK needs that angle through kappa_0).  Per point, once: n = sqrt(sum_d x_d^2), d ascending by fma,
+   * and the unit vector x_d / n (exact zeros for n = 0).  Per pair: h_0 = atan2(|xh - yh|, |xh + yh|), the two sums d
+   * ascending by fma; per layer s = 2 sin^2 h - (sin 2h - 2h cos 2h) / pi with sin 2h = 2 sin h cos h and cos 2h = 1 -
+   * 2 sin^2 h, c_{l+1} = 1 - s, kappa_0 = 1 - 2h / pi, h <- asin(sqrt(s / 2)), t <- fma(t, kappa_0, c_{l+1}), t_0 = 1 - 2 sin^2
+   * h_0.  The entry is fma((n_x n_y) T, (coef rs_i) cs_j, acc), the terms of a pair in the caller's order.  Terms of one pair
+   * that follow each other, share points, scale vectors and dimension and have depths that do not decrease -- NNGP and NTK
+   * alike -- share ONE recursion per point pair (arccos.hip): a sum over depths 1 .. L costs L layer steps per entry.
+   *
+   * Exact values: a pair of bit-equal points gives c_L = 1 and t_L = L + 1 exactly; a point of norm 0 gives an exact 0;
+   * sgp_kernelmatrix_diag equals the diagonal of sgp_kernelmatrix bit for bit; every step is symmetric in the two points, so a
+   * symmetric spec is exactly symmetric; padding coordinates contribute exact zeros.  The error model (docs/03_kernels.md,
+   * 3.2j) holds for points whose squared norm neither overflows nor underflows (norms in [1e-150, 1e150]).
+   *
+   * Gradients: grad_coef as for every kind.  grad_inscale: K is homogeneous of degree 2 in a common scale of both inputs, so
+   * it is 2 K_ij contracted with the cotangent.  grad_inputs of sgp_logpdf_grad_x (D rows per point, G the cotangent), with
+   * T = c_L or t_L and T' = dT / dc_0 by c'_{l+1} = kappa_0(c_l) c'_l, t'_{l+1} = c'_{l+1} + t'_l kappa_0(c_l) +
+   * t_l c'_l / (pi sin theta_l), c'_0 = t'_0 = 1:
+   *     row side, column i:  sum_j G_ij coef rs_i cs_j n_y [ (T - c_0 T') xh + T' yh ]
+   * and the mirror image for the column side.  The NTK is not differentiable where sin theta_l = 0 (parallel or antipodal
+   * points), as Matern-1/2 is not at coincident points: there the 1 / (pi sin theta_l) term counts 0.
+   *
+   * Refused by dspec creation, every text naming "arc-cosine": a param that is no integer in 1 .. 16 (NaN included); points
+   * of dimension > 16; SGP_KIND_TIMES_PREV on the term or on its successor; reserved != 0; a multi-GPU context.
+   * Taken and refused by the operators exactly as SGP_GIBBS is, the refusals naming "arc-cosine". */
+  SGP_NNGP = SGP_SE + 64,                    /* 64 */
+  SGP_NTK = SGP_SE + 65                      /* 65 */
 };
 /* Chain flag, or-ed into sgp_term.kind: the term multiplies the chain begun by the nearest term before it, in the same block
  * pair, that does not carry the flag.  Semantics, limits and the operators that take such specs: include/sthenomi_kprod.h. */
@@ -224,7 +264,8 @@ typedef struct {
   double coef;        /* product of scalar scales (may be negative)                      */
   double param;       /* SGP_CONST: c; SGP_RQ: alpha; SGP_LINEAR: c; SGP_GAMMAEXP: gamma; SGP_MATERN_NU: nu;
                          SGP_FBM: h; SGP_WIENER: i; SGP_PIECEWISE0 .. 3: j; SGP_DERIV_*: 17 a + b; SGP_GIBBS: p;
-                         SGP_ADDITIVE_*: the order r; ignored by the other kinds (SGP_BLUR_SE among them) */
+                         SGP_ADDITIVE_*: the order r; SGP_NNGP, SGP_NTK: the depth L; ignored by the other kinds
+                         (SGP_BLUR_SE among them) */
   const double* row_scale; /* host, length = row block length, or NULL (== ones)         */
   const double* col_scale; /* host, length = col block length, or NULL                   */
 } sgp_term;

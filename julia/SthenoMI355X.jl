@@ -108,6 +108,9 @@ const SGP_GIBBS = 40
 const SGP_ADDITIVE = 48
 # the blur kind (include/sthenomi.h: points of dimension 2 D, the locations and below them the footprint's variances)
 const SGP_BLUR_SE = 56
+# the arc-cosine kinds (include/sthenomi.h: deep ReLU-network kernels, param = the number of hidden layers L in 1 .. 16)
+const SGP_NNGP = 64
+const SGP_NTK = 65
 # derivative kinds (SGP_DERIV_SE = 32, SGP_DERIV_MATERN32 = 34, SGP_DERIV_MATERN52 = 35: 32 + the base kind, param = 17 a + b)
 # kinds of x'y, x'x and y'y (SGP_NEURALNET = 24, SGP_FBM = 25 with param = h in (0, 1], SGP_EXPONENTIATED = 26)
 leaf(::NeuralNetworkKernel) = [(24, 1.0, 0.0, Chain())]

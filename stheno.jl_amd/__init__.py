@@ -12,7 +12,7 @@ from .kernels import (ARDTransform, CosineKernel, ExponentiatedKernel, FBMKernel
                       SelectTransform, gaborkernel, spectral_mixture_kernel, spectral_mixture_product_kernel)
 from .kernels import PiecewisePolynomialKernel, RationalKernel, WienerKernel  # noqa: F401
 from .kernels import AdditiveKernel, additive_kernel  # noqa: F401
-from .kernels import (GibbsKernel, ConstantKernel, ExponentialKernel, KernelProduct, KernelSum, LinearKernel, Matern12Kernel,  # noqa: F401
+from .kernels import (GibbsKernel, NNGPKernel, NTKKernel, ConstantKernel, ExponentialKernel, KernelProduct, KernelSum, LinearKernel, Matern12Kernel,  # noqa: F401
                       Matern32Kernel, Matern52Kernel, PeriodicKernel, PeriodicTransform, PolynomialKernel,
                       RationalQuadraticKernel, ScaledKernel, ScaleTransform,
                       ScaleTransformedKernel, TransformedKernel,

@@ -48,6 +48,7 @@ using namespace sgp;
     CHECK_ARG(!((ctx)->multi && spec_has_gibbs(sp)), sgp::GIBBS_REFUSAL_MULTI); /* (gibbs.hip: likewise) */  \
     CHECK_ARG(!((ctx)->multi && spec_has_additive(sp)), sgp::ADDITIVE_REFUSAL_MULTI); /* (additive.hip) */   \
     CHECK_ARG(!((ctx)->multi && spec_has_blur(sp)), sgp::BLUR_REFUSAL_MULTI); /* (blur.hip) */               \
+    CHECK_ARG(!((ctx)->multi && spec_has_arccos(sp)), sgp::ARCCOS_REFUSAL_MULTI); /* (arccos.hip) */         \
     CHECK_ARG(!((ctx)->multi && spec_has_kprod(sp)),                                                         \
               "spec: product chains and the RQ / LINEAR kinds are not supported on a multi-GPU context");    \
   } while (0)
@@ -374,6 +375,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   // an input's variance rows gave (blur_variance_scan; -1: no blur term reads it)
   std::vector<char> is_bl(std::max(1, nterms), 0);
   std::vector<int> in_blur(std::max(1, sp->n_inputs), -1);
+  // terms of the arc-cosine kinds (include/sthenomi.h: SGP_NNGP, SGP_NTK): likewise (arccos.hip, arccos_kinds.h)
+  std::vector<char> is_ac(std::max(1, nterms), 0);
   std::vector<size_t> nuc_off(std::max(1, nterms), (size_t)-1);   // SGP_MATERN_NU: the term's constants of nu (kprod.hip)
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
@@ -383,7 +386,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
         const sgp_term& T = sp->terms[t];
         if (T.kind < 0 || (T.kind & ~(0xff | SGP_KIND_TIMES_PREV)) ||
             !(kp_kind_known(T.kind & 0xff) || deriv_kind_known(T.kind & 0xff) || gibbs_kind_known(T.kind & 0xff) ||
-              additive_kind_known(T.kind & 0xff) || blur_kind_known(T.kind & 0xff)))
+              additive_kind_known(T.kind & 0xff) || blur_kind_known(T.kind & 0xff) || arccos_kind_known(T.kind & 0xff)))
           return fail("spec: unknown kernel kind");
         const bool cont = (T.kind & SGP_KIND_TIMES_PREV) != 0;
         const bool next_cont = t + 1 < sp->term_ptr[p + 1] && sp->terms[t + 1].kind >= 0 &&
@@ -425,7 +428,16 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           }
           ++ds->n_blur;
         }
-        is_kp[t] = !is_dv[t] && !is_gb[t] && !is_ad[t] && !is_bl[t] && (cont || next_cont || (T.kind & 0xff) > SGP_CONST);
+        is_ac[t] = arccos_kind_known(T.kind & 0xff);
+        if (is_ac[t]) {
+          if (cont || next_cont) return fail(ARCCOS_REFUSAL_CHAIN);
+          if (T.reserved) return fail(ARCCOS_REFUSAL_RESERVED);
+          for (const int k : {T.row_input, T.col_input})
+            if (k >= 0 && k < sp->n_inputs)   // (else refused below)
+              if (const char* refusal = arccos_param_refusal(T.param, (long)sp->inputs[k].dim)) return fail(refusal);
+          ++ds->n_arccos;
+        }
+        is_kp[t] = !is_dv[t] && !is_gb[t] && !is_ad[t] && !is_bl[t] && !is_ac[t] && (cont || next_cont || (T.kind & 0xff) > SGP_CONST);
         if (is_kp[t]) {
           if (cont && t == sp->term_ptr[p])
             return fail("spec: product chain: a continuation (SGP_KIND_TIMES_PREV) cannot be the first term of a block pair");
@@ -498,7 +510,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
           cs_len[t] = ds->col_len[J];
           cs_off[t] = place(sizeof(double) * (size_t)cs_len[t]);
         }
-        if (!T.reserved && !is_kp[t] && !is_dv[t] && !is_gb[t] && !is_ad[t] && !is_bl[t]) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
+        if (!T.reserved && !is_kp[t] && !is_dv[t] && !is_gb[t] && !is_ad[t] && !is_bl[t] && !is_ac[t]) ds->pair_dmax[p] = std::max(ds->pair_dmax[p], pow2ceil((int)ri.dim));
       }
     }
   if (ds->n_kprod && (ctx->multi || ctx->multi_rank))
@@ -507,6 +519,7 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   if (ds->n_gibbs && (ctx->multi || ctx->multi_rank)) return fail(GIBBS_REFUSAL_MULTI);
   if (ds->n_additive && (ctx->multi || ctx->multi_rank)) return fail(ADDITIVE_REFUSAL_MULTI);
   if (ds->n_blur && (ctx->multi || ctx->multi_rank)) return fail(BLUR_REFUSAL_MULTI);
+  if (ds->n_arccos && (ctx->multi || ctx->multi_rank)) return fail(ARCCOS_REFUSAL_MULTI);
   const size_t terms_off = place(sizeof(DevTerm) * (size_t)std::max(1, nterms));
   // ---- one cached device block, one pinned staging buffer
   char* d_base = (char*)pool_alloc(ctx, total);
@@ -541,11 +554,12 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
   for (int I = 0; I < ds->nrb; ++I)
     for (int J = 0; J < ds->ncb; ++J) {
       int p = I * ds->ncb + J;
-      // plain | patch | stencil | derivative | Gibbs | additive | blur | product chains within every pair (the caller's order
-      // when the spec has none of the last seven; chains and the groups of derivative, Gibbs, additive and blur terms stay
-      // contiguous and in the caller's order: the passes below are stable)
+      // plain | patch | stencil | derivative | Gibbs | additive | blur | arc-cosine | product chains within every pair (the
+      // caller's order when the spec has none of the last eight; chains and the groups of derivative, Gibbs, additive, blur and
+      // arc-cosine terms stay contiguous and in the caller's order: the passes below are stable)
       auto cls = [&](int t) {
-        if (is_kp[t]) return 7;
+        if (is_kp[t]) return 8;
+        if (is_ac[t]) return 7;
         if (is_bl[t]) return 6;
         if (is_ad[t]) return 5;
         if (is_gb[t]) return 4;
@@ -556,8 +570,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
         return ctx->conv_geoms[id - 1].st > 0 ? 2 : 1;
       };
       std::vector<int> order;
-      int ncls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int pass = 0; pass < 8; ++pass)
+      int ncls[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      for (int pass = 0; pass < 9; ++pass)
         for (int t = sp->term_ptr[p]; t < sp->term_ptr[p + 1]; ++t)
           if (cls(t) == pass) order.push_back(t), ++ncls[pass];
       ds->pair_nplain.push_back(ncls[0]);
@@ -566,7 +580,8 @@ static int dspec_create(sgp_ctx* ctx, const sgp_cov_spec* sp, sgp_dspec** out) {
       ds->pair_ngibbs.push_back(ncls[4]);
       ds->pair_nadditive.push_back(ncls[5]);
       ds->pair_nblur.push_back(ncls[6]);
-      ds->pair_nkprod.push_back(ncls[7]);
+      ds->pair_narccos.push_back(ncls[7]);
+      ds->pair_nkprod.push_back(ncls[8]);
       for (size_t k = 0; k < order.size(); ++k) {
         const int t = order[k], pos = sp->term_ptr[p] + (int)k;
         const sgp_term& T = sp->terms[t];
@@ -665,7 +680,8 @@ extern "C" int sgp_dspec_destroy(sgp_dspec* ds) {
 // which terms of pair p are what (spec_segments.h), from the counts dspec_create fills for every spec
 static inline PairSegs pair_segments(const sgp_dspec* ds, int p) {
   return pair_segments(ds->term_ptr.data(), ds->pair_nplain.data(), ds->pair_npatch.data(), ds->pair_nderiv.data(),
-                       ds->pair_ngibbs.data(), ds->pair_nadditive.data(), ds->pair_nblur.data(), ds->pair_nkprod.data(), p);
+                       ds->pair_ngibbs.data(), ds->pair_nadditive.data(), ds->pair_nblur.data(), ds->pair_narccos.data(),
+                       ds->pair_nkprod.data(), p);
 }
 // the chain whose head sits at device position t: one past its last factor, and its DMAX
 static inline int chain_end(const sgp_dspec* ds, int t, int t1) { return chain_end(ds->h_terms.data(), t, t1); }
@@ -692,8 +708,8 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
       L.r_first = trf, L.c_first = tcf, L.r_cnt = trl - trf, L.c_cnt = tcl - tcf;
       int p = I * ds->ncb + J;
       // plain | patch (conv.hip) | stencil (stencil.hip) | derivative (deriv.hip) | Gibbs (gibbs.hip) | additive
-      // (additive.hip) | blur (blur.hip) | chains (kprod.hip)
-      const auto [t0, tp, ts, tk, t1, td, tg, ta, tb] = pair_segments(ds, p);
+      // (additive.hip) | blur (blur.hip) | arc-cosine (arccos.hip) | chains (kprod.hip)
+      const auto [t0, tp, ts, tk, t1, td, tg, ta, tb, tn] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = assemble_terms_per_launch(dmax);  // terms per launch: <= 64 KiB of LDS
       L.first = true;
@@ -732,10 +748,16 @@ static int assemble(const sgp_dspec* ds, double* Kv, long ld, long tile_r_lo, lo
         CHECK_RC(launch_assemble_additive(L, ds->h_terms.data() + t, ds->d_terms + t, cnt, s));
         t += cnt;
       }
-      for (int t = tb; t < tk;) {   // one group per launch: one exponential per point pair for all its terms (blur.hip)
-        const int cnt = blur_group(ds->h_terms.data(), t, tk);
+      for (int t = tb; t < tn;) {   // one group per launch: one exponential per point pair for all its terms (blur.hip)
+        const int cnt = blur_group(ds->h_terms.data(), t, tn);
         L.first = t == t0;
         CHECK_RC(launch_assemble_blur(L, ds->h_terms.data() + t, ds->d_terms + t, cnt, s));
+        t += cnt;
+      }
+      for (int t = tn; t < tk;) {   // one group per launch: one layer recursion per point pair for all its depths (arccos.hip)
+        const int cnt = arccos_group(ds->h_terms.data(), t, tk);
+        L.first = t == t0;
+        CHECK_RC(launch_assemble_arccos(L, ds->h_terms.data() + t, ds->d_terms + t, cnt, s));
         t += cnt;
       }
       for (int t = tk; t < t1;) {   // whole chains per launch, as many as fit its LDS (kprod.hip: kprod_group)
@@ -1688,7 +1710,7 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
   for (int I = 0; I < ds->nrb; ++I) {
     CHECK_ARG(ds->row_len[I] == ds->col_len[I], "kernelmatrix_diag: block lengths differ");
     int p = I * ds->ncb + I;
-    const auto [t0, tp, ts, tk, t1, td, tg, ta, tb] = pair_segments(ds, p);
+    const auto [t0, tp, ts, tk, t1, td, tg, ta, tb, tn] = pair_segments(ds, p);
     if (tp < ts) {   // patch terms (conv.hip), in one launch with the plain terms in front of them
       int max_d = 1, d_all = -1, max_px = 1;
       for (int t = tp; t < ts; ++t) {
@@ -1722,9 +1744,14 @@ static int diag_of_spec(sgp_ctx* ctx, const sgp_dspec* ds, double* d_out, hipStr
       CHECK_RC(launch_diag_additive(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
       t += cnt;
     }
-    for (int t = tb; t < tk;) {   // blur terms, likewise
-      const int cnt = blur_group(ds->h_terms.data(), t, tk);
+    for (int t = tb; t < tn;) {   // blur terms, likewise
+      const int cnt = blur_group(ds->h_terms.data(), t, tn);
       CHECK_RC(launch_diag_blur(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
+      t += cnt;
+    }
+    for (int t = tn; t < tk;) {   // arc-cosine terms, likewise
+      const int cnt = arccos_group(ds->h_terms.data(), t, tk);
+      CHECK_RC(launch_diag_arccos(d_out + ds->row_off[I], ds->row_len[I], ds->h_terms.data() + t, ds->d_terms + t, cnt, 1, s));
       t += cnt;
     }
     for (int t = tk; t < t1;) {   // product chains, in the launch groups of the matrix assembly: the same sums
@@ -1997,8 +2024,8 @@ struct StencilWo {
 // dgp (NULL: not asked for): d / d param per term, which for the plain terms is non-zero for SGP_CONST alone -- those run
 // through the chain kernel once more, as chains of length one, for that entry, between the stencil terms and the chains.
 static GradLeave pool_leave() {   // what sgp_logpdf_grad_batch / _pool carry beyond the plain terms: derivative, Gibbs,
-  GradLeave l;                    // additive and blur terms
-  l.deriv = l.gibbs = l.additive = l.blur = true;
+  GradLeave l;                    // additive, blur and arc-cosine terms
+  l.deriv = l.gibbs = l.additive = l.blur = l.arccos = true;
   return l;
 }
 static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const double* alpha, long n_tr, long n_tc,
@@ -2016,6 +2043,8 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
   if (ds->n_additive) need = std::max(need, grad_additive_partials(n_tr, n_tc));
   CHECK_ARG(leave.blur || !ds->n_blur, "gradient contraction: blur terms are not supported here");
   if (ds->n_blur) need = std::max(need, grad_blur_partials(n_tr, n_tc));
+  CHECK_ARG(leave.arccos || !ds->n_arccos, "gradient contraction: arc-cosine terms are not supported here");
+  if (ds->n_arccos) need = std::max(need, grad_arccos_partials(n_tr, n_tc));
   for (int p = 0; p < ds->nrb * ds->ncb; ++p) {   // the partial sums of the largest patch or stencil term
     const int I = p / ds->ncb, J = p % ds->ncb;
     const PairSegs g = pair_segments(ds, p);
@@ -2031,7 +2060,7 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
       long r0 = ds->row_off[I], nr = ds->row_len[I], c0 = ds->col_off[J], nc = ds->col_len[J];
       long trf = r0 / TILE, trl = (r0 + nr - 1) / TILE + 1, tcf = c0 / TILE, tcl = (c0 + nc - 1) / TILE + 1;
       int p = I * ds->ncb + J;
-      const auto [t0, tp, ts, tk, t1, td, tg, ta, tb] = pair_segments(ds, p);
+      const auto [t0, tp, ts, tk, t1, td, tg, ta, tb, tn] = pair_segments(ds, p);
       int dmax = ds->pair_dmax[p];
       int per = std::min(8, std::max(1, 64 / dmax));
       for (int t = t0; t < tp; t += per) {
@@ -2062,10 +2091,16 @@ static int contract_spec(const sgp_dspec* ds, const double* Gm, long ldg, const 
                                       trl - trf, tcl - tcf, dpart.p, dgc + t, dgs + t, s));
         t += cnt;
       }
-      for (int t = tb; t < tk;) {   // blur terms, likewise (blur.hip)
-        const int cnt = blur_group(ds->h_terms.data(), t, tk);
+      for (int t = tb; t < tn;) {   // blur terms, likewise (blur.hip)
+        const int cnt = blur_group(ds->h_terms.data(), t, tn);
         CHECK_RC(launch_grad_blur(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, trf, tcf, trl - trf,
                                   tcl - tcf, dpart.p, dgc + t, dgs + t, s));
+        t += cnt;
+      }
+      for (int t = tn; t < tk;) {   // arc-cosine terms, likewise (arccos.hip)
+        const int cnt = arccos_group(ds->h_terms.data(), t, tk);
+        CHECK_RC(launch_grad_arccos(Gm, ldg, alpha, r0, nr, c0, nc, ds->h_terms.data() + t, ds->d_terms + t, cnt, trf, tcf,
+                                    trl - trf, tcl - tcf, dpart.p, dgc + t, dgs + t, s));
         t += cnt;
       }
       for (int t = t0; dgp && t < tp; ++t)
@@ -2176,6 +2211,7 @@ static int input_pass(const sgp_dspec* ds, const InputPass& q, hipStream_t s) {
   CHECK_ARG(!ds->n_gibbs || !(b.want[0] || b.want[1]), "scale gradients through Gibbs terms are not supported");
   CHECK_ARG(!ds->n_additive || !(b.want[0] || b.want[1]), "scale gradients through additive terms are not supported");
   CHECK_ARG(!ds->n_blur || !(b.want[0] || b.want[1]), "scale gradients through blur terms are not supported");
+  CHECK_ARG(!ds->n_arccos || !(b.want[0] || b.want[1]), "scale gradients through arc-cosine terms are not supported");
   const bool points = b.want_x != nullptr;
   const double w = q.symmetric ? 2.0 : 1.0;
   for (int I = 0; I < ds->nrb; ++I)
@@ -2227,11 +2263,20 @@ static int input_pass(const sgp_dspec* ds, const InputPass& q, hipStream_t s) {
         t += cnt;
       }
       // a group of blur terms: one launch, variance rows included (blur.hip); symmetric cotangents only, likewise
-      for (int t = g.tb; points && t < g.tk;) {
-        const int cnt = blur_group(ds->h_terms.data(), t, g.tk);
+      for (int t = g.tb; points && t < g.tn;) {
+        const int cnt = blur_group(ds->h_terms.data(), t, g.tn);
         CHECK_ARG(q.symmetric, "input-point gradients through blur terms take a symmetric cotangent only");
         CHECK_RC(launch_grad_blur_inputs(q.Gm, 1, q.ldg, q.alpha, r0, nr, c0, nc, ds->h_terms[t], ds->d_terms + t, cnt, w,
                                          b.input(ds->term_row_input[t]), s));
+        t += cnt;
+      }
+      // a group of arc-cosine terms: one launch, one recursion per pair for all its depths (arccos.hip); symmetric cotangents
+      // only, likewise
+      for (int t = g.tn; points && t < g.tk;) {
+        const int cnt = arccos_group(ds->h_terms.data(), t, g.tk);
+        CHECK_ARG(q.symmetric, "input-point gradients through arc-cosine terms take a symmetric cotangent only");
+        CHECK_RC(launch_grad_arccos_inputs(q.Gm, 1, q.ldg, q.alpha, r0, nr, c0, nc, ds->h_terms[t], ds->h_terms.data() + t,
+                                           ds->d_terms + t, cnt, w, b.input(ds->term_row_input[t]), s));
         t += cnt;
       }
       for (int t = g.tk; t < g.t1;) {   // a chain: every factor's input and the head's scale in one launch per side (kprod.hip)
@@ -2287,6 +2332,12 @@ static int logpdf_grad_core(sgp_ctx* ctx, const LogpdfGradArgs& a) {
             "sgp_logpdf_grad_xs with scale outputs / _param / _conv / _stencil / _stencil_wo: scale, parameter, patch and stencil "
             "gradients through blur terms are not supported: sgp_logpdf_grad_x returns grad_coef, grad_inscale and grad_inputs");
   CHECK_ARG(!(ctx->multi && spec_has_blur(a.spec)), BLUR_REFUSAL_MULTI);
+  // arc-cosine terms (arccos.hip): the same entry points
+  CHECK_ARG(a.leave.arccos || !spec_has_arccos(a.spec),
+            "sgp_logpdf_grad_xs with scale outputs / _param / _conv / _stencil / _stencil_wo: scale, parameter, patch and stencil "
+            "gradients through arc-cosine terms are not supported: sgp_logpdf_grad_x returns grad_coef, grad_inscale and "
+            "grad_inputs");
+  CHECK_ARG(!(ctx->multi && spec_has_arccos(a.spec)), ARCCOS_REFUSAL_MULTI);
   CHECK_RC(check_grad_leave(ctx, "sgp_logpdf_grad", a.leave, a.spec));
   CHECK_ARG(!(a.grad_inputs || a.grad_rowscale) || a.leave.kprod || a.leave.stencil || !spec_has_kprod(a.spec),
             "sgp_logpdf_grad_x / _xs: input-point and scale gradients through product chains and the RQ / LINEAR kinds are "
@@ -2435,8 +2486,8 @@ extern "C" int sgp_logpdf_grad_xs(sgp_ctx* ctx, const sgp_cov_spec* spec, const 
   LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                                       grad_inscale);
   a.grad_inputs = grad_inputs, a.grad_rowscale = grad_rowscale;
-  // (Gibbs, additive and blur terms: the input points, no scale outputs)
-  a.leave.gibbs = a.leave.additive = a.leave.blur = grad_rowscale == nullptr;
+  // (Gibbs, additive, blur and arc-cosine terms: the input points, no scale outputs)
+  a.leave.gibbs = a.leave.additive = a.leave.blur = a.leave.arccos = grad_rowscale == nullptr;
   return drv_logpdf_grad(ctx, a);
 }
 
@@ -2447,7 +2498,7 @@ extern "C" int sgp_logpdf_grad(sgp_ctx* ctx, const sgp_cov_spec* spec, const dou
   LogpdfGradArgs a = logpdf_grad_args(spec, mean, noise_kind, noise, y, logpdf_out, grad_y, grad_mean, grad_noise, grad_coef,
                                       grad_inscale);
   a.leave.deriv = true;   // (this entry point alone carries derivative terms)
-  a.leave.gibbs = a.leave.additive = a.leave.blur = true;
+  a.leave.gibbs = a.leave.additive = a.leave.blur = a.leave.arccos = true;
   return drv_logpdf_grad(ctx, a);
 }
 
@@ -2462,6 +2513,7 @@ extern "C" int sgp_logpdf_grad_x(sgp_ctx* ctx, const sgp_cov_spec* spec, const d
   a.leave.gibbs = true;   // (Gibbs terms: D + 1 rows per point, the last the lengthscale's)
   a.leave.additive = true;
   a.leave.blur = true;   // (blur terms: 2 D rows per point, the last D the variances')
+  a.leave.arccos = true;
   return drv_logpdf_grad(ctx, a);
 }
 
@@ -3909,6 +3961,8 @@ static int elbo_grad_core(sgp_ctx* ctx, const ElboGradArgs& a, const ElboGradSha
             "sgp_elbo_grad: gradients of the ELBO through Gibbs terms are not supported");
   CHECK_ARG(!spec_has_blur(a.zz) && !spec_has_blur(a.xz),
             "sgp_elbo_grad: gradients of the ELBO through blur terms are not supported");
+  CHECK_ARG(!spec_has_arccos(a.zz) && !spec_has_arccos(a.xz),
+            "sgp_elbo_grad: gradients of the ELBO through arc-cosine terms are not supported");
   CHECK_ARG(!spec_has_additive(a.zz) && !spec_has_additive(a.xz),
             "sgp_elbo_grad: gradients of the ELBO through additive terms are not supported");
   CHECK_ARG(!spec_has_deriv(a.zz) && !spec_has_deriv(a.xz),
@@ -4226,6 +4280,8 @@ static int diag_grad_core(sgp_ctx* ctx, const DiagGradArgs& a) {
             "sgp_kernelmatrix_diag_grad: gradients of the diagonal through Gibbs terms are not supported");
   CHECK_ARG(!spec_has_blur(a.spec),
             "sgp_kernelmatrix_diag_grad: gradients of the diagonal through blur terms are not supported");
+  CHECK_ARG(!spec_has_arccos(a.spec),
+            "sgp_kernelmatrix_diag_grad: gradients of the diagonal through arc-cosine terms are not supported");
   CHECK_ARG(!spec_has_additive(a.spec),
             "sgp_kernelmatrix_diag_grad: gradients of the diagonal through additive terms are not supported");
   CHECK_ARG(!spec_has_deriv(a.spec),

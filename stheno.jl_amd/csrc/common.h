@@ -273,6 +273,20 @@ int launch_grad_blur(const double* Kinv, long ldk, const double* alpha, long r0,
 int launch_grad_blur_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
                             const DevTerm& T, const DevTerm* d_terms, int nterms, double scale, double* gx, hipStream_t s);
 
+// arccos.hip: the arc-cosine kinds (include/sthenomi.h: SGP_NNGP, SGP_NTK), a term class of its own.  A launch carries ONE group
+// of a pair's arc-cosine terms (arccos_kinds.h: arccos_group -- the same points and scale vectors, depths that do not decrease;
+// the terms differ in (kind, coef, param)).  As their additive counterparts above
+int launch_assemble_arccos(const AsmLaunch& L, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, hipStream_t s);
+int launch_diag_arccos(double* out, long n, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, int accumulate,
+                       hipStream_t s);
+long grad_arccos_partials(long trc, long tcc);
+int launch_grad_arccos(const double* Kinv, long ldk, const double* alpha, long r0, long nr, long c0, long nc,
+                       const DevTerm* h_terms, const DevTerm* d_terms, int nterms, long trf, long tcf, long trc, long tcc,
+                       double* partials, double* out_coef, double* out_scale, hipStream_t s);
+int launch_grad_arccos_inputs(const double* Gm, long sr, long sc, const double* alpha, long r0, long nr, long c0, long nc,
+                              const DevTerm& T, const DevTerm* h_terms, const DevTerm* d_terms, int nterms, double scale,
+                              double* gx, hipStream_t s);
+
 void set_error(const std::string& s);
 
 #define SGP_HIP(expr)                                                                    \

@@ -7,6 +7,7 @@
 #include "../../include/sthenomi_bench.h"
 #include "deriv_kinds.h"
 #include "additive_kinds.h"
+#include "arccos_kinds.h"
 #include "blur_kinds.h"
 #include "gibbs_kinds.h"
 
@@ -62,6 +63,7 @@ struct GradLeave {
   bool deriv = false;     // derivative terms (include/sthenomi.h: SGP_DERIV_*): sgp_logpdf_grad and its batch / pool forms alone
   bool additive = false;  // additive terms (include/sthenomi.h: SGP_ADDITIVE_*): the entry points that carry Gibbs terms
   bool blur = false;      // blur terms (include/sthenomi.h: SGP_BLUR_SE): likewise
+  bool arccos = false;    // arc-cosine terms (include/sthenomi.h: SGP_NNGP, SGP_NTK): likewise
   bool gibbs = false;     // Gibbs terms (include/sthenomi.h: SGP_GIBBS): those, and sgp_logpdf_grad_x / _xs without scale outputs
 };
 // sgp_logpdf_grad / _x / _xs / _param / _param_xs / _conv / _stencil / _stencil_wo
@@ -470,15 +472,26 @@ inline bool spec_has_blur(const sgp_cov_spec* sp) {
   return false;
 }
 
+// a term of the arc-cosine kinds (include/sthenomi.h: SGP_NNGP, SGP_NTK; arccos.hip): likewise
+inline bool term_is_arccos(const sgp_term& T) { return T.kind >= 0 && sgp::arccos_kind_known(T.kind & 0xff); }
+inline bool spec_has_arccos(const sgp_cov_spec* sp) {
+  if (!sp || !sp->term_ptr || !sp->terms) return false;
+  const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
+  for (int t = 0; t < n; ++t)
+    if (term_is_arccos(sp->terms[t])) return true;
+  return false;
+}
+
 // a term of a product chain (include/sthenomi_kprod.h) or of a kind only kprod.hip evaluates (the derivative kinds are
-// deriv.hip's, the Gibbs kind gibbs.hip's, the additive kinds additive.hip's, the blur kind blur.hip's)
+// deriv.hip's, the Gibbs kind gibbs.hip's, the additive kinds additive.hip's, the blur kind blur.hip's, the arc-cosine kinds
+// arccos.hip's)
 inline bool spec_has_kprod(const sgp_cov_spec* sp) {
   if (!sp || !sp->term_ptr || !sp->terms) return false;
   const int n = sp->term_ptr[(long)sp->n_row_blocks * sp->n_col_blocks];
   for (int t = 0; t < n; ++t)
     if ((sp->terms[t].kind & SGP_KIND_TIMES_PREV) || ((sp->terms[t].kind & 0xff) > SGP_CONST && !term_is_deriv(sp->terms[t]) &&
                                                    !term_is_gibbs(sp->terms[t]) && !term_is_additive(sp->terms[t]) &&
-                                                   !term_is_blur(sp->terms[t])))
+                                                   !term_is_blur(sp->terms[t]) && !term_is_arccos(sp->terms[t])))
       return true;
   return false;
 }
@@ -521,5 +534,8 @@ struct sgp_dspec {
   // blur terms (blur.hip): between the additive terms and the chains of their pair, likewise; n_blur == 0: none
   std::vector<int> pair_nblur;
   int n_blur = 0;
+  // arc-cosine terms (arccos.hip): between the blur terms and the chains of their pair, likewise; n_arccos == 0: none
+  std::vector<int> pair_narccos;
+  int n_arccos = 0;
   std::vector<int> term_src;           // index in the caller's spec->terms of the term at each device position
 };

@@ -518,6 +518,7 @@ extern "C" int sgp_logpdf_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const doub
               "sgp_logpdf_f32: noise kind must be SCALAR or DIAG");
   F_CHECK_ARG(!spec_has_gibbs(spec), "sgp_logpdf_f32: Gibbs terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_blur(spec), "sgp_logpdf_f32: blur terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_arccos(spec), "sgp_logpdf_f32: arc-cosine terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_additive(spec), "sgp_logpdf_f32: additive terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_deriv(spec), "sgp_logpdf_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_logpdf_f32: stencil terms have no fp32 path: use the fp64 entry point");
@@ -598,6 +599,7 @@ extern "C" int sgp_kernelmatrix_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, floa
   F_CHECK_ARG(ctx && spec && K, "sgp_kernelmatrix_f32: NULL argument");
   F_CHECK_ARG(!spec_has_gibbs(spec), "sgp_kernelmatrix_f32: Gibbs terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_blur(spec), "sgp_kernelmatrix_f32: blur terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_arccos(spec), "sgp_kernelmatrix_f32: arc-cosine terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_additive(spec), "sgp_kernelmatrix_f32: additive terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_deriv(spec), "sgp_kernelmatrix_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_kernelmatrix_f32: stencil terms have no fp32 path: use the fp64 entry point");
@@ -710,6 +712,7 @@ extern "C" int sgp_rand_f32(sgp_ctx* ctx, const sgp_cov_spec* spec, const double
   F_CHECK_ARG(noise_kind == SGP_NOISE_SCALAR || noise_kind == SGP_NOISE_DIAG, "sgp_rand_f32: noise kind must be SCALAR or DIAG");
   F_CHECK_ARG(!spec_has_gibbs(spec), "sgp_rand_f32: Gibbs terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_blur(spec), "sgp_rand_f32: blur terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_arccos(spec), "sgp_rand_f32: arc-cosine terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_additive(spec), "sgp_rand_f32: additive terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_deriv(spec), "sgp_rand_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec), "sgp_rand_f32: stencil terms have no fp32 path: use the fp64 entry point");
@@ -770,6 +773,7 @@ extern "C" int sgp_posterior_mean_var_f32(sgp_ctx* ctx, const sgp_cov_spec* spec
   F_CHECK_ARG(!var_out || prior_ss, "sgp_posterior_mean_var_f32: prior_ss spec required for var");
   F_CHECK_ARG(!spec_has_gibbs(spec) && !spec_has_gibbs(cross) && !spec_has_gibbs(prior_ss), "sgp_posterior_mean_var_f32: Gibbs terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_blur(spec) && !spec_has_blur(cross) && !spec_has_blur(prior_ss), "sgp_posterior_mean_var_f32: blur terms have no fp32 path: use the fp64 entry point");
+  F_CHECK_ARG(!spec_has_arccos(spec) && !spec_has_arccos(cross) && !spec_has_arccos(prior_ss), "sgp_posterior_mean_var_f32: arc-cosine terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_additive(spec) && !spec_has_additive(cross) && !spec_has_additive(prior_ss), "sgp_posterior_mean_var_f32: additive terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_deriv(spec) && !spec_has_deriv(cross) && !spec_has_deriv(prior_ss), "sgp_posterior_mean_var_f32: derivative terms have no fp32 path: use the fp64 entry point");
   F_CHECK_ARG(!spec_has_stencil(ctx, spec) && !spec_has_stencil(ctx, cross) && !spec_has_stencil(ctx, prior_ss), "sgp_posterior_mean_var_f32: stencil terms have no fp32 path: use the fp64 entry point");

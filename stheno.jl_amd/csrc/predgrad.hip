@@ -534,6 +534,7 @@ int enter(PostRef post, const PgArgs& a, const char* multi_refusal) {
     if (!sp) continue;
     REFUSE_UNLESS(!spec_has_gibbs(sp), a.who, "gradients through Gibbs terms are not supported");
     REFUSE_UNLESS(!spec_has_blur(sp), a.who, "gradients through blur terms are not supported");
+    REFUSE_UNLESS(!spec_has_arccos(sp), a.who, "gradients through arc-cosine terms are not supported");
     REFUSE_UNLESS(!spec_has_additive(sp), a.who, "gradients through additive terms are not supported");
     REFUSE_UNLESS(!spec_has_deriv(sp), a.who, "gradients through derivative terms are not supported");
     REFUSE_UNLESS(!spec_has_stencil(ctx, sp), a.who, "gradients through stencil terms are not supported");

@@ -89,6 +89,15 @@ def _refuse_blur(what, *specs):
                                   "logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, inputs and d_variance")
 
 
+def _refuse_arccos(what, *specs):
+    """`what` through arc-cosine terms (NNGPKernel / NTKKernel; include/sthenomi.h: SGP_NNGP, SGP_NTK) is not implemented (the
+    library refuses it too): logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, the input gradients and
+    d_transform"""
+    if any(sp.has_arccos for sp in specs):
+        raise NotImplementedError(f"{what} through arc-cosine covariance terms (NNGPKernel / NTKKernel) is not supported: "
+                                  "logpdf_and_gradient(fx, y, inputs=True) returns d_coef, d_inscale, inputs and d_transform")
+
+
 def _is_prior(f):
     return isinstance(f, (GPPP, SthenoAbstractGP))
 
@@ -286,6 +295,7 @@ def mean_and_var_and_gradient(fx):
     _refuse_gibbs("mean_and_var_and_gradient", cross, pss)
     _refuse_additive("mean_and_var_and_gradient", cross, pss)
     _refuse_blur("mean_and_var_and_gradient", cross, pss)
+    _refuse_arccos("mean_and_var_and_gradient", cross, pss)
     _refuse_patch_gradient(cross, pss)
     _refuse_product_gradient("mean_and_var_and_gradient", cross, pss)
     if (any(rs is not None for rs in cross.term_row_scale) or any(rs is not None for rs in pss.term_row_scale)
@@ -552,6 +562,7 @@ def logpdf_f32(fx, y):
     _refuse_gibbs("logpdf_f32: the fp32 path", spec)
     _refuse_additive("logpdf_f32: the fp32 path", spec)
     _refuse_blur("logpdf_f32: the fp32 path", spec)
+    _refuse_arccos("logpdf_f32: the fp32 path", spec)
     if spec.has_stencil:
         raise NotImplementedError("stencil terms have no fp32 path: call logpdf, which runs them in fp64")
     if spec.has_kprod:
@@ -639,6 +650,9 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
     caller's, and `x` is then the partial derivative with the variances held fixed.  Their d_inscale scales locations by g
     and variances by g^2.
 
+    A model with an NNGPKernel / NTKKernel (include/sthenomi.h: SGP_NNGP, SGP_NTK) is taken with scales=False.  A first-layer
+    bias is a constant coordinate of the points its terms read: `inputs` carries that row, `x` and d_transform do not.
+
     A model with a product of kernels (or a RationalQuadratic / Linear / Polynomial kernel) goes through
     sgp_logpdf_grad_param (include/sthenomi_kprod.h): every factor of a chain is a term record of its own, with `chain` (the
     index of its head's record), `factor` (its position), d_coef (the head's; 0 on the others), its own d_inscale, and
@@ -653,11 +667,13 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
             _refuse_gibbs("logpdf_and_gradient: scales=True", spec)
             _refuse_additive("logpdf_and_gradient: scales=True", spec)
             _refuse_blur("logpdf_and_gradient: scales=True", spec)
+            _refuse_arccos("logpdf_and_gradient: scales=True", spec)
         _refuse_product_gradient("logpdf_and_gradient: inputs=True / scales=True", spec)
     if spec.has_kprod:      # (sgp_logpdf_grad_param refuses the kind)
         _refuse_gibbs("logpdf_and_gradient of a model that also holds a product-path kernel", spec)
         _refuse_additive("logpdf_and_gradient of a model that also holds a product-path kernel", spec)
         _refuse_blur("logpdf_and_gradient of a model that also holds a product-path kernel", spec)
+        _refuse_arccos("logpdf_and_gradient of a model that also holds a product-path kernel", spec)
     kind, lp, bufs, args = _logpdf_grad_frame(fx, yv, spec)
     if spec.has_kprod:
         if _ctx().is_multi:
@@ -685,8 +701,8 @@ def logpdf_and_gradient(fx, y, inputs=False, scales=False):
         for r in rec["terms"]:
             if (int(r["kind"]) & _lib.KIND_MASK) == _lib.GIBBS:
                 r["d_lengthscale"] = (gx[r["row_input"]][-1, :], gx[r["col_input"]][-1, :])
-    if inputs and spec.has_additive:      # the per-dimension lengthscales of an additive model: the ARDTransform's vector
-        _attach_d_transform(rec["terms"], spec, gx)
+    if inputs and (spec.has_additive or spec.has_arccos):      # the per-dimension lengthscales of an additive or arc-cosine
+        _attach_d_transform(rec["terms"], spec, gx)            # model: the ARDTransform's vector
     if inputs and spec.has_blur:
         def d_variance(k):   # the view's variance rows back to the outermost node's variances (None: the side has no node)
             rows = spec.input_origin[k][3][-1][1]
@@ -729,6 +745,7 @@ def _refuse_param_family(what, *specs):
     _refuse_gibbs(what, *specs)
     _refuse_additive(what, *specs)
     _refuse_blur(what, *specs)
+    _refuse_arccos(what, *specs)
     _refuse_patch_gradient(*specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what}: a product of kernels (the gradients of include/sthenomi_kprod_grad.h) is not "
@@ -765,6 +782,7 @@ def _refuse_conv_family(what, *specs):
     _refuse_gibbs(what, *specs)
     _refuse_additive(what, *specs)
     _refuse_blur(what, *specs)
+    _refuse_arccos(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_stencil for sp in specs):
@@ -800,6 +818,7 @@ def _refuse_stencil_family(what, *specs):
     _refuse_gibbs(what, *specs)
     _refuse_additive(what, *specs)
     _refuse_blur(what, *specs)
+    _refuse_arccos(what, *specs)
     if getattr(_ctx(), "is_multi", False):
         raise NotImplementedError(f"{what} is not supported on a multi-GPU context")
     if any(sp.has_patch or sp.has_stencil for sp in specs) and any(sp.has_kprod for sp in specs):
@@ -1282,6 +1301,7 @@ def posterior_mean_and_var_f32(fx, y, xs):
     _refuse_gibbs("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
     _refuse_additive("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
     _refuse_blur("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
+    _refuse_arccos("posterior_mean_and_var_f32: the fp32 path", spec, cross, pss)
     kind, nbuf = _lib._noise_args(fx.noise, len(y))
     if kind == _lib.NOISE_DENSE or not spec.f32_supported() or not cross.f32_supported():
         raise NotImplementedError("beyond the fp32 kernels' limits (dense noise, input dimension > 16, too many terms)")
@@ -1565,6 +1585,7 @@ def elbo_and_gradient(vfe, fx, y=None, inputs=False, scales=False):
     _refuse_gibbs("elbo_and_gradient", *specs)
     _refuse_additive("elbo_and_gradient", *specs)
     _refuse_blur("elbo_and_gradient", *specs)
+    _refuse_arccos("elbo_and_gradient", *specs)
     _refuse_patch_gradient(*specs)
     _refuse_product_gradient("elbo_and_gradient", *specs)
     F = _elbo_grad_frame(specs, head)

@@ -485,7 +485,8 @@ def build_spec(f, x, f2=None, x2=None):
                             _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order)
                             continue
                         if len(factors) > 1 or (factors[0][0] > _lib.CONST and factors[0][0] != _lib.GIBBS
-                                                and factors[0][0] not in _lib.ADDITIVE_OF.values()):
+                                                and factors[0][0] not in _lib.ADDITIVE_OF.values()
+                                                and factors[0][0] not in (_lib.NNGP, _lib.NTK)):
                             # a product of kernels, or a kind that exists on the product path only: a chain of terms
                             # (include/sthenomi_kprod.h), each factor reading its own view of the points
                             if has_st or p.geom is not None or q.geom is not None:
@@ -529,6 +530,15 @@ def build_spec(f, x, f2=None, x2=None):
                             if has_st or p.geom is not None or q.geom is not None:
                                 raise NotImplementedError("an additive kernel (AdditiveKernel) below patch_convolve or a "
                                                           "stencil is not supported")
+                        if kind in (_lib.NNGP, _lib.NTK):
+                            if has_st or p.geom is not None or q.geom is not None:
+                                raise NotImplementedError("an arc-cosine kernel (NNGPKernel / NTKKernel) below patch_convolve "
+                                                          "or a stencil is not supported")
+                            dm = int(_kernels.apply_chain(s, p.X[:, :1]).shape[0])
+                            if dm > _lib.ARCCOS_MAX_DIM:
+                                raise NotImplementedError(f"an arc-cosine kernel (NNGPKernel / NTKKernel) on points of dimension "
+                                                          f"{dm} (the bias coordinate included) is beyond the library's limit of "
+                                                          f"{_lib.ARCCOS_MAX_DIM}")
                         if (p.geom is not None or q.geom is not None) and _kernels.chain_scale(s) is None:
                             raise NotImplementedError("patch_convolve: the kernel's input transform does not commute with "
                                                       "patch extraction (only a scalar ScaleTransform / with_lengthscale "
@@ -586,6 +596,8 @@ def _deriv_terms(p, q, kc, factors, table, symmetric, I, J, merged, order):
     transform (kernels.chain_direction), the components -- the Jacobian factors -- in its coefficient"""
     if any(f[0] in _lib.ADDITIVE_OF.values() for f in factors):
         raise NotImplementedError("derivative: an additive kernel (AdditiveKernel) below the node is not supported")
+    if any(f[0] in (_lib.NNGP, _lib.NTK) for f in factors):
+        raise NotImplementedError("derivative: an arc-cosine kernel (NNGPKernel / NTKKernel) below the node is not supported")
     if any(f[0] == _lib.GIBBS for f in factors):
         raise NotImplementedError("derivative: a GibbsKernel below the node is not supported (its lengthscale step is not linear)")
     if len(factors) > 1 or factors[0][0] not in _lib.DERIV_OF:
@@ -627,6 +639,8 @@ def _blur_terms(p, q, kc, factors, table, symmetric, I, J, merged, order, mat):
     if len(factors) > 1:
         raise NotImplementedError("blur: a product of kernels below the node is not supported (no closed form is built)")
     (kind, _, s), = factors
+    if kind in (_lib.NNGP, _lib.NTK):
+        raise NotImplementedError("blur: an arc-cosine kernel (NNGPKernel / NTKKernel) below the node is not supported")
     if kind != _lib.SE:
         raise NotImplementedError("blur: the kernel below the node must be the squared-exponential (SEKernel), or a sum or "
                                   "scaling of such (Matern and every other kernel have no closed form here)")

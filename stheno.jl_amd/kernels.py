@@ -7,7 +7,8 @@ order -- ("scale", s) for ScaleTransform(s) / with_lengthscale, ("periodic", f) 
 PeriodicTransform(f) (/root/reference/examples/extended_mauna_loa/script.jl:129), ("sincos", r) for the
 embedding behind PeriodicKernel(r), ("linear", A) / ("ard", v) / ("select", idx) for KernelFunctions' LinearTransform,
 ARDTransform and SelectTransform, ("lengthscale", fn) for the row l(X) that GibbsKernel appends below the location rows
-(always the last step) -- evaluated on the host (O(N D)) when the spec is built.  Matrices, vectors and index
+(always the last step), ("bias", s) for the constant row s that NNGPKernel / NTKKernel append (likewise) -- evaluated on
+the host (O(N D)) when the spec is built.  Matrices, vectors and index
 lists are stored as tuples of floats / ints: equal maps give equal (hashable) chains, so equal views are uploaded once
 (a lengthscale step compares by its callable).
 
@@ -55,6 +56,8 @@ def apply_chain(chain, X):
             X = X[list(v), :]
         elif kind == "lengthscale":
             X = np.vstack([X, _lengthscale_row(v, X)])     # the Gibbs kind's points: the location, then l(x)
+        elif kind == "bias":
+            X = np.vstack([X, np.full((1, X.shape[1]), float(v))])     # the arc-cosine kinds' first-layer bias: a constant row
         elif kind == "blur":
             # the blur kind's points: the location, then the variances of the footprint (zeros for a view without a node)
             S = np.zeros(X.shape) if v.S is None else v.S
@@ -162,6 +165,8 @@ def chain_vjp(chain, X, gout, transforms=None):
             g = gin
         elif kind == "lengthscale":
             found.append(g[-1, :].copy())
+            g = g[:-1, :]
+        elif kind == "bias":
             g = g[:-1, :]
         elif kind == "blur":
             found.append(g[g.shape[0] // 2:, :].copy())
@@ -373,6 +378,9 @@ class KernelProduct(Kernel):
         if len(self.kernels) > 1 and any(f[0] in _lib.ADDITIVE_OF.values() for _, fs in out for f in fs):
             raise NotImplementedError("a product of kernels with an additive factor (AdditiveKernel) is not supported (the "
                                       "additive kinds are no factors of the library's product chains)")
+        if len(self.kernels) > 1 and any(f[0] in (_lib.NNGP, _lib.NTK) for _, fs in out for f in fs):
+            raise NotImplementedError("a product of kernels with an arc-cosine factor (NNGPKernel / NTKKernel) is not supported "
+                                      "(the arc-cosine kinds are no factors of the library's product chains)")
         if len(self.kernels) > 1 and any(f[0] == _lib.GIBBS for _, fs in out for f in fs):
             raise NotImplementedError("a product of kernels with a GibbsKernel factor is not supported (the Gibbs kind is "
                                       "no factor of the library's product chains)")
@@ -396,6 +404,39 @@ class GibbsKernel(Kernel):
 
     def leaf_terms(self):
         return [(_lib.GIBBS, 1.0, float(self.power), (("lengthscale", self.lengthscale),))]
+
+
+class _ArcCosine(Kernel):
+    """depth hidden ReLU layers, weight variance 2 (norms pass through the layers), first-layer bias variance `bias` >= 0: the
+    kernel sees the points with one constant coordinate sqrt(bias) appended (a ("bias", sqrt(bias)) chain step, always the
+    last), so the user dimension is <= 15 with a bias and <= 16 without.  Without a bias a 1-D model is degenerate: the
+    cosine of the angle between two numbers is +-1"""
+    kind = None
+
+    def __init__(self, depth, bias=0.0):
+        name = type(self).__name__
+        if (isinstance(depth, bool) or not np.isreal(depth) or not np.isfinite(depth) or depth != int(depth)
+                or not 1 <= int(depth) <= _lib.ARCCOS_MAX_DEPTH):
+            raise ValueError(f"{name} (arc-cosine): depth must be an integer in 1 .. {_lib.ARCCOS_MAX_DEPTH}")
+        if not (float(bias) >= 0.0 and np.isfinite(float(bias))):
+            raise ValueError(f"{name} (arc-cosine): bias must be a finite variance >= 0")
+        self.depth, self.bias = int(depth), float(bias)
+
+    def leaf_terms(self):
+        return [(self.kind, 1.0, float(self.depth), (("bias", float(np.sqrt(self.bias))),) if self.bias > 0.0 else ())]
+
+
+class NNGPKernel(_ArcCosine):
+    """The covariance of a depth-`depth` fully connected ReLU network in the infinite-width limit (the arc-cosine kernel of Cho
+    and Saul iterated; Lee et al.): K = |x| |y| c_L, c_{l+1} = kappa_1(c_l) from the cosine c_0 of the angle between the points
+    (include/sthenomi.h: SGP_NNGP).  One layer recursion per entry on the device; a sum over depths shares it."""
+    kind = _lib.NNGP
+
+
+class NTKKernel(_ArcCosine):
+    """The neural tangent kernel of the same network (Jacot et al.): K = |x| |y| t_L, t_{l+1} = c_{l+1} + t_l kappa_0(c_l)
+    (include/sthenomi.h: SGP_NTK); k(x, x) = (depth + 1) |x|^2"""
+    kind = _lib.NTK
 
 
 class AdditiveKernel(Kernel):

@@ -44,6 +44,10 @@ ADDITIVE_MAX_DIM, ADDITIVE_MAX_ORDER = 16, 8
 # them the D variances of the Gaussian footprint at the point; param is ignored
 BLUR_SE = 56
 BLUR_MAX_DIM = 16
+# the arc-cosine kinds (include/sthenomi.h: SGP_NNGP, SGP_NTK; arccos.hip): points of dimension <= ARCCOS_MAX_DIM, param = the
+# number L of hidden ReLU layers, an integer in 1 .. ARCCOS_MAX_DEPTH
+NNGP, NTK = 64, 65
+ARCCOS_MAX_DIM, ARCCOS_MAX_DEPTH = 16, 16
 KIND_TIMES_PREV = 0x100            # SGP_KIND_TIMES_PREV: the term multiplies the chain begun before it
 KIND_MASK = 0xff
 KPROD_MAX_FACTORS, KPROD_MAX_DIM = 8, 16      # include/sthenomi_kprod.h: the limits of a chain
@@ -595,9 +599,10 @@ class Spec:
         self.has_gibbs = any(int(t[0]) == GIBBS for t in terms)                 # Gibbs terms: likewise
         self.has_additive = any(int(t[0]) in ADDITIVE_OF.values() for t in terms)   # additive terms: likewise
         self.has_blur = any(int(t[0]) == BLUR_SE for t in terms)                # blur terms: likewise
+        self.has_arccos = any(int(t[0]) in (NNGP, NTK) for t in terms)          # arc-cosine terms: likewise
         self.has_kprod = any((int(t[0]) & KIND_TIMES_PREV) or
                              ((int(t[0]) & KIND_MASK) > CONST and int(t[0]) not in DERIV_OF.values() and int(t[0]) != GIBBS
-                              and int(t[0]) not in ADDITIVE_OF.values() and int(t[0]) != BLUR_SE)
+                              and int(t[0]) not in ADDITIVE_OF.values() and int(t[0]) not in (BLUR_SE, NNGP, NTK))
                              for t in terms)
         self._bound = None
         self.n_terms = len(terms)
@@ -675,7 +680,7 @@ class Spec:
     def f32_supported(self):
         """The fp32 device kernels (csrc/f32.hip: assemble_f32) take input dimension <= 16 and, per block pair,
         (number of terms) x (dimension rounded up to a power of two) <= 64; anything else runs on the fp64 path."""
-        if self.has_patch or self.has_stencil or self.has_kprod or self.has_deriv or self.has_gibbs or self.has_additive or self.has_blur:
+        if self.has_patch or self.has_stencil or self.has_kprod or self.has_deriv or self.has_gibbs or self.has_additive or self.has_blur or self.has_arccos:
             return False                 # patch / stencil / product terms: fp64 only (a Float32 model runs there and is rounded back)
         tp = self._term_ptr
         for p in range(len(tp) - 1):

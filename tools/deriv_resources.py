@@ -42,7 +42,7 @@ def listing(source):
     return out
 
 
-SOURCES = ("kernelmatrix.hip", "grad.hip", "conv.hip", "stencil.hip", "kprod.hip", "predgrad.hip", "deriv.hip", "gibbs.hip", "additive.hip", "blur.hip")
+SOURCES = ("kernelmatrix.hip", "grad.hip", "conv.hip", "stencil.hip", "kprod.hip", "predgrad.hip", "deriv.hip", "gibbs.hip", "additive.hip", "blur.hip", "arccos.hip")
 
 
 def main():
